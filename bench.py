@@ -14,6 +14,9 @@ N>1   : weak scaling (default): RMAT scale 24+log2(N) (RMAT-27 at 8 GPUs), every
         `--scaling strong` shards the scale-24 graph instead.  Extra keys: PageRank on uniform-25 cut N ways (configs[3]) and
         Shiloach-Vishkin on the symmetrised RMAT scale 24+log2(N) (configs[4] at 8 GPUs: RMAT-27), with rank 0's kernel rooflines.
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run as a child process).
+Without --full a run builds the graph, warms up, times the steps and prints the headline keys only (metric, value, unit, ms_per_step, ...,
+config); the roofline, the checks of the timed levels, the CPU baseline and every extra key above need --full.
+--dump-outputs DIR writes what the timed path computed in its last step (dump_bfs_outputs) before anything else runs.
 """
 import argparse
 import json
@@ -98,6 +101,24 @@ def measured_copy_bandwidth(device, gib=2, reps=10):
     torch.cuda.empty_cache()
     return {"GBps": round(2.0 * n * 4 / (ms * 1e-3) / 1e9, 1), "bytes_read_plus_written": 2 * n * 4, "ms": round(ms, 4),
             "note": "torch device-to-device copy of %d GiB, %d repetitions, HIP events; bytes = read + written" % (gib, reps)}
+
+
+DUMP_SAMPLE = 1 << 22          # vertices of the levels array --dump-outputs keeps: 16 MiB as float32 (RMAT-24 has 2^24 of them)
+
+
+def dump_bfs_outputs(dirname, levels, stats, seed):
+    """--dump-outputs: what the timed path handed back for its last step, as float .npy files that two builds can be compared by.
+    bfs_levels.npy: the levels (int32 on the device, exact in float32) at a fixed, seeded, ascending sample of DUMP_SAMPLE vertex ids, all of
+    them when there are no more; bfs_levels_per_step.npy / bfs_reached_per_step.npy: level count and vertices reached of every timed step."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    lv = levels.cpu().numpy()
+    if lv.size > DUMP_SAMPLE:
+        lv = lv[np.sort(np.random.default_rng(seed).choice(lv.size, DUMP_SAMPLE, replace=False))]
+    np.save(os.path.join(dirname, "bfs_levels.npy"), lv.astype(np.float32))
+    if stats is not None:
+        np.save(os.path.join(dirname, "bfs_levels_per_step.npy"), np.array([s["levels"] for s in stats], dtype=np.float64))
+        np.save(os.path.join(dirname, "bfs_reached_per_step.npy"), np.array([s["discovered"] for s in stats], dtype=np.float64))
 
 
 def timed_kernels(ctx, names):
@@ -881,6 +902,11 @@ def main():
     ap.add_argument("--sssp-delta", type=float, default=10.0)    # 8 .. 12 measure the same (13.0 ms), 16: 13.9 ms, 4: 14.0 ms
     ap.add_argument("--renumber", default="total", choices=["none", "out", "in", "total"],
                     help="VectCSR-style degree renumbering of the stored graph (vect_csr/import.hpp:61-99)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: kernel rooflines, checks of the timed levels, the CPU baseline, the SSSP / HITS / "
+                         "SCC / PageRank / CC / RMAT-27 / operator-API legs, the measured copy rate (the --no-* options thin this out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` without a launcher: start one rank per GPU under torch.distributed.run as a CHILD process (nothing has
@@ -898,7 +924,7 @@ def main():
     # the CPU baseline's OpenMP runtime reads these when it is first loaded (scripts/helpers.py:147-153)
     os.environ.setdefault("OMP_PROC_BIND", "close")
     os.environ.setdefault("OMP_PLACES", "cores")
-    if not args.no_cpu_baseline:                        # the CPUs this process may use, counted before any OpenMP runtime binds the main thread to one place
+    if args.full and not args.no_cpu_baseline:          # the CPUs this process may use, counted before any OpenMP runtime binds the main thread to one place
         from oracle import oracle as O_early
         os.environ.setdefault("VGL_HOST_CPUS", str(O_early.host_cpus()))
 
@@ -983,16 +1009,18 @@ def main():
         # Two HIP event records per bracketed launch cost ~4-5 us of stream time: bracketing all eleven timed launches of a traversal
         # takes a tenth of it.  The warm-up traversals are bracketed completely and decide which kernel dominates; the TIMED region then
         # brackets only that kernel (the roofline's duration is measured live in it); the per-kernel breakdown of the extras comes from
-        # a repeat of the same traversals after the timed region.
+        # a repeat of the same traversals after the timed region.  Without --full nothing is bracketed.
         bfs_kernels = ("bfs_bottom_up", "bfs_bottom_up_heavy", "bfs_top_down", "bfs_small_levels", "bfs_bitmap_expand", "gnf")
-        ctx.timing(True)
+        if args.full:
+            ctx.timing(True)
         for s in sources[:max(args.warmup, 1)]:
             api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
-        warm = {name: ctx.timing_get(name)[1] for name in ("bfs_bottom_up", "bfs_top_down", "gnf")}
-        dom = max(warm, key=warm.get)
-        # ... and of its launches every 4th (a traversal has ~3 of them: the stride walks through the levels evenly): 5 us of event records per
-        # bracketed launch were 5 % of a traversal
-        ctx.timing(True, only=dom, stride=4)
+        if args.full:
+            warm = {name: ctx.timing_get(name)[1] for name in ("bfs_bottom_up", "bfs_top_down", "gnf")}
+            dom = max(warm, key=warm.get)
+            # ... and of its launches every 4th (a traversal has ~3 of them: the stride walks through the levels evenly): 5 us of event records
+            # per bracketed launch were 5 % of a traversal
+            ctx.timing(True, only=dom, stride=4)
         stats = []
         lv_do = ctx.empty(g.V, torch.int32)               # one levels array for all rounds, as apps/bfs/bfs.cpp:31,36-40 reuses its VerticesArray
         barrier()
@@ -1002,177 +1030,180 @@ def main():
         _, stats = api.bfs_batch(g, sources[args.warmup:], api.BFS_DIRECTION_OPT, levels=lv_do)
         barrier()
         dt = time.perf_counter() - t0
-        # ---- roofline of the dominant kernel, from the HIP events recorded inside the timed region ----
-        dom_n, dom_ms = ctx.timing_get(dom)
-        ctx.timing(True)
-        for s in sources[args.warmup:]:
-            api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
-        kern = {}
-        for name in bfs_kernels:
-            n, ms = ctx.timing_get(name)
-            kern[name] = {"launches": n, "total_ms": round(ms, 4)}
-        ctx.timing(False)
-        # ---- check what was timed (apps/bfs/bfs.cpp:41-46, -check): the levels of the LAST timed traversal must equal the reference
-        #      algorithm's (pure top-down) levels of the same source; a mismatch fails the run ----
-        check_source = sources[-1]                                    # lv_do: the levels the last TIMED traversal left behind
-        lv_td = api.bfs(g, check_source, api.BFS_TOP_DOWN, raw=True)[0]
-        bad = api.count_not_equal(ctx, lv_do, lv_td)
-        if bad:
-            sys.exit(f"bench.py: direction-optimising BFS levels differ from the top-down levels at {bad} vertices (source {check_source})")
-        extra["verified"] = {"bfs_do_equals_top_down": True, "source": check_source}
-        # ... and EVERY timed traversal: its level count and the number of vertices it reached (host values of its stats record, kept
-        # during the timed region at no cost) equal those of the reference algorithm from the same source
-        for s_i, st_i in zip(sources[args.warmup:], stats):
-            td_i = api.bfs(g, s_i, api.BFS_TOP_DOWN, raw=True)[1]
-            if td_i["levels"] != st_i["levels"] or td_i["discovered"] != st_i["discovered"]:
-                sys.exit(f"bench.py: timed traversal from source {s_i}: {st_i['levels']} levels / {st_i['discovered']} reached, top-down "
-                         f"{td_i['levels']} / {td_i['discovered']}")
-        extra["verified"]["every_timed_traversal_levels_and_reached_equal_top_down"] = len(stats)
-        bu_edges = sum(s["bu_edges"] for s in stats)
-        bu_found = sum(s["bu_found"] for s in stats)
-        bu_steps = sum(s["bu_steps"] for s in stats)
-        td_edges = sum(s["td_edges"] for s in stats)
-        td_front = sum(s["td_frontier"] for s in stats)
-        td_steps = sum(s["td_steps"] for s in stats)
-        levels = sum(s["levels"] for s in stats)
-        # algorithmic bytes per kernel: 8 B per examined adjacency entry (4 B id + 4 B status probe),
-        # 20 B per top-down frontier vertex (id + row offsets), 4 B per discovered vertex, V/8 per bottom-up bitmap scan,
-        # 4 B per vertex per GNF pass
-        bytes_k = {
-            "bfs_bottom_up": 8 * bu_edges + 4 * bu_found + bu_steps * (V // 8),
-            "bfs_top_down": 8 * td_edges + 20 * td_front,
-            "gnf": 4 * V * kern["gnf"]["launches"],
-        }
-        if dom_n > 0 and dom_ms > 0:
-            all_launches = max(kern[dom]["launches"], 1)     # (the timed region brackets a sample of them: every 4th)
-            per_launch_bytes = bytes_k[dom] / all_launches
-            per_launch_ms = dom_ms / dom_n
-            achieved = per_launch_bytes / (per_launch_ms * 1e-3) / 1e9
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(dom)[0], "traffic_raw": pmc_traffic(dom)[2], "traffic_source": pmc_traffic(dom)[1],
-                        "bytes_per_launch": int(per_launch_bytes), "ms_per_launch": round(per_launch_ms, 5),
-                        "launches": all_launches, "launches_timed_in_the_timed_region": dom_n,
-                        "timing_note": "HIP events around every 4th launch of this kernel inside the timed region (two event records cost ~5 us of stream time)"}
-        total_alg = sum(s["algorithmic_bytes"] for s in stats)
-        kernel_sum_ms = sum(v["total_ms"] for v in kern.values())
-        # the reference's own accounting (settings.h:140-155, INT_ELEMENTS_PER_EDGE = 4 for BFS, apps/bfs/bfs.cpp:3): 16 B per edge
-        # of the GRAPH per traversal, whatever was actually touched -- reported for comparability only
-        extra["vgl_accounting_GBps"] = round(16.0 * E * args.steps / dt / 1e9, 1)
-        extra["bfs"] = {"kernels": kern, "levels_per_bfs": levels / len(stats), "td_steps": td_steps, "bu_steps": bu_steps,
-                        "edges_examined_per_bfs": (bu_edges + td_edges) / len(stats),
-                        "kernels_note": "per-kernel HIP-event times of a repeat of the timed traversals with every kernel bracketed (the timed region brackets the roofline kernel only)",
-                        "timed_kernels_over_wall_time": round(kernel_sum_ms * 1e-3 / dt, 4),
-                        "whole_bfs_algorithmic_GBps": round(total_alg / dt / 1e9, 2),
-                        "whole_bfs_frac_of_hbm_peak": round(total_alg / dt / 1e9 / HBM_PEAK_GBS, 5)}
-        # reference algorithm (pure top-down, bfs.hpp:6-51) for comparison
-        t1 = time.perf_counter()
-        td_stats = [api.bfs(g, s, api.BFS_TOP_DOWN, raw=True)[1] for s in sources[args.warmup:args.warmup + 4]]
-        torch.cuda.synchronize()
-        dt_td = (time.perf_counter() - t1) / len(td_stats)
-        extra["bfs_top_down_reference_algorithm"] = {
-            "teps": round(E / dt_td, 1), "ms": round(dt_td * 1e3, 3),
-            "algorithmic_GBps": round(sum(s["algorithmic_bytes"] for s in td_stats) / len(td_stats) / dt_td / 1e9, 2)}
-        # ... and with the graph prepared for blocked top-down levels (vgl_hip_bfs_prepare_blocked: the levels that hold a tenth of the
-        # edges or more run as a blocked pass, one bit per edge through LDS windows).  The direction-optimising traversals above were
-        # timed before the preparation; they do not use it (their large levels are bottom-up).
-        if E >= (1 << 32) - 4096:
-            extra["bfs_top_down_reference_algorithm"]["blocked_levels"] = "not built: a blocked plan holds fewer than 2^32 edges (split the graph in shards)"
-        else:
-            torch.cuda.synchronize()
+        if args.dump_outputs:
+            dump_bfs_outputs(args.dump_outputs, lv_do, stats, seed)
+        if args.full:
+            # ---- roofline of the dominant kernel, from the HIP events recorded inside the timed region ----
+            dom_n, dom_ms = ctx.timing_get(dom)
             ctx.timing(True)
-            t1 = time.perf_counter()
-            g.prepare_blocked_bfs()
-            torch.cuda.synchronize()
-            t_prep_wall = time.perf_counter() - t1
-            t_prep = ctx.timing_get("blk_plan_build")[1] * 1e-3
+            for s in sources[args.warmup:]:
+                api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
+            kern = {}
+            for name in bfs_kernels:
+                n, ms = ctx.timing_get(name)
+                kern[name] = {"launches": n, "total_ms": round(ms, 4)}
             ctx.timing(False)
-            td_src = sources[args.warmup:args.warmup + 4]
-            lv_b, _ = api.bfs(g, td_src[0], api.BFS_TOP_DOWN, raw=True)
-            if not torch.equal(lv_b, api.bfs(g, td_src[0], api.BFS_DIRECTION_OPT, raw=True)[0]):
-                sys.exit("bench.py: blocked top-down levels differ from the direction-optimising traversal")
-            ctx.timing(True)
-            torch.cuda.synchronize()
+            # ---- check what was timed (apps/bfs/bfs.cpp:41-46, -check): the levels of the LAST timed traversal must equal the reference
+            #      algorithm's (pure top-down) levels of the same source; a mismatch fails the run ----
+            check_source = sources[-1]                                    # lv_do: the levels the last TIMED traversal left behind
+            lv_td = api.bfs(g, check_source, api.BFS_TOP_DOWN, raw=True)[0]
+            bad = api.count_not_equal(ctx, lv_do, lv_td)
+            if bad:
+                sys.exit(f"bench.py: direction-optimising BFS levels differ from the top-down levels at {bad} vertices (source {check_source})")
+            extra["verified"] = {"bfs_do_equals_top_down": True, "source": check_source}
+            # ... and EVERY timed traversal: its level count and the number of vertices it reached (host values of its stats record, kept
+            # during the timed region at no cost) equal those of the reference algorithm from the same source
+            for s_i, st_i in zip(sources[args.warmup:], stats):
+                td_i = api.bfs(g, s_i, api.BFS_TOP_DOWN, raw=True)[1]
+                if td_i["levels"] != st_i["levels"] or td_i["discovered"] != st_i["discovered"]:
+                    sys.exit(f"bench.py: timed traversal from source {s_i}: {st_i['levels']} levels / {st_i['discovered']} reached, top-down "
+                             f"{td_i['levels']} / {td_i['discovered']}")
+            extra["verified"]["every_timed_traversal_levels_and_reached_equal_top_down"] = len(stats)
+            bu_edges = sum(s["bu_edges"] for s in stats)
+            bu_found = sum(s["bu_found"] for s in stats)
+            bu_steps = sum(s["bu_steps"] for s in stats)
+            td_edges = sum(s["td_edges"] for s in stats)
+            td_front = sum(s["td_frontier"] for s in stats)
+            td_steps = sum(s["td_steps"] for s in stats)
+            levels = sum(s["levels"] for s in stats)
+            # algorithmic bytes per kernel: 8 B per examined adjacency entry (4 B id + 4 B status probe),
+            # 20 B per top-down frontier vertex (id + row offsets), 4 B per discovered vertex, V/8 per bottom-up bitmap scan,
+            # 4 B per vertex per GNF pass
+            bytes_k = {
+                "bfs_bottom_up": 8 * bu_edges + 4 * bu_found + bu_steps * (V // 8),
+                "bfs_top_down": 8 * td_edges + 20 * td_front,
+                "gnf": 4 * V * kern["gnf"]["launches"],
+            }
+            if dom_n > 0 and dom_ms > 0:
+                all_launches = max(kern[dom]["launches"], 1)     # (the timed region brackets a sample of them: every 4th)
+                per_launch_bytes = bytes_k[dom] / all_launches
+                per_launch_ms = dom_ms / dom_n
+                achieved = per_launch_bytes / (per_launch_ms * 1e-3) / 1e9
+                roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": pmc_traffic(dom)[0], "traffic_raw": pmc_traffic(dom)[2], "traffic_source": pmc_traffic(dom)[1],
+                            "bytes_per_launch": int(per_launch_bytes), "ms_per_launch": round(per_launch_ms, 5),
+                            "launches": all_launches, "launches_timed_in_the_timed_region": dom_n,
+                            "timing_note": "HIP events around every 4th launch of this kernel inside the timed region (two event records cost ~5 us of stream time)"}
+            total_alg = sum(s["algorithmic_bytes"] for s in stats)
+            kernel_sum_ms = sum(v["total_ms"] for v in kern.values())
+            # the reference's own accounting (settings.h:140-155, INT_ELEMENTS_PER_EDGE = 4 for BFS, apps/bfs/bfs.cpp:3): 16 B per edge
+            # of the GRAPH per traversal, whatever was actually touched -- reported for comparability only
+            extra["vgl_accounting_GBps"] = round(16.0 * E * args.steps / dt / 1e9, 1)
+            extra["bfs"] = {"kernels": kern, "levels_per_bfs": levels / len(stats), "td_steps": td_steps, "bu_steps": bu_steps,
+                            "edges_examined_per_bfs": (bu_edges + td_edges) / len(stats),
+                            "kernels_note": "per-kernel HIP-event times of a repeat of the timed traversals with every kernel bracketed (the timed region brackets the roofline kernel only)",
+                            "timed_kernels_over_wall_time": round(kernel_sum_ms * 1e-3 / dt, 4),
+                            "whole_bfs_algorithmic_GBps": round(total_alg / dt / 1e9, 2),
+                            "whole_bfs_frac_of_hbm_peak": round(total_alg / dt / 1e9 / HBM_PEAK_GBS, 5)}
+            # reference algorithm (pure top-down, bfs.hpp:6-51) for comparison
             t1 = time.perf_counter()
-            tdb_stats = [api.bfs(g, s, api.BFS_TOP_DOWN, raw=True)[1] for s in td_src]
+            td_stats = [api.bfs(g, s, api.BFS_TOP_DOWN, raw=True)[1] for s in sources[args.warmup:args.warmup + 4]]
             torch.cuda.synchronize()
-            dt_tdb = (time.perf_counter() - t1) / len(tdb_stats)
-            kb = timed_kernels(ctx, ("bfs_blk_gather", "bfs_blk_accumulate"))
-            ctx.timing(False)
-            one = {"teps": round(E / dt_tdb, 1), "ms": round(dt_tdb * 1e3, 3), "prepare_ms_once_per_graph_NOT_in_ms": round(t_prep * 1e3, 1),
-                   "prepare_call_wall_ms": round(t_prep_wall * 1e3, 1), "kernels": kb}
-            if kb["bfs_blk_gather"]["launches"]:
-                pass_ms = kb["bfs_blk_gather"]["ms_per_launch"] + kb["bfs_blk_accumulate"]["ms_per_launch"]
-                # streamed by one blocked level: 2 B (row index) + 2 B (destination index) per edge + 16 B per 64-edge chunk
-                streamed = 4.25 * E
-                one["blocked_level"] = {"ms": round(pass_ms, 4), "levels_per_bfs": kb["bfs_blk_gather"]["launches"] / len(tdb_stats),
-                                        "streamed_GBps": round(streamed / (pass_ms * 1e-3) / 1e9, 1),
-                                        "streamed_frac_of_hbm_peak": frac(streamed / (pass_ms * 1e-3) / 1e9)}
-            extra["bfs_top_down_reference_algorithm"]["blocked_levels"] = one
+            dt_td = (time.perf_counter() - t1) / len(td_stats)
+            extra["bfs_top_down_reference_algorithm"] = {
+                "teps": round(E / dt_td, 1), "ms": round(dt_td * 1e3, 3),
+                "algorithmic_GBps": round(sum(s["algorithmic_bytes"] for s in td_stats) / len(td_stats) / dt_td / 1e9, 2)}
+            # ... and with the graph prepared for blocked top-down levels (vgl_hip_bfs_prepare_blocked: the levels that hold a tenth of the
+            # edges or more run as a blocked pass, one bit per edge through LDS windows).  The direction-optimising traversals above were
+            # timed before the preparation; they do not use it (their large levels are bottom-up).
+            if E >= (1 << 32) - 4096:
+                extra["bfs_top_down_reference_algorithm"]["blocked_levels"] = "not built: a blocked plan holds fewer than 2^32 edges (split the graph in shards)"
+            else:
+                torch.cuda.synchronize()
+                ctx.timing(True)
+                t1 = time.perf_counter()
+                g.prepare_blocked_bfs()
+                torch.cuda.synchronize()
+                t_prep_wall = time.perf_counter() - t1
+                t_prep = ctx.timing_get("blk_plan_build")[1] * 1e-3
+                ctx.timing(False)
+                td_src = sources[args.warmup:args.warmup + 4]
+                lv_b, _ = api.bfs(g, td_src[0], api.BFS_TOP_DOWN, raw=True)
+                if not torch.equal(lv_b, api.bfs(g, td_src[0], api.BFS_DIRECTION_OPT, raw=True)[0]):
+                    sys.exit("bench.py: blocked top-down levels differ from the direction-optimising traversal")
+                ctx.timing(True)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                tdb_stats = [api.bfs(g, s, api.BFS_TOP_DOWN, raw=True)[1] for s in td_src]
+                torch.cuda.synchronize()
+                dt_tdb = (time.perf_counter() - t1) / len(tdb_stats)
+                kb = timed_kernels(ctx, ("bfs_blk_gather", "bfs_blk_accumulate"))
+                ctx.timing(False)
+                one = {"teps": round(E / dt_tdb, 1), "ms": round(dt_tdb * 1e3, 3), "prepare_ms_once_per_graph_NOT_in_ms": round(t_prep * 1e3, 1),
+                       "prepare_call_wall_ms": round(t_prep_wall * 1e3, 1), "kernels": kb}
+                if kb["bfs_blk_gather"]["launches"]:
+                    pass_ms = kb["bfs_blk_gather"]["ms_per_launch"] + kb["bfs_blk_accumulate"]["ms_per_launch"]
+                    # streamed by one blocked level: 2 B (row index) + 2 B (destination index) per edge + 16 B per 64-edge chunk
+                    streamed = 4.25 * E
+                    one["blocked_level"] = {"ms": round(pass_ms, 4), "levels_per_bfs": kb["bfs_blk_gather"]["launches"] / len(tdb_stats),
+                                            "streamed_GBps": round(streamed / (pass_ms * 1e-3) / 1e9, 1),
+                                            "streamed_frac_of_hbm_peak": frac(streamed / (pass_ms * 1e-3) / 1e9)}
+                extra["bfs_top_down_reference_algorithm"]["blocked_levels"] = one
 
-        # ---- CPU baseline: the oracle's OpenMP port of the reference top-down BFS, same graph, the CPUs the box grants ----
-        cpu = None
-        if not args.no_cpu_baseline:
-            from oracle import oracle as O
-            threads = O.set_threads()                                    # affinity / cgroup quota, not every core the box shows
-            cpu = (O, threads)
-            rp = g.out_rowptr.cpu().numpy()
-            adj = g.out_adj.cpu().numpy()
-            ref_lv, _ = O.bfs_top_down(rp, adj, check_source, parallel=True)           # warm-up / page-in, and the checker of the timed path
-            if not (lv_do.cpu().numpy() == ref_lv).all():
-                sys.exit(f"bench.py: BFS levels differ from the CPU oracle's (source {check_source})")
-            extra["verified"]["bfs_equals_cpu_oracle"] = True
-            tc = time.perf_counter()
-            n_cpu = 0
-            for s in sources[args.warmup:args.warmup + args.cpu_sources]:
-                O.bfs_top_down(rp, adj, s, parallel=True)
-                n_cpu += 1
-                if time.perf_counter() - tc > 20:
-                    break
-            dtc = time.perf_counter() - tc
-            cpu_baseline = {"value": round(n_cpu * E / dtc, 1), "unit": "edges/s", "cores": threads, "kind": "port",
-                            "sample": f"{n_cpu} top-down BFS traversals after 1 warm-up (oracle/vgl_oracle.c, OpenMP, OMP_PROC_BIND="
-                                      f"{os.environ.get('OMP_PROC_BIND')} OMP_PLACES={os.environ.get('OMP_PLACES')}) of the same RMAT-{scale} graph",
-                            "host": O.host_description()}
-            del rp, adj
-            anchor = reference_anchor(api, ctx, O, threads, seed)
-            if anchor:
-                cpu_baseline["reference_rmat18_anchor"] = anchor
-        del lv_do, lv_td
+            # ---- CPU baseline: the oracle's OpenMP port of the reference top-down BFS, same graph, the CPUs this process is granted ----
+            cpu = None
+            if not args.no_cpu_baseline:
+                from oracle import oracle as O
+                threads = O.set_threads()                                    # affinity / cgroup quota, not every core the host shows
+                cpu = (O, threads)
+                rp = g.out_rowptr.cpu().numpy()
+                adj = g.out_adj.cpu().numpy()
+                ref_lv, _ = O.bfs_top_down(rp, adj, check_source, parallel=True)           # warm-up / page-in, and the checker of the timed path
+                if not (lv_do.cpu().numpy() == ref_lv).all():
+                    sys.exit(f"bench.py: BFS levels differ from the CPU oracle's (source {check_source})")
+                extra["verified"]["bfs_equals_cpu_oracle"] = True
+                tc = time.perf_counter()
+                n_cpu = 0
+                for s in sources[args.warmup:args.warmup + args.cpu_sources]:
+                    O.bfs_top_down(rp, adj, s, parallel=True)
+                    n_cpu += 1
+                    if time.perf_counter() - tc > 20:
+                        break
+                dtc = time.perf_counter() - tc
+                cpu_baseline = {"value": round(n_cpu * E / dtc, 1), "unit": "edges/s", "cores": threads, "kind": "port",
+                                "sample": f"{n_cpu} top-down BFS traversals after 1 warm-up (oracle/vgl_oracle.c, OpenMP, OMP_PROC_BIND="
+                                          f"{os.environ.get('OMP_PROC_BIND')} OMP_PLACES={os.environ.get('OMP_PLACES')}) of the same RMAT-{scale} graph",
+                                "host": O.host_description()}
+                del rp, adj
+                anchor = reference_anchor(api, ctx, O, threads, seed)
+                if anchor:
+                    cpu_baseline["reference_rmat18_anchor"] = anchor
+            del lv_do, lv_td
 
-        # ---- SSSP (BASELINE configs[2]) ----
-        if not args.no_sssp:
-            w = ctx.gather_u32(g.perm, ctx.gen_weights(E, seed))
-            leg_sssp(api, ctx, g, w, E, V, sources, args, extra, cpu)
-            del w
+            # ---- SSSP (BASELINE configs[2]) ----
+            if not args.no_sssp:
+                w = ctx.gather_u32(g.perm, ctx.gen_weights(E, seed))
+                leg_sssp(api, ctx, g, w, E, V, sources, args, extra, cpu)
+                del w
 
-        # ---- HITS (f64) and SCC on the same graph (f1 widening) ----
-        if not args.no_pr_cc:
-            api.hits(g, 1, raw=True)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            api.hits(g, 5, raw=True)
-            torch.cuda.synchronize()
-            dth = (time.perf_counter() - t1) / 5
-            extra["hits"] = {"teps": round(2 * E / dth, 1), "ms_per_step": round(dth * 1e3, 3), "edge_sweeps_per_step": 2, "dtype": "f64"}
-            api.strongly_connected_components(g, raw=True)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            _, sst = api.strongly_connected_components(g, raw=True)
-            torch.cuda.synchronize()
-            dtsc = time.perf_counter() - t1
-            extra["scc"] = {"teps": round(E / dtsc, 1), "ms": round(dtsc * 1e3, 3), **sst}
+            # ---- HITS (f64) and SCC on the same graph (f1 widening) ----
+            if not args.no_pr_cc:
+                api.hits(g, 1, raw=True)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                api.hits(g, 5, raw=True)
+                torch.cuda.synchronize()
+                dth = (time.perf_counter() - t1) / 5
+                extra["hits"] = {"teps": round(2 * E / dth, 1), "ms_per_step": round(dth * 1e3, 3), "edge_sweeps_per_step": 2, "dtype": "f64"}
+                api.strongly_connected_components(g, raw=True)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                _, sst = api.strongly_connected_components(g, raw=True)
+                torch.cuda.synchronize()
+                dtsc = time.perf_counter() - t1
+                extra["scc"] = {"teps": round(E / dtsc, 1), "ms": round(dtsc * 1e3, 3), **sst}
 
-        if not args.no_pr_cc and scale == 24:
-            g.close()
-            g.out_adj = g.in_adj = g.perm = None
-            torch.cuda.empty_cache()
-            leg_pr_cc(api, ctx, ef, seed, renumber, extra, cpu)
-            if args.cc_scale != 0 and args.cc_scale != 24:          # configs[4] at its stated scale (27 by default) on this one GPU
-                leg_cc_big(api, vd, ctx, args.cc_scale if args.cc_scale > 0 else 27, seed, renumber, args.chunk_edges, extra)
-            if not args.no_bfs_big:                                 # the one-GPU denominator of the 8-GPU weak-scaling run (RMAT-27)
-                leg_bfs_big(api, vd, ctx, 27, ef, seed, renumber, args.chunk_edges, extra)
-        if not args.no_operator_api and not args.no_pr_cc and scale == 24:     # (the apps build their own graphs: the bench's are freed by now)
-            leg_operator_api(scale, ef, extra)
+            if not args.no_pr_cc and scale == 24:
+                g.close()
+                g.out_adj = g.in_adj = g.perm = None
+                torch.cuda.empty_cache()
+                leg_pr_cc(api, ctx, ef, seed, renumber, extra, cpu)
+                if args.cc_scale != 0 and args.cc_scale != 24:          # configs[4] at its stated scale (27 by default) on this one GPU
+                    leg_cc_big(api, vd, ctx, args.cc_scale if args.cc_scale > 0 else 27, seed, renumber, args.chunk_edges, extra)
+                if not args.no_bfs_big:                                 # the one-GPU denominator of the 8-GPU weak-scaling run (RMAT-27)
+                    leg_bfs_big(api, vd, ctx, 27, ef, seed, renumber, args.chunk_edges, extra)
+            if not args.no_operator_api and not args.no_pr_cc and scale == 24:     # (the apps build their own graphs: the bench's are freed by now)
+                leg_operator_api(scale, ef, extra)
         workload = f"BFS direction-optimising on RMAT scale-{scale} (edge factor {ef}), 1xMI355X"
         scaling = "none"
     else:
@@ -1199,63 +1230,66 @@ def main():
             tmax = torch.tensor([dt], dtype=torch.float64, device=ctx.device)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        # ---- roofline of rank 0's dominant kernel: one more, UNTIMED pass over the same sources with HIP-event timing and this shard's
-        # work counters on (the counters cost a host read per bottom-up level, so they stay out of the timed region) ----
-        ctx.timing(True)
-        st = {}
-        for s in sources[args.warmup:]:
-            _, one = vs.bfs_run_sharded(shard, comm, s, api.BFS_DIRECTION_OPT, global_edges=E, gather_levels=False, levels=levels_buf, want_stats=True)
-            for k in ("levels", "td_steps", "bu_steps", "td_edges", "td_frontier", "bu_edges", "bu_found"):
-                st[k] = st.get(k, 0) + one[k]
-        barrier()
-        # the result of the last traversal: every owner's levels are consistent over its out-edges (level[dst] <= level[src] + 1, and a
-        # reached source never has an unreached destination) -- checked on the all-gathered levels
-        if comm is not None:
-            vs.bfs_run_sharded(shard, comm, sources[-1], api.BFS_DIRECTION_OPT, global_edges=E, gather_levels=True, levels=levels_buf, want_stats=False)
-        # ... both halves of the certificate (vd.bfs_levels_certificate): no out-edge of a reached vertex leads more than one level down or to an
-        # unreached vertex, and every reached vertex but the source has an in-neighbour one level up -- together: these ARE the breadth-first
-        # levels, proven at the full size by every rank on its own rows
-        edges_ok, parents_ok = vd.bfs_levels_certificate(levels_buf, shard, sources[-1])
-        levels_ok = edges_ok and parents_ok is not False
-        if world > 1:
-            flag = torch.tensor([1 if levels_ok else 0], dtype=torch.int32, device=ctx.device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            levels_ok = bool(int(flag.item()))
-        extra["verified_sharded_levels_consistent_over_owned_edges"] = levels_ok
-        extra["verified_sharded_every_reached_vertex_has_a_parent_one_level_up"] = bool(parents_ok) if parents_ok is not None else None
-        if not levels_ok:
-            sys.exit("bench.py: sharded BFS levels fail the breadth-first certificate on rank %d" % rank)
-        kern = {}
-        for name in ("bfs_bottom_up", "bfs_bottom_up_heavy", "bfs_top_down", "bfs_small_levels", "bfs_bitmap_expand", "gnf"):
-            n, ms = ctx.timing_get(name)
-            kern[name] = {"launches": n, "total_ms": round(ms, 4)}
-        ctx.timing(False)
-        owned = int(shard.row_end - shard.row_begin)
-        bytes_k = {"bfs_bottom_up": 8 * st.get("bu_edges", 0) + 4 * st.get("bu_found", 0) + st.get("bu_steps", 0) * (owned // 8),
-                   "bfs_top_down": 8 * st.get("td_edges", 0) + 20 * st.get("td_frontier", 0)}
-        dom = max(bytes_k, key=lambda k: kern[k]["total_ms"])
-        if kern[dom]["launches"] > 0 and kern[dom]["total_ms"] > 0:
-            per_launch_bytes = bytes_k[dom] / kern[dom]["launches"]
-            per_launch_ms = kern[dom]["total_ms"] / kern[dom]["launches"]
-            achieved = per_launch_bytes / (per_launch_ms * 1e-3) / 1e9
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "bytes_per_launch": int(per_launch_bytes),
-                        "ms_per_launch": round(per_launch_ms, 5), "launches": kern[dom]["launches"], "rank": 0,
-                        "note": "rank 0's shard, measured in an untimed repeat of the timed traversals"}
-        extra["bfs"] = {"kernels_rank0": kern, "levels_per_bfs": st.get("levels", 0) / max(1, args.steps), "td_steps": st.get("td_steps", 0),
-                        "bu_steps": st.get("bu_steps", 0), "driver": "vgl_hip_bfs_run_sharded (C++ loop, RCCL on the context's stream)",
-                        "exchange_last_traversal": comm.stats() if comm is not None else None}
-        extra["shard_edges"] = int(shard.E)
+        if args.dump_outputs and rank == 0:                # rank 0's levels: its owned rows, where the timed traversals leave them
+            dump_bfs_outputs(args.dump_outputs, levels_buf[int(shard.row_begin):int(shard.row_end)], None, seed)
         workload = (f"BFS direction-optimising super-steps (frontier slices all-gathered per level) on RMAT scale-{scale} "
                     f"(edge factor {ef}), edge-cut over {world} GPUs")
         scaling = "weak" if weak else "strong"
-        if not args.no_pr_cc:
-            # BASELINE configs[3] and [4]: PageRank on uniform-25 and Shiloach-Vishkin on the symmetrised RMAT graph over the same ranks
-            shard.close()
-            del shard, degrees, levels_buf
-            torch.cuda.empty_cache()
-            leg_pr_sharded(api, vd, vs, comm, ctx, dist, world, rank, args.pr_scale, ef, seed, args.chunk_edges, extra)
-            leg_cc_sharded(api, vd, vs, comm, ctx, dist, world, rank, args.cc_scale if args.cc_scale > 0 else scale, seed, args.chunk_edges, renumber, extra)
+        if args.full:
+            # ---- roofline of rank 0's dominant kernel: one more, UNTIMED pass over the same sources with HIP-event timing and this shard's
+            # work counters on (the counters cost a host read per bottom-up level, so they stay out of the timed region) ----
+            ctx.timing(True)
+            st = {}
+            for s in sources[args.warmup:]:
+                _, one = vs.bfs_run_sharded(shard, comm, s, api.BFS_DIRECTION_OPT, global_edges=E, gather_levels=False, levels=levels_buf, want_stats=True)
+                for k in ("levels", "td_steps", "bu_steps", "td_edges", "td_frontier", "bu_edges", "bu_found"):
+                    st[k] = st.get(k, 0) + one[k]
+            barrier()
+            # the result of the last traversal: every owner's levels are consistent over its out-edges (level[dst] <= level[src] + 1, and a
+            # reached source never has an unreached destination) -- checked on the all-gathered levels
+            if comm is not None:
+                vs.bfs_run_sharded(shard, comm, sources[-1], api.BFS_DIRECTION_OPT, global_edges=E, gather_levels=True, levels=levels_buf, want_stats=False)
+            # ... both halves of the certificate (vd.bfs_levels_certificate): no out-edge of a reached vertex leads more than one level down or to an
+            # unreached vertex, and every reached vertex but the source has an in-neighbour one level up -- together: these ARE the breadth-first
+            # levels, proven at the full size by every rank on its own rows
+            edges_ok, parents_ok = vd.bfs_levels_certificate(levels_buf, shard, sources[-1])
+            levels_ok = edges_ok and parents_ok is not False
+            if world > 1:
+                flag = torch.tensor([1 if levels_ok else 0], dtype=torch.int32, device=ctx.device)
+                dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+                levels_ok = bool(int(flag.item()))
+            extra["verified_sharded_levels_consistent_over_owned_edges"] = levels_ok
+            extra["verified_sharded_every_reached_vertex_has_a_parent_one_level_up"] = bool(parents_ok) if parents_ok is not None else None
+            if not levels_ok:
+                sys.exit("bench.py: sharded BFS levels fail the breadth-first certificate on rank %d" % rank)
+            kern = {}
+            for name in ("bfs_bottom_up", "bfs_bottom_up_heavy", "bfs_top_down", "bfs_small_levels", "bfs_bitmap_expand", "gnf"):
+                n, ms = ctx.timing_get(name)
+                kern[name] = {"launches": n, "total_ms": round(ms, 4)}
+            ctx.timing(False)
+            owned = int(shard.row_end - shard.row_begin)
+            bytes_k = {"bfs_bottom_up": 8 * st.get("bu_edges", 0) + 4 * st.get("bu_found", 0) + st.get("bu_steps", 0) * (owned // 8),
+                       "bfs_top_down": 8 * st.get("td_edges", 0) + 20 * st.get("td_frontier", 0)}
+            dom = max(bytes_k, key=lambda k: kern[k]["total_ms"])
+            if kern[dom]["launches"] > 0 and kern[dom]["total_ms"] > 0:
+                per_launch_bytes = bytes_k[dom] / kern[dom]["launches"]
+                per_launch_ms = kern[dom]["total_ms"] / kern[dom]["launches"]
+                achieved = per_launch_bytes / (per_launch_ms * 1e-3) / 1e9
+                roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None, "bytes_per_launch": int(per_launch_bytes),
+                            "ms_per_launch": round(per_launch_ms, 5), "launches": kern[dom]["launches"], "rank": 0,
+                            "note": "rank 0's shard, measured in an untimed repeat of the timed traversals"}
+            extra["bfs"] = {"kernels_rank0": kern, "levels_per_bfs": st.get("levels", 0) / max(1, args.steps), "td_steps": st.get("td_steps", 0),
+                            "bu_steps": st.get("bu_steps", 0), "driver": "vgl_hip_bfs_run_sharded (C++ loop, RCCL on the context's stream)",
+                            "exchange_last_traversal": comm.stats() if comm is not None else None}
+            extra["shard_edges"] = int(shard.E)
+            if not args.no_pr_cc:
+                # BASELINE configs[3] and [4]: PageRank on uniform-25 and Shiloach-Vishkin on the symmetrised RMAT graph over the same ranks
+                shard.close()
+                del shard, degrees, levels_buf
+                torch.cuda.empty_cache()
+                leg_pr_sharded(api, vd, vs, comm, ctx, dist, world, rank, args.pr_scale, ef, seed, args.chunk_edges, extra)
+                leg_cc_sharded(api, vd, vs, comm, ctx, dist, world, rank, args.cc_scale if args.cc_scale > 0 else scale, seed, args.chunk_edges, renumber, extra)
 
     if rank == 0:
         out = {
@@ -1266,7 +1300,7 @@ def main():
                        "vertex_numbering": "identity" if args.renumber == "none" else f"degree-sorted ({args.renumber})",
                        "graph_build_s": round(t_build, 2)},
         }
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 copy = measured_copy_bandwidth(ctx.device)
                 extra["hbm_copy_measured"] = copy

@@ -6,7 +6,11 @@
 // zero elements (apps/tc/tc.cpp:67: verify_results(..., 0)) and its checker reads levels[i] where it means levels[end_vertex] (tc.hpp:183), so the
 // answers are checked HERE: every pair against a sequential breadth-first search over the same graph through VGL_Graph's public accessors.
 //
-// usage: vgl_hip_tc_check -s <scale> -e <edge factor> -type rmat|ru -format csr [-it <pairs>]          prints TC CHECK PASSED / FAILED
+// The graph is SEEDED (-seed, default 1), as in scc_check.cpp: the reference's generators seed themselves with time(NULL), and its forward-backward
+// SCC puts a few vertices into the wrong component on some small graphs on any backend (tests/golden/scc_reference_disagreements.json), so an
+// unseeded run answers a pair wrongly now and then whatever the backend does.  With a seed the outcome is a fixed function of the arguments.
+//
+// usage: vgl_hip_tc_check -s <scale> -e <edge factor> -type rmat|ru -format csr [-it <pairs>] [-seed <n>]          prints TC CHECK PASSED / FAILED
 
 #define INT_ELEMENTS_PER_EDGE 5.0
 #define VECTOR_ENGINE_THRESHOLD_VALUE VECTOR_LENGTH*MAX_SX_AURORA_THREADS*128
@@ -14,6 +18,41 @@
 
 #include "graph_library.h"
 #include <queue>
+
+static inline unsigned long long splitmix64(unsigned long long &state)
+{
+    unsigned long long z = (state += 0x9E3779B97F4A7C15ULL);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// a directed edge list from a splitmix64 stream: R-MAT (the quadrant probabilities of graph_generation.hpp:131-169, ids scrambled as in
+// scc_check.cpp) or uniformly random endpoints
+static void fill_edges(EdgesContainer &edges, int scale, int edge_factor, bool rmat, unsigned long long seed)
+{
+    const int vertices_count = 1 << scale;
+    const long long edges_count = (long long)vertices_count * edge_factor;
+    edges.resize(vertices_count, edges_count);
+    int *src_ids = edges.get_src_ids(), *dst_ids = edges.get_dst_ids();
+    unsigned long long state = seed * 0x2545F4914F6CDD1DULL + 12345;
+    for (long long e = 0; e < edges_count; e++) {
+        if (!rmat) {
+            src_ids[e] = (int)(splitmix64(state) % (unsigned long long)vertices_count);
+            dst_ids[e] = (int)(splitmix64(state) % (unsigned long long)vertices_count);
+            continue;
+        }
+        int row = 0, col = 0;
+        for (int bit = 0; bit < scale; bit++) {
+            const unsigned r = (unsigned)(splitmix64(state) % 100);
+            const int quadrant = r < 57 ? 0 : (r < 76 ? 1 : (r < 95 ? 2 : 3));
+            row = (row << 1) | (quadrant >> 1);
+            col = (col << 1) | (quadrant & 1);
+        }
+        src_ids[e] = (int)(((unsigned long long)row * 2654435761ULL + 7) % (unsigned long long)vertices_count);
+        dst_ids[e] = (int)(((unsigned long long)col * 2654435761ULL + 7) % (unsigned long long)vertices_count);
+    }
+}
 
 // is `to` reachable from `from` along stored edges (a vertex reaches itself)
 static bool reachable(VGL_Graph &graph, int from, int to, std::vector<int> &seen, int stamp)
@@ -43,8 +82,15 @@ int main(int argc, char **argv)
         VGL_RUNTIME::init_library(argc, argv);
         Parser parser;
         parser.parse_args(argc, argv);
+        unsigned long long seed = 1;
+        for (int i = 1; i + 1 < argc; i++)
+            if (string(argv[i]) == "-seed") seed = strtoull(argv[i + 1], NULL, 10);
         VGL_Graph graph(VGL_RUNTIME::select_graph_format(parser), VGL_RUNTIME::select_graph_optimizations(parser));
-        VGL_RUNTIME::prepare_graph(graph, parser);
+        {
+            EdgesContainer edges;
+            fill_edges(edges, parser.get_scale(), parser.get_avg_degree(), parser.get_synthetic_graph_type() == RMAT, seed);
+            graph.import(edges);
+        }
         if (graph.get_container_type() != CSR_GRAPH) throw "tc_check: -format csr (pairs and answers are vertex ids of ONE numbering there)";
         const int vertices_count = graph.get_vertices_count();
 

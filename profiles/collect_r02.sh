@@ -6,9 +6,9 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/r2prof
 mkdir -p $OUT
 export TMPDIR=/tmp
-BFS="python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-sssp --no-pr-cc"
+BFS="python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-sssp --no-pr-cc"
 # 1. per-kernel times of the default bench command (CPU baseline off: it only adds host time)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline > $OUT/trace_bench_line.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline > $OUT/trace_bench_line.json 2> $OUT/trace.err
 echo "trace done" > $OUT/progress.txt
 # 2. counters for the BFS kernels, one pass per block group (MI355X_MICROARCH.md: FETCH_SIZE / WRITE_SIZE in passes of their own)
 i=0

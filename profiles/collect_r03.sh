@@ -6,9 +6,9 @@ cd "$(dirname "$0")/.."
 OUT=gpurun_out/r3prof
 mkdir -p $OUT
 export TMPDIR=/tmp
-BFS="python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-sssp --no-pr-cc --no-operator-api"
+BFS="python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-sssp --no-pr-cc --no-operator-api"
 # 1. per-kernel times of the default bench command (CPU baseline and the operator-API apps off: they only add host / child-process time)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline --no-operator-api > $OUT/trace_bench_line.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline --no-operator-api > $OUT/trace_bench_line.json 2> $OUT/trace.err
 echo "trace done" > $OUT/progress.txt
 # 2. HBM traffic of the BFS kernels (MI355X_MICROARCH.md: FETCH_SIZE / WRITE_SIZE in passes of their own, no tracing in the same run)
 i=0

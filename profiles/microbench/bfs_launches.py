@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch kernel durations of the BFS traversals from a rocprofv3 kernel trace (the bottom-up levels differ a lot: an average hides it).
-usage (GPU box):  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/bfstrace -- python3 bench.py --steps 4 --warmup 1 \
-                      --no-cpu-baseline --no-sssp --no-pr-cc && python3 profiles/microbench/bfs_launches.py gpurun_out/bfstrace"""
+usage (on an MI355X):  rocprofv3 --kernel-trace --output-format csv -d build/bfstrace -- python3 bench.py --full --steps 4 --warmup 1 \
+                      --no-cpu-baseline --no-sssp --no-pr-cc && python3 profiles/microbench/bfs_launches.py build/bfstrace"""
 import csv
 import glob
 import sys

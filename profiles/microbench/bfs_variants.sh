@@ -2,7 +2,7 @@
 # BFS on RMAT-24 under run-time switches of bfs.hip (VGL_BFS_SMALL_M: edge bound of the single-workgroup levels kernel); prints value / ms / kernel times
 cd "$(dirname "$0")/../.."
 for v in ${BFS_VARIANTS:-8192}; do
-    VGL_BFS_SMALL_M=$v python3 bench.py --no-cpu-baseline --no-sssp --no-pr-cc 2>/dev/null | python3 -c "
+    VGL_BFS_SMALL_M=$v python3 bench.py --full --no-cpu-baseline --no-sssp --no-pr-cc 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['bfs']['kernels']

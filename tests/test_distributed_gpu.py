@@ -23,7 +23,7 @@ def test_sharded_drivers_through_rccl_one_rank(ctx):
 def test_bench_sharded_path_one_rank(ctx):
     """bench.py's multi-GPU branch (streaming shard build, dealt placement, equal ranges) with one rank at a small scale"""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--scale", "16", "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded", "--scale", "16", "--steps", "3", "--warmup", "1",
                           "--no-cpu-baseline", "--no-sssp", "--no-pr-cc"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -36,7 +36,7 @@ def test_bench_sharded_pagerank_and_cc_legs_one_rank(ctx):
     """the PageRank (BASELINE configs[3]) and Shiloach-Vishkin (configs[4]) legs of bench.py's multi-GPU branch with one rank at small scales:
     streaming shard builds (uniform / symmetrised RMAT, outgoing lists only), super-step drivers, result checks and rank-0 rooflines"""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--scale", "15", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded", "--scale", "15", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline", "--no-sssp", "--pr-scale", "16", "--cc-scale", "15", "--chunk-edges", str(1 << 18)],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -50,7 +50,7 @@ def test_bench_single_gpu_line_contract(ctx):
     """the one-GPU bench line at a small scale (RMAT-18, CPU baseline on, SSSP leg on): one JSON line on stdout with the contract's keys,
     the roofline object of the dominant kernel measured with HIP events, the CPU port timed beside it, and the built-in verification"""
     import json
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "18", "--steps", "4", "--warmup", "1", "--cpu-sources", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "18", "--steps", "4", "--warmup", "1", "--cpu-sources", "2",
                           "--no-pr-cc"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [x for x in out.stdout.strip().splitlines() if x.startswith("{")]
@@ -73,6 +73,34 @@ def test_bench_single_gpu_line_contract(ctx):
     assert td["ms"] > 0 and td["blocked_levels"]["ms"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(ctx, tmp_path):
+    """a plain run (no --full): the headline keys only, --steps timed traversals; --dump-outputs writes the levels the last timed traversal
+    left (every vertex at this scale) and a level count / reached count per timed step -- the same arrays in two runs with the same arguments"""
+    import json
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "16", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines = [x for x in out.stdout.strip().splitlines() if x.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "verified", "hbm_copy_measured"} & set(line), sorted(line)
+        files = {f.name: np.load(f) for f in d.iterdir()}
+        assert sorted(files) == ["bfs_levels.npy", "bfs_levels_per_step.npy", "bfs_reached_per_step.npy"], sorted(files)
+        assert files["bfs_levels.npy"].dtype == np.float32 and files["bfs_levels.npy"].shape == (1 << 16,)
+        for name in ("bfs_levels_per_step.npy", "bfs_reached_per_step.npy"):
+            assert files[name].dtype == np.float64 and files[name].shape == (3,) and (files[name] > 0).all(), name
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+
+
 def test_bench_sharded_legs_through_the_library_rccl_communicator(ctx):
     """bench.py's N > 1 form as the driver launches it (torch.distributed.run, 127.0.0.1) with ONE rank and VGL_SHARD_FORCE_COLLECTIVES=1: the
     library's RCCL communicator is created from the id rank 0 broadcasts through the torch group, and every collective of the BFS, PageRank
@@ -80,7 +108,7 @@ def test_bench_sharded_legs_through_the_library_rccl_communicator(ctx):
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", VGL_SHARD_FORCE_COLLECTIVES="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29741",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded", "--scale", "15", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sssp",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded", "--scale", "15", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sssp",
            "--pr-scale", "16", "--cc-scale", "15", "--chunk-edges", str(1 << 18)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -98,7 +126,7 @@ def test_bench_two_ranks_sharing_the_gpu_over_the_peer_transport(ctx):
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", VGL_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29743",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "15", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sssp",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--scale", "15", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-sssp",
            "--pr-scale", "16", "--cc-scale", "15", "--chunk-edges", str(1 << 18)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
