@@ -1210,7 +1210,7 @@ def test_path_structure_is_built_once_per_graph_and_shared_between_weight_arrays
     """Round 5 (the reference derives every edge-array layout from ONE permutation, csr_edges_array.hpp:31-40): the blocked layout of the path
     algorithms is a per-graph STRUCTURE that keeps the CSR position behind every value slot (vgl_hip_sssp_prepare) + per-weights value arrays filled
     by one gather pass.  Two plans with different weights share the structure and stay independent; a plan outlives the graph handle's own
-    reference to the structure; and once the structure exists SSSP_ALL_ACTIVE -- the reference's schedule -- runs as blocked passes with the bits of
+    reference to the structure (a rebuild after a layout switch, the handle's close); and once the structure exists SSSP_ALL_ACTIVE -- the reference's schedule -- runs as blocked passes with the bits of
     the atomic push kernel (VGL_SSSP_ALL_ACTIVE_PUSH=1) and of the oracle."""
     import os
     from vectorgraphlibrary_amd import api
@@ -1249,10 +1249,20 @@ def test_path_structure_is_built_once_per_graph_and_shared_between_weight_arrays
         assert st2["pull_steps"] == 0 and (d2.cpu().numpy().view(np.int32) == ref_b.view(np.int32)).all()
         wd, _ = api.sswp(g, wa_d, s, api.SSSP_ALL_ACTIVE, raw=True)               # the widest-path algebra over the same structure
         assert (wd.cpu().numpy().view(np.int32) == O.sswp_bellman_ford(rowptr, adj, wa, s)[0].view(np.int32)).all()
+        os.environ["VGL_BLK_FUSE_MIN"] = "64"                                     # a layout switch changed: the graph's structure is rebuilt ...
+        try:
+            pc = api.SsspPullPlan(g, wa_d)
+        finally:
+            del os.environ["VGL_BLK_FUSE_MIN"]
+        for plan, w_d, ref in ((pa, wa_d, ref_a), (pb, wb_d, ref_b)):             # ... and the older plans keep theirs alive
+            for mode in (api.SSSP_PULL, api.SSSP_DIRECTION_OPT):
+                d, st = api.sssp(g, w_d, s, mode, raw=True, plan=plan)
+                assert (d.cpu().numpy().view(np.int32) == ref.view(np.int32)).all(), mode
+        pc.close()
     finally:
         os.environ.pop("VGL_BLK_PIECE_EDGES", None)
     pa.close()
-    g.close()                                                                     # the structure is still shared by pb: its last sharer frees it
+    g.close()                                                                     # pb still holds the structure: it is freed with pb
     pb.close()
 
 

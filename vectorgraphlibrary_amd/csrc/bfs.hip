@@ -1295,18 +1295,19 @@ static int vgl_bfs_bu_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, 
 // one top-down level from g->bm_front / g->bm_visited (both current) into g->bm_next (all zero before) and levels
 static int vgl_bfs_blocked_level(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, int32_t next_level)
 {
-    const vgl_blocked_plan *p = g->blk_bfs;
-    if (p->n_g_units > 0) {
-        vgl_timed_launch tl(c, "bfs_blk_gather");
-        hipLaunchKernelGGL(vgl_k_bfs_blk_gather, dim3((unsigned)p->n_g_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->g_units,
-                           (const uint16_t *)p->g_lo, (const uint32_t *)p->mid_to_a, reinterpret_cast<uint64_t *>(p->vals), p->g_count,
-                           (const uint64_t *)g->bm_front, (int64_t)g->row_begin >> 6);
-    }
-    if (p->n_a_units > 0) {
-        vgl_timed_launch tl(c, "bfs_blk_accumulate");
-        hipLaunchKernelGGL(vgl_k_bfs_blk_accumulate, dim3((unsigned)p->n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->a_units,
-                           (const uint16_t *)p->a_lo, reinterpret_cast<const uint64_t *>(p->vals), p->a_count, (const uint64_t *)g->bm_visited,
-                           g->bm_next, levels, next_level);
+    for (const vgl_blocked_piece &p : g->blk_bfs->pieces) {
+        if (p.n_g_units > 0) {
+            vgl_timed_launch tl(c, "bfs_blk_gather");
+            hipLaunchKernelGGL(vgl_k_bfs_blk_gather, dim3((unsigned)p.n_g_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p.g_units,
+                               (const uint16_t *)p.g_lo, (const uint32_t *)p.mid_to_a, reinterpret_cast<uint64_t *>(p.vals), p.g_count,
+                               (const uint64_t *)g->bm_front, (int64_t)g->row_begin >> 6);
+        }
+        if (p.n_a_units > 0) {
+            vgl_timed_launch tl(c, "bfs_blk_accumulate");
+            hipLaunchKernelGGL(vgl_k_bfs_blk_accumulate, dim3((unsigned)p.n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p.a_units,
+                               (const uint16_t *)p.a_lo, reinterpret_cast<const uint64_t *>(p.vals), p.a_count, (const uint64_t *)g->bm_visited,
+                               g->bm_next, levels, next_level);
+        }
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;
@@ -1349,7 +1350,11 @@ int vgl_hip_bfs_prepare_blocked(vgl_hip_ctx *c, vgl_hip_graph *g)
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("bfs_prepare_blocked: graph handle must own all rows");
     if (g->blk_bfs) return 0;
     static_assert(VGL_BTHREADS == VGL_BLK / 32, "one 32-bit frontier word per thread");
-    return vgl_blocked_plan_build(c, g->out, g->nrows, g->row_begin, g->V, 1, 1, nullptr, VGL_BLK_BITS, &g->blk_bfs, 1);
+    vgl_blocked_spec spec;
+    spec.gather_rows = 1;
+    spec.skip_self = 1;
+    spec.value_bits = 1;
+    return vgl_blocked_build(c, g->out, g->nrows, g->row_begin, g->V, spec, &g->blk_bfs);
 }
 
 int vgl_hip_bfs_init(vgl_hip_ctx *c, int32_t V, int32_t source, int32_t *d_levels)

@@ -246,43 +246,32 @@ void make_units(const std::vector<uint32_t> &bounds, uint32_t cap, bool keep_emp
 
 }  // namespace
 
-void vgl_blocked_plan_destroy(vgl_blocked_plan *p)
+vgl_blocked_layout::~vgl_blocked_layout()
 {
-    if (!p) return;
-    if (p->next) { vgl_blocked_plan_destroy(p->next); p->next = nullptr; }
-    if (p->shared) {                                                // a second set of value arrays over somebody else's structure
-        vgl_pool_free(p->stream, p->w_mid); vgl_pool_free(p->stream, p->f_w); vgl_pool_free(p->stream, p->g_dirty);
-        vgl_blocked_plan *s = p->shared_from;
-        delete p;
-        if (s && --s->sharers == 0 && s->orphan) { s->orphan = false; vgl_blocked_plan_destroy(s); }      // its owner is gone already
-        return;
+    for (const vgl_blocked_piece &p : pieces) {
+        if (p.piece_rowptr) hipFree(p.piece_rowptr);
+        if (p.piece_tile_row) hipFree(p.piece_tile_row);
+        void *ptrs[] = {p.g_lo, p.a_lo, p.mid_to_a, p.vals, p.g_units, p.a_units, p.multi, p.slabs, p.f_g_lo, p.f_a_lo, p.f_segs, p.f_units, p.w_src_mid, p.w_src_f};
+        for (void *q : ptrs) vgl_pool_free(stream, q);
     }
-    if (p->sharers > 0) { p->orphan = true; return; }               // still in use by plans that share it: the last of them frees it
-    if (p->piece_rowptr) hipFree(p->piece_rowptr);
-    if (p->piece_tile_row) hipFree(p->piece_tile_row);
-    void *ptrs[] = {p->g_lo, p->a_lo, p->w_mid, p->mid_to_a, p->vals, p->g_units, p->a_units, p->multi, p->slabs, p->g_dirty,
-                    p->f_g_lo, p->f_a_lo, p->f_w, p->f_segs, p->f_units, p->w_src_mid, p->w_src_f};
-    for (void *q : ptrs) vgl_pool_free(p->stream, q);
-    delete p;
 }
 
-// one plan over the rows of `dir` (all rows of the direction, or a row-range piece of it: row_off = number of rows before the piece,
-// nrows_total = rows of the whole direction)
-static int vgl_blocked_plan_build_one(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                                      int skip_self, const float *d_weights, int a_bits, vgl_blocked_plan **out, int value_bits, int fuse_min_edges,
-                                      int32_t row_off, int32_t nrows_total, int keep_edge_index, int64_t w_base)
+vgl_blocked_plan::~vgl_blocked_plan()
 {
-    if (d_weights) keep_edge_index = 1;
-    if (value_bits != 32 && value_bits != 1) VGL_FAIL("blocked_plan_build: values are 32 bits or 1 bit per edge");
-    if (!c || !out) VGL_FAIL("blocked_plan_build: null argument");
-    if (a_bits != VGL_BLK_BITS && a_bits != VGL_BLK_BITS - 1) VGL_FAIL("blocked_plan_build: accumulate blocks hold 2^15 (4-byte) or 2^14 (8-byte) accumulators");
+    for (const vgl_blocked_values &v : values) { vgl_pool_free(stream, v.w_mid); vgl_pool_free(stream, v.f_w); }
+}
+
+// one piece over the rows of `dir` (all rows of the direction, or a row-range piece of it: row_off = number of rows before the piece,
+// nrows_total = rows of the whole direction, w_base = CSR position of its first edge); what it allocates belongs to the layout at once
+static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t row_base, int32_t ncols, const vgl_blocked_spec &spec,
+                                   int32_t row_off, int32_t nrows_total, int64_t w_base, vgl_blocked_piece *p)
+{
+    const int gather_rows = spec.gather_rows, skip_self = spec.skip_self, a_bits = spec.a_bits, value_bits = spec.value_bits;
+    const int fuse_min_edges = spec.fuse_min_edges, keep_edge_index = spec.keep_edge_index;
     if (dir.edges > 0 && (!dir.rowptr || !dir.adj || !dir.tile_row)) VGL_FAIL("blocked_plan_build: CSR direction is missing");
     if (dir.edges >= (1LL << 32) - VGL_TILE) VGL_FAIL("blocked_plan_build: at most 2^32 edges per plan");
     hipStream_t st = c->stream;
     const int64_t E = dir.edges;
-    vgl_blocked_plan *p = new vgl_blocked_plan();
-    struct guard { vgl_blocked_plan *p; ~guard() { if (p) vgl_blocked_plan_destroy(p); } } own{p};
-    (void)nrows;
     p->g_count = gather_rows ? nrows_total : ncols;
     p->a_count = gather_rows ? ncols : nrows_total;
     p->nG = (int32_t)std::max<int64_t>(1, vgl_ceil_div(p->g_count, VGL_BLK));
@@ -299,7 +288,6 @@ static int vgl_blocked_plan_build_one(vgl_hip_ctx *c, const vgl_dir_csr &dir, in
 
     dev_bufs tmp;
     tmp.st = st;
-    p->stream = st;
     stage_trace trace(c, st);
     std::unique_ptr<vgl_timed_launch> timed;
     uint32_t *keys = nullptr, *keys2 = nullptr, *packed = nullptr, *packed2 = nullptr, *seg_first = nullptr, *seg_end = nullptr;
@@ -400,13 +388,8 @@ static int vgl_blocked_plan_build_one(vgl_hip_ctx *c, const vgl_dir_csr &dir, in
     VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->a_lo, sizeof(uint16_t) * std::max<size_t>(slots, 8)));
     VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->vals, value_bits == 1 ? sizeof(uint64_t) * std::max<size_t>(p->nchunks, 1) : sizeof(uint32_t) * std::max<size_t>(slots, 8)));
     VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->mid_to_a, sizeof(uint32_t) * std::max<size_t>(p->nchunks, 1)));
-    if (keep_edge_index) {
-        VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_mid, sizeof(float) * std::max<size_t>(slots, 8)));
-        VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_mid, sizeof(uint32_t) * std::max<size_t>(slots, 8)));
-    }
+    if (keep_edge_index) VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_mid, sizeof(uint32_t) * std::max<size_t>(slots, 8)));
     p->w_base = w_base;
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->g_dirty, (size_t)nG));
-    VGL_HIP_TRY(hipMemsetAsync(p->g_dirty, 1, (size_t)nG, st));
     trace.mark("allocate plan arrays");
     if (p->nchunks > 0) {
         hipLaunchKernelGGL(vgl_k_blk_fill, dim3((unsigned)std::min<int64_t>(65536, vgl_ceil_div(p->nchunks, VGL_WAVES))), dim3(VGL_BLOCK), 0, st, p->nchunks, nG, nA,
@@ -462,10 +445,7 @@ static int vgl_blocked_plan_build_one(vgl_hip_ctx *c, const vgl_dir_csr &dir, in
             const size_t fslots = (size_t)chunk * VGL_CHUNK;
             VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_g_lo, sizeof(uint16_t) * fslots));
             VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_a_lo, sizeof(uint16_t) * fslots));
-            if (keep_edge_index) {
-                VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_w, sizeof(float) * fslots));
-                VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_f, sizeof(uint32_t) * fslots));
-            }
+            if (keep_edge_index) VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_f, sizeof(uint32_t) * fslots));
             VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_segs, sizeof(vgl_blk_fseg) * fsegs.size()));
             VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_units, sizeof(vgl_blk_funit) * funits.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, p->f_segs, fsegs.data(), sizeof(vgl_blk_fseg) * fsegs.size()));
@@ -506,14 +486,6 @@ static int vgl_blocked_plan_build_one(vgl_hip_ctx *c, const vgl_dir_csr &dir, in
     trace.mark("work units");
     tmp.free_all();
     trace.mark("free temporaries");
-    if (d_weights) {
-        p->next = nullptr;
-        VGL_TRY(vgl_blocked_plan_load_weights(c, p, d_weights - w_base));       // (load_weights takes the direction's array and adds the piece's base itself)
-        VGL_HIP_TRY(hipStreamSynchronize(st));
-        trace.mark("load weights");
-    }
-    own.p = nullptr;
-    *out = p;
     return 0;
 }
 
@@ -522,103 +494,82 @@ __global__ void vgl_k_blk_rebase_rows(int32_t n, const int64_t *rowptr, int64_t 
     for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += gridDim.x * blockDim.x) out[i] = rowptr[i] - base;
 }
 
-int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan *p, const float *d_weights)
+int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan &p, const float *d_weights)
 {
-    if (!c || !p || !d_weights) VGL_FAIL("blocked_plan_load_weights: null argument");
-    for (vgl_blocked_plan *q = p; q; q = q->next) {
-        if ((q->nchunks > 0 && (!q->w_src_mid || !q->w_mid)) || (q->f_nchunks > 0 && (!q->w_src_f || !q->f_w)))
+    if (!c || !p.layout || !d_weights) VGL_FAIL("blocked_plan_load_weights: null argument");
+    if (p.values.size() != p.layout->pieces.size()) VGL_FAIL("blocked_plan_load_weights: the plan has no value arrays");
+    for (size_t k = 0; k < p.layout->pieces.size(); k++) {
+        const vgl_blocked_piece &q = p.layout->pieces[k];
+        const vgl_blocked_values &v = p.values[k];
+        if ((q.nchunks > 0 && (!q.w_src_mid || !v.w_mid)) || (q.f_nchunks > 0 && (!q.w_src_f || !v.f_w)))
             VGL_FAIL("blocked_plan_load_weights: the layout was built without its edge index");
         vgl_timed_launch tl(c, "blk_load_weights");
-        const size_t slots = (size_t)q->nchunks * VGL_CHUNK, fslots = (size_t)q->f_nchunks * VGL_CHUNK;
+        const size_t slots = (size_t)q.nchunks * VGL_CHUNK, fslots = (size_t)q.f_nchunks * VGL_CHUNK;
         if (slots) hipLaunchKernelGGL(vgl_k_blk_load_weights, dim3((unsigned)std::min<size_t>(16384, (slots / 4 + VGL_BLOCK - 1) / VGL_BLOCK)), dim3(VGL_BLOCK), 0, c->stream,
-                                      slots, (const uint32_t *)q->w_src_mid, d_weights + q->w_base, q->w_mid);
+                                      slots, (const uint32_t *)q.w_src_mid, d_weights + q.w_base, v.w_mid);
         if (fslots) hipLaunchKernelGGL(vgl_k_blk_load_weights, dim3((unsigned)std::min<size_t>(16384, (fslots / 4 + VGL_BLOCK - 1) / VGL_BLOCK)), dim3(VGL_BLOCK), 0, c->stream,
-                                       fslots, (const uint32_t *)q->w_src_f, d_weights + q->w_base, q->f_w);
+                                       fslots, (const uint32_t *)q.w_src_f, d_weights + q.w_base, v.f_w);
         VGL_HIP_TRY(hipGetLastError());
     }
     return 0;
 }
 
-int vgl_blocked_plan_share(vgl_hip_ctx *c, const vgl_blocked_plan *structure, vgl_blocked_plan **out)
+int vgl_blocked_plan_share(vgl_hip_ctx *c, std::shared_ptr<const vgl_blocked_layout> layout, std::unique_ptr<vgl_blocked_plan> *out)
 {
-    if (!c || !structure || !out) VGL_FAIL("blocked_plan_share: null argument");
-    vgl_blocked_plan *head = nullptr, *tail = nullptr;
-    struct guard { vgl_blocked_plan **h; ~guard() { if (*h) vgl_blocked_plan_destroy(*h); } } own{&head};
-    for (const vgl_blocked_plan *s = structure; s; s = s->next) {
-        if ((s->nchunks > 0 && !s->w_src_mid) || (s->f_nchunks > 0 && !s->w_src_f)) VGL_FAIL("blocked_plan_share: the layout was built without its edge index");
-        vgl_blocked_plan *q = new vgl_blocked_plan(*s);
-        q->shared = true; q->next = nullptr; q->w_mid = nullptr; q->f_w = nullptr; q->g_dirty = nullptr;
-        q->stream = c->stream;
-        if (tail) tail->next = q; else head = q;
-        tail = q;
-        const size_t slots = (size_t)q->nchunks * VGL_CHUNK, fslots = (size_t)q->f_nchunks * VGL_CHUNK;
-        VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&q->w_mid, sizeof(float) * std::max<size_t>(slots, 8)));
-        if (fslots) VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&q->f_w, sizeof(float) * fslots));
-        VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&q->g_dirty, (size_t)std::max(q->nG, 1)));
-        VGL_HIP_TRY(hipMemsetAsync(q->g_dirty, 1, (size_t)std::max(q->nG, 1), c->stream));
+    if (!c || !layout || !out) VGL_FAIL("blocked_plan_share: null argument");
+    auto p = std::make_unique<vgl_blocked_plan>();
+    p->stream = c->stream;
+    for (const vgl_blocked_piece &s : layout->pieces) {
+        if ((s.nchunks > 0 && !s.w_src_mid) || (s.f_nchunks > 0 && !s.w_src_f)) VGL_FAIL("blocked_plan_share: the layout was built without its edge index");
+        vgl_blocked_values &v = p->values.emplace_back();
+        const size_t slots = (size_t)s.nchunks * VGL_CHUNK, fslots = (size_t)s.f_nchunks * VGL_CHUNK;
+        VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&v.w_mid, sizeof(float) * std::max<size_t>(slots, 8)));
+        if (fslots) VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&v.f_w, sizeof(float) * fslots));
     }
-    own.h = &tail; tail = nullptr;                                  // (disarm)
-    head->shared_from = const_cast<vgl_blocked_plan *>(structure);
-    const_cast<vgl_blocked_plan *>(structure)->sharers++;
-    *out = head;
+    p->layout = std::move(layout);
+    *out = std::move(p);
     return 0;
 }
 
-static int vgl_blocked_plan_build_any(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                                      int skip_self, const float *d_weights, int a_bits, vgl_blocked_plan **out, int value_bits, int fuse_min_edges, int keep_edge_index);
-
-int vgl_blocked_plan_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                           int skip_self, const float *d_weights, int a_bits, vgl_blocked_plan **out, int value_bits, int fuse_min_edges)
+int vgl_blocked_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, const vgl_blocked_spec &spec,
+                      std::shared_ptr<const vgl_blocked_layout> *out)
 {
-    return vgl_blocked_plan_build_any(c, dir, nrows, row_base, ncols, gather_rows, skip_self, d_weights, a_bits, out, value_bits, fuse_min_edges, d_weights ? 1 : 0);
-}
-int vgl_blocked_plan_build_indexed(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                                   int skip_self, int a_bits, vgl_blocked_plan **out, int fuse_min_edges)
-{
-    return vgl_blocked_plan_build_any(c, dir, nrows, row_base, ncols, gather_rows, skip_self, nullptr, a_bits, out, 32, fuse_min_edges, 1);
-}
-
-static int vgl_blocked_plan_build_any(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                                      int skip_self, const float *d_weights, int a_bits, vgl_blocked_plan **out, int value_bits, int fuse_min_edges, int keep_edge_index)
-{
+    if (spec.value_bits != 32 && spec.value_bits != 1) VGL_FAIL("blocked_plan_build: values are 32 bits or 1 bit per edge");
     if (!c || !out) VGL_FAIL("blocked_plan_build: null argument");
+    if (spec.a_bits != VGL_BLK_BITS && spec.a_bits != VGL_BLK_BITS - 1) VGL_FAIL("blocked_plan_build: accumulate blocks hold 2^15 (4-byte) or 2^14 (8-byte) accumulators");
+    auto L = std::make_shared<vgl_blocked_layout>();
+    L->stream = c->stream;
     // chunk positions are 32-bit: a direction is laid out whole below 2^32 - 2048 edges (VGL_BLK_PIECE_EDGES lowers the bound: tests)
     int64_t limit = (1LL << 32) - VGL_TILE;
-    const bool cuttable = value_bits == 32 && a_bits == VGL_BLK_BITS;            // (the variable only lowers the bound of layouts that can be cut)
+    const bool cuttable = spec.value_bits == 32 && spec.a_bits == VGL_BLK_BITS;  // (the variable only lowers the bound of layouts that can be cut)
     if (const char *e = vgl_env(c, "VGL_BLK_PIECE_EDGES")) if (cuttable) limit = std::max<int64_t>(4096, atoll(e));
-    if (dir.edges < limit) return vgl_blocked_plan_build_one(c, dir, nrows, row_base, ncols, gather_rows, skip_self, d_weights, a_bits, out, value_bits, fuse_min_edges, 0, nrows, keep_edge_index, 0);
-    if (!cuttable) VGL_FAIL("blocked_plan_build: only 4-byte min / max-type layouts can be cut into row-range pieces (2^32 edges or more)");
-    // row ranges of at most `piece` edges each (a single row above the bound cannot be cut)
-    const int64_t piece = std::min<int64_t>(limit, 1LL << 31);
-    const int parts = (int)std::min<int64_t>(4096, vgl_ceil_div(dir.edges, piece) + 1);
-    std::vector<int32_t> bounds((size_t)parts + 1);
-    VGL_TRY(vgl_hip_partition_rows(c, nrows, dir.rowptr, parts, bounds.data()));
-    std::vector<int64_t> starts((size_t)parts + 1);
-    for (int k = 0; k <= parts; k++) VGL_TRY(vgl_hip_memcpy_d2h(c, &starts[(size_t)k], dir.rowptr + bounds[(size_t)k], sizeof(int64_t)));
-    vgl_blocked_plan *head = nullptr, *tail = nullptr;
-    struct guard { vgl_blocked_plan **h; ~guard() { if (*h) vgl_blocked_plan_destroy(*h); } } own{&head};
-    for (int k = 0; k < parts; k++) {
-        const int32_t lo = bounds[(size_t)k], hi = bounds[(size_t)k + 1];
-        const int64_t e0 = starts[(size_t)k], e1 = starts[(size_t)k + 1];
-        if (hi <= lo || e1 <= e0) continue;
-        if (e1 - e0 >= (1LL << 32) - VGL_TILE) VGL_FAIL("blocked_plan_build: a row range of one piece holds 2^32 edges or more");
-        vgl_dir_csr view;
-        int64_t *rp = nullptr;
-        VGL_HIP_TRY(hipMalloc((void **)&rp, sizeof(int64_t) * ((size_t)(hi - lo) + 1)));
-        hipLaunchKernelGGL(vgl_k_blk_rebase_rows, dim3((unsigned)std::min<int64_t>(4096, vgl_ceil_div((int64_t)(hi - lo) + 1, 256))), dim3(256), 0, c->stream, hi - lo,
-                           dir.rowptr + lo, e0, rp);
-        view.rowptr = rp; view.adj = dir.adj + e0; view.edges = e1 - e0;
-        int rc = vgl_build_tile_rows(c, view, hi - lo);
-        vgl_blocked_plan *q = nullptr;
-        if (!rc) rc = vgl_blocked_plan_build_one(c, view, hi - lo, row_base, ncols, gather_rows, skip_self, d_weights ? d_weights + e0 : nullptr, a_bits, &q, value_bits,
-                                                 fuse_min_edges, lo, nrows, keep_edge_index, e0);
-        if (rc) { hipFree(rp); if (view.tile_row) hipFree(view.tile_row); return rc; }
-        q->piece_rowptr = rp; q->piece_tile_row = view.tile_row;
-        if (tail) tail->next = q; else head = q;
-        tail = q;
+    if (dir.edges >= limit) {
+        if (!cuttable) VGL_FAIL("blocked_plan_build: only 4-byte min / max-type layouts can be cut into row-range pieces (2^32 edges or more)");
+        // row ranges of at most `piece` edges each (a single row above the bound cannot be cut)
+        const int64_t piece = std::min<int64_t>(limit, 1LL << 31);
+        const int parts = (int)std::min<int64_t>(4096, vgl_ceil_div(dir.edges, piece) + 1);
+        std::vector<int32_t> bounds((size_t)parts + 1);
+        VGL_TRY(vgl_hip_partition_rows(c, nrows, dir.rowptr, parts, bounds.data()));
+        std::vector<int64_t> starts((size_t)parts + 1);
+        for (int k = 0; k <= parts; k++) VGL_TRY(vgl_hip_memcpy_d2h(c, &starts[(size_t)k], dir.rowptr + bounds[(size_t)k], sizeof(int64_t)));
+        for (int k = 0; k < parts; k++) {
+            const int32_t lo = bounds[(size_t)k], hi = bounds[(size_t)k + 1];
+            const int64_t e0 = starts[(size_t)k], e1 = starts[(size_t)k + 1];
+            if (hi <= lo || e1 <= e0) continue;
+            if (e1 - e0 >= (1LL << 32) - VGL_TILE) VGL_FAIL("blocked_plan_build: a row range of one piece holds 2^32 edges or more");
+            vgl_blocked_piece &q = L->pieces.emplace_back();
+            VGL_HIP_TRY(hipMalloc((void **)&q.piece_rowptr, sizeof(int64_t) * ((size_t)(hi - lo) + 1)));
+            hipLaunchKernelGGL(vgl_k_blk_rebase_rows, dim3((unsigned)std::min<int64_t>(4096, vgl_ceil_div((int64_t)(hi - lo) + 1, 256))), dim3(256), 0, c->stream, hi - lo,
+                               dir.rowptr + lo, e0, q.piece_rowptr);
+            vgl_dir_csr view;
+            view.rowptr = q.piece_rowptr; view.adj = dir.adj + e0; view.edges = e1 - e0;
+            const int rc = vgl_build_tile_rows(c, view, hi - lo);
+            q.piece_tile_row = view.tile_row;
+            if (rc) return rc;
+            VGL_TRY(vgl_blocked_build_piece(c, view, row_base, ncols, spec, lo, nrows, e0, &q));
+        }
     }
-    if (!head) return vgl_blocked_plan_build_one(c, dir, nrows, row_base, ncols, gather_rows, skip_self, d_weights, a_bits, out, value_bits, fuse_min_edges, 0, nrows, keep_edge_index, 0);
-    *out = head;
-    head = nullptr;
+    if (L->pieces.empty()) VGL_TRY(vgl_blocked_build_piece(c, dir, row_base, ncols, spec, 0, nrows, 0, &L->pieces.emplace_back()));
+    *out = std::move(L);
     return 0;
 }

@@ -379,6 +379,16 @@ static int vgl_pr_mode_auto(vgl_hip_ctx *c, vgl_hip_graph *g, int *mode)
     return 0;
 }
 
+// the layout of PageRank's pull and of the sum over edges: the ids gather, the rows accumulate 8-byte sums, self loops left out (pr.hpp:111)
+static int vgl_pr_layout(vgl_hip_ctx *c, vgl_hip_graph *g)
+{
+    if (g->blk_pr) return 0;
+    vgl_blocked_spec spec;
+    spec.skip_self = 1;
+    spec.a_bits = VGL_BLK_BITS - 1;
+    return vgl_blocked_build(c, g->out, g->nrows, g->row_begin, g->V, spec, &g->blk_pr);
+}
+
 int vgl_pr_iteration(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *indeg, const float *rdeg, float *ranks, float *contrib,
                      float *ranks_out, int mode)
 {
@@ -388,13 +398,13 @@ int vgl_pr_iteration(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *indeg, con
         const float d = 0.85f;
         const float k = (float)((1.0 - (double)d) / (double)((float)V));
         const int npart = (int)vgl_grid3(V, 1024);
-        if (!g->blk_pr) VGL_TRY(vgl_blocked_plan_build(c, g->out, g->nrows, g->row_begin, V, 0, 1, nullptr, VGL_BLK_BITS - 1, &g->blk_pr));
+        VGL_TRY(vgl_pr_layout(c, g));
         VGL_TRY(vgl_ensure_partials(c, (size_t)npart + 8));
         float *dangling = reinterpret_cast<float *>(c->d_partials + npart);
         hipLaunchKernelGGL(vgl_k_pr_prepare, dim3(npart), dim3(VGL_BLOCK), 0, c->stream, V, indeg, rdeg, ranks, contrib, c->d_partials);
         hipLaunchKernelGGL(vgl_k_pr_dangling, dim3(1), dim3(VGL_BLOCK), 0, c->stream, npart, c->d_partials, dangling);
         const vgl_pr_blk_op op{contrib, dangling, k, d, ranks_out, g->row_begin};
-        return vgl_blocked_pass<vgl_pr_blk_op, false, true>(c, g->blk_pr, op, "pr_blk_gather", "pr_blk_accumulate");
+        return vgl_blocked_pass<vgl_pr_blk_op, false, true>(c, *g->blk_pr, nullptr, op, "pr_blk_gather", "pr_blk_accumulate");
     }
     const int32_t V = g->V;
     const float d = 0.85f;
@@ -441,9 +451,9 @@ int vgl_hip_sum_over_edges_f32(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_
     int bound_exp = 0;
     (void)frexpf(sum_bound, &bound_exp);                    // sum_bound = m * 2^bound_exp, 0.5 <= m < 1: sums < 2^bound_exp, one spare bit on top
     bound_exp += 1;
-    if (!g->blk_pr) VGL_TRY(vgl_blocked_plan_build(c, g->out, g->nrows, g->row_begin, g->V, 0, 1, nullptr, VGL_BLK_BITS - 1, &g->blk_pr));
+    VGL_TRY(vgl_pr_layout(c, g));
     const vgl_sum_blk_op op{d_values, d_sums, g->row_begin, bound_exp};
-    return vgl_blocked_pass<vgl_sum_blk_op, false, true>(c, g->blk_pr, op, "sum_blk_gather", "sum_blk_accumulate");
+    return vgl_blocked_pass<vgl_sum_blk_op, false, true>(c, *g->blk_pr, nullptr, op, "sum_blk_gather", "sum_blk_accumulate");
 }
 
 int vgl_hip_pr_setup(vgl_hip_ctx *c, int32_t V, const int32_t *d_indeg, float *d_ranks, float *d_rdeg)
@@ -468,7 +478,7 @@ int vgl_hip_pr_prepare(vgl_hip_ctx *c, vgl_hip_graph *g, int mode, int *resolved
     if (mode < VGL_HIP_PR_EXACT_ORDER || mode > VGL_HIP_PR_AUTO) VGL_FAIL("pr_prepare: unknown mode");
     VGL_TRY(vgl_pr_mode_auto(c, g, &mode));
     if (mode == VGL_HIP_PR_BLOCKED) {
-        if (!g->blk_pr) VGL_TRY(vgl_blocked_plan_build(c, g->out, g->nrows, g->row_begin, g->V, 0, 1, nullptr, VGL_BLK_BITS - 1, &g->blk_pr));
+        VGL_TRY(vgl_pr_layout(c, g));
     } else VGL_TRY(vgl_pull_find_hubs(c, g, g->out));
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
     if (resolved_mode) *resolved_mode = mode;

@@ -308,7 +308,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sssp_relax_sparse(const int32
 }
 
 struct vgl_hip_sssp_pull_plan {
-    vgl_blocked_plan *blk = nullptr;
+    std::unique_ptr<vgl_blocked_plan> blk;      // a plan over the graph's path layout (vgl_hip_graph::blk_path), with these weights
     const float *weights = nullptr;
     vgl_hip_graph *g = nullptr;
     uint64_t g_uid = 0;              // the handle's uid: a destroyed graph whose address was reused is not mistaken for the plan's graph
@@ -348,8 +348,9 @@ static int vgl_path_run_pull(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
                            (double)M / (double)std::max<int64_t>(g->out.edges, 1), pull ? "pull" : "push");
         if (pull) {
             const vgl_path_blk_op<Path> op{d_dist, next, g->row_begin};
-            VGL_TRY((vgl_blocked_pass<vgl_path_blk_op<Path>, true, false>(c, plan->blk, op, "sssp_pull_gather", "sssp_pull_accumulate", false, "sssp_pull_fused")));
-            pull_edges += vgl_blocked_plan_edges(plan->blk);
+            VGL_TRY((vgl_blocked_pass<vgl_path_blk_op<Path>, true, false>(c, *plan->blk->layout, plan->blk->values.data(), op, "sssp_pull_gather",
+                                                                          "sssp_pull_accumulate", "sssp_pull_fused")));
+            pull_edges += plan->blk->layout->edges();
             st.pull_steps++;
         } else if (M > 0) {
             VGL_TRY(vgl_bfs_bm_gnf(c, g, front, false, true, M));       // ids + edge offsets + tile table of the frontier
@@ -370,7 +371,8 @@ static int vgl_path_run_pull(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
     return 0;
 }
 
-// the path structure of a graph (vgl_hip_graph::blk_path), built on first use and rebuilt when a layout switch changed since
+// the path layout of a graph (vgl_hip_graph::blk_path), built on first use and rebuilt when a layout switch changed since (plans built over the
+// old one keep it alive)
 static int vgl_path_structure(vgl_hip_ctx *c, vgl_hip_graph *g)
 {
     // pairs of 16384-id blocks with at least VGL_BLK_FUSE_MIN (16384) edges become fused tiles (vgl_blocked.h): on a degree-sorted RMAT graph
@@ -384,8 +386,12 @@ static int vgl_path_structure(vgl_hip_ctx *c, vgl_hip_graph *g)
         key += "|"; key += v ? v : "";
     }
     if (g->blk_path && g->blk_path_key == key) return 0;
-    if (g->blk_path) { VGL_HIP_TRY(hipStreamSynchronize(c->stream)); vgl_blocked_plan_destroy(g->blk_path); g->blk_path = nullptr; }
-    VGL_TRY(vgl_blocked_plan_build_indexed(c, g->out, g->nrows, g->row_begin, g->V, 1, 0, VGL_BLK_BITS, &g->blk_path, fuse_min));
+    if (g->blk_path) { VGL_HIP_TRY(hipStreamSynchronize(c->stream)); g->blk_path.reset(); }
+    vgl_blocked_spec spec;
+    spec.gather_rows = 1;
+    spec.fuse_min_edges = fuse_min;
+    spec.keep_edge_index = 1;
+    VGL_TRY(vgl_blocked_build(c, g->out, g->nrows, g->row_begin, g->V, spec, &g->blk_path));
     g->blk_path_key = key;
     return 0;
 }
@@ -396,13 +402,13 @@ static int vgl_pull_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d
     vgl_hip_sssp_pull_plan *p = new vgl_hip_sssp_pull_plan();
     p->g = g; p->g_uid = g->uid; p->weights = d_weights;
     // Round 5: the layout is a per-GRAPH structure (one radix sort of the edges by block pair, the CSR position behind every value slot kept -- the
-    // role of the reference's edges_reorder_indexes, csr_edges_array.hpp:31-40) plus per-WEIGHTS value arrays filled by one gather pass: a second
-    // weights array on the same graph costs ~3 ms instead of the 37 ms of a full build (RMAT-24)
+    // role of the reference's edges_reorder_indexes, csr_edges_array.hpp:31-40); a plan is a reference to it plus per-WEIGHTS value arrays filled
+    // by one gather pass: a second weights array on the same graph costs ~3 ms instead of the 37 ms of a full build (RMAT-24)
     int rc = vgl_path_structure(c, g);
     if (!rc) rc = vgl_blocked_plan_share(c, g->blk_path, &p->blk);
-    if (!rc) rc = vgl_blocked_plan_load_weights(c, p->blk, d_weights);
+    if (!rc) rc = vgl_blocked_plan_load_weights(c, *p->blk, d_weights);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = vgl_set_error(__FILE__, __LINE__, "sssp_pull_plan_create: the weights pass failed");
-    if (rc) { if (p->blk) vgl_blocked_plan_destroy(p->blk); delete p; return rc; }
+    if (rc) { delete p; return rc; }
     *out = p;
     return 0;
 }
@@ -428,7 +434,6 @@ static int vgl_path_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights
         VGL_TRY(vgl_pull_plan_create(c, g, d_weights, &plan));
         const int rc = vgl_path_run_pull<Path>(c, g, d_weights, plan, source, mode, d_dist, stats, who);
         hipStreamSynchronize(c->stream);
-        vgl_blocked_plan_destroy(plan->blk);
         delete plan;
         return rc;
     }
@@ -477,9 +482,9 @@ int vgl_hip_sssp_pull_plan_info(vgl_hip_sssp_pull_plan *p, int64_t *edges, int64
 {
     if (!p || !p->blk) VGL_FAIL("sssp_pull_plan_info: null plan");
     int64_t two_pass_slots = 0, fused_slots = 0, e_all = 0, f_all = 0, nch = 0;
-    for (const vgl_blocked_plan *b = p->blk; b; b = b->next) {          // (a direction with 2^32 edges or more is laid out in pieces)
-        two_pass_slots += (int64_t)b->nchunks * VGL_CHUNK; fused_slots += (int64_t)b->f_nchunks * VGL_CHUNK;
-        e_all += b->edges; f_all += b->f_edges; nch += b->nchunks;
+    for (const vgl_blocked_piece &b : p->blk->layout->pieces) {          // (a direction with 2^32 edges or more is laid out in pieces)
+        two_pass_slots += (int64_t)b.nchunks * VGL_CHUNK; fused_slots += (int64_t)b.f_nchunks * VGL_CHUNK;
+        e_all += b.edges; f_all += b.f_edges; nch += b.nchunks;
     }
     if (edges) *edges = e_all;
     if (fused_edges) *fused_edges = f_all;
@@ -492,7 +497,6 @@ int vgl_hip_sssp_pull_plan_destroy(vgl_hip_ctx *c, vgl_hip_sssp_pull_plan *p)
 {
     if (!p) return 0;
     if (c) hipStreamSynchronize(c->stream);
-    vgl_blocked_plan_destroy(p->blk);
     delete p;
     return 0;
 }
@@ -506,7 +510,8 @@ int vgl_hip_sssp_pull_pass(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_hip_sssp_pull_p
     const int64_t words = vgl_ceil_div(g->V, 64);
     VGL_TRY(vgl_zero_words(c, g->bm_next, words));
     const vgl_path_blk_op<vgl_path_shortest> op{d_dist, g->bm_next, g->row_begin};
-    VGL_TRY((vgl_blocked_pass<vgl_path_blk_op<vgl_path_shortest>, true, false>(c, plan->blk, op, "sssp_pull_gather", "sssp_pull_accumulate", false, "sssp_pull_fused")));
+    VGL_TRY((vgl_blocked_pass<vgl_path_blk_op<vgl_path_shortest>, true, false>(c, *plan->blk->layout, plan->blk->values.data(), op, "sssp_pull_gather",
+                                                                               "sssp_pull_accumulate", "sssp_pull_fused")));
     VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_next, true, false));          // (the improved vertices were marked in the bitmap: its size says whether any were)
     if (changed) *changed = c->h_counters[C_FRONT] != 0;
     return 0;

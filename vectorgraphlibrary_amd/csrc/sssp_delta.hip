@@ -55,7 +55,7 @@ struct vgl_hip_sssp_plan {
     // round 4: the two parts laid out for the blocked advance as well (vgl_blocked.h, fused tiles for the dense block pairs): a DENSE step then
     // streams its part at ~5 TB/s with every random access in LDS instead of one L2 line per gather (the heavy step of the first bucket of an
     // RMAT-24 run: 465 M edges, 3.4 ms as a static sweep -- the push relax kernel at 0.21 of the HBM peak -- a quarter of the run)
-    vgl_blocked_plan *blk[2] = {nullptr, nullptr};
+    std::unique_ptr<vgl_blocked_plan> blk[2];
 };
 
 // the relax of a DENSE step as a blocked pass over a part: rows that are not scheduled load +inf and contribute nothing, every improvement
@@ -787,8 +787,13 @@ int vgl_hip_sssp_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
         const char *fm = fm0 ? fm_keep.c_str() : nullptr;
         for (int k = level >= 2 ? 0 : 1; k < 2 && want; k++) {
             if (part_edges[k] < (1LL << 20) && !(e && *e)) continue;
-            const int fuse_min = (fm && *fm) ? atoi(fm) : (part_edges[k] >= (1LL << 22) ? 16384 : 0);
-            if (vgl_blocked_plan_build(c, p->part[k], g->nrows, g->row_begin, g->V, 1, 0, p->pw[k], VGL_BLK_BITS, &p->blk[k], 32, fuse_min)) {
+            vgl_blocked_spec spec;
+            spec.gather_rows = 1;
+            spec.fuse_min_edges = (fm && *fm) ? atoi(fm) : (part_edges[k] >= (1LL << 22) ? 16384 : 0);
+            spec.keep_edge_index = 1;
+            std::shared_ptr<const vgl_blocked_layout> layout;
+            if (vgl_blocked_build(c, p->part[k], g->nrows, g->row_begin, g->V, spec, &layout) || vgl_blocked_plan_share(c, layout, &p->blk[k]) ||
+                vgl_blocked_plan_load_weights(c, *p->blk[k], p->pw[k])) {
                 vgl_hip_sssp_plan_destroy(c, p);
                 return 1;
             }
@@ -804,7 +809,6 @@ int vgl_hip_sssp_plan_destroy(vgl_hip_ctx *c, vgl_hip_sssp_plan *p)
     if (c) hipStreamSynchronize(c->stream);
     for (int k = 0; k < 2; k++) { vgl_pool_free(p->stream, p->prow[k]); vgl_pool_free(p->stream, p->padj[k]); vgl_pool_free(p->stream, p->pw[k]); hipFree(p->part[k].tile_row); }
     hipFree(p->state); hipFree(p->active); hipFree(p->vt_aux); hipFree(p->partials); hipFree(p->tickets);
-    for (int k = 0; k < 2; k++) if (p->blk[k]) vgl_blocked_plan_destroy(p->blk[k]);
     delete p;
     return 0;
 }
@@ -838,7 +842,7 @@ int vgl_hip_sssp_run_plan(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_hip_sssp_plan *p
                                g->vt_deg_off, c->d_counters, g->offs);
             if (p->blk[k]) {
                 const vgl_ds_blk_op op{d_dist, p->state, p->active, T, near_partials, g->row_begin};
-                VGL_TRY((vgl_blocked_pass<vgl_ds_blk_op, true, false>(c, p->blk[k], op, "sssp_relax", "sssp_relax", false, "sssp_relax")));
+                VGL_TRY((vgl_blocked_pass<vgl_ds_blk_op, true, false>(c, *p->blk[k]->layout, p->blk[k]->values.data(), op, "sssp_relax", "sssp_relax", "sssp_relax")));
             } else {
                 vgl_timed_launch tl(c, "sssp_relax");
                 hipLaunchKernelGGL(vgl_k_ds_relax_static, dim3((unsigned)p->part[k].ntiles), dim3(VGL_BLOCK), 0, st, p->prow[k], p->padj[k], p->pw[k],

@@ -64,15 +64,15 @@ constexpr int VGL_FBLK = 1 << VGL_FBLK_BITS;
 struct vgl_blk_fseg { int32_t ab; uint32_t chunk0, chunk1; };      // one dense pair of the unit's gather block: chunks [chunk0, chunk1)
 struct vgl_blk_funit { int32_t gb, seg0, seg1, pad; };             // a workgroup's share: segments [seg0, seg1) of gather block gb
 
-struct vgl_blocked_plan {
-    hipStream_t stream = nullptr;                // the stream whose memory pool owns the arrays below
+// One row range of a CSR direction laid out for the blocked pass: the whole direction, or (a direction with 2^32 edges or more) one of
+// its row-range PIECES of at most 2^31 edges over the same index spaces (its rows keep their global numbers)
+struct vgl_blocked_piece {
     int32_t g_count = 0, a_count = 0;            // index ranges of the gather / accumulate side
     int32_t nG = 0, nA = 0;
     int a_bits = VGL_BLK_BITS;                   // log2 of the accumulate-side block (15: 4-byte accumulators, 14: 8-byte)
     int64_t edges = 0;                           // edges kept (self loops may be dropped at build time)
     uint32_t nchunks = 0;
     uint16_t *g_lo = nullptr, *a_lo = nullptr;
-    float *w_mid = nullptr;
     uint32_t *mid_to_a = nullptr;
     uint32_t *vals = nullptr;                    // scratch: 4 bytes per entry (or 8 per chunk: value_bits = 1)
     vgl_blk_unit *g_units = nullptr, *a_units = nullptr;
@@ -80,50 +80,64 @@ struct vgl_blocked_plan {
     vgl_blk_multi *multi = nullptr;
     int n_multi = 0, n_slabs = 0;
     void *slabs = nullptr;                       // n_slabs * 128 KiB (one window of accumulators each)
-    uint8_t *g_dirty = nullptr;                  // nG: gather blocks whose x changed since the last pass (filtered passes)
-    // fused tiles (empty unless the plan was built with fuse_min_edges > 0)
+    // fused tiles (empty unless the layout was built with fuse_min_edges > 0)
     uint16_t *f_g_lo = nullptr, *f_a_lo = nullptr;
-    float *f_w = nullptr;
     vgl_blk_fseg *f_segs = nullptr;
     vgl_blk_funit *f_units = nullptr;
     int n_f_segs = 0, n_f_units = 0;
     uint32_t f_nchunks = 0;
     int64_t f_edges = 0;                         // edges laid out as fused tiles (part of `edges`)
-    // a direction with 2^32 edges or more is laid out in row-range PIECES of at most 2^31 edges, each a plan of its own over the same
-    // index spaces (its rows keep their global numbers); a pass runs the pieces one after the other (min / max-type operators only)
-    vgl_blocked_plan *next = nullptr;
-    int64_t *piece_rowptr = nullptr;             // the piece's rebased row offsets and tile table (owned; null for a whole-direction plan)
-    int32_t *piece_tile_row = nullptr;
-    // Edge values (round 5).  The STRUCTURE above depends on the graph alone; a layout that carries edge values also keeps, per slot of w_mid / f_w,
-    // the CSR position its value comes from (0xFFFFFFFF: a pad entry) -- the counterpart of the reference's edges_reorder_indexes, from which every
-    // weight layout is derived (csr_edges_array.hpp:31-40).  Loading another weights array is then one gather pass (vgl_blocked_plan_load_weights)
-    // instead of a second radix sort, and several value arrays can share one structure (vgl_blocked_plan_share).
+    // keep_edge_index: per slot of g_lo / f_g_lo the CSR position its value comes from (0xFFFFFFFF: a pad entry) -- the counterpart of the
+    // reference's edges_reorder_indexes, from which every weight layout is derived (csr_edges_array.hpp:31-40).  A plan's edge values are
+    // then one gather pass (vgl_blocked_plan_load_weights) instead of a second radix sort.
     uint32_t *w_src_mid = nullptr, *w_src_f = nullptr;
     int64_t w_base = 0;                          // CSR position of the piece's first edge (a piece indexes the direction's weights from there)
-    bool shared = false;                         // everything but w_mid / f_w / g_dirty belongs to the plan this one was shared from
-    vgl_blocked_plan *shared_from = nullptr;     // (head of a shared chain only) the structure's head
-    int sharers = 0;                             // (structure head) plans that share it; a structure destroyed while shared is freed by its last sharer
-    bool orphan = false;
+    int64_t *piece_rowptr = nullptr;             // a piece's rebased row offsets and tile table (hipMalloc; null for a whole direction)
+    int32_t *piece_tile_row = nullptr;
 };
 
-// Build the plan from one CSR direction.  gather_rows = 0: x is indexed by the adjacency ids (range `ncols`), y by the local rows;
-// gather_rows = 1: x by the local rows, y by the adjacency ids.  skip_self: edges whose adjacency id equals row_base + row are left
-// out (PageRank, pr.hpp:111).  d_weights (optional): f32 per CSR position, carried to the mid order.  Synchronises; offline cost
-// (a 3-pass radix sort of the edges), like the reference's graph import.
-// value_bits = 1: what travels is one BIT per edge (the blocked top-down BFS level): `vals` then holds one 64-bit word per chunk.
-// fuse_min_edges > 0 (4-byte accumulators and 32-bit values only): block pairs of 16384 x 16384 ids with at least that many edges become
-// fused tiles.
-int vgl_blocked_plan_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                           int skip_self, const float *d_weights, int a_bits, vgl_blocked_plan **out, int value_bits = 32, int fuse_min_edges = 0);
-// keep_edge_index != 0 (implied by d_weights): the layout keeps the CSR position behind every value slot, see vgl_blocked_plan::w_src_mid
-int vgl_blocked_plan_build_indexed(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, int gather_rows,
-                                   int skip_self, int a_bits, vgl_blocked_plan **out, int fuse_min_edges);
-// (re)fills the value arrays of a layout that keeps its edge index from d_weights (f32 per CSR position of the direction): one gather pass
-int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan *p, const float *d_weights);
-// a second set of value arrays over the structure of `structure` (which must outlive the result and keep its edge index)
-int vgl_blocked_plan_share(vgl_hip_ctx *c, const vgl_blocked_plan *structure, vgl_blocked_plan **out);
-void vgl_blocked_plan_destroy(vgl_blocked_plan *p);
-static inline int64_t vgl_blocked_plan_edges(const vgl_blocked_plan *p) { int64_t e = 0; for (; p; p = p->next) e += p->edges; return e; }
+// The layout of one CSR direction: everything that depends on the graph alone.  Immutable once built; the graph handle and every plan over
+// it hold it by std::shared_ptr, and the last of them frees it.  Plans that share a layout also share its `vals` and `slabs` scratch, so
+// their passes must be ordered on one stream.
+struct vgl_blocked_layout {
+    hipStream_t stream = nullptr;                // the stream whose memory pool owns the arrays of the pieces
+    std::vector<vgl_blocked_piece> pieces;       // a pass runs them one after the other (several: min / max-type operators only)
+    int64_t edges() const { int64_t e = 0; for (const vgl_blocked_piece &p : pieces) e += p.edges; return e; }
+    vgl_blocked_layout() = default;
+    vgl_blocked_layout(const vgl_blocked_layout &) = delete;
+    vgl_blocked_layout &operator=(const vgl_blocked_layout &) = delete;
+    ~vgl_blocked_layout();
+};
+
+// A plan: a layout plus one set of edge values (f32 per slot of g_lo / f_g_lo) per piece
+struct vgl_blocked_values { float *w_mid = nullptr, *f_w = nullptr; };
+struct vgl_blocked_plan {
+    std::shared_ptr<const vgl_blocked_layout> layout;
+    hipStream_t stream = nullptr;                // the stream whose memory pool owns the value arrays
+    std::vector<vgl_blocked_values> values;      // one per piece of the layout
+    vgl_blocked_plan() = default;
+    vgl_blocked_plan(const vgl_blocked_plan &) = delete;
+    vgl_blocked_plan &operator=(const vgl_blocked_plan &) = delete;
+    ~vgl_blocked_plan();
+};
+
+struct vgl_blocked_spec {
+    int gather_rows = 0;                         // 0: x is indexed by the adjacency ids (range `ncols`), y by the local rows; 1: x by the rows, y by the ids
+    int skip_self = 0;                           // edges whose adjacency id equals row_base + row are left out (PageRank, pr.hpp:111)
+    int a_bits = VGL_BLK_BITS;                   // accumulate blocks of 2^15 (4-byte accumulators) or 2^14 (8-byte) ids
+    int value_bits = 32;                         // 1: what travels is one BIT per edge (the blocked top-down BFS level): `vals` holds one 64-bit word per chunk
+    int fuse_min_edges = 0;                      // > 0 (4-byte accumulators and 32-bit values only): block pairs of 16384 x 16384 ids with at least that
+                                                 // many edges become fused tiles
+    int keep_edge_index = 0;                     // keep the CSR position behind every value slot (w_src_mid / w_src_f): needed by plans with edge values
+};
+
+// Lay out one CSR direction.  Synchronises; offline cost (a 3-pass radix sort of the edges), like the reference's graph import.
+int vgl_blocked_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int32_t row_base, int32_t ncols, const vgl_blocked_spec &spec,
+                      std::shared_ptr<const vgl_blocked_layout> *out);
+// a plan over an existing layout (built with keep_edge_index) with value arrays of its own, to be filled by vgl_blocked_plan_load_weights
+int vgl_blocked_plan_share(vgl_hip_ctx *c, std::shared_ptr<const vgl_blocked_layout> layout, std::unique_ptr<vgl_blocked_plan> *out);
+// (re)fills the plan's value arrays from d_weights (f32 per CSR position of the direction): one gather pass
+int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan &p, const float *d_weights);
 
 #ifdef __HIPCC__
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -142,12 +156,10 @@ static inline int64_t vgl_blocked_plan_edges(const vgl_blocked_plan *p) { int64_
 // ---------------------------------------------------------------------------------------------------------------------------
 template <class OP, bool WEIGHTED>
 __global__ __launch_bounds__(VGL_BTHREADS) void vgl_k_blk_gather(const vgl_blk_unit *units, const uint16_t *g_lo, const float *w_mid,
-                                                                 const uint32_t *mid_to_a, uint32_t *vals, int32_t g_count,
-                                                                 const uint8_t *g_dirty, OP op)
+                                                                 const uint32_t *mid_to_a, uint32_t *vals, int32_t g_count, OP op)
 {
     __shared__ uint32_t s_x[VGL_BLK];
     const vgl_blk_unit u = units[blockIdx.x];
-    if (g_dirty && !g_dirty[u.block]) return;                       // nothing in this block changed: its values in `vals` still stand
     const int32_t base = u.block << VGL_BLK_BITS;
     const int n = min(VGL_BLK, g_count - base);
     for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) s_x[i] = op.load(base + i);
@@ -304,47 +316,45 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_blk_finish_slabs(const vgl_bl
     }
 }
 
-// one blocked pass: gather kernel, accumulate kernel and (sum-type operators) the slab epilogue, enqueued on the context stream
+// one blocked pass: per piece the gather kernel, the accumulate kernel, the fused tiles and (sum-type operators) the slab epilogue, enqueued on
+// the context stream.  values: the plan's arrays, one per piece (WEIGHTED), else null.
 template <class OP, bool WEIGHTED, bool SLABS>
-static inline int vgl_blocked_pass_one(vgl_hip_ctx *c, const vgl_blocked_plan *p, const OP &op, const char *gather_name, const char *accum_name,
-                                       bool filtered, const char *fused_name)
+static inline int vgl_blocked_pass(vgl_hip_ctx *c, const vgl_blocked_layout &L, const vgl_blocked_values *values, const OP &op, const char *gather_name,
+                                   const char *accum_name, const char *fused_name = nullptr)
 {
-    if (p->n_g_units > 0) {
-        vgl_timed_launch tl(c, gather_name);
-        hipLaunchKernelGGL((vgl_k_blk_gather<OP, WEIGHTED>), dim3((unsigned)p->n_g_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->g_units,
-                           (const uint16_t *)p->g_lo, (const float *)p->w_mid, (const uint32_t *)p->mid_to_a, p->vals, p->g_count,
-                           (const uint8_t *)(filtered ? p->g_dirty : nullptr), op);
-    }
-    if (p->a_bits != (sizeof(typename OP::acc_t) == 8 ? VGL_BLK_BITS - 1 : VGL_BLK_BITS)) VGL_FAIL("blocked pass: the plan's accumulate blocks do not fit the operator's accumulators");
-    if (p->n_a_units > 0) {
-        vgl_timed_launch tl(c, accum_name);
-        hipLaunchKernelGGL((vgl_k_blk_accumulate<OP>), dim3((unsigned)p->n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->a_units,
-                           (const uint16_t *)p->a_lo, (const uint32_t *)p->vals, p->a_count, (typename OP::acc_t *)p->slabs, op);
-    }
-    if (p->n_f_units > 0) {
-        // after the two-pass part: the fused tiles load their x windows now, so they already see what the accumulate kernel just improved
-        // (any order of relaxations reaches the same fixed point; a later read only helps)
-        if constexpr (SLABS) VGL_FAIL("blocked pass: fused tiles are for min / max-type operators");
-        else {
-            vgl_timed_launch tl(c, fused_name ? fused_name : accum_name);
-            hipLaunchKernelGGL((vgl_k_blk_fused<OP, WEIGHTED>), dim3((unsigned)p->n_f_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_funit *)p->f_units,
-                               (const vgl_blk_fseg *)p->f_segs, (const uint16_t *)p->f_g_lo, (const uint16_t *)p->f_a_lo, (const float *)p->f_w, p->g_count, p->a_count, op);
+    if (SLABS && L.pieces.size() > 1) VGL_FAIL("blocked pass: a plan in several pieces needs a min / max-type operator");
+    if (WEIGHTED && !values) VGL_FAIL("blocked pass: the plan has no edge values");
+    for (size_t k = 0; k < L.pieces.size(); k++) {
+        const vgl_blocked_piece *p = &L.pieces[k];
+        const float *w_mid = WEIGHTED ? values[k].w_mid : nullptr, *f_w = WEIGHTED ? values[k].f_w : nullptr;
+        if (p->n_g_units > 0) {
+            vgl_timed_launch tl(c, gather_name);
+            hipLaunchKernelGGL((vgl_k_blk_gather<OP, WEIGHTED>), dim3((unsigned)p->n_g_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->g_units,
+                               (const uint16_t *)p->g_lo, w_mid, (const uint32_t *)p->mid_to_a, p->vals, p->g_count, op);
         }
+        if (p->a_bits != (sizeof(typename OP::acc_t) == 8 ? VGL_BLK_BITS - 1 : VGL_BLK_BITS)) VGL_FAIL("blocked pass: the plan's accumulate blocks do not fit the operator's accumulators");
+        if (p->n_a_units > 0) {
+            vgl_timed_launch tl(c, accum_name);
+            hipLaunchKernelGGL((vgl_k_blk_accumulate<OP>), dim3((unsigned)p->n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->a_units,
+                               (const uint16_t *)p->a_lo, (const uint32_t *)p->vals, p->a_count, (typename OP::acc_t *)p->slabs, op);
+        }
+        if (p->n_f_units > 0) {
+            // after the two-pass part: the fused tiles load their x windows now, so they already see what the accumulate kernel just improved
+            // (any order of relaxations reaches the same fixed point; a later read only helps)
+            if constexpr (SLABS) VGL_FAIL("blocked pass: fused tiles are for min / max-type operators");
+            else {
+                vgl_timed_launch tl(c, fused_name ? fused_name : accum_name);
+                hipLaunchKernelGGL((vgl_k_blk_fused<OP, WEIGHTED>), dim3((unsigned)p->n_f_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_funit *)p->f_units,
+                                   (const vgl_blk_fseg *)p->f_segs, (const uint16_t *)p->f_g_lo, (const uint16_t *)p->f_a_lo, f_w, p->g_count, p->a_count, op);
+            }
+        }
+        if constexpr (SLABS) {
+            if (p->n_multi > 0)
+                hipLaunchKernelGGL((vgl_k_blk_finish_slabs<OP>), dim3((unsigned)p->n_multi, 16), dim3(VGL_BLOCK), 0, c->stream, (const vgl_blk_multi *)p->multi,
+                                   (const typename OP::acc_t *)p->slabs, p->a_count, op);
+        }
+        VGL_HIP_TRY(hipGetLastError());
     }
-    if constexpr (SLABS) {
-        if (p->n_multi > 0)
-            hipLaunchKernelGGL((vgl_k_blk_finish_slabs<OP>), dim3((unsigned)p->n_multi, 16), dim3(VGL_BLOCK), 0, c->stream, (const vgl_blk_multi *)p->multi,
-                               (const typename OP::acc_t *)p->slabs, p->a_count, op);
-    }
-    VGL_HIP_TRY(hipGetLastError());
-    return 0;
-}
-template <class OP, bool WEIGHTED, bool SLABS>
-static inline int vgl_blocked_pass(vgl_hip_ctx *c, const vgl_blocked_plan *p, const OP &op, const char *gather_name, const char *accum_name,
-                                   bool filtered = false, const char *fused_name = nullptr)
-{
-    if (SLABS && p->next) VGL_FAIL("blocked pass: a plan in several pieces needs a min / max-type operator");
-    for (const vgl_blocked_plan *q = p; q; q = q->next) VGL_TRY((vgl_blocked_pass_one<OP, WEIGHTED, SLABS>(c, q, op, gather_name, accum_name, filtered, fused_name)));
     return 0;
 }
 #endif  // __HIPCC__

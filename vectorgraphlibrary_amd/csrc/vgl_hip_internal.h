@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <string>
 #include <map>
+#include <memory>
 #include <vector>
 #include "../../include/vgl_hip.h"
 
@@ -139,11 +140,12 @@ struct vgl_hip_graph {
     uint8_t *ds_tile_active = nullptr;   // delta-stepping SSSP: one byte per out-edge tile (lazy)
     vgl_hip_graph *transposed = nullptr; // SCC: handle with the two directions swapped (backward reach = BFS on it), lazy, owned
     int64_t *ds_partials = nullptr;
-    struct vgl_blocked_plan *blk_pr = nullptr;  // PageRank's blocked pull over the outgoing CSR (lazy, owned; vgl_blocked.h)
-    struct vgl_blocked_plan *blk_cc = nullptr;  // the Shiloach-Vishkin hook as a blocked pass (lazy, owned)
-    struct vgl_blocked_plan *blk_bfs = nullptr; // the large top-down BFS levels as a blocked pass (vgl_hip_bfs_prepare_blocked, owned)
-    struct vgl_blocked_plan *blk_path = nullptr; // STRUCTURE of the path layouts (Bellman-Ford / widest-path pull: rows gather, edge values; lazy, owned): built once
-                                                 // per graph, every vgl_hip_sssp_pull_plan shares it and loads its own weights with one gather pass
+    // blocked layouts (vgl_blocked.h): lazy, shared with the plans built over them -- the graph drops its reference, the last holder frees
+    std::shared_ptr<const struct vgl_blocked_layout> blk_pr;    // PageRank's blocked pull over the outgoing CSR
+    std::shared_ptr<const struct vgl_blocked_layout> blk_cc;    // the Shiloach-Vishkin hook as a blocked pass
+    std::shared_ptr<const struct vgl_blocked_layout> blk_bfs;   // the large top-down BFS levels as a blocked pass (vgl_hip_bfs_prepare_blocked)
+    std::shared_ptr<const struct vgl_blocked_layout> blk_path;  // the path layouts (Bellman-Ford / widest-path pull: rows gather, edge index kept): built
+                                                                // once per graph, every vgl_hip_sssp_pull_plan is a plan over it with weights of its own
     std::string blk_path_key;                    // the layout switches it was built under (fuse threshold, unit sizes, piece bound: the tests vary them per plan)
 };
 
