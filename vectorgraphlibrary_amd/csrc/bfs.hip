@@ -8,18 +8,16 @@
 // Kernels and what bounds them (all HBM/L2-latency bound gathers, no MFMA):
 //   gnf count/scan/write (vgl_gnf.h)   : V*4 B streamed per pass
 //   vgl_k_td_expand                    : per examined edge 4 B adjacency (coalesced) + bitmap probe (L2) [+4 B levels]
-//   vgl_k_bu_probe / vgl_k_bu_heavy    : per unvisited vertex 16 B row offsets + up to 8 adjacency probes (thread-serial),
-//                                        remaining long rows strip-mined 64-wide by one wavefront per vertex
+//   vgl_k_bu_probe                     : per unvisited vertex 16 B row offsets + up to 8 adjacency probes (thread-serial),
+//                                        remaining long rows strip-mined 16 lanes per vertex by the same workgroup
 #include "vgl_hip_internal.h"
 #include <chrono>
 #include "vgl_gnf.h"
 #include "vgl_blocked.h"
 
 #ifndef VGL_BU_HEAVY_LANES
-#define VGL_BU_HEAVY_LANES 16       // lanes per deferred vertex in the second bottom-up pass
-#endif       // thread-serial probes before a vertex is deferred to the wavefront pass
-constexpr int VGL_DO_ALPHA = 15;       // change_state.hpp:5
-constexpr int VGL_DO_BETA = 18;        // change_state.hpp:6
+#define VGL_BU_HEAVY_LANES 16       // lanes per deferred vertex in the bottom-up step's scan of the long rows
+#endif
 
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init(int32_t V, int32_t source, int32_t *levels)
 {
@@ -341,7 +339,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bm_gnf_count(int64_t nwords, 
         // level bottom-up, nobody needs the rows' degrees or the compaction offsets: only the bitmaps move on (what vgl_k_bm_advance
         // does) and the first workgroup hands F and M over at once.
         const int64_t nf = counters[C_NEXT_F], nm = counters[C_NEXT_M];
-        if (nf > hint.prev_f && nm >= ((hint.V - hint.visited_total - nf) * hint.factor + hint.V) / VGL_DO_ALPHA) {
+        if (vgl_do_turn_bottom_up(nf, nm, hint.prev_f, hint.visited_total + nf, hint.V, hint.factor)) {
             if (wi < nwords) {
                 const uint64_t w = next[word0 + wi];
                 front[word0 + wi] = w;
@@ -743,11 +741,11 @@ __global__ __launch_bounds__(VGL_SMALL_THREADS) void vgl_k_bfs_small_levels(int3
 
 // Bottom-up step.  No global atomics: a single same-address device atomic costs ~12 ns and serialises (65 536 blocks
 // adding to one counter took 1.5 ms per launch in the first version); instead a fixed grid of VGL_BU_BLOCKS persistent
-// workgroups each owns a contiguous vertex range, a private segment of the deferred-vertex list and a private slot of
-// partial counters, which the last workgroup of the second pass sums in a fixed order.
+// workgroups each owns a share of the vertex groups, a private segment of the deferred-vertex list and a private slot of
+// partial counters, which the last workgroup sums in a fixed order.
 constexpr int VGL_BU_BLOCKS = 2048;
 
-// pass 1: one thread per owned vertex.  A vertex is a candidate when it is unvisited AND has incoming edges (in_nz
+// One thread per owned vertex.  A vertex is a candidate when it is unvisited AND has incoming edges (in_nz
 // bitmap, built once per graph: ~45 % of RMAT vertices have none and would otherwise re-read 16 B of row offsets in every
 // bottom-up level).  The first VGL_BU_PROBES incoming neighbours are loaded together and their frontier bits tested
 // together (two dependent memory round trips per vertex).  Writes whole words of the next-frontier bitmap.
@@ -788,18 +786,19 @@ typedef int vgl_int4_u __attribute__((ext_vector_type(4), aligned(4)));     // 1
 // switch rule, speculative launches of the next levels return at once when it says stop; one host wait per chain): 0.394 ms per
 // traversal with three levels per wait against 0.389 with one -- the polled hand-over costs less than the extra launches.
 // INLINE_HEAVY (round 3): the rows a workgroup defers are scanned by the same workgroup right after its probe loop, 16 lanes per row, and
-// the last workgroup folds the counters and hands them to the host -- no second launch (vgl_k_bu_heavy: ~15 us per level even when it has
-// nothing to scan, three levels per traversal).  The 64-row groups are dealt round-robin to the wavefronts of the grid, so the deferred
-// rows -- the hubs, i.e. the first ids of a degree-sorted graph -- are spread over all workgroups by construction; the balanced second
-// pass dates from the time of contiguous chunks.  VGL_BU_SPLIT=1 keeps the two-launch form.
+// the last workgroup folds the counters and hands them to the host -- no second launch (the separate balanced pass over all deferred rows
+// cost ~15 us per level even when it had nothing to scan, three levels per traversal; it dates from the time of contiguous chunks and was
+// removed).  The 64-row groups are dealt round-robin to the wavefronts of the grid, so the deferred rows -- the hubs, i.e. the first ids of a
+// degree-sorted graph -- are spread over all workgroups by construction.  (Only <true> exists; the template keeps the kernel's name.)
 template <bool INLINE_HEAVY>
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32_t row_base, int32_t chunk, const int64_t *in_rowptr,
-                                                            const int32_t *in_adj, int64_t in_edges, const uint64_t *visited, const uint64_t *in_nz,
-                                                            const uint64_t *front, uint64_t *next, int32_t *levels,
-                                                            int32_t next_level, int32_t *heavy, int32_t *heavy_cnt, int64_t *partials,
-                                                            int32_t *heavy_off, uint32_t *ticket, const int4 *in_head, const uint64_t *in_long,
-                                                            int64_t *counters, volatile int64_t *host, int64_t seq, const int32_t *nz_rank, int32_t nz_rows)
+                                                            const int32_t *in_adj, const uint64_t *visited, const uint64_t *in_nz,
+                                                            const uint64_t *front, uint64_t *next, int32_t *levels, int32_t next_level,
+                                                            int32_t *heavy, int64_t *partials, uint32_t *ticket, const int4 *in_head,
+                                                            const uint64_t *in_long, const int32_t *nz_rank, int32_t nz_rows, int64_t *counters,
+                                                            volatile int64_t *host, int64_t seq)
 {
+    static_assert(INLINE_HEAVY, "the deferred rows are scanned in the same launch");
     __shared__ int64_t s64[VGL_WAVES];
     __shared__ int s_nheavy;
     if (threadIdx.x == 0) s_nheavy = 0;
@@ -885,107 +884,16 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32
             }
         }
     }
-    if (INLINE_HEAVY) {
-        __syncthreads();                                    // the workgroup's deferred list is complete (and its stores to `next` have landed)
-        const int nh = s_nheavy;
-        constexpr int G = VGL_BU_HEAVY_LANES, NG = 64 / G;  // lanes per deferred row, rows per wavefront
-        const int quarter = lane / G, ql = lane % G;
-        for (int h0 = vgl_wave() * NG; h0 < nh; h0 += VGL_WAVES * NG) {
-            const int h = h0 + quarter;
-            bool done = h >= nh, hit_any = false;
-            int32_t r = 0;
-            int64_t p = 0, e = 0;
-            if (!done) { r = my_heavy[h]; p = in_rowptr[r]; e = in_rowptr[r + 1]; }     // the whole row: its head records are a selection, not a prefix
-            while (!__all(done)) {
-                const int64_t q = p + ql;
-                bool hit = false;
-                if (!done && q < e) { const int32_t u = in_adj[q]; hit = (front[u >> 6] >> (u & 63)) & 1ULL; }
-                const unsigned long long hm = __ballot(hit);
-                const unsigned qm = (unsigned)(hm >> (quarter * G)) & (G >= 32 ? 0xFFFFFFFFu : ((1u << (G & 31)) - 1u));
-                if (!done) {
-                    if (qm) { hit_any = true; done = true; if (ql == 0) probes += __ffs(qm); }
-                    else { if (ql == 0) probes += min((int64_t)G, e - p); p += G; if (p >= e) done = true; }
-                }
-            }
-            if (hit_any && ql == 0) {
-                const int32_t v = row_base + r;
-                levels[v] = next_level;
-                atomicOr((unsigned long long *)&next[v >> 6], 1ULL << (v & 63));
-                found_cnt++;
-            }
-        }
-        found_cnt = vgl_block_reduce_add(found_cnt, s64);
-        probes = vgl_block_reduce_add(probes, s64);
-        uint32_t dep2 = 0;
-        if (threadIdx.x == 0) dep2 = vgl_put_agent(partials + blockIdx.x * 4 + 0, found_cnt) ^ vgl_put_agent(partials + blockIdx.x * 4 + 1, probes);
-        if (!vgl_last_block(ticket, dep2)) return;
-        int64_t f = 0, pr = 0;
-        for (int b = threadIdx.x; b < (int)gridDim.x; b += VGL_BLOCK) { f += vgl_load_agent(partials + b * 4 + 0); pr += vgl_load_agent(partials + b * 4 + 1); }
-        f = vgl_block_reduce_add(f, s64);
-        pr = vgl_block_reduce_add(pr, s64);
-        if (threadIdx.x == 0) {
-            if (host) vgl_publish2(counters, host, seq, C_BU_FOUND, f, C_BU_EDGES, pr);
-            else { counters[C_BU_FOUND] = f; counters[C_BU_EDGES] = pr; }
-        }
-        return;
-    }
-    found_cnt = vgl_block_reduce_add(found_cnt, s64);
-    probes = vgl_block_reduce_add(probes, s64);
-    uint32_t dep = 0;
-    if (threadIdx.x == 0) {
-        partials[blockIdx.x * 4 + 0] = found_cnt;
-        partials[blockIdx.x * 4 + 1] = probes;
-        dep = vgl_put_agent(heavy_cnt + blockIdx.x, (int32_t)s_nheavy);
-    }
-    // last workgroup: exclusive prefix of the per-workgroup deferred counts (VGL_BU_BLOCKS entries -> VGL_BU_BLOCKS+1 offsets)
-    if (!vgl_last_block(ticket, dep)) return;
-    __shared__ int s32[VGL_WAVES];
-    constexpr int PER = VGL_BU_BLOCKS / VGL_BLOCK;
-    int local[PER], sum = 0;
-#pragma unroll
-    for (int j = 0; j < PER; j++) { local[j] = vgl_load_agent(heavy_cnt + threadIdx.x * PER + j); sum += local[j]; }
-    int total;
-    int pre = vgl_block_excl_add(sum, s32, &total);
-#pragma unroll
-    for (int j = 0; j < PER; j++) { heavy_off[threadIdx.x * PER + j] = pre; pre += local[j]; }
-    if (threadIdx.x == 0) heavy_off[VGL_BU_BLOCKS] = total;
-}
-
-// pass 2: all deferred vertices, a quarter wavefront per vertex, 16 incoming neighbours per step, early exit on the first hit.
-// The deferred lists are per-workgroup segments (pass 1); wavefronts stride over the CONCATENATION of the segments so the
-// work is balanced even when the deferred vertices cluster (in a degree-sorted graph they are the first ids).
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_heavy(int32_t row_base, int32_t chunk, const int64_t *in_rowptr,
-                                                            const int32_t *in_adj, const uint64_t *front, uint64_t *next,
-                                                            int32_t *levels, int32_t next_level, const int32_t *heavy,
-                                                            const int32_t *heavy_off, int64_t *partials, int64_t *counters, uint32_t *ticket,
-                                                            volatile int64_t *host, int64_t seq)
-{
-    __shared__ int64_t s64[VGL_WAVES];
-    __shared__ int s_off[VGL_BU_BLOCKS + 1];
-    // most levels defer a few hundred rows or none: only the workgroups that will scan rows stage the 8 KiB offset table (every one of
-    // the 2048 doing it made an empty pass cost 11 us)
-    const int total = heavy_off[VGL_BU_BLOCKS];
-    if ((int64_t)blockIdx.x * VGL_WAVES * (64 / VGL_BU_HEAVY_LANES) < total) {
-        for (int i = threadIdx.x; i <= VGL_BU_BLOCKS; i += VGL_BLOCK) s_off[i] = heavy_off[i];
-    }
-    __syncthreads();
-    int64_t found_cnt = 0, probes = 0;
-    // Four deferred vertices per wavefront, 16 lanes each: most deferred rows have a few dozen entries left, a whole wavefront per
-    // row left three quarters of the lanes idle.  A quarter scans 16 entries per step and stops at its first hit; the wavefront
-    // moves on when all four are done.
-    constexpr int G = VGL_BU_HEAVY_LANES, NG = 64 / G;       // lanes per vertex, vertices per wavefront
-    const int quarter = vgl_lane() / G, ql = vgl_lane() % G;
-    for (int h0 = (blockIdx.x * VGL_WAVES + vgl_wave()) * NG; h0 < total; h0 += gridDim.x * VGL_WAVES * NG) {
+    __syncthreads();                                    // the workgroup's deferred list is complete (and its stores to `next` have landed)
+    const int nh = s_nheavy;
+    constexpr int G = VGL_BU_HEAVY_LANES, NG = 64 / G;  // lanes per deferred row, rows per wavefront
+    const int quarter = lane / G, ql = lane % G;
+    for (int h0 = vgl_wave() * NG; h0 < nh; h0 += VGL_WAVES * NG) {
         const int h = h0 + quarter;
-        bool done = h >= total, hit_any = false;
+        bool done = h >= nh, hit_any = false;
         int32_t r = 0;
         int64_t p = 0, e = 0;
-        if (!done) {
-            int lo = 0, hi = VGL_BU_BLOCKS;                 // segment s with s_off[s] <= h < s_off[s+1]
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_off[mid] <= h) lo = mid; else hi = mid; }
-            r = heavy[(int64_t)lo * chunk + (h - s_off[lo])];
-            p = in_rowptr[r]; e = in_rowptr[r + 1];             // the whole row: its head records are a selection (the smallest ids), not a prefix
-        }
+        if (!done) { r = my_heavy[h]; p = in_rowptr[r]; e = in_rowptr[r + 1]; }     // the whole row: its head records are a selection, not a prefix
         while (!__all(done)) {
             const int64_t q = p + ql;
             bool hit = false;
@@ -1007,21 +915,15 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_heavy(int32_t row_base, in
     found_cnt = vgl_block_reduce_add(found_cnt, s64);
     probes = vgl_block_reduce_add(probes, s64);
     uint32_t dep = 0;
-    if (threadIdx.x == 0) dep = vgl_put_agent(partials + blockIdx.x * 4 + 2, found_cnt) ^ vgl_put_agent(partials + blockIdx.x * 4 + 3, probes);
-    // last workgroup: counters[C_BU_FOUND] / [C_BU_EDGES] = sums of the per-workgroup partials of both passes in a fixed order,
-    // handed to the host (when it listens: host != nullptr)
+    if (threadIdx.x == 0) dep = vgl_put_agent(partials + blockIdx.x * 4 + 0, found_cnt) ^ vgl_put_agent(partials + blockIdx.x * 4 + 1, probes);
     if (!vgl_last_block(ticket, dep)) return;
-    int64_t f = 0, p = 0;
-    for (int b = threadIdx.x; b < VGL_BU_BLOCKS; b += VGL_BLOCK) {      // (this pass may run with fewer workgroups than the probe pass)
-        f += partials[b * 4 + 0];
-        p += partials[b * 4 + 1];
-        if (b < (int)gridDim.x) { f += vgl_load_agent(partials + b * 4 + 2); p += vgl_load_agent(partials + b * 4 + 3); }
-    }
+    int64_t f = 0, pr = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += VGL_BLOCK) { f += vgl_load_agent(partials + b * 4 + 0); pr += vgl_load_agent(partials + b * 4 + 1); }
     f = vgl_block_reduce_add(f, s64);
-    p = vgl_block_reduce_add(p, s64);
+    pr = vgl_block_reduce_add(pr, s64);
     if (threadIdx.x == 0) {
-        if (host) vgl_publish2(counters, host, seq, C_BU_FOUND, f, C_BU_EDGES, p);
-        else { counters[C_BU_FOUND] = f; counters[C_BU_EDGES] = p; }
+        if (host) vgl_publish2(counters, host, seq, C_BU_FOUND, f, C_BU_EDGES, pr);
+        else { counters[C_BU_FOUND] = f; counters[C_BU_EDGES] = pr; }
     }
 }
 
@@ -1185,6 +1087,18 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_apply_fold(int n, const int64
 
 static inline unsigned vgl_grid(int64_t n, int64_t cap = 8192) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(n, VGL_BLOCK))); }
 
+// vgl_k_td_expand<EMIT, COUNT, filter> over the frontier ids / offs (F vertices, M edges, tile_first ready); a counting launch leaves F and M of
+// the next frontier in the device counters
+template <bool EMIT, bool COUNT>
+static void vgl_td_expand_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_t M, const uint64_t *visited, int32_t *levels,
+                                 int32_t next_level, uint64_t *next, bool filter = true)
+{
+    const auto kernel = filter ? vgl_k_td_expand<EMIT, COUNT, true> : vgl_k_td_expand<EMIT, COUNT, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)vgl_ceil_div(M, VGL_TILE)), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs, g->tile_first, F, M,
+                       g->out.rowptr, g->out.adj, g->row_begin, visited, levels, next_level, next, COUNT ? g->bu_partials : (int64_t *)nullptr,
+                       COUNT ? g->tickets + 3 * VGL_TICKET_WORDS : (uint32_t *)nullptr, COUNT ? c->d_counters : (int64_t *)nullptr);
+}
+
 // expand frontier (ids/offs with F vertices, M edges already produced by a frontier-generation write pass)
 constexpr int64_t VGL_TD_COUNT_TILES = 8192;           // (the counting level's partial sums live in g->bu_partials: 4 * 4096 slots)
 static int vgl_bfs_td_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_t M, int32_t *levels, int32_t next_level, bool emit,
@@ -1192,26 +1106,11 @@ static int vgl_bfs_td_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_
 {
     if (F <= 0 || M <= 0) return 0;
     if (!have_tile_first) hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F)), dim3(VGL_BLOCK), 0, c->stream, F, g->offs, g->tile_first);
-    const int64_t nt = vgl_ceil_div(M, VGL_TILE);
     {
         vgl_timed_launch tl(c, "bfs_top_down");
-        int64_t *no_i64 = nullptr;
-        uint32_t *no_u32 = nullptr;
-#define VGL_TD_LAUNCH(E, C, F, PARTIALS, TICKET, COUNTERS)                                                                                          \
-        hipLaunchKernelGGL((vgl_k_td_expand<E, C, F>), dim3((unsigned)nt), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs, g->tile_first, F_, M, \
-                           g->out.rowptr, g->out.adj, g->row_begin, g->bm_visited, levels, next_level, g->bm_next, PARTIALS, TICKET, COUNTERS)
-        const int32_t F_ = F;
-        if (emit && count) {
-            if (filter) VGL_TD_LAUNCH(true, true, true, g->bu_partials, g->tickets + 3 * VGL_TICKET_WORDS, c->d_counters);
-            else VGL_TD_LAUNCH(true, true, false, g->bu_partials, g->tickets + 3 * VGL_TICKET_WORDS, c->d_counters);
-        } else if (emit) {
-            if (filter) VGL_TD_LAUNCH(true, false, true, no_i64, no_u32, no_i64);
-            else VGL_TD_LAUNCH(true, false, false, no_i64, no_u32, no_i64);
-        } else {
-            if (filter) VGL_TD_LAUNCH(false, false, true, no_i64, no_u32, no_i64);
-            else VGL_TD_LAUNCH(false, false, false, no_i64, no_u32, no_i64);
-        }
-#undef VGL_TD_LAUNCH
+        if (emit && count) vgl_td_expand_launch<true, true>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
+        else if (emit) vgl_td_expand_launch<true, false>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
+        else vgl_td_expand_launch<false, false>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;
@@ -1253,39 +1152,19 @@ int vgl_bfs_bm_gnf(vgl_hip_ctx *c, vgl_hip_graph *g, const uint64_t *front, bool
     return 0;
 }
 
-// one bottom-up step over the owned rows: probe (+ deferred-list offsets) and the balanced heavy pass (+ fold of the counters
-// C_BU_FOUND / C_BU_EDGES, published to the host under sequence number *seq_out: vgl_wait_counters when they are needed)
-// heavy_blocks: workgroups of the deferred pass.  A bottom-up phase defers rows on its first level (when the frontier is still small
-// against the unvisited rows); on the levels after it the pass finds nothing to do in almost every launch and costs what its launch
-// costs -- 9 us with 2048 workgroups, so those levels run it with a small grid (correct for any number of deferred rows, only slower).
+// one bottom-up step over the owned rows, deferred long rows included, with the fold of the counters C_BU_FOUND / C_BU_EDGES (published
+// to the host under sequence number *seq_out: vgl_wait_counters when they are needed)
 static int vgl_bfs_bu_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, int32_t next_level, const uint64_t *visited,
-                             const uint64_t *front, uint64_t *next, int64_t *seq_out, int heavy_blocks = VGL_BU_BLOCKS)
+                             const uint64_t *front, uint64_t *next, int64_t *seq_out)
 {
     const int32_t chunk = (int32_t)(vgl_ceil_div(vgl_ceil_div(g->nrows, VGL_BU_BLOCKS), VGL_BLOCK) * VGL_BLOCK);
-    const bool split = c->bfs.bu_split;
     const int64_t seq = vgl_next_seq(c);
-    if (!split) {
+    {
         vgl_timed_launch tl(c, "bfs_bottom_up");
         hipLaunchKernelGGL(vgl_k_bu_probe<true>, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
-                           g->in.rowptr, g->in.adj, g->in.edges, visited, g->bm_in_nz, front, next, levels, next_level,
-                           g->heavy, g->heavy_cnt, g->bu_partials, g->heavy_off, g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head), g->bm_in_long,
-                           c->d_counters, (volatile int64_t *)c->h_counters, seq, (const int32_t *)g->in_nz_rank, g->in_nz_rows);
-        VGL_HIP_TRY(hipGetLastError());
-        if (seq_out) *seq_out = seq;
-        return 0;
-    }
-    {
-        vgl_timed_launch tl(c, "bfs_bottom_up");
-        hipLaunchKernelGGL(vgl_k_bu_probe<false>, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
-                           g->in.rowptr, g->in.adj, g->in.edges, visited, g->bm_in_nz, front, next, levels, next_level,
-                           g->heavy, g->heavy_cnt, g->bu_partials, g->heavy_off, g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head), g->bm_in_long,
-                           c->d_counters, (volatile int64_t *)c->h_counters, seq, (const int32_t *)g->in_nz_rank, g->in_nz_rows);
-    }
-    {
-        vgl_timed_launch tl(c, "bfs_bottom_up_heavy");
-        hipLaunchKernelGGL(vgl_k_bu_heavy, dim3((unsigned)heavy_blocks), dim3(VGL_BLOCK), 0, c->stream, g->row_begin, chunk, g->in.rowptr,
-                           g->in.adj, front, next, levels, next_level, g->heavy, g->heavy_off, g->bu_partials, c->d_counters, g->tickets + 2 * VGL_TICKET_WORDS,
-                           (volatile int64_t *)c->h_counters, seq);
+                           g->in.rowptr, g->in.adj, visited, g->bm_in_nz, front, next, levels, next_level, g->heavy, g->bu_partials,
+                           g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head), g->bm_in_long,
+                           (const int32_t *)g->in_nz_rank, g->in_nz_rows, c->d_counters, (volatile int64_t *)c->h_counters, seq);
     }
     VGL_HIP_TRY(hipGetLastError());
     if (seq_out) *seq_out = seq;
@@ -1339,6 +1218,327 @@ int vgl_bitmap_to_ids(vgl_hip_ctx *c, int64_t words, const uint64_t *d_bits, int
     return 0;
 }
 
+// ---- the fused traversal (vgl_hip_bfs_run) ----
+// An emitting top-down level pays one device-scope atomicOr per discovery, a plain one a scan of `levels` (V * 4 bytes) by the next frontier
+// generation: the bitmap pays only while the level is small against V.  RMAT-24 (V = 16.8 M), direction-optimising traversal: bound 16 M edges
+// 0.392 ms, 4 M 0.377, 2 M 0.381, 1 M 0.366, 512 K 0.361, 256 K 0.364.
+// Round 4: 64 K edges on RMAT-24 (V / 256).  The emitting form is dearer than round 2 priced it -- its atomics go to the memory side at
+// ~2.6e10 /s when they scatter and SERIALISE at ~12 ns each when they meet (profiles/r04_atomic_scope_bench.log; every edge into a popular
+// vertex that arrives before the first store is visible issues its own: a 500 K-edge level took 170 us) -- and the scan it avoids is
+// cheaper (vgl_k_bfs_scan_bound: 13 us): V / 24 0.317 ms per traversal, V / 64 0.305, V / 256 0.3047, V / 1024 0.306, never 0.317.
+static int64_t vgl_bfs_td_emit_edges(int64_t V) { return std::max<int64_t>(65536, V / 256); }
+
+// c->bfs (DESIGN "Run-time switches") turned into the numbers one traversal runs with: the defaults and what they were measured on
+struct vgl_bfs_params {
+    int64_t td_emit_edges;      // top-down levels with at most this many edges OR their discoveries into bm_next
+    double td_filter_share;     // the top-down expansion probes the visited bitmap from this share of V visited on (0 = always, 2 = never)
+    double td_late_share;       // "late": at most this share of V left to discover (0 = rule off)
+    double blocked_share;       // top-down levels with at least this share of the edges take the blocked pass (when prepared)
+    int64_t small_m;            // edge bound of the list kernel (0: not used)
+    int64_t bm_expand_f;        // frontiers up to this size are expanded from the bitmap when the list kernel is to follow
+    bool use_hints, scan_bound, trace;
+};
+static vgl_bfs_params vgl_bfs_params_of(const vgl_bfs_tunables &tn, int64_t V, int mode)
+{
+    const bool do_mode = mode == VGL_HIP_BFS_DIRECTION_OPT;
+    vgl_bfs_params p;
+    p.td_emit_edges = tn.td_emit_edges >= 0 ? tn.td_emit_edges : vgl_bfs_td_emit_edges(V);
+    p.td_filter_share = tn.td_filter_share >= 0.0 ? tn.td_filter_share : 0.125;
+    // Late levels: once all but a few of the vertices that CAN be discovered (rows with incoming edges; known when the incoming CSR is stored)
+    // are visited, an emitting level is cheap whatever its edge count -- its visited-bitmap probe turns almost every edge away before the
+    // atomic -- and it leaves the next frontier as a bitmap (2 MiB to count) instead of only in `levels` (64 MiB to scan).
+    p.td_late_share = tn.td_late_share >= 0.0 ? tn.td_late_share : 1.0 / 64;
+    // RMAT-24 top-down traversal: 1.83 ms at 0.2, 1.67 at 0.1, 1.66 at 0.05, 1.69 at 0.02
+    p.blocked_share = tn.blocked_share >= 0.0 ? tn.blocked_share : 0.1;
+    // small frontiers (the first and the last levels): several levels in one single-workgroup launch, vgl_k_bfs_small_levels.  4096 .. 16384
+    // measure the same on RMAT-24 (0.628 ms against 0.711 without, 0.646 at 65536).  The kernel scans 32-bit degree sums; in a
+    // direction-optimising run the bound also keeps the direction rule silent inside the kernel (below the fewest edges that turn bottom-up).
+    p.small_m = tn.small_m >= 0 ? std::min<int64_t>(tn.small_m, 1 << 20) : 8192;
+    if (do_mode) p.small_m = std::min<int64_t>(p.small_m, vgl_do_bottom_up_edges(V, V, 1) - 1);
+    if (p.small_m < 64) p.small_m = 0;                       // not worth a launch of its own
+    p.bm_expand_f = tn.bm_expand >= 0 ? tn.bm_expand : 262144;
+    if (vgl_ceil_div(vgl_ceil_div(V, 64), VGL_BLOCK) > 8192) p.bm_expand_f = 0;     // (edge partials live in g->bu_partials: 4 * VGL_BU_BLOCKS slots)
+    p.use_hints = do_mode && !tn.no_hint;
+    p.scan_bound = do_mode && !tn.no_scan_bound;
+    p.trace = tn.trace;
+    return p;
+}
+
+// where the frontier of level `cur` is
+enum class vgl_bfs_front {
+    levels,            // only in `levels` (a top-down level that did not emit): the count scans them and rebuilds both bitmaps
+    pending,           // its vertices wait in bm_next (an emitting or blocked level, the list kernel): the count launch moves them to bm_front
+    bitmap,            // in bm_front / bm_visited, not counted (the start, a bottom-up step, a count that left the degrees out)
+    counted_bitmap,    // in the bitmaps, F / M and the write pass's per-tile offsets counted off the bitmap words
+    counted_scan,      // counted by a scan of `levels`, which rebuilt the bitmaps too
+    ids,               // ids / offs / tile_first written by the list kernel: F and M known, no count and no write pass
+};
+
+// One traversal: the loop in run() decides, the members launch and keep the books.  F / M: size and out-degree sum of level `cur`
+// (after a bottom-up step M is not known: it is not needed to stay bottom-up).
+struct vgl_bfs_traversal {
+    vgl_hip_ctx *c;
+    vgl_hip_graph *g;
+    int mode;
+    int32_t *levels;
+    vgl_bfs_params p;
+    int32_t V;
+    int64_t E, words, factor;
+    unsigned bm_blocks;
+    unsigned long long *list_count;     // list length of vgl_k_bm_expand: a counter slot the fused traversal does not use otherwise
+    std::chrono::steady_clock::time_point t0;
+
+    int32_t cur = 1;
+    vgl_bfs_front front = vgl_bfs_front::bitmap;
+    bool bottom_up = false;             // the direction that PROCESSES level `cur`
+    // hint_ready: the launch that produced the frontier about to be counted left its F and M on the device (a counting top-down level, or the
+    // list kernel leaving with a frontier too long for its list): the count launch may then skip everything but the bitmaps when the rule turns
+    // the level bottom-up (`skipped`; the rule in run() must -- and does, same integers -- come to the same conclusion)
+    bool hint_ready = false, skipped = false, finished = false;
+    int64_t F = 0, M = 0, prevF = 0, visited_total = 0;
+    vgl_hip_bfs_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+    vgl_bfs_traversal(vgl_hip_ctx *c_, vgl_hip_graph *g_, int mode_, int32_t *levels_)
+        : c(c_), g(g_), mode(mode_), levels(levels_), p(vgl_bfs_params_of(c_->bfs, g_->V, mode_)), V(g_->V), E(g_->out.edges)
+    {
+        words = vgl_ceil_div(V, 64);
+        factor = vgl_do_factor(E, V);
+        bm_blocks = (unsigned)vgl_ceil_div(words, VGL_BLOCK);
+        list_count = reinterpret_cast<unsigned long long *>(c->d_counters + C_HEAVY);
+    }
+
+    // VGL_BFS_TRACE=1: one line per dispatch (level, frontier, edges, path taken, milliseconds since the start; every line synchronises)
+    void trace(const char *what)
+    {
+        if (!p.trace) return;
+        hipStreamSynchronize(c->stream);
+        fprintf(stderr, "[bfs trace] %7.3f ms  level %d  F %lld  M %lld  visited %lld  %s\n",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), (int)cur, (long long)F, (long long)M,
+                (long long)visited_total, what);
+    }
+    void begin_level(int64_t f) { visited_total += f; st.levels++; st.frontier_total += f; }
+    void book_top_down(int64_t f, int64_t m) { st.td_steps++; st.edges_examined += m; st.td_edges += m; st.td_frontier += f; }
+    // evaluated when visited_total already holds the frontier about to be expanded
+    bool late() const
+    {
+        if (g->in_nz_rows <= 0 || p.td_late_share <= 0.0) return false;
+        const int64_t remain = std::max<int64_t>(0, (int64_t)g->in_nz_rows + 1 - visited_total);      // (+1: the source may have no incoming edge)
+        return (double)remain <= p.td_late_share * (double)V;
+    }
+
+    // F and M of level `cur` (and the bitmaps, when only `levels` knows the frontier)
+    int count()
+    {
+        trace("-> count");
+        skipped = false;
+        const char *done = "count done (bitmap)";
+        if (front != vgl_bfs_front::levels) {
+            const bool advance = front == vgl_bfs_front::pending;
+            const vgl_do_hint hint = {prevF, visited_total, (int64_t)V, factor};
+            const bool hinted = hint_ready && advance && p.use_hints;
+            VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, advance, hinted ? &hint : nullptr));
+            skipped = hinted && c->h_counters[C_SKIPPED] != 0;
+            front = skipped ? vgl_bfs_front::bitmap : vgl_bfs_front::counted_bitmap;
+        } else if (p.scan_bound && g->nvtiles <= 8192) {         // (per-tile partials live in g->bu_partials: 4 * 4096 slots)
+            const int64_t seq = vgl_next_seq(c);
+            {
+                vgl_timed_launch tl(c, "gnf");
+                hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, (const int32_t *)levels,
+                                   cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, g->bu_partials,
+                                   g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters, (volatile int64_t *)c->h_counters, seq);
+            }
+            VGL_HIP_TRY(hipGetLastError());
+            VGL_TRY(vgl_wait_counters(c, seq));
+            front = vgl_bfs_front::bitmap;
+            const int64_t f = c->h_counters[C_FRONT], m_lb = c->h_counters[C_NEIGH];
+            if (vgl_do_turn_bottom_up(f, m_lb, prevF, visited_total + f, V, factor)) {
+                // bottom-up whatever the exact edge count is (the rule in run() sees M = the bound and comes to the same conclusion)
+                F = f; M = m_lb; skipped = true; hint_ready = false;
+                trace("count done (levels scan)");
+                return 0;
+            }
+            VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, false, nullptr));      // exact sizes off the bitmap
+            front = vgl_bfs_front::counted_bitmap;
+        } else {
+            vgl_pred_equal_i32 pred{levels, cur};
+            VGL_TRY(vgl_gnf_run(c, g, pred, g->ids, g->offs, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, nullptr, false, true));
+            front = vgl_bfs_front::counted_scan;
+            done = "count done (levels scan)";
+        }
+        F = c->h_counters[C_FRONT]; M = c->h_counters[C_NEIGH];
+        hint_ready = false;
+        trace(done);
+        return 0;
+    }
+
+    // the list kernel on g->ids[0..listF) of level `cur` (or on {source}); from_bitmap: level `cur` is expanded from bm_front by vgl_k_bm_expand
+    // first and the list kernel starts at level cur + 1.  It returns through C_* what it did.
+    int small_levels(int32_t listF, int32_t src, bool from_bitmap)
+    {
+        if (from_bitmap) {
+            vgl_timed_launch tl(c, "bfs_bitmap_expand");
+            hipLaunchKernelGGL(vgl_k_bm_expand, dim3(bm_blocks), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_front, g->out.rowptr, g->out.adj, g->bm_visited,
+                               g->bm_next, levels, cur + 1, g->ids, list_count, (int32_t)VGL_SMALL_F, g->bu_partials);
+        }
+        const int64_t seq = vgl_next_seq(c);
+        {
+            vgl_timed_launch tl(c, "bfs_small_levels");
+            hipLaunchKernelGGL(vgl_k_bfs_small_levels, dim3(1), dim3(VGL_SMALL_THREADS), 0, c->stream, g->ids, listF, src, g->out.rowptr, g->out.adj,
+                               g->bm_visited, g->bm_next, levels, from_bitmap ? cur + 1 : cur, p.small_m, c->d_counters, (volatile int64_t *)c->h_counters,
+                               seq, from_bitmap ? list_count : (unsigned long long *)nullptr, (const int64_t *)g->bu_partials, from_bitmap ? (int)bm_blocks : 0,
+                               g->bm_front, g->offs, g->tile_first);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_wait_counters(c, seq));
+        return 0;
+    }
+    // books the levels the list kernel ran beyond the first one (the caller has booked that one, entered with firstF vertices) and moves `cur`
+    // past all of them
+    void book_small(int64_t firstF)
+    {
+        const int64_t *h = c->h_counters;
+        const int64_t run = h[C_TMP0], later = h[C_TMP1];
+        st.td_steps += (int32_t)run; st.edges_examined += h[C_EDGES]; st.td_edges += h[C_EDGES];
+        st.td_frontier += firstF + later;
+        visited_total += later; st.levels += (int32_t)(run - 1); st.frontier_total += later;
+        if (run > 1) prevF = h[C_JUMP];
+        cur += (int32_t)run;
+        if (h[C_FRONT] == 0) finished = true;                               // the last level run discovered nothing
+        else if (h[C_HEAVY] != 0) { F = h[C_FRONT]; M = h[C_BU_EDGES]; front = vgl_bfs_front::ids; }      // handed over
+        else { front = vgl_bfs_front::pending; hint_ready = h[C_HINT] != 0; }
+    }
+    // a modest frontier of short rows in bm_front: expand it from the bitmap and let the list kernel run whatever follows -- no count / host /
+    // write rounds.  Level `cur` is booked here, the list kernel's levels by book_small.
+    int expand_from_bitmap()
+    {
+        trace("counted -> bitmap expand + list kernel");
+        VGL_TRY(small_levels(0, -1, true));
+        trace("bitmap expand + list kernel done");
+        const int64_t m_level = c->h_counters[C_CHANGED], n_next = c->h_counters[C_BU_FOUND];
+        book_top_down(F, m_level);
+        prevF = F;
+        cur++;
+        if (n_next == 0) { finished = true; return 0; }                    // nothing discovered: the traversal is complete
+        if (c->h_counters[C_TMP0] > 0) {                                    // the list kernel ran level cur (and maybe more)
+            begin_level(n_next);
+            prevF = n_next;
+            book_small(n_next);
+        } else front = vgl_bfs_front::pending;                              // too many discoveries (or edges) for it: they wait in bm_next
+        return 0;
+    }
+    // a level that holds a large share of the edges: the blocked pass (bitmaps in, bitmap + levels out: the state afterwards is that after an
+    // emitting top-down level)
+    int blocked_level()
+    {
+        trace("counted -> blocked level");
+        VGL_TRY(vgl_bfs_blocked_level(c, g, levels, cur + 1));
+        trace("blocked level done");
+        front = vgl_bfs_front::pending;
+        book_top_down(F, M);
+        cur++;
+        return 0;
+    }
+    int top_down_level()
+    {
+        switch (front) {
+        case vgl_bfs_front::ids: break;                                     // written by the list kernel
+        case vgl_bfs_front::counted_bitmap: VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, false, true, M)); break;
+        case vgl_bfs_front::counted_scan: {
+            vgl_pred_equal_i32 pred{levels, cur};
+            vgl_timed_launch tl(c, "gnf");
+            hipLaunchKernelGGL(vgl_k_gnf_write<vgl_pred_equal_i32>, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, pred,
+                               g->nrows, g->row_begin, g->out.rowptr, g->vt_cnt_off, g->vt_deg_off, g->ids, g->offs, (int32_t *)nullptr, (int64_t)0);
+            break;
+        }
+        default: VGL_FAIL("bfs_run: internal error (frontier not counted)");
+        }
+        trace("ids written");
+        const bool have_tile_first = front != vgl_bfs_front::counted_scan;  // (the bitmap write pass and the list kernel fill it)
+        if (p.small_m > 0 && have_tile_first && F <= VGL_SMALL_F && M <= p.small_m) {
+            trace("counted + ids -> list kernel");
+            VGL_TRY(small_levels((int32_t)F, -1, false));
+            trace("list kernel done");
+            book_small(F);
+            return 0;
+        }
+        const bool is_late = late();
+        const bool emit = M <= p.td_emit_edges || is_late;                  // bm_next is all zero here (init / vgl_k_bm_advance leave it so)
+        const bool td_counts = emit && p.use_hints && vgl_ceil_div(M, VGL_TILE) <= VGL_TD_COUNT_TILES;
+        const bool filter = is_late || (double)visited_total >= p.td_filter_share * (double)V;
+        trace(emit ? "counted + ids -> top-down (emitting)" : "counted + ids -> top-down (levels only)");
+        VGL_TRY(vgl_bfs_td_launch(c, g, (int32_t)F, M, levels, cur + 1, emit, have_tile_first, td_counts, filter));
+        trace("top-down done");
+        hint_ready = td_counts && F > 0 && M > 0;     // (a level without edges launches nothing: C_NEXT_* would be another traversal's)
+        front = emit ? vgl_bfs_front::pending : vgl_bfs_front::levels;      // a top-down level is always followed by a count (or the loop ends)
+        book_top_down(F, M);
+        cur++;
+        return 0;
+    }
+    int bottom_up_level()
+    {
+        if (front == vgl_bfs_front::levels || front == vgl_bfs_front::pending) VGL_FAIL("bfs_run: internal error (bitmaps missing)");
+        int64_t seq = 0;
+        trace("-> bottom-up");
+        VGL_TRY(vgl_bfs_bu_launch(c, g, levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq));
+        hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited, g->bm_front, g->bm_next);
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_wait_counters(c, seq));
+        st.bu_steps++; st.edges_examined += c->h_counters[C_BU_EDGES];
+        st.bu_edges += c->h_counters[C_BU_EDGES]; st.bu_found += c->h_counters[C_BU_FOUND];
+        F = c->h_counters[C_BU_FOUND]; M = 0;                               // next frontier; the bitmaps now describe level cur + 1
+        front = vgl_bfs_front::bitmap;
+        cur++;
+        return 0;
+    }
+
+    int run(int32_t source)
+    {
+        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(V)), dim3(VGL_BLOCK), 0, c->stream, V, source, levels, words, g->bm_visited, g->bm_front,
+                           g->bm_next, g->tickets, list_count);
+        t0 = std::chrono::steady_clock::now();
+        if (p.small_m > 0) {                                                // level 1 = {source}
+            VGL_TRY(small_levels(1, source, false));
+            if (c->h_counters[C_TMP0] > 0) {
+                begin_level(1);
+                prevF = 1;
+                book_small(1);
+            }
+        }
+        while (!finished) {
+            if (front != vgl_bfs_front::ids && !bottom_up) VGL_TRY(count());    // after a bottom-up step F is already known
+            if (F == 0) break;
+            begin_level(F);
+            // direction for this level (gpu_change_state, change_state.hpp:100-141, evaluated with the frontier about to be expanded)
+            if (mode == VGL_HIP_BFS_DIRECTION_OPT) {
+                if (!bottom_up) bottom_up = vgl_do_turn_bottom_up(F, M, prevF, visited_total, V, factor);
+                else if (vgl_do_turn_top_down(F, prevF, visited_total, V, factor)) {
+                    bottom_up = false;
+                    if (p.small_m > 0 && F <= p.bm_expand_f) {
+                        VGL_TRY(expand_from_bitmap());
+                        continue;
+                    }
+                    VGL_TRY(count());                                       // ids / offsets of level cur are needed again (bm_front is valid: cheap)
+                }
+            }
+            // the tail of a traversal whose frontier came as a bitmap (top-down mode, or a direction-optimising one that never went bottom-up):
+            // the treatment the switch back from bottom-up gets above
+            if (!bottom_up && front == vgl_bfs_front::counted_bitmap && p.small_m > 0 && F <= p.bm_expand_f && late()) {
+                VGL_TRY(expand_from_bitmap());
+                continue;
+            }
+            prevF = F;
+            if (skipped && !bottom_up) VGL_FAIL("bfs_run: internal error (the count launch and the host disagree on the direction rule)");
+            if (bottom_up) VGL_TRY(bottom_up_level());
+            else if (g->blk_bfs && front != vgl_bfs_front::levels && (double)M >= p.blocked_share * (double)E) VGL_TRY(blocked_level());
+            else VGL_TRY(top_down_level());
+        }
+        st.discovered = visited_total;
+        st.algorithmic_bytes = 8 * st.edges_examined + 20 * st.frontier_total + 4 * st.discovered + 4 * (int64_t)V +
+                               (int64_t)st.bu_steps * (V / 8);
+        return 0;
+    }
+};
+
 extern "C" {
 
 // Graph preparation for repeated top-down traversals (like the reference's offline import, vgl_graph.hpp:57-68): lays the outgoing
@@ -1372,277 +1572,11 @@ int vgl_hip_bfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int mode, 
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("bfs_run: graph handle must own all rows (use the step API for shards)");
     if (mode != VGL_HIP_BFS_TOP_DOWN && mode != VGL_HIP_BFS_DIRECTION_OPT) VGL_FAIL("bfs_run: unknown mode");
     if (mode == VGL_HIP_BFS_DIRECTION_OPT && !g->in.rowptr) VGL_FAIL("bfs_run: direction-optimising mode needs the incoming CSR");
-    const int32_t V = g->V;
-    const int64_t E = g->out.edges;
-    const int64_t words = vgl_ceil_div(V, 64);
-    if (source < 0 || source >= V) VGL_FAIL("bfs_run: source vertex out of range");
+    if (source < 0 || source >= g->V) VGL_FAIL("bfs_run: source vertex out of range");
     vgl_ctx_refresh_env(c);                                  // (a pass over the pointers of `environ`; the strings are parsed only when something was set since)
-    const vgl_bfs_tunables &tn = c->bfs;
-    hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(V)), dim3(VGL_BLOCK), 0, c->stream, V, source, d_levels, words, g->bm_visited, g->bm_front,
-                       g->bm_next, g->tickets, reinterpret_cast<unsigned long long *>(c->d_counters + C_HEAVY));
-
-    vgl_hip_bfs_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    int32_t cur = 1;
-    bool bottom_up = false;          // state used to PROCESS level `cur`
-    // Frontier of level `cur`: bm_front when front_valid (bm_visited is then current too); otherwise only `levels` knows it and
-    // the levels-scanning GNF rebuilds both bitmaps.  Frontiers are kept as bitmaps whenever the level that produced them was
-    // small (bottom-up steps always; top-down steps with at most VGL_TD_EMIT_EDGES edges, which OR their discoveries in).
-    bool front_valid = true;
-    bool counted = false;            // vt_cnt_off / vt_deg_off describe the frontier (needed by the write pass)
-    bool counted_from_bitmap = false;
-    bool advance_pending = false;    // bm_next holds the discoveries of the last (top-down, emitting) level: the count launch applies them
-    int64_t F = 0, M = 0, prevF = 0, visited_total = 0;
-    const int64_t factor = std::max<int64_t>(1, (E / V) / 2);     // change_state.hpp:104
-    // An emitting level pays one device-scope atomicOr per discovery, a plain one a scan of `levels` (V * 4 bytes) by the next frontier
-    // generation: the bitmap pays only while the level is small against V.  RMAT-24 (V = 16.8 M), direction-optimising traversal: bound
-    // 16 M edges 0.392 ms, 4 M 0.377, 2 M 0.381, 1 M 0.366, 512 K 0.361, 256 K 0.364.
-    // Round 4: 64 K edges on RMAT-24 (V / 256).  The emitting form is dearer than round 2 priced it -- its atomics go to the memory side at
-    // ~2.6e10 /s when they scatter and SERIALISE at ~12 ns each when they meet (profiles/r04_atomic_scope_bench.log; every edge into a popular
-    // vertex that arrives before the first store is visible issues its own: a 500 K-edge level took 170 us) -- and the scan it avoids is
-    // cheaper (vgl_k_bfs_scan_bound: 13 us): V / 24 0.317 ms per traversal, V / 64 0.305, V / 256 0.3047, V / 1024 0.306, never 0.317.
-    int64_t VGL_TD_EMIT_EDGES = std::max<int64_t>(65536, (int64_t)V / 256);
-    if (tn.td_emit_edges >= 0) VGL_TD_EMIT_EDGES = tn.td_emit_edges;
-    double td_filter_share = 0.125;
-    if (tn.td_filter_share >= 0.0) td_filter_share = tn.td_filter_share;
-    // Late levels: once all but a few of the vertices that CAN be discovered (rows with incoming edges; known when the incoming CSR is stored)
-    // are visited, an emitting level is cheap whatever its edge count -- its visited-bitmap probe turns almost every edge away before the
-    // atomic -- and it leaves the next frontier as a bitmap (2 MiB to count) instead of only in `levels` (64 MiB to scan).  VGL_TD_LATE_SHARE:
-    // "few" as a share of V (0 = rule off).
-    double td_late_share = 1.0 / 64;
-    if (tn.td_late_share >= 0.0) td_late_share = tn.td_late_share;
-    auto late = [&]() -> bool {          // evaluated when visited_total already holds the frontier about to be expanded
-        if (g->in_nz_rows <= 0 || td_late_share <= 0.0) return false;
-        const int64_t remain = std::max<int64_t>(0, (int64_t)g->in_nz_rows + 1 - visited_total);      // (+1: the source may have no incoming edge)
-        return (double)remain <= td_late_share * (double)V;
-    };
-    int bu_in_a_row = 0;                                 // bottom-up levels since the last top-down one
-    int later_heavy_blocks = 256;                        // RMAT-24 traversal: 0.376 ms with 2048, 0.368-0.370 with 512 / 256 / 128
-    if (tn.later_heavy_blocks >= 0) later_heavy_blocks = std::max(1, std::min(VGL_BU_BLOCKS, tn.later_heavy_blocks));
-    double blocked_share = 0.1;                          // top-down levels with at least this share of the edges take the blocked pass (when prepared;
-                                                         // RMAT-24 top-down traversal: 1.83 ms at 0.2, 1.67 at 0.1, 1.66 at 0.05, 1.69 at 0.02)
-    if (tn.blocked_share >= 0.0) blocked_share = tn.blocked_share;
-    // hint_ready: the launch that produced the frontier about to be counted left its F and M on the device (a counting top-down level, or
-    // the list kernel leaving with a frontier too long for its list): the count launch may then skip everything but the bitmaps when the
-    // rule turns the level bottom-up (`skipped`; the rule below must -- and does, same integers -- come to the same conclusion)
-    bool hint_ready = false, skipped = false;
-    const bool use_hints = mode == VGL_HIP_BFS_DIRECTION_OPT && !tn.no_hint;
-    const bool scan_bound = mode == VGL_HIP_BFS_DIRECTION_OPT && !tn.no_scan_bound;
-    auto count_frontier = [&]() -> int {
-        skipped = false;
-        if (front_valid) {
-            const vgl_do_hint hint = {prevF, visited_total, (int64_t)V, factor};
-            const bool hinted = hint_ready && advance_pending && use_hints;
-            VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, advance_pending, hinted ? &hint : nullptr));
-            skipped = hinted && c->h_counters[C_SKIPPED] != 0;
-            counted_from_bitmap = true; advance_pending = false;
-        }
-        else if (scan_bound && g->nvtiles <= 8192) {           // (per-tile partials live in g->bu_partials: 4 * 4096 slots)
-            const int64_t seq = vgl_next_seq(c);
-            {
-                vgl_timed_launch tl(c, "gnf");
-                hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, (const int32_t *)d_levels,
-                                   cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, g->bu_partials,
-                                   g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters, (volatile int64_t *)c->h_counters, seq);
-            }
-            VGL_HIP_TRY(hipGetLastError());
-            VGL_TRY(vgl_wait_counters(c, seq));
-            front_valid = true; advance_pending = false;
-            const int64_t f = c->h_counters[C_FRONT], m_lb = c->h_counters[C_NEIGH];
-            if (f > prevF && m_lb >= ((V - (visited_total + f)) * factor + V) / VGL_DO_ALPHA) {
-                // bottom-up whatever the exact edge count is (the rule below sees M = the bound and comes to the same conclusion)
-                F = f; M = m_lb; counted = false; skipped = true; hint_ready = false;
-                return 0;
-            }
-            VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, false, nullptr));      // exact sizes off the bitmap
-            counted_from_bitmap = true;
-        }
-        else {
-            vgl_pred_equal_i32 pred{d_levels, cur};
-            VGL_TRY(vgl_gnf_run(c, g, pred, g->ids, g->offs, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, nullptr, false, true));
-            front_valid = true; counted_from_bitmap = false;
-        }
-        F = c->h_counters[C_FRONT]; M = c->h_counters[C_NEIGH];
-        counted = !skipped;
-        hint_ready = false;
-        return 0;
-    };
-    // small frontiers (the first and the last levels): several levels in one single-workgroup launch, vgl_k_bfs_small_levels.  The edge
-    // bound also keeps the direction rule silent inside the kernel: it needs M >= ((V - visited) * factor + V) / ALPHA >= V / ALPHA.
-    int64_t small_m = 8192;                              // 4096 .. 16384 measure the same on RMAT-24 (0.628 ms against 0.711 without, 0.646 at 65536)
-    if (tn.small_m >= 0) small_m = std::min<int64_t>(tn.small_m, 1 << 20);     // (the kernel scans 32-bit degree sums)
-    if (mode == VGL_HIP_BFS_DIRECTION_OPT) small_m = std::min<int64_t>(small_m, (int64_t)V / VGL_DO_ALPHA - 1);
-    if (small_m < 64) small_m = 0;                       // not worth a launch of its own
-    // VGL_BFS_TRACE=1: one line per dispatch (level, frontier, edges, path taken, milliseconds since the start; every line synchronises)
-    const bool trace_on = tn.trace;
-    const auto trace_t0 = std::chrono::steady_clock::now();
-    auto trace = [&](const char *what) {
-        if (!trace_on) return;
-        hipStreamSynchronize(c->stream);
-        fprintf(stderr, "[bfs trace] %7.3f ms  level %d  F %lld  M %lld  visited %lld  %s\n",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - trace_t0).count(), (int)cur, (long long)F, (long long)M, (long long)visited_total, what);
-    };
-    bool finished = false;
-    bool precounted = false;         // F, M, ids, offs, tile_first of level cur were left by vgl_k_bfs_small_levels: no count, no write pass
-    // runs the kernel on the list g->ids[0..F) of level `cur` (or on {source}); returns through C_* what it did
-    unsigned long long *list_count = reinterpret_cast<unsigned long long *>(c->d_counters + C_HEAVY);      // slot unused by the fused traversal
-    const unsigned bm_blocks = (unsigned)vgl_ceil_div(words, VGL_BLOCK);
-    int64_t bm_expand_f = 262144;                        // bottom-up -> top-down switch: frontiers up to this size are expanded from the bitmap
-    if (tn.bm_expand >= 0) bm_expand_f = tn.bm_expand;
-    if (bm_blocks > 8192) bm_expand_f = 0;               // (edge partials live in g->bu_partials: 4 * VGL_BU_BLOCKS slots)
-    // from_bitmap: level `cur` is expanded from bm_front by vgl_k_bm_expand first, the list kernel starts at level cur + 1
-    auto small_levels = [&](int32_t listF, int32_t src, bool from_bitmap = false) -> int {
-        if (from_bitmap) {
-            vgl_timed_launch tl(c, "bfs_bitmap_expand");
-            hipLaunchKernelGGL(vgl_k_bm_expand, dim3(bm_blocks), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_front, g->out.rowptr, g->out.adj, g->bm_visited,
-                               g->bm_next, d_levels, cur + 1, g->ids, list_count, (int32_t)VGL_SMALL_F, g->bu_partials);
-        }
-        const int64_t seq = vgl_next_seq(c);
-        {
-            vgl_timed_launch tl(c, "bfs_small_levels");
-            hipLaunchKernelGGL(vgl_k_bfs_small_levels, dim3(1), dim3(VGL_SMALL_THREADS), 0, c->stream, g->ids, listF, src, g->out.rowptr, g->out.adj,
-                               g->bm_visited, g->bm_next, d_levels, from_bitmap ? cur + 1 : cur, small_m, c->d_counters, (volatile int64_t *)c->h_counters,
-                               seq, from_bitmap ? list_count : (unsigned long long *)nullptr, (const int64_t *)g->bu_partials, from_bitmap ? (int)bm_blocks : 0,
-                               g->bm_front, g->offs, g->tile_first);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_TRY(vgl_wait_counters(c, seq));
-        return 0;
-    };
-    // books the levels the kernel ran beyond the first one (the caller has booked that one) and moves `cur` past all of them
-    auto account_small = [&](int64_t firstF) {
-        const int64_t run = c->h_counters[C_TMP0], later = c->h_counters[C_TMP1];
-        st.td_steps += (int32_t)run; st.edges_examined += c->h_counters[C_EDGES]; st.td_edges += c->h_counters[C_EDGES];
-        st.td_frontier += firstF + later;
-        visited_total += later; st.levels += (int32_t)(run - 1); st.frontier_total += later;
-        if (run > 1) prevF = c->h_counters[C_JUMP];
-        cur += (int32_t)run;
-        if (c->h_counters[C_FRONT] == 0) finished = true;                      // the last level run discovered nothing
-        else if (c->h_counters[C_HEAVY] != 0) {                                // handed over: ids / offs / tile_first / bm_front describe level cur
-            F = c->h_counters[C_FRONT]; M = c->h_counters[C_BU_EDGES];
-            precounted = true; front_valid = true; advance_pending = false;
-        } else { advance_pending = true; front_valid = true; hint_ready = c->h_counters[C_HINT] != 0; }      // its discoveries wait in bm_next
-    };
-    if (small_m > 0) {                                                         // level 1 = {source}
-        VGL_TRY(small_levels(1, source));
-        if (c->h_counters[C_TMP0] > 0) {
-            visited_total += 1; st.levels++; st.frontier_total += 1; prevF = 1;
-            account_small(1);
-        }
-    }
-    for (;;) {
-        if (finished) break;
-        counted = false;
-        const bool ids_ready = precounted;
-        if (precounted) { counted = true; counted_from_bitmap = true; precounted = false; }
-        else if (!bottom_up) { trace("-> count"); VGL_TRY(count_frontier()); trace(counted_from_bitmap ? "count done (bitmap)" : "count done (levels scan)"); }      // after a bottom-up step F is already known (M is not needed to stay bottom-up)
-        if (F == 0) break;
-        visited_total += F;
-        st.levels++; st.frontier_total += F;
-        // direction for this level (gpu_change_state, change_state.hpp:100-141, evaluated with the frontier about to be expanded)
-        if (mode == VGL_HIP_BFS_DIRECTION_OPT) {
-            if (!bottom_up) {
-                if (F > prevF && M >= ((V - visited_total) * factor + V) / VGL_DO_ALPHA) { bottom_up = true; bu_in_a_row = 0; }
-            } else if (F <= prevF && F < ((V - visited_total) * factor + V) / (factor * VGL_DO_BETA)) {      // "shrinking phase" = not growing (change_state.hpp:106,121)
-                bottom_up = false;
-                if (small_m > 0 && F <= bm_expand_f) {
-                    // a modest frontier of short rows: expand it from the bitmap and let the list kernel run whatever follows -- no
-                    // count / host / write rounds.  Level cur is booked here, the list kernel's levels by account_small.
-                    VGL_TRY(small_levels(0, -1, true));
-                    const int64_t m_level = c->h_counters[C_CHANGED], n_next = c->h_counters[C_BU_FOUND];
-                    st.td_steps++; st.edges_examined += m_level; st.td_edges += m_level; st.td_frontier += F;
-                    prevF = F;
-                    cur++;
-                    if (n_next == 0) break;                                     // nothing discovered: the traversal is complete
-                    if (c->h_counters[C_TMP0] > 0) {                            // the list kernel ran level cur (and maybe more)
-                        visited_total += n_next; st.levels++; st.frontier_total += n_next; prevF = n_next;
-                        account_small(n_next);
-                    } else { advance_pending = true; front_valid = true; }      // too many discoveries (or edges) for it: they wait in bm_next
-                    continue;
-                }
-                VGL_TRY(count_frontier());              // ids / offsets of level cur are needed again (bm_front is valid: cheap)
-            }
-        }
-        if (!bottom_up && !ids_ready && counted && counted_from_bitmap && small_m > 0 && F <= bm_expand_f && late()) {
-            // the tail of a traversal whose frontier came as a bitmap (top-down mode, or a direction-optimising one that never went bottom-up):
-            // expand it from the bitmap and let the list kernel run whatever follows -- the treatment the switch back from bottom-up gets above
-            trace("counted -> bitmap expand + list kernel");
-            VGL_TRY(small_levels(0, -1, true));
-            trace("bitmap expand + list kernel done");
-            const int64_t m_level = c->h_counters[C_CHANGED], n_next = c->h_counters[C_BU_FOUND];
-            st.td_steps++; st.edges_examined += m_level; st.td_edges += m_level; st.td_frontier += F;
-            prevF = F;
-            cur++;
-            if (n_next == 0) break;
-            if (c->h_counters[C_TMP0] > 0) {
-                visited_total += n_next; st.levels++; st.frontier_total += n_next; prevF = n_next;
-                account_small(n_next);
-            } else { advance_pending = true; front_valid = true; }
-            continue;
-        }
-        prevF = F;
-        if (skipped && !bottom_up) VGL_FAIL("bfs_run: internal error (the count launch and the host disagree on the direction rule)");
-        if (!bottom_up && g->blk_bfs && front_valid && (double)M >= blocked_share * (double)E) {
-            // a level that holds a large share of the edges: the blocked pass (bitmaps in, bitmap + levels out: the state afterwards is
-            // that after an emitting top-down level)
-            trace("counted -> blocked level");
-            VGL_TRY(vgl_bfs_blocked_level(c, g, d_levels, cur + 1));
-            trace("blocked level done");
-            advance_pending = true;
-            st.td_steps++; st.edges_examined += M; st.td_edges += M; st.td_frontier += F;
-            cur++;
-            continue;
-        }
-        if (!bottom_up) {
-            if (!counted) VGL_FAIL("bfs_run: internal error (frontier not counted)");
-            if (ids_ready) {}                                   // written by the list kernel
-            else if (counted_from_bitmap) VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, false, true, M));
-            else {
-                vgl_pred_equal_i32 pred{d_levels, cur};
-                vgl_timed_launch tl(c, "gnf");
-                hipLaunchKernelGGL(vgl_k_gnf_write<vgl_pred_equal_i32>, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, pred,
-                                   g->nrows, g->row_begin, g->out.rowptr, g->vt_cnt_off, g->vt_deg_off, g->ids, g->offs, (int32_t *)nullptr, (int64_t)0);
-            }
-            trace("ids written");
-            if (small_m > 0 && counted_from_bitmap && F <= VGL_SMALL_F && M <= small_m) {
-                trace("counted + ids -> list kernel");
-                VGL_TRY(small_levels((int32_t)F, -1));
-                trace("list kernel done");
-                account_small(F);
-                continue;
-            }
-            const bool is_late = late();
-            const bool emit = M <= VGL_TD_EMIT_EDGES || is_late;        // bm_next is all zero here (init / vgl_k_bm_advance leave it so)
-            const bool td_counts = emit && use_hints && vgl_ceil_div(M, VGL_TILE) <= VGL_TD_COUNT_TILES;
-            // the visited-bitmap probe pays once a good part of the vertices is visited (VGL_TD_FILTER_SHARE of V; 0 = always, 2 = never)
-            const bool filter = is_late || (double)visited_total >= td_filter_share * (double)V;
-            trace(emit ? "counted + ids -> top-down (emitting)" : "counted + ids -> top-down (levels only)");
-            VGL_TRY(vgl_bfs_td_launch(c, g, (int32_t)F, M, d_levels, cur + 1, emit, counted_from_bitmap, td_counts, filter));
-            trace("top-down done");
-            hint_ready = td_counts && F > 0 && M > 0;     // (a level without edges launches nothing: C_NEXT_* would be another traversal's)
-            advance_pending = emit;          // a top-down level is always followed by count_frontier (or the loop ends below)
-            front_valid = emit;
-            st.td_steps++; st.edges_examined += M; st.td_edges += M; st.td_frontier += F;
-        } else {
-            if (!front_valid) VGL_FAIL("bfs_run: internal error (bitmaps missing)");
-            int64_t seq = 0;
-            trace("-> bottom-up");
-            VGL_TRY(vgl_bfs_bu_launch(c, g, d_levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq, bu_in_a_row > 0 ? later_heavy_blocks : VGL_BU_BLOCKS));
-            bu_in_a_row++;
-            hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited,
-                               g->bm_front, g->bm_next);
-            VGL_HIP_TRY(hipGetLastError());
-            VGL_TRY(vgl_wait_counters(c, seq));
-            st.bu_steps++; st.edges_examined += c->h_counters[C_BU_EDGES];
-            st.bu_edges += c->h_counters[C_BU_EDGES]; st.bu_found += c->h_counters[C_BU_FOUND];
-            F = c->h_counters[C_BU_FOUND]; M = 0;      // next frontier; bitmaps now describe level cur+1
-            front_valid = true;
-        }
-        cur++;
-    }
-    st.discovered = visited_total;
-    st.algorithmic_bytes = 8 * st.edges_examined + 20 * st.frontier_total + 4 * st.discovered + 4 * (int64_t)V +
-                           (int64_t)st.bu_steps * (V / 8);
-    if (stats) *stats = st;
+    vgl_bfs_traversal t(c, g, mode, d_levels);
+    VGL_TRY(t.run(source));
+    if (stats) *stats = t.st;
     return 0;
 }
 
@@ -1674,9 +1608,7 @@ int vgl_hip_bfs_step_top_down(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_level
     if (F > 0 && M > 0) {
         hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F)), dim3(VGL_BLOCK), 0, c->stream, (int32_t)F, g->offs, g->tile_first);
         vgl_timed_launch tl(c, "bfs_top_down");
-        hipLaunchKernelGGL((vgl_k_td_expand<false, false>), dim3((unsigned)vgl_ceil_div(M, VGL_TILE)), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs,
-                           g->tile_first, (int32_t)F, M, g->out.rowptr, g->out.adj, g->row_begin, visited, d_levels, level + 1,
-                           (uint64_t *)nullptr, (int64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
+        vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, visited, d_levels, level + 1, nullptr);
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;                                    // enqueued; the caller's next call on this context orders after it
@@ -1694,22 +1626,15 @@ int vgl_hip_bfs_step_top_down_bits(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_
     // Small levels OR every discovery into the candidate bitmap (one device-scope atomic each); a level with many edges leaves its
     // discoveries in `levels` only -- the value level + 1 is stored by this level and nobody else -- and the bitmap is read off `levels`
     // afterwards: V * 4 bytes streamed against ~40 us per million edges of atomics (a 4.3 M-edge level of an RMAT-24 traversal: 180 us
-    // with the atomics; the fused traversal draws the same line at V / 24 edges, VGL_TD_EMIT_EDGES)
-    int64_t emit_edges = std::max<int64_t>(65536, (int64_t)g->V / 256);        // (round 4: as VGL_TD_EMIT_EDGES of the fused traversal)
-    if (c->bfs.shard_td_emit_edges >= 0) emit_edges = c->bfs.shard_td_emit_edges;
+    // with the atomics; the fused traversal draws the same line, vgl_bfs_td_emit_edges)
+    const int64_t emit_edges = c->bfs.shard_td_emit_edges >= 0 ? c->bfs.shard_td_emit_edges : vgl_bfs_td_emit_edges(g->V);
     const bool emit = M <= emit_edges;
     const int64_t words = vgl_ceil_div(g->V, 64);
     if (emit) VGL_TRY(vgl_zero_words(c, d_next_bits, words));
     if (F > 0 && M > 0) {                                        // tile_first came with the write pass
         vgl_timed_launch tl(c, "bfs_top_down");
-        if (emit)
-            hipLaunchKernelGGL((vgl_k_td_expand<true, false>), dim3((unsigned)vgl_ceil_div(M, VGL_TILE)), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs,
-                               g->tile_first, (int32_t)F, M, g->out.rowptr, g->out.adj, g->row_begin, d_visited_bits, d_levels, level + 1,
-                               d_next_bits, (int64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
-        else
-            hipLaunchKernelGGL((vgl_k_td_expand<false, false>), dim3((unsigned)vgl_ceil_div(M, VGL_TILE)), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs,
-                               g->tile_first, (int32_t)F, M, g->out.rowptr, g->out.adj, g->row_begin, d_visited_bits, d_levels, level + 1,
-                               d_next_bits, (int64_t *)nullptr, (uint32_t *)nullptr, (int64_t *)nullptr);
+        if (emit) vgl_td_expand_launch<true, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, d_next_bits);
+        else vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, d_next_bits);
     }
     if (!emit) {
         vgl_timed_launch tl(c, "gnf");

@@ -227,7 +227,7 @@ extern "C" int vgl_hip_bfs_run_sharded(vgl_hip_ctx *c, vgl_hip_comm *given, vgl_
     vgl_hip_bfs_stats st = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const bool direction_opt = mode == VGL_HIP_BFS_DIRECTION_OPT;
     const int64_t E = global_edges > 0 ? global_edges : g->out.edges;
-    const int64_t factor = std::max<int64_t>(1, (E / V) / 2);                   // change_state.hpp:104
+    const int64_t factor = vgl_do_factor(E, V);
     int64_t F = 1, M = 0, prevF = 0, visited_total = 0;
     bool bottom_up = false;
     // Who reads the words of the frontier a rank does not own: only a bottom-up level (its probes test arbitrary in-neighbours); a
@@ -241,9 +241,8 @@ extern "C" int vgl_hip_bfs_run_sharded(vgl_hip_ctx *c, vgl_hip_comm *given, vgl_
         visited_total += F;
         st.levels++; st.frontier_total += F;
         if (direction_opt) {                                                    // gpu_change_state on the frontier about to be expanded
-            if (!bottom_up) {
-                if (F > prevF && M >= ((V - visited_total) * factor + V) / 15) bottom_up = true;
-            } else if (F <= prevF && F < ((V - visited_total) * factor + V) / (factor * 18)) bottom_up = false;
+            if (!bottom_up) bottom_up = vgl_do_turn_bottom_up(F, M, prevF, visited_total, V, factor);
+            else bottom_up = !vgl_do_turn_top_down(F, prevF, visited_total, V, factor);
         }
         prevF = F;
         bool exchanged_sparse = false;

@@ -84,9 +84,8 @@ void vgl_ctx_refresh_env(vgl_hip_ctx *c)
     if (const char *v = str("VGL_TD_FILTER_SHARE")) t.td_filter_share = atof(v);
     if (const char *v = str("VGL_TD_LATE_SHARE")) t.td_late_share = atof(v);
     if (const char *v = str("VGL_BFS_BLOCKED_SHARE")) t.blocked_share = atof(v);
-    if (const char *v = str("VGL_BU_LATER_HEAVY_BLOCKS")) t.later_heavy_blocks = atoi(v);
     if (const char *v = str("VGL_SHARD_SPARSE_CAP")) t.shard_sparse_cap = std::max(0, atoi(v));
-    t.no_hint = on("VGL_BFS_NO_HINT"); t.no_scan_bound = on("VGL_BFS_NO_SCAN_BOUND"); t.trace = on("VGL_BFS_TRACE"); t.bu_split = on("VGL_BU_SPLIT");
+    t.no_hint = on("VGL_BFS_NO_HINT"); t.no_scan_bound = on("VGL_BFS_NO_SCAN_BOUND"); t.trace = on("VGL_BFS_TRACE");
     c->bfs = t;
 }
 const char *vgl_env(vgl_hip_ctx *c, const char *name)

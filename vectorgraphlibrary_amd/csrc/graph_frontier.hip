@@ -315,8 +315,6 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
     hipLaunchKernelGGL(vgl_k_tile_min_degree, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->out.rowptr, g->vt_min_deg);
     VGL_TRY(vgl_alloc(&g->tile_first, (size_t)g->out.ntiles + 2));
     VGL_TRY(vgl_alloc(&g->heavy, (size_t)g->nrows + 4096 * VGL_BLOCK));
-    VGL_TRY(vgl_alloc(&g->heavy_cnt, (size_t)4096));
-    VGL_TRY(vgl_alloc(&g->heavy_off, (size_t)4097));
     VGL_TRY(vgl_alloc(&g->bu_partials, (size_t)4096 * 4));
     VGL_TRY(vgl_alloc(&g->tickets, (size_t)4 * VGL_TICKET_WORDS));
     VGL_HIP_TRY(hipMemsetAsync(g->tickets, 0, 4 * VGL_TICKET_WORDS * sizeof(uint32_t), c->stream));
@@ -356,7 +354,7 @@ int vgl_hip_graph_destroy(vgl_hip_ctx *c, vgl_hip_graph *g)
     if (c) hipStreamSynchronize(c->stream);
     if (g->transposed) { vgl_hip_graph_destroy(c, g->transposed); g->transposed = nullptr; }
     void *ptrs[] = {g->out.tile_row, g->in.tile_row, g->bm_visited, g->bm_front, g->bm_next, g->bm_in_nz, g->in_head, g->in_nz_rank, g->bm_in_long, g->ids, g->offs, g->vt_cnt,
-                    g->vt_cnt_off, g->vt_deg, g->vt_deg_off, g->tile_first, g->heavy, g->heavy_cnt, g->heavy_off, g->bu_partials, g->tickets, g->epoch, g->fscratch, g->fscratch2,
+                    g->vt_cnt_off, g->vt_deg, g->vt_deg_off, g->tile_first, g->heavy, g->bu_partials, g->tickets, g->epoch, g->fscratch, g->fscratch2,
                     g->fscratch3, g->iscratch, g->ds_tile_active, g->ds_partials, g->out.hub_rows, g->in.hub_rows, g->out.giant_rows, g->in.giant_rows, g->out.pull_blk_row,
                     g->in.pull_blk_row, g->vt_min_deg, g->gnf_bits, g->out.hub_chunks, g->in.hub_chunks, g->out.hub_chunk_sums, g->in.hub_chunk_sums, g->pr_indeg};
     for (void *p : ptrs) if (p) hipFree(p);

@@ -53,8 +53,8 @@ struct vgl_timing_slot {
 struct vgl_bfs_tunables {
     int64_t td_emit_edges = -1, small_m = -1, bm_expand = -1, shard_td_emit_edges = -1;
     double td_filter_share = -1.0, td_late_share = -1.0, blocked_share = -1.0;
-    int later_heavy_blocks = -1, shard_sparse_cap = -1;
-    bool no_hint = false, no_scan_bound = false, trace = false, bu_split = false;
+    int shard_sparse_cap = -1;
+    bool no_hint = false, no_scan_bound = false, trace = false;
 };
 
 struct vgl_hip_ctx {
@@ -128,8 +128,6 @@ struct vgl_hip_graph {
                                      // compaction of a SPARSE result reads these 2 MiB instead of 64 MiB of int32 flags (vgl_hip_gnf_begin / _complete)
     int32_t *tile_first = nullptr;   // out.ntiles + 2
     int32_t *heavy = nullptr;        // nrows + slack: per-workgroup segments of deferred bottom-up vertices
-    int32_t *heavy_cnt = nullptr;    // one count per bottom-up workgroup
-    int32_t *heavy_off = nullptr;    // exclusive prefix of heavy_cnt (+ total)
     int64_t *bu_partials = nullptr;  // 4 partial counters per bottom-up workgroup
     uint32_t *tickets = nullptr;     // arrival counters of the "last workgroup finishes the job" kernels (reset by that workgroup)
     int32_t *epoch = nullptr;        // V (SSSP active filter)
@@ -180,13 +178,30 @@ int64_t vgl_next_seq(vgl_hip_ctx *ctx);
 int vgl_wait_counters(vgl_hip_ctx *ctx, int64_t seq);
 int vgl_zero_counters(vgl_hip_ctx *ctx, int first, int count);
 int vgl_ensure_partials(vgl_hip_ctx *ctx, size_t n);
-int vgl_build_tile_rows(vgl_hip_ctx *ctx, struct vgl_dir_csr &d, int32_t nrows);
+int vgl_build_tile_rows(vgl_hip_ctx *ctx, struct vgl_dir_csr &d, int32_t nrows);     // d.tile_row / d.ntiles from d.rowptr / d.edges (owned by the caller)
+// The direction rule itself (gpu_change_state, change_state.hpp:100-141), for the host loops and the count launch alike: the same exact int64_t
+// arithmetic on both sides, so that they reach the same decision.  `visited` counts the vertices visited so far WITH the frontier F about to be
+// expanded; M is its out-degree sum.
+constexpr int VGL_DO_ALPHA = 15;       // change_state.hpp:5
+constexpr int VGL_DO_BETA = 18;        // change_state.hpp:6
+__host__ __device__ inline int64_t vgl_do_factor(int64_t E, int64_t V) { return E / V / 2 > 1 ? E / V / 2 : 1; }     // change_state.hpp:104
+// the fewest frontier edges that turn a level bottom-up (at least V / ALPHA, when every vertex is visited)
+__host__ __device__ inline int64_t vgl_do_bottom_up_edges(int64_t V, int64_t visited, int64_t factor) { return ((V - visited) * factor + V) / VGL_DO_ALPHA; }
+__host__ __device__ inline bool vgl_do_turn_bottom_up(int64_t F, int64_t M, int64_t prev_f, int64_t visited, int64_t V, int64_t factor)
+{
+    return F > prev_f && M >= vgl_do_bottom_up_edges(V, visited, factor);
+}
+// back to top-down in the "shrinking phase" = not growing (change_state.hpp:106,121)
+__host__ __device__ inline bool vgl_do_turn_top_down(int64_t F, int64_t prev_f, int64_t visited, int64_t V, int64_t factor)
+{
+    return F <= prev_f && F < ((V - visited) * factor + V) / (factor * VGL_DO_BETA);
+}
 // frontier from a bitmap over the owned words (bfs.hip): count = sizes to h_counters[C_FRONT / C_NEIGH] (waits), write = ids + edge offsets + tile table
 // what the direction rule (gpu_change_state) needs besides the new frontier's F and M: with it the count launch may find on the device that
 // the level turns bottom-up and leave out everything a top-down level would need (degree sums, compaction offsets)
 struct vgl_do_hint { int64_t prev_f, visited_total, V, factor; };
 int vgl_bfs_bm_gnf(vgl_hip_ctx *c, struct vgl_hip_graph *g, const uint64_t *front, bool count, bool write, int64_t M_known = -1, bool advance = false,
-                   const vgl_do_hint *hint = nullptr);   // d.tile_row / d.ntiles from d.rowptr / d.edges (owned by the caller)
+                   const vgl_do_hint *hint = nullptr);
 // set bits of `words` 64-bit words as ids (64 * (word_base + word) + bit): d_out[0] = their number, d_out[1 .. 1 + cap) = the first cap handed out
 int vgl_bitmap_to_ids(vgl_hip_ctx *c, int64_t words, const uint64_t *d_bits, int64_t word_base, int32_t cap, int32_t *d_out);
 int vgl_zero_words(vgl_hip_ctx *c, uint64_t *d_words, int64_t words);      // one launch (bfs.hip)
