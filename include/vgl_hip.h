@@ -326,6 +326,43 @@ int vgl_hip_cc_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t *d_comp, vgl_hip_
  * link passes (sampling rounds + 1), algorithmic_bytes what those passes had to touch. */
 int vgl_hip_cc_run_symmetric(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t *d_comp, vgl_hip_cc_stats *stats);
 
+/* Label propagation: the AlwaysActive GPU path of LabelPropagation::gpu_lp (algorithms/lp/gpu/lp_gpu.cu:185-420 with
+ * active_conditions.cuh:6-37), stated so that a sequential restatement reproduces it bit for bit:
+ *   N(v)   v's stored adjacency in `direction` (0 = OUT, 1 = IN).  Every stored entry counts once: multi-edges with their multiplicity,
+ *          a self-loop with v's own label (the reference's gather, lp_gpu.cu:290-298).
+ *   L0     d_init[v], or -- d_init == NULL -- v's id in the graph's numbering (callers of a renumbered graph pass its stored -> original
+ *          table, so that the answer does not depend on the numbering).  Labels are arbitrary int32 values, INT32_MIN / INT32_MAX included.
+ *   step   synchronous: every read of iteration t sees L_{t-1}.  N(v) empty: L_t[v] = L_{t-1}[v].  Otherwise L_t[v] is the label with
+ *          the highest count in N(v); a tie goes to the LARGEST label (the reference sorts each segment ascending and reduces with
+ *          `w_a > w_b ? a : b`, lp_gpu.cu:374, which keeps the rightmost maximum whatever the association order).
+ *   stop   after the first iteration that changes no label (converged = 1; that iteration is counted), or after max_iterations
+ *          (the reference's default 20, lp.h:10).  The reference always runs to the cap (it sets updated[0] = 1 unconditionally,
+ *          lp_gpu.cu:414); a fixed point is stable, so the labels are the same.  A synchronous LP can oscillate (K2,2): the cap decides.
+ * Not reproduced: seq_lp (vertex shuffle and coin-flip ties, seq_lp.hpp:36,71) and the heuristic active conditions.
+ * mode: ALL_ACTIVE evaluates every row every iteration; FRONTIER evaluates only the rows with a neighbour that changed in the iteration
+ * before (exact: such a row keeps its label), found by pushing the changed vertices over the REVERSE CSR -- the incoming one for OUT, the
+ * outgoing one for IN, or the CSR in use itself when the caller vouches that it is symmetric; AUTO = FRONTIER when that reverse is
+ * available, else ALL_ACTIVE.  All modes give the same labels, iteration counts and changed counts.
+ * changed_history (host, may be NULL): entry t = vertices whose label changed in iteration t, for t < stats->iterations.
+ * Fails for a sharded handle, IN without the incoming CSR, FRONTIER without a reverse CSR, max_iterations < 0.
+ * vgl_hip_lp_prepare builds the degree classes of `direction` (and the push schedule of its reverse) now, outside any timing; the
+ * first run would build them otherwise.  They are cached on the graph handle and freed with it. */
+#define VGL_LP_ALL_ACTIVE 0
+#define VGL_LP_FRONTIER 1
+#define VGL_LP_AUTO 2
+typedef struct {
+    int32_t iterations;          /* iterations run, the last one (no change) included when converged */
+    int32_t converged;
+    int32_t frontier_steps;      /* iterations that evaluated a frontier instead of every row */
+    int64_t changed_last;        /* vertices changed by the last iteration */
+    int64_t rows_processed;      /* rows (with at least one entry) evaluated, summed over the iterations */
+    int64_t edges_examined;      /* their entries: iterations * E when every iteration evaluates every row */
+    int64_t algorithmic_bytes;   /* 16*V + 8*E per all-active iteration (row offsets, label read / write; adjacency, gathered labels) + frontier upkeep */
+} vgl_hip_lp_stats;
+int vgl_hip_lp_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction);
+int vgl_hip_lp_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction, int mode, int symmetric, int max_iterations, const int32_t *d_init,
+                   int32_t *d_labels, int64_t *changed_history, vgl_hip_lp_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

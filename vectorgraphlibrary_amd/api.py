@@ -18,6 +18,7 @@ BFS_TOP_DOWN, BFS_DIRECTION_OPT = 0, 1
 SSSP_ALL_ACTIVE, SSSP_ACTIVE_TILES, SSSP_DELTA_STEPPING, SSSP_PULL, SSSP_DIRECTION_OPT = 0, 1, 2, 3, 4
 DENSE, SPARSE, ALL_ACTIVE = 0, 1, 2    # framework_types.h:156-160
 PR_EXACT_ORDER, PR_BLOCKED, PR_AUTO = 0, 1, 2
+LP_ALL_ACTIVE, LP_FRONTIER, LP_AUTO = 0, 1, 2
 
 
 def _ptr(t):
@@ -211,6 +212,10 @@ class Graph:
 
     def prepare_cc(self):
         _l.check(self.ctx.L.vgl_hip_cc_prepare(self.ctx.h, self.h))
+
+    def prepare_label_propagation(self, direction="out"):
+        """degree classes of `direction` (and the push schedule of its reverse) now, outside any timing (vgl_hip_lp_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_lp_prepare(self.ctx.h, self.h, {"out": 0, "in": 1}[direction]))
 
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
@@ -439,6 +444,28 @@ def connected_components(graph, comp=None, raw=False, symmetric=False):
     out, scratch = ctx.empty(graph.V, torch.int32), ctx.empty(graph.V, torch.int32)
     _l.check(ctx.L.vgl_hip_cc_labels_to_original(ctx.h, graph.V, _ptr(comp), _ptr(graph.fwd), _ptr(graph.bwd), _ptr(scratch), _ptr(out)))
     return out, _stats(st)
+
+
+def label_propagation(graph, max_iterations=20, direction="out", mode=LP_AUTO, labels=None, symmetric=False, raw=False):
+    """label propagation (the contract of vgl_hip_lp_run in include/vgl_hip.h): every iteration each vertex takes the most frequent label among
+    its neighbours in `direction` ("out" / "in"), ties to the largest label, until nothing changes or after max_iterations.
+    labels: int32 start labels in ORIGINAL vertex order (raw=True: the graph's own order); None = the original vertex ids.
+    mode: LP_ALL_ACTIVE, LP_FRONTIER or LP_AUTO (same answer).  symmetric=True: the caller vouches that every edge is stored both ways.
+    Returns (labels in ORIGINAL order unless raw=True, stats dict with "changed_history")."""
+    ctx = graph.ctx
+    if labels is not None:
+        labels = torch.as_tensor(labels, dtype=torch.int32, device=ctx.device).contiguous()
+        init = labels if (raw or graph.fwd is None) else ctx.permute(graph.bwd, labels)
+    else:
+        init = graph.bwd                      # None for a graph in original numbering: the library starts from the ids
+    out = ctx.empty(graph.V, torch.int32)
+    hist = (C.c_int64 * max(int(max_iterations), 1))()
+    st = _l.LpStats()
+    _l.check(ctx.L.vgl_hip_lp_run(ctx.h, graph.h, {"out": 0, "in": 1}[direction], int(mode), int(bool(symmetric)), int(max_iterations),
+                                  _ptr(init), _ptr(out), hist, C.byref(st)))
+    stats = _stats(st)
+    stats["changed_history"] = [hist[i] for i in range(st.iterations)]
+    return (out if raw else graph.to_original(out)), stats
 
 
 def count_not_equal(ctx, a, b):

@@ -39,6 +39,11 @@ class CcStats(C.Structure):
     _fields_ = [("hook_passes", C.c_int32), ("algorithmic_bytes", C.c_int64)]
 
 
+class LpStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("frontier_steps", C.c_int32), ("changed_last", C.c_int64),
+                ("rows_processed", C.c_int64), ("edges_examined", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -115,6 +120,8 @@ _SIGNATURES = {
     "vgl_hip_scc_run": [_p, _p, _p, C.POINTER(SccStats)],
     "vgl_hip_cc_run": [_p, _p, _p, C.POINTER(CcStats)],
     "vgl_hip_cc_run_symmetric": [_p, _p, _p, C.POINTER(CcStats)],
+    "vgl_hip_lp_prepare": [_p, _p, _int],
+    "vgl_hip_lp_run": [_p, _p, _int, _int, _int, _int, _p, _p, C.POINTER(_i64), C.POINTER(LpStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
