@@ -363,6 +363,37 @@ int vgl_hip_lp_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction);
 int vgl_hip_lp_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction, int mode, int symmetric, int max_iterations, const int32_t *d_init,
                    int32_t *d_labels, int64_t *changed_history, vgl_hip_lp_stats *stats);
 
+/* Triangle counting (`tri`; `tc` in this library is transitive closure).  The reference has none, so this comment is the contract:
+ *   input     any vgl_hip_graph that owns all rows (not a sharded handle).  Only the stored OUTGOING CSR is read; the incoming CSR is not needed.
+ *   graph     the simple undirected graph underlying the stored entries: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *             Self-loops are ignored; multi-edges and an edge stored both ways count once.  A directed 3-cycle is one triangle.
+ *   triangles number of unordered vertex triples that are pairwise adjacent (int64, host).
+ *   d_per_vertex[v]  number of triangles that contain v (int64, device, may be NULL), in the graph's own numbering.  Sum over v = 3 * triangles.
+ *   d_degree[v]      degree of v in that simple undirected graph (int32, device, may be NULL).  The local clustering coefficient
+ *             2 t[v] / (d[v] (d[v] - 1)), 0 where d < 2, is derived by the callers in float64; there is no float on the device.
+ *   The answer does not depend on the vertex order used internally, on the VGL_TRI_* thresholds or on the order of the entries in a row.
+ * Method: every undirected edge is given to its endpoint that is LOWER in the total order (stored out-degree [+ in-degree when the incoming CSR
+ * exists], id) -- the oriented CSR, rows ascending by vertex id, built once by vgl_hip_tri_prepare (or by the first run), cached on the handle and
+ * freed with it -- and triangles = sum over oriented edges (a, b) of |N+(a) & N+(b)|.
+ * stats: undirected_edges = E' (simple undirected edges = entries of the oriented CSR); intersections = oriented edges evaluated = E';
+ * elements_examined = entries of second lists examined, exactly: for an edge (a, b) of a light row min(d+(a), d+(b)) (the shorter list is walked, each
+ * element searched in the longer one), of a table row d+(b) (N+(b) is streamed once against the LDS set of N+(a)), of a huge row d+(b) times the row's
+ * chunks, ceil(d+(a) / VGL_TRI_HUGE_CHUNK); algorithmic_bytes = 8 V + 4 E' + 4 elements_examined (the oriented CSR read once + every examined
+ * element); rows_* = rows with at least one oriented entry per class.  prepared_now = 1 when this call built the oriented CSR.
+ * Fails for a sharded handle and for triangles == NULL. */
+typedef struct {
+    int64_t triangles;
+    int64_t undirected_edges;
+    int64_t intersections;
+    int64_t elements_examined;
+    int64_t algorithmic_bytes;
+    int32_t max_oriented_degree;
+    int32_t prepared_now;
+    int64_t rows_light, rows_table, rows_huge;
+} vgl_hip_tri_stats;
+int vgl_hip_tri_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
+int vgl_hip_tri_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *triangles, int64_t *d_per_vertex, int32_t *d_degree, vgl_hip_tri_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -217,6 +217,10 @@ class Graph:
         """degree classes of `direction` (and the push schedule of its reverse) now, outside any timing (vgl_hip_lp_prepare)"""
         _l.check(self.ctx.L.vgl_hip_lp_prepare(self.ctx.h, self.h, {"out": 0, "in": 1}[direction]))
 
+    def prepare_triangle_count(self):
+        """the oriented CSR and row classes of triangle_count() now, outside any timing (vgl_hip_tri_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_tri_prepare(self.ctx.h, self.h))
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -466,6 +470,31 @@ def label_propagation(graph, max_iterations=20, direction="out", mode=LP_AUTO, l
     stats = _stats(st)
     stats["changed_history"] = [hist[i] for i in range(st.iterations)]
     return (out if raw else graph.to_original(out)), stats
+
+
+def triangle_count(graph, per_vertex=False, clustering=False, raw=False):
+    """triangles of the simple undirected graph underlying the stored outgoing CSR (the contract of vgl_hip_tri_run in include/vgl_hip.h; `tc` is
+    transitive closure, this is `tri`).  Returns (triangles, stats dict).  per_vertex=True adds stats["per_vertex"] (int64 tensor: triangles that
+    contain each vertex); clustering=True adds that, stats["degree"] (int32, undirected simple degree) and stats["clustering"] (float64:
+    2 t / (d (d - 1)), 0 where d < 2) -- all in ORIGINAL vertex order unless raw=True."""
+    ctx = graph.ctx
+    want_pv = bool(per_vertex or clustering)
+    pv = ctx.empty(graph.V, torch.int64) if want_pv else None
+    deg = ctx.empty(graph.V, torch.int32) if clustering else None
+    tri = C.c_int64()
+    st = _l.TriStats()
+    _l.check(ctx.L.vgl_hip_tri_run(ctx.h, graph.h, C.byref(tri), _ptr(pv), _ptr(deg), C.byref(st)))
+    stats = _stats(st)
+    if want_pv:
+        # 8-byte values: reordered with a torch index over the same mapping that to_original applies to 4-byte arrays
+        stats["per_vertex"] = pv if (raw or graph.fwd is None) else pv[graph.fwd.long()]
+    if clustering:
+        deg = deg if raw else graph.to_original(deg)
+        d = deg.to(torch.float64)
+        pairs = d * (d - 1.0)
+        stats["degree"] = deg
+        stats["clustering"] = torch.where(deg >= 2, 2.0 * stats["per_vertex"].to(torch.float64) / torch.clamp(pairs, min=1.0), torch.zeros_like(d))
+    return int(tri.value), stats
 
 
 def count_not_equal(ctx, a, b):

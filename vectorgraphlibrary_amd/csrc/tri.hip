@@ -1,0 +1,633 @@
+// tri.hip -- triangle counting (global count, per-vertex counts, undirected degrees) on the simple undirected graph underlying the stored outgoing
+// CSR.  The contract is written out in include/vgl_hip.h.  (`tc` in this tree is transitive closure; triangle counting is `tri` everywhere.)
+//
+// Prepare (once per graph, cached on the handle): every stored entry (u, v), u != v, becomes the 64-bit key  lower << 32 | higher  under the total
+// order  (stored out-degree [+ in-degree when the incoming CSR exists], id);  the keys are sorted (rocprim radix sort) and deduplicated (rocprim unique),
+// in pieces of consecutive `lower` vertices when all of them would need more scratch than VGL_TRI_SORT_CAP_MB.  The sorted keys ARE the oriented CSR:
+// row = high half, entry = low half, every row ascending BY VERTEX ID and free of duplicates.  The intersections compare vertex ids, so no rank array is
+// kept: the order only decides which endpoint owns an edge.  Degree order bounds every oriented row by about sqrt(2 E').
+//
+// Count: triangles = sum over oriented edges (a, b) of |N+(a) & N+(b)|; {a < b < c in the order} is found once, at (a, b) with witness c.
+// Rows a are split by oriented out-degree d = d+(a) (heaviest first inside a class):
+//   light (d <= VGL_TRI_LIGHT, <= 64)  : a wave takes 64 rows, expands their edges through an LDS owner map, and a group of G = 4 / 8 / 16 / 32 lanes
+//                                        (by d) takes one edge (a, b): the lanes stride over the shorter of N+(a), N+(b) and binary-search the longer.
+//   table (d <= VGL_TRI_TABLE, <= 8192): one 256-thread workgroup per row: N+(a) into an LDS open-addressing set (pow2 >= 2 d slots; 2048 slots up to
+//                                        VGL_TRI_TABLE_SMALL, <= 1024, else 16384), then groups of 16 lanes stream N+(b) for every b of N+(a) and probe.
+//   huge  (d > VGL_TRI_TABLE)          : the same kernel over (row, chunk) units: VGL_TRI_HUGE_CHUNK (<= 8192) entries of N+(a) per LDS set, the N+(b)
+//                                        streams repeated per chunk.  No scratch block; a row of any length is ceil(d / chunk) workgroups.
+// Hits are summed in registers, per wave, then one 64-bit atomic per wave.  With per-vertex counts (template parameter) the witness takes one atomic
+// per hit, b one per edge, a one per edge (light) or per unit (table, huge); without them none of these atomics exist in the kernel.
+#include "vgl_hip_internal.h"
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+namespace {
+
+constexpr int TRI_NCLS = 7;                 // light G = 4, 8, 16, 32 | table 2048 | table 16384 | huge
+constexpr int TRI_TS = 4, TRI_TL = 5, TRI_HUGE = 6;
+constexpr int TRI_LIGHT_MAX = 64;           // owner map: 64 rows x 64 entries of one byte per wave
+constexpr int TRI_SLOTS_S = 2048, TRI_SLOTS_L = 16384;
+constexpr int TRI_TG = 16;                  // lanes that stream one N+(b) in the table kernels
+constexpr int64_t TRI_MAX_GRID = 1 << 20;
+enum { TRI_C_TRI = 0, TRI_C_WORK = 1, TRI_NCNT = 2 };
+
+struct tri_bounds { int light, small, table; };
+
+__host__ __device__ inline int tri_class_of(int64_t d, tri_bounds b)
+{
+    if (d <= 0) return -1;
+    if (d <= b.light) return d <= 8 ? 0 : d <= 16 ? 1 : d <= 32 ? 2 : 3;
+    if (d <= b.small) return TRI_TS;
+    if (d <= b.table) return TRI_TL;
+    return TRI_HUGE;
+}
+
+__device__ __forceinline__ void tri_add64(int64_t *p, int64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+__device__ __forceinline__ uint32_t tri_hash(int32_t x, int bits) { return ((uint32_t)x * 0x9E3779B1u) >> (32 - bits); }
+
+// every lane of the wave, once, at the end of a count kernel
+__device__ __forceinline__ void tri_flush(int64_t *cnt, int64_t tri, int64_t work)
+{
+    tri = vgl_wave_reduce_add(tri);
+    work = vgl_wave_reduce_add(work);
+    if (vgl_lane() == 0) {
+        if (tri) tri_add64(cnt + TRI_C_TRI, tri);
+        if (work) tri_add64(cnt + TRI_C_WORK, work);
+    }
+}
+
+// ---- prepare ----
+// ord[v] = degree << 32 | v: u is below v in the order iff ord[u] < ord[v]
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_order(int32_t V, const int64_t *out_rp, const int64_t *in_rp, uint64_t *ord)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        int64_t d = out_rp[v + 1] - out_rp[v];
+        if (in_rp) d += in_rp[v + 1] - in_rp[v];
+        ord[v] = (uint64_t)min(d, (int64_t)0xFFFFFFFFll) << 32 | (uint64_t)v;
+    }
+}
+__device__ __forceinline__ int32_t tri_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
+{
+    int32_t lo = 0, hi = V;                     // invariant: rp[lo] <= e < rp[hi]
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (rp[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// stored entry e -> key (lower << 32 | higher); false for a self-loop
+__device__ __forceinline__ bool tri_key_of(const int64_t *rp, const int32_t *adj, int32_t V, const uint64_t *ord, int64_t e, uint64_t *key)
+{
+    const int32_t u = tri_row_of(rp, V, e), v = adj[e];
+    if (u == v || v < 0 || v >= V) return false;
+    const bool u_low = ord[u] < ord[v];
+    *key = (uint64_t)(uint32_t)(u_low ? u : v) << 32 | (uint32_t)(u_low ? v : u);
+    return true;
+}
+// entries per lower endpoint (only when the keys do not fit one piece)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_count_lower(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, const uint64_t *ord, int32_t *per_lower)
+{
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
+        uint64_t key;
+        if (tri_key_of(rp, adj, V, ord, e, &key)) atomicAdd(per_lower + (key >> 32), 1);
+    }
+}
+// the keys whose lower endpoint is in [v0, v1), appended in any order (the sort follows); never more than cap are written
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_emit(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, const uint64_t *ord, int32_t v0, int32_t v1,
+                                                             uint64_t *keys, unsigned long long *n_keys, int64_t cap)
+{
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
+        uint64_t key;
+        if (!tri_key_of(rp, adj, V, ord, e, &key)) continue;
+        const int32_t lower = (int32_t)(key >> 32);
+        if (lower < v0 || lower >= v1) continue;
+        const unsigned long long pos = atomicAdd(n_keys, 1ull);
+        if ((int64_t)pos < cap) keys[pos] = key;
+    }
+}
+// sorted unique keys of the piece [v0, v1) -> entries [base, base + n) of the oriented CSR; the higher endpoint's degree takes one add per entry
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_fill(const uint64_t *keys, int64_t n, int64_t base, int32_t *adj, int64_t adj_cap, int32_t V, int32_t *deg)
+{
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t hi = (int32_t)(uint32_t)keys[i];
+        if (base + i < adj_cap) adj[base + i] = hi;
+        if (hi >= 0 && hi < V) atomicAdd(deg + hi, 1);
+    }
+}
+// rowptr[r] = base + (keys of the piece below row r), r in [v0, v1]
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_rowptr(const uint64_t *keys, int64_t n, int32_t v0, int32_t v1, int64_t base, int64_t *rowptr)
+{
+    for (int64_t r = v0 + (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; r <= v1; r += (int64_t)gridDim.x * VGL_BLOCK) {
+        const uint64_t first = (uint64_t)r << 32;
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (keys[mid] < first) lo = mid + 1; else hi = mid;
+        }
+        rowptr[r] = base + lo;
+    }
+}
+// deg[v] += d+(v); the class histogram and the longest oriented row
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_degrees(int32_t V, const int64_t *rowptr, int32_t *deg, int32_t *max_deg)
+{
+    int m = 0;
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int d = (int)(rowptr[v + 1] - rowptr[v]);
+        deg[v] += d;
+        m = max(m, d);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+    if (vgl_lane() == 0 && m) atomicMax(max_deg, m);
+}
+// sort key of a row: class << 28 | (2^28 - 1 - min(d, 2^28 - 1)): classes ascending, heaviest rows first inside a class; rows without entries last
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_classify(int32_t V, const int64_t *rowptr, tri_bounds b, uint32_t *keys, int32_t *ids, int32_t *sizes)
+{
+    __shared__ int s_n[TRI_NCLS];
+    if (threadIdx.x < TRI_NCLS) s_n[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int64_t d = rowptr[v + 1] - rowptr[v];
+        const int cls = tri_class_of(d, b);
+        keys[v] = cls < 0 ? 0xFFFFFFFFu : (uint32_t)cls << 28 | (0x0FFFFFFFu - (uint32_t)min(d, (int64_t)0x0FFFFFFF));
+        ids[v] = (int32_t)v;
+        if (cls >= 0) atomicAdd(&s_n[cls], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < TRI_NCLS && s_n[threadIdx.x]) atomicAdd(sizes + threadIdx.x, s_n[threadIdx.x]);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_row_degrees(int32_t n, const int32_t *rows, const int64_t *rowptr, int32_t *out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) out[i] = (int32_t)(rowptr[rows[i] + 1] - rowptr[rows[i]]);
+}
+
+// ---- count: light rows ----
+// x in adj[s, s + n) (ascending, no duplicates)?
+__device__ __forceinline__ bool tri_contains(const int32_t *adj, int64_t s, int n, int32_t x)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (adj[s + mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && adj[s + lo] == x;
+}
+
+template <int G, bool PV>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_light(const int32_t *rows, int32_t n, const int64_t *rowptr, const int32_t *adj, int64_t *cnt, int64_t *pv)
+{
+    constexpr int EPW = 64 / G;                                 // edges per wave and round
+    __shared__ uint8_t s_owner[VGL_WAVES][64 * TRI_LIGHT_MAX];  // edge slot of the wave's 64 rows -> the lane that holds its row
+    uint8_t *owner = s_owner[vgl_wave()];
+    const int lane = vgl_lane(), gi = lane & (G - 1);
+    int64_t tri = 0, work = 0;
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t r = base + threadIdx.x;
+        int32_t a = 0;
+        int64_t sa = 0;
+        int da = 0;
+        if (r < n) {
+            a = rows[r];
+            sa = rowptr[a];
+            da = min((int)(rowptr[a + 1] - sa), TRI_LIGHT_MAX);      // (the class bound; the clamp keeps the map in bounds whatever the list holds)
+        }
+        const int incl = vgl_wave_incl_add(da), excl = incl - da;
+        const int total = __shfl(incl, 63);
+        __syncthreads();                                             // the map of the round before has been read
+        for (int k = 0; k < da; k++) owner[excl + k] = (uint8_t)lane;
+        __syncthreads();
+        for (int t0 = 0; t0 < total; t0 += EPW) {                    // (uniform over the wave: the shuffles below read every lane)
+            const int t = t0 + lane / G;
+            const bool valid = t < total;
+            const int own = valid ? owner[t] : 0;
+            const int32_t ea = __shfl(a, own);
+            const int64_t esa = __shfl(sa, own);
+            const int eda = __shfl(da, own), eex = __shfl(excl, own);
+            int hits = 0;
+            int32_t b = 0;
+            if (valid) {
+                b = adj[esa + (t - eex)];
+                const int64_t sb = rowptr[b];
+                const int db = (int)min(rowptr[b + 1] - sb, (int64_t)0x7FFFFFFF);
+                const bool a_short = eda <= db;
+                const int64_t ss = a_short ? esa : sb, ls = a_short ? sb : esa;
+                const int sn = a_short ? eda : db, ln = a_short ? db : eda;
+                if (gi == 0) work += sn;
+                for (int i = gi; i < sn; i += G) {
+                    const int32_t x = adj[ss + i];
+                    if (tri_contains(adj, ls, ln, x)) {
+                        hits++;
+                        if (PV) tri_add64(pv + x, 1);
+                    }
+                }
+            }
+            tri += hits;
+            if (PV) {
+#pragma unroll
+                for (int o = G / 2; o > 0; o >>= 1) hits += __shfl_xor(hits, o);
+                if (valid && gi == 0 && hits) { tri_add64(pv + ea, hits); tri_add64(pv + b, hits); }
+            }
+        }
+    }
+    tri_flush(cnt, tri, work);
+}
+
+// ---- count: table and huge rows ----
+// unit u: row unit_row[u]; entries [chunk * chunk_len, + chunk_len) of N+(a) go into the LDS set (unit_chunk == nullptr: the whole row, chunk 0), and
+// every N+(b), b in the WHOLE of N+(a), is streamed against it.  chunk_len <= SLOTS / 2.
+template <int SLOTS, bool PV>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit_row, const int32_t *unit_chunk, int32_t n_units, int chunk_len, const int64_t *rowptr,
+                                                              const int32_t *adj, int64_t *cnt, int64_t *pv)
+{
+    __shared__ int32_t s_tab[SLOTS];
+    __shared__ int64_t s_red[VGL_WAVES];
+    const int gi = threadIdx.x & (TRI_TG - 1);
+    int64_t tri = 0, work = 0;
+    for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {      // (uniform over the workgroup)
+        const int32_t a = unit_row[u];
+        const int64_t sa = rowptr[a];
+        const int64_t da = rowptr[a + 1] - sa;
+        const int64_t c0 = unit_chunk ? (int64_t)unit_chunk[u] * chunk_len : 0;
+        const int cn = (int)max((int64_t)0, min(da - c0, (int64_t)min(chunk_len, SLOTS / 2)));
+        int bits = 6;
+        while ((1 << bits) < 2 * cn) bits++;                         // <= log2(SLOTS) because cn <= SLOTS / 2
+        const uint32_t mask = (1u << bits) - 1u;
+        __syncthreads();                                             // the set of the unit before has been probed
+        for (int i = threadIdx.x; i <= (int)mask; i += VGL_BLOCK) s_tab[i] = -1;
+        __syncthreads();
+        for (int i = threadIdx.x; i < cn; i += VGL_BLOCK) {
+            const int32_t x = adj[sa + c0 + i];
+            uint32_t h = tri_hash(x, bits);
+            while (atomicCAS(&s_tab[h], -1, x) != -1) h = (h + 1) & mask;      // (no duplicates in a row: a taken slot holds another id)
+        }
+        __syncthreads();
+        int64_t unit_hits = 0;
+        for (int64_t j = threadIdx.x / TRI_TG; j < da; j += VGL_BLOCK / TRI_TG) {
+            const int32_t b = adj[sa + j];
+            const int64_t sb = rowptr[b], db = rowptr[b + 1] - sb;
+            int hits = 0;
+            for (int64_t p = gi; p < db; p += TRI_TG) {
+                const int32_t x = adj[sb + p];
+                uint32_t h = tri_hash(x, bits);
+                for (int32_t y = s_tab[h]; y != -1; y = s_tab[h]) {
+                    if (y == x) {
+                        hits++;
+                        if (PV) tri_add64(pv + x, 1);
+                        break;
+                    }
+                    h = (h + 1) & mask;
+                }
+            }
+            if (gi == 0) work += db;
+            unit_hits += hits;
+            if (PV) {                                                 // (the group's 16 lanes share j: they are all here)
+#pragma unroll
+                for (int o = TRI_TG / 2; o > 0; o >>= 1) hits += __shfl_xor(hits, o);
+                if (gi == 0 && hits) tri_add64(pv + b, hits);
+            }
+        }
+        tri += unit_hits;
+        if (PV) {
+            const int64_t row_hits = vgl_block_reduce_add(unit_hits, s_red);
+            if (threadIdx.x == 0 && row_hits) tri_add64(pv + a, row_hits);
+        }
+    }
+    tri_flush(cnt, tri, work);
+}
+
+template <class T> int tri_dev_alloc(T **p, size_t n) { VGL_HIP_TRY(hipMalloc((void **)p, sizeof(T) * (n ? n : 1))); return 0; }
+
+int64_t tri_env_int(vgl_hip_ctx *c, const char *name, int64_t dflt, int64_t lo, int64_t hi)
+{
+    const char *s = vgl_env(c, name);
+    const int64_t v = (s && *s) ? strtoll(s, nullptr, 10) : dflt;
+    return std::min(hi, std::max(lo, v));
+}
+
+unsigned tri_grid(int64_t work, int64_t per_block, int64_t cap = 16384) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
+
+// scratch of the prepare step: freed when the function leaves, however it leaves
+struct tri_scratch {
+    hipStream_t st;
+    std::vector<void *> blocks;
+    template <class T> int get(T **p, size_t n)
+    {
+        void *q = nullptr;
+        VGL_HIP_TRY(vgl_pool_alloc(st, &q, sizeof(T) * (n ? n : 1)));
+        blocks.push_back(q);
+        *p = static_cast<T *>(q);
+        return 0;
+    }
+    void drop(void *p)
+    {
+        auto it = std::find(blocks.begin(), blocks.end(), p);
+        if (it != blocks.end()) { vgl_pool_free(st, p); blocks.erase(it); }
+    }
+    ~tri_scratch() { for (void *p : blocks) vgl_pool_free(st, p); }
+};
+
+}  // namespace
+
+// The oriented CSR of a graph and the class lists of its rows (cached on the handle, freed with it)
+struct vgl_tri_cache {
+    int32_t V = 0;
+    int64_t edges = 0;                           // E'
+    int64_t *rowptr = nullptr;                   // V + 1
+    int32_t *adj = nullptr;                      // E', rows ascending by vertex id
+    int32_t *deg = nullptr;                      // V: degree in the simple undirected graph
+    int32_t max_deg = 0;                         // longest oriented row
+    // classes (rebuilt when the switches change; the oriented CSR stays)
+    int64_t key[4] = {-1, -1, -1, -1};
+    tri_bounds b{};
+    int32_t *rows = nullptr;                     // V: the rows of class c at [off[c], off[c] + size[c])
+    int32_t off[TRI_NCLS + 1] = {}, size[TRI_NCLS] = {};
+    int32_t n_units = 0, chunk_len = 0;          // huge: (row, chunk) units
+    int32_t *unit_row = nullptr, *unit_chunk = nullptr;
+    void free_classes()
+    {
+        for (void *p : {(void *)rows, (void *)unit_row, (void *)unit_chunk}) if (p) (void)hipFree(p);
+        rows = unit_row = unit_chunk = nullptr;
+        n_units = 0;
+    }
+    ~vgl_tri_cache()
+    {
+        free_classes();
+        for (void *p : {(void *)rowptr, (void *)adj, (void *)deg}) if (p) (void)hipFree(p);
+    }
+};
+
+void vgl_tri_cache_free(vgl_tri_cache *p) { delete p; }
+
+namespace {
+
+// the oriented CSR
+int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out)
+{
+    const int32_t V = g->V;
+    const vgl_dir_csr &d = g->out;
+    const int64_t E = d.edges;
+    hipStream_t st = c->stream;
+    vgl_tri_cache *p = new vgl_tri_cache();
+    struct guard { vgl_tri_cache *p; ~guard() { delete p; } } undo{p};
+    p->V = V;
+    VGL_TRY(tri_dev_alloc(&p->rowptr, (size_t)V + 1));
+    VGL_TRY(tri_dev_alloc(&p->deg, (size_t)V));
+    VGL_HIP_TRY(hipMemsetAsync(p->rowptr, 0, sizeof(int64_t) * ((size_t)V + 1), st));
+    VGL_HIP_TRY(hipMemsetAsync(p->deg, 0, sizeof(int32_t) * (size_t)std::max(V, 1), st));
+    if (V > 0 && E > 0) {
+        tri_scratch sc{st, {}};
+        // keys per piece: in + out buffers of 8 bytes each within the cap
+        const int64_t cap_keys = std::max<int64_t>(1, tri_env_int(c, "VGL_TRI_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
+        uint64_t *ord = nullptr;
+        VGL_TRY(sc.get(&ord, (size_t)V));
+        hipLaunchKernelGGL(vgl_k_tri_order, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, d.rowptr, g->in.rowptr, ord);
+        VGL_HIP_TRY(hipGetLastError());
+        std::vector<int32_t> bounds{0, V};                            // pieces of consecutive lower endpoints
+        int64_t piece_keys = E;
+        if (E > cap_keys) {
+            int32_t *per_lower = nullptr;
+            VGL_TRY(sc.get(&per_lower, (size_t)V));
+            VGL_HIP_TRY(hipMemsetAsync(per_lower, 0, sizeof(int32_t) * (size_t)V, st));
+            hipLaunchKernelGGL(vgl_k_tri_count_lower, dim3(tri_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, (const uint64_t *)ord, per_lower);
+            VGL_HIP_TRY(hipGetLastError());
+            std::vector<int32_t> h((size_t)V);
+            VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_lower, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+            sc.drop(per_lower);
+            bounds.assign(1, 0);
+            int64_t acc = 0;
+            piece_keys = 0;
+            for (int32_t v = 0; v < V; v++) {                         // greedy; a vertex with more keys than the cap is a piece of its own
+                if (acc > 0 && acc + h[(size_t)v] > cap_keys) { bounds.push_back(v); piece_keys = std::max(piece_keys, acc); acc = 0; }
+                acc += h[(size_t)v];
+            }
+            bounds.push_back(V);
+            piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
+        }
+        uint64_t *keys_a = nullptr, *keys_b = nullptr;
+        unsigned long long *n_keys = nullptr;
+        size_t *n_unique = nullptr;
+        int32_t *adj_tmp = nullptr;                                   // E entries bound E' from above
+        VGL_TRY(sc.get(&keys_a, (size_t)piece_keys));
+        VGL_TRY(sc.get(&keys_b, (size_t)piece_keys));
+        VGL_TRY(sc.get(&n_keys, 1));
+        VGL_TRY(sc.get(&n_unique, 1));
+        VGL_TRY(sc.get(&adj_tmp, (size_t)E));
+        int end_bit = 33;
+        while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
+        size_t temp_sort = 0, temp_unique = 0;
+        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a, keys_b, (size_t)piece_keys, 0, (unsigned)end_bit, st));
+        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b, keys_a, n_unique, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
+        const size_t temp_bytes = std::max(temp_sort, temp_unique);
+        char *temp = nullptr;
+        VGL_TRY(sc.get(&temp, temp_bytes));
+        int64_t base = 0;
+        for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
+            const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
+            VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
+            hipLaunchKernelGGL(vgl_k_tri_emit, dim3(tri_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, (const uint64_t *)ord, v0, v1, keys_a, n_keys,
+                               piece_keys);
+            VGL_HIP_TRY(hipGetLastError());
+            unsigned long long nk = 0;
+            VGL_HIP_TRY(hipMemcpyAsync(&nk, n_keys, sizeof(nk), hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+            if ((int64_t)nk > piece_keys) VGL_FAIL("tri_prepare: a piece holds more keys than were counted for it");
+            size_t nu = 0;
+            if (nk) {
+                size_t need = temp_bytes;
+                VGL_HIP_TRY(rocprim::radix_sort_keys(temp, need, keys_a, keys_b, (size_t)nk, 0, (unsigned)end_bit, st));
+                need = temp_bytes;
+                VGL_HIP_TRY(rocprim::unique(temp, need, keys_b, keys_a, n_unique, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
+                VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
+                VGL_HIP_TRY(hipStreamSynchronize(st));
+            }
+            if (base + (int64_t)nu > E) VGL_FAIL("tri_prepare: more oriented edges than stored entries");
+            hipLaunchKernelGGL(vgl_k_tri_fill, dim3(tri_grid((int64_t)nu, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a, (int64_t)nu, base, adj_tmp, E, V, p->deg);
+            hipLaunchKernelGGL(vgl_k_tri_rowptr, dim3(tri_grid((int64_t)v1 - v0 + 1, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a, (int64_t)nu, v0, v1, base,
+                               p->rowptr);
+            VGL_HIP_TRY(hipGetLastError());
+            base += (int64_t)nu;
+        }
+        p->edges = base;
+        VGL_TRY(tri_dev_alloc(&p->adj, (size_t)base));
+        if (base) VGL_HIP_TRY(hipMemcpyAsync(p->adj, adj_tmp, sizeof(int32_t) * (size_t)base, hipMemcpyDeviceToDevice, st));
+        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys);
+        VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(vgl_k_tri_degrees, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->deg, d_max);
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_HIP_TRY(hipMemcpyAsync(&p->max_deg, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        VGL_TRY(tri_dev_alloc(&p->adj, 1));
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+    }
+    undo.p = nullptr;
+    *out = p;
+    return 0;
+}
+
+// the class lists under the switches `key`
+int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
+{
+    hipStream_t st = c->stream;
+    const int32_t V = p->V;
+    p->free_classes();
+    std::fill(p->key, p->key + 4, -1);
+    p->b = tri_bounds{(int)key[0], (int)key[1], (int)key[2]};
+    p->chunk_len = (int32_t)key[3];
+    std::fill(p->size, p->size + TRI_NCLS, 0);
+    std::fill(p->off, p->off + TRI_NCLS + 1, 0);
+    VGL_TRY(tri_dev_alloc(&p->rows, (size_t)V));
+    if (V > 0) {
+        tri_scratch sc{st, {}};
+        uint32_t *k_in = nullptr, *k_out = nullptr;
+        int32_t *ids = nullptr, *sizes = nullptr;
+        VGL_TRY(sc.get(&k_in, (size_t)V));
+        VGL_TRY(sc.get(&k_out, (size_t)V));
+        VGL_TRY(sc.get(&ids, (size_t)V));
+        VGL_TRY(sc.get(&sizes, TRI_NCLS));
+        VGL_HIP_TRY(hipMemsetAsync(sizes, 0, sizeof(int32_t) * TRI_NCLS, st));
+        hipLaunchKernelGGL(vgl_k_tri_classify, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->b, k_in, ids, sizes);
+        VGL_HIP_TRY(hipGetLastError());
+        size_t need = 0;
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k_in, k_out, ids, p->rows, (size_t)V, 0, 32, st));
+        char *temp = nullptr;
+        VGL_TRY(sc.get(&temp, need));
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp, need, k_in, k_out, ids, p->rows, (size_t)V, 0, 32, st));
+        VGL_HIP_TRY(hipMemcpyAsync(p->size, sizes, sizeof(p->size), hipMemcpyDeviceToHost, st));
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+        for (int k = 0; k < TRI_NCLS; k++) p->off[k + 1] = p->off[k] + p->size[k];
+        const int32_t nh = p->size[TRI_HUGE];
+        if (nh) {                                                     // (row, chunk) units of the huge rows, heaviest row first
+            int32_t *d_deg = nullptr;
+            VGL_TRY(sc.get(&d_deg, (size_t)nh));
+            const int32_t *hrows = p->rows + p->off[TRI_HUGE];
+            hipLaunchKernelGGL(vgl_k_tri_row_degrees, dim3(tri_grid(nh, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, nh, hrows, (const int64_t *)p->rowptr, d_deg);
+            VGL_HIP_TRY(hipGetLastError());
+            std::vector<int32_t> hr((size_t)nh), hd((size_t)nh), ur, uc;
+            VGL_HIP_TRY(hipMemcpyAsync(hr.data(), hrows, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipMemcpyAsync(hd.data(), d_deg, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+            for (int32_t i = 0; i < nh; i++)
+                for (int64_t k = 0; k < vgl_ceil_div(hd[(size_t)i], p->chunk_len); k++) { ur.push_back(hr[(size_t)i]); uc.push_back((int32_t)k); }
+            p->n_units = (int32_t)ur.size();
+            VGL_TRY(tri_dev_alloc(&p->unit_row, ur.size()));
+            VGL_TRY(tri_dev_alloc(&p->unit_chunk, uc.size()));
+            VGL_HIP_TRY(hipMemcpyAsync(p->unit_row, ur.data(), sizeof(int32_t) * ur.size(), hipMemcpyHostToDevice, st));
+            VGL_HIP_TRY(hipMemcpyAsync(p->unit_chunk, uc.data(), sizeof(int32_t) * uc.size(), hipMemcpyHostToDevice, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    std::copy(key, key + 4, p->key);
+    return 0;
+}
+
+int tri_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out, bool *built)
+{
+    int64_t key[4];
+    key[0] = tri_env_int(c, "VGL_TRI_LIGHT", 64, 0, TRI_LIGHT_MAX);
+    key[1] = tri_env_int(c, "VGL_TRI_TABLE_SMALL", 1024, key[0], TRI_SLOTS_S / 2);
+    key[2] = tri_env_int(c, "VGL_TRI_TABLE", 8192, key[1], TRI_SLOTS_L / 2);
+    key[3] = tri_env_int(c, "VGL_TRI_HUGE_CHUNK", 8192, 16, TRI_SLOTS_L / 2);
+    *built = false;
+    if (!g->tri) {
+        VGL_TRY(tri_build_csr(c, g, &g->tri));
+        *built = true;
+    }
+    if (!std::equal(key, key + 4, g->tri->key)) {
+        VGL_HIP_TRY(hipStreamSynchronize(c->stream));
+        VGL_TRY(tri_build_classes(c, g->tri, key));
+    }
+    *out = g->tri;
+    return 0;
+}
+
+template <bool PV>
+int tri_count(vgl_hip_ctx *c, const vgl_tri_cache &k, int64_t *cnt, int64_t *pv)
+{
+    const int64_t *rp = k.rowptr;
+    const int32_t *adj = k.adj;
+#define TRI_LIGHT(cls, G)                                                                                                                          \
+    if (k.size[cls]) {                                                                                                                             \
+        vgl_timed_launch tl(c, "tri_light");                                                                                                       \
+        hipLaunchKernelGGL((vgl_k_tri_light<G, PV>), dim3(tri_grid(k.size[cls], VGL_BLOCK, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)(k.rows + k.off[cls]), \
+                           k.size[cls], rp, adj, cnt, pv);                                                                                          \
+    }
+    TRI_LIGHT(0, 4) TRI_LIGHT(1, 8) TRI_LIGHT(2, 16) TRI_LIGHT(3, 32)
+#undef TRI_LIGHT
+    if (k.size[TRI_TS]) {
+        vgl_timed_launch tl(c, "tri_table");
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_S, PV>), dim3(tri_grid(k.size[TRI_TS], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
+                           (const int32_t *)(k.rows + k.off[TRI_TS]), (const int32_t *)nullptr, k.size[TRI_TS], TRI_SLOTS_S / 2, rp, adj, cnt, pv);
+    }
+    if (k.size[TRI_TL]) {
+        vgl_timed_launch tl(c, "tri_table");
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(tri_grid(k.size[TRI_TL], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
+                           (const int32_t *)(k.rows + k.off[TRI_TL]), (const int32_t *)nullptr, k.size[TRI_TL], TRI_SLOTS_L / 2, rp, adj, cnt, pv);
+    }
+    if (k.n_units) {
+        vgl_timed_launch tl(c, "tri_huge");
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(tri_grid(k.n_units, 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)k.unit_row,
+                           (const int32_t *)k.unit_chunk, k.n_units, k.chunk_len, rp, adj, cnt, pv);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vgl_hip_tri_prepare(vgl_hip_ctx *c, vgl_hip_graph *g)
+{
+    if (!c || !g) VGL_FAIL("tri_prepare: null argument");
+    if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("tri_prepare: graph handle must own all rows (triangle counting has no sharded form)");
+    vgl_tri_cache *k = nullptr;
+    bool built = false;
+    VGL_TRY(tri_ensure(c, g, &k, &built));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vgl_hip_tri_run(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *triangles, int64_t *d_per_vertex, int32_t *d_degree, vgl_hip_tri_stats *stats)
+{
+    if (!c || !g) VGL_FAIL("tri_run: null argument");
+    if (!triangles) VGL_FAIL("tri_run: triangles must not be NULL");
+    if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("tri_run: graph handle must own all rows (triangle counting has no sharded form)");
+    vgl_tri_cache *k = nullptr;
+    bool built = false;
+    VGL_TRY(tri_ensure(c, g, &k, &built));
+    const int32_t V = g->V;
+    void *block = nullptr;                                            // the one scratch draw: the two counters
+    VGL_HIP_TRY(vgl_pool_alloc(c->stream, &block, sizeof(int64_t) * TRI_NCNT));
+    struct guard { hipStream_t st; void *p; ~guard() { vgl_pool_free(st, p); } } release{c->stream, block};
+    int64_t *cnt = static_cast<int64_t *>(block);
+    VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int64_t) * TRI_NCNT, c->stream));
+    if (d_per_vertex && V > 0) VGL_HIP_TRY(hipMemsetAsync(d_per_vertex, 0, sizeof(int64_t) * (size_t)V, c->stream));
+    if (d_degree && V > 0) VGL_HIP_TRY(hipMemcpyAsync(d_degree, k->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
+    if (d_per_vertex) VGL_TRY(tri_count<true>(c, *k, cnt, d_per_vertex));
+    else VGL_TRY(tri_count<false>(c, *k, cnt, nullptr));
+    int64_t h[TRI_NCNT] = {0, 0};
+    VGL_HIP_TRY(hipMemcpyAsync(h, cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));
+    *triangles = h[TRI_C_TRI];
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->triangles = h[TRI_C_TRI];
+        stats->undirected_edges = k->edges;
+        stats->intersections = k->edges;
+        stats->elements_examined = h[TRI_C_WORK];
+        stats->algorithmic_bytes = 8 * (int64_t)V + 4 * k->edges + 4 * h[TRI_C_WORK];
+        stats->max_oriented_degree = k->max_deg;
+        stats->prepared_now = built ? 1 : 0;
+        stats->rows_light = (int64_t)k->size[0] + k->size[1] + k->size[2] + k->size[3];
+        stats->rows_table = (int64_t)k->size[TRI_TS] + k->size[TRI_TL];
+        stats->rows_huge = k->size[TRI_HUGE];
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -146,8 +146,10 @@ struct vgl_hip_graph {
                                                                 // once per graph, every vgl_hip_sssp_pull_plan is a plan over it with weights of its own
     std::string blk_path_key;                    // the layout switches it was built under (fuse threshold, unit sizes, piece bound: the tests vary them per plan)
     struct vgl_lp_cache *lp[2] = {nullptr, nullptr};   // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
+    struct vgl_tri_cache *tri = nullptr;         // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
 };
 void vgl_lp_cache_free(struct vgl_lp_cache *p);  // lp.hip
+void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
 
 struct vgl_hip_frontier {
     vgl_hip_graph *g = nullptr;

@@ -44,6 +44,12 @@ class LpStats(C.Structure):
                 ("rows_processed", C.c_int64), ("edges_examined", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class TriStats(C.Structure):
+    _fields_ = [("triangles", C.c_int64), ("undirected_edges", C.c_int64), ("intersections", C.c_int64), ("elements_examined", C.c_int64),
+                ("algorithmic_bytes", C.c_int64), ("max_oriented_degree", C.c_int32), ("prepared_now", C.c_int32), ("rows_light", C.c_int64),
+                ("rows_table", C.c_int64), ("rows_huge", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -122,6 +128,8 @@ _SIGNATURES = {
     "vgl_hip_cc_run_symmetric": [_p, _p, _p, C.POINTER(CcStats)],
     "vgl_hip_lp_prepare": [_p, _p, _int],
     "vgl_hip_lp_run": [_p, _p, _int, _int, _int, _int, _p, _p, C.POINTER(_i64), C.POINTER(LpStats)],
+    "vgl_hip_tri_prepare": [_p, _p],
+    "vgl_hip_tri_run": [_p, _p, C.POINTER(_i64), _p, _p, C.POINTER(TriStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
