@@ -1163,7 +1163,7 @@ static int vgl_bfs_bu_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, 
         vgl_timed_launch tl(c, "bfs_bottom_up");
         hipLaunchKernelGGL(vgl_k_bu_probe<true>, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
                            g->in.rowptr, g->in.adj, visited, g->bm_in_nz, front, next, levels, next_level, g->heavy, g->bu_partials,
-                           g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head), g->bm_in_long,
+                           g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head.p), g->bm_in_long,
                            (const int32_t *)g->in_nz_rank, g->in_nz_rows, c->d_counters, (volatile int64_t *)c->h_counters, seq);
     }
     VGL_HIP_TRY(hipGetLastError());
@@ -1178,13 +1178,13 @@ static int vgl_bfs_blocked_level(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *leve
         if (p.n_g_units > 0) {
             vgl_timed_launch tl(c, "bfs_blk_gather");
             hipLaunchKernelGGL(vgl_k_bfs_blk_gather, dim3((unsigned)p.n_g_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p.g_units,
-                               (const uint16_t *)p.g_lo, (const uint32_t *)p.mid_to_a, reinterpret_cast<uint64_t *>(p.vals), p.g_count,
+                               (const uint16_t *)p.g_lo, (const uint32_t *)p.mid_to_a, reinterpret_cast<uint64_t *>(p.vals.p), p.g_count,
                                (const uint64_t *)g->bm_front, (int64_t)g->row_begin >> 6);
         }
         if (p.n_a_units > 0) {
             vgl_timed_launch tl(c, "bfs_blk_accumulate");
             hipLaunchKernelGGL(vgl_k_bfs_blk_accumulate, dim3((unsigned)p.n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p.a_units,
-                               (const uint16_t *)p.a_lo, reinterpret_cast<const uint64_t *>(p.vals), p.a_count, (const uint64_t *)g->bm_visited,
+                               (const uint16_t *)p.a_lo, reinterpret_cast<const uint64_t *>(p.vals.p), p.a_count, (const uint64_t *)g->bm_visited,
                                g->bm_next, levels, next_level);
         }
     }
@@ -1344,7 +1344,7 @@ struct vgl_bfs_traversal {
             {
                 vgl_timed_launch tl(c, "gnf");
                 hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, (const int32_t *)levels,
-                                   cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, g->bu_partials,
+                                   cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front.p, (uint8_t *)g->bm_visited.p, g->bu_partials,
                                    g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters, (volatile int64_t *)c->h_counters, seq);
             }
             VGL_HIP_TRY(hipGetLastError());
@@ -1361,7 +1361,7 @@ struct vgl_bfs_traversal {
             front = vgl_bfs_front::counted_bitmap;
         } else {
             vgl_pred_equal_i32 pred{levels, cur};
-            VGL_TRY(vgl_gnf_run(c, g, pred, g->ids, g->offs, (uint8_t *)g->bm_front, (uint8_t *)g->bm_visited, nullptr, false, true));
+            VGL_TRY(vgl_gnf_run(c, g, pred, g->ids, g->offs, (uint8_t *)g->bm_front.p, (uint8_t *)g->bm_visited.p, nullptr, false, true));
             front = vgl_bfs_front::counted_scan;
             done = "count done (levels scan)";
         }

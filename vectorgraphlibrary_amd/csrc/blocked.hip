@@ -12,23 +12,6 @@
 
 namespace {
 
-struct dev_bufs {                                   // frees whatever the build still holds when it leaves, error or not
-    hipStream_t st = nullptr;
-    std::vector<void *> ptrs;
-    template <class T> hipError_t alloc(T **p, size_t n)
-    {
-        hipError_t e = vgl_pool_alloc(st, (void **)p, sizeof(T) * std::max<size_t>(n, 1));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-    void release(void *p)
-    {
-        for (auto &q : ptrs) if (q == p) { vgl_pool_free(st, q); q = nullptr; }
-    }
-    void free_all() { for (auto &q : ptrs) if (q) { vgl_pool_free(st, q); q = nullptr; } }
-    ~dev_bufs() { free_all(); }
-};
-
 // edges per (gather block, accumulate block) pair of VGL_FBLK x VGL_FBLK ids: count16[gb16 * nA16 + ab16].  The rows of a 2048-edge tile
 // lie in one row block almost always, so the tile counts its column blocks in LDS and adds the non-zero counters to memory once (a
 // global atomic per edge would serialise on the hub pairs: millions of increments of one address).
@@ -217,12 +200,6 @@ struct stage_trace {
     }
 };
 
-int env_int(vgl_hip_ctx *c, const char *name, int dflt)
-{
-    const char *s = vgl_env(c, name);
-    return (s && *s) ? atoi(s) : dflt;
-}
-
 // cut blocks into units of at most `cap` chunks; bounds[b] .. bounds[b+1] = chunk range of block b
 void make_units(const std::vector<uint32_t> &bounds, uint32_t cap, bool keep_empty, bool want_slabs, std::vector<vgl_blk_unit> &units,
                 std::vector<vgl_blk_multi> &multi, int &n_slabs)
@@ -245,21 +222,6 @@ void make_units(const std::vector<uint32_t> &bounds, uint32_t cap, bool keep_emp
 }
 
 }  // namespace
-
-vgl_blocked_layout::~vgl_blocked_layout()
-{
-    for (const vgl_blocked_piece &p : pieces) {
-        if (p.piece_rowptr) hipFree(p.piece_rowptr);
-        if (p.piece_tile_row) hipFree(p.piece_tile_row);
-        void *ptrs[] = {p.g_lo, p.a_lo, p.mid_to_a, p.vals, p.g_units, p.a_units, p.multi, p.slabs, p.f_g_lo, p.f_a_lo, p.f_segs, p.f_units, p.w_src_mid, p.w_src_f};
-        for (void *q : ptrs) vgl_pool_free(stream, q);
-    }
-}
-
-vgl_blocked_plan::~vgl_blocked_plan()
-{
-    for (const vgl_blocked_values &v : values) { vgl_pool_free(stream, v.w_mid); vgl_pool_free(stream, v.f_w); }
-}
 
 // one piece over the rows of `dir` (all rows of the direction, or a row-range piece of it: row_off = number of rows before the piece,
 // nrows_total = rows of the whole direction, w_base = CSR position of its first edge); what it allocates belongs to the layout at once
@@ -286,34 +248,31 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
                       (int64_t)nG16 * nA16 + nseg + 1 < (1LL << 31);
     const uint32_t nseg16 = fuse ? nG16 * nA16 : 0, nkeys = nseg + 1 + nseg16;
 
-    dev_bufs tmp;
-    tmp.st = st;
     stage_trace trace(c, st);
     std::unique_ptr<vgl_timed_launch> timed;
-    uint32_t *keys = nullptr, *keys2 = nullptr, *packed = nullptr, *packed2 = nullptr, *seg_first = nullptr, *seg_end = nullptr;
-    uint32_t *nch_a = nullptr, *nch_m = nullptr, *a_start = nullptr, *m_start = nullptr, *picked = nullptr;
-    uint32_t *idx2 = nullptr;                                       // CSR positions in sorted order (layouts with edge values)
-    void *sort_tmp = nullptr;
-    uint32_t *count16 = nullptr;
-    VGL_HIP_TRY(tmp.alloc(&seg_first, (size_t)nkeys + 1));
-    VGL_HIP_TRY(tmp.alloc(&seg_end, (size_t)nkeys + 1));
-    VGL_HIP_TRY(tmp.alloc(&nch_a, (size_t)nseg + 1));
-    VGL_HIP_TRY(tmp.alloc(&nch_m, (size_t)nseg + 1));
-    VGL_HIP_TRY(tmp.alloc(&a_start, (size_t)nseg + 1));
-    VGL_HIP_TRY(tmp.alloc(&m_start, (size_t)nseg + 1));
-    VGL_HIP_TRY(tmp.alloc(&picked, (size_t)nG + nA + 2));
+    // temporaries of the build: freed when it leaves, error or not
+    vgl_dev<uint32_t> keys, keys2, keys3, packed, packed2, seg_first, seg_end, nch_a, nch_m, a_start, m_start, picked, count16, d_chunk0, d_key;
+    vgl_dev<uint32_t> idx2;                                         // CSR positions in sorted order (layouts with edge values)
+    vgl_dev<char> sort_tmp, scan_tmp;
+    VGL_TRY(seg_first.alloc(st, (size_t)nkeys + 1));
+    VGL_TRY(seg_end.alloc(st, (size_t)nkeys + 1));
+    VGL_TRY(nch_a.alloc(st, (size_t)nseg + 1));
+    VGL_TRY(nch_m.alloc(st, (size_t)nseg + 1));
+    VGL_TRY(a_start.alloc(st, (size_t)nseg + 1));
+    VGL_TRY(m_start.alloc(st, (size_t)nseg + 1));
+    VGL_TRY(picked.alloc(st, (size_t)nG + nA + 2));
     VGL_HIP_TRY(hipMemsetAsync(seg_first, 0, sizeof(uint32_t) * ((size_t)nkeys + 1), st));
     VGL_HIP_TRY(hipMemsetAsync(seg_end, 0, sizeof(uint32_t) * ((size_t)nkeys + 1), st));
     if (E > 0) {
-        VGL_HIP_TRY(tmp.alloc(&keys, (size_t)E));
-        VGL_HIP_TRY(tmp.alloc(&keys2, (size_t)E));
-        VGL_HIP_TRY(tmp.alloc(&packed, (size_t)E));
-        VGL_HIP_TRY(tmp.alloc(&packed2, (size_t)E));
+        VGL_TRY(keys.alloc(st, (size_t)E));
+        VGL_TRY(keys2.alloc(st, (size_t)E));
+        VGL_TRY(packed.alloc(st, (size_t)E));
+        VGL_TRY(packed2.alloc(st, (size_t)E));
         trace.mark("allocate keys");
         // (timing on: the stream time from here to the fill kernel is booked under "blk_plan_build" -- what the build costs the GPU,
         // without the allocator, which can stall for seconds right after tens of GB were freed)
         if (fuse) {
-            VGL_HIP_TRY(tmp.alloc(&count16, (size_t)nseg16));
+            VGL_TRY(count16.alloc(st, (size_t)nseg16));
             VGL_HIP_TRY(hipMemsetAsync(count16, 0, sizeof(uint32_t) * (size_t)nseg16, st));
         }
         timed.reset(new vgl_timed_launch(c, "blk_plan_build"));
@@ -330,24 +289,22 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
         int bits = 1;
         while ((1ull << bits) <= (unsigned long long)nkeys) bits++;      // every key, the sentinel nseg and the fused range behind it, must be representable
         size_t need = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys, keys2, packed, packed2, (size_t)E, 0, bits, st));
-        VGL_HIP_TRY(tmp.alloc((char **)&sort_tmp, std::max<size_t>(need, 16)));
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp, need, keys, keys2, packed, packed2, (size_t)E, 0, bits, st));
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys.p, keys2.p, packed.p, packed2.p, (size_t)E, 0, bits, st));
+        VGL_TRY(sort_tmp.alloc(st, std::max<size_t>(need, 16)));
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, need, keys.p, keys2.p, packed.p, packed2.p, (size_t)E, 0, bits, st));
         trace.mark("sort (block pair, packed ids)");
         if (keep_edge_index) {                                      // same keys, same stable sort: the CSR positions land in the order of the entries
             VGL_HIP_TRY(hipStreamSynchronize(st));
-            tmp.release(packed);
-            packed = nullptr;
-            VGL_HIP_TRY(tmp.alloc(&idx2, (size_t)E));
+            packed.reset();
+            VGL_TRY(idx2.alloc(st, (size_t)E));
             size_t need2 = 0;
-            uint32_t *keys3 = nullptr;
-            VGL_HIP_TRY(tmp.alloc(&keys3, (size_t)E));
+            VGL_TRY(keys3.alloc(st, (size_t)E));
             rocprim::counting_iterator<uint32_t> positions(0);
-            VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, keys, keys3, positions, idx2, (size_t)E, 0, bits, st));
+            VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, keys.p, keys3.p, positions, idx2.p, (size_t)E, 0, bits, st));
             if (need2 > need) VGL_FAIL("blocked_plan_build: radix sort scratch grew between two calls of the same size");
-            VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp, need2, keys, keys3, positions, idx2, (size_t)E, 0, bits, st));
+            VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, need2, keys.p, keys3.p, positions, idx2.p, (size_t)E, 0, bits, st));
             VGL_HIP_TRY(hipStreamSynchronize(st));
-            tmp.release(keys3);
+            keys3.reset();
             trace.mark("sort edge positions");
         }
         hipLaunchKernelGGL(vgl_k_blk_runs, dim3((unsigned)std::min<int64_t>(16384, vgl_ceil_div(E, VGL_BLOCK))), dim3(VGL_BLOCK), 0, st, E,
@@ -359,11 +316,10 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
     VGL_HIP_TRY(hipGetLastError());
     {
         size_t need = 0;
-        void *scan_tmp = nullptr;
-        VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, nch_a, a_start, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
-        VGL_HIP_TRY(tmp.alloc((char **)&scan_tmp, std::max<size_t>(need, 16)));
-        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp, need, nch_a, a_start, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
-        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp, need, nch_m, m_start, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
+        VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, nch_a.p, a_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
+        VGL_TRY(scan_tmp.alloc(st, std::max<size_t>(need, 16)));
+        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, need, nch_a.p, a_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
+        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, need, nch_m.p, m_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
     }
     trace.mark("runs, chunk counts, scans");
     // chunk ranges of the blocks on both sides -> host
@@ -384,11 +340,11 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
         p->edges = kept_end;
     }
     const size_t slots = (size_t)p->nchunks * VGL_CHUNK;
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->g_lo, sizeof(uint16_t) * std::max<size_t>(slots, 8)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->a_lo, sizeof(uint16_t) * std::max<size_t>(slots, 8)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->vals, value_bits == 1 ? sizeof(uint64_t) * std::max<size_t>(p->nchunks, 1) : sizeof(uint32_t) * std::max<size_t>(slots, 8)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->mid_to_a, sizeof(uint32_t) * std::max<size_t>(p->nchunks, 1)));
-    if (keep_edge_index) VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_mid, sizeof(uint32_t) * std::max<size_t>(slots, 8)));
+    VGL_TRY(p->g_lo.alloc(st, std::max<size_t>(slots, 8)));
+    VGL_TRY(p->a_lo.alloc(st, std::max<size_t>(slots, 8)));
+    VGL_TRY(p->vals.alloc(st, value_bits == 1 ? 2 * std::max<size_t>(p->nchunks, 1) : std::max<size_t>(slots, 8)));      // (one 64-bit word per chunk)
+    VGL_TRY(p->mid_to_a.alloc(st, std::max<size_t>(p->nchunks, 1)));
+    if (keep_edge_index) VGL_TRY(p->w_src_mid.alloc(st, std::max<size_t>(slots, 8)));
     p->w_base = w_base;
     trace.mark("allocate plan arrays");
     if (p->nchunks > 0) {
@@ -403,7 +359,7 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
         // one workgroup must not be left alone with it), pieces grouped into units per gather block
         std::vector<uint32_t> cnt((size_t)nseg16);
         VGL_TRY(vgl_hip_memcpy_d2h(c, cnt.data(), count16, sizeof(uint32_t) * cnt.size()));
-        const uint32_t f_cap = (uint32_t)std::max(64, env_int(c, "VGL_BLK_FUSED_UNIT", 4096));
+        const uint32_t f_cap = (uint32_t)std::max(64, (int)vgl_env_int(c, "VGL_BLK_FUSED_UNIT", 4096, INT_MIN, INT_MAX));
         std::vector<uint32_t> seg_chunk0, seg_key;
         std::vector<vgl_blk_fseg> fsegs;
         std::vector<vgl_blk_funit> funits;
@@ -437,17 +393,16 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
             std::stable_sort(funits.begin(), funits.end(), [&](const vgl_blk_funit &x, const vgl_blk_funit &y) { return unit_chunks(x) > unit_chunks(y); });
             p->n_f_units = (int)funits.size();
             seg_chunk0.push_back(chunk);
-            uint32_t *d_chunk0 = nullptr, *d_key = nullptr;
-            VGL_HIP_TRY(tmp.alloc(&d_chunk0, seg_chunk0.size()));
-            VGL_HIP_TRY(tmp.alloc(&d_key, seg_key.size()));
+            VGL_TRY(d_chunk0.alloc(st, seg_chunk0.size()));
+            VGL_TRY(d_key.alloc(st, seg_key.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, d_chunk0, seg_chunk0.data(), sizeof(uint32_t) * seg_chunk0.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, d_key, seg_key.data(), sizeof(uint32_t) * seg_key.size()));
             const size_t fslots = (size_t)chunk * VGL_CHUNK;
-            VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_g_lo, sizeof(uint16_t) * fslots));
-            VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_a_lo, sizeof(uint16_t) * fslots));
-            if (keep_edge_index) VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->w_src_f, sizeof(uint32_t) * fslots));
-            VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_segs, sizeof(vgl_blk_fseg) * fsegs.size()));
-            VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->f_units, sizeof(vgl_blk_funit) * funits.size()));
+            VGL_TRY(p->f_g_lo.alloc(st, fslots));
+            VGL_TRY(p->f_a_lo.alloc(st, fslots));
+            if (keep_edge_index) VGL_TRY(p->w_src_f.alloc(st, fslots));
+            VGL_TRY(p->f_segs.alloc(st, fsegs.size()));
+            VGL_TRY(p->f_units.alloc(st, funits.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, p->f_segs, fsegs.data(), sizeof(vgl_blk_fseg) * fsegs.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, p->f_units, funits.data(), sizeof(vgl_blk_funit) * funits.size()));
             hipLaunchKernelGGL(vgl_k_blk_fill_fused, dim3((unsigned)std::min<int64_t>(65536, vgl_ceil_div(chunk, VGL_WAVES))), dim3(VGL_BLOCK), 0, st, chunk,
@@ -467,25 +422,23 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
     // (accumulate blocks up to 1.5x the average stay whole -- on a uniform graph every block is one unit and nothing goes through slabs --
     // but never beyond 16 K chunks = 1 M entries, ~0.25 ms of one CU's share of the HBM stream)
     const uint32_t avg_a = (uint32_t)(p->nchunks / nA);
-    const uint32_t g_cap = (uint32_t)std::max(64, env_int(c, "VGL_BLK_GATHER_UNIT", 4096));
-    const uint32_t a_cap = (uint32_t)std::max(64, env_int(c, "VGL_BLK_ACCUM_UNIT", (int)std::min<uint32_t>(16384, std::max<uint32_t>(4096, avg_a + avg_a / 2))));
+    const uint32_t g_cap = (uint32_t)std::max(64, (int)vgl_env_int(c, "VGL_BLK_GATHER_UNIT", 4096, INT_MIN, INT_MAX));
+    const uint32_t a_cap = (uint32_t)std::max(64, (int)vgl_env_int(c, "VGL_BLK_ACCUM_UNIT", std::min<uint32_t>(16384, std::max<uint32_t>(4096, avg_a + avg_a / 2)), INT_MIN, INT_MAX));
     std::vector<vgl_blk_unit> gu, au;
     std::vector<vgl_blk_multi> multi, none;
     int dummy = 0;
     make_units(g_bounds, g_cap, false, false, gu, none, dummy);
     make_units(a_bounds, a_cap, true, true, au, multi, p->n_slabs);
     p->n_g_units = (int)gu.size(); p->n_a_units = (int)au.size(); p->n_multi = (int)multi.size();
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->g_units, sizeof(vgl_blk_unit) * std::max<size_t>(gu.size(), 1)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->a_units, sizeof(vgl_blk_unit) * std::max<size_t>(au.size(), 1)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->multi, sizeof(vgl_blk_multi) * std::max<size_t>(multi.size(), 1)));
+    VGL_TRY(p->g_units.alloc(st, std::max<size_t>(gu.size(), 1)));
+    VGL_TRY(p->a_units.alloc(st, std::max<size_t>(au.size(), 1)));
+    VGL_TRY(p->multi.alloc(st, std::max<size_t>(multi.size(), 1)));
     if (!gu.empty()) VGL_TRY(vgl_hip_memcpy_h2d(c, p->g_units, gu.data(), sizeof(vgl_blk_unit) * gu.size()));
     if (!au.empty()) VGL_TRY(vgl_hip_memcpy_h2d(c, p->a_units, au.data(), sizeof(vgl_blk_unit) * au.size()));
     if (!multi.empty()) VGL_TRY(vgl_hip_memcpy_h2d(c, p->multi, multi.data(), sizeof(vgl_blk_multi) * multi.size()));
-    VGL_HIP_TRY(vgl_pool_alloc(st, &p->slabs, sizeof(uint32_t) * VGL_BLK * (size_t)std::max(p->n_slabs, 1)));
+    VGL_TRY(p->slabs.alloc(st, VGL_BLK * (size_t)std::max(p->n_slabs, 1)));
     VGL_HIP_TRY(hipStreamSynchronize(st));
     trace.mark("work units");
-    tmp.free_all();
-    trace.mark("free temporaries");
     return 0;
 }
 
@@ -518,13 +471,12 @@ int vgl_blocked_plan_share(vgl_hip_ctx *c, std::shared_ptr<const vgl_blocked_lay
 {
     if (!c || !layout || !out) VGL_FAIL("blocked_plan_share: null argument");
     auto p = std::make_unique<vgl_blocked_plan>();
-    p->stream = c->stream;
     for (const vgl_blocked_piece &s : layout->pieces) {
         if ((s.nchunks > 0 && !s.w_src_mid) || (s.f_nchunks > 0 && !s.w_src_f)) VGL_FAIL("blocked_plan_share: the layout was built without its edge index");
         vgl_blocked_values &v = p->values.emplace_back();
         const size_t slots = (size_t)s.nchunks * VGL_CHUNK, fslots = (size_t)s.f_nchunks * VGL_CHUNK;
-        VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&v.w_mid, sizeof(float) * std::max<size_t>(slots, 8)));
-        if (fslots) VGL_HIP_TRY(vgl_pool_alloc(c->stream, (void **)&v.f_w, sizeof(float) * fslots));
+        VGL_TRY(v.w_mid.alloc(c->stream, std::max<size_t>(slots, 8)));
+        if (fslots) VGL_TRY(v.f_w.alloc(c->stream, fslots));
     }
     p->layout = std::move(layout);
     *out = std::move(p);
@@ -538,7 +490,6 @@ int vgl_blocked_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int
     if (!c || !out) VGL_FAIL("blocked_plan_build: null argument");
     if (spec.a_bits != VGL_BLK_BITS && spec.a_bits != VGL_BLK_BITS - 1) VGL_FAIL("blocked_plan_build: accumulate blocks hold 2^15 (4-byte) or 2^14 (8-byte) accumulators");
     auto L = std::make_shared<vgl_blocked_layout>();
-    L->stream = c->stream;
     // chunk positions are 32-bit: a direction is laid out whole below 2^32 - 2048 edges (VGL_BLK_PIECE_EDGES lowers the bound: tests)
     int64_t limit = (1LL << 32) - VGL_TILE;
     const bool cuttable = spec.value_bits == 32 && spec.a_bits == VGL_BLK_BITS;  // (the variable only lowers the bound of layouts that can be cut)
@@ -558,15 +509,14 @@ int vgl_blocked_build(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32_t nrows, int
             if (hi <= lo || e1 <= e0) continue;
             if (e1 - e0 >= (1LL << 32) - VGL_TILE) VGL_FAIL("blocked_plan_build: a row range of one piece holds 2^32 edges or more");
             vgl_blocked_piece &q = L->pieces.emplace_back();
-            VGL_HIP_TRY(hipMalloc((void **)&q.piece_rowptr, sizeof(int64_t) * ((size_t)(hi - lo) + 1)));
+            VGL_TRY(q.piece_rowptr.alloc((size_t)(hi - lo) + 1));
             hipLaunchKernelGGL(vgl_k_blk_rebase_rows, dim3((unsigned)std::min<int64_t>(4096, vgl_ceil_div((int64_t)(hi - lo) + 1, 256))), dim3(256), 0, c->stream, hi - lo,
                                dir.rowptr + lo, e0, q.piece_rowptr);
             vgl_dir_csr view;
             view.rowptr = q.piece_rowptr; view.adj = dir.adj + e0; view.edges = e1 - e0;
-            const int rc = vgl_build_tile_rows(c, view, hi - lo);
-            q.piece_tile_row = view.tile_row;
-            if (rc) return rc;
+            VGL_TRY(vgl_build_tile_rows(c, view, hi - lo));
             VGL_TRY(vgl_blocked_build_piece(c, view, row_base, ncols, spec, lo, nrows, e0, &q));
+            q.piece_tile_row = std::move(view.tile_row);
         }
     }
     if (L->pieces.empty()) VGL_TRY(vgl_blocked_build_piece(c, dir, row_base, ncols, spec, 0, nrows, 0, &L->pieces.emplace_back()));

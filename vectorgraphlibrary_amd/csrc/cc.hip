@@ -298,7 +298,7 @@ int vgl_hip_cc_run_symmetric(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_comp, 
     // most frequent label among a fixed sample = the largest tree so far (any label is a correct choice; it only decides what is skipped)
     int32_t giant = -1;
     if (V > 0) {
-        int32_t *d_samples = reinterpret_cast<int32_t *>(g->iscratch);
+        int32_t *d_samples = reinterpret_cast<int32_t *>(g->iscratch.p);
         const int ns = std::min<int64_t>(NSAMPLES, V);
         hipLaunchKernelGGL(vgl_k_cc_sample_labels, dim3(vgl_ceil_div(ns, VGL_BLOCK)), dim3(VGL_BLOCK), 0, c->stream, V, d_comp, ns, d_samples);
         VGL_HIP_TRY(hipGetLastError());

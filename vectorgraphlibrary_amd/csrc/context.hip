@@ -94,6 +94,12 @@ const char *vgl_env(vgl_hip_ctx *c, const char *name)
     auto it = c->env.find(name);
     return it == c->env.end() ? nullptr : it->second.c_str();
 }
+int64_t vgl_env_int(vgl_hip_ctx *c, const char *name, int64_t dflt, int64_t lo, int64_t hi)
+{
+    const char *s = vgl_env(c, name);
+    const int64_t v = (s && *s) ? strtoll(s, nullptr, 10) : dflt;
+    return std::min(hi, std::max(lo, v));
+}
 
 extern "C" {
 

@@ -216,21 +216,18 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
     // the temporaries (about 26 bytes per edge) come from the library's stream-ordered pool, like those of the plan builders: what the graph
     // build has touched once is what the blocked-plan build of the same graph gets next -- the PageRank plan of uniform-25 paid 1.2 s for FRESH memory
     // (first touch, ~14 ms per GB, and the allocator's stalls) in front of 60 ms of kernels while the build before it took and returned device memory directly
-    vgl_scratch b_kept, b_sorted, b_nkept, b_keys, b_keys_sorted, b_temp;
-    struct cleanup {
-        hipStream_t st;
-        vgl_scratch *all[6];
-        ~cleanup() { for (vgl_scratch *b : all) vgl_scratch_free(st, b); }
-    } guard{st, {&b_kept, &b_sorted, &b_nkept, &b_keys, &b_keys_sorted, &b_temp}};
+    vgl_dev<int64_t> b_kept, b_sorted, b_nkept;
+    vgl_dev<int32_t> b_keys, b_keys_sorted;
+    vgl_dev<char> b_temp;
     size_t temp_bytes = 0, need = 0;
-    VGL_HIP_TRY(vgl_scratch_alloc(st, &b_kept, sizeof(int64_t) * (size_t)count));
-    VGL_HIP_TRY(vgl_scratch_alloc(st, &b_nkept, sizeof(int64_t)));
-    int64_t *kept_idx = (int64_t *)b_kept.p, *d_nkept = (int64_t *)b_nkept.p;
+    VGL_TRY(b_kept.alloc(st, (size_t)count));
+    VGL_TRY(b_nkept.alloc(st, 1));
+    int64_t *kept_idx = b_kept, *d_nkept = b_nkept;
     rocprim::counting_iterator<int64_t> iota(0);
     vgl_in_range pred{d_src, row_begin, row_end};
     VGL_HIP_TRY(rocprim::select(nullptr, need, iota, kept_idx, (size_t *)d_nkept, (size_t)count, pred, st));
     temp_bytes = need;
-    VGL_HIP_TRY(vgl_scratch_alloc(st, &b_temp, temp_bytes ? temp_bytes : 16));
+    VGL_TRY(b_temp.alloc(st, temp_bytes ? temp_bytes : 16));
     VGL_HIP_TRY(rocprim::select(b_temp.p, temp_bytes, iota, kept_idx, (size_t *)d_nkept, (size_t)count, pred, st));
     int64_t nkept = 0;
     VGL_HIP_TRY(hipMemcpyAsync(&nkept, d_nkept, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -238,11 +235,11 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
     if (kept_out) *kept_out = nkept;
     if (nkept > 0) {
         // 2. keys = local rows, row histogram
-        VGL_HIP_TRY(vgl_scratch_alloc(st, &b_keys, sizeof(int32_t) * (size_t)nkept));
-        VGL_HIP_TRY(vgl_scratch_alloc(st, &b_keys_sorted, sizeof(int32_t) * (size_t)nkept));
-        VGL_HIP_TRY(vgl_scratch_alloc(st, &b_sorted, sizeof(int64_t) * (size_t)nkept));
-        int32_t *keys = (int32_t *)b_keys.p, *keys_sorted = (int32_t *)b_keys_sorted.p;
-        int64_t *sorted_idx = (int64_t *)b_sorted.p;
+        VGL_TRY(b_keys.alloc(st, (size_t)nkept));
+        VGL_TRY(b_keys_sorted.alloc(st, (size_t)nkept));
+        VGL_TRY(b_sorted.alloc(st, (size_t)nkept));
+        int32_t *keys = b_keys, *keys_sorted = b_keys_sorted;
+        int64_t *sorted_idx = b_sorted;
         hipLaunchKernelGGL(vgl_k_keys, dim3(vgl_grid_for(nkept)), dim3(VGL_BLOCK), 0, st, nkept, kept_idx, d_src, row_begin,
                            keys, (unsigned long long *)(d_rowptr + 1));
         VGL_HIP_TRY(hipGetLastError());
@@ -251,7 +248,7 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
         while (bits < 31 && (1LL << bits) < (int64_t)nrows) bits++;
         need = 0;
         VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys, keys_sorted, kept_idx, sorted_idx, (size_t)nkept, 0, bits, st));
-        if (need > temp_bytes) { vgl_scratch_free(st, &b_temp); temp_bytes = need; VGL_HIP_TRY(vgl_scratch_alloc(st, &b_temp, temp_bytes)); }
+        if (need > temp_bytes) { temp_bytes = need; VGL_TRY(b_temp.alloc(st, temp_bytes)); }
         VGL_HIP_TRY(rocprim::radix_sort_pairs(b_temp.p, need, keys, keys_sorted, kept_idx, sorted_idx, (size_t)nkept, 0, bits, st));
         // 4. adjacency + optional permutation
         hipLaunchKernelGGL(vgl_k_gather<int32_t>, dim3(vgl_grid_for(nkept)), dim3(VGL_BLOCK), 0, st, nkept, sorted_idx, d_dst, d_adj);
@@ -260,7 +257,7 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
         // 5. row offsets: inclusive scan of the histogram stored at rowptr[1..nrows]
         need = 0;
         VGL_HIP_TRY(rocprim::inclusive_scan(nullptr, need, d_rowptr + 1, d_rowptr + 1, (size_t)nrows, rocprim::plus<int64_t>(), st));
-        if (need > temp_bytes) { vgl_scratch_free(st, &b_temp); temp_bytes = need; VGL_HIP_TRY(vgl_scratch_alloc(st, &b_temp, temp_bytes)); }
+        if (need > temp_bytes) { temp_bytes = need; VGL_TRY(b_temp.alloc(st, temp_bytes)); }
         VGL_HIP_TRY(rocprim::inclusive_scan(b_temp.p, need, d_rowptr + 1, d_rowptr + 1, (size_t)nrows, rocprim::plus<int64_t>(), st));
     }
     VGL_HIP_TRY(hipStreamSynchronize(st));
@@ -280,13 +277,12 @@ int vgl_hip_degree_order(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t
                          int32_t *d_fwd, int32_t *d_bwd)
 {
     if (!c || !d_fwd || !d_bwd || (count > 0 && (!d_src || !d_dst))) VGL_FAIL("degree_order: null argument");
-    uint32_t *deg = nullptr;
-    VGL_HIP_TRY(hipMalloc((void **)&deg, sizeof(uint32_t) * (size_t)V));
+    vgl_dev<uint32_t> deg;
+    VGL_TRY(deg.alloc((size_t)V));
     VGL_HIP_TRY(hipMemsetAsync(deg, 0, sizeof(uint32_t) * (size_t)V, c->stream));
     int rc = vgl_hip_degree_hist_add(c, count, d_src, d_dst, degree_kind, deg);
     if (rc == 0) rc = vgl_hip_degree_order_from_degrees(c, V, deg, d_fwd, d_bwd);
     hipStreamSynchronize(c->stream);
-    hipFree(deg);
     return rc;
 }
 
@@ -294,23 +290,18 @@ int vgl_hip_degree_order_from_degrees(vgl_hip_ctx *c, int32_t V, const uint32_t 
 {
     if (!c || !deg || !d_fwd || !d_bwd) VGL_FAIL("degree_order_from_degrees: null argument");
     hipStream_t st = c->stream;
-    uint32_t *keys = nullptr, *keys_out = nullptr;
-    int32_t *ids = nullptr;
-    void *temp = nullptr;
+    vgl_dev<uint32_t> keys, keys_out;
+    vgl_dev<int32_t> ids;
+    vgl_dev<char> temp;
     size_t need = 0;
-    struct cleanup {
-        hipStream_t st;
-        uint32_t *&a, *&b; int32_t *&c; void *&d;
-        ~cleanup() { for (void *p : {(void *)a, (void *)b, (void *)c, d}) vgl_pool_free(st, p); }
-    } guard{st, keys, keys_out, ids, temp};
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&keys, sizeof(uint32_t) * (size_t)V));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&keys_out, sizeof(uint32_t) * (size_t)V));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&ids, sizeof(int32_t) * (size_t)V));
+    VGL_TRY(keys.alloc(st, (size_t)V));
+    VGL_TRY(keys_out.alloc(st, (size_t)V));
+    VGL_TRY(ids.alloc(st, (size_t)V));
     hipLaunchKernelGGL(vgl_k_order_keys, dim3(vgl_grid_for(V)), dim3(VGL_BLOCK), 0, st, V, deg, keys, ids);
     VGL_HIP_TRY(hipGetLastError());
-    VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, ids, d_bwd, (size_t)V, 0, 32, st));
-    VGL_HIP_TRY(vgl_pool_alloc(st, &temp, need ? need : 16));
-    VGL_HIP_TRY(rocprim::radix_sort_pairs(temp, need, keys, keys_out, ids, d_bwd, (size_t)V, 0, 32, st));
+    VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys.p, keys_out.p, ids.p, d_bwd, (size_t)V, 0, 32, st));
+    VGL_TRY(temp.alloc(st, need ? need : 16));
+    VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, need, keys.p, keys_out.p, ids.p, d_bwd, (size_t)V, 0, 32, st));
     hipLaunchKernelGGL(vgl_k_invert, dim3(vgl_grid_for(V)), dim3(VGL_BLOCK), 0, st, V, d_bwd, d_fwd);
     VGL_HIP_TRY(hipGetLastError());
     VGL_HIP_TRY(hipStreamSynchronize(st));

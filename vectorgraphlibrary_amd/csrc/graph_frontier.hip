@@ -255,15 +255,12 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_plan_tile_first(int32_t F, co
 int vgl_build_tile_rows(vgl_hip_ctx *c, vgl_dir_csr &d, int32_t nrows)
 {
     d.ntiles = vgl_ceil_div(d.edges, VGL_TILE);
-    VGL_HIP_TRY(hipMalloc((void **)&d.tile_row, sizeof(int32_t) * ((size_t)d.ntiles + 2)));
+    VGL_TRY(d.tile_row.alloc((size_t)d.ntiles + 2));
     int grid = (int)std::min<int64_t>(8192, std::max<int64_t>(1, vgl_ceil_div(nrows, VGL_BLOCK)));
     hipLaunchKernelGGL(vgl_k_tile_rows, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, nrows, d.rowptr, d.tile_row, d.ntiles);
     VGL_HIP_TRY(hipGetLastError());
     return 0;
 }
-
-template <class T>
-static int vgl_alloc(T **p, size_t n) { VGL_HIP_TRY(hipMalloc((void **)p, sizeof(T) * (n ? n : 1))); return 0; }
 
 static int vgl_reduce_common(vgl_hip_ctx *c, int nblocks, double *result)
 {
@@ -287,11 +284,10 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
     if (!d_out_rowptr || (!d_out_adj && out_edges > 0)) VGL_FAIL("graph_create: outgoing CSR is required");
     if (out_edges < 0 || in_edges < 0) VGL_FAIL("graph_create: negative edge count");
     VGL_HIP_TRY(hipSetDevice(c->device));
-    vgl_hip_graph *g = new vgl_hip_graph();
+    // a failure below (an allocation, a launch) must not leave the half-built handle and its device arrays behind
+    vgl_building<vgl_hip_graph> g(new vgl_hip_graph(), {c});
     static std::atomic<uint64_t> next_uid{1};
     g->uid = next_uid.fetch_add(1);
-    // a failure below (an allocation, a launch) must not leave the half-built handle and its device arrays behind
-    struct rollback { vgl_hip_ctx *c; vgl_hip_graph *g; ~rollback() { if (g) vgl_hip_graph_destroy(c, g); } } undo{c, g};
     g->V = V; g->row_begin = row_begin; g->row_end = row_end; g->nrows = row_end - row_begin;
     g->out.rowptr = d_out_rowptr; g->out.adj = d_out_adj; g->out.edges = out_edges;
     VGL_TRY(vgl_build_tile_rows(c, g->out, g->nrows));
@@ -300,29 +296,29 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
         VGL_TRY(vgl_build_tile_rows(c, g->in, g->nrows));
     }
     const size_t words = (size_t)vgl_ceil_div(V, 64) + 1;
-    VGL_TRY(vgl_alloc(&g->bm_visited, words));
-    VGL_TRY(vgl_alloc(&g->bm_front, words));
-    VGL_TRY(vgl_alloc(&g->bm_next, words));
-    VGL_TRY(vgl_alloc(&g->bm_in_nz, words));
-    VGL_TRY(vgl_alloc(&g->ids, (size_t)g->nrows));
-    VGL_TRY(vgl_alloc(&g->offs, (size_t)g->nrows + 1));
+    VGL_TRY(g->bm_visited.alloc(words));
+    VGL_TRY(g->bm_front.alloc(words));
+    VGL_TRY(g->bm_next.alloc(words));
+    VGL_TRY(g->bm_in_nz.alloc(words));
+    VGL_TRY(g->ids.alloc((size_t)g->nrows));
+    VGL_TRY(g->offs.alloc((size_t)g->nrows + 1));
     g->nvtiles = vgl_ceil_div(g->nrows, VGL_TILE);
-    VGL_TRY(vgl_alloc(&g->vt_cnt, (size_t)g->nvtiles));
-    VGL_TRY(vgl_alloc(&g->vt_cnt_off, (size_t)g->nvtiles));
-    VGL_TRY(vgl_alloc(&g->vt_deg, (size_t)g->nvtiles));
-    VGL_TRY(vgl_alloc(&g->vt_deg_off, (size_t)g->nvtiles));
-    VGL_TRY(vgl_alloc(&g->vt_min_deg, (size_t)g->nvtiles));
+    VGL_TRY(g->vt_cnt.alloc((size_t)g->nvtiles));
+    VGL_TRY(g->vt_cnt_off.alloc((size_t)g->nvtiles));
+    VGL_TRY(g->vt_deg.alloc((size_t)g->nvtiles));
+    VGL_TRY(g->vt_deg_off.alloc((size_t)g->nvtiles));
+    VGL_TRY(g->vt_min_deg.alloc((size_t)g->nvtiles));
     hipLaunchKernelGGL(vgl_k_tile_min_degree, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->out.rowptr, g->vt_min_deg);
-    VGL_TRY(vgl_alloc(&g->tile_first, (size_t)g->out.ntiles + 2));
-    VGL_TRY(vgl_alloc(&g->heavy, (size_t)g->nrows + 4096 * VGL_BLOCK));
-    VGL_TRY(vgl_alloc(&g->bu_partials, (size_t)4096 * 4));
-    VGL_TRY(vgl_alloc(&g->tickets, (size_t)4 * VGL_TICKET_WORDS));
+    VGL_TRY(g->tile_first.alloc((size_t)g->out.ntiles + 2));
+    VGL_TRY(g->heavy.alloc((size_t)g->nrows + 4096 * VGL_BLOCK));
+    VGL_TRY(g->bu_partials.alloc((size_t)4096 * 4));
+    VGL_TRY(g->tickets.alloc((size_t)4 * VGL_TICKET_WORDS));
     VGL_HIP_TRY(hipMemsetAsync(g->tickets, 0, 4 * VGL_TICKET_WORDS * sizeof(uint32_t), c->stream));
-    VGL_TRY(vgl_alloc(&g->epoch, (size_t)V));
-    VGL_TRY(vgl_alloc(&g->fscratch, (size_t)V));
-    VGL_TRY(vgl_alloc(&g->fscratch2, (size_t)V));
-    VGL_TRY(vgl_alloc(&g->fscratch3, (size_t)V));
-    VGL_TRY(vgl_alloc(&g->iscratch, (size_t)V));
+    VGL_TRY(g->epoch.alloc((size_t)V));
+    VGL_TRY(g->fscratch.alloc((size_t)V));
+    VGL_TRY(g->fscratch2.alloc((size_t)V));
+    VGL_TRY(g->fscratch3.alloc((size_t)V));
+    VGL_TRY(g->iscratch.alloc((size_t)V));
     VGL_HIP_TRY(hipMemsetAsync(g->bm_visited, 0, words * 8, c->stream));
     VGL_HIP_TRY(hipMemsetAsync(g->bm_front, 0, words * 8, c->stream));
     VGL_HIP_TRY(hipMemsetAsync(g->bm_next, 0, words * 8, c->stream));
@@ -331,20 +327,19 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
         int grid = (int)std::min<int64_t>(8192, std::max<int64_t>(1, vgl_ceil_div(g->nrows, VGL_BLOCK)));
         hipLaunchKernelGGL(vgl_k_nonempty_rows, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, g->in.rowptr, g->bm_in_nz);
         const int64_t ngroups = vgl_ceil_div(g->nrows, 64);
-        VGL_TRY(vgl_alloc(&g->in_nz_rank, (size_t)ngroups + 1));
+        VGL_TRY(g->in_nz_rank.alloc((size_t)ngroups + 1));
         hipLaunchKernelGGL(vgl_k_nz_rank, dim3(1), dim3(1024), 0, c->stream, ngroups, (const uint64_t *)(g->bm_in_nz + (row_begin >> 6)), g->in_nz_rank);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_hip_memcpy_d2h(c, &g->in_nz_rows, g->in_nz_rank + ngroups, sizeof(int32_t)));
-        VGL_TRY(vgl_alloc(&g->in_head, (size_t)std::max(g->in_nz_rows, 1) * 8));
-        VGL_TRY(vgl_alloc(&g->bm_in_long, words));
+        VGL_TRY(g->in_head.alloc((size_t)std::max(g->in_nz_rows, 1) * 8));
+        VGL_TRY(g->bm_in_long.alloc(words));
         VGL_HIP_TRY(hipMemsetAsync(g->bm_in_long, 0, words * 8, c->stream));
         hipLaunchKernelGGL(vgl_k_row_heads, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, g->in.rowptr, g->in.adj,
-                           reinterpret_cast<int4 *>(g->in_head), reinterpret_cast<int4 *>(g->in_head) + g->in_nz_rows, g->bm_in_long, (const int32_t *)g->in_nz_rank);
+                           reinterpret_cast<int4 *>(g->in_head.p), reinterpret_cast<int4 *>(g->in_head.p) + g->in_nz_rows, g->bm_in_long, (const int32_t *)g->in_nz_rank);
         VGL_HIP_TRY(hipGetLastError());
     }
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
-    undo.g = nullptr;
-    *out = g;
+    *out = g.release();
     return 0;
 }
 
@@ -352,14 +347,6 @@ int vgl_hip_graph_destroy(vgl_hip_ctx *c, vgl_hip_graph *g)
 {
     if (!g) return 0;
     if (c) hipStreamSynchronize(c->stream);
-    if (g->transposed) { vgl_hip_graph_destroy(c, g->transposed); g->transposed = nullptr; }
-    for (vgl_lp_cache *p : g->lp) vgl_lp_cache_free(p);
-    vgl_tri_cache_free(g->tri);
-    void *ptrs[] = {g->out.tile_row, g->in.tile_row, g->bm_visited, g->bm_front, g->bm_next, g->bm_in_nz, g->in_head, g->in_nz_rank, g->bm_in_long, g->ids, g->offs, g->vt_cnt,
-                    g->vt_cnt_off, g->vt_deg, g->vt_deg_off, g->tile_first, g->heavy, g->bu_partials, g->tickets, g->epoch, g->fscratch, g->fscratch2,
-                    g->fscratch3, g->iscratch, g->ds_tile_active, g->ds_partials, g->out.hub_rows, g->in.hub_rows, g->out.giant_rows, g->in.giant_rows, g->out.pull_blk_row,
-                    g->in.pull_blk_row, g->vt_min_deg, g->gnf_bits, g->out.hub_chunks, g->in.hub_chunks, g->out.hub_chunk_sums, g->in.hub_chunk_sums, g->pr_indeg};
-    for (void *p : ptrs) if (p) hipFree(p);
     delete g;
     return 0;
 }
@@ -367,12 +354,13 @@ int vgl_hip_graph_destroy(vgl_hip_ctx *c, vgl_hip_graph *g)
 int vgl_hip_frontier_create(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_hip_frontier **out)
 {
     if (!c || !g || !out) VGL_FAIL("frontier_create: null argument");
-    vgl_hip_frontier *f = new vgl_hip_frontier();
+    std::unique_ptr<vgl_hip_frontier> f(new vgl_hip_frontier());
     f->g = g;
-    VGL_TRY(vgl_alloc(&f->flags, (size_t)g->V));
-    VGL_TRY(vgl_alloc(&f->ids, (size_t)g->V));
-    *out = f;
-    return vgl_hip_frontier_set_all_active(c, f);   // VGL frontiers start all-active (base_frontier.h ctor)
+    VGL_TRY(f->own_flags.alloc((size_t)g->V));
+    VGL_TRY(f->own_ids.alloc((size_t)g->V));
+    f->flags = f->own_flags; f->ids = f->own_ids;
+    *out = f.release();
+    return vgl_hip_frontier_set_all_active(c, *out);   // VGL frontiers start all-active (base_frontier.h ctor)
 }
 // a frontier handle over arrays the CALLER owns (a backend bound to another library's frontier container, whose flags / ids arrays host code of
 // that library reads and writes: FrontierCSR / FrontierVectorCSR, base_frontier.h:5-62).  Nothing is initialised: vgl_hip_frontier_set_state says
@@ -381,7 +369,7 @@ int vgl_hip_frontier_create_on(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_flag
 {
     if (!c || !g || !d_flags || !d_ids || !out) VGL_FAIL("frontier_create_on: null argument");
     vgl_hip_frontier *f = new vgl_hip_frontier();
-    f->g = g; f->flags = d_flags; f->ids = d_ids; f->borrowed = true;
+    f->g = g; f->flags = d_flags; f->ids = d_ids;
     f->size = 0; f->neighbours = 0; f->sparsity = VGL_HIP_FRONTIER_SPARSE; f->plan_dir = -1;
     *out = f;
     return 0;
@@ -400,8 +388,6 @@ int vgl_hip_frontier_destroy(vgl_hip_ctx *c, vgl_hip_frontier *f)
 {
     if (!f) return 0;
     if (c) hipStreamSynchronize(c->stream);
-    if (!f->borrowed) { hipFree(f->flags); hipFree(f->ids); }
-    if (f->offs) { hipFree(f->offs); hipFree(f->tile_first); hipFree(f->blk_sum); hipFree(f->blk_off); }
     delete f;
     return 0;
 }
@@ -460,10 +446,10 @@ static int vgl_frontier_reserve(vgl_hip_graph *g, vgl_hip_frontier *f)
 {
     if (f->offs) return 0;
     const int64_t emax = std::max(g->out.edges, g->in.edges);
-    VGL_TRY(vgl_alloc(&f->offs, (size_t)g->V + 1));
-    VGL_TRY(vgl_alloc(&f->tile_first, (size_t)vgl_ceil_div(emax, VGL_TILE) + 2));
-    VGL_TRY(vgl_alloc(&f->blk_sum, (size_t)vgl_ceil_div(g->V, VGL_TILE) + 1));
-    VGL_TRY(vgl_alloc(&f->blk_off, (size_t)vgl_ceil_div(g->V, VGL_TILE) + 1));
+    VGL_TRY(f->offs.alloc((size_t)g->V + 1));
+    VGL_TRY(f->tile_first.alloc((size_t)vgl_ceil_div(emax, VGL_TILE) + 2));
+    VGL_TRY(f->blk_sum.alloc((size_t)vgl_ceil_div(g->V, VGL_TILE) + 1));
+    VGL_TRY(f->blk_off.alloc((size_t)vgl_ceil_div(g->V, VGL_TILE) + 1));
     return 0;
 }
 
@@ -486,7 +472,7 @@ int vgl_hip_gnf_begin(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_hip_frontier *f, int
     out->ticket = g->nvtiles <= 16384 ? g->tickets + 0 * VGL_TICKET_WORDS : nullptr;      // beyond 2^25 vertices vgl_hip_gnf_complete runs the scan pass
     out->counters = c->d_counters; out->host_counters = (volatile int64_t *)c->h_counters;
     if (!g->gnf_bits) {
-        VGL_TRY(vgl_alloc(&g->gnf_bits, (size_t)vgl_ceil_div(g->V, 8) + 8));
+        VGL_TRY(g->gnf_bits.alloc((size_t)vgl_ceil_div(g->V, 8) + 8));
         VGL_HIP_TRY(hipMemsetAsync(g->gnf_bits, 0, (size_t)vgl_ceil_div(g->V, 8) + 8, c->stream));
     }
     out->front_bytes = g->gnf_bits;

@@ -364,18 +364,10 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_lp_push_big(const int32_t *ch
     for (int64_t p = s + threadIdx.x; p < e; p += VGL_BLOCK) lp_mark(active, adj[p]);
 }
 
-template <class T> int lp_dev_alloc(T **p, size_t n) { VGL_HIP_TRY(hipMalloc((void **)p, sizeof(T) * (n ? n : 1))); return 0; }
 template <class T> int lp_h2d(vgl_hip_ctx *c, T *d, const std::vector<T> &h)
 {
     if (!h.empty()) VGL_HIP_TRY(hipMemcpyAsync(d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, c->stream));
     return 0;
-}
-
-int64_t lp_env_int(vgl_hip_ctx *c, const char *name, int64_t dflt, int64_t lo, int64_t hi)
-{
-    const char *s = vgl_env(c, name);
-    const int64_t v = (s && *s) ? strtoll(s, nullptr, 10) : dflt;
-    return std::min(hi, std::max(lo, v));
 }
 
 }  // namespace
@@ -386,31 +378,26 @@ struct vgl_lp_cache {
     int64_t key[6] = {-1, -1, -1, -1, -1, -1};   // the switches it was built under
     lp_bounds b{};
     int32_t V = 0;
-    int32_t *rows = nullptr;                     // V: the rows of class c at [off[c], off[c] + size[c])
-    int32_t *d_off = nullptr, *d_size = nullptr; // LP_NCLS each (device)
+    vgl_dev<int32_t> rows;                       // V: the rows of class c at [off[c], off[c] + size[c])
+    vgl_dev<int32_t> d_off, d_size;              // LP_NCLS each (device)
     int32_t off[LP_NCLS + 1] = {}, size[LP_NCLS] = {};
     int64_t nz_rows = 0;                         // rows with at least one entry
     // hubs
     int32_t nhubs = 0, n_echunks = 0, n_rchunks = 0, hub_chunk = 0;
-    int32_t *hub_i32 = nullptr;                  // row | efirst | rfirst | tbits (nhubs each) | echunk_hub | rchunk_hub
-    int64_t *hub_tbl = nullptr;
+    vgl_dev<int32_t> hub_i32;                    // row | efirst | rfirst | tbits (nhubs each) | echunk_hub | rchunk_hub
+    vgl_dev<int64_t> hub_tbl;
     struct batch { int32_t e0, e1, r0, r1; };
     std::vector<batch> batches;
     int64_t table_slots = 0;                     // slots of the largest batch
     // push over this CSR
     int64_t push_big = 0;
     int32_t n_pchunks = 0;
-    int32_t *pchunk_row = nullptr;
-    int64_t *pchunk_start = nullptr;
+    vgl_dev<int32_t> pchunk_row;
+    vgl_dev<int64_t> pchunk_start;
     lp_hub_sched sched() const
     {
         const int32_t *p = hub_i32;
         return lp_hub_sched{p, p + nhubs, p + 2 * nhubs, hub_tbl, p + 3 * nhubs, p + 4 * nhubs, p + 4 * nhubs + n_echunks};
-    }
-    ~vgl_lp_cache()
-    {
-        void *ptrs[] = {rows, d_off, d_size, hub_i32, hub_tbl, pchunk_row, pchunk_start};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
     }
 };
 
@@ -420,12 +407,12 @@ namespace {
 
 void lp_switches(vgl_hip_ctx *c, int64_t key[6])
 {
-    key[0] = lp_env_int(c, "VGL_LP_LIGHT", 32, 0, 64);
-    key[1] = lp_env_int(c, "VGL_LP_WAVE", 512, key[0], 512);
-    key[2] = lp_env_int(c, "VGL_LP_MEDIUM", 4096, key[1], 4096);
-    key[3] = lp_env_int(c, "VGL_LP_HUB_CHUNK", 4096, 64, 4096);
-    key[4] = lp_env_int(c, "VGL_LP_HUB_SCRATCH_KB", 256 * 1024, 1, (int64_t)1 << 30) * 1024;
-    key[5] = lp_env_int(c, "VGL_LP_PUSH_BIG", 256, 16, (int64_t)1 << 40);
+    key[0] = vgl_env_int(c, "VGL_LP_LIGHT", 32, 0, 64);
+    key[1] = vgl_env_int(c, "VGL_LP_WAVE", 512, key[0], 512);
+    key[2] = vgl_env_int(c, "VGL_LP_MEDIUM", 4096, key[1], 4096);
+    key[3] = vgl_env_int(c, "VGL_LP_HUB_CHUNK", 4096, 64, 4096);
+    key[4] = vgl_env_int(c, "VGL_LP_HUB_SCRATCH_KB", 256 * 1024, 1, (int64_t)1 << 30) * 1024;
+    key[5] = vgl_env_int(c, "VGL_LP_PUSH_BIG", 256, 16, (int64_t)1 << 40);
 }
 
 // rows of the CSR with more than thr entries, ascending, with their (start, end)
@@ -454,19 +441,18 @@ int lp_big_rows(vgl_hip_ctx *c, const vgl_dir_csr &d, int32_t V, int64_t thr, in
     return 0;
 }
 
-int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64_t key[6], vgl_lp_cache **out)
+int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64_t key[6], std::unique_ptr<vgl_lp_cache, vgl_lp_cache_delete> &out)
 {
     const int32_t V = g->V;
-    vgl_lp_cache *p = new vgl_lp_cache();
-    struct guard { vgl_lp_cache *p; ~guard() { delete p; } } undo{p};
+    std::unique_ptr<vgl_lp_cache> p(new vgl_lp_cache());
     std::copy(key, key + 6, p->key);
     p->b = lp_bounds{(int)key[0], (int)key[1], (int)key[2]};
     p->V = V;
     p->hub_chunk = (int32_t)key[3];
     p->push_big = key[5];
-    VGL_TRY(lp_dev_alloc(&p->rows, (size_t)V));
-    VGL_TRY(lp_dev_alloc(&p->d_off, LP_NCLS));
-    VGL_TRY(lp_dev_alloc(&p->d_size, LP_NCLS));
+    VGL_TRY(p->rows.alloc((size_t)V));
+    VGL_TRY(p->d_off.alloc(LP_NCLS));
+    VGL_TRY(p->d_size.alloc(LP_NCLS));
     // classes: count, offsets, scatter (ids in ascending order within each workgroup's range)
     const unsigned grid = (unsigned)std::min<int64_t>(LP_MAX_GRID, vgl_ceil_div(V, VGL_BLOCK));
     VGL_HIP_TRY(hipMemsetAsync(p->d_size, 0, sizeof(int32_t) * LP_NCLS, c->stream));
@@ -483,9 +469,8 @@ int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64
                        (const int32_t *)p->d_off, p->d_size, p->rows, (int64_t *)nullptr);
     VGL_HIP_TRY(hipGetLastError());
     // hubs: sorted ids from the host, edge chunks, table sizes, batches within the scratch cap (a hub larger than the cap is a batch of its own)
-    int32_t *d_tmp = nullptr;
-    VGL_HIP_TRY(hipMalloc((void **)&d_tmp, sizeof(int32_t) * (size_t)V * 6 + 64));
-    struct tmp_guard { int32_t *p; ~tmp_guard() { (void)hipFree(p); } } tg{d_tmp};
+    vgl_dev<int32_t> d_tmp;
+    VGL_TRY(d_tmp.alloc((size_t)V * 6 + 16));
     std::vector<int32_t> rows;
     std::vector<int64_t> se;
     VGL_TRY(lp_big_rows(c, d, V, p->b.medium, d_tmp, rows, se));
@@ -518,10 +503,10 @@ int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64
     p->n_rchunks = (int32_t)rchunk_hub.size();
     std::vector<int32_t> packed(rows);
     for (auto *v : {&efirst, &rfirst, &tbits, &echunk_hub, &rchunk_hub}) packed.insert(packed.end(), v->begin(), v->end());
-    VGL_TRY(lp_dev_alloc(&p->hub_i32, packed.size()));
-    VGL_TRY(lp_dev_alloc(&p->hub_tbl, tbl.size()));
-    VGL_TRY(lp_h2d(c, p->hub_i32, packed));
-    VGL_TRY(lp_h2d(c, p->hub_tbl, tbl));
+    VGL_TRY(p->hub_i32.alloc(packed.size()));
+    VGL_TRY(p->hub_tbl.alloc(tbl.size()));
+    VGL_TRY(lp_h2d(c, p->hub_i32.p, packed));
+    VGL_TRY(lp_h2d(c, p->hub_tbl.p, tbl));
     // push schedule over this CSR: chunks of the rows with more than push_big entries
     VGL_TRY(lp_big_rows(c, d, V, p->push_big, d_tmp, rows, se));
     std::vector<int32_t> prow;
@@ -529,13 +514,12 @@ int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64
     for (size_t i = 0; i < rows.size(); i++)
         for (int64_t s = se[2 * i]; s < se[2 * i + 1]; s += LP_PUSH_CHUNK) { prow.push_back(rows[i]); pstart.push_back(s); }
     p->n_pchunks = (int32_t)prow.size();
-    VGL_TRY(lp_dev_alloc(&p->pchunk_row, prow.size()));
-    VGL_TRY(lp_dev_alloc(&p->pchunk_start, pstart.size()));
-    VGL_TRY(lp_h2d(c, p->pchunk_row, prow));
-    VGL_TRY(lp_h2d(c, p->pchunk_start, pstart));
+    VGL_TRY(p->pchunk_row.alloc(prow.size()));
+    VGL_TRY(p->pchunk_start.alloc(pstart.size()));
+    VGL_TRY(lp_h2d(c, p->pchunk_row.p, prow));
+    VGL_TRY(lp_h2d(c, p->pchunk_start.p, pstart));
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
-    undo.p = nullptr;
-    *out = p;
+    out.reset(p.release());
     return 0;
 }
 
@@ -545,30 +529,14 @@ int lp_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, int dir, vgl_lp_cache **out)
     const vgl_dir_csr &d = dir ? g->in : g->out;
     int64_t key[6];
     lp_switches(c, key);
-    vgl_lp_cache *&slot = g->lp[dir];
-    if (slot && std::equal(key, key + 6, slot->key)) { *out = slot; return 0; }
+    auto &slot = g->lp[dir];
+    if (slot && std::equal(key, key + 6, slot->key)) { *out = slot.get(); return 0; }
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
-    delete slot;
-    slot = nullptr;
-    VGL_TRY(lp_build(c, g, d, key, &slot));
-    *out = slot;
+    slot.reset();
+    VGL_TRY(lp_build(c, g, d, key, slot));
+    *out = slot.get();
     return 0;
 }
-
-// per-call scratch (vgl_pool_alloc: blocks of >= 64 MiB are plain hipMalloc blocks)
-struct lp_scratch {
-    hipStream_t st;
-    std::vector<void *> blocks;
-    template <class T> int get(T **p, size_t n)
-    {
-        void *q = nullptr;
-        VGL_HIP_TRY(vgl_pool_alloc(st, &q, sizeof(T) * (n ? n : 1)));
-        blocks.push_back(q);
-        *p = static_cast<T *>(q);
-        return 0;
-    }
-    ~lp_scratch() { for (void *p : blocks) vgl_pool_free(st, p); }
-};
 
 unsigned lp_grid(int64_t work, int64_t per_block) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(LP_MAX_GRID, vgl_ceil_div(work, per_block))); }
 
@@ -657,22 +625,21 @@ int vgl_hip_lp_run(vgl_hip_ctx *c, vgl_hip_graph *g, int direction, int mode, in
     if (rdir == direction) kr = k;
 
     // scratch, once per call
-    lp_scratch sc{c->stream, {}};
-    int32_t *next = nullptr, *chg = nullptr, *act = nullptr, *flist = nullptr, *fcnt = nullptr;
-    uint64_t *changed = nullptr, *active = nullptr;
-    int64_t *cnt = nullptr;
-    unsigned long long *tables = nullptr, *best = nullptr;
-    VGL_TRY(sc.get(&next, (size_t)V));
-    VGL_TRY(sc.get(&changed, (size_t)words));
-    VGL_TRY(sc.get(&cnt, LP_NCNT));
-    VGL_TRY(sc.get(&tables, (size_t)k->table_slots));
-    VGL_TRY(sc.get(&best, (size_t)k->nhubs));
+    vgl_dev<int32_t> next, chg, act, flist, fcnt;
+    vgl_dev<uint64_t> changed, active;
+    vgl_dev<int64_t> cnt;
+    vgl_dev<unsigned long long> tables, best;
+    VGL_TRY(next.alloc(c->stream, (size_t)V));
+    VGL_TRY(changed.alloc(c->stream, (size_t)words));
+    VGL_TRY(cnt.alloc(c->stream, LP_NCNT));
+    VGL_TRY(tables.alloc(c->stream, (size_t)k->table_slots));
+    VGL_TRY(best.alloc(c->stream, (size_t)k->nhubs));
     if (frontier) {
-        VGL_TRY(sc.get(&chg, (size_t)V + 1));
-        VGL_TRY(sc.get(&act, (size_t)V + 1));
-        VGL_TRY(sc.get(&flist, (size_t)V));
-        VGL_TRY(sc.get(&fcnt, LP_NCLS));
-        VGL_TRY(sc.get(&active, (size_t)words));
+        VGL_TRY(chg.alloc(c->stream, (size_t)V + 1));
+        VGL_TRY(act.alloc(c->stream, (size_t)V + 1));
+        VGL_TRY(flist.alloc(c->stream, (size_t)V));
+        VGL_TRY(fcnt.alloc(c->stream, LP_NCLS));
+        VGL_TRY(active.alloc(c->stream, (size_t)words));
     }
     VGL_HIP_TRY(hipMemsetAsync(changed, 0, sizeof(uint64_t) * (size_t)words, c->stream));
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int64_t) * LP_NCNT, c->stream));

@@ -138,11 +138,11 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_indeg_sub_loops(const int64_t
 int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
 {
     if (dir.hub_rows) return 0;
-    int32_t *d_rows = nullptr, *d_deg = nullptr, *d_count = nullptr;
+    vgl_dev<int32_t> d_rows, d_deg, d_count;
     const size_t cap = (size_t)std::max<int32_t>(g->nrows, 1);
-    VGL_HIP_TRY(hipMalloc((void **)&d_rows, sizeof(int32_t) * cap));
-    VGL_HIP_TRY(hipMalloc((void **)&d_deg, sizeof(int32_t) * cap));
-    VGL_HIP_TRY(hipMalloc((void **)&d_count, sizeof(int32_t)));
+    VGL_TRY(d_rows.alloc(cap));
+    VGL_TRY(d_deg.alloc(cap));
+    VGL_TRY(d_count.alloc(1));
     VGL_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int32_t), c->stream));
     hipLaunchKernelGGL(vgl_k_pull_find_hubs, dim3(vgl_grid3(g->nrows, 4096)), dim3(VGL_BLOCK), 0, c->stream, g->nrows, dir.rowptr, d_rows,
                        d_deg, d_count);
@@ -153,7 +153,7 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
     dir.hub_blocks = n ? (int)std::min<int64_t>(hub_blocks_cap, vgl_ceil_div((int64_t)n, VGL_WAVES)) : 0;
     const int W = dir.hub_blocks * VGL_WAVES;
     // device layout: [n hub rows grouped by wavefront][W+1 offsets]
-    VGL_HIP_TRY(hipMalloc((void **)&dir.hub_rows, sizeof(int32_t) * (n + (size_t)W + 1)));
+    VGL_TRY(dir.hub_rows.alloc(n + (size_t)W + 1));
     if (n > 0) {
         std::vector<int32_t> rows(n), deg(n), order(n);
         VGL_TRY(vgl_hip_memcpy_d2h(c, rows.data(), d_rows, sizeof(int32_t) * n));
@@ -190,7 +190,7 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
                 for (int32_t r : glists[(size_t)b]) gp[gpos++] = r;
             }
             gp[ng + (size_t)dir.giant_blocks] = (int32_t)gpos;
-            VGL_HIP_TRY(hipMalloc((void **)&dir.giant_rows, sizeof(int32_t) * gp.size()));
+            VGL_TRY(dir.giant_rows.alloc(gp.size()));
             VGL_TRY(vgl_hip_memcpy_h2d(c, dir.giant_rows, gp.data(), sizeof(int32_t) * gp.size()));
         }
         // longest-processing-time list scheduling: the next-largest hub goes to the least loaded wavefront, so the critical path is
@@ -226,13 +226,11 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
         }
         dir.n_hub_chunks = (int)(chunks.size() / 2); dir.n_hub_list = (int)n;
         chunks.insert(chunks.end(), hubs.begin(), hubs.end());              // [2 * n_chunks | 3 * n_hubs]
-        VGL_HIP_TRY(hipMalloc((void **)&dir.hub_chunks, sizeof(int32_t) * chunks.size()));
+        VGL_TRY(dir.hub_chunks.alloc(chunks.size()));
         VGL_TRY(vgl_hip_memcpy_h2d(c, dir.hub_chunks, chunks.data(), sizeof(int32_t) * chunks.size()));
-        VGL_HIP_TRY(hipMalloc((void **)&dir.hub_chunk_sums, sizeof(double) * (size_t)std::max(1, dir.n_hub_chunks)));
+        VGL_TRY(dir.hub_chunk_sums.alloc((size_t)std::max(1, dir.n_hub_chunks)));
     }
-    VGL_HIP_TRY(hipFree(d_rows));
-    VGL_HIP_TRY(hipFree(d_deg));
-    VGL_HIP_TRY(hipFree(d_count));
+    d_rows.reset(); d_deg.reset(); d_count.reset();
     // row blocks of the ordinary workgroups: every aligned group of 256 rows is cut into 1, 2, 4, ... 32 equal parts until a part
     // holds about VGL_PULL_BLOCK_EDGES edges (hub rows count too: they only make their neighbourhood's parts smaller)
     {
@@ -259,7 +257,7 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
         }
         blk_row.push_back(nrows);
         dir.pull_nblk = (int)blk_row.size() - 1;
-        VGL_HIP_TRY(hipMalloc((void **)&dir.pull_blk_row, sizeof(int32_t) * blk_row.size()));
+        VGL_TRY(dir.pull_blk_row.alloc(blk_row.size()));
         VGL_TRY(vgl_hip_memcpy_h2d(c, dir.pull_blk_row, blk_row.data(), sizeof(int32_t) * blk_row.size()));
     }
     return 0;

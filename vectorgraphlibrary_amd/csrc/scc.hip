@@ -233,15 +233,18 @@ int vgl_hip_scc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_comp, vgl_hip_s
     if (!g->in.rowptr) VGL_FAIL("scc_run: the incoming CSR is required (backward reach, predecessor counts)");
     const int32_t V = g->V;
     hipStream_t st = c->stream;
-    if (!g->transposed)
-        VGL_TRY(vgl_hip_graph_create(c, V, 0, V, g->in.rowptr, g->in.adj, g->in.edges, g->out.rowptr, g->out.adj, g->out.edges, &g->transposed));
-    int32_t *buf = nullptr;                      // act | od | id | colour | reach | minrep | fw | bw
-    VGL_HIP_TRY(hipMalloc((void **)&buf, sizeof(int32_t) * 8 * (size_t)V));
+    if (!g->transposed) {
+        vgl_hip_graph *t = nullptr;
+        VGL_TRY(vgl_hip_graph_create(c, V, 0, V, g->in.rowptr, g->in.adj, g->in.edges, g->out.rowptr, g->out.adj, g->out.edges, &t));
+        g->transposed.reset(t);
+    }
+    vgl_dev<int32_t> buf;                        // act | od | id | colour | reach | minrep | fw | bw
+    VGL_TRY(buf.alloc(8 * (size_t)V));
     int32_t *act = buf, *od = buf + (size_t)V, *id = buf + 2 * (size_t)V, *colour = buf + 3 * (size_t)V, *reach = buf + 4 * (size_t)V,
             *minrep = buf + 5 * (size_t)V, *fw = buf + 6 * (size_t)V, *bw = buf + 7 * (size_t)V;
     vgl_hip_scc_stats s = {0, 0, 0, 0};
     int rc = 0;
-    auto fail = [&](int code) { hipStreamSynchronize(st); hipFree(buf); return code; };
+    auto fail = [&](int code) { hipStreamSynchronize(st); return code; };      // (buf is freed on the way out: the kernels must be done with it)
 #define SCC_TRY(expr) do { rc = (expr); if (rc != 0) return fail(rc); } while (0)
     auto recount = [&](bool all) -> int {
         hipLaunchKernelGGL(vgl_k_scc_colour_init, dim3(scc_grid(V)), dim3(VGL_BLOCK), 0, st, V, act, colour, od, id);      // zeroes od / id too
@@ -287,7 +290,7 @@ int vgl_hip_scc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_comp, vgl_hip_s
     SCC_TRY(survey(&active, &pivot, &key));
     if (active > 0 && key > 0) {                 // the big component: forward and backward reach of the best-connected vertex
         SCC_TRY(vgl_hip_bfs_run(c, g, pivot, VGL_HIP_BFS_DIRECTION_OPT, fw, nullptr));
-        SCC_TRY(vgl_hip_bfs_run(c, g->transposed, pivot, VGL_HIP_BFS_DIRECTION_OPT, bw, nullptr));
+        SCC_TRY(vgl_hip_bfs_run(c, g->transposed.get(), pivot, VGL_HIP_BFS_DIRECTION_OPT, bw, nullptr));
         const int64_t big = LLONG_MAX;
         SCC_TRY(vgl_hip_memcpy_h2d(c, c->d_counters + C_JUMP, &big, sizeof(int64_t)));
         hipLaunchKernelGGL(vgl_k_scc_intersect, dim3(scc_grid(V)), dim3(VGL_BLOCK), 0, st, V, fw, bw, act, d_comp, 0, c->d_counters);
@@ -326,7 +329,6 @@ int vgl_hip_scc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_comp, vgl_hip_s
     }
 #undef SCC_TRY
     VGL_HIP_TRY(hipStreamSynchronize(st));
-    hipFree(buf);
     if (stats) *stats = s;
     return 0;
 }

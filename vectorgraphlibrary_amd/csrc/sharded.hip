@@ -139,7 +139,7 @@ int vgl_hip_pr_run_sharded(vgl_hip_ctx *c, vgl_hip_comm *given, vgl_hip_graph *g
     VGL_TRY(vgl_comm_allreduce_host_i64(m, &all_ready, 1, VGL_OP_MIN));
     if (!all_ready) g->pr_indeg_ready = false;
     if (!g->pr_indeg_ready) {
-        if (!g->pr_indeg) VGL_HIP_TRY(hipMalloc((void **)&g->pr_indeg, sizeof(int32_t) * (size_t)std::max(V, 1)));
+        if (!g->pr_indeg) VGL_TRY(g->pr_indeg.alloc((size_t)std::max(V, 1)));
         VGL_HIP_TRY(hipMemsetAsync(g->pr_indeg, 0, sizeof(int32_t) * (size_t)V, c->stream));
         VGL_TRY(vgl_hip_indegree_noloops_add(c, g, g->pr_indeg));
         VGL_TRY(vgl_comm_allreduce(m, g->pr_indeg, V, VGL_DT_I32, VGL_OP_SUM));

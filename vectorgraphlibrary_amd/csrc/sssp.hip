@@ -399,17 +399,16 @@ static int vgl_path_structure(vgl_hip_ctx *c, vgl_hip_graph *g)
 static int vgl_pull_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, vgl_hip_sssp_pull_plan **out)
 {
     if (!c || !g || !d_weights || !out) VGL_FAIL("sssp_pull_plan_create: null argument");
-    vgl_hip_sssp_pull_plan *p = new vgl_hip_sssp_pull_plan();
+    std::unique_ptr<vgl_hip_sssp_pull_plan> p(new vgl_hip_sssp_pull_plan());
     p->g = g; p->g_uid = g->uid; p->weights = d_weights;
     // Round 5: the layout is a per-GRAPH structure (one radix sort of the edges by block pair, the CSR position behind every value slot kept -- the
     // role of the reference's edges_reorder_indexes, csr_edges_array.hpp:31-40); a plan is a reference to it plus per-WEIGHTS value arrays filled
     // by one gather pass: a second weights array on the same graph costs ~3 ms instead of the 37 ms of a full build (RMAT-24)
-    int rc = vgl_path_structure(c, g);
-    if (!rc) rc = vgl_blocked_plan_share(c, g->blk_path, &p->blk);
-    if (!rc) rc = vgl_blocked_plan_load_weights(c, *p->blk, d_weights);
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = vgl_set_error(__FILE__, __LINE__, "sssp_pull_plan_create: the weights pass failed");
-    if (rc) { delete p; return rc; }
-    *out = p;
+    VGL_TRY(vgl_path_structure(c, g));
+    VGL_TRY(vgl_blocked_plan_share(c, g->blk_path, &p->blk));
+    VGL_TRY(vgl_blocked_plan_load_weights(c, *p->blk, d_weights));
+    if (hipStreamSynchronize(c->stream) != hipSuccess) VGL_FAIL("sssp_pull_plan_create: the weights pass failed");
+    *out = p.release();
     return 0;
 }
 

@@ -38,20 +38,19 @@ constexpr int VGL_DS_BLOCKS = 2048;       // persistent grid of the relax kernel
 
 struct vgl_hip_sssp_plan {
     float delta = 0.0f;
-    hipStream_t stream = nullptr;        // the stream whose pool owns the part arrays
     // the edges split into two CSRs over the same rows, both in original relative order: [0] light (w < delta), [1] heavy.
     // Own row offsets / adjacency / weights / tile table each, so a step can either walk a compacted frontier's segments or
     // sweep the whole part as static tiles.
     vgl_dir_csr part[2];
-    int64_t *prow[2] = {nullptr, nullptr};
-    int32_t *padj[2] = {nullptr, nullptr};
-    float *pw[2] = {nullptr, nullptr};
+    vgl_dev<int64_t> prow[2];
+    vgl_dev<int32_t> padj[2];
+    vgl_dev<float> pw[2];
     int64_t rows_nonempty[2] = {0, 0};   // rows that have edges in the part (what "most of the part is scheduled" is measured against)
-    uint8_t *state = nullptr;     // V: bit0 light edges pending, bit1 heavy edges pending
-    uint8_t *active = nullptr;    // V: rows scheduled by the current DENSE step (static sweep over a whole part)
-    int32_t *vt_aux = nullptr;    // per vertex tile: rows with heavy pending below T
-    int64_t *partials = nullptr;  // min-pending reduction (1024) followed by the relax kernels' near-improvement counts (+ 1 flag word)
-    uint32_t *tickets = nullptr;  // arrival counters of the min_pending kernel ([1]; [0] unused)
+    vgl_dev<uint8_t> state;       // V: bit0 light edges pending, bit1 heavy edges pending
+    vgl_dev<uint8_t> active;      // V: rows scheduled by the current DENSE step (static sweep over a whole part)
+    vgl_dev<int32_t> vt_aux;      // per vertex tile: rows with heavy pending below T
+    vgl_dev<int64_t> partials;    // min-pending reduction (1024) followed by the relax kernels' near-improvement counts (+ 1 flag word)
+    vgl_dev<uint32_t> tickets;    // arrival counters of the min_pending kernel ([1]; [0] unused)
     // round 4: the two parts laid out for the blocked advance as well (vgl_blocked.h, fused tiles for the dense block pairs): a DENSE step then
     // streams its part at ~5 TB/s with every random access in LDS instead of one L2 line per gather (the heavy step of the first bucket of an
     // RMAT-24 run: 465 M edges, 3.4 ms as a static sweep -- the push relax kernel at 0.21 of the HBM peak -- a quarter of the run)
@@ -724,35 +723,34 @@ int vgl_hip_sssp_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
     const int64_t E = g->out.edges;
     if (E >= 0xFFFFFFF0LL) VGL_FAIL("sssp_plan_create: at most 2^32-16 edges per graph handle");
     hipStream_t st = c->stream;
-    vgl_hip_sssp_plan *p = new vgl_hip_sssp_plan();
+    vgl_building<vgl_hip_sssp_plan> p(new vgl_hip_sssp_plan(), {c});
     p->delta = delta;
-    p->stream = st;
-    VGL_HIP_TRY(hipMalloc((void **)&p->state, (size_t)g->V + 8));
-    VGL_HIP_TRY(hipMalloc((void **)&p->active, (size_t)g->V + 8));
+    VGL_TRY(p->state.alloc((size_t)g->V + 8));
+    VGL_TRY(p->active.alloc((size_t)g->V + 8));
     VGL_HIP_TRY(hipMemsetAsync(p->active, 0, (size_t)g->V + 8, st));
-    VGL_HIP_TRY(hipMalloc((void **)&p->vt_aux, sizeof(int32_t) * (size_t)std::max<int64_t>(g->nvtiles, 1)));
-    VGL_HIP_TRY(hipMalloc((void **)&p->partials, sizeof(int64_t) * (1024 + VGL_DS_BLOCKS + 2)));          // minima | near counts + flag | select cursor
+    VGL_TRY(p->vt_aux.alloc((size_t)std::max<int64_t>(g->nvtiles, 1)));
+    VGL_TRY(p->partials.alloc(1024 + VGL_DS_BLOCKS + 2));          // minima | near counts + flag | select cursor
     VGL_HIP_TRY(hipMemsetAsync(p->partials, 0, sizeof(int64_t) * (1024 + VGL_DS_BLOCKS + 2), st));
-    VGL_HIP_TRY(hipMalloc((void **)&p->tickets, sizeof(uint32_t) * 2 * VGL_TICKET_WORDS));
+    VGL_TRY(p->tickets.alloc(2 * VGL_TICKET_WORDS));
     VGL_HIP_TRY(hipMemsetAsync(p->tickets, 0, sizeof(uint32_t) * 2 * VGL_TICKET_WORDS, st));
-    uint32_t *flags = nullptr, *S = nullptr;
-    void *temp = nullptr;
+    vgl_dev<uint32_t> flags, S;
+    vgl_dev<char> temp;
     size_t need = 0;
     // (the multi-gigabyte temporaries and part arrays come from the library's stream-ordered pool: fresh hipMalloc / hipFree calls of that size
     // stalled for hundreds of milliseconds in the bench, where another plan had just been released -- 357 ms for a 42 ms build)
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&flags, sizeof(uint32_t) * ((size_t)E + 1)));
-    VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&S, sizeof(uint32_t) * ((size_t)E + 1)));
+    VGL_TRY(flags.alloc(st, (size_t)E + 1));
+    VGL_TRY(S.alloc(st, (size_t)E + 1));
     hipLaunchKernelGGL(vgl_k_ds_light_flags, dim3(vgl_ds_grid(std::max<int64_t>(E, 1), 16384)), dim3(VGL_BLOCK), 0, st, E, d_weights, delta, flags);
-    VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, flags, S, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
-    VGL_HIP_TRY(vgl_pool_alloc(st, &temp, need ? need : 16));
-    VGL_HIP_TRY(rocprim::exclusive_scan(temp, need, flags, S, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, flags.p, S.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    VGL_TRY(temp.alloc(st, need ? need : 16));
+    VGL_HIP_TRY(rocprim::exclusive_scan(temp.p, need, flags.p, S.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
     uint32_t n_light = 0;                                   // S[E] = number of light edges: sizes of the two parts
     VGL_TRY(vgl_hip_memcpy_d2h(c, &n_light, S + E, sizeof(uint32_t)));
     const int64_t part_edges[2] = {(int64_t)n_light, E - (int64_t)n_light};
     for (int k = 0; k < 2; k++) {
-        VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->prow[k], sizeof(int64_t) * ((size_t)g->nrows + 1)));
-        VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->padj[k], sizeof(int32_t) * (size_t)std::max<int64_t>(part_edges[k], 1)));
-        VGL_HIP_TRY(vgl_pool_alloc(st, (void **)&p->pw[k], sizeof(float) * (size_t)std::max<int64_t>(part_edges[k], 1)));
+        VGL_TRY(p->prow[k].alloc(st, (size_t)g->nrows + 1));
+        VGL_TRY(p->padj[k].alloc(st, (size_t)std::max<int64_t>(part_edges[k], 1)));
+        VGL_TRY(p->pw[k].alloc(st, (size_t)std::max<int64_t>(part_edges[k], 1)));
     }
     if (E > 0)
         hipLaunchKernelGGL(vgl_k_ds_partition, dim3(vgl_ds_grid(E, 16384)), dim3(VGL_BLOCK), 0, st, E, g->out.adj, d_weights, S, delta, p->padj[0],
@@ -770,7 +768,7 @@ int vgl_hip_sssp_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
     VGL_TRY(vgl_hip_memcpy_d2h(c, p->rows_nonempty, p->partials, 2 * sizeof(int64_t)));
     VGL_HIP_TRY(hipMemsetAsync(p->partials, 0, 2 * sizeof(int64_t), st));
     VGL_HIP_TRY(hipStreamSynchronize(st));
-    vgl_pool_free(st, temp); vgl_pool_free(st, flags); vgl_pool_free(st, S);
+    temp.reset(); flags.reset(); S.reset();      // (before the blocked layouts are built: they are the peak of the build otherwise)
     // blocked layout of the HEAVY part for its dense steps (VGL_DS_BLOCKED: 0 never, 1 the heavy part, 2 both parts; default: the heavy part
     // from 2^25 edges -- the build costs about four static sweeps of the part, once per plan).  The light part keeps the static sweep: a
     // blocked pass streams the WHOLE part and sees the distances of the step's start (Jacobi), so the light rounds of the first bucket took
@@ -782,24 +780,19 @@ int vgl_hip_sssp_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
         const char *e = e0 ? e_keep.c_str() : nullptr;
         const int level = (e && *e) ? atoi(e) : (E >= (1LL << 25) ? 1 : 0);
         const bool want = level > 0;
-        const char *fm0 = vgl_env(c, "VGL_BLK_FUSE_MIN");
-        const std::string fm_keep = fm0 ? fm0 : "";
-        const char *fm = fm0 ? fm_keep.c_str() : nullptr;
         for (int k = level >= 2 ? 0 : 1; k < 2 && want; k++) {
             if (part_edges[k] < (1LL << 20) && !(e && *e)) continue;
             vgl_blocked_spec spec;
             spec.gather_rows = 1;
-            spec.fuse_min_edges = (fm && *fm) ? atoi(fm) : (part_edges[k] >= (1LL << 22) ? 16384 : 0);
+            spec.fuse_min_edges = (int)vgl_env_int(c, "VGL_BLK_FUSE_MIN", part_edges[k] >= (1LL << 22) ? 16384 : 0, INT_MIN, INT_MAX);
             spec.keep_edge_index = 1;
             std::shared_ptr<const vgl_blocked_layout> layout;
-            if (vgl_blocked_build(c, p->part[k], g->nrows, g->row_begin, g->V, spec, &layout) || vgl_blocked_plan_share(c, layout, &p->blk[k]) ||
-                vgl_blocked_plan_load_weights(c, *p->blk[k], p->pw[k])) {
-                vgl_hip_sssp_plan_destroy(c, p);
-                return 1;
-            }
+            VGL_TRY(vgl_blocked_build(c, p->part[k], g->nrows, g->row_begin, g->V, spec, &layout));
+            VGL_TRY(vgl_blocked_plan_share(c, layout, &p->blk[k]));
+            VGL_TRY(vgl_blocked_plan_load_weights(c, *p->blk[k], p->pw[k]));
         }
     }
-    *out = p;
+    *out = p.release();
     return 0;
 }
 
@@ -807,8 +800,6 @@ int vgl_hip_sssp_plan_destroy(vgl_hip_ctx *c, vgl_hip_sssp_plan *p)
 {
     if (!p) return 0;
     if (c) hipStreamSynchronize(c->stream);
-    for (int k = 0; k < 2; k++) { vgl_pool_free(p->stream, p->prow[k]); vgl_pool_free(p->stream, p->padj[k]); vgl_pool_free(p->stream, p->pw[k]); hipFree(p->part[k].tile_row); }
-    hipFree(p->state); hipFree(p->active); hipFree(p->vt_aux); hipFree(p->partials); hipFree(p->tickets);
     delete p;
     return 0;
 }

@@ -298,36 +298,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit
     tri_flush(cnt, tri, work);
 }
 
-template <class T> int tri_dev_alloc(T **p, size_t n) { VGL_HIP_TRY(hipMalloc((void **)p, sizeof(T) * (n ? n : 1))); return 0; }
-
-int64_t tri_env_int(vgl_hip_ctx *c, const char *name, int64_t dflt, int64_t lo, int64_t hi)
-{
-    const char *s = vgl_env(c, name);
-    const int64_t v = (s && *s) ? strtoll(s, nullptr, 10) : dflt;
-    return std::min(hi, std::max(lo, v));
-}
-
 unsigned tri_grid(int64_t work, int64_t per_block, int64_t cap = 16384) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
-
-// scratch of the prepare step: freed when the function leaves, however it leaves
-struct tri_scratch {
-    hipStream_t st;
-    std::vector<void *> blocks;
-    template <class T> int get(T **p, size_t n)
-    {
-        void *q = nullptr;
-        VGL_HIP_TRY(vgl_pool_alloc(st, &q, sizeof(T) * (n ? n : 1)));
-        blocks.push_back(q);
-        *p = static_cast<T *>(q);
-        return 0;
-    }
-    void drop(void *p)
-    {
-        auto it = std::find(blocks.begin(), blocks.end(), p);
-        if (it != blocks.end()) { vgl_pool_free(st, p); blocks.erase(it); }
-    }
-    ~tri_scratch() { for (void *p : blocks) vgl_pool_free(st, p); }
-};
 
 }  // namespace
 
@@ -335,28 +306,17 @@ struct tri_scratch {
 struct vgl_tri_cache {
     int32_t V = 0;
     int64_t edges = 0;                           // E'
-    int64_t *rowptr = nullptr;                   // V + 1
-    int32_t *adj = nullptr;                      // E', rows ascending by vertex id
-    int32_t *deg = nullptr;                      // V: degree in the simple undirected graph
+    vgl_dev<int64_t> rowptr;                     // V + 1
+    vgl_dev<int32_t> adj;                        // E', rows ascending by vertex id
+    vgl_dev<int32_t> deg;                        // V: degree in the simple undirected graph
     int32_t max_deg = 0;                         // longest oriented row
     // classes (rebuilt when the switches change; the oriented CSR stays)
     int64_t key[4] = {-1, -1, -1, -1};
     tri_bounds b{};
-    int32_t *rows = nullptr;                     // V: the rows of class c at [off[c], off[c] + size[c])
+    vgl_dev<int32_t> rows;                       // V: the rows of class c at [off[c], off[c] + size[c])
     int32_t off[TRI_NCLS + 1] = {}, size[TRI_NCLS] = {};
     int32_t n_units = 0, chunk_len = 0;          // huge: (row, chunk) units
-    int32_t *unit_row = nullptr, *unit_chunk = nullptr;
-    void free_classes()
-    {
-        for (void *p : {(void *)rows, (void *)unit_row, (void *)unit_chunk}) if (p) (void)hipFree(p);
-        rows = unit_row = unit_chunk = nullptr;
-        n_units = 0;
-    }
-    ~vgl_tri_cache()
-    {
-        free_classes();
-        for (void *p : {(void *)rowptr, (void *)adj, (void *)deg}) if (p) (void)hipFree(p);
-    }
+    vgl_dev<int32_t> unit_row, unit_chunk;
 };
 
 void vgl_tri_cache_free(vgl_tri_cache *p) { delete p; }
@@ -364,39 +324,37 @@ void vgl_tri_cache_free(vgl_tri_cache *p) { delete p; }
 namespace {
 
 // the oriented CSR
-int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out)
+int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, std::unique_ptr<vgl_tri_cache, vgl_tri_cache_delete> &out)
 {
     const int32_t V = g->V;
     const vgl_dir_csr &d = g->out;
     const int64_t E = d.edges;
     hipStream_t st = c->stream;
-    vgl_tri_cache *p = new vgl_tri_cache();
-    struct guard { vgl_tri_cache *p; ~guard() { delete p; } } undo{p};
+    std::unique_ptr<vgl_tri_cache> p(new vgl_tri_cache());
     p->V = V;
-    VGL_TRY(tri_dev_alloc(&p->rowptr, (size_t)V + 1));
-    VGL_TRY(tri_dev_alloc(&p->deg, (size_t)V));
+    VGL_TRY(p->rowptr.alloc((size_t)V + 1));
+    VGL_TRY(p->deg.alloc((size_t)V));
     VGL_HIP_TRY(hipMemsetAsync(p->rowptr, 0, sizeof(int64_t) * ((size_t)V + 1), st));
     VGL_HIP_TRY(hipMemsetAsync(p->deg, 0, sizeof(int32_t) * (size_t)std::max(V, 1), st));
     if (V > 0 && E > 0) {
-        tri_scratch sc{st, {}};
         // keys per piece: in + out buffers of 8 bytes each within the cap
-        const int64_t cap_keys = std::max<int64_t>(1, tri_env_int(c, "VGL_TRI_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
-        uint64_t *ord = nullptr;
-        VGL_TRY(sc.get(&ord, (size_t)V));
+        const int64_t cap_keys = std::max<int64_t>(1, vgl_env_int(c, "VGL_TRI_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
+        vgl_dev<uint64_t> ord;
+        VGL_TRY(ord.alloc(st, (size_t)V));
         hipLaunchKernelGGL(vgl_k_tri_order, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, d.rowptr, g->in.rowptr, ord);
         VGL_HIP_TRY(hipGetLastError());
         std::vector<int32_t> bounds{0, V};                            // pieces of consecutive lower endpoints
         int64_t piece_keys = E;
         if (E > cap_keys) {
-            int32_t *per_lower = nullptr;
-            VGL_TRY(sc.get(&per_lower, (size_t)V));
+            vgl_dev<int32_t> per_lower;
+            VGL_TRY(per_lower.alloc(st, (size_t)V));
             VGL_HIP_TRY(hipMemsetAsync(per_lower, 0, sizeof(int32_t) * (size_t)V, st));
             hipLaunchKernelGGL(vgl_k_tri_count_lower, dim3(tri_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, (const uint64_t *)ord, per_lower);
             VGL_HIP_TRY(hipGetLastError());
             std::vector<int32_t> h((size_t)V);
             VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_lower, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
             VGL_HIP_TRY(hipStreamSynchronize(st));
-            sc.drop(per_lower);
+            per_lower.reset();
             bounds.assign(1, 0);
             int64_t acc = 0;
             piece_keys = 0;
@@ -407,23 +365,23 @@ int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out)
             bounds.push_back(V);
             piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
         }
-        uint64_t *keys_a = nullptr, *keys_b = nullptr;
-        unsigned long long *n_keys = nullptr;
-        size_t *n_unique = nullptr;
-        int32_t *adj_tmp = nullptr;                                   // E entries bound E' from above
-        VGL_TRY(sc.get(&keys_a, (size_t)piece_keys));
-        VGL_TRY(sc.get(&keys_b, (size_t)piece_keys));
-        VGL_TRY(sc.get(&n_keys, 1));
-        VGL_TRY(sc.get(&n_unique, 1));
-        VGL_TRY(sc.get(&adj_tmp, (size_t)E));
+        vgl_dev<uint64_t> keys_a, keys_b;
+        vgl_dev<unsigned long long> n_keys;
+        vgl_dev<size_t> n_unique;
+        vgl_dev<int32_t> adj_tmp;                                     // E entries bound E' from above
+        VGL_TRY(keys_a.alloc(st, (size_t)piece_keys));
+        VGL_TRY(keys_b.alloc(st, (size_t)piece_keys));
+        VGL_TRY(n_keys.alloc(st, 1));
+        VGL_TRY(n_unique.alloc(st, 1));
+        VGL_TRY(adj_tmp.alloc(st, (size_t)E));
         int end_bit = 33;
         while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
         size_t temp_sort = 0, temp_unique = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a, keys_b, (size_t)piece_keys, 0, (unsigned)end_bit, st));
-        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b, keys_a, n_unique, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
+        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a.p, keys_b.p, (size_t)piece_keys, 0, (unsigned)end_bit, st));
+        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
         const size_t temp_bytes = std::max(temp_sort, temp_unique);
-        char *temp = nullptr;
-        VGL_TRY(sc.get(&temp, temp_bytes));
+        vgl_dev<char> temp;
+        VGL_TRY(temp.alloc(st, temp_bytes));
         int64_t base = 0;
         for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
             const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
@@ -438,9 +396,9 @@ int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out)
             size_t nu = 0;
             if (nk) {
                 size_t need = temp_bytes;
-                VGL_HIP_TRY(rocprim::radix_sort_keys(temp, need, keys_a, keys_b, (size_t)nk, 0, (unsigned)end_bit, st));
+                VGL_HIP_TRY(rocprim::radix_sort_keys(temp.p, need, keys_a.p, keys_b.p, (size_t)nk, 0, (unsigned)end_bit, st));
                 need = temp_bytes;
-                VGL_HIP_TRY(rocprim::unique(temp, need, keys_b, keys_a, n_unique, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
+                VGL_HIP_TRY(rocprim::unique(temp.p, need, keys_b.p, keys_a.p, n_unique.p, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
                 VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
                 VGL_HIP_TRY(hipStreamSynchronize(st));
             }
@@ -452,20 +410,19 @@ int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out)
             base += (int64_t)nu;
         }
         p->edges = base;
-        VGL_TRY(tri_dev_alloc(&p->adj, (size_t)base));
+        VGL_TRY(p->adj.alloc((size_t)base));
         if (base) VGL_HIP_TRY(hipMemcpyAsync(p->adj, adj_tmp, sizeof(int32_t) * (size_t)base, hipMemcpyDeviceToDevice, st));
-        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys);
+        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys.p);
         VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(vgl_k_tri_degrees, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->deg, d_max);
         VGL_HIP_TRY(hipGetLastError());
         VGL_HIP_TRY(hipMemcpyAsync(&p->max_deg, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         VGL_HIP_TRY(hipStreamSynchronize(st));
     } else {
-        VGL_TRY(tri_dev_alloc(&p->adj, 1));
+        VGL_TRY(p->adj.alloc(1));
         VGL_HIP_TRY(hipStreamSynchronize(st));
     }
-    undo.p = nullptr;
-    *out = p;
+    out.reset(p.release());
     return 0;
 }
 
@@ -474,36 +431,36 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
 {
     hipStream_t st = c->stream;
     const int32_t V = p->V;
-    p->free_classes();
+    p->rows.reset(); p->unit_row.reset(); p->unit_chunk.reset();
+    p->n_units = 0;
     std::fill(p->key, p->key + 4, -1);
     p->b = tri_bounds{(int)key[0], (int)key[1], (int)key[2]};
     p->chunk_len = (int32_t)key[3];
     std::fill(p->size, p->size + TRI_NCLS, 0);
     std::fill(p->off, p->off + TRI_NCLS + 1, 0);
-    VGL_TRY(tri_dev_alloc(&p->rows, (size_t)V));
+    VGL_TRY(p->rows.alloc((size_t)V));
     if (V > 0) {
-        tri_scratch sc{st, {}};
-        uint32_t *k_in = nullptr, *k_out = nullptr;
-        int32_t *ids = nullptr, *sizes = nullptr;
-        VGL_TRY(sc.get(&k_in, (size_t)V));
-        VGL_TRY(sc.get(&k_out, (size_t)V));
-        VGL_TRY(sc.get(&ids, (size_t)V));
-        VGL_TRY(sc.get(&sizes, TRI_NCLS));
+        vgl_dev<uint32_t> k_in, k_out;
+        vgl_dev<int32_t> ids, sizes;
+        VGL_TRY(k_in.alloc(st, (size_t)V));
+        VGL_TRY(k_out.alloc(st, (size_t)V));
+        VGL_TRY(ids.alloc(st, (size_t)V));
+        VGL_TRY(sizes.alloc(st, TRI_NCLS));
         VGL_HIP_TRY(hipMemsetAsync(sizes, 0, sizeof(int32_t) * TRI_NCLS, st));
         hipLaunchKernelGGL(vgl_k_tri_classify, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->b, k_in, ids, sizes);
         VGL_HIP_TRY(hipGetLastError());
         size_t need = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k_in, k_out, ids, p->rows, (size_t)V, 0, 32, st));
-        char *temp = nullptr;
-        VGL_TRY(sc.get(&temp, need));
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp, need, k_in, k_out, ids, p->rows, (size_t)V, 0, 32, st));
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32, st));
+        vgl_dev<char> temp;
+        VGL_TRY(temp.alloc(st, need));
+        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, need, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32, st));
         VGL_HIP_TRY(hipMemcpyAsync(p->size, sizes, sizeof(p->size), hipMemcpyDeviceToHost, st));
         VGL_HIP_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < TRI_NCLS; k++) p->off[k + 1] = p->off[k] + p->size[k];
         const int32_t nh = p->size[TRI_HUGE];
         if (nh) {                                                     // (row, chunk) units of the huge rows, heaviest row first
-            int32_t *d_deg = nullptr;
-            VGL_TRY(sc.get(&d_deg, (size_t)nh));
+            vgl_dev<int32_t> d_deg;
+            VGL_TRY(d_deg.alloc(st, (size_t)nh));
             const int32_t *hrows = p->rows + p->off[TRI_HUGE];
             hipLaunchKernelGGL(vgl_k_tri_row_degrees, dim3(tri_grid(nh, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, nh, hrows, (const int64_t *)p->rowptr, d_deg);
             VGL_HIP_TRY(hipGetLastError());
@@ -514,8 +471,8 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
             for (int32_t i = 0; i < nh; i++)
                 for (int64_t k = 0; k < vgl_ceil_div(hd[(size_t)i], p->chunk_len); k++) { ur.push_back(hr[(size_t)i]); uc.push_back((int32_t)k); }
             p->n_units = (int32_t)ur.size();
-            VGL_TRY(tri_dev_alloc(&p->unit_row, ur.size()));
-            VGL_TRY(tri_dev_alloc(&p->unit_chunk, uc.size()));
+            VGL_TRY(p->unit_row.alloc(ur.size()));
+            VGL_TRY(p->unit_chunk.alloc(uc.size()));
             VGL_HIP_TRY(hipMemcpyAsync(p->unit_row, ur.data(), sizeof(int32_t) * ur.size(), hipMemcpyHostToDevice, st));
             VGL_HIP_TRY(hipMemcpyAsync(p->unit_chunk, uc.data(), sizeof(int32_t) * uc.size(), hipMemcpyHostToDevice, st));
             VGL_HIP_TRY(hipStreamSynchronize(st));
@@ -528,20 +485,20 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
 int tri_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out, bool *built)
 {
     int64_t key[4];
-    key[0] = tri_env_int(c, "VGL_TRI_LIGHT", 64, 0, TRI_LIGHT_MAX);
-    key[1] = tri_env_int(c, "VGL_TRI_TABLE_SMALL", 1024, key[0], TRI_SLOTS_S / 2);
-    key[2] = tri_env_int(c, "VGL_TRI_TABLE", 8192, key[1], TRI_SLOTS_L / 2);
-    key[3] = tri_env_int(c, "VGL_TRI_HUGE_CHUNK", 8192, 16, TRI_SLOTS_L / 2);
+    key[0] = vgl_env_int(c, "VGL_TRI_LIGHT", 64, 0, TRI_LIGHT_MAX);
+    key[1] = vgl_env_int(c, "VGL_TRI_TABLE_SMALL", 1024, key[0], TRI_SLOTS_S / 2);
+    key[2] = vgl_env_int(c, "VGL_TRI_TABLE", 8192, key[1], TRI_SLOTS_L / 2);
+    key[3] = vgl_env_int(c, "VGL_TRI_HUGE_CHUNK", 8192, 16, TRI_SLOTS_L / 2);
     *built = false;
     if (!g->tri) {
-        VGL_TRY(tri_build_csr(c, g, &g->tri));
+        VGL_TRY(tri_build_csr(c, g, g->tri));
         *built = true;
     }
     if (!std::equal(key, key + 4, g->tri->key)) {
         VGL_HIP_TRY(hipStreamSynchronize(c->stream));
-        VGL_TRY(tri_build_classes(c, g->tri, key));
+        VGL_TRY(tri_build_classes(c, g->tri.get(), key));
     }
-    *out = g->tri;
+    *out = g->tri.get();
     return 0;
 }
 
@@ -601,10 +558,8 @@ int vgl_hip_tri_run(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *triangles, int64_
     bool built = false;
     VGL_TRY(tri_ensure(c, g, &k, &built));
     const int32_t V = g->V;
-    void *block = nullptr;                                            // the one scratch draw: the two counters
-    VGL_HIP_TRY(vgl_pool_alloc(c->stream, &block, sizeof(int64_t) * TRI_NCNT));
-    struct guard { hipStream_t st; void *p; ~guard() { vgl_pool_free(st, p); } } release{c->stream, block};
-    int64_t *cnt = static_cast<int64_t *>(block);
+    vgl_dev<int64_t> cnt;                                             // the one scratch draw: the two counters
+    VGL_TRY(cnt.alloc(c->stream, TRI_NCNT));
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int64_t) * TRI_NCNT, c->stream));
     if (d_per_vertex && V > 0) VGL_HIP_TRY(hipMemsetAsync(d_per_vertex, 0, sizeof(int64_t) * (size_t)V, c->stream));
     if (d_degree && V > 0) VGL_HIP_TRY(hipMemcpyAsync(d_degree, k->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, c->stream));

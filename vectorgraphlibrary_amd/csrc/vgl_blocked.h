@@ -72,53 +72,43 @@ struct vgl_blocked_piece {
     int a_bits = VGL_BLK_BITS;                   // log2 of the accumulate-side block (15: 4-byte accumulators, 14: 8-byte)
     int64_t edges = 0;                           // edges kept (self loops may be dropped at build time)
     uint32_t nchunks = 0;
-    uint16_t *g_lo = nullptr, *a_lo = nullptr;
-    uint32_t *mid_to_a = nullptr;
-    uint32_t *vals = nullptr;                    // scratch: 4 bytes per entry (or 8 per chunk: value_bits = 1)
-    vgl_blk_unit *g_units = nullptr, *a_units = nullptr;
+    vgl_dev<uint16_t> g_lo, a_lo;
+    vgl_dev<uint32_t> mid_to_a;
+    vgl_dev<uint32_t> vals;                      // scratch: 4 bytes per entry (or 8 per chunk: value_bits = 1)
+    vgl_dev<vgl_blk_unit> g_units, a_units;
     int n_g_units = 0, n_a_units = 0;
-    vgl_blk_multi *multi = nullptr;
+    vgl_dev<vgl_blk_multi> multi;
     int n_multi = 0, n_slabs = 0;
-    void *slabs = nullptr;                       // n_slabs * 128 KiB (one window of accumulators each)
+    vgl_dev<uint32_t> slabs;                     // n_slabs * 128 KiB (one window of accumulators each)
     // fused tiles (empty unless the layout was built with fuse_min_edges > 0)
-    uint16_t *f_g_lo = nullptr, *f_a_lo = nullptr;
-    vgl_blk_fseg *f_segs = nullptr;
-    vgl_blk_funit *f_units = nullptr;
+    vgl_dev<uint16_t> f_g_lo, f_a_lo;
+    vgl_dev<vgl_blk_fseg> f_segs;
+    vgl_dev<vgl_blk_funit> f_units;
     int n_f_segs = 0, n_f_units = 0;
     uint32_t f_nchunks = 0;
     int64_t f_edges = 0;                         // edges laid out as fused tiles (part of `edges`)
     // keep_edge_index: per slot of g_lo / f_g_lo the CSR position its value comes from (0xFFFFFFFF: a pad entry) -- the counterpart of the
     // reference's edges_reorder_indexes, from which every weight layout is derived (csr_edges_array.hpp:31-40).  A plan's edge values are
     // then one gather pass (vgl_blocked_plan_load_weights) instead of a second radix sort.
-    uint32_t *w_src_mid = nullptr, *w_src_f = nullptr;
+    vgl_dev<uint32_t> w_src_mid, w_src_f;
     int64_t w_base = 0;                          // CSR position of the piece's first edge (a piece indexes the direction's weights from there)
-    int64_t *piece_rowptr = nullptr;             // a piece's rebased row offsets and tile table (hipMalloc; null for a whole direction)
-    int32_t *piece_tile_row = nullptr;
+    vgl_dev<int64_t> piece_rowptr;               // a piece's rebased row offsets and tile table (hipMalloc; null for a whole direction)
+    vgl_dev<int32_t> piece_tile_row;
 };
 
 // The layout of one CSR direction: everything that depends on the graph alone.  Immutable once built; the graph handle and every plan over
 // it hold it by std::shared_ptr, and the last of them frees it.  Plans that share a layout also share its `vals` and `slabs` scratch, so
 // their passes must be ordered on one stream.
 struct vgl_blocked_layout {
-    hipStream_t stream = nullptr;                // the stream whose memory pool owns the arrays of the pieces
     std::vector<vgl_blocked_piece> pieces;       // a pass runs them one after the other (several: min / max-type operators only)
     int64_t edges() const { int64_t e = 0; for (const vgl_blocked_piece &p : pieces) e += p.edges; return e; }
-    vgl_blocked_layout() = default;
-    vgl_blocked_layout(const vgl_blocked_layout &) = delete;
-    vgl_blocked_layout &operator=(const vgl_blocked_layout &) = delete;
-    ~vgl_blocked_layout();
 };
 
 // A plan: a layout plus one set of edge values (f32 per slot of g_lo / f_g_lo) per piece
-struct vgl_blocked_values { float *w_mid = nullptr, *f_w = nullptr; };
+struct vgl_blocked_values { vgl_dev<float> w_mid, f_w; };
 struct vgl_blocked_plan {
     std::shared_ptr<const vgl_blocked_layout> layout;
-    hipStream_t stream = nullptr;                // the stream whose memory pool owns the value arrays
     std::vector<vgl_blocked_values> values;      // one per piece of the layout
-    vgl_blocked_plan() = default;
-    vgl_blocked_plan(const vgl_blocked_plan &) = delete;
-    vgl_blocked_plan &operator=(const vgl_blocked_plan &) = delete;
-    ~vgl_blocked_plan();
 };
 
 struct vgl_blocked_spec {
@@ -336,7 +326,7 @@ static inline int vgl_blocked_pass(vgl_hip_ctx *c, const vgl_blocked_layout &L, 
         if (p->n_a_units > 0) {
             vgl_timed_launch tl(c, accum_name);
             hipLaunchKernelGGL((vgl_k_blk_accumulate<OP>), dim3((unsigned)p->n_a_units), dim3(VGL_BTHREADS), 0, c->stream, (const vgl_blk_unit *)p->a_units,
-                               (const uint16_t *)p->a_lo, (const uint32_t *)p->vals, p->a_count, (typename OP::acc_t *)p->slabs, op);
+                               (const uint16_t *)p->a_lo, (const uint32_t *)p->vals, p->a_count, (typename OP::acc_t *)p->slabs.p, op);
         }
         if (p->n_f_units > 0) {
             // after the two-pass part: the fused tiles load their x windows now, so they already see what the accumulate kernel just improved
@@ -351,7 +341,7 @@ static inline int vgl_blocked_pass(vgl_hip_ctx *c, const vgl_blocked_layout &L, 
         if constexpr (SLABS) {
             if (p->n_multi > 0)
                 hipLaunchKernelGGL((vgl_k_blk_finish_slabs<OP>), dim3((unsigned)p->n_multi, 16), dim3(VGL_BLOCK), 0, c->stream, (const vgl_blk_multi *)p->multi,
-                                   (const typename OP::acc_t *)p->slabs, p->a_count, op);
+                                   (const typename OP::acc_t *)p->slabs.p, p->a_count, op);
         }
         VGL_HIP_TRY(hipGetLastError());
     }

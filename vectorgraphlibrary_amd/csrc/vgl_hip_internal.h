@@ -81,63 +81,145 @@ struct vgl_hip_ctx {
 // the environment as the context sees it: refresh at the entry of a run (cheap when nothing changed), then read from the snapshot
 void vgl_ctx_refresh_env(vgl_hip_ctx *c);
 const char *vgl_env(vgl_hip_ctx *c, const char *name);            // refreshes, then looks up; nullptr when unset (use the value at once)
+int64_t vgl_env_int(vgl_hip_ctx *c, const char *name, int64_t dflt, int64_t lo, int64_t hi);    // unset or empty: dflt; always within [lo, hi]
+
+// Large, short-lived or plan-sized device buffers come from a stream-ordered memory pool OWNED BY THIS LIBRARY (one per device, created on
+// first use: hipMemPoolCreate + hipMallocFromPoolAsync on the context's stream; the device's default pool, which other hipMallocAsync
+// users of the process share, is left as it was found).  The pool keeps what is freed up to VGL_POOL_KEEP_GB (default 48 GiB): a plain
+// hipMalloc right after tens of GB were hipFree'd was measured to stall for 0.5 - 1.3 s on this driver, and fresh mappings cost ~14 ms
+// per GB on first touch; pool memory that has been used once costs neither.  vgl_hip_ctx_trim / vgl_hip_ctx_destroy hand it back.
+hipMemPool_t vgl_lib_pool(int device);          // context.hip; nullptr when the pool could not be created (callers fall back to hipMallocAsync)
+// LARGE blocks do not come from the pool (round 5, late).  Kernels that touched a freshly grown multi-GB pool block ended in a GPU memory fault in
+// 2 - 12 % of the processes that built an RMAT-24 graph (apps/bin/*_hip -s 24: `GPU coredump`, exit by SIGPIPE, the bench's operator leg lost a row;
+// profiles/r05_pool_fault_ab.log: 7 of 60 runs with the scratch of vgl_hip_coo_to_csr from the pool, 0 of 60 with it from hipMalloc; ROCm 7.2; the
+// round's first workaround drew the line at 2^33 bytes, where the fault was first seen).  Blocks of at least vgl_pool_block_limit() bytes
+// (VGL_POOL_MAX_MB, default 64 MiB) are plain hipMalloc blocks, remembered so that vgl_pool_free hands them to hipFree after a stream
+// synchronisation; the pool keeps what it is good at, the many small buffers of a plan build.
+size_t vgl_pool_block_limit();                  // context.hip
+void vgl_big_block_remember(void *p);           // context.hip: p came from hipMalloc
+bool vgl_big_block_forget(void *p);             // context.hip: true (and forgotten) when p came from hipMalloc
+static inline hipError_t vgl_pool_alloc(hipStream_t st, void **p, size_t bytes)
+{
+    if (bytes >= vgl_pool_block_limit()) {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) vgl_big_block_remember(*p);
+        return e;
+    }
+    int dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess)
+        if (hipMemPool_t pool = vgl_lib_pool(dev)) return hipMallocFromPoolAsync(p, bytes ? bytes : 16, pool, st);
+    return hipMallocAsync(p, bytes ? bytes : 16, st);
+}
+static inline void vgl_pool_free(hipStream_t st, void *p)
+{
+    if (!p) return;
+    if (vgl_big_block_forget(p)) { (void)hipStreamSynchronize(st); (void)hipFree(p); }      // (kernels of this stream may still use it)
+    else (void)hipFreeAsync(p, st);
+}
+// One owned device block of T: freed by the destructor, move-only (a copy -- a buffer object handed to a kernel by value -- would be a double
+// free, so it does not compile), read as a plain T * everywhere else.  Where the block comes from is chosen where it is allocated and never
+// changes: alloc(n) is hipMalloc / hipFree, alloc(st, n) the stream-ordered path above (the buffer remembers the stream).  A struct that owns
+// device memory holds it in members of this type; whoever deletes the struct synchronises the stream first (kernels may still use the blocks).
+template <class T>
+struct vgl_dev {
+    T *p = nullptr;
+    hipStream_t st = nullptr;
+    bool pooled = false;
+    vgl_dev() = default;
+    vgl_dev(const vgl_dev &) = delete;
+    vgl_dev &operator=(const vgl_dev &) = delete;
+    vgl_dev(vgl_dev &&o) noexcept : p(o.p), st(o.st), pooled(o.pooled) { o.p = nullptr; }
+    vgl_dev &operator=(vgl_dev &&o) noexcept
+    {
+        if (this != &o) { reset(); p = o.p; st = o.st; pooled = o.pooled; o.p = nullptr; }
+        return *this;
+    }
+    ~vgl_dev() { reset(); }
+    operator T *() const { return p; }
+    int alloc(size_t n)                             // n elements (none: a minimal block), replacing what was held
+    {
+        reset();
+        pooled = false;
+        return held(hipMalloc((void **)&p, sizeof(T) * (n ? n : 1)));
+    }
+    int alloc(hipStream_t stream, size_t n)
+    {
+        reset();
+        pooled = true; st = stream;
+        return held(vgl_pool_alloc(stream, (void **)&p, sizeof(T) * (n ? n : 1)));
+    }
+    int held(hipError_t e)
+    {
+        if (e != hipSuccess) p = nullptr;
+        VGL_HIP_TRY(e);
+        return 0;
+    }
+    void reset()
+    {
+        if (!p) return;
+        if (pooled) vgl_pool_free(st, p); else (void)hipFree(p);
+        p = nullptr;
+    }
+};
 
 struct vgl_dir_csr {                 // one direction of the graph (borrowed) + derived tile table (owned)
     const int64_t *rowptr = nullptr; // nrows+1, rebased to 0
     const int32_t *adj = nullptr;    // global vertex ids
     int64_t edges = 0;
-    int32_t *tile_row = nullptr;     // ntiles+1: local row that contains edge t*VGL_TILE
+    vgl_dev<int32_t> tile_row;       // ntiles+1: local row that contains edge t*VGL_TILE
     int64_t ntiles = 0;
-    int32_t *hub_rows = nullptr;     // pull sums (PageRank, HITS): rows with >= 512 edges grouped per wavefront + offsets (lazy)
+    vgl_dev<int32_t> hub_rows;     // pull sums (PageRank, HITS): rows with >= 512 edges grouped per wavefront + offsets (lazy)
     int32_t nhubs = 0;
     int hub_blocks = 0;              // workgroups of the pull kernel that run the hub schedule
-    int32_t *giant_rows = nullptr;   // rows of at least VGL_PULL_GIANT_DEGREE entries, grouped per workgroup + offsets (the workgroup scheme of vgl_pull.h)
+    vgl_dev<int32_t> giant_rows;   // rows of at least VGL_PULL_GIANT_DEGREE entries, grouped per workgroup + offsets (the workgroup scheme of vgl_pull.h)
     int ngiants = 0, giant_blocks = 0;
-    int32_t *hub_chunks = nullptr;   // unordered hub sums (HITS): per chunk (row, first entry - row start in units of VGL_PULL_CHUNK); then, per hub in
+    vgl_dev<int32_t> hub_chunks;   // unordered hub sums (HITS): per chunk (row, first entry - row start in units of VGL_PULL_CHUNK); then, per hub in
                                      // row order, (row, first chunk, chunks) triples -- see vgl_pull_find_hubs
     int n_hub_chunks = 0, n_hub_list = 0;
-    double *hub_chunk_sums = nullptr;
-    int32_t *pull_blk_row = nullptr; // pull sums: first row of every ordinary workgroup (+ end): <= 256 rows and ~16 K edges each (lazy)
+    vgl_dev<double> hub_chunk_sums;
+    vgl_dev<int32_t> pull_blk_row; // pull sums: first row of every ordinary workgroup (+ end): <= 256 rows and ~16 K edges each (lazy)
     int pull_nblk = 0;
     int64_t max_row = -1;            // longest row (lazy; PageRank's choice between the ordered and the blocked pull)
 };
 
+void vgl_lp_cache_free(struct vgl_lp_cache *p);  // lp.hip
+void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
+struct vgl_lp_cache_delete { void operator()(struct vgl_lp_cache *p) const { vgl_lp_cache_free(p); } };      // (the types are complete in their files only)
+struct vgl_tri_cache_delete { void operator()(struct vgl_tri_cache *p) const { vgl_tri_cache_free(p); } };
 struct vgl_hip_graph {
     uint64_t uid = 0;                // unique per created handle (a freed handle's address may be reused: caches key on this, not on the pointer)
     int32_t V = 0, row_begin = 0, row_end = 0, nrows = 0;
     vgl_dir_csr out, in;
     // scratch shared by the fused algorithms (allocated at creation, sized by V / nrows / edges)
-    uint64_t *bm_visited = nullptr, *bm_front = nullptr, *bm_next = nullptr; // ceil(V/64)+1 words each
-    uint64_t *bm_in_nz = nullptr;    // bit v = owned vertex v has incoming edges (bottom-up candidates)
-    int32_t *in_head = nullptr;      // two planes of 16-byte records (in-neighbours 0-3 and 4-7 of the eight smallest ids, -1 padded), ONE RECORD PER
+    vgl_dev<uint64_t> bm_visited, bm_front, bm_next; // ceil(V/64)+1 words each
+    vgl_dev<uint64_t> bm_in_nz;    // bit v = owned vertex v has incoming edges (bottom-up candidates)
+    vgl_dev<int32_t> in_head;      // two planes of 16-byte records (in-neighbours 0-3 and 4-7 of the eight smallest ids, -1 padded), ONE RECORD PER
                                      // OWNED ROW THAT HAS INCOMING EDGES, in row order: record index = in_nz_rank[group] + rank of the row among the set
                                      // bits of its in_nz word -- the rows without incoming edges (45 % of an RMAT graph) are never bottom-up
                                      // candidates and used to take half of every 128-byte line of the planes
-    int32_t *in_nz_rank = nullptr;   // per 64-row group: number of owned rows with incoming edges before the group
+    vgl_dev<int32_t> in_nz_rank;   // per 64-row group: number of owned rows with incoming edges before the group
     int32_t in_nz_rows = 0;          // owned rows with incoming edges = records per plane
-    int32_t *pr_indeg = nullptr;     // sharded PageRank: in-degrees minus self loops of ALL vertices, summed over the ranks once per graph handle
+    vgl_dev<int32_t> pr_indeg;     // sharded PageRank: in-degrees minus self loops of ALL vertices, summed over the ranks once per graph handle
     bool pr_indeg_ready = false;
-    uint64_t *bm_in_long = nullptr;  // bit v = owned vertex v has more than 8 incoming edges (deferred to the wavefront pass when it misses)
-    int32_t *ids = nullptr;          // nrows
-    int64_t *offs = nullptr;         // nrows+1
-    int32_t *vt_cnt = nullptr, *vt_cnt_off = nullptr;   // per vertex tile
-    int64_t *vt_deg = nullptr, *vt_deg_off = nullptr;
+    vgl_dev<uint64_t> bm_in_long;  // bit v = owned vertex v has more than 8 incoming edges (deferred to the wavefront pass when it misses)
+    vgl_dev<int32_t> ids;          // nrows
+    vgl_dev<int64_t> offs;         // nrows+1
+    vgl_dev<int32_t> vt_cnt, vt_cnt_off;   // per vertex tile
+    vgl_dev<int64_t> vt_deg, vt_deg_off;
     int64_t nvtiles = 0;
-    int32_t *vt_min_deg = nullptr;   // per vertex tile: smallest out-degree of its rows (lower bound of a frontier's edge count from its per-tile sizes)
-    uint8_t *gnf_bits = nullptr;     // generate_new_frontier of the operator classes: the predicate's bits (byte v >> 3, bit v & 7; lazy, V / 8 bytes) -- the
+    vgl_dev<int32_t> vt_min_deg;   // per vertex tile: smallest out-degree of its rows (lower bound of a frontier's edge count from its per-tile sizes)
+    vgl_dev<uint8_t> gnf_bits;     // generate_new_frontier of the operator classes: the predicate's bits (byte v >> 3, bit v & 7; lazy, V / 8 bytes) -- the
                                      // compaction of a SPARSE result reads these 2 MiB instead of 64 MiB of int32 flags (vgl_hip_gnf_begin / _complete)
-    int32_t *tile_first = nullptr;   // out.ntiles + 2
-    int32_t *heavy = nullptr;        // nrows + slack: per-workgroup segments of deferred bottom-up vertices
-    int64_t *bu_partials = nullptr;  // 4 partial counters per bottom-up workgroup
-    uint32_t *tickets = nullptr;     // arrival counters of the "last workgroup finishes the job" kernels (reset by that workgroup)
-    int32_t *epoch = nullptr;        // V (SSSP active filter)
-    float *fscratch = nullptr;       // V (PR contrib)
-    float *fscratch2 = nullptr;      // V (PR rdeg)
-    float *fscratch3 = nullptr;      // V (PR new ranks)
-    int32_t *iscratch = nullptr;     // V (PR indeg when not supplied)
-    uint8_t *ds_tile_active = nullptr;   // delta-stepping SSSP: one byte per out-edge tile (lazy)
-    vgl_hip_graph *transposed = nullptr; // SCC: handle with the two directions swapped (backward reach = BFS on it), lazy, owned
-    int64_t *ds_partials = nullptr;
+    vgl_dev<int32_t> tile_first;   // out.ntiles + 2
+    vgl_dev<int32_t> heavy;        // nrows + slack: per-workgroup segments of deferred bottom-up vertices
+    vgl_dev<int64_t> bu_partials;  // 4 partial counters per bottom-up workgroup
+    vgl_dev<uint32_t> tickets;     // arrival counters of the "last workgroup finishes the job" kernels (reset by that workgroup)
+    vgl_dev<int32_t> epoch;        // V (SSSP active filter)
+    vgl_dev<float> fscratch;       // V (PR contrib)
+    vgl_dev<float> fscratch2;      // V (PR rdeg)
+    vgl_dev<float> fscratch3;      // V (PR new ranks)
+    vgl_dev<int32_t> iscratch;     // V (PR indeg when not supplied)
+    std::unique_ptr<vgl_hip_graph> transposed;   // SCC: handle with the two directions swapped (backward reach = BFS on it), lazy, owned
     // blocked layouts (vgl_blocked.h): lazy, shared with the plans built over them -- the graph drops its reference, the last holder frees
     std::shared_ptr<const struct vgl_blocked_layout> blk_pr;    // PageRank's blocked pull over the outgoing CSR
     std::shared_ptr<const struct vgl_blocked_layout> blk_cc;    // the Shiloach-Vishkin hook as a blocked pass
@@ -145,28 +227,34 @@ struct vgl_hip_graph {
     std::shared_ptr<const struct vgl_blocked_layout> blk_path;  // the path layouts (Bellman-Ford / widest-path pull: rows gather, edge index kept): built
                                                                 // once per graph, every vgl_hip_sssp_pull_plan is a plan over it with weights of its own
     std::string blk_path_key;                    // the layout switches it was built under (fuse threshold, unit sizes, piece bound: the tests vary them per plan)
-    struct vgl_lp_cache *lp[2] = {nullptr, nullptr};   // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
-    struct vgl_tri_cache *tri = nullptr;         // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
+    std::unique_ptr<struct vgl_lp_cache, vgl_lp_cache_delete> lp[2];   // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
+    std::unique_ptr<struct vgl_tri_cache, vgl_tri_cache_delete> tri;   // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
 };
-void vgl_lp_cache_free(struct vgl_lp_cache *p);  // lp.hip
-void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
 
 struct vgl_hip_frontier {
     vgl_hip_graph *g = nullptr;
-    int32_t *flags = nullptr;        // V
+    int32_t *flags = nullptr;        // V: what the kernels use -- own_flags / own_ids below, or the arrays of the caller of vgl_hip_frontier_create_on
     int32_t *ids = nullptr;          // V
+    vgl_dev<int32_t> own_flags, own_ids;   // empty when the frontier borrows its arrays
     int32_t size = 0;
     int64_t neighbours = 0;
     int sparsity = VGL_HIP_FRONTIER_ALL_ACTIVE;
     // advance plan of a SPARSE frontier (built on demand by vgl_hip_frontier_advance_plan)
-    int64_t *offs = nullptr;         // V+1 exclusive edge offsets of ids[] in the planned direction
-    int32_t *tile_first = nullptr;   // ceil(E/VGL_TILE)+2
-    int64_t *blk_sum = nullptr, *blk_off = nullptr;   // per 2048-id block degree sums / offsets
-    bool borrowed = false;           // flags / ids belong to the caller (vgl_hip_frontier_create_on)
+    vgl_dev<int64_t> offs;           // V+1 exclusive edge offsets of ids[] in the planned direction
+    vgl_dev<int32_t> tile_first;     // ceil(E/VGL_TILE)+2
+    vgl_dev<int64_t> blk_sum, blk_off;  // per 2048-id block degree sums / offsets
     int plan_dir = -1;               // direction whose edge offsets `offs` AND tile table `tile_first` describe the current ids (-1: none; set by
                                      // vgl_hip_gnf_complete and vgl_hip_frontier_advance_plan, voided by every change of the ids)
     int64_t plan_edges = 0;          // edges of the ids in that direction
 };
+
+// a handle while its entry point builds it: an early return deletes it the way its destroy function does, after a stream synchronise
+template <class T>
+struct vgl_synced_delete {
+    vgl_hip_ctx *c;
+    void operator()(T *p) const { (void)hipStreamSynchronize(c->stream); delete p; }
+};
+template <class T> using vgl_building = std::unique_ptr<T, vgl_synced_delete<T>>;
 
 // timing helpers (no-ops unless ctx->timing)
 struct vgl_timed_launch {
@@ -211,52 +299,6 @@ int vgl_bitmap_to_ids(vgl_hip_ctx *c, int64_t words, const uint64_t *d_bits, int
 int vgl_zero_words(vgl_hip_ctx *c, uint64_t *d_words, int64_t words);      // one launch (bfs.hip)
 
 static inline int64_t vgl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// Large, short-lived or plan-sized device buffers come from a stream-ordered memory pool OWNED BY THIS LIBRARY (one per device, created on
-// first use: hipMemPoolCreate + hipMallocFromPoolAsync on the context's stream; the device's default pool, which other hipMallocAsync
-// users of the process share, is left as it was found).  The pool keeps what is freed up to VGL_POOL_KEEP_GB (default 48 GiB): a plain
-// hipMalloc right after tens of GB were hipFree'd was measured to stall for 0.5 - 1.3 s on this driver, and fresh mappings cost ~14 ms
-// per GB on first touch; pool memory that has been used once costs neither.  vgl_hip_ctx_trim / vgl_hip_ctx_destroy hand it back.
-hipMemPool_t vgl_lib_pool(int device);          // context.hip; nullptr when the pool could not be created (callers fall back to hipMallocAsync)
-// LARGE blocks do not come from the pool (round 5, late).  Kernels that touched a freshly grown multi-GB pool block ended in a GPU memory fault in
-// 2 - 12 % of the processes that built an RMAT-24 graph (apps/bin/*_hip -s 24: `GPU coredump`, exit by SIGPIPE, the bench's operator leg lost a row;
-// profiles/r05_pool_fault_ab.log: 7 of 60 runs with the scratch of vgl_hip_coo_to_csr from the pool, 0 of 60 with it from hipMalloc; ROCm 7.2; the
-// round's first workaround drew the line at 2^33 bytes, where the fault was first seen).  Blocks of at least vgl_pool_block_limit() bytes
-// (VGL_POOL_MAX_MB, default 64 MiB) are plain hipMalloc blocks, remembered so that vgl_pool_free hands them to hipFree after a stream
-// synchronisation; the pool keeps what it is good at, the many small buffers of a plan build.
-size_t vgl_pool_block_limit();                  // context.hip
-void vgl_big_block_remember(void *p);           // context.hip: p came from hipMalloc
-bool vgl_big_block_forget(void *p);             // context.hip: true (and forgotten) when p came from hipMalloc
-static inline hipError_t vgl_pool_alloc(hipStream_t st, void **p, size_t bytes)
-{
-    if (bytes >= vgl_pool_block_limit()) {
-        const hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) vgl_big_block_remember(*p);
-        return e;
-    }
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess)
-        if (hipMemPool_t pool = vgl_lib_pool(dev)) return hipMallocFromPoolAsync(p, bytes ? bytes : 16, pool, st);
-    return hipMallocAsync(p, bytes ? bytes : 16, st);
-}
-static inline void vgl_pool_free(hipStream_t st, void *p)
-{
-    if (!p) return;
-    if (vgl_big_block_forget(p)) { (void)hipStreamSynchronize(st); (void)hipFree(p); }      // (kernels of this stream may still use it)
-    else (void)hipFreeAsync(p, st);
-}
-// scratch of the graph builders (a block and where it came from: kept as a type of its own for the cleanup guards of gen.hip)
-struct vgl_scratch {
-    void *p = nullptr;
-    bool pooled = false;
-};
-static inline hipError_t vgl_scratch_alloc(hipStream_t st, vgl_scratch *b, size_t bytes) { b->pooled = true; return vgl_pool_alloc(st, &b->p, bytes); }
-static inline void vgl_scratch_free(hipStream_t st, vgl_scratch *b)
-{
-    if (!b->p) return;
-    vgl_pool_free(st, b->p);
-    b->p = nullptr;
-}
 
 // ---------------------------------------------------------------------------------------------
 // device helpers (wave = 64 lanes)
