@@ -6,7 +6,8 @@
 // vgl_compute_api/gpu/graph_abstractions_gpu.h:17-190.  It reads CSRGraph / VectorCSRGraph through their public accessors and writes
 // FrontierCSR / FrontierVectorCSR through friend access, exactly like GraphAbstractionsGPU / GraphAbstractionsMulticore.
 //
-//   kernels   : vectorgraphlibrary_amd/hip/vgl_hip_kernels.hpp (templated on the user's device lambdas; plain pointers only)
+//   kernels   : vectorgraphlibrary_amd/hip/vgl_hip_kernels.hpp (templated on the user's device lambdas; plain pointers only) and, in the same file, the
+//               launchers of those kernels that this class and the repository's own class both call (mode ladders and argument lists written once)
 //   library   : libvgl_hip.so through the C ABI include/vgl_hip.h -- graph handles work on DEVICE COPIES of the containers' vertex_pointers / adjacent_ids
 //               (+ the vector extension), made when a container is first used; frontier handles BORROW the containers' flags / ids
 //               (vgl_hip_frontier_create_on), so host code of the reference that writes those arrays (add_vertex, set_all_active) needs no change
@@ -206,7 +207,8 @@ private:
         for (auto &kv : frontier_handles) vgl_hip_frontier_destroy(ctx, kv.second.handle);
         frontier_handles.clear();
     }
-    static int grid_for(long long n) { return (int)std::min<long long>(4096, std::max<long long>(1, (n + VGL_BLOCK - 1) / VGL_BLOCK)); }
+    static constexpr int GRID_CAP = 4096;           // workgroups of a grid-stride launch
+    static int grid_for(long long n) { return (int)vgl_grid_for(n, GRID_CAP); }
     static int sparsity_code(FrontierSparsityType t)
     { return t == ALL_ACTIVE_FRONTIER ? VGL_HIP_FRONTIER_ALL_ACTIVE : (t == DENSE_FRONTIER ? VGL_HIP_FRONTIER_DENSE : VGL_HIP_FRONTIER_SPARSE); }
     void finish() { VGL_HIP_BIND_RT(hipGetLastError()); VGL_HIP_BIND_RT(hipStreamSynchronize(stream)); }
@@ -338,44 +340,62 @@ private:
         _frontier.hip_plan_token = fb.plan_token;
     }
 
-    // per-vertex operator over the active vertices of a range of ids
-    template <typename Op>
-    void vertex_pass(int _vertices_count, const long long *_vertex_pointers, FrontierSparsityType _type, int *_flags, int *_ids, int _frontier_size,
-                     int _row_lo, int _row_hi, Op &&op)
+    // the front half of a frontier generation on a CSR-family container: user arrays up, handles, the library's buffers, the count pass with the user's
+    // condition as its predicate.  The caller may queue more on the stream, then hands `seq` to vgl_hip_gnf_complete.
+    struct gnf_started { vgl_hip_graph *gh; vgl_hip_frontier *fh; vgl_hip_gnf_buffers b; };
+    template <typename GraphContainer, typename FrontierContainer, typename FilterCondition>
+    gnf_started gnf_start(GraphContainer &_graph, FrontierContainer &_frontier, FilterCondition &&filter_cond)
     {
-        using O = typename std::decay<Op>::type;
-        if (_type == ALL_ACTIVE_FRONTIER)
-            hipLaunchKernelGGL((vgl_k_vertex_op<0, O>), dim3(grid_for(_vertices_count)), dim3(VGL_BLOCK), 0, stream, _vertices_count, _vertex_pointers, _flags, _ids, _row_lo, _row_hi, op);
-        else if (_type == DENSE_FRONTIER)
-            hipLaunchKernelGGL((vgl_k_vertex_op<1, O>), dim3(grid_for(_vertices_count)), dim3(VGL_BLOCK), 0, stream, _vertices_count, _vertex_pointers, _flags, _ids, _row_lo, _row_hi, op);
-        else if (_frontier_size > 0)
-            hipLaunchKernelGGL((vgl_k_vertex_op<2, O>), dim3(grid_for(_frontier_size)), dim3(VGL_BLOCK), 0, stream, _frontier_size, _vertex_pointers, _flags, _ids, _row_lo, _row_hi, op);
+        hip_shadows_to_device(stream);
+        gnf_started s;
+        s.gh = handle_of(_graph);
+        s.fh = handle_of(_frontier, s.gh);
+        VGL_HIP_BIND_CALL(vgl_hip_gnf_begin(ctx, s.gh, s.fh, 1, &s.b));
+        vgl_launch_gnf_count(stream, vgl_pred_user<typename std::decay<FilterCondition>::type>{filter_cond, binding_of(_graph).d_vertex_pointers}, s.b);
+        VGL_HIP_BIND_RT(hipGetLastError());
+        return s;
     }
+
+    // the frontier container and the device copy of a CSR-family container as the launchers of vgl_hip_kernels.hpp take them
+    template <typename FrontierContainer>
+    static vgl_active_view active_of(FrontierContainer &_frontier)
+    {
+        LOAD_FRONTIER_DATA(_frontier);
+        const FrontierSparsityType t = _frontier.get_sparsity_type();
+        return vgl_active_view{t == ALL_ACTIVE_FRONTIER ? 0 : (t == DENSE_FRONTIER ? 1 : 2), frontier_flags, frontier_ids, frontier_size};
+    }
+    template <typename GraphContainer>
+    vgl_rows_view rows_of(GraphContainer &_graph)
+    {
+        const graph_binding &gb = binding_of(_graph);
+        return vgl_rows_view{gb.d_vertex_pointers, gb.d_adjacent_ids, (long long)_graph.get_edges_count(), _graph.get_vertices_count()};
+    }
+    // where the per-vertex kernels read a vertex's connection count from: the containers compute_worker / reduce_worker serve
+    const long long *row_pointers_of(CSRGraph &_graph) { return binding_of(_graph).d_vertex_pointers; }
+    const long long *row_pointers_of(VectorCSRGraph &_graph) { return binding_of(_graph).d_vertex_pointers; }
+    const long long *row_pointers_of(EdgesListGraph &_graph) { return edges_list_of(_graph).d_degree_prefix; }
+    template <typename GraphContainer>
+    static constexpr bool has_row_pointers() { return std::is_same<GraphContainer, CSRGraph>::value || std::is_same<GraphContainer, VectorCSRGraph>::value || std::is_same<GraphContainer, EdgesListGraph>::value; }
+
     template <typename Op> static constexpr bool is_empty_op() { return std::is_empty<typename std::decay<Op>::type>::value && std::is_same<typename std::decay<Op>::type, decltype(EMPTY_VERTEX_OP)>::value; }
 
     // edges of the active vertices with ids in [_row_lo, _row_hi): static edge tiles (ALL_ACTIVE / DENSE) or the frontier's own edge space (SPARSE)
     template <typename GraphContainer, typename FrontierContainer, typename EdgeOp>
     void edge_pass(GraphContainer &_graph, FrontierContainer &_frontier, long long _process_shift, int _row_lo, int _row_hi, EdgeOp &&edge_op)
     {
-        using E = typename std::decay<EdgeOp>::type;
-        LOAD_FRONTIER_DATA(_frontier);
-        const graph_binding &gb = binding_of(_graph);
+        const vgl_active_view active = active_of(_frontier);
+        const vgl_rows_view rows = rows_of(_graph);
         const long long *host_vertex_pointers = _graph.get_vertex_pointers();      // (read on the host below: the container's own array)
-        const long long *vertex_pointers = gb.d_vertex_pointers;
-        const int *adjacent_ids = gb.d_adjacent_ids;
-        const long long edges_count = _graph.get_edges_count();
-        vgl_hip_graph *gh = gb.handle;
-        if (_frontier.get_sparsity_type() == SPARSE_FRONTIER) {
-            if (frontier_size == 0) return;
+        vgl_hip_graph *gh = handle_of(_graph);
+        if (active.mode == 2) {
+            if (active.size == 0) return;
             vgl_hip_frontier *fh = handle_of(_frontier, gh);
             const int64_t *offs; const int32_t *tile_first; int64_t M;
             VGL_HIP_BIND_CALL(vgl_hip_frontier_advance_plan(ctx, gh, fh, 0, &offs, &tile_first, &M));
-            if (M > 0)
-                hipLaunchKernelGGL((vgl_k_advance_sparse<E>), dim3((unsigned)((M + VGL_TILE - 1) / VGL_TILE)), dim3(VGL_ADV_THREADS), 0, stream, frontier_ids, offs, tile_first,
-                                   frontier_size, (long long)M, vertex_pointers, adjacent_ids, _process_shift, _row_lo, _row_hi, edge_op);
+            vgl_launch_advance_sparse(stream, rows, active, offs, tile_first, (long long)M, _process_shift, _row_lo, _row_hi, edge_op);
             return;
         }
-        if (edges_count == 0 || _row_hi <= _row_lo) return;
+        if (rows.edges == 0 || _row_hi <= _row_lo) return;
         const int32_t *tile_row; int64_t ntiles;
         VGL_HIP_BIND_CALL(vgl_hip_graph_tile_rows(gh, 0, &tile_row, &ntiles));
         // rows are stored in id order: the tiles past the last edge of row _row_hi - 1 hold nothing of the range
@@ -383,110 +403,51 @@ private:
         const long long first_edge = host_vertex_pointers[_row_lo];
         if (last_edge <= first_edge) return;
         const unsigned tiles = (unsigned)std::min<long long>(ntiles, (last_edge + VGL_TILE - 1) / VGL_TILE);
-        if (_frontier.get_sparsity_type() == DENSE_FRONTIER)
-            hipLaunchKernelGGL((vgl_k_advance_static<true, E>), dim3(tiles), dim3(VGL_BLOCK), 0, stream, vertex_pointers, adjacent_ids, tile_row, edges_count, _process_shift,
-                               frontier_flags, _row_lo, _row_hi, edge_op);
-        else
-            hipLaunchKernelGGL((vgl_k_advance_static<false, E>), dim3(tiles), dim3(VGL_BLOCK), 0, stream, vertex_pointers, adjacent_ids, tile_row, edges_count, _process_shift,
-                               frontier_flags, _row_lo, _row_hi, edge_op);
+        vgl_launch_advance_tiles(stream, rows, active, tile_row, tiles, _process_shift, _row_lo, _row_hi, edge_op);
     }
-
-    // the same, one lane per active vertex (safe stores): pre, the vertex's edges in adjacency order, post
+    // one advance over the rows [_row_lo, _row_hi): pre -> edges of the active vertices -> post as three passes (a pass of an empty operator is
+    // skipped), or under safe stores one lane per active vertex: pre, the vertex's edges in adjacency order, post (vgl_k_advance_rows)
     template <typename GraphContainer, typename FrontierContainer, typename EdgeOp, typename PreOp, typename PostOp>
-    void rows_pass(GraphContainer &_graph, FrontierContainer &_frontier, long long _process_shift, int _row_lo, int _row_hi, EdgeOp &&edge_op, PreOp &&pre_op, PostOp &&post_op)
+    void advance_rows_range(GraphContainer &_graph, FrontierContainer &_frontier, long long _process_shift, int _row_lo, int _row_hi, EdgeOp &&edge_op, PreOp &&pre_op,
+                            bool _skip_pre, PostOp &&post_op, bool _skip_post)
     {
-        using E = typename std::decay<EdgeOp>::type; using P = typename std::decay<PreOp>::type; using Q = typename std::decay<PostOp>::type;
-        LOAD_FRONTIER_DATA(_frontier);
-        const graph_binding &gb = binding_of(_graph);
-        const int vertices_count = _graph.get_vertices_count();
-        const FrontierSparsityType t = _frontier.get_sparsity_type();
-        if (_row_hi <= _row_lo) return;
-        if (t == ALL_ACTIVE_FRONTIER)
-            hipLaunchKernelGGL((vgl_k_advance_rows<0, E, P, Q>), dim3(grid_for(vertices_count)), dim3(VGL_BLOCK), 0, stream, vertices_count, gb.d_vertex_pointers, gb.d_adjacent_ids,
-                               frontier_flags, frontier_ids, _process_shift, _row_lo, _row_hi, edge_op, pre_op, post_op);
-        else if (t == DENSE_FRONTIER)
-            hipLaunchKernelGGL((vgl_k_advance_rows<1, E, P, Q>), dim3(grid_for(vertices_count)), dim3(VGL_BLOCK), 0, stream, vertices_count, gb.d_vertex_pointers, gb.d_adjacent_ids,
-                               frontier_flags, frontier_ids, _process_shift, _row_lo, _row_hi, edge_op, pre_op, post_op);
-        else if (frontier_size > 0)
-            hipLaunchKernelGGL((vgl_k_advance_rows<2, E, P, Q>), dim3(grid_for(frontier_size)), dim3(VGL_BLOCK), 0, stream, frontier_size, gb.d_vertex_pointers, gb.d_adjacent_ids,
-                               frontier_flags, frontier_ids, _process_shift, _row_lo, _row_hi, edge_op, pre_op, post_op);
+        const vgl_active_view active = active_of(_frontier);
+        const vgl_rows_view rows = rows_of(_graph);
+        if (safe_stores) {
+            if (_row_hi > _row_lo) vgl_launch_advance_rows(stream, GRID_CAP, rows, active, _process_shift, _row_lo, _row_hi, edge_op, pre_op, post_op);
+            return;
+        }
+        if (!_skip_pre) vgl_launch_vertex_op(stream, GRID_CAP, rows, active, _row_lo, _row_hi, pre_op);
+        edge_pass(_graph, _frontier, _process_shift, _row_lo, _row_hi, edge_op);
+        if (!_skip_post) vgl_launch_vertex_op(stream, GRID_CAP, rows, active, _row_lo, _row_hi, post_op);
     }
 
-    // compute inner implementation
+    // compute inner implementation: CSR_GRAPH, VECTOR_CSR_GRAPH, EDGES_LIST_GRAPH (row_pointers_of); the other containers throw
     template <typename ComputeOperation, typename GraphContainer, typename FrontierContainer>
-    void compute_worker(GraphContainer &_graph, FrontierContainer &_frontier, ComputeOperation &&compute_op);
-    template <typename ComputeOperation>
-    void compute_worker(CSRGraph &_graph, FrontierCSR &_frontier, ComputeOperation &&compute_op)
-    { compute_on_csr_pointers(_graph, _frontier, compute_op); }
-    template <typename ComputeOperation>
-    void compute_worker(VectorCSRGraph &_graph, FrontierVectorCSR &_frontier, ComputeOperation &&compute_op)
-    { compute_on_csr_pointers(_graph, _frontier, compute_op); }
-    template <typename ComputeOperation>
-    void compute_worker(EdgesListGraph &_graph, FrontierEdgesList &_frontier, ComputeOperation &&compute_op)
+    typename std::enable_if<has_row_pointers<GraphContainer>()>::type compute_worker(GraphContainer &_graph, FrontierContainer &_frontier, ComputeOperation &&compute_op)
     {
-        LOAD_FRONTIER_DATA(_frontier);
         hip_shadows_to_device(stream);
         const int vertices_count = _graph.get_vertices_count();
-        vertex_pass(vertices_count, edges_list_of(_graph).d_degree_prefix, _frontier.get_sparsity_type(), frontier_flags, frontier_ids, frontier_size, 0, vertices_count, compute_op);
+        vgl_launch_vertex_op(stream, GRID_CAP, vgl_rows_view{row_pointers_of(_graph), nullptr, 0, vertices_count}, active_of(_frontier), 0, vertices_count, compute_op);
         finish();
     }
     template <typename ComputeOperation, typename GraphContainer, typename FrontierContainer>
-    void compute_on_csr_pointers(GraphContainer &_graph, FrontierContainer &_frontier, ComputeOperation &&compute_op)
-    {
-        LOAD_FRONTIER_DATA(_frontier);
-        hip_shadows_to_device(stream);
-        const int vertices_count = _graph.get_vertices_count();
-        vertex_pass(vertices_count, binding_of(_graph).d_vertex_pointers, _frontier.get_sparsity_type(), frontier_flags, frontier_ids, frontier_size, 0, vertices_count, compute_op);
-        finish();
-    }
+    typename std::enable_if<!has_row_pointers<GraphContainer>()>::type compute_worker(GraphContainer &_graph, FrontierContainer &_frontier, ComputeOperation &&compute_op)
+    { throw "Error in GraphAbstractionsHIP::compute : this graph container is not served by the HIP backend"; }
 
-    // reduce inner implementation
+    // reduce inner implementation: the same containers
     template <typename _T, typename ReduceOperation, typename GraphContainer, typename FrontierContainer>
-    void reduce_worker(GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result);
-    template <typename _T, typename ReduceOperation>
-    void reduce_worker(CSRGraph &_graph, FrontierCSR &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
-    { reduce_on_csr_pointers(_graph, _frontier, reduce_op, _reduce_type, _result); }
-    template <typename _T, typename ReduceOperation>
-    void reduce_worker(VectorCSRGraph &_graph, FrontierVectorCSR &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
-    { reduce_on_csr_pointers(_graph, _frontier, reduce_op, _reduce_type, _result); }
-    template <typename _T, typename ReduceOperation>
-    void reduce_worker(EdgesListGraph &_graph, FrontierEdgesList &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
-    { reduce_on_pointers(edges_list_of(_graph).d_degree_prefix, _graph, _frontier, reduce_op, _reduce_type, _result); }
-    template <typename _T, typename ReduceOperation, typename GraphContainer, typename FrontierContainer>
-    void reduce_on_csr_pointers(GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
-    { reduce_on_pointers(binding_of(_graph).d_vertex_pointers, _graph, _frontier, reduce_op, _reduce_type, _result); }
-    template <typename _T, typename ReduceOperation, typename GraphContainer, typename FrontierContainer>
-    void reduce_on_pointers(const long long *vertex_pointers, GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
+    typename std::enable_if<has_row_pointers<GraphContainer>()>::type reduce_worker(GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
     {
         if (_reduce_type != REDUCE_SUM && _reduce_type != REDUCE_MAX) throw "Error in GraphAbstractionsHIP::reduce_worker: unsupported reduce type";   // multicore/reduce.hpp:144-150
-        using R = typename std::decay<ReduceOperation>::type;
-        LOAD_FRONTIER_DATA(_frontier);
         hip_shadows_to_device(stream);
-        const FrontierSparsityType t = _frontier.get_sparsity_type();
-        const int n = t == SPARSE_FRONTIER ? frontier_size : _graph.get_vertices_count();
-        _result = 0;
-        if (n <= 0) return;
-        const int nb = (int)std::min<long long>(1024, ((long long)n + VGL_BLOCK - 1) / VGL_BLOCK);
-        const bool mx = _reduce_type == REDUCE_MAX;
-#define VGL_BIND_REDUCE(MODE)                                                                                                                                     \
-        do {                                                                                                                                                      \
-            if (mx) hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, true, R>), dim3(nb), dim3(VGL_BLOCK), 0, stream, n, vertex_pointers, frontier_flags, frontier_ids, reduce_op, reduce_partials); \
-            else hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, false, R>), dim3(nb), dim3(VGL_BLOCK), 0, stream, n, vertex_pointers, frontier_flags, frontier_ids, reduce_op, reduce_partials); \
-        } while (0)
-        if (t == ALL_ACTIVE_FRONTIER) VGL_BIND_REDUCE(0);
-        else if (t == DENSE_FRONTIER) VGL_BIND_REDUCE(1);
-        else VGL_BIND_REDUCE(2);
-#undef VGL_BIND_REDUCE
-        VGL_HIP_BIND_RT(hipGetLastError());
         double r = 0.0;
-        if (mx) {
-            hipLaunchKernelGGL(vgl_k_max_fold, dim3(1), dim3(VGL_BLOCK), 0, stream, nb, (const double *)reduce_partials, reduce_partials + 1024);
-            VGL_HIP_BIND_RT(hipGetLastError());
-            VGL_HIP_BIND_CALL(vgl_hip_memcpy_d2h(ctx, &r, reduce_partials + 1024, sizeof(double)));
-        } else
-            VGL_HIP_BIND_CALL(vgl_hip_reduce_sum_f64_buffer(ctx, nb, reduce_partials, &r));      // fixed-order fold of the partials
+        VGL_HIP_BIND_CALL(vgl_reduce(ctx, stream, row_pointers_of(_graph), active_of(_frontier), _graph.get_vertices_count(), reduce_op, _reduce_type == REDUCE_MAX, reduce_partials, &r));
         _result = (_T)r;
     }
+    template <typename _T, typename ReduceOperation, typename GraphContainer, typename FrontierContainer>
+    typename std::enable_if<!has_row_pointers<GraphContainer>()>::type reduce_worker(GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
+    { throw "Error in GraphAbstractionsHIP::reduce : this graph container is not served by the HIP backend"; }
 
     // advance inner implementation
     template <typename EdgeOperation, typename VertexPreprocessOperation, typename VertexPostprocessOperation, typename CollectiveEdgeOperation,
@@ -673,14 +634,6 @@ GraphAbstractionsHIP::~GraphAbstractionsHIP()
     hipHostFree(part_sizes);
 }
 
-template <typename ComputeOperation, typename GraphContainer, typename FrontierContainer>
-void GraphAbstractionsHIP::compute_worker(GraphContainer &_graph, FrontierContainer &_frontier, ComputeOperation &&compute_op)
-{ throw "Error in GraphAbstractionsHIP::compute : this graph container is not served by the HIP backend"; }
-
-template <typename _T, typename ReduceOperation, typename GraphContainer, typename FrontierContainer>
-void GraphAbstractionsHIP::reduce_worker(GraphContainer &_graph, FrontierContainer &_frontier, ReduceOperation &&reduce_op, REDUCE_TYPE _reduce_type, _T &_result)
-{ throw "Error in GraphAbstractionsHIP::reduce : this graph container is not served by the HIP backend"; }
-
 // CSR_GRAPH: pre -> every edge of the active vertices -> post; the collective set is never called (advance_worker.hpp:62-149)
 template <typename EdgeOperation, typename VertexPreprocessOperation, typename VertexPostprocessOperation, typename CollectiveEdgeOperation,
           typename CollectiveVertexPreprocessOperation, typename CollectiveVertexPostprocessOperation>
@@ -692,21 +645,11 @@ void GraphAbstractionsHIP::advance_worker(CSRGraph &_graph, FrontierCSR &_fronti
     Timer tm;
     tm.start();
     hip_shadows_to_device(stream);
-    const int vertices_count = _graph.get_vertices_count();
-    const long long edges_count = _graph.get_edges_count();
-    const long long *vertex_pointers = binding_of(_graph).d_vertex_pointers;       // the device copy (the kernels' view of the container)
-    LOAD_FRONTIER_DATA(_frontier);
-    const long long process_shift = compute_process_shift(current_traversal_direction, CSR_STORAGE);
-    const FrontierSparsityType t = _frontier.get_sparsity_type();
-    if (safe_stores) rows_pass(_graph, _frontier, process_shift, 0, vertices_count, edge_op, vertex_preprocess_op, vertex_postprocess_op);
-    else {
-        if (!is_empty_op<VertexPreprocessOperation>()) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, vertices_count, vertex_preprocess_op);
-        edge_pass(_graph, _frontier, process_shift, 0, vertices_count, edge_op);
-        if (!is_empty_op<VertexPostprocessOperation>()) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, vertices_count, vertex_postprocess_op);
-    }
+    advance_rows_range(_graph, _frontier, compute_process_shift(current_traversal_direction, CSR_STORAGE), 0, _graph.get_vertices_count(), edge_op,
+                       vertex_preprocess_op, is_empty_op<VertexPreprocessOperation>(), vertex_postprocess_op, is_empty_op<VertexPostprocessOperation>());
     finish();
     tm.end();
-    const long long work = t == ALL_ACTIVE_FRONTIER ? edges_count : frontier_neighbours_count;
+    const long long work = _frontier.get_sparsity_type() == ALL_ACTIVE_FRONTIER ? (long long)_graph.get_edges_count() : _frontier.get_neighbours_count();
     performance_stats.update_advance_stats(tm.get_time(), work * INT_ELEMENTS_PER_EDGE * sizeof(int), work);
 }
 
@@ -745,20 +688,12 @@ void GraphAbstractionsHIP::advance_worker(VectorCSRGraph &_graph, FrontierVector
         const vgl_range_edge_op<E, CE> both{edge_op, collective_edge_op, collective_start};
         const bool no_pre = is_empty_op<VertexPreprocessOperation>() && is_empty_op<CollectiveVertexPreprocessOperation>();
         const bool no_post = is_empty_op<VertexPostprocessOperation>() && is_empty_op<CollectiveVertexPostprocessOperation>();
-        if (safe_stores) rows_pass(_graph, _frontier, csr_shift, 0, vertices_count, both, pre, post);
-        else {
-            if (!no_pre) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, vertices_count, pre);
-            edge_pass(_graph, _frontier, csr_shift, 0, vertices_count, both);
-            if (!no_post) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, vertices_count, post);
-        }
+        advance_rows_range(_graph, _frontier, csr_shift, 0, vertices_count, both, pre, no_pre, post, no_post);
         work = frontier_neighbours_count;
     } else {
-        if (collective_start > 0 && safe_stores) rows_pass(_graph, _frontier, csr_shift, 0, collective_start, edge_op, vertex_preprocess_op, vertex_postprocess_op);
-        else if (collective_start > 0) {
-            if (!is_empty_op<VertexPreprocessOperation>()) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, collective_start, vertex_preprocess_op);
-            edge_pass(_graph, _frontier, csr_shift, 0, collective_start, edge_op);
-            if (!is_empty_op<VertexPostprocessOperation>()) vertex_pass(vertices_count, vertex_pointers, t, frontier_flags, frontier_ids, frontier_size, 0, collective_start, vertex_postprocess_op);
-        }
+        if (collective_start > 0)
+            advance_rows_range(_graph, _frontier, csr_shift, 0, collective_start, edge_op, vertex_preprocess_op, is_empty_op<VertexPreprocessOperation>(), vertex_postprocess_op,
+                               is_empty_op<VertexPostprocessOperation>());
         if (ve_vector_segments_count > 0) {
             const unsigned blocks = (unsigned)(((long long)ve_vector_segments_count * 64 + VGL_BLOCK - 1) / VGL_BLOCK);
             if (t == DENSE_FRONTIER)
@@ -781,21 +716,14 @@ void GraphAbstractionsHIP::advance_worker(VectorCSRGraph &_graph, FrontierVector
 template <typename FilterCondition>
 void GraphAbstractionsHIP::generate_new_frontier_worker(CSRGraph &_graph, FrontierCSR &_frontier, FilterCondition &&filter_cond)
 {
-    using C = typename std::decay<FilterCondition>::type;
     Timer tm;
     tm.start();
-    hip_shadows_to_device(stream);
     _frontier.set_direction(current_traversal_direction);
     const int vertices_count = _graph.get_vertices_count();
-    vgl_hip_graph *gh = handle_of(_graph);
-    vgl_hip_frontier *fh = handle_of(_frontier, gh);
-    vgl_hip_gnf_buffers b;
-    VGL_HIP_BIND_CALL(vgl_hip_gnf_begin(ctx, gh, fh, 1, &b));
-    const vgl_pred_user<C> pred{filter_cond, binding_of(_graph).d_vertex_pointers};
-    hipLaunchKernelGGL((vgl_k_gnf_count<vgl_pred_user<C>>), dim3((unsigned)b.nvtiles), dim3(VGL_BLOCK), 0, stream, pred, b.nrows, b.row_begin, b.out_rowptr, b.vt_cnt, b.vt_deg,
-                       b.front_bytes, (uint8_t *)nullptr, b.flags, b.ticket, b.vt_cnt_off, b.vt_deg_off, b.counters, b.plan_offs, b.host_counters, b.seq);
-    VGL_HIP_BIND_RT(hipGetLastError());
-    VGL_HIP_BIND_CALL(vgl_hip_gnf_complete(ctx, gh, fh, 0.0, 1, b.seq));
+    const gnf_started s = gnf_start(_graph, _frontier, filter_cond);
+    vgl_hip_graph *gh = s.gh;
+    vgl_hip_frontier *fh = s.fh;
+    VGL_HIP_BIND_CALL(vgl_hip_gnf_complete(ctx, gh, fh, 0.0, 1, s.b.seq));
     int32_t size = 0; int64_t neighbours = 0; int sparsity = 0;
     VGL_HIP_BIND_CALL(vgl_hip_frontier_info(ctx, fh, &size, &neighbours, &sparsity));
     finish();
@@ -813,19 +741,13 @@ void GraphAbstractionsHIP::generate_new_frontier_worker(CSRGraph &_graph, Fronti
 template <typename FilterCondition>
 void GraphAbstractionsHIP::generate_new_frontier_worker(VectorCSRGraph &_graph, FrontierVectorCSR &_frontier, FilterCondition &&filter_cond)
 {
-    using C = typename std::decay<FilterCondition>::type;
     Timer tm;
     tm.start();
-    hip_shadows_to_device(stream);
     const int vertices_count = _graph.get_vertices_count();
-    vgl_hip_graph *gh = handle_of(_graph);
-    vgl_hip_frontier *fh = handle_of(_frontier, gh);
-    vgl_hip_gnf_buffers b;
-    VGL_HIP_BIND_CALL(vgl_hip_gnf_begin(ctx, gh, fh, 1, &b));
-    const vgl_pred_user<C> pred{filter_cond, binding_of(_graph).d_vertex_pointers};
-    hipLaunchKernelGGL((vgl_k_gnf_count<vgl_pred_user<C>>), dim3((unsigned)b.nvtiles), dim3(VGL_BLOCK), 0, stream, pred, b.nrows, b.row_begin, b.out_rowptr, b.vt_cnt, b.vt_deg,
-                       b.front_bytes, (uint8_t *)nullptr, b.flags, b.ticket, b.vt_cnt_off, b.vt_deg_off, b.counters, b.plan_offs, b.host_counters, b.seq);
-    VGL_HIP_BIND_RT(hipGetLastError());
+    const gnf_started s = gnf_start(_graph, _frontier, filter_cond);
+    vgl_hip_graph *gh = s.gh;
+    vgl_hip_frontier *fh = s.fh;
+    const vgl_hip_gnf_buffers &b = s.b;
     // the three parts' sizes from the per-tile counts the pass above leaves (stream order: after it, before the host looks), while the host waits for the totals
     hipLaunchKernelGGL(vgl_k_frontier_parts_from_tiles, dim3(1), dim3(VGL_PARTS_THREADS), 0, stream, vertices_count, (long long)b.nvtiles, (const int *)b.vt_cnt,
                        (const long long *)b.vt_deg, (const unsigned char *)b.front_bytes, (const long long *)binding_of(_graph).d_vertex_pointers,

@@ -194,6 +194,15 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_gnf_count(Pred pred, int32_t 
     }
 }
 
+// the count launch of a frontier generation with the CALLER's predicate (the operator classes, include/vgl_hip.h: vgl_hip_gnf_begin hands the
+// buffers out, vgl_hip_gnf_complete waits for the sequence number this launch publishes); hipGetLastError() is left to the caller
+template <class Pred>
+static void vgl_launch_gnf_count(hipStream_t st, const Pred &pred, const vgl_hip_gnf_buffers &b)
+{
+    hipLaunchKernelGGL((vgl_k_gnf_count<Pred>), dim3((unsigned)b.nvtiles), dim3(VGL_BLOCK), 0, st, pred, b.nrows, b.row_begin, b.out_rowptr, b.vt_cnt, b.vt_deg,
+                       b.front_bytes, (uint8_t *)nullptr, b.flags, b.ticket, b.vt_cnt_off, b.vt_deg_off, b.counters, b.plan_offs, b.host_counters, b.seq);
+}
+
 // scan pass: single workgroup of 1024 threads; exclusive offsets per tile; totals to counters[C_FRONT], counters[C_NEIGH];
 // also terminates the edge-offset array: offs[size] = neighbours.  A thread takes eight consecutive tiles per round and loads them before
 // it adds anything (one entry per loop iteration was a chain of 2 x ntiles / 1024 dependent L2 round trips: 19 us for the 8192 tiles of

@@ -1003,7 +1003,17 @@ class GraphAbstractionsHIP {
     bool sequential_rows = false;               // enable_sequential_rows()
 
     static int active_count(VGL_Graph &g, VGL_Frontier &f) { return f.get_sparsity_type() == ALL_ACTIVE_FRONTIER ? g.get_vertices_count() : f.size(); }
-    static unsigned grid_for(long long n) { long long b = (n + VGL_BLOCK - 1) / VGL_BLOCK; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
+    static constexpr int GRID_CAP = 8192;       // workgroups of a grid-stride launch
+    static unsigned grid_for(long long n) { return vgl_grid_for(n, GRID_CAP); }
+    // the frontier and one direction of the graph as the launchers of vgl_hip_kernels.hpp take them
+    static vgl_active_view active_of(VGL_Frontier &f)
+    {
+        const FrontierSparsityType t = f.get_sparsity_type();
+        return vgl_active_view{t == ALL_ACTIVE_FRONTIER ? 0 : (t == DENSE_FRONTIER ? 1 : 2), f.get_flags(), f.get_ids(), f.size()};
+    }
+    static vgl_rows_view rows_of(VGL_Graph &g, TraversalDirection dir) { const vgl_csr_view v = g.get_direction_view(dir); return vgl_rows_view{v.rowptr, v.adj, v.edges, g.get_vertices_count()}; }
+    void advance_stats(const vgl_stopwatch &watch, long long work, bool gather)
+    { performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, gather); }
     template <class T> static constexpr bool is_empty_vertex_op() { return std::is_same<typename std::decay<T>::type, vgl_empty_vertex_op>::value; }
 
     // see MemoryAPI::live_host_arrays
@@ -1019,13 +1029,7 @@ class GraphAbstractionsHIP {
     template <class Op>
     void vertex_pass(VGL_Graph &g, VGL_Frontier &f, TraversalDirection dir, Op &&op, int row_lo = 0, int row_hi = 0x7fffffff)
     {
-        const vgl_csr_view v = g.get_direction_view(dir);
-        const FrontierSparsityType t = f.get_sparsity_type();
-        hipStream_t st = VGL_RUNTIME::stream();
-        const int V = g.get_vertices_count();
-        if (t == ALL_ACTIVE_FRONTIER) hipLaunchKernelGGL((vgl_k_vertex_op<0, typename std::decay<Op>::type>), dim3(grid_for(V)), dim3(VGL_BLOCK), 0, st, V, v.rowptr, f.get_flags(), f.get_ids(), row_lo, row_hi, op);
-        else if (t == DENSE_FRONTIER) hipLaunchKernelGGL((vgl_k_vertex_op<1, typename std::decay<Op>::type>), dim3(grid_for(V)), dim3(VGL_BLOCK), 0, st, V, v.rowptr, f.get_flags(), f.get_ids(), row_lo, row_hi, op);
-        else if (f.size() > 0) hipLaunchKernelGGL((vgl_k_vertex_op<2, typename std::decay<Op>::type>), dim3(grid_for(f.size())), dim3(VGL_BLOCK), 0, st, f.size(), v.rowptr, f.get_flags(), f.get_ids(), row_lo, row_hi, op);
+        vgl_launch_vertex_op(VGL_RUNTIME::stream(), GRID_CAP, rows_of(g, dir), active_of(f), row_lo, row_hi, op);
         VGL_HIP_RT(hipGetLastError());
     }
 
@@ -1038,23 +1042,19 @@ class GraphAbstractionsHIP {
         hipStream_t st = VGL_RUNTIME::stream();
         const vgl_stopwatch watch;
         long long work = 0;                                 // edges the frontier touches (advance_worker.hpp:140-149)
-        const vgl_csr_view v = g.get_direction_view(dir);
+        const vgl_rows_view v = rows_of(g, dir);
+        const vgl_active_view a = active_of(f);
         const long long process_shift = (dir == GATHER) ? g.get_edges_count() : 0;     // compute_process_shift (graph_abstractions.hpp:19-28)
         // several ranks (inner_mpi_processing, common/advance.hpp:28-31, nec/advance_worker.hpp:239-251): this rank's vertex range only
         const std::pair<int, int> range = g.get_mpi_thresholds(dir);
         const int row_lo = range.first, row_hi = range.second;
         const FrontierSparsityType t = f.get_sparsity_type();
-        using E = typename std::decay<EdgeOp>::type;
         if (sequential_rows) {
-            using P = typename std::decay<PreOp>::type; using Q = typename std::decay<PostOp>::type;
-            const int V = g.get_vertices_count();
             work = t == ALL_ACTIVE_FRONTIER ? v.edges : f.get_neighbours_count();
-            if (t == ALL_ACTIVE_FRONTIER) hipLaunchKernelGGL((vgl_k_advance_rows<0, E, P, Q>), dim3(grid_for(V)), dim3(VGL_BLOCK), 0, st, V, v.rowptr, v.adj, f.get_flags(), f.get_ids(), process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
-            else if (t == DENSE_FRONTIER) hipLaunchKernelGGL((vgl_k_advance_rows<1, E, P, Q>), dim3(grid_for(V)), dim3(VGL_BLOCK), 0, st, V, v.rowptr, v.adj, f.get_flags(), f.get_ids(), process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
-            else if (f.size() > 0) hipLaunchKernelGGL((vgl_k_advance_rows<2, E, P, Q>), dim3(grid_for(f.size())), dim3(VGL_BLOCK), 0, st, f.size(), v.rowptr, v.adj, f.get_flags(), f.get_ids(), process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
+            vgl_launch_advance_rows(st, GRID_CAP, v, a, process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
             VGL_HIP_RT(hipGetLastError());
             if (sync_after_primitive()) VGL_RUNTIME::sync();
-            performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, dir == GATHER);
+            advance_stats(watch, work, dir == GATHER);
             return;
         }
         if (!is_empty_vertex_op<PreOp>()) vertex_pass(g, f, dir, pre_op, row_lo, row_hi);
@@ -1062,24 +1062,17 @@ class GraphAbstractionsHIP {
             const int64_t *offs; const int32_t *tile_first; int64_t M;
             VGL_HIP_CALL(vgl_hip_frontier_advance_plan(c, g.get_handle(), f.get_handle(), dir == GATHER, &offs, &tile_first, &M));
             work = M;
-            if (M > 0) {
-                const unsigned nt = (unsigned)((M + VGL_TILE - 1) / VGL_TILE);
-                hipLaunchKernelGGL((vgl_k_advance_sparse<E>), dim3(nt), dim3(VGL_ADV_THREADS), 0, st, f.get_ids(), offs, tile_first, f.size(), (long long)M,
-                                   v.rowptr, v.adj, process_shift, row_lo, row_hi, edge_op);
-            }
+            vgl_launch_advance_sparse(st, v, a, offs, tile_first, (long long)M, process_shift, row_lo, row_hi, edge_op);
         } else if (v.edges > 0) {
             work = t == ALL_ACTIVE_FRONTIER ? v.edges : f.get_neighbours_count();
             const int32_t *tile_row; int64_t ntiles;
             VGL_HIP_CALL(vgl_hip_graph_tile_rows(g.get_handle(), dir == GATHER, &tile_row, &ntiles));
-            if (t == DENSE_FRONTIER)
-                hipLaunchKernelGGL((vgl_k_advance_static<true, E>), dim3((unsigned)ntiles), dim3(VGL_BLOCK), 0, st, v.rowptr, v.adj, tile_row, v.edges, process_shift, f.get_flags(), row_lo, row_hi, edge_op);
-            else
-                hipLaunchKernelGGL((vgl_k_advance_static<false, E>), dim3((unsigned)ntiles), dim3(VGL_BLOCK), 0, st, v.rowptr, v.adj, tile_row, v.edges, process_shift, f.get_flags(), row_lo, row_hi, edge_op);
+            vgl_launch_advance_tiles(st, v, a, tile_row, (unsigned)ntiles, process_shift, row_lo, row_hi, edge_op);      // every tile of the direction
         }
         VGL_HIP_RT(hipGetLastError());
         if (!is_empty_vertex_op<PostOp>()) vertex_pass(g, f, dir, post_op, row_lo, row_hi);
         if (sync_after_primitive()) VGL_RUNTIME::sync();     // synchronous like the reference GPU backend (advance_csr.hpp:204) whenever the host could see a result
-        performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, dir == GATHER);
+        advance_stats(watch, work, dir == GATHER);
     }
 
     // the six-functor form (common/advance.hpp:6-115).  CSR_GRAPH: the reference's CSR worker never calls the collective set
@@ -1103,6 +1096,20 @@ class GraphAbstractionsHIP {
             advance_worker(g, f, dir, e2, EMPTY_VERTEX_OP, EMPTY_VERTEX_OP);
         else
             advance_worker(g, f, dir, e2, vgl_split_vertex_op<P, CP>{pre, c_pre, thr}, vgl_split_vertex_op<Q, CQ>{post, c_post, thr});
+    }
+    // what every declared-operator scatter asks for and what every prepare(declared operator) does around its build
+    void require_declared_scatter(VGL_Frontier &f) const
+    {
+        if (current_traversal_direction != SCATTER) throw "VGL ERROR: incorrect traversal direction in scatter";
+        if (f.get_sparsity_type() != ALL_ACTIVE_FRONTIER) throw "VGL ERROR: a declared operator needs an all-active frontier";
+    }
+    template <class Build>
+    static double timed_prepare(Build &&build)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        build();
+        VGL_RUNTIME::sync();
+        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
     std::vector<void *> user_data_containers;
 
@@ -1140,64 +1147,40 @@ public:
     // a declared operator over an ALL_ACTIVE frontier (see VGL_MIN_LABEL_OVER_EDGES): returns whether any label changed (host value: the call synchronises)
     bool scatter(VGL_Graph &g, VGL_Frontier &f, vgl_declared_relax op)
     {
-        if (current_traversal_direction != SCATTER) throw "VGL ERROR: incorrect traversal direction in scatter";
-        if (f.get_sparsity_type() != ALL_ACTIVE_FRONTIER) throw "VGL ERROR: a declared operator needs an all-active frontier";
+        require_declared_scatter(f);
         vgl_hip_ctx *c = VGL_RUNTIME::ctx();
         vgl_hip_sssp_pull_plan *plan = g.get_relax_plan(op.weights, op.weights_version);       // (kept by the graph: the next call with the same weights pays nothing)
         const vgl_stopwatch watch;
         int changed = 0;
         VGL_HIP_CALL(vgl_hip_sssp_pull_pass(c, g.get_handle(), plan, op.distances, &changed));
-        const long long work = g.get_direction_view(SCATTER).edges;
-        performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, false);
+        advance_stats(watch, g.get_direction_view(SCATTER).edges, false);
         return changed != 0;
     }
     template <class PreOp, class PostOp>
     void scatter(VGL_Graph &g, VGL_Frontier &f, vgl_declared_sum op, PreOp &&pre_op, PostOp &&post_op)
     {
-        if (current_traversal_direction != SCATTER) throw "VGL ERROR: incorrect traversal direction in scatter";
-        if (f.get_sparsity_type() != ALL_ACTIVE_FRONTIER) throw "VGL ERROR: a declared operator needs an all-active frontier";
+        require_declared_scatter(f);
         const vgl_stopwatch watch;
         if (!is_empty_vertex_op<PreOp>()) vertex_pass(g, f, SCATTER, pre_op);
         VGL_HIP_CALL(vgl_hip_sum_over_edges_f32(VGL_RUNTIME::ctx(), g.get_handle(), op.values, op.bound, op.sums));
         if (!is_empty_vertex_op<PostOp>()) vertex_pass(g, f, SCATTER, post_op);
         if (sync_after_primitive()) VGL_RUNTIME::sync();
-        const long long work = g.get_direction_view(SCATTER).edges;
-        performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, false);
+        advance_stats(watch, g.get_direction_view(SCATTER).edges, false);
     }
     void scatter(VGL_Graph &g, VGL_Frontier &f, vgl_declared_sum op) { scatter(g, f, op, EMPTY_VERTEX_OP, EMPTY_VERTEX_OP); }
     // prepare(declared operator): builds NOW the blocked layout the operator's first scatter would otherwise build inside the caller's timer (the
     // counterpart of what the reference keeps out of its timers: import, move_to_device; the library's own legs report their plans apart too).
     // Idempotent; returns the seconds it took.
-    double prepare(VGL_Graph &g, vgl_declared_sum)
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        VGL_HIP_CALL(vgl_hip_pr_prepare(VGL_RUNTIME::ctx(), g.get_handle(), VGL_HIP_PR_BLOCKED, nullptr));
-        VGL_RUNTIME::sync();
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    double prepare(VGL_Graph &g, vgl_declared_min_label)
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        VGL_HIP_CALL(vgl_hip_cc_prepare(VGL_RUNTIME::ctx(), g.get_handle()));
-        VGL_RUNTIME::sync();
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    double prepare(VGL_Graph &g, vgl_declared_relax op)
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        g.get_relax_plan(op.weights, op.weights_version);
-        VGL_RUNTIME::sync();
-        return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
+    double prepare(VGL_Graph &g, vgl_declared_sum) { return timed_prepare([&] { VGL_HIP_CALL(vgl_hip_pr_prepare(VGL_RUNTIME::ctx(), g.get_handle(), VGL_HIP_PR_BLOCKED, nullptr)); }); }
+    double prepare(VGL_Graph &g, vgl_declared_min_label) { return timed_prepare([&] { VGL_HIP_CALL(vgl_hip_cc_prepare(VGL_RUNTIME::ctx(), g.get_handle())); }); }
+    double prepare(VGL_Graph &g, vgl_declared_relax op) { return timed_prepare([&] { g.get_relax_plan(op.weights, op.weights_version); }); }
     bool scatter(VGL_Graph &g, VGL_Frontier &f, vgl_declared_min_label op)
     {
-        if (current_traversal_direction != SCATTER) throw "VGL ERROR: incorrect traversal direction in scatter";
-        if (f.get_sparsity_type() != ALL_ACTIVE_FRONTIER) throw "VGL ERROR: a declared operator needs an all-active frontier";
+        require_declared_scatter(f);
         const vgl_stopwatch watch;
         int changed = 0;
         VGL_HIP_CALL(vgl_hip_cc_hook_owned(VGL_RUNTIME::ctx(), g.get_handle(), op.labels, &changed));
-        const long long work = g.get_direction_view(SCATTER).edges;
-        performance_stats.update_advance_stats(watch.seconds(), (size_t)(work * INT_ELEMENTS_PER_EDGE * sizeof(int)), (size_t)work, false);
+        advance_stats(watch, g.get_direction_view(SCATTER).edges, false);
         return changed != 0;
     }
     template <typename EdgeOperation, typename VertexPreprocessOperation, typename VertexPostprocessOperation,
@@ -1229,32 +1212,12 @@ public:
     {
         if (type != REDUCE_SUM && type != REDUCE_MAX) throw "Error in GraphAbstractionsHIP::reduce : unsupported reduce type";   // reduce.hpp:144-150
         const vgl_stopwatch watch;
-        const vgl_csr_view v = g.get_direction_view(current_traversal_direction);
-        const FrontierSparsityType t = f.get_sparsity_type();
-        hipStream_t st = VGL_RUNTIME::stream();
-        using R = typename std::decay<ReduceOperation>::type;
+        const vgl_active_view a = active_of(f);
         const int V = g.get_vertices_count();
-        const int n = t == SPARSE_FRONTIER ? f.size() : V;
+        const int n = a.mode == 2 ? a.size : V;
         if (n <= 0) return (_T)0;
-        const int nb = (int)std::min<long long>(1024, ((long long)n + VGL_BLOCK - 1) / VGL_BLOCK);
-        const bool mx = type == REDUCE_MAX;
-#define VGL_REDUCE_LAUNCH(MODE)                                                                                                                          \
-        do {                                                                                                                                             \
-            if (mx) hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, true, R>), dim3(nb), dim3(VGL_BLOCK), 0, st, n, v.rowptr, f.get_flags(), f.get_ids(), reduce_op, reduce_partials); \
-            else hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, false, R>), dim3(nb), dim3(VGL_BLOCK), 0, st, n, v.rowptr, f.get_flags(), f.get_ids(), reduce_op, reduce_partials); \
-        } while (0)
-        if (t == ALL_ACTIVE_FRONTIER) VGL_REDUCE_LAUNCH(0);
-        else if (t == DENSE_FRONTIER) VGL_REDUCE_LAUNCH(1);
-        else VGL_REDUCE_LAUNCH(2);
-#undef VGL_REDUCE_LAUNCH
-        VGL_HIP_RT(hipGetLastError());
         double r = 0.0;
-        if (mx) {
-            hipLaunchKernelGGL(vgl_k_max_fold, dim3(1), dim3(VGL_BLOCK), 0, st, nb, (const double *)reduce_partials, reduce_partials + 1024);
-            VGL_HIP_RT(hipGetLastError());
-            VGL_HIP_CALL(vgl_hip_memcpy_d2h(VGL_RUNTIME::ctx(), &r, reduce_partials + 1024, sizeof(double)));
-        } else
-            VGL_HIP_CALL(vgl_hip_reduce_sum_f64_buffer(VGL_RUNTIME::ctx(), nb, reduce_partials, &r));      // fixed-order fold of the partials
+        VGL_HIP_CALL(vgl_reduce(VGL_RUNTIME::ctx(), VGL_RUNTIME::stream(), rows_of(g, current_traversal_direction).rowptr, a, V, reduce_op, type == REDUCE_MAX, reduce_partials, &r));
         performance_stats.update_reduce_stats(watch.seconds(), (size_t)n);
         return (_T)r;
     }
@@ -1278,9 +1241,7 @@ public:
         vgl_hip_gnf_buffers b;
         VGL_HIP_CALL(vgl_hip_gnf_begin(c, g.get_handle(), f.get_handle(), plan ? 1 : 0, &b));
         const vgl_pred_user<C> pred{filter_cond, v.rowptr};
-        hipLaunchKernelGGL((vgl_k_gnf_count<vgl_pred_user<C>>), dim3((unsigned)b.nvtiles), dim3(VGL_BLOCK), 0, VGL_RUNTIME::stream(), pred, b.nrows, b.row_begin,
-                           b.out_rowptr, b.vt_cnt, b.vt_deg, b.front_bytes, (uint8_t *)nullptr, b.flags, b.ticket, b.vt_cnt_off, b.vt_deg_off, b.counters,
-                           b.plan_offs, b.host_counters, b.seq);
+        vgl_launch_gnf_count(VGL_RUNTIME::stream(), pred, b);
         VGL_HIP_RT(hipGetLastError());
         VGL_HIP_CALL(vgl_hip_gnf_complete(c, g.get_handle(), f.get_handle(), dense_threshold, plan ? 1 : 0, b.seq));
         performance_stats.update_gnf_stats(watch.seconds(), (size_t)V);

@@ -1,11 +1,18 @@
 // vgl_hip_kernels.hpp -- the templated HIP kernels of the operator API that call USER operators (device lambdas): advance over static edge
 // tiles / over a sparse frontier's edge space / over sequential rows, per-vertex operators, reductions, the frontier predicate adaptor, the
-// merge kernels of exchange_vertices_array, the degree-class splitters of the six-functor advance.  They depend on plain pointers only --
-// not on any graph / frontier / array class -- so the same file serves this repository's own minimal classes (vgl_hip.hpp) and the
-// backend class bound to the REFERENCE's containers (integration/vgl_compute_api/hip/graph_abstractions_hip.h: CSRGraph,
+// merge kernels of exchange_vertices_array, the degree-class splitters of the six-functor advance -- and, at the end of the file, the host-side
+// LAUNCHERS of those kernels (vgl_launch_vertex_op, vgl_launch_advance_rows / _tiles / _sparse, vgl_reduce; vgl_launch_gnf_count sits beside its
+// kernel in csrc/vgl_gnf.h): each ALL_ACTIVE / DENSE / SPARSE ladder and each argument list is written there once.  Kernels and launchers depend
+// on plain pointers only -- not on any graph / frontier / array class -- so the same file serves this repository's own minimal classes
+// (vgl_hip.hpp) and the backend class bound to the REFERENCE's containers (integration/vgl_compute_api/hip/graph_abstractions_hip.h: CSRGraph,
 // VectorCSRGraph, FrontierCSR, FrontierVectorCSR through friend access, vgl_compute_api/template/graph_abstractions_template.h:5-107).
+// What the launchers deliberately do NOT own, because the two classes differ there: when the host synchronises (sync_after_primitive() /
+// finish()), the upload of shadowed user arrays, timers and performance_stats, the grid cap and the number of static tiles (arguments), and the
+// error convention -- they never throw; the ones that only launch leave hipGetLastError() to the caller, vgl_reduce returns a C ABI status
+// for the caller's own macro (VGL_HIP_CALL / VGL_HIP_BIND_CALL).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <type_traits>
 #include "../../include/vgl_hip.h"
@@ -328,3 +335,79 @@ struct vgl_split_vertex_op {
     }
 };
 
+// ------------------------------------------------------------------------------------------------------------------
+// host-side launchers: what both operator classes call instead of hipLaunchKernelGGL (see the head of the file for what they leave to the caller)
+// ------------------------------------------------------------------------------------------------------------------
+struct vgl_rows_view { const long long *rowptr; const int *adj; long long edges; int vertices; };     // one direction of a graph as the kernels read it
+struct vgl_active_view { int mode; const int *flags; const int *ids; int size; };                      // mode = the kernels' MODE: 0 all-active, 1 dense (flags), 2 sparse (ids, size)
+inline unsigned vgl_grid_for(long long n, int cap) { const long long b = (n + VGL_BLOCK - 1) / VGL_BLOCK; return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b)); }
+
+// per-vertex operator over the active vertices with ids in [row_lo, row_hi); a SPARSE frontier of size 0 launches nothing
+template <class Op>
+void vgl_launch_vertex_op(hipStream_t st, int grid_cap, const vgl_rows_view &r, const vgl_active_view &a, int row_lo, int row_hi, Op &&op)
+{
+    using O = typename std::decay<Op>::type;
+    if (a.mode == 2 && a.size <= 0) return;
+    const int n = a.mode == 2 ? a.size : r.vertices;
+    const dim3 grid(vgl_grid_for(n, grid_cap)), block(VGL_BLOCK);
+    if (a.mode == 0) hipLaunchKernelGGL((vgl_k_vertex_op<0, O>), grid, block, 0, st, n, r.rowptr, a.flags, a.ids, row_lo, row_hi, op);
+    else if (a.mode == 1) hipLaunchKernelGGL((vgl_k_vertex_op<1, O>), grid, block, 0, st, n, r.rowptr, a.flags, a.ids, row_lo, row_hi, op);
+    else hipLaunchKernelGGL((vgl_k_vertex_op<2, O>), grid, block, 0, st, n, r.rowptr, a.flags, a.ids, row_lo, row_hi, op);
+}
+// pre -> the vertex's edges in adjacency order -> post, one lane per active vertex (vgl_k_advance_rows)
+template <class EdgeOp, class PreOp, class PostOp>
+void vgl_launch_advance_rows(hipStream_t st, int grid_cap, const vgl_rows_view &r, const vgl_active_view &a, long long process_shift, int row_lo, int row_hi,
+                             EdgeOp &&edge_op, PreOp &&pre_op, PostOp &&post_op)
+{
+    using E = typename std::decay<EdgeOp>::type; using P = typename std::decay<PreOp>::type; using Q = typename std::decay<PostOp>::type;
+    if (a.mode == 2 && a.size <= 0) return;
+    const int n = a.mode == 2 ? a.size : r.vertices;
+    const dim3 grid(vgl_grid_for(n, grid_cap)), block(VGL_BLOCK);
+    if (a.mode == 0) hipLaunchKernelGGL((vgl_k_advance_rows<0, E, P, Q>), grid, block, 0, st, n, r.rowptr, r.adj, a.flags, a.ids, process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
+    else if (a.mode == 1) hipLaunchKernelGGL((vgl_k_advance_rows<1, E, P, Q>), grid, block, 0, st, n, r.rowptr, r.adj, a.flags, a.ids, process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
+    else hipLaunchKernelGGL((vgl_k_advance_rows<2, E, P, Q>), grid, block, 0, st, n, r.rowptr, r.adj, a.flags, a.ids, process_shift, row_lo, row_hi, edge_op, pre_op, post_op);
+}
+// the first `tiles` static edge tiles of the direction (tile_row: vgl_hip_graph_tile_rows), ALL_ACTIVE or DENSE frontier
+template <class EdgeOp>
+void vgl_launch_advance_tiles(hipStream_t st, const vgl_rows_view &r, const vgl_active_view &a, const int32_t *tile_row, unsigned tiles, long long process_shift,
+                              int row_lo, int row_hi, EdgeOp &&edge_op)
+{
+    using E = typename std::decay<EdgeOp>::type;
+    if (tiles == 0) return;
+    if (a.mode == 1) hipLaunchKernelGGL((vgl_k_advance_static<true, E>), dim3(tiles), dim3(VGL_BLOCK), 0, st, r.rowptr, r.adj, tile_row, r.edges, process_shift, a.flags, row_lo, row_hi, edge_op);
+    else hipLaunchKernelGGL((vgl_k_advance_static<false, E>), dim3(tiles), dim3(VGL_BLOCK), 0, st, r.rowptr, r.adj, tile_row, r.edges, process_shift, a.flags, row_lo, row_hi, edge_op);
+}
+// the M edges of a SPARSE frontier's own edge space (offs, tile_first: vgl_hip_frontier_advance_plan); M == 0 launches nothing
+template <class EdgeOp>
+void vgl_launch_advance_sparse(hipStream_t st, const vgl_rows_view &r, const vgl_active_view &a, const int64_t *offs, const int32_t *tile_first, long long M,
+                               long long process_shift, int row_lo, int row_hi, EdgeOp &&edge_op)
+{
+    if (M <= 0) return;
+    hipLaunchKernelGGL((vgl_k_advance_sparse<typename std::decay<EdgeOp>::type>), dim3((unsigned)((M + VGL_TILE - 1) / VGL_TILE)), dim3(VGL_ADV_THREADS), 0, st, a.ids, offs,
+                       tile_first, a.size, M, r.rowptr, r.adj, process_shift, row_lo, row_hi, edge_op);
+}
+// reduce: per-workgroup partials of op over the active vertices (partials: 1024 doubles + 8), then their maximum folded on the device or their
+// fixed-order sum by the library; *result on the host (the call synchronises).  Returns a C ABI status (vgl_hip_last_error() has the text).
+template <int MODE, class Op>
+void vgl_launch_reduce_partials(hipStream_t st, int nb, int n, const long long *rowptr, const vgl_active_view &a, const Op &op, bool is_max, double *partials)
+{
+    if (is_max) hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, true, Op>), dim3(nb), dim3(VGL_BLOCK), 0, st, n, rowptr, a.flags, a.ids, op, partials);
+    else hipLaunchKernelGGL((vgl_k_reduce_partials<MODE, false, Op>), dim3(nb), dim3(VGL_BLOCK), 0, st, n, rowptr, a.flags, a.ids, op, partials);
+}
+template <class Op>
+int vgl_reduce(vgl_hip_ctx *ctx, hipStream_t st, const long long *rowptr, const vgl_active_view &a, int vertices, Op &&op, bool is_max, double *partials, double *result)
+{
+    using R = typename std::decay<Op>::type;
+    *result = 0.0;
+    const int n = a.mode == 2 ? a.size : vertices;
+    if (n <= 0) return 0;
+    const int nb = (int)std::min<long long>(1024, ((long long)n + VGL_BLOCK - 1) / VGL_BLOCK);
+    if (a.mode == 0) vgl_launch_reduce_partials<0, R>(st, nb, n, rowptr, a, op, is_max, partials);
+    else if (a.mode == 1) vgl_launch_reduce_partials<1, R>(st, nb, n, rowptr, a, op, is_max, partials);
+    else vgl_launch_reduce_partials<2, R>(st, nb, n, rowptr, a, op, is_max, partials);
+    VGL_HIP_TRY(hipGetLastError());
+    if (!is_max) return vgl_hip_reduce_sum_f64_buffer(ctx, nb, partials, result);      // fixed-order fold of the partials
+    hipLaunchKernelGGL(vgl_k_max_fold, dim3(1), dim3(VGL_BLOCK), 0, st, nb, (const double *)partials, partials + 1024);
+    VGL_HIP_TRY(hipGetLastError());
+    return vgl_hip_memcpy_d2h(ctx, result, partials + 1024, sizeof(double));
+}
