@@ -394,6 +394,50 @@ typedef struct {
 int vgl_hip_tri_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
 int vgl_hip_tri_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *triangles, int64_t *d_per_vertex, int32_t *d_degree, vgl_hip_tri_stats *stats);
 
+/* Betweenness centrality (`bc`, Brandes' algorithm).  The reference has none, so this comment is the contract:
+ *   graph     the stored DIRECTED, unweighted graph of a handle that owns all rows.  Every stored entry is an edge of its own: multi-edges count with
+ *             their multiplicity in the path counts (as in label propagation's contract); a self-loop is never on a shortest path and has no effect.
+ *   per source s (levels exactly as vgl_hip_bfs_run writes them: source 1, unreached -1; below d(s, v) = levels[v] - 1 counts edges):
+ *             sigma_s[s] = 1, sigma_s[v] = sum over the stored entries (u, v) with d(s, u) = d(s, v) - 1 of sigma_s[u]; unreached: sigma = 0;
+ *             delta_s[v] = sum over the stored entries (v, w) with d(s, w) = d(s, v) + 1 of sigma_s[v] / sigma_s[w] * (1 + delta_s[w]),
+ *             evaluated as sigma_s[v] * (sum of coef[w]), coef[w] = (1 + delta_s[w]) / sigma_s[w]; unreached: delta = 0.
+ *   result    d_bc[v] = sum over the sources s != v of delta_s[v]: float64, in the graph's own numbering, directed, unnormalised, endpoints not
+ *             counted.  accumulate = 0 overwrites d_bc, 1 adds to what it holds.  On a symmetric graph every unordered pair is counted twice; halving,
+ *             the V / k rescaling of a source sample and any normalisation are the callers' business, in float64.
+ *   types     sigma, delta, bc are float64; there is no float32 on this path.  sigma is exact while below 2^53 and rounded above;
+ *             stats->sigma_inexact counts the sources whose largest sigma reached 2^53.
+ *   directions the forward sweep (sigma) reads the incoming CSR, the backward sweep (delta) the outgoing one.  symmetric = 1: the caller vouches that
+ *             the stored graph is symmetric, and the outgoing CSR serves both (the rule of vgl_hip_lp_run).
+ *   determinism no floating-point atomics: both sweeps are pulls, every value has one writer per source and a summation shape fixed by the row's
+ *             length and the VGL_BC_* switches.  Two runs of the same call on the same handle under the same switches give bit-identical d_bc.
+ *   sources   host array of `count` vertex ids in the graph's numbering, run one after the other (a repeated source counts again).
+ *   d_levels, d_sigma, d_delta (device, V each, optional): the LAST source's arrays.
+ * Method: per source the levels come from the traversal of vgl_hip_bfs_run; the reached vertices are bucketed by (level, row class) once, so that the two
+ * sweeps cost O(reached vertices + their entries) and not O(depth * V); rows are split by length into classes (VGL_BC_SHORT 32: 8 lanes per row,
+ * VGL_BC_WAVE 1024: a wavefront, VGL_BC_WG 32768: a workgroup, longer: one workgroup per VGL_BC_CHUNK 16384 entries and a fold in chunk order).
+ * The classes of both directions are built by vgl_hip_bc_prepare or the first run, cached on the graph handle and freed with it.
+ * stats: sources = traversals run; max_depth = largest d(s, v); levels_total = sum over the sources of (deepest d + 1), the frontiers a traversal
+ * expands; reached_total = vertices reached, source included; edges_forward = entries of the forward CSR in the rows of the reached non-source
+ * vertices, edges_backward = outgoing entries of the reached vertices that are not on the last level: exactly the rows the sweeps are launched over;
+ * algorithmic_bytes = per source the traversal's own model + (10 V + 4 reached) per order (one order per direction: levels and class read twice,
+ * the order written) + 28 (reached - 1) + 52 reached for the per-row reads and writes of the two sweeps + 8 per entry walked (adjacency and
+ * the endpoint's level; the 8-byte gathers of matching entries are left out: a lower bound).
+ * Fails, before d_bc is written: a sharded handle, no incoming CSR without symmetric = 1, a source outside [0, V), count < 0, d_bc == NULL. */
+typedef struct {
+    int32_t sources;            /* traversals run */
+    int32_t max_depth;          /* largest d(s, v) over all sources */
+    int32_t sigma_inexact;      /* sources whose largest sigma reached 2^53 */
+    int32_t prepared_now;       /* this call built row classes */
+    int64_t levels_total;       /* sum over sources of frontiers expanded */
+    int64_t reached_total;      /* sum over sources of vertices reached, source included */
+    int64_t edges_forward;      /* forward-CSR entries of reached non-source vertices, summed over sources: exact */
+    int64_t edges_backward;     /* outgoing entries of reached vertices that are not on the last level, summed: exact */
+    int64_t algorithmic_bytes;
+} vgl_hip_bc_stats;
+int vgl_hip_bc_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int symmetric);
+int vgl_hip_bc_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int symmetric, int accumulate, double *d_bc,
+                   int32_t *d_levels, double *d_sigma, double *d_delta, vgl_hip_bc_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -221,6 +221,10 @@ class Graph:
         """the oriented CSR and row classes of triangle_count() now, outside any timing (vgl_hip_tri_prepare)"""
         _l.check(self.ctx.L.vgl_hip_tri_prepare(self.ctx.h, self.h))
 
+    def prepare_betweenness(self, symmetric=False):
+        """the row classes of betweenness_centrality() now, outside any timing (vgl_hip_bc_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_bc_prepare(self.ctx.h, self.h, int(bool(symmetric))))
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -495,6 +499,52 @@ def triangle_count(graph, per_vertex=False, clustering=False, raw=False):
         stats["degree"] = deg
         stats["clustering"] = torch.where(deg >= 2, 2.0 * stats["per_vertex"].to(torch.float64) / torch.clamp(pairs, min=1.0), torch.zeros_like(d))
     return int(tri.value), stats
+
+
+def betweenness_centrality(graph, sources=None, symmetric=False, rescale=False, halve=False, raw=False, want_last=False, bc=None):
+    """betweenness centrality of the stored directed graph (the contract of vgl_hip_bc_run in include/vgl_hip.h): bc[v] = sum over the sources
+    s != v of Brandes' dependency delta_s[v]; float64, unnormalised, endpoints not counted, multi-edges with their multiplicity.
+    sources: None = every vertex (exact), else a sequence / tensor of ORIGINAL vertex ids (raw=True: the graph's own ids).  symmetric=True: the caller
+    vouches that every edge is stored both ways (no incoming CSR needed).  rescale multiplies by V / len(sources), halve by 1/2 (an undirected graph
+    stored both ways counts every pair twice).  bc: a float64 tensor in the graph's OWN numbering to accumulate into (implies raw; no rescale / halve).
+    want_last adds the last source's "levels", "sigma", "delta".  Returns (bc in ORIGINAL order unless raw=True, stats dict)."""
+    ctx = graph.ctx
+    V = graph.V
+    if sources is None:
+        ids = list(range(V))
+    else:
+        ids = [int(s) for s in (sources.tolist() if torch.is_tensor(sources) else sources)]
+    if not raw and bc is None and graph.fwd is not None and ids:
+        if min(ids) < 0 or max(ids) >= V:
+            raise _l.VglHipError("betweenness_centrality: source vertex out of range")
+        fwd = graph.fwd.cpu()
+        ids = [int(fwd[s]) for s in ids]
+    n = len(ids)
+    src = (C.c_int32 * max(n, 1))(*ids)
+    accumulate = bc is not None
+    if accumulate and (rescale or halve):
+        raise _l.VglHipError("betweenness_centrality: rescale / halve do not apply to an accumulating call")
+    out = bc if accumulate else ctx.empty(V, torch.float64)
+    levels = ctx.empty(V, torch.int32) if want_last else None
+    sigma = ctx.empty(V, torch.float64) if want_last else None
+    delta = ctx.empty(V, torch.float64) if want_last else None
+    st = _l.BcStats()
+    _l.check(ctx.L.vgl_hip_bc_run(ctx.h, graph.h, src, n, int(bool(symmetric)), int(accumulate), _ptr(out), _ptr(levels), _ptr(sigma), _ptr(delta),
+                                  C.byref(st)))
+    stats = _stats(st)
+    to_orig = not (raw or accumulate or graph.fwd is None)
+    idx = graph.fwd.long() if to_orig else None                     # 8-byte values: a torch index over the mapping to_original applies
+    if want_last:
+        stats["levels"] = levels[idx] if to_orig else levels
+        stats["sigma"] = sigma[idx] if to_orig else sigma
+        stats["delta"] = delta[idx] if to_orig else delta
+    if accumulate:
+        return out, stats
+    if rescale and n:
+        out = out * (float(V) / float(n))
+    if halve:
+        out = out * 0.5
+    return (out[idx] if to_orig else out), stats
 
 
 def count_not_equal(ctx, a, b):
