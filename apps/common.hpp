@@ -12,7 +12,7 @@
 #include <queue>
 
 struct Parser {
-    int scale = 10, avg_degree = 5, rounds = 1, source = -1, sink = -1, walk_vertices_percent = 1, sources = 16;
+    int scale = 10, avg_degree = 5, rounds = 1, source = -1, sink = -1, walk_vertices_percent = 1, sources = 16, k_limit = 0;
     bool rmat = true, check = false, direction_optimising = false, fused = false, undirected = false, bfs_based = false, blocked = false, deterministic = false, declared = false;
     enum Traversal { PUSH_TRAVERSAL, PULL_TRAVERSAL } traversal = PUSH_TRAVERSAL;                   // cmd_parser.hpp (-push / -pull)
     enum FrontierKind { ALL_ACTIVE_KIND, PARTIAL_ACTIVE_KIND } frontier_kind = ALL_ACTIVE_KIND;     // (-all-active / -partial-active)
@@ -35,6 +35,7 @@ struct Parser {
             else if (a == "-source") source = atoi(next());
             else if (a == "-sink") sink = atoi(next());
             else if (a == "-sources") sources = atoi(next());               // bc: how many sources (the first vertices with outgoing edges)
+            else if (a == "-klimit") k_limit = atoi(next());                // kcore: stop the peel at this k (0: the whole decomposition)
             else if (a == "-undirected") undirected = true;
             else if (a == "-import") { graph_file_name = next(); compute_mode = IMPORT_EDGES_CONTAINER; }     // .el_container
             else if (a == "-load" || a == "-file" || a == "-f") { graph_file_name = next(); compute_mode = LOAD_GRAPH_FROM_FILE; }   // .csr / .vcsr graph file

@@ -438,6 +438,45 @@ int vgl_hip_bc_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int symmetric);
 int vgl_hip_bc_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int symmetric, int accumulate, double *d_bc,
                    int32_t *d_levels, double *d_sigma, double *d_delta, vgl_hip_bc_stats *stats);
 
+/* k-core decomposition (`kcore`): core numbers and the degeneracy.  The reference has none, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *             Self-loops are ignored; multi-edges and an edge stored both ways count once.
+ *   result    d_core[v] (int32, device, V entries, required), in the graph's own numbering: the largest k such that v lies in a subgraph in which
+ *             every vertex has degree >= k.  An isolated vertex gets 0.
+ *   k_limit   > 0: the peel stops once k reaches it and every remaining vertex gets k_limit, so that d_core = min(core, k_limit) -- one k-core
+ *             ({v : d_core[v] >= k}) without paying for the denser tail.  0: the whole decomposition.  Negative: an error.
+ *   d_degree  (int32, device, V entries, optional): the degree in that simple graph (the meaning of vgl_hip_tri_run's d_degree).
+ *   The answer does not depend on the vertex order used internally, on the VGL_KCORE_* switches, on the order of the entries in a row or on the
+ *   order in which the atomics land: core numbers are integers and unique.
+ * Method: the symmetric simple CSR (row offsets int64, adjacency int32, degrees int32) is built once by vgl_hip_kcore_prepare (or by the first run) from
+ * the sorted, deduplicated 64-bit keys u << 32 | v and v << 32 | u of the stored entries -- in pieces of consecutive rows when the keys would need more
+ * scratch than VGL_KCORE_SORT_CAP_MB -- cached on the handle and freed with it.  The peel is level-synchronous on a working copy of the degrees: for
+ * the current k the vertices with degree <= k form the first frontier; an expanded vertex gets core = k and, for every neighbour u whose degree is
+ * still above k, old = atomicSub(&deg[u], 1): the one thread that sees old == k + 1 appends u to the next frontier, a thread that sees old <= k puts its
+ * decrement back.  When the frontier is empty k becomes the smallest remaining degree (a device reduction: no walk through empty shells).  Frontier
+ * rows are split by length (VGL_KCORE_SHORT 32: 8 lanes per row, VGL_KCORE_WAVE 1024: a wavefront, longer: one workgroup per VGL_KCORE_CHUNK 16384
+ * entries); frontiers of at most 2048 vertices and VGL_KCORE_SMALL (8192; 0 = off) entries run several per launch in ONE workgroup.
+ * stats, all exact and the same on every run (sub_rounds depends on the VGL_KCORE_SMALL switch only through how the work is batched, not in value):
+ * degeneracy = the largest value written to d_core; rounds = values of k the peel visited (a full run: the number of distinct core values);
+ * sub_rounds = frontiers expanded; undirected_edges = E'; edges_examined = adjacency entries walked (<= 2 E': every vertex is expanded at most
+ * once); max_degree = the longest row of the symmetric CSR; prepared_now = this call built the symmetric CSR;
+ * algorithmic_bytes = 20 V (row offsets read once, degrees copied, core written) + 8 per entry walked (the adjacency entry and the neighbour's
+ * degree); the per-k scans of the degree array and the atomics' write traffic are left out: a lower bound.
+ * Fails, before d_core is written: a sharded handle, d_core == NULL, k_limit < 0. */
+typedef struct {
+    int32_t degeneracy;         /* largest value written to d_core */
+    int32_t rounds;             /* values of k visited */
+    int32_t max_degree;         /* longest row of the symmetric CSR */
+    int32_t prepared_now;       /* this call built the symmetric CSR */
+    int64_t sub_rounds;         /* frontiers expanded */
+    int64_t undirected_edges;   /* E' */
+    int64_t edges_examined;     /* adjacency entries walked */
+    int64_t algorithmic_bytes;
+} vgl_hip_kcore_stats;
+int vgl_hip_kcore_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
+int vgl_hip_kcore_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int32_t *d_core, int32_t *d_degree, vgl_hip_kcore_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -225,6 +225,10 @@ class Graph:
         """the row classes of betweenness_centrality() now, outside any timing (vgl_hip_bc_prepare)"""
         _l.check(self.ctx.L.vgl_hip_bc_prepare(self.ctx.h, self.h, int(bool(symmetric))))
 
+    def prepare_kcore(self):
+        """the symmetric simple CSR of core_numbers() / k_core() now, outside any timing (vgl_hip_kcore_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_kcore_prepare(self.ctx.h, self.h))
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -545,6 +549,31 @@ def betweenness_centrality(graph, sources=None, symmetric=False, rescale=False, 
     if halve:
         out = out * 0.5
     return (out[idx] if to_orig else out), stats
+
+
+def core_numbers(graph, k_limit=0, degree=False, raw=False):
+    """k-core decomposition of the simple undirected graph underlying the stored outgoing CSR (the contract of vgl_hip_kcore_run in
+    include/vgl_hip.h).  Returns (degeneracy, stats dict); stats["core"] is an int32 tensor: the core number of every vertex, or
+    min(core, k_limit) when k_limit > 0 (the peel stops there).  degree=True adds stats["degree"] (int32, undirected simple degree).  Both in
+    ORIGINAL vertex order unless raw=True."""
+    ctx = graph.ctx
+    core = ctx.empty(graph.V, torch.int32)
+    deg = ctx.empty(graph.V, torch.int32) if degree else None
+    st = _l.KcoreStats()
+    _l.check(ctx.L.vgl_hip_kcore_run(ctx.h, graph.h, int(k_limit), _ptr(core), _ptr(deg), C.byref(st)))
+    stats = _stats(st)
+    stats["core"] = core if raw else graph.to_original(core)
+    if degree:
+        stats["degree"] = deg if raw else graph.to_original(deg)
+    return int(st.degeneracy), stats
+
+
+def k_core(graph, k, raw=False):
+    """membership of the k-core: a bool tensor, True where core >= k; the peel stops at k (core_numbers with k_limit=k).  k >= 1."""
+    if int(k) < 1:
+        raise _l.VglHipError("k_core: k must be at least 1 (every vertex is in the 0-core)")
+    _, stats = core_numbers(graph, k_limit=int(k), raw=raw)
+    return stats["core"] >= int(k)
 
 
 def count_not_equal(ctx, a, b):

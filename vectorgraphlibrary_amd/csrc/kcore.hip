@@ -1,0 +1,740 @@
+// kcore.hip -- k-core decomposition (core numbers, degeneracy, undirected degrees) of the simple undirected graph underlying the stored outgoing CSR.
+// The contract is written out in include/vgl_hip.h; DESIGN section 15 has the schedule, the kernel resources and the bytes model.
+//
+// Prepare (once per graph, cached on the handle): every stored entry (u, v), u != v, gives the 64-bit keys  u << 32 | v  and  v << 32 | u;  the keys are
+// sorted (rocprim radix sort) and deduplicated (rocprim unique), in pieces of consecutive rows when all of them would need more scratch than
+// VGL_KCORE_SORT_CAP_MB.  The sorted keys ARE the symmetric CSR: row = high half, entry = low half.  degree = row length.
+//
+// Peel (level-synchronous; deg = a working copy of the degrees; a vertex is alive while deg > the last finished k):
+//   k change   k = min over the alive vertices of deg (a device reduction: never a walk through empty shells); the alive vertices with deg <= k are
+//              the first frontier of k.
+//   sub-round  an expanded vertex v gets core[v] = k; for every entry u of its row with deg[u] > k:  old = atomicSub(&deg[u], 1);  old == k + 1: this
+//              thread appends u to the next frontier (deg[u] crosses k + 1 -> k once and never comes back: below);  old <= k: the decrement is put back.
+// A vertex enters a frontier exactly once, so the frontiers are consecutive segments [head, tail) of one list per row class and nothing is ever
+// cleared or swapped.  Appends are aggregated: one returning atomic per wave and class (ballot + popcount).  Rows are split by length: short
+// (<= VGL_KCORE_SHORT: 8 lanes per row), wave (<= VGL_KCORE_WAVE: one wavefront), workgroup (longer: one workgroup per VGL_KCORE_CHUNK entries).
+// Small frontiers (<= 2048 vertices, <= VGL_KCORE_SMALL entries) run in vgl_k_kcore_small: ONE workgroup that loops over sub-rounds -- and over k
+// changes while the vertices to scan are few (the whole graph, or the compacted list of the alive ones) -- until the work grows past the bound
+// or the graph is exhausted, and reports through the pinned mirror what it did.  No cooperative launch, no workgroup waits for another.
+// The host reads the pinned mirror once per sub-round of the large path (list tails, entry total, k); no allocation inside the loop.
+#include "vgl_hip_internal.h"
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <climits>
+#include <vector>
+
+namespace {
+
+constexpr int KC_NCLS = 3;
+enum { KC_SHORT = 0, KC_WAVE = 1, KC_WG = 2 };
+constexpr int KC_G = 8;                         // lanes per short row
+constexpr int KC_MAX_CHUNKS = 32768;            // grid.y of the workgroup kernel
+constexpr int KC_SMALL_THREADS = 1024;
+constexpr int KC_SMALL_F = 2048;                // vertices of a frontier the one-workgroup kernel takes
+constexpr int KC_SMALL_SCAN = 65536;            // vertices it scans itself on a k change (64 per thread)
+constexpr int64_t KC_NO_K = 0x7F7F7F7F7F7F7F7Fll;      // "no alive vertex" in KC_K (a byte pattern: one memset arms the min kernel)
+// device counters of a run (cumulative) and their slots in the pinned mirror
+enum {
+    KC_TAIL = 0,        // + class: entries appended to the class list so far
+    KC_M = 3,           // row lengths of the appended vertices, summed = entries walked once they are all expanded
+    KC_K = 4,           // the min kernel's result; published: the current (or last finished) k
+    KC_ALIVE = 5,       // length of the compacted list of alive vertices
+    KC_HEAD = 6,        // + class (mirror only, small kernel): the frontier it leaves starts here
+    KC_CUR_M = 9,       // (mirror only, small kernel) entries of the frontier it leaves
+    KC_ROUNDS = 10, KC_SUBS = 11, KC_STATE = 12,      // (mirror only, small kernel) k changes and sub-rounds it ran, why it ended
+    KC_NCNT = 16
+};
+enum { KC_ST_BIG = 0, KC_ST_NEED_K = 1, KC_ST_DONE = 2, KC_ST_LIMIT = 3 };
+static_assert(KC_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
+
+struct kc_bounds { int32_t shrt, wave; };
+__host__ __device__ inline int kc_class_of(int64_t d, kc_bounds b) { return d <= b.shrt ? KC_SHORT : d <= b.wave ? KC_WAVE : KC_WG; }
+
+struct kc_lists { int32_t *list[KC_NCLS]; int32_t cap; };      // one list per class, `cap` entries each
+struct kc_graph {
+    const int64_t *rowptr;       // the symmetric CSR
+    const int32_t *adj;
+    int32_t *deg;                // working degrees
+    int32_t *core;
+    kc_bounds b;
+    kc_lists L;
+};
+
+// ---- prepare ----
+__device__ __forceinline__ int32_t kc_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
+{
+    int32_t lo = 0, hi = V;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (rp[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// keys per row of the symmetric CSR before deduplication (only when the keys do not fit one piece)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_count_rows(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, int32_t *per_row)
+{
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t u = kc_row_of(rp, V, e), v = adj[e];
+        if (u == v || v < 0 || v >= V) continue;
+        atomicAdd(per_row + u, 1);
+        atomicAdd(per_row + v, 1);
+    }
+}
+// the keys whose row is in [v0, v1), appended in any order (the sort follows); never more than cap are written
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_emit(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, int32_t v0, int32_t v1, uint64_t *keys,
+                                                               unsigned long long *n_keys, int64_t cap)
+{
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t u = kc_row_of(rp, V, e), v = adj[e];
+        if (u == v || v < 0 || v >= V) continue;
+        if (u >= v0 && u < v1) {
+            const unsigned long long pos = atomicAdd(n_keys, 1ull);
+            if ((int64_t)pos < cap) keys[pos] = (uint64_t)(uint32_t)u << 32 | (uint32_t)v;
+        }
+        if (v >= v0 && v < v1) {
+            const unsigned long long pos = atomicAdd(n_keys, 1ull);
+            if ((int64_t)pos < cap) keys[pos] = (uint64_t)(uint32_t)v << 32 | (uint32_t)u;
+        }
+    }
+}
+// sorted unique keys of the piece -> entries [base, base + n) of the adjacency
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_fill(const uint64_t *keys, int64_t n, int64_t base, int32_t *adj, int64_t adj_cap)
+{
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK)
+        if (base + i < adj_cap) adj[base + i] = (int32_t)(uint32_t)keys[i];
+}
+// rowptr[r] = base + (keys of the piece below row r), r in [v0, v1]
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_rowptr(const uint64_t *keys, int64_t n, int32_t v0, int32_t v1, int64_t base, int64_t *rowptr)
+{
+    for (int64_t r = v0 + (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; r <= v1; r += (int64_t)gridDim.x * VGL_BLOCK) {
+        const uint64_t first = (uint64_t)r << 32;
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+            const int64_t mid = lo + (hi - lo) / 2;
+            if (keys[mid] < first) lo = mid + 1; else hi = mid;
+        }
+        rowptr[r] = base + lo;
+    }
+}
+// deg[v] = length of row v; the longest row
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_degrees(int32_t V, const int64_t *rowptr, int32_t *deg, int32_t *max_deg)
+{
+    int m = 0;
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int d = (int)(rowptr[v + 1] - rowptr[v]);
+        deg[v] = d;
+        m = max(m, d);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+    if (vgl_lane() == 0 && m) atomicMax(max_deg, m);
+}
+
+// ---- the peel: shared device pieces ----
+// Every lane of the wave calls (uniform control flow).  The lanes with `want` append u to the list of class `cls`: one returning atomic per wave
+// and class.  tail: the three cumulative list lengths, in global memory (large path) or in LDS (one-workgroup kernel).
+__device__ __forceinline__ void kc_append(bool want, int32_t u, int cls, const kc_lists &L, unsigned long long *tail)
+{
+    if (!__any(want)) return;
+    const int lane = vgl_lane();
+#pragma unroll
+    for (int c = 0; c < KC_NCLS; c++) {
+        const bool mine = want && cls == c;
+        const unsigned long long m = __ballot(mine);
+        if (!m) continue;                                             // (uniform)
+        const int leader = __ffsll((long long)m) - 1;
+        unsigned long long base = 0;
+        if (lane == leader) base = atomicAdd(tail + c, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader);
+        if (mine) {
+            const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+            if (pos < (unsigned long long)L.cap) vgl_store_agent(L.list[c] + pos, u);
+        }
+    }
+}
+// One adjacency entry u of a vertex expanded at level k (active = this lane holds one).  deg[u] crosses k + 1 -> k exactly once: while it is above k
+// it only falls; once it is at or below k every decrement that lands sees old <= k and is put back, so the value never returns to k + 1 and the
+// append below happens in one thread.  A stale deg[u] can only be too large (the pre-check reads at device scope anyway), which costs an atomic.
+__device__ __forceinline__ void kc_relax(bool active, int32_t u, int32_t k, const kc_graph &g, unsigned long long *tail, int64_t &m_acc)
+{
+    bool want = false;
+    int cls = 0;
+    if (active && vgl_load_agent(g.deg + u) > k) {
+        const int32_t old = atomicSub(g.deg + u, 1);
+        if (old == k + 1) {
+            const int64_t len = g.rowptr[u + 1] - g.rowptr[u];
+            want = true;
+            cls = kc_class_of(len, g.b);
+            m_acc += len;
+        } else if (old <= k) atomicAdd(g.deg + u, 1);
+    }
+    kc_append(want, u, cls, g.L, tail);
+}
+// the entries [lo, hi) of one row, `stride` lanes of which this is lane `li`; uniform over the wave as long as every lane of the wave calls
+__device__ __forceinline__ void kc_walk(int64_t lo, int64_t hi, int li, int stride, int32_t k, const kc_graph &g, unsigned long long *tail, int64_t &m_acc)
+{
+    int64_t e = lo + li;
+    while (__any(e < hi)) {
+        const bool active = e < hi;
+        const int32_t u = active ? g.adj[e] : 0;
+        kc_relax(active, u, k, g, tail, m_acc);
+        e += stride;
+    }
+}
+__device__ __forceinline__ void kc_flush_m(unsigned long long *cnt, int64_t m)      // every lane of the wave, once, at the end of a kernel
+{
+    m = vgl_wave_reduce_add(m);
+    if (vgl_lane() == 0 && m) atomicAdd(cnt + KC_M, (unsigned long long)m);
+}
+
+// ---- the peel: large path ----
+// cnt[KC_K] = min(deg) over the alive vertices of the scan domain (ids == nullptr: every vertex); alive: deg > k_prev
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_min(const int32_t *ids, int32_t n, const int32_t *deg, int32_t k_prev, unsigned long long *cnt)
+{
+    int m = INT_MAX;
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t d = deg[ids ? ids[i] : (int32_t)i];
+        if (d > k_prev) m = min(m, d);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+    if (vgl_lane() == 0 && m != INT_MAX) atomicMin(cnt + KC_K, (unsigned long long)m);
+}
+// the first frontier of k = cnt[KC_K]: the alive vertices of the domain with deg <= k (nothing when no vertex is alive or k has reached k_limit)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_scan(const int32_t *ids, int32_t n, kc_graph g, int32_t k_prev, int32_t k_limit, unsigned long long *cnt)
+{
+    const unsigned long long k64 = cnt[KC_K];
+    if (k64 == (unsigned long long)KC_NO_K || (k_limit > 0 && k64 >= (unsigned long long)k_limit)) return;
+    const int32_t k = (int32_t)k64;
+    int64_t m_acc = 0;
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x;
+        bool want = false;
+        int cls = 0;
+        int32_t v = 0;
+        if (i < n) {
+            v = ids ? ids[i] : (int32_t)i;
+            const int32_t d = g.deg[v];
+            if (d > k_prev && d <= k) {
+                const int64_t len = g.rowptr[v + 1] - g.rowptr[v];
+                want = true;
+                cls = kc_class_of(len, g.b);
+                m_acc += len;
+            }
+        }
+        kc_append(want, v, cls, g.L, cnt + KC_TAIL);
+    }
+    kc_flush_m(cnt, m_acc);
+}
+// the alive vertices, compacted (once, when few are left: the scans of the dense tail then read this list and not V degrees)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_compact(int32_t V, const int32_t *deg, int32_t k_prev, int32_t *alive, int32_t cap, unsigned long long *cnt)
+{
+    kc_lists L;
+    L.list[0] = L.list[1] = L.list[2] = alive;
+    L.cap = cap;
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t v = base + threadIdx.x;
+        kc_append(v < V && deg[v] > k_prev, (int32_t)v, 0, L, cnt + KC_ALIVE);
+    }
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_short(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
+{
+    const int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / KC_G;
+    const int gi = threadIdx.x & (KC_G - 1);
+    int64_t lo = 0, hi = 0, m_acc = 0;
+    if (i < n) {
+        const int32_t v = rows[i];
+        lo = g.rowptr[v]; hi = g.rowptr[v + 1];
+        if (gi == 0) g.core[v] = k;
+    }
+    kc_walk(lo, hi, gi, KC_G, k, g, cnt + KC_TAIL, m_acc);
+    kc_flush_m(cnt, m_acc);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wave(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
+{
+    const int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave();
+    if (i >= n) return;                                               // (uniform over the wave)
+    const int32_t v = rows[i];
+    int64_t m_acc = 0;
+    if (vgl_lane() == 0) g.core[v] = k;
+    kc_walk(g.rowptr[v], g.rowptr[v + 1], vgl_lane(), 64, k, g, cnt + KC_TAIL, m_acc);
+    kc_flush_m(cnt, m_acc);
+}
+// workgroup (row blockIdx.x, chunk blockIdx.y): `chunk` entries of the row; a workgroup past the end of its row has nothing to do
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wg(kc_graph g, const int32_t *rows, int32_t chunk, int32_t k, unsigned long long *cnt)
+{
+    const int32_t v = rows[blockIdx.x];
+    const int64_t end = g.rowptr[v + 1], lo = g.rowptr[v] + (int64_t)blockIdx.y * chunk;
+    if (blockIdx.y == 0 && threadIdx.x == 0) g.core[v] = k;
+    if (lo >= end) return;                                            // (uniform over the workgroup)
+    int64_t m_acc = 0;
+    kc_walk(lo, min(end, lo + chunk), (int)threadIdx.x, VGL_BLOCK, k, g, cnt + KC_TAIL, m_acc);
+    kc_flush_m(cnt, m_acc);
+}
+// the peel stopped at k_limit: what is still alive gets k_limit
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_fill_limit(int32_t V, const int32_t *deg, int32_t k_last, int32_t k_limit, int32_t *core)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK)
+        if (deg[v] > k_last) core[v] = k_limit;
+}
+// the counters into the pinned mirror, then the sequence number (one wavefront)
+__global__ void vgl_k_kcore_publish(const unsigned long long *cnt, volatile int64_t *host, int64_t seq)
+{
+    if (threadIdx.x < KC_NCNT) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
+}
+
+// ---- the peel: small frontiers, ONE workgroup ----
+// Entry: the frontier of level k is [head[c], cnt[KC_TAIL + c]) of the class lists and has cur_m entries; it may be empty, k then being the last
+// finished level (-1: none yet).  dom_n > 0: on a k change this workgroup scans the domain (dom_ids == nullptr: the vertices 0 .. dom_n - 1) itself;
+// dom_n == 0: it ends there and the host runs the scan kernels.  It ends (state in the mirror) when the next frontier is too large for it
+// (KC_ST_BIG: the lists hold it, as after a sub-round of the large path), a k change is not its to make (KC_ST_NEED_K), no vertex is alive
+// (KC_ST_DONE) or k has reached k_limit (KC_ST_LIMIT).  Every turn of the loop expands a frontier or changes k, so it ends after at most 2 V turns.
+// Values other threads of the workgroup wrote are read at device scope (degrees, list entries), never from a line this CU may have cached.
+__global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g, const int32_t *dom_ids, int32_t dom_n, int64_t head0, int64_t head1, int64_t head2,
+                                                                      int64_t cur_m, int32_t k, int32_t k_limit, int64_t cap_m, unsigned long long *cnt,
+                                                                      volatile int64_t *host, int64_t seq)
+{
+    constexpr int NT = KC_SMALL_THREADS, NW = NT / 64;
+    __shared__ unsigned long long s_tail[KC_NCLS];
+    __shared__ unsigned long long s_m;
+    __shared__ int s_min;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t head[KC_NCLS] = {head0, head1, head2};
+    int64_t rounds = 0, subs = 0, m_total = 0;
+    int state = KC_ST_BIG;
+    if (tid < KC_NCLS) s_tail[tid] = cnt[KC_TAIL + tid];
+    if (tid == 0) s_m = 0;
+    for (;;) {
+        __syncthreads();                                              // the lists, s_tail and s_m = 0 are in place; s_min has been read
+        int64_t tail[KC_NCLS];
+        int64_t F = 0;
+#pragma unroll
+        for (int c = 0; c < KC_NCLS; c++) { tail[c] = (int64_t)s_tail[c]; F += tail[c] - head[c]; }
+        int64_t m_acc = 0;
+        if (F == 0) {                                                 // ---- k change ----
+            if (dom_n <= 0) { state = KC_ST_NEED_K; break; }
+            if (tid == 0) s_min = INT_MAX;
+            __syncthreads();
+            int m = INT_MAX;
+            for (int i = tid; i < dom_n; i += NT) {
+                const int32_t d = vgl_load_agent(g.deg + (dom_ids ? dom_ids[i] : i));
+                if (d > k) m = min(m, d);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+            if (lane == 0 && m != INT_MAX) atomicMin(&s_min, m);
+            __syncthreads();
+            const int kn = s_min;
+            if (kn == INT_MAX) { state = KC_ST_DONE; break; }
+            if (k_limit > 0 && kn >= k_limit) { state = KC_ST_LIMIT; break; }
+            for (int base = 0; base < dom_n; base += NT) {            // (uniform over the workgroup)
+                const int i = base + tid;
+                bool want = false;
+                int cls = 0;
+                int32_t v = 0;
+                if (i < dom_n) {
+                    v = dom_ids ? dom_ids[i] : i;
+                    const int32_t d = vgl_load_agent(g.deg + v);
+                    if (d > k && d <= kn) {
+                        const int64_t len = g.rowptr[v + 1] - g.rowptr[v];
+                        want = true;
+                        cls = kc_class_of(len, g.b);
+                        m_acc += len;
+                    }
+                }
+                kc_append(want, v, cls, g.L, s_tail);
+            }
+            k = kn;
+            rounds++;
+        } else {                                                      // ---- one sub-round ----
+            if (F > KC_SMALL_F || cur_m > cap_m) { state = KC_ST_BIG; break; }
+            {                                                         // short rows: 8 lanes each
+                const int64_t n = tail[KC_SHORT] - head[KC_SHORT];
+                for (int64_t i0 = 0; i0 < n; i0 += NT / KC_G) {       // (uniform over the workgroup)
+                    const int64_t i = i0 + tid / KC_G;
+                    int64_t lo = 0, hi = 0;
+                    if (i < n) {
+                        const int32_t v = vgl_load_agent(g.L.list[KC_SHORT] + head[KC_SHORT] + i);
+                        lo = g.rowptr[v]; hi = g.rowptr[v + 1];
+                        if ((tid & (KC_G - 1)) == 0) g.core[v] = k;
+                    }
+                    kc_walk(lo, hi, tid & (KC_G - 1), KC_G, k, g, s_tail, m_acc);
+                }
+            }
+            {                                                         // longer rows: a wavefront each (cur_m <= cap_m bounds them)
+                const int64_t n1 = tail[KC_WAVE] - head[KC_WAVE], n = n1 + tail[KC_WG] - head[KC_WG];
+                for (int64_t j = wave; j < n; j += NW) {              // (uniform over the wave)
+                    const int32_t v = j < n1 ? vgl_load_agent(g.L.list[KC_WAVE] + head[KC_WAVE] + j) : vgl_load_agent(g.L.list[KC_WG] + head[KC_WG] + (j - n1));
+                    if (lane == 0) g.core[v] = k;
+                    kc_walk(g.rowptr[v], g.rowptr[v + 1], lane, 64, k, g, s_tail, m_acc);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < KC_NCLS; c++) head[c] = tail[c];
+            subs++;
+        }
+        m_acc = vgl_wave_reduce_add(m_acc);
+        if (lane == 0 && m_acc) atomicAdd(&s_m, (unsigned long long)m_acc);
+        __syncthreads();                                              // every append and every add to s_m has landed
+        cur_m = (int64_t)s_m;
+        m_total += cur_m;
+        __syncthreads();
+        if (tid == 0) s_m = 0;
+    }
+    // (the breaks above are uniform over the workgroup and come right after a barrier: nobody is still appending)
+    if (tid == 0) {
+#pragma unroll
+        for (int c = 0; c < KC_NCLS; c++) {
+            cnt[KC_TAIL + c] = s_tail[c];
+            host[KC_TAIL + c] = (int64_t)s_tail[c];
+            host[KC_HEAD + c] = head[c];
+        }
+        const unsigned long long m_cum = cnt[KC_M] + (unsigned long long)m_total;
+        cnt[KC_M] = m_cum;
+        host[KC_M] = (int64_t)m_cum;
+        host[KC_K] = k;
+        host[KC_CUR_M] = cur_m;
+        host[KC_ROUNDS] = rounds;
+        host[KC_SUBS] = subs;
+        host[KC_STATE] = state;
+        __threadfence_system();
+        host[C_NSLOTS] = seq;
+        __threadfence_system();
+    }
+}
+
+unsigned kc_grid(int64_t work, int64_t per_block, int64_t cap = (int64_t)1 << 20) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
+
+}  // namespace
+
+// The symmetric simple CSR of a graph (cached on the handle, freed with it)
+struct vgl_kcore_cache {
+    int32_t V = 0;
+    int64_t nnz = 0;                             // 2 E'
+    vgl_dev<int64_t> rowptr;                     // V + 1
+    vgl_dev<int32_t> adj;                        // 2 E'
+    vgl_dev<int32_t> deg;                        // V: degree in the simple undirected graph
+    int32_t max_deg = 0;
+};
+
+void vgl_kcore_cache_free(vgl_kcore_cache *p) { delete p; }
+
+namespace {
+
+int kc_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, std::unique_ptr<vgl_kcore_cache, vgl_kcore_cache_delete> &out)
+{
+    const int32_t V = g->V;
+    const vgl_dir_csr &d = g->out;
+    const int64_t E = d.edges;
+    hipStream_t st = c->stream;
+    std::unique_ptr<vgl_kcore_cache> p(new vgl_kcore_cache());
+    p->V = V;
+    VGL_TRY(p->rowptr.alloc((size_t)V + 1));
+    VGL_TRY(p->deg.alloc((size_t)V));
+    VGL_HIP_TRY(hipMemsetAsync(p->rowptr, 0, sizeof(int64_t) * ((size_t)V + 1), st));
+    VGL_HIP_TRY(hipMemsetAsync(p->deg, 0, sizeof(int32_t) * (size_t)std::max(V, 1), st));
+    if (V > 0 && E > 0) {
+        // keys per piece: in + out buffers of 8 bytes each within the cap
+        const int64_t cap_keys = std::max<int64_t>(1, vgl_env_int(c, "VGL_KCORE_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
+        std::vector<int32_t> bounds{0, V};                            // pieces of consecutive rows
+        int64_t piece_keys = 2 * E;
+        if (2 * E > cap_keys) {
+            vgl_dev<int32_t> per_row;
+            VGL_TRY(per_row.alloc(st, (size_t)V));
+            VGL_HIP_TRY(hipMemsetAsync(per_row, 0, sizeof(int32_t) * (size_t)V, st));
+            hipLaunchKernelGGL(vgl_k_kcore_count_rows, dim3(kc_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, per_row.p);
+            VGL_HIP_TRY(hipGetLastError());
+            std::vector<int32_t> h((size_t)V);
+            VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_row, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+            per_row.reset();
+            bounds.assign(1, 0);
+            int64_t acc = 0;
+            piece_keys = 0;
+            for (int32_t v = 0; v < V; v++) {                         // greedy; a row with more keys than the cap is a piece of its own
+                if (acc > 0 && acc + h[(size_t)v] > cap_keys) { bounds.push_back(v); piece_keys = std::max(piece_keys, acc); acc = 0; }
+                acc += h[(size_t)v];
+            }
+            bounds.push_back(V);
+            piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
+        }
+        vgl_dev<uint64_t> keys_a, keys_b;
+        vgl_dev<unsigned long long> n_keys;
+        vgl_dev<size_t> n_unique;
+        vgl_dev<int32_t> adj_tmp;                                     // 2 E entries bound 2 E' from above
+        VGL_TRY(keys_a.alloc(st, (size_t)piece_keys));
+        VGL_TRY(keys_b.alloc(st, (size_t)piece_keys));
+        VGL_TRY(n_keys.alloc(st, 1));
+        VGL_TRY(n_unique.alloc(st, 1));
+        VGL_TRY(adj_tmp.alloc(st, (size_t)(2 * E)));
+        int end_bit = 33;
+        while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
+        size_t temp_sort = 0, temp_unique = 0;
+        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a.p, keys_b.p, (size_t)piece_keys, 0, (unsigned)end_bit, st));
+        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
+        const size_t temp_bytes = std::max(temp_sort, temp_unique);
+        vgl_dev<char> temp;
+        VGL_TRY(temp.alloc(st, temp_bytes));
+        int64_t base = 0;
+        for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
+            const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
+            VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
+            hipLaunchKernelGGL(vgl_k_kcore_emit, dim3(kc_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, v0, v1, keys_a.p, n_keys.p, piece_keys);
+            VGL_HIP_TRY(hipGetLastError());
+            unsigned long long nk = 0;
+            VGL_HIP_TRY(hipMemcpyAsync(&nk, n_keys, sizeof(nk), hipMemcpyDeviceToHost, st));
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+            if ((int64_t)nk > piece_keys) VGL_FAIL("kcore_prepare: a piece holds more keys than were counted for it");
+            size_t nu = 0;
+            if (nk) {
+                size_t need = temp_bytes;
+                VGL_HIP_TRY(rocprim::radix_sort_keys(temp.p, need, keys_a.p, keys_b.p, (size_t)nk, 0, (unsigned)end_bit, st));
+                need = temp_bytes;
+                VGL_HIP_TRY(rocprim::unique(temp.p, need, keys_b.p, keys_a.p, n_unique.p, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
+                VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
+                VGL_HIP_TRY(hipStreamSynchronize(st));
+            }
+            if (base + (int64_t)nu > 2 * E) VGL_FAIL("kcore_prepare: more symmetric entries than twice the stored ones");
+            hipLaunchKernelGGL(vgl_k_kcore_fill, dim3(kc_grid((int64_t)nu, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a.p, (int64_t)nu, base, adj_tmp.p, 2 * E);
+            hipLaunchKernelGGL(vgl_k_kcore_rowptr, dim3(kc_grid((int64_t)v1 - v0 + 1, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a.p, (int64_t)nu, v0, v1, base,
+                               p->rowptr.p);
+            VGL_HIP_TRY(hipGetLastError());
+            base += (int64_t)nu;
+        }
+        p->nnz = base;
+        VGL_TRY(p->adj.alloc((size_t)base));
+        if (base) VGL_HIP_TRY(hipMemcpyAsync(p->adj, adj_tmp, sizeof(int32_t) * (size_t)base, hipMemcpyDeviceToDevice, st));
+        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys.p);
+        VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
+        hipLaunchKernelGGL(vgl_k_kcore_degrees, dim3(kc_grid(V, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr.p, p->deg.p, d_max);
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_HIP_TRY(hipMemcpyAsync(&p->max_deg, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        VGL_TRY(p->adj.alloc(1));
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+    }
+    out.reset(p.release());
+    return 0;
+}
+
+int kc_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_kcore_cache **out, bool *built)
+{
+    *built = false;
+    if (!g->kcore) {
+        VGL_TRY(kc_build_csr(c, g, g->kcore));
+        *built = true;
+    }
+    *out = g->kcore.get();
+    return 0;
+}
+
+// the host side of one run: where the frontier is, what has been counted
+struct kc_run {
+    vgl_hip_ctx *c;
+    kc_graph g;
+    unsigned long long *cnt;
+    int64_t head[KC_NCLS] = {0, 0, 0}, tail[KC_NCLS] = {0, 0, 0};
+    int64_t m_cum = 0, cur_m = 0;        // entries of every frontier so far / of the current one
+    int32_t k = -1;                      // the current level, or the last finished one while the frontier is empty
+    int32_t rounds = 0;
+    int64_t subs = 0;
+
+    int64_t frontier() const { return tail[0] - head[0] + tail[1] - head[1] + tail[2] - head[2]; }
+    int64_t removed() const { return tail[0] + tail[1] + tail[2]; }
+    // the one host-visible read of a sub-round of the large path: list tails and entry total
+    int read()
+    {
+        const int64_t seq = vgl_next_seq(c);
+        {
+            vgl_timed_launch tl(c, "kcore_publish");
+            hipLaunchKernelGGL(vgl_k_kcore_publish, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)cnt, (volatile int64_t *)c->h_counters, seq);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_wait_counters(c, seq));
+        for (int k_ = 0; k_ < KC_NCLS; k_++) {
+            head[k_] = tail[k_];
+            tail[k_] = c->h_counters[KC_TAIL + k_];
+            if (tail[k_] < head[k_] || tail[k_] > g.L.cap) VGL_FAIL("kcore_run: internal error (a frontier list ran past its end)");
+        }
+        cur_m = c->h_counters[KC_M] - m_cum;
+        m_cum = c->h_counters[KC_M];
+        return 0;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int vgl_hip_kcore_prepare(vgl_hip_ctx *c, vgl_hip_graph *g)
+{
+    if (!c || !g) VGL_FAIL("kcore_prepare: null argument");
+    if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("kcore_prepare: graph handle must own all rows (the k-core decomposition has no sharded form)");
+    vgl_kcore_cache *k = nullptr;
+    bool built = false;
+    VGL_TRY(kc_ensure(c, g, &k, &built));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t *d_core, int32_t *d_degree, vgl_hip_kcore_stats *stats)
+{
+    if (!c || !g) VGL_FAIL("kcore_run: null argument");
+    if (!d_core) VGL_FAIL("kcore_run: d_core must not be NULL");
+    if (k_limit < 0) VGL_FAIL("kcore_run: k_limit must not be negative");
+    if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("kcore_run: graph handle must own all rows (the k-core decomposition has no sharded form)");
+    vgl_kcore_cache *kc = nullptr;
+    bool built = false;
+    VGL_TRY(kc_ensure(c, g, &kc, &built));
+    const int32_t V = g->V;
+    hipStream_t st = c->stream;
+    const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_KCORE_SHORT", 32, 0, 1 << 20);
+    const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_KCORE_WAVE", 1024, b_short, 1 << 24);
+    const int64_t chunk_env = vgl_env_int(c, "VGL_KCORE_CHUNK", 16384, 16, 1 << 28);
+    const int64_t small_m = vgl_env_int(c, "VGL_KCORE_SMALL", 8192, 0, 1 << 20);
+    vgl_hip_kcore_stats out;
+    memset(&out, 0, sizeof(out));
+    out.prepared_now = built ? 1 : 0;
+    out.undirected_edges = kc->nnz / 2;
+    out.max_degree = kc->max_deg;
+    if (V == 0) {
+        if (stats) *stats = out;
+        return 0;
+    }
+    if (d_degree) VGL_HIP_TRY(hipMemcpyAsync(d_degree, kc->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, st));
+
+    // scratch of the call, all of it drawn before the loop: working degrees, the class lists, the compacted alive list, the counters
+    vgl_dev<int32_t> deg, lists, alive;
+    vgl_dev<unsigned long long> cnt;
+    VGL_TRY(deg.alloc(st, (size_t)V));
+    VGL_TRY(lists.alloc(st, (size_t)V * KC_NCLS));
+    VGL_TRY(alive.alloc(st, (size_t)std::min<int32_t>(V, KC_SMALL_SCAN)));
+    VGL_TRY(cnt.alloc(st, KC_NCNT));
+    VGL_HIP_TRY(hipMemcpyAsync(deg, kc->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, st));
+    VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * KC_NCNT, st));
+
+    kc_run r;
+    r.c = c;
+    r.cnt = cnt;
+    r.g.rowptr = kc->rowptr; r.g.adj = kc->adj; r.g.deg = deg; r.g.core = d_core;
+    r.g.b = kc_bounds{b_short, b_wave};
+    for (int k_ = 0; k_ < KC_NCLS; k_++) r.g.L.list[k_] = lists.p + (size_t)V * k_;
+    r.g.L.cap = V;
+    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(kc->max_deg, 1), KC_MAX_CHUNKS));
+    const unsigned max_chunks = (unsigned)std::max<int64_t>(1, vgl_ceil_div(std::max(kc->max_deg, 1), chunk));
+    const int32_t *dom_ids = nullptr;                                 // the scan domain: every vertex, or the compacted alive list
+    int32_t dom_n = V;
+    bool limited = false;
+
+    // one launch of the one-workgroup kernel and the read of what it did
+    auto small = [&]() -> int {
+        const int64_t seq = vgl_next_seq(c);
+        {
+            vgl_timed_launch tl(c, "kcore_small");
+            hipLaunchKernelGGL(vgl_k_kcore_small, dim3(1), dim3(KC_SMALL_THREADS), 0, st, r.g, dom_ids, dom_n <= KC_SMALL_SCAN ? dom_n : 0, r.head[0], r.head[1], r.head[2], r.cur_m,
+                               r.k, k_limit, small_m, cnt.p, (volatile int64_t *)c->h_counters, seq);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_wait_counters(c, seq));
+        const int64_t *h = c->h_counters;
+        for (int k_ = 0; k_ < KC_NCLS; k_++) {
+            r.head[k_] = h[KC_HEAD + k_];
+            r.tail[k_] = h[KC_TAIL + k_];
+            if (r.head[k_] < 0 || r.tail[k_] < r.head[k_] || r.tail[k_] > V) VGL_FAIL("kcore_run: internal error (a frontier list ran past its end)");
+        }
+        r.m_cum = h[KC_M];
+        r.cur_m = h[KC_CUR_M];
+        r.k = (int32_t)h[KC_K];
+        r.rounds += (int32_t)h[KC_ROUNDS];
+        r.subs += h[KC_SUBS];
+        return (int)h[KC_STATE];
+    };
+
+    for (;;) {
+        const int64_t F = r.frontier();
+        if (F == 0) {                                                 // ---- k change ----
+            const int64_t left = V - r.removed();
+            if (left == 0) break;
+            if (small_m > 0 && !dom_ids && V > KC_SMALL_SCAN && left <= KC_SMALL_SCAN) {      // few are left: from now on the scans read their list
+                {
+                    vgl_timed_launch tl(c, "kcore_scan");
+                    hipLaunchKernelGGL(vgl_k_kcore_compact, dim3(kc_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, alive.p, KC_SMALL_SCAN, cnt.p);
+                }
+                VGL_HIP_TRY(hipGetLastError());
+                dom_ids = alive;
+                dom_n = (int32_t)left;                                // (alive = not yet in a list: the kernel appends exactly these)
+            }
+            if (small_m > 0 && dom_n <= KC_SMALL_SCAN) {
+                const int state = small();
+                if (state == KC_ST_DONE) break;
+                if (state == KC_ST_LIMIT) { limited = true; break; }
+                if (state == KC_ST_NEED_K) VGL_FAIL("kcore_run: internal error (the one-workgroup kernel refused a scan it was given)");
+                continue;
+            }
+            VGL_HIP_TRY(hipMemsetAsync(cnt.p + KC_K, 0x7F, sizeof(unsigned long long), st));      // KC_NO_K
+            {
+                vgl_timed_launch tl(c, "kcore_scan");
+                hipLaunchKernelGGL(vgl_k_kcore_min, dim3(kc_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, (const int32_t *)deg.p, r.k, cnt.p);
+            }
+            {
+                vgl_timed_launch tl(c, "kcore_scan");
+                hipLaunchKernelGGL(vgl_k_kcore_scan, dim3(kc_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, r.g, r.k, k_limit, cnt.p);
+            }
+            VGL_HIP_TRY(hipGetLastError());
+            VGL_TRY(r.read());
+            const int64_t kn = c->h_counters[KC_K];
+            if (kn == KC_NO_K) VGL_FAIL("kcore_run: internal error (vertices are left but none is alive)");
+            if (k_limit > 0 && kn >= k_limit) { limited = true; break; }
+            r.k = (int32_t)kn;
+            r.rounds++;
+            if (r.frontier() == 0) VGL_FAIL("kcore_run: internal error (the shell of the smallest remaining degree is empty)");
+            continue;
+        }
+        if (small_m > 0 && F <= KC_SMALL_F && r.cur_m <= small_m) {   // ---- small frontier: several sub-rounds in one workgroup ----
+            const int state = small();
+            if (state == KC_ST_DONE) break;
+            if (state == KC_ST_LIMIT) { limited = true; break; }
+            continue;
+        }
+        // ---- one sub-round of the large path: a launch per class that has rows, then the read ----
+        if (r.tail[KC_SHORT] > r.head[KC_SHORT]) {
+            const int64_t n = r.tail[KC_SHORT] - r.head[KC_SHORT];
+            vgl_timed_launch tl(c, "kcore_short");
+            hipLaunchKernelGGL(vgl_k_kcore_short, dim3(kc_grid(n * KC_G, VGL_BLOCK, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_SHORT] + r.head[KC_SHORT]), (int32_t)n,
+                               r.k, cnt.p);
+        }
+        if (r.tail[KC_WAVE] > r.head[KC_WAVE]) {
+            const int64_t n = r.tail[KC_WAVE] - r.head[KC_WAVE];
+            vgl_timed_launch tl(c, "kcore_wave");
+            hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(kc_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WAVE] + r.head[KC_WAVE]),
+                               (int32_t)n, r.k, cnt.p);
+        }
+        if (r.tail[KC_WG] > r.head[KC_WG]) {
+            const int64_t n = r.tail[KC_WG] - r.head[KC_WG];
+            vgl_timed_launch tl(c, "kcore_wg");
+            hipLaunchKernelGGL(vgl_k_kcore_wg, dim3((unsigned)n, max_chunks), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WG] + r.head[KC_WG]), chunk, r.k, cnt.p);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(r.read());
+        r.subs++;
+    }
+    if (limited) {
+        hipLaunchKernelGGL(vgl_k_kcore_fill_limit, dim3(kc_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, k_limit, d_core);
+        VGL_HIP_TRY(hipGetLastError());
+    }
+    VGL_HIP_TRY(hipStreamSynchronize(st));
+    out.degeneracy = limited ? k_limit : std::max(r.k, 0);
+    out.rounds = r.rounds;
+    out.sub_rounds = r.subs;
+    out.edges_examined = r.m_cum;
+    out.algorithmic_bytes = 20 * (int64_t)V + 8 * r.m_cum;
+    if (stats) *stats = out;
+    return 0;
+}
+
+}  // extern "C"

@@ -185,9 +185,11 @@ struct vgl_dir_csr {                 // one direction of the graph (borrowed) + 
 void vgl_lp_cache_free(struct vgl_lp_cache *p);  // lp.hip
 void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
 void vgl_bc_cache_free(struct vgl_bc_cache *p);  // bc.hip
+void vgl_kcore_cache_free(struct vgl_kcore_cache *p);  // kcore.hip
 struct vgl_lp_cache_delete { void operator()(struct vgl_lp_cache *p) const { vgl_lp_cache_free(p); } };      // (the types are complete in their files only)
 struct vgl_tri_cache_delete { void operator()(struct vgl_tri_cache *p) const { vgl_tri_cache_free(p); } };
 struct vgl_bc_cache_delete { void operator()(struct vgl_bc_cache *p) const { vgl_bc_cache_free(p); } };
+struct vgl_kcore_cache_delete { void operator()(struct vgl_kcore_cache *p) const { vgl_kcore_cache_free(p); } };
 struct vgl_hip_graph {
     uint64_t uid = 0;                // unique per created handle (a freed handle's address may be reused: caches key on this, not on the pointer)
     int32_t V = 0, row_begin = 0, row_end = 0, nrows = 0;
@@ -232,6 +234,7 @@ struct vgl_hip_graph {
     std::unique_ptr<struct vgl_lp_cache, vgl_lp_cache_delete> lp[2];   // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
     std::unique_ptr<struct vgl_tri_cache, vgl_tri_cache_delete> tri;   // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
     std::unique_ptr<struct vgl_bc_cache, vgl_bc_cache_delete> bc;      // betweenness centrality: the row classes of both directions (bc.hip, lazy, owned)
+    std::unique_ptr<struct vgl_kcore_cache, vgl_kcore_cache_delete> kcore;   // k-core decomposition: the symmetric simple CSR and its degrees (kcore.hip, lazy, owned)
 };
 
 struct vgl_hip_frontier {
