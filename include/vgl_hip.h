@@ -477,6 +477,54 @@ typedef struct {
 int vgl_hip_kcore_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
 int vgl_hip_kcore_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int32_t *d_core, int32_t *d_degree, vgl_hip_kcore_stats *stats);
 
+/* k-truss decomposition (`ktruss`): the truss number of every edge.  The reference has none, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *   edges     the E' undirected edges {lo < hi} are numbered 0 .. E' - 1 in ascending (lo, hi) order of the graph's own vertex numbering.  This is the
+ *             library's edge numbering of that graph: d_edge_u[i] = lo, d_edge_v[i] = hi of edge i.  E' >= 2^31 is an error.
+ *   support   support(e) = number of triangles of that graph that contain e; d_support receives this INITIAL support.  Sum = 3 * triangles.
+ *   result    d_truss[e] (int32, device, E' entries, required): the largest k such that e lies in a subgraph in which every edge is in at least k - 2
+ *             triangles of that subgraph.  An edge in no triangle has truss 2; every edge of K_n has truss n.
+ *   k_limit   0: the whole decomposition.  >= 2: the peel stops when k reaches it and every remaining edge gets k_limit, so that
+ *             d_truss = min(truss, k_limit).  1 or negative: an error.
+ *   The answer does not depend on the vertex order used internally, on any VGL_KTRUSS_* switch, on the order of the entries in a row or on the order in
+ *   which the atomics land: truss numbers are integers and unique.
+ * Method: vgl_hip_ktruss_prepare (or the first run) takes the symmetric simple CSR of `kcore` (built if the handle has none; the two share it) and adds
+ * eid (int32 per adjacency slot: the edge id) and the endpoint arrays, cached on the handle and freed with it; *undirected_edges (host, may be NULL)
+ * receives E'.  A run computes the initial support in one pass without atomics on the supports (per edge the SHORTER of the two full rows is walked,
+ * each entry searched in the longer), then peels level-synchronously: k = the smallest support of an alive edge + 2 (a device reduction, no walk through
+ * empty levels); the alive edges with support <= k - 2 are the first frontier of k; an expanded edge gets truss k, and every triangle it is in whose
+ * other two edges have not been removed in an earlier sub-round is destroyed exactly once: if neither of the two is in the current frontier both are
+ * decremented, if exactly one is the third edge is decremented by the frontier edge of the smaller id, if both are nothing is.  A decrement is
+ * old = atomicSub(&support[e], 1): old == k - 1 appends e to the next frontier, old <= k - 2 is put back.  Edges are split by the length of the shorter
+ * row: <= VGL_KTRUSS_SHORT (32) 8 lanes per edge, <= VGL_KTRUSS_WAVE (1024) a wavefront, longer a workgroup.
+ * stats, all exact and the same on every run:
+ *   max_truss = the largest value written to d_truss (0 when E' = 0); rounds = values of k the peel visited (= the distinct truss values below
+ *   k_limit); sub_rounds = frontiers expanded; max_support = the largest initial support; prepared_now = this call built eid and the endpoint arrays;
+ *   undirected_edges = E'; triangles = sum of the initial supports / 3;
+ *   support_elements = adjacency entries the support pass walked = sum over all edges (u, v) of min(d(u), d(v)), d = the degree in the simple graph
+ *   (the shorter row is walked once, whatever the class; the probes of the binary search in the longer row are not counted);
+ *   peel_elements = adjacency entries the peel walked = the same sum over the edges the peel expanded (every edge, or those of truss < k_limit);
+ *   algorithmic_bytes = 28 E' (support pass: two endpoints read, the support written; peel: two endpoints read, truss and the sub-round stamp written)
+ *   + 4 (support_elements + peel_elements) (every walked entry once); the search probes, the edge ids, stamps and supports read per triangle, the
+ *   atomics' traffic and the per-k scans are left out: a lower bound.
+ * Fails, before anything is written: a sharded handle, d_truss == NULL, one of d_edge_u / d_edge_v without the other, k_limit == 1 or < 0. */
+typedef struct {
+    int32_t max_truss;          /* largest value written to d_truss; 0 when E' = 0 */
+    int32_t rounds;             /* values of k visited */
+    int32_t max_support;        /* largest initial support */
+    int32_t prepared_now;       /* this call built the edge ids */
+    int64_t sub_rounds;         /* frontiers expanded */
+    int64_t undirected_edges;   /* E' */
+    int64_t triangles;
+    int64_t support_elements;   /* entries walked by the support pass */
+    int64_t peel_elements;      /* entries walked by the peel */
+    int64_t algorithmic_bytes;
+} vgl_hip_ktruss_stats;
+int vgl_hip_ktruss_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected_edges);
+int vgl_hip_ktruss_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int32_t *d_edge_u, int32_t *d_edge_v, int32_t *d_truss, int32_t *d_support,
+                       vgl_hip_ktruss_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

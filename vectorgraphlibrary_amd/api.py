@@ -229,6 +229,13 @@ class Graph:
         """the symmetric simple CSR of core_numbers() / k_core() now, outside any timing (vgl_hip_kcore_prepare)"""
         _l.check(self.ctx.L.vgl_hip_kcore_prepare(self.ctx.h, self.h))
 
+    def prepare_ktruss(self):
+        """the edge numbering of truss_numbers() / k_truss() (and the symmetric simple CSR it shares with core_numbers()) now, outside any timing
+        (vgl_hip_ktruss_prepare); returns the number of undirected edges"""
+        n = C.c_int64()
+        _l.check(self.ctx.L.vgl_hip_ktruss_prepare(self.ctx.h, self.h, C.byref(n)))
+        return n.value
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -574,6 +581,44 @@ def k_core(graph, k, raw=False):
         raise _l.VglHipError("k_core: k must be at least 1 (every vertex is in the 0-core)")
     _, stats = core_numbers(graph, k_limit=int(k), raw=raw)
     return stats["core"] >= int(k)
+
+
+def truss_numbers(graph, k_limit=0, support=False, raw=False):
+    """k-truss decomposition of the simple undirected graph underlying the stored outgoing CSR (the contract of vgl_hip_ktruss_run in
+    include/vgl_hip.h).  Returns (max_truss, stats dict); stats["edges"] is an int32 tensor [E', 2], the endpoints lo < hi of every undirected edge,
+    stats["truss"] an int32 tensor [E']: the truss number of that edge, or min(truss, k_limit) when k_limit >= 2 (the peel stops there).
+    support=True adds stats["support"] (int32 [E']: the triangles that contain the edge).  The endpoints are ORIGINAL vertex ids and the rows ascend by
+    (lo, hi) unless raw=True, which keeps the graph's own numbering and its edge order."""
+    ctx = graph.ctx
+    cap = max(graph.E, 1)                                           # E' <= the stored entries: the run itself tells E' (and whether it prepared)
+    eu, ev, truss = ctx.empty(cap, torch.int32), ctx.empty(cap, torch.int32), ctx.empty(cap, torch.int32)
+    sup = ctx.empty(cap, torch.int32) if support else None
+    st = _l.KtrussStats()
+    _l.check(ctx.L.vgl_hip_ktruss_run(ctx.h, graph.h, int(k_limit), _ptr(eu), _ptr(ev), _ptr(truss), _ptr(sup), C.byref(st)))
+    stats = _stats(st)
+    n = int(st.undirected_edges)
+    eu, ev, truss = eu[:n], ev[:n], truss[:n]
+    sup = sup[:n] if support else None
+    if not raw and graph.bwd is not None and n:
+        a, b = graph.bwd[eu.long()], graph.bwd[ev.long()]
+        eu, ev = torch.minimum(a, b), torch.maximum(a, b)
+        order = torch.argsort(eu.long() * graph.V + ev.long())
+        eu, ev, truss = eu[order], ev[order], truss[order]
+        sup = sup[order] if support else None
+    stats["edges"] = torch.stack([eu, ev], dim=1)
+    stats["truss"] = truss
+    if support:
+        stats["support"] = sup
+    return int(st.max_truss), stats
+
+
+def k_truss(graph, k, raw=False):
+    """the edges of the k-truss: an int32 tensor [n, 2] of the edges with truss >= k, in the order of truss_numbers(); the peel stops at k
+    (truss_numbers with k_limit=k).  k >= 2."""
+    if int(k) < 2:
+        raise _l.VglHipError("k_truss: k must be at least 2 (every edge is in the 2-truss)")
+    _, stats = truss_numbers(graph, k_limit=int(k), raw=raw)
+    return stats["edges"][stats["truss"] >= int(k)]
 
 
 def count_not_equal(ctx, a, b):

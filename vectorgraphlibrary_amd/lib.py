@@ -61,6 +61,12 @@ class KcoreStats(C.Structure):
                 ("sub_rounds", C.c_int64), ("undirected_edges", C.c_int64), ("edges_examined", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class KtrussStats(C.Structure):
+    _fields_ = [("max_truss", C.c_int32), ("rounds", C.c_int32), ("max_support", C.c_int32), ("prepared_now", C.c_int32),
+                ("sub_rounds", C.c_int64), ("undirected_edges", C.c_int64), ("triangles", C.c_int64), ("support_elements", C.c_int64),
+                ("peel_elements", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -145,6 +151,8 @@ _SIGNATURES = {
     "vgl_hip_bc_run": [_p, _p, C.POINTER(_i32), _i32, _int, _int, _p, _p, _p, _p, C.POINTER(BcStats)],
     "vgl_hip_kcore_prepare": [_p, _p],
     "vgl_hip_kcore_run": [_p, _p, _i32, _p, _p, C.POINTER(KcoreStats)],
+    "vgl_hip_ktruss_prepare": [_p, _p, C.POINTER(_i64)],
+    "vgl_hip_ktruss_run": [_p, _p, _i32, _p, _p, _p, _p, C.POINTER(KtrussStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
