@@ -525,6 +525,61 @@ int vgl_hip_ktruss_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirect
 int vgl_hip_ktruss_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int32_t *d_edge_u, int32_t *d_edge_v, int32_t *d_truss, int32_t *d_support,
                        vgl_hip_ktruss_stats *stats);
 
+/* Minimum spanning forest (`msf`): Boruvka on the weighted simple undirected graph.  The reference has none, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.  d_weights: float32, device, one per stored outgoing entry in
+ *             the order of the outgoing CSR, exactly as vgl_hip_sssp_run takes them (may be NULL only when nothing is stored).
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *   weight    of the undirected edge {lo, hi}: the smallest weight over all stored entries (lo, hi) and (hi, lo) -- a multi-edge counts with its
+ *             lightest copy.  Loops are ignored, their weights included.
+ *   edges     carry the library's edge numbering of vgl_hip_ktruss_run (ascending (lo, hi) in the graph's own vertex numbering, E' < 2^31); it is
+ *             taken from the handle's k-truss cache (built if absent, shared afterwards), there is no second numbering.
+ *   order     edges are totally ordered by (weight, edge id); weights compare as numbers: -0.0 equals +0.0, -inf and +inf are allowed.  The order is
+ *             strict, so the forest is unique: e is in it iff e is not the largest edge of any cycle.
+ *   NaN       a NaN among the weights of non-loop entries is an error (the message names `weights`), reported before any output is written.
+ *   outputs   d_in_forest (uint8, E' entries, required): 1 / 0;  d_edge_weight (float32, E', optional): the folded weight;  d_edge_u / d_edge_v
+ *             (int32, E', optional, both or neither): lo, hi as in k-truss;  d_component (int32, V, optional): the smallest vertex id, in the
+ *             graph's own numbering, of the vertex's component of that graph -- an isolated vertex is its own component.
+ *   rounds    the number of synchronous Boruvka rounds that added an edge, under this rule: in a round every current component that has a crossing
+ *             edge picks its smallest crossing edge in the order above; all picked edges join the forest; the components are merged along all of
+ *             them to completion before the next round.  With the strict order this is a function of the graph and the weights alone: rounds is
+ *             exact, 0 when E' = 0, at most ceil(log2 V).
+ *   The answer does not depend on the order of the entries in a row, on any VGL_MSF_* switch or on the order in which the atomics land.
+ * Method: vgl_hip_msf_prepare (or the first run) takes the symmetric simple CSR of `kcore` and the edge ids of `ktruss` (built if the handle has none)
+ * and adds slot_eid, int32 per STORED outgoing entry: its undirected edge, -1 for a loop (a binary search of the entry in its symmetric row); cached on
+ * the handle and freed with it; *undirected_edges (host, may be NULL) receives E'.  Structure is per graph, values are per weights: a run folds the
+ * weights in one streaming pass (the float as an order-preserving uint32 -- -0.0 canonicalised, the sign bit flipped, negatives complemented -- and
+ * an integer atomicMin per entry on wkey[edge]; the same pass counts the NaNs).  A round: the live rows, one kernel per row class (<= VGL_MSF_SHORT
+ * (32): 8 lanes per row, <= VGL_MSF_WAVE (1024): a wavefront, longer: one workgroup per VGL_MSF_CHUNK (16384) entries), keep per row the smallest
+ * key  wkey << 32 | edge id  over the entries that lead into another component and make one 64-bit atomicMin on best[component] (skipped when the
+ * slot already holds a smaller key; the short rows of a wave that share a component go as one); a row without a crossing entry leaves the live list
+ * for good.  Every root c with a pick e hooks to the component d at the far end -- unless d picked e as well and c < d, then c stays a root --
+ * sets in_forest[e] and counts the edge (so an edge is counted once); parents are chased to the roots into a second array, the labels rewritten, and
+ * the host reads the round's totals once from the pinned mirror.  The loop ends on a round with no pick.
+ * stats, all exact and the same on every run:
+ *   rounds as above; prepared_now = this call built slot_eid; forest_edges = edges in the forest; components = V - forest_edges;
+ *   undirected_edges = E';  entries_walked = adjacency entries the min-edge passes walked = the row lengths of the live rows, summed over the rounds
+ *   (for E' > 0: 2 E' <= entries_walked <= (rounds + 1) 2 E');
+ *   algorithmic_bytes = 8 E (fold: slot_eid and the weight of every stored entry) + 5 E' (wkey and in_forest written) + 12 entries_walked (the
+ *   adjacency entry, its edge id and the far end's component) + 20 V rounds (hook: component and best read; relabel: component read and written);
+ *   the keys of the crossing entries, the atomics' traffic, the live lists and the last, empty round's vertex passes are left out: a lower bound; 0 when E' = 0 (no pass runs);
+ *   total_weight = the float64 sum of the forest edges' float32 weights, without floating-point atomics and in a shape fixed by E' alone (per-workgroup
+ *   partials stored, then one workgroup sums them in index order): bit-identical from run to run.
+ * Fails, before anything is written: a sharded handle, d_in_forest == NULL, d_weights == NULL while entries are stored, one of d_edge_u / d_edge_v
+ * without the other, a NaN weight on a non-loop entry. */
+typedef struct {
+    int32_t rounds;             /* Boruvka rounds that added an edge */
+    int32_t prepared_now;       /* this call built slot_eid */
+    int64_t forest_edges;
+    int64_t components;         /* V - forest_edges */
+    int64_t undirected_edges;   /* E' */
+    int64_t entries_walked;     /* adjacency entries walked by the min-edge passes */
+    int64_t algorithmic_bytes;
+    double total_weight;        /* float64 sum of the forest edges' float32 weights */
+} vgl_hip_msf_stats;
+int vgl_hip_msf_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected_edges);
+int vgl_hip_msf_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_weights, int32_t *d_edge_u, int32_t *d_edge_v, float *d_edge_weight,
+                    uint8_t *d_in_forest, int32_t *d_component, vgl_hip_msf_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -236,6 +236,13 @@ class Graph:
         _l.check(self.ctx.L.vgl_hip_ktruss_prepare(self.ctx.h, self.h, C.byref(n)))
         return n.value
 
+    def prepare_msf(self):
+        """what minimum_spanning_forest() keeps per graph (the symmetric simple CSR, the edge numbering it shares with truss_numbers() and the edge of
+        every stored entry) now, outside any timing (vgl_hip_msf_prepare); returns the number of undirected edges"""
+        n = C.c_int64()
+        _l.check(self.ctx.L.vgl_hip_msf_prepare(self.ctx.h, self.h, C.byref(n)))
+        return n.value
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -619,6 +626,42 @@ def k_truss(graph, k, raw=False):
         raise _l.VglHipError("k_truss: k must be at least 2 (every edge is in the 2-truss)")
     _, stats = truss_numbers(graph, k_limit=int(k), raw=raw)
     return stats["edges"][stats["truss"] >= int(k)]
+
+
+def minimum_spanning_forest(graph, weights, component=False, raw=False):
+    """minimum spanning forest of the simple undirected graph underlying the stored outgoing CSR (the contract of vgl_hip_msf_run in
+    include/vgl_hip.h); weights: float32, one per stored outgoing entry in CSR order, as sssp() takes them.  Returns (total_weight, stats dict);
+    stats["edges"] is an int32 tensor [n, 2], the forest edges lo < hi, stats["weights"] a float32 tensor [n], their weights.  Of ALL E' undirected
+    edges, in the same numbering and order: stats["all_edges"] (int32 [E', 2]), stats["edge_weight"] (float32 [E'], the lightest stored copy) and
+    stats["in_forest"] (bool [E']).  component=True adds stats["component"] (int32 [V]): one representative vertex per component (the smallest id
+    in the graph's own numbering).  all_edges / edge_weight / in_forest go beyond the forest itself: the run fills them anyway (the library writes
+    the mask and, on request, endpoints and folded weights per undirected edge; the four result arrays are sized by the stored entries, 13 bytes
+    each, because E' is known only after the run), and the tests compare them.  Endpoints and representatives are ORIGINAL vertex ids, the edges ascend by (lo, hi) and component is in
+    ORIGINAL vertex order unless raw=True, which keeps the graph's own numbering and its edge order."""
+    ctx = graph.ctx
+    cap = max(graph.E, 1)                                           # E' <= the stored entries: the run itself tells E' (and whether it prepared)
+    eu, ev = ctx.empty(cap, torch.int32), ctx.empty(cap, torch.int32)
+    ew, mask = ctx.empty(cap, torch.float32), ctx.empty(cap, torch.uint8)
+    comp = ctx.empty(graph.V, torch.int32) if component else None
+    st = _l.MsfStats()
+    _l.check(ctx.L.vgl_hip_msf_run(ctx.h, graph.h, _ptr(weights), _ptr(eu), _ptr(ev), _ptr(ew), _ptr(mask), _ptr(comp), C.byref(st)))
+    stats = _stats(st)
+    n = int(st.undirected_edges)
+    eu, ev, ew, mask = eu[:n], ev[:n], ew[:n], mask[:n].bool()
+    to_orig = not raw and graph.bwd is not None
+    if to_orig and n:
+        a, b = graph.bwd[eu.long()], graph.bwd[ev.long()]
+        eu, ev = torch.minimum(a, b), torch.maximum(a, b)
+        order = torch.argsort(eu.long() * graph.V + ev.long())
+        eu, ev, ew, mask = eu[order], ev[order], ew[order], mask[order]
+    stats["all_edges"] = torch.stack([eu, ev], dim=1)
+    stats["edge_weight"] = ew
+    stats["in_forest"] = mask
+    stats["edges"] = stats["all_edges"][mask]
+    stats["weights"] = ew[mask]
+    if component:
+        stats["component"] = graph.to_original(graph.bwd[comp.long()]) if to_orig else comp
+    return float(st.total_weight), stats
 
 
 def count_not_equal(ctx, a, b):

@@ -409,6 +409,17 @@ int kt_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_ktruss_cac
 
 }  // namespace
 
+int vgl_ktruss_edge_ids(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *out)
+{
+    vgl_ktruss_cache *kt = nullptr;
+    bool built = false;
+    VGL_TRY(kt_ensure(c, g, csr, &kt, &built));
+    out->ne = kt->ne;
+    out->eid = kt->eid; out->eu = kt->eu; out->ev = kt->ev;
+    out->built_now = built;
+    return 0;
+}
+
 extern "C" {
 
 int vgl_hip_ktruss_prepare(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *undirected_edges)

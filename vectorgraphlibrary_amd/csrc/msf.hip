@@ -1,0 +1,636 @@
+// msf.hip -- minimum spanning forest (Boruvka) of the simple undirected graph underlying the stored outgoing CSR, with float32 weights per stored entry.
+// The contract is written out in include/vgl_hip.h; DESIGN section 17 has the round, the kernel resources and the bytes model.
+//
+// Prepare (once per graph, cached on the handle): the symmetric simple CSR is kcore's, the edge numbering (eid per slot, endpoints) ktruss's
+// (vgl_ktruss_edge_ids: built there if the handle has none, shared afterwards).  On top of them: slot_eid[s] = the undirected edge of the STORED
+// outgoing entry s (a binary search of the entry in its symmetric row), -1 for a loop.  Structure is per graph, values are per weights.
+//
+// Fold (per run): wkey[e] = min over the stored entries of e of the order-preserving uint32 image of the weight (-0.0 canonicalised, sign bit
+// flipped, negatives complemented): one streaming pass, an integer atomicMin per entry, NaNs counted for the error.
+//
+// Round (comp[v] = the root vertex of v's component; best[c] = the smallest key  wkey << 32 | eid  of an edge that leaves component c):
+//   min-edge  the live rows, one kernel per row class (short: 8 lanes per row, wave, workgroup per chunk): a lane keeps the smallest key over its
+//             entries u with comp[u] != comp[v]; one 64-bit atomicMin per row on best[comp[v]], skipped when the slot already holds a smaller key
+//             (it only falls within a round); a row WITH a crossing entry is appended to the live list of the next round, a row without one never
+//             gets one again (components only grow) and is dropped.
+//   hook      every root c with a pick e: d = the component at the far end; if d picked e too and c < d, c stays a root, otherwise parent[c] = d,
+//             in_forest[e] = 1 and the edge is counted.  Under the strict order (weight, id) mutual picks are the only cycles.
+//   flatten   chase parent (read-only) from every old root to its new root, into a second array; comp[v] = root[comp[v]]; best reset for the roots.
+//   publish   list tails, picks and entries walked into the pinned mirror: one host read per round.  The loop ends on a round with no pick.
+// The live lists are one ring per class of twice the class's rows: a round reads [head, tail) and appends behind tail, positions taken modulo the
+// capacity; appends are staged per wave in LDS and cost one returning atomic per 64 or more rows.  No cooperative launch, no grid barrier.
+#include "vgl_hip_internal.h"
+#include <cstring>
+#include <algorithm>
+#include <climits>
+
+namespace {
+
+constexpr int MSF_NCLS = 3;
+enum { MSF_SHORT = 0, MSF_WAVE = 1, MSF_WG = 2 };
+constexpr int MSF_G = 8;                          // lanes per short row
+constexpr int MSF_MAX_CHUNKS = 32768;             // chunks of the longest row
+constexpr int64_t MSF_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
+constexpr int MSF_STAGE = 128;                    // LDS slots per wave of the append staging (fewer than 64 wait, at most 64 arrive)
+constexpr int MSF_MAX_ROUNDS = 64;                // (a run has at most ceil(log2 V) <= 31 rounds that add an edge, plus the empty one)
+constexpr int MSF_SUM_GRID = 1024;                // partials of the weight sum at most
+constexpr unsigned long long MSF_NONE = ~0ull;    // "no crossing edge" in best (a byte pattern: one memset arms the array)
+enum {
+    MSF_TAIL = 0,       // + class: rows appended to the class ring so far (cumulative)
+    MSF_PICKS = 3,      // edges the hooks added to the forest so far
+    MSF_WALK = 4,       // adjacency entries the min-edge passes walked so far
+    MSF_NAN = 5,        // NaN weights on non-loop entries
+    MSF_ROWS = 6,       // + class: rows with an entry, per class
+    MSF_NCNT = 9
+};
+static_assert(MSF_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
+
+struct msf_ring { int32_t *rows; uint32_t cap; };      // positions are cumulative: slot = position % cap
+struct msf_graph {
+    const int64_t *rowptr;       // the symmetric CSR
+    const int32_t *adj;
+    const int32_t *eid;          // edge id of every adjacency slot
+    const uint32_t *wkey;        // folded weight of every edge, as an order-preserving uint32
+    const int32_t *comp;
+    unsigned long long *best;
+};
+__device__ __forceinline__ int msf_class_of(int32_t d, int32_t b_short, int32_t b_wave) { return d <= b_short ? MSF_SHORT : d <= b_wave ? MSF_WAVE : MSF_WG; }
+
+// float -> uint32 that orders as the numbers do (-0.0 == +0.0; -inf smallest, +inf largest), and back
+__device__ __forceinline__ uint32_t msf_key_of(float w)
+{
+    uint32_t b = __float_as_uint(w);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float msf_weight_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+
+__device__ __forceinline__ int32_t msf_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
+{
+    int32_t lo = 0, hi = V;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (rp[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ unsigned long long msf_wave_min(unsigned long long m)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+    return m;
+}
+__device__ __forceinline__ void msf_flush_add(unsigned long long *cnt, int slot, int64_t m)      // every lane of the wave, once, at the end of a kernel
+{
+    m = vgl_wave_reduce_add(m);
+    if (vgl_lane() == 0 && m) atomicAdd(cnt + slot, (unsigned long long)m);
+}
+
+// ---- prepare ----
+// slot_eid of every stored outgoing entry: the entry (r, c), c != r, is found in row r of the symmetric CSR; eid of that slot
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_slot_eid(int32_t V, int64_t E, const int64_t *out_rp, const int32_t *out_adj, const int64_t *rowptr, const int32_t *adj,
+                                                                 const int32_t *eid, int32_t ne, int32_t *slot_eid)
+{
+    for (int64_t s = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; s < E; s += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t r = msf_row_of(out_rp, V, s), c = out_adj[s];
+        int32_t id = -1;
+        if (c >= 0 && c < V && c != r) {
+            int64_t lo = rowptr[r], hi = rowptr[r + 1];
+            while (lo < hi) {
+                const int64_t mid = lo + (hi - lo) / 2;
+                const int32_t x = adj[mid];
+                if (x < c) lo = mid + 1; else if (x > c) hi = mid; else { id = eid[mid]; break; }
+            }
+            if (id >= ne) id = -1;                                    // (the numbering has no such id)
+        }
+        slot_eid[s] = id;
+    }
+}
+
+// ---- fold ----
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_fold(int64_t E, const int32_t *slot_eid, const float *w, uint32_t *wkey, unsigned long long *cnt)
+{
+    int64_t nans = 0;
+    for (int64_t s = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; s < E; s += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t e = slot_eid[s];
+        if (e < 0) continue;
+        const float x = w[s];
+        if (x != x) { nans++; continue; }
+        atomicMin(wkey + e, msf_key_of(x));
+    }
+    msf_flush_add(cnt, MSF_NAN, nans);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_edge_weight(int32_t ne, const uint32_t *wkey, float *out)
+{
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < ne; e += (int64_t)gridDim.x * VGL_BLOCK) out[e] = msf_weight_of(wkey[e]);
+}
+
+// ---- the live lists ----
+// A wave's staged appends: `n` (uniform over the wave) rows wait in `buf` (LDS, MSF_STAGE slots, this wave's own).
+struct msf_stage { int32_t *buf; int n; };
+__device__ __forceinline__ void msf_flush(msf_stage &s, const msf_ring &R, unsigned long long *tail)      // every lane of the wave
+{
+    if (s.n == 0) return;                                             // (uniform)
+    unsigned long long base = 0;
+    if (vgl_lane() == 0) base = atomicAdd(tail, (unsigned long long)s.n);
+    base = __shfl(base, 0);
+    for (int j = vgl_lane(); j < s.n; j += 64) R.rows[(base + (unsigned long long)j) % R.cap] = s.buf[j];
+    __builtin_amdgcn_wave_barrier();
+    s.n = 0;
+}
+__device__ __forceinline__ void msf_keep(msf_stage &s, bool want, int32_t v, const msf_ring &R, unsigned long long *tail)      // every lane of the wave
+{
+    const unsigned long long m = __ballot(want);
+    if (!m) return;                                                   // (uniform)
+    if (want) s.buf[s.n + __popcll(m & ((1ull << vgl_lane()) - 1ull))] = v;
+    s.n += __popcll(m);
+    __builtin_amdgcn_wave_barrier();
+    if (s.n >= 64) msf_flush(s, R, tail);
+}
+// rows with an entry, per class
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_count(int32_t V, const int32_t *deg, int32_t b_short, int32_t b_wave, unsigned long long *cnt)
+{
+    int64_t n[MSF_NCLS] = {0, 0, 0};
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t d = deg[v];
+        if (d > 0) n[msf_class_of(d, b_short, b_wave)]++;
+    }
+#pragma unroll
+    for (int c = 0; c < MSF_NCLS; c++) msf_flush_add(cnt, MSF_ROWS + c, n[c]);
+}
+// comp[v] = v; the rows with an entry into the ring of their class
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_init(int32_t V, const int32_t *deg, int32_t b_short, int32_t b_wave, int32_t *comp, msf_ring R0, msf_ring R1, msf_ring R2,
+                                                             unsigned long long *cnt)
+{
+    __shared__ int32_t s_keep[MSF_NCLS][VGL_WAVES][MSF_STAGE];
+    const msf_ring R[MSF_NCLS] = {R0, R1, R2};
+    msf_stage st[MSF_NCLS];
+#pragma unroll
+    for (int c = 0; c < MSF_NCLS; c++) st[c] = msf_stage{s_keep[c][vgl_wave()], 0};
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t v = base + threadIdx.x;
+        int32_t d = 0;
+        if (v < V) { d = deg[v]; comp[v] = (int32_t)v; }
+        const int cls = msf_class_of(d, b_short, b_wave);
+#pragma unroll
+        for (int c = 0; c < MSF_NCLS; c++) msf_keep(st[c], d > 0 && cls == c, (int32_t)v, R[c], cnt + MSF_TAIL + c);
+    }
+#pragma unroll
+    for (int c = 0; c < MSF_NCLS; c++) msf_flush(st[c], R[c], cnt + MSF_TAIL + c);
+}
+
+// ---- the min-edge pass ----
+// the smallest key over the entries lo, lo + stride, ... < hi whose far end lies in another component than cv
+__device__ __forceinline__ unsigned long long msf_walk(int64_t lo, int64_t hi, int stride, int32_t cv, const msf_graph &g)
+{
+    unsigned long long m = MSF_NONE;
+    for (int64_t i = lo; i < hi; i += stride)
+        if (g.comp[g.adj[i]] != cv) {
+            const int32_t e = g.eid[i];
+            m = min(m, (unsigned long long)g.wkey[e] << 32 | (unsigned long long)(uint32_t)e);
+        }
+    return m;
+}
+// best[c] = min(best[c], key).  The slot only falls within a round, so a stored key that is already smaller settles it without the atomic.
+__device__ __forceinline__ void msf_offer(unsigned long long *slot, unsigned long long key)
+{
+    if (vgl_load_agent(slot) > key) atomicMin(slot, key);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, msf_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
+{
+    __shared__ int32_t s_keep[VGL_WAVES][MSF_STAGE];
+    msf_stage st{s_keep[vgl_wave()], 0};
+    const int gi = threadIdx.x & (MSF_G - 1), lane = vgl_lane();
+    int64_t walked = 0;
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / MSF_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / MSF_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / MSF_G;
+        int32_t v = 0, cv = 0;
+        int64_t lo = 0, hi = 0;
+        if (i < n) {
+            v = R.rows[(head + (unsigned long long)i) % R.cap];
+            cv = g.comp[v];
+            lo = g.rowptr[v]; hi = g.rowptr[v + 1];
+        }
+        unsigned long long m = msf_walk(lo + gi, hi, MSF_G, cv, g);
+#pragma unroll
+        for (int o = MSF_G / 2; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+        if (gi == 0) walked += hi - lo;
+        const bool found = gi == 0 && m != MSF_NONE;
+        // the rows of this wave that share the first found row's component go to its slot as one
+        const unsigned long long f = __ballot(found);
+        if (f) {                                                      // (uniform)
+            const int leader = __ffsll((long long)f) - 1;
+            const int32_t c0 = __shfl(cv, leader);
+            const bool same = found && cv == c0;
+            const unsigned long long k0 = msf_wave_min(same ? m : MSF_NONE);
+            if (lane == leader) msf_offer(g.best + c0, k0);
+            else if (found && !same) msf_offer(g.best + cv, m);
+        }
+        msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_SHORT);
+    }
+    msf_flush(st, R, cnt + MSF_TAIL + MSF_SHORT);
+    msf_flush_add(cnt, MSF_WALK, walked);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, msf_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
+{
+    __shared__ int32_t s_keep[VGL_WAVES][MSF_STAGE];
+    msf_stage st{s_keep[vgl_wave()], 0};
+    const int lane = vgl_lane();
+    int64_t walked = 0;
+    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
+        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
+        const int32_t cv = g.comp[v];
+        const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
+        const unsigned long long m = msf_wave_min(msf_walk(lo + lane, hi, 64, cv, g));
+        const bool found = lane == 0 && m != MSF_NONE;
+        if (lane == 0) walked += hi - lo;
+        if (found) msf_offer(g.best + cv, m);
+        msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_WAVE);
+    }
+    msf_flush(st, R, cnt + MSF_TAIL + MSF_WAVE);
+    msf_flush_add(cnt, MSF_WALK, walked);
+}
+// work item w = (row w / nchunks of the segment, chunk w % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do.
+// A row is appended by the first of its chunks that finds a crossing entry: stamp[position in the segment] = the round.
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, msf_ring R, unsigned long long head, int32_t n, int32_t chunk, int32_t nchunks, int32_t round, int32_t *stamp,
+                                                               unsigned long long *cnt)
+{
+    __shared__ unsigned long long s_red[VGL_WAVES];
+    const int64_t total = (int64_t)n * nchunks;
+    int64_t walked = 0;
+    for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {         // (uniform over the workgroup)
+        const int64_t i = w / nchunks;
+        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
+        const int64_t end = g.rowptr[v + 1], lo = g.rowptr[v] + (w % nchunks) * chunk;
+        if (lo >= end) continue;
+        const int64_t hi = min(end, lo + chunk);
+        const int32_t cv = g.comp[v];
+        unsigned long long m = msf_wave_min(msf_walk(lo + threadIdx.x, hi, VGL_BLOCK, cv, g));
+        __syncthreads();
+        if (vgl_lane() == 0) s_red[vgl_wave()] = m;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < VGL_WAVES; k++) m = min(m, s_red[k]);
+            walked += hi - lo;
+            if (m != MSF_NONE) {
+                msf_offer(g.best + cv, m);
+                if (atomicExch(stamp + i, round) != round) {
+                    const unsigned long long pos = atomicAdd(cnt + MSF_TAIL + MSF_WG, 1ull);
+                    R.rows[pos % R.cap] = v;
+                }
+            }
+        }
+    }
+    if (threadIdx.x == 0 && walked) atomicAdd(cnt + MSF_WALK, (unsigned long long)walked);
+}
+
+// ---- hook, flatten ----
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_hook(int32_t V, const int32_t *comp, const unsigned long long *best, const int32_t *eu, const int32_t *ev, int32_t *parent,
+                                                             uint8_t *in_forest, unsigned long long *cnt)
+{
+    int64_t picks = 0;
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        if (comp[v] != (int32_t)v) continue;                          // roots only
+        const unsigned long long k = best[v];
+        int32_t p = (int32_t)v;
+        if (k != MSF_NONE) {
+            const int32_t e = (int32_t)(uint32_t)k;
+            const int32_t ca = comp[eu[e]], cb = comp[ev[e]];
+            const int32_t d = ca == (int32_t)v ? cb : ca;
+            if (!(best[d] == k && (int32_t)v < d)) {                  // not the lower side of a mutual pick: v hooks, and counts the edge
+                p = d;
+                in_forest[e] = 1;
+                picks++;
+            }
+        }
+        parent[v] = p;
+    }
+    msf_flush_add(cnt, MSF_PICKS, picks);
+}
+// root[c] = the root of old root c under parent (read-only here; acyclic, and the walk is bounded by V all the same)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_chase(int32_t V, const int32_t *comp, const int32_t *parent, int32_t *root)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        if (comp[v] != (int32_t)v) continue;
+        int32_t x = (int32_t)v;
+        for (int32_t it = 0; it < V; it++) {
+            const int32_t p = parent[x];
+            if (p == x) break;
+            x = p;
+        }
+        root[v] = x;
+    }
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_relabel(int32_t V, int32_t *comp, const int32_t *root, unsigned long long *best)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t c = root[comp[v]];
+        comp[v] = c;
+        if (c == (int32_t)v) best[v] = MSF_NONE;
+    }
+}
+// the counters into the pinned mirror, then the sequence number (one wavefront)
+__global__ void vgl_k_msf_publish(const unsigned long long *cnt, volatile int64_t *host, int64_t seq)
+{
+    if (threadIdx.x < MSF_NCNT) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
+}
+
+// ---- after the loop ----
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_iota(int32_t V, int32_t *out)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) out[v] = (int32_t)v;
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_id(int32_t V, const int32_t *comp, int32_t *minid)      // minid[c] starts as c
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t c = comp[v];
+        if ((int32_t)v < c) atomicMin(minid + c, (int32_t)v);
+    }
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_component(int32_t V, const int32_t *comp, const int32_t *minid, int32_t *out)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) out[v] = minid[comp[v]];
+}
+// The float64 sum of the forest edges' weights, in a shape fixed by E' alone: thread t of workgroup b adds the edges b * 256 + t + k * grid * 256 in
+// ascending k, the wave adds by the xor tree, thread 0 the four waves in order; then one workgroup does the same over the partials.
+__device__ __forceinline__ double msf_block_sum(double x, double *s_red)
+{
+    x = vgl_wave_reduce_add(x);
+    __syncthreads();
+    if (vgl_lane() == 0) s_red[vgl_wave()] = x;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < VGL_WAVES; k++) t += s_red[k];
+    return t;
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_sum_partials(int32_t ne, const uint8_t *in_forest, const uint32_t *wkey, double *partials)
+{
+    __shared__ double s_red[VGL_WAVES];
+    double x = 0.0;
+    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < ne; e += (int64_t)gridDim.x * VGL_BLOCK)
+        if (in_forest[e]) x += (double)msf_weight_of(wkey[e]);
+    x = msf_block_sum(x, s_red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = x;
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_sum_final(int32_t n, const double *partials, double *out)
+{
+    __shared__ double s_red[VGL_WAVES];
+    double x = 0.0;
+    for (int i = threadIdx.x; i < n; i += VGL_BLOCK) x += partials[i];
+    x = msf_block_sum(x, s_red);
+    if (threadIdx.x == 0) *out = x;
+}
+
+unsigned msf_grid(int64_t work, int64_t per_block, int64_t cap = MSF_MAX_GRID) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
+
+}  // namespace
+
+// The undirected edge of every stored outgoing entry (cached on the handle, freed with it)
+struct vgl_msf_cache {
+    vgl_dev<int32_t> slot_eid;                   // E
+};
+
+void vgl_msf_cache_free(vgl_msf_cache *p) { delete p; }
+
+namespace {
+
+int msf_check_handle(vgl_hip_graph *g, const char *msg)
+{
+    if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL(msg);
+    return 0;
+}
+
+int msf_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *ids, bool *built)
+{
+    *built = false;
+    VGL_TRY(vgl_ktruss_edge_ids(c, g, csr, ids));
+    if (!g->msf) {
+        const int64_t E = g->out.edges;
+        hipStream_t st = c->stream;
+        std::unique_ptr<vgl_msf_cache> p(new vgl_msf_cache());
+        VGL_TRY(p->slot_eid.alloc((size_t)E));
+        if (E > 0) {
+            {
+                vgl_timed_launch tl(c, "msf_prepare");
+                hipLaunchKernelGGL(vgl_k_msf_slot_eid, dim3(msf_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, g->V, E, g->out.rowptr, g->out.adj, csr->rowptr, csr->adj, ids->eid,
+                                   (int32_t)ids->ne, p->slot_eid.p);
+            }
+            VGL_HIP_TRY(hipGetLastError());
+            VGL_HIP_TRY(hipStreamSynchronize(st));
+        }
+        g->msf.reset(p.release());
+        *built = true;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vgl_hip_msf_prepare(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *undirected_edges)
+{
+    if (!c || !g) VGL_FAIL("msf_prepare: null argument");
+    VGL_TRY(msf_check_handle(g, "msf_prepare: graph handle must own all rows (the minimum spanning forest has no sharded form)"));
+    vgl_sym_csr csr;
+    vgl_edge_ids ids;
+    bool built = false;
+    VGL_TRY(msf_ensure(c, g, &csr, &ids, &built));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));
+    if (undirected_edges) *undirected_edges = ids.ne;
+    return 0;
+}
+
+int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, int32_t *d_edge_u, int32_t *d_edge_v, float *d_edge_weight, uint8_t *d_in_forest,
+                    int32_t *d_component, vgl_hip_msf_stats *stats)
+{
+    if (!c || !g) VGL_FAIL("msf_run: null argument");
+    VGL_TRY(msf_check_handle(g, "msf_run: graph handle must own all rows (the minimum spanning forest has no sharded form)"));
+    if (!d_in_forest) VGL_FAIL("msf_run: d_in_forest must not be NULL");
+    if (!d_weights && g->out.edges > 0) VGL_FAIL("msf_run: d_weights must not be NULL (one float32 per stored outgoing entry)");
+    if ((d_edge_u == nullptr) != (d_edge_v == nullptr)) VGL_FAIL("msf_run: d_edge_u and d_edge_v go together (both or neither)");
+    vgl_sym_csr csr;
+    vgl_edge_ids ids;
+    bool built = false;
+    VGL_TRY(msf_ensure(c, g, &csr, &ids, &built));
+    const int32_t V = g->V;
+    const int64_t E = g->out.edges;
+    hipStream_t st = c->stream;
+    const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_MSF_SHORT", 32, 0, 1 << 20);
+    const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_MSF_WAVE", 1024, b_short, 1 << 24);
+    const int64_t chunk_env = vgl_env_int(c, "VGL_MSF_CHUNK", 16384, 16, 1 << 28);
+    vgl_hip_msf_stats out;
+    memset(&out, 0, sizeof(out));
+    out.prepared_now = built ? 1 : 0;
+    out.undirected_edges = ids.ne;
+    out.components = V;
+    const int32_t ne = (int32_t)ids.ne;
+
+    // the one host-visible read of a step: the counters through the pinned mirror
+    vgl_dev<unsigned long long> cnt;
+    VGL_TRY(cnt.alloc(st, MSF_NCNT));
+    VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * MSF_NCNT, st));
+    auto read = [&]() -> int {
+        const int64_t seq = vgl_next_seq(c);
+        {
+            vgl_timed_launch tl(c, "msf_publish");
+            hipLaunchKernelGGL(vgl_k_msf_publish, dim3(1), dim3(64), 0, st, (const unsigned long long *)cnt.p, (volatile int64_t *)c->h_counters, seq);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        return vgl_wait_counters(c, seq);
+    };
+
+    // ---- fold; the NaN check comes before any output is written ----
+    vgl_dev<uint32_t> wkey;
+    VGL_TRY(wkey.alloc(st, (size_t)ne));
+    if (ne > 0) {
+        VGL_HIP_TRY(hipMemsetAsync(wkey, 0xFF, sizeof(uint32_t) * (size_t)ne, st));
+        {
+            vgl_timed_launch tl(c, "msf_fold");
+            hipLaunchKernelGGL(vgl_k_msf_fold, dim3(msf_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, E, (const int32_t *)g->msf->slot_eid.p, d_weights, wkey.p, cnt.p);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(read());
+        if (c->h_counters[MSF_NAN] != 0) VGL_FAIL("msf_run: weights holds a NaN on an entry that is not a loop (the order of the edges needs numbers)");
+    }
+
+    if (V > 0 && ne == 0 && d_component) {
+        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, d_component);
+        VGL_HIP_TRY(hipGetLastError());
+    }
+    if (ne == 0) {
+        VGL_HIP_TRY(hipStreamSynchronize(st));
+        if (stats) *stats = out;
+        return 0;
+    }
+    if (d_edge_u) {
+        VGL_HIP_TRY(hipMemcpyAsync(d_edge_u, ids.eu, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
+        VGL_HIP_TRY(hipMemcpyAsync(d_edge_v, ids.ev, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
+    }
+    if (d_edge_weight) {
+        hipLaunchKernelGGL(vgl_k_msf_edge_weight, dim3(msf_grid(ne, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, ne, (const uint32_t *)wkey.p, d_edge_weight);
+        VGL_HIP_TRY(hipGetLastError());
+    }
+    VGL_HIP_TRY(hipMemsetAsync(d_in_forest, 0, (size_t)ne, st));
+
+    // ---- scratch of the call, all of it drawn before the loop ----
+    vgl_dev<int32_t> comp, parent, root, lists, stamp;
+    vgl_dev<unsigned long long> best;
+    vgl_dev<double> partials;
+    const int sum_grid = (int)msf_grid(ne, VGL_BLOCK, MSF_SUM_GRID);
+    VGL_TRY(comp.alloc(st, (size_t)V));
+    VGL_TRY(parent.alloc(st, (size_t)V));
+    VGL_TRY(root.alloc(st, (size_t)V));
+    VGL_TRY(best.alloc(st, (size_t)V));
+    VGL_TRY(partials.alloc(st, (size_t)sum_grid + 1));
+    VGL_HIP_TRY(hipMemsetAsync(best, 0xFF, sizeof(unsigned long long) * (size_t)V, st));      // MSF_NONE
+    hipLaunchKernelGGL(vgl_k_msf_count, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr.deg, b_short, b_wave, cnt.p);
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_TRY(read());
+    int64_t rows[MSF_NCLS], rows_total = 0;
+    for (int k = 0; k < MSF_NCLS; k++) {
+        rows[k] = c->h_counters[MSF_ROWS + k];
+        if (rows[k] < 0 || rows[k] > V) VGL_FAIL("msf_run: internal error (more rows in a class than vertices)");
+        rows_total += rows[k];
+    }
+    if (rows_total < 2 || rows_total > V) VGL_FAIL("msf_run: internal error (the classes do not add up to the rows that have an entry)");
+    VGL_TRY(lists.alloc(st, (size_t)(2 * rows_total)));
+    VGL_TRY(stamp.alloc(st, (size_t)rows[MSF_WG]));
+    VGL_HIP_TRY(hipMemsetAsync(stamp, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(rows[MSF_WG], 1), st));
+    msf_ring R[MSF_NCLS];
+    {
+        int64_t off = 0;
+        for (int k = 0; k < MSF_NCLS; k++) {
+            R[k].rows = lists.p + off;
+            R[k].cap = (uint32_t)(2 * rows[k]);
+            off += 2 * rows[k];
+        }
+    }
+    hipLaunchKernelGGL(vgl_k_msf_init, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr.deg, b_short, b_wave, comp.p, R[0], R[1], R[2], cnt.p);
+    VGL_HIP_TRY(hipGetLastError());
+
+    msf_graph mg;
+    mg.rowptr = csr.rowptr; mg.adj = csr.adj; mg.eid = ids.eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;
+    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(csr.max_deg, 1), MSF_MAX_CHUNKS));
+    const int32_t nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max(csr.max_deg, 1), chunk));
+    int64_t head[MSF_NCLS] = {0, 0, 0}, tail[MSF_NCLS] = {rows[0], rows[1], rows[2]}, picks = 0;
+    int32_t rounds = 0;
+    for (int32_t round = 1;; round++) {
+        if (round > MSF_MAX_ROUNDS) VGL_FAIL("msf_run: internal error (more rounds than a forest can take)");
+        // ---- the min-edge pass: a launch per class that has live rows ----
+        if (tail[MSF_SHORT] > head[MSF_SHORT]) {
+            const int64_t n = tail[MSF_SHORT] - head[MSF_SHORT];
+            vgl_timed_launch tl(c, "msf_min_short");
+            hipLaunchKernelGGL(vgl_k_msf_min_short, dim3(msf_grid(n * MSF_G, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_SHORT], (unsigned long long)head[MSF_SHORT], (int32_t)n, cnt.p);
+        }
+        if (tail[MSF_WAVE] > head[MSF_WAVE]) {
+            const int64_t n = tail[MSF_WAVE] - head[MSF_WAVE];
+            vgl_timed_launch tl(c, "msf_min_wave");
+            hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(msf_grid(n, VGL_WAVES)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WAVE], (unsigned long long)head[MSF_WAVE], (int32_t)n, cnt.p);
+        }
+        if (tail[MSF_WG] > head[MSF_WG]) {
+            const int64_t n = tail[MSF_WG] - head[MSF_WG];
+            vgl_timed_launch tl(c, "msf_min_wg");
+            hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(msf_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WG], (unsigned long long)head[MSF_WG], (int32_t)n, chunk,
+                               nchunks, round, stamp.p, cnt.p);
+        }
+        {
+            vgl_timed_launch tl(c, "msf_hook");
+            hipLaunchKernelGGL(vgl_k_msf_hook, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const unsigned long long *)best.p, ids.eu, ids.ev, parent.p,
+                               d_in_forest, cnt.p);
+        }
+        {
+            vgl_timed_launch tl(c, "msf_flatten");
+            hipLaunchKernelGGL(vgl_k_msf_chase, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)parent.p, root.p);
+        }
+        {
+            vgl_timed_launch tl(c, "msf_flatten");
+            hipLaunchKernelGGL(vgl_k_msf_relabel, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, comp.p, (const int32_t *)root.p, best.p);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(read());
+        int64_t live = 0;
+        for (int k = 0; k < MSF_NCLS; k++) {
+            const int64_t was = tail[k] - head[k];
+            head[k] = tail[k];
+            tail[k] = c->h_counters[MSF_TAIL + k];
+            if (tail[k] < head[k] || tail[k] - head[k] > was) VGL_FAIL("msf_run: internal error (a live list grew)");
+            live += tail[k] - head[k];
+        }
+        const int64_t now = c->h_counters[MSF_PICKS];
+        if (now < picks || now >= V) VGL_FAIL("msf_run: internal error (more forest edges than a forest has)");
+        if (now == picks) break;                                      // a round with no pick: every live row saw its own component only
+        picks = now;
+        rounds++;
+        if (live == 0) break;                                         // no row has a crossing entry left
+    }
+
+    // ---- the smallest vertex id of every component; the weight of the forest ----
+    if (d_component) {
+        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, root.p);
+        hipLaunchKernelGGL(vgl_k_msf_min_id, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, root.p);
+        hipLaunchKernelGGL(vgl_k_msf_component, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)root.p, d_component);
+        VGL_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(vgl_k_msf_sum_partials, dim3(sum_grid), dim3(VGL_BLOCK), 0, st, ne, (const uint8_t *)d_in_forest, (const uint32_t *)wkey.p, partials.p);
+    hipLaunchKernelGGL(vgl_k_msf_sum_final, dim3(1), dim3(VGL_BLOCK), 0, st, sum_grid, (const double *)partials.p, partials.p + sum_grid);
+    VGL_HIP_TRY(hipGetLastError());
+    double total = 0.0;
+    VGL_HIP_TRY(hipMemcpyAsync(&total, partials.p + sum_grid, sizeof(double), hipMemcpyDeviceToHost, st));
+    VGL_HIP_TRY(hipStreamSynchronize(st));
+    out.rounds = rounds;
+    out.forest_edges = picks;
+    out.components = V - picks;
+    out.entries_walked = c->h_counters[MSF_WALK];
+    out.algorithmic_bytes = 8 * E + 5 * (int64_t)ne + 12 * out.entries_walked + 20 * (int64_t)V * rounds;
+    out.total_weight = total;
+    if (stats) *stats = out;
+    return 0;
+}
+
+}  // extern "C"

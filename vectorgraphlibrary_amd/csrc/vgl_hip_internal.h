@@ -187,11 +187,13 @@ void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
 void vgl_bc_cache_free(struct vgl_bc_cache *p);  // bc.hip
 void vgl_kcore_cache_free(struct vgl_kcore_cache *p);  // kcore.hip
 void vgl_ktruss_cache_free(struct vgl_ktruss_cache *p);  // ktruss.hip
+void vgl_msf_cache_free(struct vgl_msf_cache *p);  // msf.hip
 struct vgl_lp_cache_delete { void operator()(struct vgl_lp_cache *p) const { vgl_lp_cache_free(p); } };      // (the types are complete in their files only)
 struct vgl_tri_cache_delete { void operator()(struct vgl_tri_cache *p) const { vgl_tri_cache_free(p); } };
 struct vgl_bc_cache_delete { void operator()(struct vgl_bc_cache *p) const { vgl_bc_cache_free(p); } };
 struct vgl_kcore_cache_delete { void operator()(struct vgl_kcore_cache *p) const { vgl_kcore_cache_free(p); } };
 struct vgl_ktruss_cache_delete { void operator()(struct vgl_ktruss_cache *p) const { vgl_ktruss_cache_free(p); } };
+struct vgl_msf_cache_delete { void operator()(struct vgl_msf_cache *p) const { vgl_msf_cache_free(p); } };
 struct vgl_hip_graph {
     uint64_t uid = 0;                // unique per created handle (a freed handle's address may be reused: caches key on this, not on the pointer)
     int32_t V = 0, row_begin = 0, row_end = 0, nrows = 0;
@@ -238,6 +240,7 @@ struct vgl_hip_graph {
     std::unique_ptr<struct vgl_bc_cache, vgl_bc_cache_delete> bc;      // betweenness centrality: the row classes of both directions (bc.hip, lazy, owned)
     std::unique_ptr<struct vgl_kcore_cache, vgl_kcore_cache_delete> kcore;   // k-core decomposition: the symmetric simple CSR and its degrees (kcore.hip, lazy, owned)
     std::unique_ptr<struct vgl_ktruss_cache, vgl_ktruss_cache_delete> ktruss;   // k-truss decomposition: edge ids of the symmetric CSR's slots and the edge endpoints (ktruss.hip, lazy, owned)
+    std::unique_ptr<struct vgl_msf_cache, vgl_msf_cache_delete> msf;   // minimum spanning forest: the undirected edge id of every STORED outgoing entry (msf.hip, lazy, owned)
 };
 // The symmetric simple CSR of the graph (rows ascending by id; the arrays belong to the handle's kcore cache and live as long as the handle), built
 // by this call when the handle has none yet (built_now).  kcore.hip owns the builder; ktruss.hip reads the CSR through this.
@@ -251,6 +254,16 @@ struct vgl_sym_csr {
     bool built_now = false;
 };
 int vgl_kcore_sym_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *out);      // kcore.hip
+// The library's numbering of the undirected edges of that CSR (the arrays belong to the handle's ktruss cache and live as long as the handle), built by
+// this call -- and the symmetric CSR under it -- when the handle has none yet (built_now).  ktruss.hip owns the builder; msf.hip reads it through this.
+struct vgl_edge_ids {
+    int64_t ne = 0;                  // E'
+    const int32_t *eid = nullptr;    // 2 E': the edge of every slot of the symmetric CSR
+    const int32_t *eu = nullptr;     // E': lo
+    const int32_t *ev = nullptr;     // E': hi
+    bool built_now = false;
+};
+int vgl_ktruss_edge_ids(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *out);      // ktruss.hip
 
 struct vgl_hip_frontier {
     vgl_hip_graph *g = nullptr;

@@ -67,6 +67,11 @@ class KtrussStats(C.Structure):
                 ("peel_elements", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class MsfStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("prepared_now", C.c_int32), ("forest_edges", C.c_int64), ("components", C.c_int64),
+                ("undirected_edges", C.c_int64), ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64), ("total_weight", C.c_double)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -153,6 +158,8 @@ _SIGNATURES = {
     "vgl_hip_kcore_run": [_p, _p, _i32, _p, _p, C.POINTER(KcoreStats)],
     "vgl_hip_ktruss_prepare": [_p, _p, C.POINTER(_i64)],
     "vgl_hip_ktruss_run": [_p, _p, _i32, _p, _p, _p, _p, C.POINTER(KtrussStats)],
+    "vgl_hip_msf_prepare": [_p, _p, C.POINTER(_i64)],
+    "vgl_hip_msf_run": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(MsfStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
