@@ -489,7 +489,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int32
  *             d_truss = min(truss, k_limit).  1 or negative: an error.
  *   The answer does not depend on the vertex order used internally, on any VGL_KTRUSS_* switch, on the order of the entries in a row or on the order in
  *   which the atomics land: truss numbers are integers and unique.
- * Method: vgl_hip_ktruss_prepare (or the first run) takes the symmetric simple CSR of `kcore` (built if the handle has none; the two share it) and adds
+ * Method: vgl_hip_ktruss_prepare (or the first run) takes the handle's symmetric simple CSR (built if the handle has none; kcore, ktruss and msf share it) and adds
  * eid (int32 per adjacency slot: the edge id) and the endpoint arrays, cached on the handle and freed with it; *undirected_edges (host, may be NULL)
  * receives E'.  A run computes the initial support in one pass without atomics on the supports (per edge the SHORTER of the two full rows is walked,
  * each entry searched in the longer), then peels level-synchronously: k = the smallest support of an alive edge + 2 (a device reduction, no walk through
@@ -544,7 +544,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t k_limit, int3
  *             them to completion before the next round.  With the strict order this is a function of the graph and the weights alone: rounds is
  *             exact, 0 when E' = 0, at most ceil(log2 V).
  *   The answer does not depend on the order of the entries in a row, on any VGL_MSF_* switch or on the order in which the atomics land.
- * Method: vgl_hip_msf_prepare (or the first run) takes the symmetric simple CSR of `kcore` and the edge ids of `ktruss` (built if the handle has none)
+ * Method: vgl_hip_msf_prepare (or the first run) takes the handle's symmetric simple CSR and the edge ids of its slots (built if the handle has none; shared with kcore and ktruss)
  * and adds slot_eid, int32 per STORED outgoing entry: its undirected edge, -1 for a loop (a binary search of the entry in its symmetric row); cached on
  * the handle and freed with it; *undirected_edges (host, may be NULL) receives E'.  Structure is per graph, values are per weights: a run folds the
  * weights in one streaming pass (the float as an order-preserving uint32 -- -0.0 canonicalised, the sign bit flipped, negatives complemented -- and

@@ -136,6 +136,47 @@ def test_every_class_with_shrunk_thresholds(ctx, monkeypatch):
     g.close()
 
 
+def test_sort_cap_zero_makes_every_row_a_piece(ctx, monkeypatch):
+    """VGL_KCORE_SORT_CAP_MB=0 leaves one key per piece: every row with a key exceeds it and is sorted as a piece of its own.  The 64-vertex golden
+    graph, stored in both directions.  Core numbers and degrees, truss numbers with the edge endpoints (the numbering of the edges needs the rows
+    sorted ACROSS the pieces) and the forest under fixed weights: equal to the references, and bit for bit what a handle built under the default
+    cap returns."""
+    import ktruss_reference as KT
+    import msf_reference as MR
+    A = api()
+    raw = open(os.path.join(ROOT, "tests", "golden", "rmat_s6_e8_seed1.el_container"), "rb").read()
+    V, E = int(np.frombuffer(raw, np.int32, 1, 0)[0]), int(np.frombuffer(raw, np.int64, 1, 4)[0])
+    src, dst = np.frombuffer(raw, np.int32, E, 16), np.frombuffer(raw, np.int32, E, 16 + 4 * E)
+    assert V == 64
+    s2, d2 = np.concatenate([src, dst]), np.concatenate([dst, src])
+    w = ((np.arange(2 * E, dtype=np.int64) * 7919) % 97 + 1).astype(np.float32)      # fixed; the two directions of an edge differ: the smaller counts
+    core = R.core_numbers(V, s2, d2)
+    eu, ev, truss, support = KT.truss_numbers(V, s2, d2)[:4]
+    forest = MR.minimum_spanning_forest(V, s2, d2, w)
+
+    def run(what):
+        g = A.Graph.from_coo(ctx, V, *coo(ctx, s2, d2), with_incoming=False, want_perm=True)
+        kc = assert_equals_reference(g, core, what)
+        assert kc["prepared_now"] == 1
+        _, kt = A.truss_numbers(g, support=True)
+        total, ms = A.minimum_spanning_forest(g, ctx.gather_u32(g.perm, torch.tensor(w, device=ctx.device)), component=True, raw=True)
+        g.close()
+        assert np.array_equal(kt["edges"].cpu().numpy(), np.stack([eu, ev], axis=1)), what
+        assert np.array_equal(kt["truss"].cpu().numpy(), truss) and np.array_equal(kt["support"].cpu().numpy(), support), what
+        assert np.array_equal(ms["all_edges"].cpu().numpy(), np.stack([forest["edge_u"], forest["edge_v"]], axis=1)), what
+        assert np.array_equal(ms["edge_weight"].cpu().numpy(), forest["edge_w"]) and np.array_equal(ms["in_forest"].cpu().numpy(), forest["forest"]), what
+        assert np.array_equal(ms["component"].cpu().numpy(), forest["component"]) and total == forest["total"], what      # integer-valued weights: exact
+        return kc, kt, ms
+
+    default = run("default cap")
+    monkeypatch.setenv("VGL_KCORE_SORT_CAP_MB", "0")
+    pieces = run("one piece per row")
+    for a, b in zip(default, pieces):
+        assert a.keys() == b.keys()
+        for k in a:
+            assert torch.equal(a[k], b[k]) if torch.is_tensor(a[k]) else a[k] == b[k], k
+
+
 def test_star_contention_on_the_hub(ctx):
     """100 000 leaves decrement one address; the hub crosses k + 1 -> k once, every later decrement is put back"""
     A = api()

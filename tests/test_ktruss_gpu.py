@@ -129,28 +129,47 @@ def test_every_class_with_shrunk_thresholds(ctx, monkeypatch):
     g.close()
 
 
-@pytest.mark.parametrize("first", ["kcore", "ktruss"])
+@pytest.mark.parametrize("first", ["kcore", "ktruss", "msf"])
 def test_kcore_and_ktruss_share_the_symmetric_csr(first, ctx):
+    """kcore, ktruss and msf on one handle, each of them first once: the symmetric CSR is built once, and prepared_now is 1 only for the caller
+    that built its own stage (kcore: the CSR, ktruss: the edge numbering, msf: the edge of every stored entry)"""
     import kcore_reference as KR
+    import msf_reference as MR
     A = api()
     V = 1 << 10
     src, dst, ref = generated(ctx, "rmat", 10, 16, 1)
     core = KR.core_numbers(V, src.cpu().numpy(), dst.cpu().numpy())
-    g = A.Graph.from_coo(ctx, V, src, dst)
+    w = ctx.gen_weights(src.numel(), 1)
+    forest = MR.minimum_spanning_forest(V, src.cpu().numpy(), dst.cpu().numpy(), w.cpu().numpy())
+    g = A.Graph.from_coo(ctx, V, src, dst, want_perm=True)
+    w_csr = ctx.gather_u32(g.perm, w)
     ctx.timing(True)
     if first == "kcore":
         _, kc = A.core_numbers(g, degree=True)
         kt = assert_equals_reference(g, ref, "after kcore")
         assert kc["prepared_now"] == 1 and kt["prepared_now"] == 1              # each built what is its own: the CSR / the edge numbering
-    else:
+        _, ms = A.minimum_spanning_forest(g, w_csr, component=True, raw=True)
+        assert ms["prepared_now"] == 1                                           # ... / the edge of every stored entry
+    elif first == "ktruss":
         kt = assert_equals_reference(g, ref, "before kcore")
         _, kc = A.core_numbers(g, degree=True)
         assert kt["prepared_now"] == 1 and kc["prepared_now"] == 0
+        _, ms = A.minimum_spanning_forest(g, w_csr, component=True, raw=True)
+        assert ms["prepared_now"] == 1
+    else:
+        _, ms = A.minimum_spanning_forest(g, w_csr, component=True, raw=True)
+        kt = assert_equals_reference(g, ref, "after msf")
+        _, kc = A.core_numbers(g, degree=True)
+        assert ms["prepared_now"] == 1 and kt["prepared_now"] == 0 and kc["prepared_now"] == 0      # msf built all three stages
     built = ctx.timing_get("kcore_csr")[0]
     ctx.timing(False)
-    assert built == 1, built                                                     # the symmetric CSR was built once for the two of them
+    assert built == 1, built                                                     # the symmetric CSR was built once for the three of them
     assert np.array_equal(kc["core"].cpu().numpy(), core[0]) and np.array_equal(kc["degree"].cpu().numpy(), core[1])
     assert kc["undirected_edges"] == kt["undirected_edges"] == core[2]
+    assert ms["undirected_edges"] == core[2] and ms["forest_edges"] == forest["forest_edges"] and ms["rounds"] == forest["rounds"]
+    assert np.array_equal(ms["all_edges"].cpu().numpy(), np.stack([forest["edge_u"], forest["edge_v"]], axis=1))
+    assert np.array_equal(ms["edge_weight"].cpu().numpy(), forest["edge_w"]) and np.array_equal(ms["in_forest"].cpu().numpy(), forest["forest"])
+    assert np.array_equal(ms["component"].cpu().numpy(), forest["component"])
     g.close()
 
 

@@ -111,6 +111,31 @@ def test_every_class_with_shrunk_thresholds(ctx, monkeypatch):
     g.close()
 
 
+def test_sort_cap_zero_makes_every_row_a_piece(ctx, monkeypatch):
+    """VGL_TRI_SORT_CAP_MB=0 leaves one key per piece: every row with a key exceeds it and is sorted as a piece of its own.  The 64-vertex golden
+    graph, stored in both directions: equal to the reference, and bit for bit what a handle built under the default cap returns."""
+    A = api()
+    raw = open(os.path.join(ROOT, "tests", "golden", "rmat_s6_e8_seed1.el_container"), "rb").read()
+    V, E = int(np.frombuffer(raw, np.int32, 1, 0)[0]), int(np.frombuffer(raw, np.int64, 1, 4)[0])
+    src, dst = np.frombuffer(raw, np.int32, E, 16), np.frombuffer(raw, np.int32, E, 16 + 4 * E)
+    assert V == 64
+    both = coo(ctx, np.concatenate([src, dst]), np.concatenate([dst, src]))
+    ref = R.triangle_count(V, src, dst)
+    g = A.Graph.from_coo(ctx, V, *both, with_incoming=False)
+    T0, st0 = A.triangle_count(g, clustering=True)
+    g.close()
+    monkeypatch.setenv("VGL_TRI_SORT_CAP_MB", "0")
+    g = A.Graph.from_coo(ctx, V, *both, with_incoming=False)
+    T1, st1 = A.triangle_count(g, clustering=True)
+    assert st0["prepared_now"] == 1 and st1["prepared_now"] == 1
+    assert_equals_reference(g, ref, "one piece per row")
+    g.close()
+    assert T1 == T0 == ref[0]
+    for k in ("per_vertex", "degree", "clustering"):
+        assert torch.equal(st0[k], st1[k]), k
+    assert {k: v for k, v in st0.items() if not torch.is_tensor(v)} == {k: v for k, v in st1.items() if not torch.is_tensor(v)}
+
+
 def test_clique_3000_exceeds_32_bits(ctx):
     """K_3000: C(3000, 3) = 4 495 501 000 > 2^32 triangles, C(2999, 2) per vertex"""
     A = api()

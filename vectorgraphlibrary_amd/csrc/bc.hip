@@ -35,7 +35,6 @@ enum { BC_C_FWD = 0, BC_C_BWD = 1, BC_C_OVERFLOW = 2, BC_NCNT = 3 };
 struct bc_bounds { int32_t shrt, wave, wg; };
 __host__ __device__ inline int bc_class_of(int64_t d, bc_bounds b) { return d <= b.shrt ? BC_SHORT : d <= b.wave ? BC_WAVE : d <= b.wg ? BC_WG : BC_HUB; }
 
-__device__ __forceinline__ void bc_add64(int64_t *p, int64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
 
 // ---- prepare: the class of every row of one direction, the class sizes and the longest row ----
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_classify(int32_t V, const int64_t *rowptr, bc_bounds b, uint8_t *cls, int32_t *sizes, unsigned long long *max_row)
@@ -73,7 +72,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_count(int32_t V, int32_t p
     for (int64_t v = v0 + threadIdx.x; v < v1; v += VGL_BLOCK) {
         const int32_t l = levels[v];
         if (l <= 0) continue;
-        if (l > level_cap) { bc_add64(cnt + BC_C_OVERFLOW, 1); continue; }
+        if (l > level_cap) { vgl_atomic_add64(cnt + BC_C_OVERFLOW, 1); continue; }
         const int key = (l - 1) * BC_NCLS + cls[v];
         if (LDS) atomicAdd(&s_h[key], 1); else atomicAdd(hist + key, 1);
     }
@@ -135,8 +134,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_scatter(int32_t V, int32_t
     ef = vgl_block_reduce_add(ef, s_red);
     eb = vgl_block_reduce_add(eb, s_red);
     if (threadIdx.x == 0) {
-        if (ef) bc_add64(cnt + BC_C_FWD, ef);
-        if (eb) bc_add64(cnt + BC_C_BWD, eb);
+        if (ef) vgl_atomic_add64(cnt + BC_C_FWD, ef);
+        if (eb) vgl_atomic_add64(cnt + BC_C_BWD, eb);
     }
 }
 
@@ -278,7 +277,7 @@ struct vgl_bc_cache {
     int32_t chunk = 0;
 };
 
-void vgl_bc_cache_free(vgl_bc_cache *p) { delete p; }
+template <> void vgl_cache_free(vgl_bc_cache *p) { delete p; }
 
 namespace {
 

@@ -1085,7 +1085,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_apply_fold(int n, const int64
     if (threadIdx.x == 0) { counters[C_TMP0] = a; counters[C_TMP1] = b; }
 }
 
-static inline unsigned vgl_grid(int64_t n, int64_t cap = 8192) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(n, VGL_BLOCK))); }
 
 // vgl_k_td_expand<EMIT, COUNT, filter> over the frontier ids / offs (F vertices, M edges, tile_first ready); a counting launch leaves F and M of
 // the next frontier in the device counters
@@ -1105,7 +1104,7 @@ static int vgl_bfs_td_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_
                              bool have_tile_first, bool count = false, bool filter = true)
 {
     if (F <= 0 || M <= 0) return 0;
-    if (!have_tile_first) hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F)), dim3(VGL_BLOCK), 0, c->stream, F, g->offs, g->tile_first);
+    if (!have_tile_first) hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, F, g->offs, g->tile_first);
     {
         vgl_timed_launch tl(c, "bfs_top_down");
         if (emit && count) vgl_td_expand_launch<true, true>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
@@ -1480,7 +1479,7 @@ struct vgl_bfs_traversal {
         int64_t seq = 0;
         trace("-> bottom-up");
         VGL_TRY(vgl_bfs_bu_launch(c, g, levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq));
-        hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited, g->bm_front, g->bm_next);
+        hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited, g->bm_front, g->bm_next);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_wait_counters(c, seq));
         st.bu_steps++; st.edges_examined += c->h_counters[C_BU_EDGES];
@@ -1493,7 +1492,7 @@ struct vgl_bfs_traversal {
 
     int run(int32_t source)
     {
-        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(V)), dim3(VGL_BLOCK), 0, c->stream, V, source, levels, words, g->bm_visited, g->bm_front,
+        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, V, source, levels, words, g->bm_visited, g->bm_front,
                            g->bm_next, g->tickets, list_count);
         t0 = std::chrono::steady_clock::now();
         if (p.small_m > 0) {                                                // level 1 = {source}
@@ -1561,7 +1560,7 @@ int vgl_hip_bfs_init(vgl_hip_ctx *c, int32_t V, int32_t source, int32_t *d_level
 {
     if (!c || !d_levels) VGL_FAIL("bfs_init: null argument");
     if (source < 0 || source >= V) VGL_FAIL("bfs_init: source vertex out of range");
-    hipLaunchKernelGGL(vgl_k_bfs_init, dim3(vgl_grid(V)), dim3(VGL_BLOCK), 0, c->stream, V, source, d_levels);
+    hipLaunchKernelGGL(vgl_k_bfs_init, dim3(vgl_grid(V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, V, source, d_levels);
     VGL_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1596,7 +1595,7 @@ int vgl_hip_bfs_step_top_down(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_level
     // visited bitmap over ALL vertices (destinations may live in any shard): the caller's replicated one, or rebuilt here
     const uint64_t *visited = d_visited_bits;
     if (!visited) {
-        hipLaunchKernelGGL(vgl_k_levels_to_bitmap<true>, dim3(vgl_grid(g->V)), dim3(VGL_BLOCK), 0, c->stream, g->V, d_levels, -1,
+        hipLaunchKernelGGL(vgl_k_levels_to_bitmap<true>, dim3(vgl_grid(g->V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, g->V, d_levels, -1,
                            g->bm_visited);
         visited = g->bm_visited;
     }
@@ -1606,7 +1605,7 @@ int vgl_hip_bfs_step_top_down(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_level
     if (local_frontier) *local_frontier = F;
     if (local_edges) *local_edges = M;
     if (F > 0 && M > 0) {
-        hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F)), dim3(VGL_BLOCK), 0, c->stream, (int32_t)F, g->offs, g->tile_first);
+        hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, (int32_t)F, g->offs, g->tile_first);
         vgl_timed_launch tl(c, "bfs_top_down");
         vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, visited, d_levels, level + 1, nullptr);
     }
@@ -1638,7 +1637,7 @@ int vgl_hip_bfs_step_top_down_bits(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_
     }
     if (!emit) {
         vgl_timed_launch tl(c, "gnf");
-        hipLaunchKernelGGL(vgl_k_levels_to_bitmap<false>, dim3(vgl_grid(g->V)), dim3(VGL_BLOCK), 0, c->stream, g->V, (const int32_t *)d_levels, level + 1, d_next_bits);
+        hipLaunchKernelGGL(vgl_k_levels_to_bitmap<false>, dim3(vgl_grid(g->V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, g->V, (const int32_t *)d_levels, level + 1, d_next_bits);
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;
@@ -1665,7 +1664,7 @@ int vgl_hip_bitmap_or_parts(vgl_hip_ctx *c, int64_t words, int parts, const uint
 {
     if (!c || !d_in || !d_out) VGL_FAIL("bitmap_or_parts: null argument");
     if (words < 0 || parts < 1) VGL_FAIL("bitmap_or_parts: bad size");
-    if (words > 0) hipLaunchKernelGGL(vgl_k_bitmap_or_parts, dim3(vgl_grid(words)), dim3(VGL_BLOCK), 0, c->stream, words, parts, d_in, d_out);
+    if (words > 0) hipLaunchKernelGGL(vgl_k_bitmap_or_parts, dim3(vgl_grid(words, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, words, parts, d_in, d_out);
     VGL_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1673,7 +1672,7 @@ int vgl_hip_bitmap_or_parts(vgl_hip_ctx *c, int64_t words, int parts, const uint
 int vgl_hip_levels_to_bitmap(vgl_hip_ctx *c, int32_t V, const int32_t *d_levels, int32_t level, uint64_t *d_bits)
 {
     if (!c || !d_levels || !d_bits) VGL_FAIL("levels_to_bitmap: null argument");
-    hipLaunchKernelGGL(vgl_k_levels_to_bitmap<false>, dim3(vgl_grid(V)), dim3(VGL_BLOCK), 0, c->stream, V, d_levels, level, d_bits);
+    hipLaunchKernelGGL(vgl_k_levels_to_bitmap<false>, dim3(vgl_grid(V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, V, d_levels, level, d_bits);
     VGL_HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1690,7 +1689,7 @@ int vgl_hip_bfs_apply_ids(vgl_hip_ctx *c, int32_t V, int parts, int32_t cap, con
 {
     if (!c || !d_lists || !d_levels || !d_visited_bits || !d_front_bits) VGL_FAIL("bfs_apply_ids: null argument");
     if (parts < 1 || cap < 1) VGL_FAIL("bfs_apply_ids: parts and cap must be >= 1");
-    const int nb = (int)vgl_grid((int64_t)parts * cap, 256);
+    const int nb = (int)vgl_grid((int64_t)parts * cap, VGL_BLOCK, 256);
     VGL_TRY(vgl_ensure_partials(c, (size_t)nb * 2 + 2));
     int64_t *partials = reinterpret_cast<int64_t *>(c->d_partials);
     VGL_HIP_TRY(hipMemsetAsync(d_front_bits, 0, sizeof(uint64_t) * (size_t)vgl_ceil_div(V, 64), c->stream));      // the new frontier is these vertices only
@@ -1732,7 +1731,7 @@ static int vgl_bfs_apply_bitmaps_range(vgl_hip_ctx *c, int32_t V, int parts, con
 {
     if (!c || !d_bits_all || !d_levels) VGL_FAIL("bfs_apply_bitmaps: null argument");
     if (parts < 1) VGL_FAIL("bfs_apply_bitmaps: parts must be >= 1");
-    const int nb = (int)vgl_grid(vgl_ceil_div(V, 64), 1024);
+    const int nb = (int)vgl_grid(vgl_ceil_div(V, 64), VGL_BLOCK, 1024);
     VGL_TRY(vgl_ensure_partials(c, (size_t)nb * 2 + 2));
     int64_t *partials = reinterpret_cast<int64_t *>(c->d_partials);
     hipLaunchKernelGGL(vgl_k_apply_bitmaps, dim3(nb), dim3(VGL_BLOCK), 0, c->stream, V, parts, vgl_ceil_div(V, 64), d_bits_all,

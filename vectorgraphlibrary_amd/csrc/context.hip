@@ -297,9 +297,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_fold_shards(int64_t *shards, 
 // One wavefront copies the counter slots into pinned host memory and then publishes a sequence number with system scope.
 // The host spins on the sequence number: a few microseconds after the producing kernels finish, instead of a
 // hipMemcpyAsync (blit/SDMA setup) + hipStreamSynchronize round trip per BFS level / SSSP step.
-__global__ void vgl_k_publish(const int64_t *counters, volatile int64_t *host, int64_t seq)
+__global__ void vgl_k_publish_counters(const unsigned long long *cnt, int n, volatile int64_t *host, int64_t seq)
 {
-    if (threadIdx.x < C_NSLOTS) host[threadIdx.x] = counters[threadIdx.x];
+    if ((int)threadIdx.x < n) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
@@ -309,7 +309,17 @@ int vgl_read_counters(vgl_hip_ctx *c, bool fold_shards)
 {
     if (fold_shards) hipLaunchKernelGGL(vgl_k_fold_shards, dim3(1), dim3(VGL_BLOCK), 0, c->stream, c->d_shards, c->d_counters);
     const int64_t seq = ++c->publish_seq;
-    hipLaunchKernelGGL(vgl_k_publish, dim3(1), dim3(64), 0, c->stream, c->d_counters, (volatile int64_t *)c->h_counters, seq);
+    hipLaunchKernelGGL(vgl_k_publish_counters, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)c->d_counters, (int)C_NSLOTS, (volatile int64_t *)c->h_counters, seq);
+    VGL_HIP_TRY(hipGetLastError());
+    return vgl_wait_counters(c, seq);
+}
+int vgl_publish_counters(vgl_hip_ctx *c, const char *slot, const unsigned long long *cnt, int n)
+{
+    const int64_t seq = ++c->publish_seq;
+    {
+        vgl_timed_launch tl(c, slot);
+        hipLaunchKernelGGL(vgl_k_publish_counters, dim3(1), dim3(64), 0, c->stream, cnt, n, (volatile int64_t *)c->h_counters, seq);
+    }
     VGL_HIP_TRY(hipGetLastError());
     return vgl_wait_counters(c, seq);
 }

@@ -1,9 +1,8 @@
 // kcore.hip -- k-core decomposition (core numbers, degeneracy, undirected degrees) of the simple undirected graph underlying the stored outgoing CSR.
 // The contract is written out in include/vgl_hip.h; DESIGN section 15 has the schedule, the kernel resources and the bytes model.
 //
-// Prepare (once per graph, cached on the handle): every stored entry (u, v), u != v, gives the 64-bit keys  u << 32 | v  and  v << 32 | u;  the keys are
-// sorted (rocprim radix sort) and deduplicated (rocprim unique), in pieces of consecutive rows when all of them would need more scratch than
-// VGL_KCORE_SORT_CAP_MB.  The sorted keys ARE the symmetric CSR: row = high half, entry = low half.  degree = row length.
+// Prepare (once per graph, cached on the handle): the symmetric simple CSR of simple.hip (vgl_simple_ensure_csr), shared with ktruss and msf.
+// degree = row length.
 //
 // Peel (level-synchronous; deg = a working copy of the degrees; a vertex is alive while deg > the last finished k):
 //   k change   k = min over the alive vertices of deg (a device reduction: never a walk through empty shells); the alive vertices with deg <= k are
@@ -17,12 +16,10 @@
 // changes while the vertices to scan are few (the whole graph, or the compacted list of the alive ones) -- until the work grows past the bound
 // or the graph is exhausted, and reports through the pinned mirror what it did.  No cooperative launch, no workgroup waits for another.
 // The host reads the pinned mirror once per sub-round of the large path (list tails, entry total, k); no allocation inside the loop.
-#include "vgl_hip_internal.h"
+#include "vgl_simple.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <climits>
-#include <vector>
 
 namespace {
 
@@ -61,98 +58,8 @@ struct kc_graph {
     kc_lists L;
 };
 
-// ---- prepare ----
-__device__ __forceinline__ int32_t kc_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
-{
-    int32_t lo = 0, hi = V;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if (rp[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-// keys per row of the symmetric CSR before deduplication (only when the keys do not fit one piece)
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_count_rows(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, int32_t *per_row)
-{
-    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t u = kc_row_of(rp, V, e), v = adj[e];
-        if (u == v || v < 0 || v >= V) continue;
-        atomicAdd(per_row + u, 1);
-        atomicAdd(per_row + v, 1);
-    }
-}
-// the keys whose row is in [v0, v1), appended in any order (the sort follows); never more than cap are written
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_emit(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, int32_t v0, int32_t v1, uint64_t *keys,
-                                                               unsigned long long *n_keys, int64_t cap)
-{
-    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t u = kc_row_of(rp, V, e), v = adj[e];
-        if (u == v || v < 0 || v >= V) continue;
-        if (u >= v0 && u < v1) {
-            const unsigned long long pos = atomicAdd(n_keys, 1ull);
-            if ((int64_t)pos < cap) keys[pos] = (uint64_t)(uint32_t)u << 32 | (uint32_t)v;
-        }
-        if (v >= v0 && v < v1) {
-            const unsigned long long pos = atomicAdd(n_keys, 1ull);
-            if ((int64_t)pos < cap) keys[pos] = (uint64_t)(uint32_t)v << 32 | (uint32_t)u;
-        }
-    }
-}
-// sorted unique keys of the piece -> entries [base, base + n) of the adjacency
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_fill(const uint64_t *keys, int64_t n, int64_t base, int32_t *adj, int64_t adj_cap)
-{
-    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK)
-        if (base + i < adj_cap) adj[base + i] = (int32_t)(uint32_t)keys[i];
-}
-// rowptr[r] = base + (keys of the piece below row r), r in [v0, v1]
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_rowptr(const uint64_t *keys, int64_t n, int32_t v0, int32_t v1, int64_t base, int64_t *rowptr)
-{
-    for (int64_t r = v0 + (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; r <= v1; r += (int64_t)gridDim.x * VGL_BLOCK) {
-        const uint64_t first = (uint64_t)r << 32;
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (keys[mid] < first) lo = mid + 1; else hi = mid;
-        }
-        rowptr[r] = base + lo;
-    }
-}
-// deg[v] = length of row v; the longest row
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_degrees(int32_t V, const int64_t *rowptr, int32_t *deg, int32_t *max_deg)
-{
-    int m = 0;
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int d = (int)(rowptr[v + 1] - rowptr[v]);
-        deg[v] = d;
-        m = max(m, d);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-    if (vgl_lane() == 0 && m) atomicMax(max_deg, m);
-}
-
 // ---- the peel: shared device pieces ----
-// Every lane of the wave calls (uniform control flow).  The lanes with `want` append u to the list of class `cls`: one returning atomic per wave
-// and class.  tail: the three cumulative list lengths, in global memory (large path) or in LDS (one-workgroup kernel).
-__device__ __forceinline__ void kc_append(bool want, int32_t u, int cls, const kc_lists &L, unsigned long long *tail)
-{
-    if (!__any(want)) return;
-    const int lane = vgl_lane();
-#pragma unroll
-    for (int c = 0; c < KC_NCLS; c++) {
-        const bool mine = want && cls == c;
-        const unsigned long long m = __ballot(mine);
-        if (!m) continue;                                             // (uniform)
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(tail + c, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (mine) {
-            const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (pos < (unsigned long long)L.cap) vgl_store_agent(L.list[c] + pos, u);
-        }
-    }
-}
+// (appends: vgl_wave_append, one returning atomic per wave and class; tail: the three cumulative list lengths, in global memory or in LDS)
 // One adjacency entry u of a vertex expanded at level k (active = this lane holds one).  deg[u] crosses k + 1 -> k exactly once: while it is above k
 // it only falls; once it is at or below k every decrement that lands sees old <= k and is put back, so the value never returns to k + 1 and the
 // append below happens in one thread.  A stale deg[u] can only be too large (the pre-check reads at device scope anyway), which costs an atomic.
@@ -169,7 +76,7 @@ __device__ __forceinline__ void kc_relax(bool active, int32_t u, int32_t k, cons
             m_acc += len;
         } else if (old <= k) atomicAdd(g.deg + u, 1);
     }
-    kc_append(want, u, cls, g.L, tail);
+    vgl_wave_append<KC_NCLS>(want, u, cls, g.L.list, g.L.cap, tail);
 }
 // the entries [lo, hi) of one row, `stride` lanes of which this is lane `li`; uniform over the wave as long as every lane of the wave calls
 __device__ __forceinline__ void kc_walk(int64_t lo, int64_t hi, int li, int stride, int32_t k, const kc_graph &g, unsigned long long *tail, int64_t &m_acc)
@@ -181,11 +88,6 @@ __device__ __forceinline__ void kc_walk(int64_t lo, int64_t hi, int li, int stri
         kc_relax(active, u, k, g, tail, m_acc);
         e += stride;
     }
-}
-__device__ __forceinline__ void kc_flush_m(unsigned long long *cnt, int64_t m)      // every lane of the wave, once, at the end of a kernel
-{
-    m = vgl_wave_reduce_add(m);
-    if (vgl_lane() == 0 && m) atomicAdd(cnt + KC_M, (unsigned long long)m);
 }
 
 // ---- the peel: large path ----
@@ -223,9 +125,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_scan(const int32_t *ids
                 m_acc += len;
             }
         }
-        kc_append(want, v, cls, g.L, cnt + KC_TAIL);
+        vgl_wave_append<KC_NCLS>(want, v, cls, g.L.list, g.L.cap, cnt + KC_TAIL);
     }
-    kc_flush_m(cnt, m_acc);
+    vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 // the alive vertices, compacted (once, when few are left: the scans of the dense tail then read this list and not V degrees)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_compact(int32_t V, const int32_t *deg, int32_t k_prev, int32_t *alive, int32_t cap, unsigned long long *cnt)
@@ -235,7 +137,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_compact(int32_t V, cons
     L.cap = cap;
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t v = base + threadIdx.x;
-        kc_append(v < V && deg[v] > k_prev, (int32_t)v, 0, L, cnt + KC_ALIVE);
+        vgl_wave_append<KC_NCLS>(v < V && deg[v] > k_prev, (int32_t)v, 0, L.list, L.cap, cnt + KC_ALIVE);
     }
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_short(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
@@ -249,7 +151,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_short(kc_graph g, const
         if (gi == 0) g.core[v] = k;
     }
     kc_walk(lo, hi, gi, KC_G, k, g, cnt + KC_TAIL, m_acc);
-    kc_flush_m(cnt, m_acc);
+    vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wave(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
 {
@@ -259,7 +161,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wave(kc_graph g, const 
     int64_t m_acc = 0;
     if (vgl_lane() == 0) g.core[v] = k;
     kc_walk(g.rowptr[v], g.rowptr[v + 1], vgl_lane(), 64, k, g, cnt + KC_TAIL, m_acc);
-    kc_flush_m(cnt, m_acc);
+    vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 // workgroup (row blockIdx.x, chunk blockIdx.y): `chunk` entries of the row; a workgroup past the end of its row has nothing to do
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wg(kc_graph g, const int32_t *rows, int32_t chunk, int32_t k, unsigned long long *cnt)
@@ -270,21 +172,13 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wg(kc_graph g, const in
     if (lo >= end) return;                                            // (uniform over the workgroup)
     int64_t m_acc = 0;
     kc_walk(lo, min(end, lo + chunk), (int)threadIdx.x, VGL_BLOCK, k, g, cnt + KC_TAIL, m_acc);
-    kc_flush_m(cnt, m_acc);
+    vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 // the peel stopped at k_limit: what is still alive gets k_limit
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_fill_limit(int32_t V, const int32_t *deg, int32_t k_last, int32_t k_limit, int32_t *core)
 {
     for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK)
         if (deg[v] > k_last) core[v] = k_limit;
-}
-// the counters into the pinned mirror, then the sequence number (one wavefront)
-__global__ void vgl_k_kcore_publish(const unsigned long long *cnt, volatile int64_t *host, int64_t seq)
-{
-    if (threadIdx.x < KC_NCNT) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
 }
 
 // ---- the peel: small frontiers, ONE workgroup ----
@@ -346,7 +240,7 @@ __global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g
                         m_acc += len;
                     }
                 }
-                kc_append(want, v, cls, g.L, s_tail);
+                vgl_wave_append<KC_NCLS>(want, v, cls, g.L.list, g.L.cap, s_tail);
             }
             k = kn;
             rounds++;
@@ -407,135 +301,6 @@ __global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g
     }
 }
 
-unsigned kc_grid(int64_t work, int64_t per_block, int64_t cap = (int64_t)1 << 20) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
-
-}  // namespace
-
-// The symmetric simple CSR of a graph (cached on the handle, freed with it)
-struct vgl_kcore_cache {
-    int32_t V = 0;
-    int64_t nnz = 0;                             // 2 E'
-    vgl_dev<int64_t> rowptr;                     // V + 1
-    vgl_dev<int32_t> adj;                        // 2 E'
-    vgl_dev<int32_t> deg;                        // V: degree in the simple undirected graph
-    int32_t max_deg = 0;
-};
-
-void vgl_kcore_cache_free(vgl_kcore_cache *p) { delete p; }
-
-namespace {
-
-int kc_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, std::unique_ptr<vgl_kcore_cache, vgl_kcore_cache_delete> &out)
-{
-    const int32_t V = g->V;
-    const vgl_dir_csr &d = g->out;
-    const int64_t E = d.edges;
-    hipStream_t st = c->stream;
-    std::unique_ptr<vgl_kcore_cache> p(new vgl_kcore_cache());
-    p->V = V;
-    VGL_TRY(p->rowptr.alloc((size_t)V + 1));
-    VGL_TRY(p->deg.alloc((size_t)V));
-    VGL_HIP_TRY(hipMemsetAsync(p->rowptr, 0, sizeof(int64_t) * ((size_t)V + 1), st));
-    VGL_HIP_TRY(hipMemsetAsync(p->deg, 0, sizeof(int32_t) * (size_t)std::max(V, 1), st));
-    if (V > 0 && E > 0) {
-        // keys per piece: in + out buffers of 8 bytes each within the cap
-        const int64_t cap_keys = std::max<int64_t>(1, vgl_env_int(c, "VGL_KCORE_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
-        std::vector<int32_t> bounds{0, V};                            // pieces of consecutive rows
-        int64_t piece_keys = 2 * E;
-        if (2 * E > cap_keys) {
-            vgl_dev<int32_t> per_row;
-            VGL_TRY(per_row.alloc(st, (size_t)V));
-            VGL_HIP_TRY(hipMemsetAsync(per_row, 0, sizeof(int32_t) * (size_t)V, st));
-            hipLaunchKernelGGL(vgl_k_kcore_count_rows, dim3(kc_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, per_row.p);
-            VGL_HIP_TRY(hipGetLastError());
-            std::vector<int32_t> h((size_t)V);
-            VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_row, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-            per_row.reset();
-            bounds.assign(1, 0);
-            int64_t acc = 0;
-            piece_keys = 0;
-            for (int32_t v = 0; v < V; v++) {                         // greedy; a row with more keys than the cap is a piece of its own
-                if (acc > 0 && acc + h[(size_t)v] > cap_keys) { bounds.push_back(v); piece_keys = std::max(piece_keys, acc); acc = 0; }
-                acc += h[(size_t)v];
-            }
-            bounds.push_back(V);
-            piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
-        }
-        vgl_dev<uint64_t> keys_a, keys_b;
-        vgl_dev<unsigned long long> n_keys;
-        vgl_dev<size_t> n_unique;
-        vgl_dev<int32_t> adj_tmp;                                     // 2 E entries bound 2 E' from above
-        VGL_TRY(keys_a.alloc(st, (size_t)piece_keys));
-        VGL_TRY(keys_b.alloc(st, (size_t)piece_keys));
-        VGL_TRY(n_keys.alloc(st, 1));
-        VGL_TRY(n_unique.alloc(st, 1));
-        VGL_TRY(adj_tmp.alloc(st, (size_t)(2 * E)));
-        int end_bit = 33;
-        while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
-        size_t temp_sort = 0, temp_unique = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a.p, keys_b.p, (size_t)piece_keys, 0, (unsigned)end_bit, st));
-        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
-        const size_t temp_bytes = std::max(temp_sort, temp_unique);
-        vgl_dev<char> temp;
-        VGL_TRY(temp.alloc(st, temp_bytes));
-        int64_t base = 0;
-        for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
-            const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
-            VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(vgl_k_kcore_emit, dim3(kc_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, v0, v1, keys_a.p, n_keys.p, piece_keys);
-            VGL_HIP_TRY(hipGetLastError());
-            unsigned long long nk = 0;
-            VGL_HIP_TRY(hipMemcpyAsync(&nk, n_keys, sizeof(nk), hipMemcpyDeviceToHost, st));
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-            if ((int64_t)nk > piece_keys) VGL_FAIL("kcore_prepare: a piece holds more keys than were counted for it");
-            size_t nu = 0;
-            if (nk) {
-                size_t need = temp_bytes;
-                VGL_HIP_TRY(rocprim::radix_sort_keys(temp.p, need, keys_a.p, keys_b.p, (size_t)nk, 0, (unsigned)end_bit, st));
-                need = temp_bytes;
-                VGL_HIP_TRY(rocprim::unique(temp.p, need, keys_b.p, keys_a.p, n_unique.p, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
-                VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
-                VGL_HIP_TRY(hipStreamSynchronize(st));
-            }
-            if (base + (int64_t)nu > 2 * E) VGL_FAIL("kcore_prepare: more symmetric entries than twice the stored ones");
-            hipLaunchKernelGGL(vgl_k_kcore_fill, dim3(kc_grid((int64_t)nu, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a.p, (int64_t)nu, base, adj_tmp.p, 2 * E);
-            hipLaunchKernelGGL(vgl_k_kcore_rowptr, dim3(kc_grid((int64_t)v1 - v0 + 1, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a.p, (int64_t)nu, v0, v1, base,
-                               p->rowptr.p);
-            VGL_HIP_TRY(hipGetLastError());
-            base += (int64_t)nu;
-        }
-        p->nnz = base;
-        VGL_TRY(p->adj.alloc((size_t)base));
-        if (base) VGL_HIP_TRY(hipMemcpyAsync(p->adj, adj_tmp, sizeof(int32_t) * (size_t)base, hipMemcpyDeviceToDevice, st));
-        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys.p);
-        VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
-        {
-            vgl_timed_launch tl(c, "kcore_csr");                      // once per built CSR: what a caller counts to see that a handle built it once
-            hipLaunchKernelGGL(vgl_k_kcore_degrees, dim3(kc_grid(V, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr.p, p->deg.p, d_max);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_HIP_TRY(hipMemcpyAsync(&p->max_deg, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        VGL_HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        VGL_TRY(p->adj.alloc(1));
-        VGL_HIP_TRY(hipStreamSynchronize(st));
-    }
-    out.reset(p.release());
-    return 0;
-}
-
-int kc_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_kcore_cache **out, bool *built)
-{
-    *built = false;
-    if (!g->kcore) {
-        VGL_TRY(kc_build_csr(c, g, g->kcore));
-        *built = true;
-    }
-    *out = g->kcore.get();
-    return 0;
-}
-
 // the host side of one run: where the frontier is, what has been counted
 struct kc_run {
     vgl_hip_ctx *c;
@@ -552,13 +317,7 @@ struct kc_run {
     // the one host-visible read of a sub-round of the large path: list tails and entry total
     int read()
     {
-        const int64_t seq = vgl_next_seq(c);
-        {
-            vgl_timed_launch tl(c, "kcore_publish");
-            hipLaunchKernelGGL(vgl_k_kcore_publish, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)cnt, (volatile int64_t *)c->h_counters, seq);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_TRY(vgl_wait_counters(c, seq));
+        VGL_TRY(vgl_publish_counters(c, "kcore_publish", cnt, KC_NCNT));
         for (int k_ = 0; k_ < KC_NCLS; k_++) {
             head[k_] = tail[k_];
             tail[k_] = c->h_counters[KC_TAIL + k_];
@@ -572,27 +331,15 @@ struct kc_run {
 
 }  // namespace
 
-int vgl_kcore_sym_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *out)
-{
-    vgl_kcore_cache *k = nullptr;
-    bool built = false;
-    VGL_TRY(kc_ensure(c, g, &k, &built));
-    out->V = k->V; out->nnz = k->nnz;
-    out->rowptr = k->rowptr; out->adj = k->adj; out->deg = k->deg;
-    out->max_deg = k->max_deg;
-    out->built_now = built;
-    return 0;
-}
-
 extern "C" {
 
 int vgl_hip_kcore_prepare(vgl_hip_ctx *c, vgl_hip_graph *g)
 {
     if (!c || !g) VGL_FAIL("kcore_prepare: null argument");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("kcore_prepare: graph handle must own all rows (the k-core decomposition has no sharded form)");
-    vgl_kcore_cache *k = nullptr;
+    const vgl_simple_cache *k = nullptr;
     bool built = false;
-    VGL_TRY(kc_ensure(c, g, &k, &built));
+    VGL_TRY(vgl_simple_ensure_csr(c, g, &k, &built));
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -603,9 +350,10 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     if (!d_core) VGL_FAIL("kcore_run: d_core must not be NULL");
     if (k_limit < 0) VGL_FAIL("kcore_run: k_limit must not be negative");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("kcore_run: graph handle must own all rows (the k-core decomposition has no sharded form)");
-    vgl_kcore_cache *kc = nullptr;
+    const vgl_simple_cache *sc = nullptr;
     bool built = false;
-    VGL_TRY(kc_ensure(c, g, &kc, &built));
+    VGL_TRY(vgl_simple_ensure_csr(c, g, &sc, &built));
+    const vgl_simple_csr *kc = &sc->csr;
     const int32_t V = g->V;
     hipStream_t st = c->stream;
     const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_KCORE_SHORT", 32, 0, 1 << 20);
@@ -678,7 +426,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
             if (small_m > 0 && !dom_ids && V > KC_SMALL_SCAN && left <= KC_SMALL_SCAN) {      // few are left: from now on the scans read their list
                 {
                     vgl_timed_launch tl(c, "kcore_scan");
-                    hipLaunchKernelGGL(vgl_k_kcore_compact, dim3(kc_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, alive.p, KC_SMALL_SCAN, cnt.p);
+                    hipLaunchKernelGGL(vgl_k_kcore_compact, dim3(vgl_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, alive.p, KC_SMALL_SCAN, cnt.p);
                 }
                 VGL_HIP_TRY(hipGetLastError());
                 dom_ids = alive;
@@ -694,11 +442,11 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
             VGL_HIP_TRY(hipMemsetAsync(cnt.p + KC_K, 0x7F, sizeof(unsigned long long), st));      // KC_NO_K
             {
                 vgl_timed_launch tl(c, "kcore_scan");
-                hipLaunchKernelGGL(vgl_k_kcore_min, dim3(kc_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, (const int32_t *)deg.p, r.k, cnt.p);
+                hipLaunchKernelGGL(vgl_k_kcore_min, dim3(vgl_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, (const int32_t *)deg.p, r.k, cnt.p);
             }
             {
                 vgl_timed_launch tl(c, "kcore_scan");
-                hipLaunchKernelGGL(vgl_k_kcore_scan, dim3(kc_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, r.g, r.k, k_limit, cnt.p);
+                hipLaunchKernelGGL(vgl_k_kcore_scan, dim3(vgl_grid(dom_n, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, dom_ids, dom_n, r.g, r.k, k_limit, cnt.p);
             }
             VGL_HIP_TRY(hipGetLastError());
             VGL_TRY(r.read());
@@ -720,13 +468,13 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
         if (r.tail[KC_SHORT] > r.head[KC_SHORT]) {
             const int64_t n = r.tail[KC_SHORT] - r.head[KC_SHORT];
             vgl_timed_launch tl(c, "kcore_short");
-            hipLaunchKernelGGL(vgl_k_kcore_short, dim3(kc_grid(n * KC_G, VGL_BLOCK, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_SHORT] + r.head[KC_SHORT]), (int32_t)n,
+            hipLaunchKernelGGL(vgl_k_kcore_short, dim3(vgl_grid(n * KC_G, VGL_BLOCK, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_SHORT] + r.head[KC_SHORT]), (int32_t)n,
                                r.k, cnt.p);
         }
         if (r.tail[KC_WAVE] > r.head[KC_WAVE]) {
             const int64_t n = r.tail[KC_WAVE] - r.head[KC_WAVE];
             vgl_timed_launch tl(c, "kcore_wave");
-            hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(kc_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WAVE] + r.head[KC_WAVE]),
+            hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(vgl_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WAVE] + r.head[KC_WAVE]),
                                (int32_t)n, r.k, cnt.p);
         }
         if (r.tail[KC_WG] > r.head[KC_WG]) {
@@ -739,7 +487,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
         r.subs++;
     }
     if (limited) {
-        hipLaunchKernelGGL(vgl_k_kcore_fill_limit, dim3(kc_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, k_limit, d_core);
+        hipLaunchKernelGGL(vgl_k_kcore_fill_limit, dim3(vgl_grid(V, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)deg.p, r.k, k_limit, d_core);
         VGL_HIP_TRY(hipGetLastError());
     }
     VGL_HIP_TRY(hipStreamSynchronize(st));

@@ -1,10 +1,8 @@
 // ktruss.hip -- k-truss decomposition (truss number and initial triangle support of every edge) of the simple undirected graph underlying the stored
 // outgoing CSR.  The contract is written out in include/vgl_hip.h; DESIGN section 16 has the rule, the kernel resources and the bytes model.
 //
-// Prepare (once per graph, cached on the handle): the symmetric simple CSR, rows ascending by id, is kcore's (vgl_kcore_sym_csr: built there if the
-// handle has none, shared afterwards).  On top of it: up[u] = entries of row u above u (one binary search per row), their exclusive scan = the id of
-// the first edge whose lower endpoint is u, and eid[slot]: a slot (u, v), u < v, is edge up_off[u] + its rank among the upper entries of row u; a
-// slot (v, u) finds the slot (u, v) by a binary search of row u.  edge_u / edge_v are written by the upper slots.  The ids ascend with (lo, hi).
+// Prepare (once per graph, cached on the handle): the symmetric simple CSR, rows ascending by id, and the numbering of its edges (eid of every slot,
+// lo / hi of every edge, ids ascending with (lo, hi)) are simple.hip's (vgl_simple_ensure_edge_ids), shared with kcore and msf.
 //
 // Support (per run; one pass, every support written once, no atomics on them): the edges are appended to one list per class of the SHORTER row's
 // length (<= VGL_KTRUSS_SHORT: 8 lanes per edge, <= VGL_KTRUSS_WAVE: a wavefront, longer: a workgroup); the lanes stride over the shorter row and
@@ -21,9 +19,8 @@
 // An edge enters a frontier exactly once, so the frontiers are consecutive segments of one list per class; appends are aggregated per wave (ballot +
 // one returning atomic).  The host reads the pinned mirror once per sub-round.  No cooperative launch, no grid barrier, no workgroup waits for another:
 // every turn of the host loop expands a non-empty frontier or changes k.
-#include "vgl_hip_internal.h"
+#include "vgl_simple.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <climits>
 
@@ -61,85 +58,8 @@ struct kt_graph {
 __device__ __forceinline__ int kt_class_of(int32_t d, const kt_graph &g) { return d <= g.b_short ? KT_SHORT : d <= g.b_wave ? KT_WAVE : KT_WG; }
 __device__ __forceinline__ int32_t kt_shorter(int32_t e, const kt_graph &g) { return min(g.deg[g.eu[e]], g.deg[g.ev[e]]); }
 
-// the slot of `w` in the ascending entries [lo, hi) of adj, or -1
-__device__ __forceinline__ int64_t kt_find(const int32_t *adj, int64_t lo, int64_t hi, int32_t w)
-{
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        const int32_t x = adj[mid];
-        if (x < w) lo = mid + 1; else if (x > w) hi = mid; else return mid;
-    }
-    return -1;
-}
-__device__ __forceinline__ int32_t kt_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
-{
-    int32_t lo = 0, hi = V;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if (rp[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// ---- prepare ----
-// up[u] = entries of row u above u (u < V); up[V] = 0
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_upper(int32_t V, const int64_t *rowptr, const int32_t *adj, int32_t *up)
-{
-    for (int64_t u = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; u <= V; u += (int64_t)gridDim.x * VGL_BLOCK) {
-        int32_t n = 0;
-        if (u < V) {
-            int64_t lo = rowptr[u];
-            const int64_t end = rowptr[u + 1];
-            int64_t hi = end;
-            while (lo < hi) {                                         // the first entry above u
-                const int64_t mid = lo + (hi - lo) / 2;
-                if (adj[mid] <= (int32_t)u) lo = mid + 1; else hi = mid;
-            }
-            n = (int32_t)(end - lo);
-        }
-        up[u] = n;
-    }
-}
-// eid of every slot; edge_u / edge_v from the upper slots.  up_off: the exclusive scan of up (V + 1 entries; up_off[V] = E').
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_eid(int32_t V, int64_t nnz, const int64_t *rowptr, const int32_t *adj, const int32_t *up_off, int32_t *eid,
-                                                               int32_t *eu, int32_t *ev, int32_t ne)
-{
-    for (int64_t s = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; s < nnz; s += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t r = kt_row_of(rowptr, V, s), c = adj[s];
-        if (c < 0 || c >= V || c == r) continue;                      // (the builder leaves none of these)
-        const int32_t lo = min(r, c), hi = max(r, c);
-        const int64_t first_up = rowptr[lo + 1] - (up_off[lo + 1] - up_off[lo]);      // slot of the first upper entry of row lo
-        const int64_t slot = r < c ? s : kt_find(adj, first_up, rowptr[lo + 1], hi);
-        if (slot < 0) continue;                                       // (a symmetric CSR has the slot)
-        const int32_t id = up_off[lo] + (int32_t)(slot - first_up);
-        if (id < 0 || id >= ne) continue;
-        eid[s] = id;
-        if (r < c) { eu[id] = lo; ev[id] = hi; }
-    }
-}
-
 // ---- shared device pieces ----
-// Every lane of the wave calls (uniform control flow).  The lanes with `want` append e to the list of class `cls`: one returning atomic per wave and
-// class.
-__device__ __forceinline__ void kt_append(bool want, int32_t e, int cls, const kt_lists &L, unsigned long long *tail)
-{
-    if (!__any(want)) return;
-    const int lane = vgl_lane();
-#pragma unroll
-    for (int c = 0; c < KT_NCLS; c++) {
-        const bool mine = want && cls == c;
-        const unsigned long long m = __ballot(mine);
-        if (!m) continue;                                             // (uniform)
-        const int leader = __ffsll((long long)m) - 1;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(tail + c, (unsigned long long)__popcll(m));
-        base = __shfl(base, leader);
-        if (mine) {
-            const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
-            if (pos < (unsigned long long)L.cap) vgl_store_agent(L.list[c] + pos, e);
-        }
-    }
-}
+// (appends: vgl_wave_append, one returning atomic per wave and class)
 // the two rows of an edge: [a_lo, a_hi) is walked (the shorter; ties: the lower endpoint's), [b_lo, b_hi) is searched
 struct kt_rows { int64_t a_lo, a_hi, b_lo, b_hi; };
 __device__ __forceinline__ kt_rows kt_rows_of(int32_t e, const kt_graph &g)
@@ -148,12 +68,6 @@ __device__ __forceinline__ kt_rows kt_rows_of(int32_t e, const kt_graph &g)
     const int64_t u0 = g.rowptr[u], u1 = g.rowptr[u + 1], v0 = g.rowptr[v], v1 = g.rowptr[v + 1];
     return (u1 - u0 <= v1 - v0) ? kt_rows{u0, u1, v0, v1} : kt_rows{v0, v1, u0, u1};
 }
-// every lane of the wave, once, at the end of a kernel
-__device__ __forceinline__ void kt_flush(unsigned long long *cnt, int slot, int64_t m)
-{
-    m = vgl_wave_reduce_add(m);
-    if (vgl_lane() == 0 && m) atomicAdd(cnt + slot, (unsigned long long)m);
-}
 
 // ---- support ----
 // the triangles of one edge that this lane sees: lane `li` of `stride` strides over the walked row
@@ -161,13 +75,13 @@ __device__ __forceinline__ int32_t kt_count(const kt_rows &r, int li, int stride
 {
     int32_t n = 0;
     for (int64_t i = r.a_lo + li; i < r.a_hi; i += stride)
-        if (kt_find(adj, r.b_lo, r.b_hi, adj[i]) >= 0) n++;
+        if (vgl_slot_of(adj, r.b_lo, r.b_hi, adj[i]) >= 0) n++;
     return n;
 }
 __device__ __forceinline__ void kt_support_done(unsigned long long *cnt, int64_t sum, int64_t walk, int32_t mx)
 {
-    kt_flush(cnt, KT_SUM, sum);
-    kt_flush(cnt, KT_WALK, walk);
+    vgl_wave_flush_add(cnt + KT_SUM, sum);
+    vgl_wave_flush_add(cnt + KT_WALK, walk);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
     if (vgl_lane() == 0 && mx) atomicMax(cnt + KT_MAXSUP, (unsigned long long)mx);
@@ -178,7 +92,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_classify(int32_t ne, k
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < ne; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t e = base + threadIdx.x;
         const bool want = e < ne;
-        kt_append(want, (int32_t)e, want ? kt_class_of(kt_shorter((int32_t)e, g), g) : 0, g.L, cnt + KT_TAIL);
+        vgl_wave_append<KT_NCLS>(want, (int32_t)e, want ? kt_class_of(kt_shorter((int32_t)e, g), g) : 0, g.L.list, g.L.cap, cnt + KT_TAIL);
     }
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup_short(kt_graph g, const int32_t *edges, int32_t n, unsigned long long *cnt)
@@ -239,7 +153,7 @@ __device__ __forceinline__ void kt_dec(bool active, int32_t e, int32_t k, int32_
             m_acc += len;
         } else if (old <= k - 2) atomicAdd(g.sup + e, 1);
     }
-    kt_append(want, e, cls, g.L, tail);
+    vgl_wave_append<KT_NCLS>(want, e, cls, g.L.list, g.L.cap, tail);
 }
 // The frontier edge e1 with rows r, lane `li` of `stride`.  Uniform over the wave as long as every lane of the wave calls (has = this lane has an edge).
 __device__ __forceinline__ void kt_expand(bool has, int32_t e1, const kt_rows &r, int li, int stride, int32_t k, int32_t s, const kt_graph &g,
@@ -251,7 +165,7 @@ __device__ __forceinline__ void kt_expand(bool has, int32_t e1, const kt_rows &r
         bool dec2 = false, dec3 = false;
         int32_t e2 = 0, e3 = 0;
         if (i < end) {
-            const int64_t j = kt_find(g.adj, r.b_lo, r.b_hi, g.adj[i]);
+            const int64_t j = vgl_slot_of(g.adj, r.b_lo, r.b_hi, g.adj[i]);
             if (j >= 0) {
                 e2 = g.eid[i]; e3 = g.eid[j];
                 const int32_t s2 = vgl_load_agent(g.stamp + e2), s3 = vgl_load_agent(g.stamp + e3);
@@ -297,9 +211,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_scan(int32_t ne, kt_gr
             cls = kt_class_of(len, g);
             m_acc += len;
         }
-        kt_append(want, (int32_t)e, cls, g.L, cnt + KT_TAIL);
+        vgl_wave_append<KT_NCLS>(want, (int32_t)e, cls, g.L.list, g.L.cap, cnt + KT_TAIL);
     }
-    kt_flush(cnt, KT_M, m_acc);
+    vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_short(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
 {
@@ -313,7 +227,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_short(kt_graph g, cons
         if (has) r = kt_rows_of(e, g);
         kt_expand(has, e, r, gi, KT_G, k, s, g, cnt + KT_TAIL, m_acc);
     }
-    kt_flush(cnt, KT_M, m_acc);
+    vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wave(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
 {
@@ -322,7 +236,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wave(kt_graph g, const
         const int32_t e = edges[i];
         kt_expand(true, e, kt_rows_of(e, g), vgl_lane(), 64, k, s, g, cnt + KT_TAIL, m_acc);
     }
-    kt_flush(cnt, KT_M, m_acc);
+    vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wg(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
 {
@@ -331,7 +245,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wg(kt_graph g, const i
         const int32_t e = edges[i];
         kt_expand(true, e, kt_rows_of(e, g), (int)threadIdx.x, VGL_BLOCK, k, s, g, cnt + KT_TAIL, m_acc);
     }
-    kt_flush(cnt, KT_M, m_acc);
+    vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
 // the peel stopped at k_limit: what is still alive gets k_limit
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_fill_limit(int32_t ne, const int32_t *stamp, int32_t k_limit, int32_t *truss)
@@ -339,86 +253,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_fill_limit(int32_t ne,
     for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < ne; e += (int64_t)gridDim.x * VGL_BLOCK)
         if (stamp[e] == 0) truss[e] = k_limit;
 }
-// the counters into the pinned mirror, then the sequence number (one wavefront)
-__global__ void vgl_k_ktruss_publish(const unsigned long long *cnt, volatile int64_t *host, int64_t seq)
-{
-    if (threadIdx.x < KT_NCNT) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
-}
-
-unsigned kt_grid(int64_t work, int64_t per_block, int64_t cap = KT_MAX_GRID) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
 
 }  // namespace
-
-// The edge numbering of a graph's symmetric simple CSR (cached on the handle, freed with it)
-struct vgl_ktruss_cache {
-    int64_t ne = 0;                              // E'
-    vgl_dev<int32_t> eid;                        // 2 E'
-    vgl_dev<int32_t> eu, ev;                     // E' each
-};
-
-void vgl_ktruss_cache_free(vgl_ktruss_cache *p) { delete p; }
-
-namespace {
-
-int kt_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_ktruss_cache **out, bool *built)
-{
-    *built = false;
-    VGL_TRY(vgl_kcore_sym_csr(c, g, csr));
-    if (!g->ktruss) {
-        const int32_t V = csr->V;
-        const int64_t ne = csr->nnz / 2;
-        if (ne >= ((int64_t)1 << 31)) VGL_FAIL("ktruss_prepare: 2^31 or more undirected edges (edge ids are int32)");
-        hipStream_t st = c->stream;
-        std::unique_ptr<vgl_ktruss_cache> p(new vgl_ktruss_cache());
-        p->ne = ne;
-        VGL_TRY(p->eid.alloc((size_t)(2 * ne)));
-        VGL_TRY(p->eu.alloc((size_t)ne));
-        VGL_TRY(p->ev.alloc((size_t)ne));
-        if (ne > 0) {
-            vgl_dev<int32_t> up, up_off;
-            vgl_dev<char> temp;
-            VGL_TRY(up.alloc(st, (size_t)V + 1));
-            VGL_TRY(up_off.alloc(st, (size_t)V + 1));
-            size_t temp_bytes = 0;
-            VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, up.p, up_off.p, (int32_t)0, (size_t)V + 1, rocprim::plus<int32_t>(), st));
-            VGL_TRY(temp.alloc(st, temp_bytes));
-            VGL_HIP_TRY(hipMemsetAsync(p->eid, 0, sizeof(int32_t) * (size_t)(2 * ne), st));
-            {
-                vgl_timed_launch tl(c, "ktruss_prepare");
-                hipLaunchKernelGGL(vgl_k_ktruss_upper, dim3(kt_grid((int64_t)V + 1, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr->rowptr, csr->adj, up.p);
-            }
-            VGL_HIP_TRY(hipGetLastError());
-            VGL_HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, up.p, up_off.p, (int32_t)0, (size_t)V + 1, rocprim::plus<int32_t>(), st));
-            {
-                vgl_timed_launch tl(c, "ktruss_prepare");
-                hipLaunchKernelGGL(vgl_k_ktruss_eid, dim3(kt_grid(csr->nnz, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr->nnz, csr->rowptr, csr->adj, (const int32_t *)up_off.p, p->eid.p,
-                                   p->eu.p, p->ev.p, (int32_t)ne);
-            }
-            VGL_HIP_TRY(hipGetLastError());
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-        }
-        g->ktruss.reset(p.release());
-        *built = true;
-    }
-    *out = g->ktruss.get();
-    return 0;
-}
-
-}  // namespace
-
-int vgl_ktruss_edge_ids(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *out)
-{
-    vgl_ktruss_cache *kt = nullptr;
-    bool built = false;
-    VGL_TRY(kt_ensure(c, g, csr, &kt, &built));
-    out->ne = kt->ne;
-    out->eid = kt->eid; out->eu = kt->eu; out->ev = kt->ev;
-    out->built_now = built;
-    return 0;
-}
 
 extern "C" {
 
@@ -426,10 +262,9 @@ int vgl_hip_ktruss_prepare(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *undirected
 {
     if (!c || !g) VGL_FAIL("ktruss_prepare: null argument");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("ktruss_prepare: graph handle must own all rows (the k-truss decomposition has no sharded form)");
-    vgl_sym_csr csr;
-    vgl_ktruss_cache *kt = nullptr;
+    const vgl_simple_cache *kt = nullptr;
     bool built = false;
-    VGL_TRY(kt_ensure(c, g, &csr, &kt, &built));
+    VGL_TRY(vgl_simple_ensure_edge_ids(c, g, &kt, &built));
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
     if (undirected_edges) *undirected_edges = kt->ne;
     return 0;
@@ -443,10 +278,9 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     if ((d_edge_u == nullptr) != (d_edge_v == nullptr)) VGL_FAIL("ktruss_run: d_edge_u and d_edge_v go together (both or neither)");
     if (k_limit < 0 || k_limit == 1) VGL_FAIL("ktruss_run: k_limit must be 0 (the whole decomposition) or at least 2");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("ktruss_run: graph handle must own all rows (the k-truss decomposition has no sharded form)");
-    vgl_sym_csr csr;
-    vgl_ktruss_cache *kt = nullptr;
+    const vgl_simple_cache *kt = nullptr;
     bool built = false;
-    VGL_TRY(kt_ensure(c, g, &csr, &kt, &built));
+    VGL_TRY(vgl_simple_ensure_edge_ids(c, g, &kt, &built));
     hipStream_t st = c->stream;
     const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_KTRUSS_SHORT", 32, 0, 1 << 20);
     const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_KTRUSS_WAVE", 1024, b_short, 1 << 24);
@@ -475,7 +309,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * KT_NCNT, st));
 
     kt_graph kg;
-    kg.rowptr = csr.rowptr; kg.adj = csr.adj; kg.deg = csr.deg;
+    kg.rowptr = kt->csr.rowptr; kg.adj = kt->csr.adj; kg.deg = kt->csr.deg;
     kg.eid = kt->eid; kg.eu = kt->eu; kg.ev = kt->ev;
     kg.sup = sup; kg.stamp = stamp; kg.truss = d_truss;
     kg.b_short = b_short; kg.b_wave = b_wave;
@@ -485,13 +319,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     int64_t head[KT_NCLS] = {0, 0, 0}, tail[KT_NCLS] = {0, 0, 0}, m_cum = 0;
     // the one host-visible read of a step: the counters through the pinned mirror; the lists' new tails
     auto read = [&]() -> int {
-        const int64_t seq = vgl_next_seq(c);
-        {
-            vgl_timed_launch tl(c, "ktruss_publish");
-            hipLaunchKernelGGL(vgl_k_ktruss_publish, dim3(1), dim3(64), 0, st, (const unsigned long long *)cnt.p, (volatile int64_t *)c->h_counters, seq);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_TRY(vgl_wait_counters(c, seq));
+        VGL_TRY(vgl_publish_counters(c, "ktruss_publish", cnt, KT_NCNT));
         for (int k_ = 0; k_ < KT_NCLS; k_++) {
             head[k_] = tail[k_];
             tail[k_] = c->h_counters[KT_TAIL + k_];
@@ -506,18 +334,18 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
         if (tail[KT_SHORT] > head[KT_SHORT]) {                                                                                                       \
             const int64_t n = tail[KT_SHORT] - head[KT_SHORT];                                                                                       \
             vgl_timed_launch tl(c, slot_short);                                                                                                      \
-            hipLaunchKernelGGL(k_short, dim3(kt_grid(n * KT_G, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_SHORT] + head[KT_SHORT]), (int32_t)n, \
+            hipLaunchKernelGGL(k_short, dim3(vgl_grid(n * KT_G, VGL_BLOCK, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_SHORT] + head[KT_SHORT]), (int32_t)n, \
                                __VA_ARGS__);                                                                                                         \
         }                                                                                                                                            \
         if (tail[KT_WAVE] > head[KT_WAVE]) {                                                                                                         \
             const int64_t n = tail[KT_WAVE] - head[KT_WAVE];                                                                                         \
             vgl_timed_launch tl(c, slot_wave);                                                                                                       \
-            hipLaunchKernelGGL(k_wave, dim3(kt_grid(n, VGL_WAVES)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WAVE] + head[KT_WAVE]), (int32_t)n, __VA_ARGS__); \
+            hipLaunchKernelGGL(k_wave, dim3(vgl_grid(n, VGL_WAVES, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WAVE] + head[KT_WAVE]), (int32_t)n, __VA_ARGS__); \
         }                                                                                                                                            \
         if (tail[KT_WG] > head[KT_WG]) {                                                                                                             \
             const int64_t n = tail[KT_WG] - head[KT_WG];                                                                                             \
             vgl_timed_launch tl(c, slot_wg);                                                                                                         \
-            hipLaunchKernelGGL(k_wg, dim3(kt_grid(n, 1)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WG] + head[KT_WG]), (int32_t)n, __VA_ARGS__); \
+            hipLaunchKernelGGL(k_wg, dim3(vgl_grid(n, 1, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WG] + head[KT_WG]), (int32_t)n, __VA_ARGS__); \
         }                                                                                                                                            \
         VGL_HIP_TRY(hipGetLastError());                                                                                                              \
     } while (0)
@@ -525,7 +353,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     // ---- the initial supports ----
     {
         vgl_timed_launch tl(c, "ktruss_classify");
-        hipLaunchKernelGGL(vgl_k_ktruss_classify, dim3(kt_grid(ne, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, ne, kg, cnt.p);
+        hipLaunchKernelGGL(vgl_k_ktruss_classify, dim3(vgl_grid(ne, VGL_BLOCK, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, ne, kg, cnt.p);
     }
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
@@ -551,11 +379,11 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
             VGL_HIP_TRY(hipMemsetAsync(cnt.p + KT_K, 0x7F, sizeof(unsigned long long), st));      // KT_NO_K
             {
                 vgl_timed_launch tl(c, "ktruss_scan");
-                hipLaunchKernelGGL(vgl_k_ktruss_min, dim3(kt_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, (const int32_t *)sup.p, (const int32_t *)stamp.p, cnt.p);
+                hipLaunchKernelGGL(vgl_k_ktruss_min, dim3(vgl_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, (const int32_t *)sup.p, (const int32_t *)stamp.p, cnt.p);
             }
             {
                 vgl_timed_launch tl(c, "ktruss_scan");
-                hipLaunchKernelGGL(vgl_k_ktruss_scan, dim3(kt_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, kg, s + 1, k_limit, cnt.p);
+                hipLaunchKernelGGL(vgl_k_ktruss_scan, dim3(vgl_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, kg, s + 1, k_limit, cnt.p);
             }
             VGL_HIP_TRY(hipGetLastError());
             VGL_TRY(read());
@@ -578,7 +406,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     }
 #undef KT_PER_CLASS
     if (limited) {
-        hipLaunchKernelGGL(vgl_k_ktruss_fill_limit, dim3(kt_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, (const int32_t *)stamp.p, k_limit, d_truss);
+        hipLaunchKernelGGL(vgl_k_ktruss_fill_limit, dim3(vgl_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, (const int32_t *)stamp.p, k_limit, d_truss);
         VGL_HIP_TRY(hipGetLastError());
     }
     VGL_HIP_TRY(hipStreamSynchronize(st));

@@ -401,7 +401,7 @@ struct vgl_lp_cache {
     }
 };
 
-void vgl_lp_cache_free(vgl_lp_cache *p) { delete p; }
+template <> void vgl_cache_free(vgl_lp_cache *p) { delete p; }
 
 namespace {
 
@@ -441,7 +441,7 @@ int lp_big_rows(vgl_hip_ctx *c, const vgl_dir_csr &d, int32_t V, int64_t thr, in
     return 0;
 }
 
-int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64_t key[6], std::unique_ptr<vgl_lp_cache, vgl_lp_cache_delete> &out)
+int lp_build(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_dir_csr &d, const int64_t key[6], vgl_cache<vgl_lp_cache> &out)
 {
     const int32_t V = g->V;
     std::unique_ptr<vgl_lp_cache> p(new vgl_lp_cache());

@@ -1,9 +1,9 @@
 // msf.hip -- minimum spanning forest (Boruvka) of the simple undirected graph underlying the stored outgoing CSR, with float32 weights per stored entry.
 // The contract is written out in include/vgl_hip.h; DESIGN section 17 has the round, the kernel resources and the bytes model.
 //
-// Prepare (once per graph, cached on the handle): the symmetric simple CSR is kcore's, the edge numbering (eid per slot, endpoints) ktruss's
-// (vgl_ktruss_edge_ids: built there if the handle has none, shared afterwards).  On top of them: slot_eid[s] = the undirected edge of the STORED
-// outgoing entry s (a binary search of the entry in its symmetric row), -1 for a loop.  Structure is per graph, values are per weights.
+// Prepare (once per graph, cached on the handle): the symmetric simple CSR, the edge numbering (eid per slot, endpoints) and slot_eid[s] = the
+// undirected edge of the STORED outgoing entry s, -1 for a loop, are simple.hip's (vgl_simple_ensure_slot_ids), shared with kcore and ktruss.
+// Structure is per graph, values are per weights.
 //
 // Fold (per run): wkey[e] = min over the stored entries of e of the order-preserving uint32 image of the weight (-0.0 canonicalised, sign bit
 // flipped, negatives complemented): one streaming pass, an integer atomicMin per entry, NaNs counted for the error.
@@ -19,7 +19,7 @@
 //   publish   list tails, picks and entries walked into the pinned mirror: one host read per round.  The loop ends on a round with no pick.
 // The live lists are one ring per class of twice the class's rows: a round reads [head, tail) and appends behind tail, positions taken modulo the
 // capacity; appends are staged per wave in LDS and cost one returning atomic per 64 or more rows.  No cooperative launch, no grid barrier.
-#include "vgl_hip_internal.h"
+#include "vgl_simple.h"
 #include <cstring>
 #include <algorithm>
 #include <climits>
@@ -65,46 +65,11 @@ __device__ __forceinline__ uint32_t msf_key_of(float w)
 }
 __device__ __forceinline__ float msf_weight_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-__device__ __forceinline__ int32_t msf_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
-{
-    int32_t lo = 0, hi = V;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if (rp[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 __device__ __forceinline__ unsigned long long msf_wave_min(unsigned long long m)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
     return m;
-}
-__device__ __forceinline__ void msf_flush_add(unsigned long long *cnt, int slot, int64_t m)      // every lane of the wave, once, at the end of a kernel
-{
-    m = vgl_wave_reduce_add(m);
-    if (vgl_lane() == 0 && m) atomicAdd(cnt + slot, (unsigned long long)m);
-}
-
-// ---- prepare ----
-// slot_eid of every stored outgoing entry: the entry (r, c), c != r, is found in row r of the symmetric CSR; eid of that slot
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_slot_eid(int32_t V, int64_t E, const int64_t *out_rp, const int32_t *out_adj, const int64_t *rowptr, const int32_t *adj,
-                                                                 const int32_t *eid, int32_t ne, int32_t *slot_eid)
-{
-    for (int64_t s = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; s < E; s += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t r = msf_row_of(out_rp, V, s), c = out_adj[s];
-        int32_t id = -1;
-        if (c >= 0 && c < V && c != r) {
-            int64_t lo = rowptr[r], hi = rowptr[r + 1];
-            while (lo < hi) {
-                const int64_t mid = lo + (hi - lo) / 2;
-                const int32_t x = adj[mid];
-                if (x < c) lo = mid + 1; else if (x > c) hi = mid; else { id = eid[mid]; break; }
-            }
-            if (id >= ne) id = -1;                                    // (the numbering has no such id)
-        }
-        slot_eid[s] = id;
-    }
 }
 
 // ---- fold ----
@@ -118,7 +83,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_fold(int64_t E, const int
         if (x != x) { nans++; continue; }
         atomicMin(wkey + e, msf_key_of(x));
     }
-    msf_flush_add(cnt, MSF_NAN, nans);
+    vgl_wave_flush_add(cnt + MSF_NAN, nans);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_edge_weight(int32_t ne, const uint32_t *wkey, float *out)
 {
@@ -156,7 +121,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_count(int32_t V, const in
         if (d > 0) n[msf_class_of(d, b_short, b_wave)]++;
     }
 #pragma unroll
-    for (int c = 0; c < MSF_NCLS; c++) msf_flush_add(cnt, MSF_ROWS + c, n[c]);
+    for (int c = 0; c < MSF_NCLS; c++) vgl_wave_flush_add(cnt + MSF_ROWS + c, n[c]);
 }
 // comp[v] = v; the rows with an entry into the ring of their class
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_init(int32_t V, const int32_t *deg, int32_t b_short, int32_t b_wave, int32_t *comp, msf_ring R0, msf_ring R1, msf_ring R2,
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, ms
         msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_SHORT);
     }
     msf_flush(st, R, cnt + MSF_TAIL + MSF_SHORT);
-    msf_flush_add(cnt, MSF_WALK, walked);
+    vgl_wave_flush_add(cnt + MSF_WALK, walked);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, msf_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
 {
@@ -248,7 +213,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, msf
         msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_WAVE);
     }
     msf_flush(st, R, cnt + MSF_TAIL + MSF_WAVE);
-    msf_flush_add(cnt, MSF_WALK, walked);
+    vgl_wave_flush_add(cnt + MSF_WALK, walked);
 }
 // work item w = (row w / nchunks of the segment, chunk w % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do.
 // A row is appended by the first of its chunks that finds a crossing entry: stamp[position in the segment] = the round.
@@ -306,7 +271,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_hook(int32_t V, const int
         }
         parent[v] = p;
     }
-    msf_flush_add(cnt, MSF_PICKS, picks);
+    vgl_wave_flush_add(cnt + MSF_PICKS, picks);
 }
 // root[c] = the root of old root c under parent (read-only here; acyclic, and the walk is bounded by V all the same)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_chase(int32_t V, const int32_t *comp, const int32_t *parent, int32_t *root)
@@ -330,15 +295,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_relabel(int32_t V, int32_
         if (c == (int32_t)v) best[v] = MSF_NONE;
     }
 }
-// the counters into the pinned mirror, then the sequence number (one wavefront)
-__global__ void vgl_k_msf_publish(const unsigned long long *cnt, volatile int64_t *host, int64_t seq)
-{
-    if (threadIdx.x < MSF_NCNT) host[threadIdx.x] = (int64_t)cnt[threadIdx.x];
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) { host[C_NSLOTS] = seq; __threadfence_system(); }
-}
-
 // ---- after the loop ----
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_iota(int32_t V, int32_t *out)
 {
@@ -386,46 +342,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_sum_final(int32_t n, cons
     if (threadIdx.x == 0) *out = x;
 }
 
-unsigned msf_grid(int64_t work, int64_t per_block, int64_t cap = MSF_MAX_GRID) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
-
-}  // namespace
-
-// The undirected edge of every stored outgoing entry (cached on the handle, freed with it)
-struct vgl_msf_cache {
-    vgl_dev<int32_t> slot_eid;                   // E
-};
-
-void vgl_msf_cache_free(vgl_msf_cache *p) { delete p; }
-
-namespace {
-
 int msf_check_handle(vgl_hip_graph *g, const char *msg)
 {
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL(msg);
-    return 0;
-}
-
-int msf_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *ids, bool *built)
-{
-    *built = false;
-    VGL_TRY(vgl_ktruss_edge_ids(c, g, csr, ids));
-    if (!g->msf) {
-        const int64_t E = g->out.edges;
-        hipStream_t st = c->stream;
-        std::unique_ptr<vgl_msf_cache> p(new vgl_msf_cache());
-        VGL_TRY(p->slot_eid.alloc((size_t)E));
-        if (E > 0) {
-            {
-                vgl_timed_launch tl(c, "msf_prepare");
-                hipLaunchKernelGGL(vgl_k_msf_slot_eid, dim3(msf_grid(E, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, g->V, E, g->out.rowptr, g->out.adj, csr->rowptr, csr->adj, ids->eid,
-                                   (int32_t)ids->ne, p->slot_eid.p);
-            }
-            VGL_HIP_TRY(hipGetLastError());
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-        }
-        g->msf.reset(p.release());
-        *built = true;
-    }
     return 0;
 }
 
@@ -437,12 +356,11 @@ int vgl_hip_msf_prepare(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *undirected_ed
 {
     if (!c || !g) VGL_FAIL("msf_prepare: null argument");
     VGL_TRY(msf_check_handle(g, "msf_prepare: graph handle must own all rows (the minimum spanning forest has no sharded form)"));
-    vgl_sym_csr csr;
-    vgl_edge_ids ids;
+    const vgl_simple_cache *sg = nullptr;
     bool built = false;
-    VGL_TRY(msf_ensure(c, g, &csr, &ids, &built));
+    VGL_TRY(vgl_simple_ensure_slot_ids(c, g, &sg, &built));
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (undirected_edges) *undirected_edges = ids.ne;
+    if (undirected_edges) *undirected_edges = sg->ne;
     return 0;
 }
 
@@ -454,10 +372,9 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     if (!d_in_forest) VGL_FAIL("msf_run: d_in_forest must not be NULL");
     if (!d_weights && g->out.edges > 0) VGL_FAIL("msf_run: d_weights must not be NULL (one float32 per stored outgoing entry)");
     if ((d_edge_u == nullptr) != (d_edge_v == nullptr)) VGL_FAIL("msf_run: d_edge_u and d_edge_v go together (both or neither)");
-    vgl_sym_csr csr;
-    vgl_edge_ids ids;
+    const vgl_simple_cache *sg = nullptr;
     bool built = false;
-    VGL_TRY(msf_ensure(c, g, &csr, &ids, &built));
+    VGL_TRY(vgl_simple_ensure_slot_ids(c, g, &sg, &built));
     const int32_t V = g->V;
     const int64_t E = g->out.edges;
     hipStream_t st = c->stream;
@@ -467,22 +384,16 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     vgl_hip_msf_stats out;
     memset(&out, 0, sizeof(out));
     out.prepared_now = built ? 1 : 0;
-    out.undirected_edges = ids.ne;
+    out.undirected_edges = sg->ne;
     out.components = V;
-    const int32_t ne = (int32_t)ids.ne;
+    const int32_t ne = (int32_t)sg->ne;
 
     // the one host-visible read of a step: the counters through the pinned mirror
     vgl_dev<unsigned long long> cnt;
     VGL_TRY(cnt.alloc(st, MSF_NCNT));
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * MSF_NCNT, st));
     auto read = [&]() -> int {
-        const int64_t seq = vgl_next_seq(c);
-        {
-            vgl_timed_launch tl(c, "msf_publish");
-            hipLaunchKernelGGL(vgl_k_msf_publish, dim3(1), dim3(64), 0, st, (const unsigned long long *)cnt.p, (volatile int64_t *)c->h_counters, seq);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        return vgl_wait_counters(c, seq);
+        return vgl_publish_counters(c, "msf_publish", cnt, MSF_NCNT);
     };
 
     // ---- fold; the NaN check comes before any output is written ----
@@ -492,7 +403,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
         VGL_HIP_TRY(hipMemsetAsync(wkey, 0xFF, sizeof(uint32_t) * (size_t)ne, st));
         {
             vgl_timed_launch tl(c, "msf_fold");
-            hipLaunchKernelGGL(vgl_k_msf_fold, dim3(msf_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, E, (const int32_t *)g->msf->slot_eid.p, d_weights, wkey.p, cnt.p);
+            hipLaunchKernelGGL(vgl_k_msf_fold, dim3(vgl_grid(E, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, E, (const int32_t *)sg->slot_eid.p, d_weights, wkey.p, cnt.p);
         }
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(read());
@@ -500,7 +411,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     }
 
     if (V > 0 && ne == 0 && d_component) {
-        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, d_component);
+        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_component);
         VGL_HIP_TRY(hipGetLastError());
     }
     if (ne == 0) {
@@ -509,11 +420,11 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
         return 0;
     }
     if (d_edge_u) {
-        VGL_HIP_TRY(hipMemcpyAsync(d_edge_u, ids.eu, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
-        VGL_HIP_TRY(hipMemcpyAsync(d_edge_v, ids.ev, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
+        VGL_HIP_TRY(hipMemcpyAsync(d_edge_u, sg->eu, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
+        VGL_HIP_TRY(hipMemcpyAsync(d_edge_v, sg->ev, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToDevice, st));
     }
     if (d_edge_weight) {
-        hipLaunchKernelGGL(vgl_k_msf_edge_weight, dim3(msf_grid(ne, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, ne, (const uint32_t *)wkey.p, d_edge_weight);
+        hipLaunchKernelGGL(vgl_k_msf_edge_weight, dim3(vgl_grid(ne, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, ne, (const uint32_t *)wkey.p, d_edge_weight);
         VGL_HIP_TRY(hipGetLastError());
     }
     VGL_HIP_TRY(hipMemsetAsync(d_in_forest, 0, (size_t)ne, st));
@@ -522,14 +433,14 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     vgl_dev<int32_t> comp, parent, root, lists, stamp;
     vgl_dev<unsigned long long> best;
     vgl_dev<double> partials;
-    const int sum_grid = (int)msf_grid(ne, VGL_BLOCK, MSF_SUM_GRID);
+    const int sum_grid = (int)vgl_grid(ne, VGL_BLOCK, MSF_SUM_GRID);
     VGL_TRY(comp.alloc(st, (size_t)V));
     VGL_TRY(parent.alloc(st, (size_t)V));
     VGL_TRY(root.alloc(st, (size_t)V));
     VGL_TRY(best.alloc(st, (size_t)V));
     VGL_TRY(partials.alloc(st, (size_t)sum_grid + 1));
     VGL_HIP_TRY(hipMemsetAsync(best, 0xFF, sizeof(unsigned long long) * (size_t)V, st));      // MSF_NONE
-    hipLaunchKernelGGL(vgl_k_msf_count, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr.deg, b_short, b_wave, cnt.p);
+    hipLaunchKernelGGL(vgl_k_msf_count, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b_short, b_wave, cnt.p);
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
     int64_t rows[MSF_NCLS], rows_total = 0;
@@ -551,13 +462,13 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
             off += 2 * rows[k];
         }
     }
-    hipLaunchKernelGGL(vgl_k_msf_init, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, csr.deg, b_short, b_wave, comp.p, R[0], R[1], R[2], cnt.p);
+    hipLaunchKernelGGL(vgl_k_msf_init, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b_short, b_wave, comp.p, R[0], R[1], R[2], cnt.p);
     VGL_HIP_TRY(hipGetLastError());
 
     msf_graph mg;
-    mg.rowptr = csr.rowptr; mg.adj = csr.adj; mg.eid = ids.eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;
-    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(csr.max_deg, 1), MSF_MAX_CHUNKS));
-    const int32_t nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max(csr.max_deg, 1), chunk));
+    mg.rowptr = sg->csr.rowptr; mg.adj = sg->csr.adj; mg.eid = sg->eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;
+    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(sg->csr.max_deg, 1), MSF_MAX_CHUNKS));
+    const int32_t nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max(sg->csr.max_deg, 1), chunk));
     int64_t head[MSF_NCLS] = {0, 0, 0}, tail[MSF_NCLS] = {rows[0], rows[1], rows[2]}, picks = 0;
     int32_t rounds = 0;
     for (int32_t round = 1;; round++) {
@@ -566,31 +477,31 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
         if (tail[MSF_SHORT] > head[MSF_SHORT]) {
             const int64_t n = tail[MSF_SHORT] - head[MSF_SHORT];
             vgl_timed_launch tl(c, "msf_min_short");
-            hipLaunchKernelGGL(vgl_k_msf_min_short, dim3(msf_grid(n * MSF_G, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_SHORT], (unsigned long long)head[MSF_SHORT], (int32_t)n, cnt.p);
+            hipLaunchKernelGGL(vgl_k_msf_min_short, dim3(vgl_grid(n * MSF_G, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_SHORT], (unsigned long long)head[MSF_SHORT], (int32_t)n, cnt.p);
         }
         if (tail[MSF_WAVE] > head[MSF_WAVE]) {
             const int64_t n = tail[MSF_WAVE] - head[MSF_WAVE];
             vgl_timed_launch tl(c, "msf_min_wave");
-            hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(msf_grid(n, VGL_WAVES)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WAVE], (unsigned long long)head[MSF_WAVE], (int32_t)n, cnt.p);
+            hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(vgl_grid(n, VGL_WAVES, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WAVE], (unsigned long long)head[MSF_WAVE], (int32_t)n, cnt.p);
         }
         if (tail[MSF_WG] > head[MSF_WG]) {
             const int64_t n = tail[MSF_WG] - head[MSF_WG];
             vgl_timed_launch tl(c, "msf_min_wg");
-            hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(msf_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WG], (unsigned long long)head[MSF_WG], (int32_t)n, chunk,
+            hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(vgl_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WG], (unsigned long long)head[MSF_WG], (int32_t)n, chunk,
                                nchunks, round, stamp.p, cnt.p);
         }
         {
             vgl_timed_launch tl(c, "msf_hook");
-            hipLaunchKernelGGL(vgl_k_msf_hook, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const unsigned long long *)best.p, ids.eu, ids.ev, parent.p,
+            hipLaunchKernelGGL(vgl_k_msf_hook, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const unsigned long long *)best.p, sg->eu, sg->ev, parent.p,
                                d_in_forest, cnt.p);
         }
         {
             vgl_timed_launch tl(c, "msf_flatten");
-            hipLaunchKernelGGL(vgl_k_msf_chase, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)parent.p, root.p);
+            hipLaunchKernelGGL(vgl_k_msf_chase, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)parent.p, root.p);
         }
         {
             vgl_timed_launch tl(c, "msf_flatten");
-            hipLaunchKernelGGL(vgl_k_msf_relabel, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, comp.p, (const int32_t *)root.p, best.p);
+            hipLaunchKernelGGL(vgl_k_msf_relabel, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, comp.p, (const int32_t *)root.p, best.p);
         }
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(read());
@@ -612,9 +523,9 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
 
     // ---- the smallest vertex id of every component; the weight of the forest ----
     if (d_component) {
-        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, root.p);
-        hipLaunchKernelGGL(vgl_k_msf_min_id, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, root.p);
-        hipLaunchKernelGGL(vgl_k_msf_component, dim3(msf_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)root.p, d_component);
+        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, root.p);
+        hipLaunchKernelGGL(vgl_k_msf_min_id, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, root.p);
+        hipLaunchKernelGGL(vgl_k_msf_component, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)root.p, d_component);
         VGL_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(vgl_k_msf_sum_partials, dim3(sum_grid), dim3(VGL_BLOCK), 0, st, ne, (const uint8_t *)d_in_forest, (const uint32_t *)wkey.p, partials.p);

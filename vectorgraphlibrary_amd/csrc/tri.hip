@@ -1,11 +1,10 @@
 // tri.hip -- triangle counting (global count, per-vertex counts, undirected degrees) on the simple undirected graph underlying the stored outgoing
 // CSR.  The contract is written out in include/vgl_hip.h.  (`tc` in this tree is transitive closure; triangle counting is `tri` everywhere.)
 //
-// Prepare (once per graph, cached on the handle): every stored entry (u, v), u != v, becomes the 64-bit key  lower << 32 | higher  under the total
-// order  (stored out-degree [+ in-degree when the incoming CSR exists], id);  the keys are sorted (rocprim radix sort) and deduplicated (rocprim unique),
-// in pieces of consecutive `lower` vertices when all of them would need more scratch than VGL_TRI_SORT_CAP_MB.  The sorted keys ARE the oriented CSR:
-// row = high half, entry = low half, every row ascending BY VERTEX ID and free of duplicates.  The intersections compare vertex ids, so no rank array is
-// kept: the order only decides which endpoint owns an edge.  Degree order bounds every oriented row by about sqrt(2 E').
+// Prepare (once per graph, cached on the handle): the oriented CSR of the simple graph, from the key sort of simple.hip (vgl_simple_build_oriented):
+// every edge once, in the row of its lower endpoint under the total order  (stored out-degree [+ in-degree when the incoming CSR exists], id),  every
+// row ascending BY VERTEX ID and free of duplicates.  The intersections compare vertex ids, so no rank array is kept: the order only decides which
+// endpoint owns an edge.  Degree order bounds every oriented row by about sqrt(2 E').
 //
 // Count: triangles = sum over oriented edges (a, b) of |N+(a) & N+(b)|; {a < b < c in the order} is found once, at (a, b) with witness c.
 // Rows a are split by oriented out-degree d = d+(a) (heaviest first inside a class):
@@ -17,7 +16,7 @@
 //                                        streams repeated per chunk.  No scratch block; a row of any length is ceil(d / chunk) workgroups.
 // Hits are summed in registers, per wave, then one 64-bit atomic per wave.  With per-vertex counts (template parameter) the witness takes one atomic
 // per hit, b one per edge, a one per edge (light) or per unit (table, huge); without them none of these atomics exist in the kernel.
-#include "vgl_hip_internal.h"
+#include "vgl_simple.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include <algorithm>
@@ -45,7 +44,6 @@ __host__ __device__ inline int tri_class_of(int64_t d, tri_bounds b)
     return TRI_HUGE;
 }
 
-__device__ __forceinline__ void tri_add64(int64_t *p, int64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
 __device__ __forceinline__ uint32_t tri_hash(int32_t x, int bits) { return ((uint32_t)x * 0x9E3779B1u) >> (32 - bits); }
 
 // every lane of the wave, once, at the end of a count kernel
@@ -54,95 +52,12 @@ __device__ __forceinline__ void tri_flush(int64_t *cnt, int64_t tri, int64_t wor
     tri = vgl_wave_reduce_add(tri);
     work = vgl_wave_reduce_add(work);
     if (vgl_lane() == 0) {
-        if (tri) tri_add64(cnt + TRI_C_TRI, tri);
-        if (work) tri_add64(cnt + TRI_C_WORK, work);
+        if (tri) vgl_atomic_add64(cnt + TRI_C_TRI, tri);
+        if (work) vgl_atomic_add64(cnt + TRI_C_WORK, work);
     }
 }
 
 // ---- prepare ----
-// ord[v] = degree << 32 | v: u is below v in the order iff ord[u] < ord[v]
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_order(int32_t V, const int64_t *out_rp, const int64_t *in_rp, uint64_t *ord)
-{
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
-        int64_t d = out_rp[v + 1] - out_rp[v];
-        if (in_rp) d += in_rp[v + 1] - in_rp[v];
-        ord[v] = (uint64_t)min(d, (int64_t)0xFFFFFFFFll) << 32 | (uint64_t)v;
-    }
-}
-__device__ __forceinline__ int32_t tri_row_of(const int64_t *rp, int32_t V, int64_t e)      // the row u with rp[u] <= e < rp[u + 1]
-{
-    int32_t lo = 0, hi = V;                     // invariant: rp[lo] <= e < rp[hi]
-    while (hi - lo > 1) {
-        const int32_t mid = lo + (hi - lo) / 2;
-        if (rp[mid] <= e) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-// stored entry e -> key (lower << 32 | higher); false for a self-loop
-__device__ __forceinline__ bool tri_key_of(const int64_t *rp, const int32_t *adj, int32_t V, const uint64_t *ord, int64_t e, uint64_t *key)
-{
-    const int32_t u = tri_row_of(rp, V, e), v = adj[e];
-    if (u == v || v < 0 || v >= V) return false;
-    const bool u_low = ord[u] < ord[v];
-    *key = (uint64_t)(uint32_t)(u_low ? u : v) << 32 | (uint32_t)(u_low ? v : u);
-    return true;
-}
-// entries per lower endpoint (only when the keys do not fit one piece)
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_count_lower(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, const uint64_t *ord, int32_t *per_lower)
-{
-    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
-        uint64_t key;
-        if (tri_key_of(rp, adj, V, ord, e, &key)) atomicAdd(per_lower + (key >> 32), 1);
-    }
-}
-// the keys whose lower endpoint is in [v0, v1), appended in any order (the sort follows); never more than cap are written
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_emit(int32_t V, int64_t E, const int64_t *rp, const int32_t *adj, const uint64_t *ord, int32_t v0, int32_t v1,
-                                                             uint64_t *keys, unsigned long long *n_keys, int64_t cap)
-{
-    for (int64_t e = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; e < E; e += (int64_t)gridDim.x * VGL_BLOCK) {
-        uint64_t key;
-        if (!tri_key_of(rp, adj, V, ord, e, &key)) continue;
-        const int32_t lower = (int32_t)(key >> 32);
-        if (lower < v0 || lower >= v1) continue;
-        const unsigned long long pos = atomicAdd(n_keys, 1ull);
-        if ((int64_t)pos < cap) keys[pos] = key;
-    }
-}
-// sorted unique keys of the piece [v0, v1) -> entries [base, base + n) of the oriented CSR; the higher endpoint's degree takes one add per entry
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_fill(const uint64_t *keys, int64_t n, int64_t base, int32_t *adj, int64_t adj_cap, int32_t V, int32_t *deg)
-{
-    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t hi = (int32_t)(uint32_t)keys[i];
-        if (base + i < adj_cap) adj[base + i] = hi;
-        if (hi >= 0 && hi < V) atomicAdd(deg + hi, 1);
-    }
-}
-// rowptr[r] = base + (keys of the piece below row r), r in [v0, v1]
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_rowptr(const uint64_t *keys, int64_t n, int32_t v0, int32_t v1, int64_t base, int64_t *rowptr)
-{
-    for (int64_t r = v0 + (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; r <= v1; r += (int64_t)gridDim.x * VGL_BLOCK) {
-        const uint64_t first = (uint64_t)r << 32;
-        int64_t lo = 0, hi = n;
-        while (lo < hi) {
-            const int64_t mid = lo + (hi - lo) / 2;
-            if (keys[mid] < first) lo = mid + 1; else hi = mid;
-        }
-        rowptr[r] = base + lo;
-    }
-}
-// deg[v] += d+(v); the class histogram and the longest oriented row
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_degrees(int32_t V, const int64_t *rowptr, int32_t *deg, int32_t *max_deg)
-{
-    int m = 0;
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int d = (int)(rowptr[v + 1] - rowptr[v]);
-        deg[v] += d;
-        m = max(m, d);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
-    if (vgl_lane() == 0 && m) atomicMax(max_deg, m);
-}
 // sort key of a row: class << 28 | (2^28 - 1 - min(d, 2^28 - 1)): classes ascending, heaviest rows first inside a class; rows without entries last
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_classify(int32_t V, const int64_t *rowptr, tri_bounds b, uint32_t *keys, int32_t *ids, int32_t *sizes)
 {
@@ -220,7 +135,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_light(const int32_t *rows
                     const int32_t x = adj[ss + i];
                     if (tri_contains(adj, ls, ln, x)) {
                         hits++;
-                        if (PV) tri_add64(pv + x, 1);
+                        if (PV) vgl_atomic_add64(pv + x, 1);
                     }
                 }
             }
@@ -228,7 +143,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_light(const int32_t *rows
             if (PV) {
 #pragma unroll
                 for (int o = G / 2; o > 0; o >>= 1) hits += __shfl_xor(hits, o);
-                if (valid && gi == 0 && hits) { tri_add64(pv + ea, hits); tri_add64(pv + b, hits); }
+                if (valid && gi == 0 && hits) { vgl_atomic_add64(pv + ea, hits); vgl_atomic_add64(pv + b, hits); }
             }
         }
     }
@@ -275,7 +190,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit
                 for (int32_t y = s_tab[h]; y != -1; y = s_tab[h]) {
                     if (y == x) {
                         hits++;
-                        if (PV) tri_add64(pv + x, 1);
+                        if (PV) vgl_atomic_add64(pv + x, 1);
                         break;
                     }
                     h = (h + 1) & mask;
@@ -286,30 +201,24 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit
             if (PV) {                                                 // (the group's 16 lanes share j: they are all here)
 #pragma unroll
                 for (int o = TRI_TG / 2; o > 0; o >>= 1) hits += __shfl_xor(hits, o);
-                if (gi == 0 && hits) tri_add64(pv + b, hits);
+                if (gi == 0 && hits) vgl_atomic_add64(pv + b, hits);
             }
         }
         tri += unit_hits;
         if (PV) {
             const int64_t row_hits = vgl_block_reduce_add(unit_hits, s_red);
-            if (threadIdx.x == 0 && row_hits) tri_add64(pv + a, row_hits);
+            if (threadIdx.x == 0 && row_hits) vgl_atomic_add64(pv + a, row_hits);
         }
     }
     tri_flush(cnt, tri, work);
 }
-
-unsigned tri_grid(int64_t work, int64_t per_block, int64_t cap = 16384) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cap, vgl_ceil_div(work, per_block))); }
 
 }  // namespace
 
 // The oriented CSR of a graph and the class lists of its rows (cached on the handle, freed with it)
 struct vgl_tri_cache {
     int32_t V = 0;
-    int64_t edges = 0;                           // E'
-    vgl_dev<int64_t> rowptr;                     // V + 1
-    vgl_dev<int32_t> adj;                        // E', rows ascending by vertex id
-    vgl_dev<int32_t> deg;                        // V: degree in the simple undirected graph
-    int32_t max_deg = 0;                         // longest oriented row
+    vgl_simple_csr csr;                          // nnz = E'; max_deg: the longest oriented row
     // classes (rebuilt when the switches change; the oriented CSR stays)
     int64_t key[4] = {-1, -1, -1, -1};
     tri_bounds b{};
@@ -319,112 +228,9 @@ struct vgl_tri_cache {
     vgl_dev<int32_t> unit_row, unit_chunk;
 };
 
-void vgl_tri_cache_free(vgl_tri_cache *p) { delete p; }
+template <> void vgl_cache_free(vgl_tri_cache *p) { delete p; }
 
 namespace {
-
-// the oriented CSR
-int tri_build_csr(vgl_hip_ctx *c, vgl_hip_graph *g, std::unique_ptr<vgl_tri_cache, vgl_tri_cache_delete> &out)
-{
-    const int32_t V = g->V;
-    const vgl_dir_csr &d = g->out;
-    const int64_t E = d.edges;
-    hipStream_t st = c->stream;
-    std::unique_ptr<vgl_tri_cache> p(new vgl_tri_cache());
-    p->V = V;
-    VGL_TRY(p->rowptr.alloc((size_t)V + 1));
-    VGL_TRY(p->deg.alloc((size_t)V));
-    VGL_HIP_TRY(hipMemsetAsync(p->rowptr, 0, sizeof(int64_t) * ((size_t)V + 1), st));
-    VGL_HIP_TRY(hipMemsetAsync(p->deg, 0, sizeof(int32_t) * (size_t)std::max(V, 1), st));
-    if (V > 0 && E > 0) {
-        // keys per piece: in + out buffers of 8 bytes each within the cap
-        const int64_t cap_keys = std::max<int64_t>(1, vgl_env_int(c, "VGL_TRI_SORT_CAP_MB", 4096, 0, (int64_t)1 << 24) * (1 << 20) / 16);
-        vgl_dev<uint64_t> ord;
-        VGL_TRY(ord.alloc(st, (size_t)V));
-        hipLaunchKernelGGL(vgl_k_tri_order, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, d.rowptr, g->in.rowptr, ord);
-        VGL_HIP_TRY(hipGetLastError());
-        std::vector<int32_t> bounds{0, V};                            // pieces of consecutive lower endpoints
-        int64_t piece_keys = E;
-        if (E > cap_keys) {
-            vgl_dev<int32_t> per_lower;
-            VGL_TRY(per_lower.alloc(st, (size_t)V));
-            VGL_HIP_TRY(hipMemsetAsync(per_lower, 0, sizeof(int32_t) * (size_t)V, st));
-            hipLaunchKernelGGL(vgl_k_tri_count_lower, dim3(tri_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, (const uint64_t *)ord, per_lower);
-            VGL_HIP_TRY(hipGetLastError());
-            std::vector<int32_t> h((size_t)V);
-            VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_lower, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-            per_lower.reset();
-            bounds.assign(1, 0);
-            int64_t acc = 0;
-            piece_keys = 0;
-            for (int32_t v = 0; v < V; v++) {                         // greedy; a vertex with more keys than the cap is a piece of its own
-                if (acc > 0 && acc + h[(size_t)v] > cap_keys) { bounds.push_back(v); piece_keys = std::max(piece_keys, acc); acc = 0; }
-                acc += h[(size_t)v];
-            }
-            bounds.push_back(V);
-            piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
-        }
-        vgl_dev<uint64_t> keys_a, keys_b;
-        vgl_dev<unsigned long long> n_keys;
-        vgl_dev<size_t> n_unique;
-        vgl_dev<int32_t> adj_tmp;                                     // E entries bound E' from above
-        VGL_TRY(keys_a.alloc(st, (size_t)piece_keys));
-        VGL_TRY(keys_b.alloc(st, (size_t)piece_keys));
-        VGL_TRY(n_keys.alloc(st, 1));
-        VGL_TRY(n_unique.alloc(st, 1));
-        VGL_TRY(adj_tmp.alloc(st, (size_t)E));
-        int end_bit = 33;
-        while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
-        size_t temp_sort = 0, temp_unique = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a.p, keys_b.p, (size_t)piece_keys, 0, (unsigned)end_bit, st));
-        VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
-        const size_t temp_bytes = std::max(temp_sort, temp_unique);
-        vgl_dev<char> temp;
-        VGL_TRY(temp.alloc(st, temp_bytes));
-        int64_t base = 0;
-        for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
-            const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
-            VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
-            hipLaunchKernelGGL(vgl_k_tri_emit, dim3(tri_grid(E, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, (const uint64_t *)ord, v0, v1, keys_a, n_keys,
-                               piece_keys);
-            VGL_HIP_TRY(hipGetLastError());
-            unsigned long long nk = 0;
-            VGL_HIP_TRY(hipMemcpyAsync(&nk, n_keys, sizeof(nk), hipMemcpyDeviceToHost, st));
-            VGL_HIP_TRY(hipStreamSynchronize(st));
-            if ((int64_t)nk > piece_keys) VGL_FAIL("tri_prepare: a piece holds more keys than were counted for it");
-            size_t nu = 0;
-            if (nk) {
-                size_t need = temp_bytes;
-                VGL_HIP_TRY(rocprim::radix_sort_keys(temp.p, need, keys_a.p, keys_b.p, (size_t)nk, 0, (unsigned)end_bit, st));
-                need = temp_bytes;
-                VGL_HIP_TRY(rocprim::unique(temp.p, need, keys_b.p, keys_a.p, n_unique.p, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
-                VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
-                VGL_HIP_TRY(hipStreamSynchronize(st));
-            }
-            if (base + (int64_t)nu > E) VGL_FAIL("tri_prepare: more oriented edges than stored entries");
-            hipLaunchKernelGGL(vgl_k_tri_fill, dim3(tri_grid((int64_t)nu, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a, (int64_t)nu, base, adj_tmp, E, V, p->deg);
-            hipLaunchKernelGGL(vgl_k_tri_rowptr, dim3(tri_grid((int64_t)v1 - v0 + 1, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a, (int64_t)nu, v0, v1, base,
-                               p->rowptr);
-            VGL_HIP_TRY(hipGetLastError());
-            base += (int64_t)nu;
-        }
-        p->edges = base;
-        VGL_TRY(p->adj.alloc((size_t)base));
-        if (base) VGL_HIP_TRY(hipMemcpyAsync(p->adj, adj_tmp, sizeof(int32_t) * (size_t)base, hipMemcpyDeviceToDevice, st));
-        int32_t *d_max = reinterpret_cast<int32_t *>(n_keys.p);
-        VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
-        hipLaunchKernelGGL(vgl_k_tri_degrees, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->deg, d_max);
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_HIP_TRY(hipMemcpyAsync(&p->max_deg, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        VGL_HIP_TRY(hipStreamSynchronize(st));
-    } else {
-        VGL_TRY(p->adj.alloc(1));
-        VGL_HIP_TRY(hipStreamSynchronize(st));
-    }
-    out.reset(p.release());
-    return 0;
-}
 
 // the class lists under the switches `key`
 int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
@@ -447,7 +253,7 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
         VGL_TRY(ids.alloc(st, (size_t)V));
         VGL_TRY(sizes.alloc(st, TRI_NCLS));
         VGL_HIP_TRY(hipMemsetAsync(sizes, 0, sizeof(int32_t) * TRI_NCLS, st));
-        hipLaunchKernelGGL(vgl_k_tri_classify, dim3(tri_grid(V, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->rowptr, p->b, k_in, ids, sizes);
+        hipLaunchKernelGGL(vgl_k_tri_classify, dim3(vgl_grid(V, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->csr.rowptr.p, p->b, k_in, ids, sizes);
         VGL_HIP_TRY(hipGetLastError());
         size_t need = 0;
         VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32, st));
@@ -462,7 +268,7 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
             vgl_dev<int32_t> d_deg;
             VGL_TRY(d_deg.alloc(st, (size_t)nh));
             const int32_t *hrows = p->rows + p->off[TRI_HUGE];
-            hipLaunchKernelGGL(vgl_k_tri_row_degrees, dim3(tri_grid(nh, VGL_BLOCK)), dim3(VGL_BLOCK), 0, st, nh, hrows, (const int64_t *)p->rowptr, d_deg);
+            hipLaunchKernelGGL(vgl_k_tri_row_degrees, dim3(vgl_grid(nh, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, nh, hrows, (const int64_t *)p->csr.rowptr.p, d_deg);
             VGL_HIP_TRY(hipGetLastError());
             std::vector<int32_t> hr((size_t)nh), hd((size_t)nh), ur, uc;
             VGL_HIP_TRY(hipMemcpyAsync(hr.data(), hrows, sizeof(int32_t) * (size_t)nh, hipMemcpyDeviceToHost, st));
@@ -491,7 +297,10 @@ int tri_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out, bool *buil
     key[3] = vgl_env_int(c, "VGL_TRI_HUGE_CHUNK", 8192, 16, TRI_SLOTS_L / 2);
     *built = false;
     if (!g->tri) {
-        VGL_TRY(tri_build_csr(c, g, g->tri));
+        vgl_cache<vgl_tri_cache> p(new vgl_tri_cache());
+        p->V = g->V;
+        VGL_TRY(vgl_simple_build_oriented(c, g, &p->csr));
+        g->tri = std::move(p);
         *built = true;
     }
     if (!std::equal(key, key + 4, g->tri->key)) {
@@ -505,29 +314,29 @@ int tri_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_tri_cache **out, bool *buil
 template <bool PV>
 int tri_count(vgl_hip_ctx *c, const vgl_tri_cache &k, int64_t *cnt, int64_t *pv)
 {
-    const int64_t *rp = k.rowptr;
-    const int32_t *adj = k.adj;
+    const int64_t *rp = k.csr.rowptr;
+    const int32_t *adj = k.csr.adj;
 #define TRI_LIGHT(cls, G)                                                                                                                          \
     if (k.size[cls]) {                                                                                                                             \
         vgl_timed_launch tl(c, "tri_light");                                                                                                       \
-        hipLaunchKernelGGL((vgl_k_tri_light<G, PV>), dim3(tri_grid(k.size[cls], VGL_BLOCK, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)(k.rows + k.off[cls]), \
+        hipLaunchKernelGGL((vgl_k_tri_light<G, PV>), dim3(vgl_grid(k.size[cls], VGL_BLOCK, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)(k.rows + k.off[cls]), \
                            k.size[cls], rp, adj, cnt, pv);                                                                                          \
     }
     TRI_LIGHT(0, 4) TRI_LIGHT(1, 8) TRI_LIGHT(2, 16) TRI_LIGHT(3, 32)
 #undef TRI_LIGHT
     if (k.size[TRI_TS]) {
         vgl_timed_launch tl(c, "tri_table");
-        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_S, PV>), dim3(tri_grid(k.size[TRI_TS], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_S, PV>), dim3(vgl_grid(k.size[TRI_TS], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
                            (const int32_t *)(k.rows + k.off[TRI_TS]), (const int32_t *)nullptr, k.size[TRI_TS], TRI_SLOTS_S / 2, rp, adj, cnt, pv);
     }
     if (k.size[TRI_TL]) {
         vgl_timed_launch tl(c, "tri_table");
-        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(tri_grid(k.size[TRI_TL], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(vgl_grid(k.size[TRI_TL], 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream,
                            (const int32_t *)(k.rows + k.off[TRI_TL]), (const int32_t *)nullptr, k.size[TRI_TL], TRI_SLOTS_L / 2, rp, adj, cnt, pv);
     }
     if (k.n_units) {
         vgl_timed_launch tl(c, "tri_huge");
-        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(tri_grid(k.n_units, 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)k.unit_row,
+        hipLaunchKernelGGL((vgl_k_tri_table<TRI_SLOTS_L, PV>), dim3(vgl_grid(k.n_units, 1, TRI_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, (const int32_t *)k.unit_row,
                            (const int32_t *)k.unit_chunk, k.n_units, k.chunk_len, rp, adj, cnt, pv);
     }
     VGL_HIP_TRY(hipGetLastError());
@@ -562,7 +371,7 @@ int vgl_hip_tri_run(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *triangles, int64_
     VGL_TRY(cnt.alloc(c->stream, TRI_NCNT));
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(int64_t) * TRI_NCNT, c->stream));
     if (d_per_vertex && V > 0) VGL_HIP_TRY(hipMemsetAsync(d_per_vertex, 0, sizeof(int64_t) * (size_t)V, c->stream));
-    if (d_degree && V > 0) VGL_HIP_TRY(hipMemcpyAsync(d_degree, k->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
+    if (d_degree && V > 0) VGL_HIP_TRY(hipMemcpyAsync(d_degree, k->csr.deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, c->stream));
     if (d_per_vertex) VGL_TRY(tri_count<true>(c, *k, cnt, d_per_vertex));
     else VGL_TRY(tri_count<false>(c, *k, cnt, nullptr));
     int64_t h[TRI_NCNT] = {0, 0};
@@ -572,11 +381,11 @@ int vgl_hip_tri_run(vgl_hip_ctx *c, vgl_hip_graph *g, int64_t *triangles, int64_
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         stats->triangles = h[TRI_C_TRI];
-        stats->undirected_edges = k->edges;
-        stats->intersections = k->edges;
+        stats->undirected_edges = k->csr.nnz;
+        stats->intersections = k->csr.nnz;
         stats->elements_examined = h[TRI_C_WORK];
-        stats->algorithmic_bytes = 8 * (int64_t)V + 4 * k->edges + 4 * h[TRI_C_WORK];
-        stats->max_oriented_degree = k->max_deg;
+        stats->algorithmic_bytes = 8 * (int64_t)V + 4 * k->csr.nnz + 4 * h[TRI_C_WORK];
+        stats->max_oriented_degree = k->csr.max_deg;
         stats->prepared_now = built ? 1 : 0;
         stats->rows_light = (int64_t)k->size[0] + k->size[1] + k->size[2] + k->size[3];
         stats->rows_table = (int64_t)k->size[TRI_TS] + k->size[TRI_TL];

@@ -182,18 +182,11 @@ struct vgl_dir_csr {                 // one direction of the graph (borrowed) + 
     int64_t max_row = -1;            // longest row (lazy; PageRank's choice between the ordered and the blocked pull)
 };
 
-void vgl_lp_cache_free(struct vgl_lp_cache *p);  // lp.hip
-void vgl_tri_cache_free(struct vgl_tri_cache *p);  // tri.hip
-void vgl_bc_cache_free(struct vgl_bc_cache *p);  // bc.hip
-void vgl_kcore_cache_free(struct vgl_kcore_cache *p);  // kcore.hip
-void vgl_ktruss_cache_free(struct vgl_ktruss_cache *p);  // ktruss.hip
-void vgl_msf_cache_free(struct vgl_msf_cache *p);  // msf.hip
-struct vgl_lp_cache_delete { void operator()(struct vgl_lp_cache *p) const { vgl_lp_cache_free(p); } };      // (the types are complete in their files only)
-struct vgl_tri_cache_delete { void operator()(struct vgl_tri_cache *p) const { vgl_tri_cache_free(p); } };
-struct vgl_bc_cache_delete { void operator()(struct vgl_bc_cache *p) const { vgl_bc_cache_free(p); } };
-struct vgl_kcore_cache_delete { void operator()(struct vgl_kcore_cache *p) const { vgl_kcore_cache_free(p); } };
-struct vgl_ktruss_cache_delete { void operator()(struct vgl_ktruss_cache *p) const { vgl_ktruss_cache_free(p); } };
-struct vgl_msf_cache_delete { void operator()(struct vgl_msf_cache *p) const { vgl_msf_cache_free(p); } };
+// The lazy per-algorithm caches of a graph handle.  Their types are complete in their own files only, so the handle deletes them through a function
+// that the owner's file defines for its type (template <> void vgl_cache_free(vgl_x_cache *p) { delete p; }).
+template <class T> void vgl_cache_free(T *p);
+template <class T> struct vgl_cache_delete { void operator()(T *p) const { vgl_cache_free(p); } };
+template <class T> using vgl_cache = std::unique_ptr<T, vgl_cache_delete<T>>;
 struct vgl_hip_graph {
     uint64_t uid = 0;                // unique per created handle (a freed handle's address may be reused: caches key on this, not on the pointer)
     int32_t V = 0, row_begin = 0, row_end = 0, nrows = 0;
@@ -235,35 +228,12 @@ struct vgl_hip_graph {
     std::shared_ptr<const struct vgl_blocked_layout> blk_path;  // the path layouts (Bellman-Ford / widest-path pull: rows gather, edge index kept): built
                                                                 // once per graph, every vgl_hip_sssp_pull_plan is a plan over it with weights of its own
     std::string blk_path_key;                    // the layout switches it was built under (fuse threshold, unit sizes, piece bound: the tests vary them per plan)
-    std::unique_ptr<struct vgl_lp_cache, vgl_lp_cache_delete> lp[2];   // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
-    std::unique_ptr<struct vgl_tri_cache, vgl_tri_cache_delete> tri;   // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
-    std::unique_ptr<struct vgl_bc_cache, vgl_bc_cache_delete> bc;      // betweenness centrality: the row classes of both directions (bc.hip, lazy, owned)
-    std::unique_ptr<struct vgl_kcore_cache, vgl_kcore_cache_delete> kcore;   // k-core decomposition: the symmetric simple CSR and its degrees (kcore.hip, lazy, owned)
-    std::unique_ptr<struct vgl_ktruss_cache, vgl_ktruss_cache_delete> ktruss;   // k-truss decomposition: edge ids of the symmetric CSR's slots and the edge endpoints (ktruss.hip, lazy, owned)
-    std::unique_ptr<struct vgl_msf_cache, vgl_msf_cache_delete> msf;   // minimum spanning forest: the undirected edge id of every STORED outgoing entry (msf.hip, lazy, owned)
+    vgl_cache<struct vgl_lp_cache> lp[2];        // label propagation: degree classes, hub and push schedules of the out / in CSR (lp.hip, lazy, owned)
+    vgl_cache<struct vgl_tri_cache> tri;         // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
+    vgl_cache<struct vgl_bc_cache> bc;           // betweenness centrality: the row classes of both directions (bc.hip, lazy, owned)
+    vgl_cache<struct vgl_simple_cache> simple;   // k-core, k-truss, minimum spanning forest: the symmetric simple CSR, its edge ids and the edge id of
+                                                 // every stored entry, in three lazy stages (vgl_simple.h, simple.hip; owned)
 };
-// The symmetric simple CSR of the graph (rows ascending by id; the arrays belong to the handle's kcore cache and live as long as the handle), built
-// by this call when the handle has none yet (built_now).  kcore.hip owns the builder; ktruss.hip reads the CSR through this.
-struct vgl_sym_csr {
-    int32_t V = 0;
-    int64_t nnz = 0;                 // 2 E'
-    const int64_t *rowptr = nullptr; // V + 1
-    const int32_t *adj = nullptr;    // 2 E'
-    const int32_t *deg = nullptr;    // V
-    int32_t max_deg = 0;
-    bool built_now = false;
-};
-int vgl_kcore_sym_csr(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *out);      // kcore.hip
-// The library's numbering of the undirected edges of that CSR (the arrays belong to the handle's ktruss cache and live as long as the handle), built by
-// this call -- and the symmetric CSR under it -- when the handle has none yet (built_now).  ktruss.hip owns the builder; msf.hip reads it through this.
-struct vgl_edge_ids {
-    int64_t ne = 0;                  // E'
-    const int32_t *eid = nullptr;    // 2 E': the edge of every slot of the symmetric CSR
-    const int32_t *eu = nullptr;     // E': lo
-    const int32_t *ev = nullptr;     // E': hi
-    bool built_now = false;
-};
-int vgl_ktruss_edge_ids(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_sym_csr *csr, vgl_edge_ids *out);      // ktruss.hip
 
 struct vgl_hip_frontier {
     vgl_hip_graph *g = nullptr;
@@ -302,6 +272,8 @@ int vgl_read_counters(vgl_hip_ctx *ctx, bool fold_shards = true);   // D2H all s
 // seq = vgl_next_seq() is passed to the kernel, vgl_wait_counters(seq) spins until it shows up
 int64_t vgl_next_seq(vgl_hip_ctx *ctx);
 int vgl_wait_counters(vgl_hip_ctx *ctx, int64_t seq);
+// counters of an algorithm's own (n <= C_NSLOTS): cnt[0 .. n) into h_counters by one launch under the timing slot `slot`, then waits for them
+int vgl_publish_counters(vgl_hip_ctx *ctx, const char *slot, const unsigned long long *cnt, int n);
 int vgl_zero_counters(vgl_hip_ctx *ctx, int first, int count);
 int vgl_ensure_partials(vgl_hip_ctx *ctx, size_t n);
 int vgl_build_tile_rows(vgl_hip_ctx *ctx, struct vgl_dir_csr &d, int32_t nrows);     // d.tile_row / d.ntiles from d.rowptr / d.edges (owned by the caller)
@@ -333,6 +305,12 @@ int vgl_bitmap_to_ids(vgl_hip_ctx *c, int64_t words, const uint64_t *d_bits, int
 int vgl_zero_words(vgl_hip_ctx *c, uint64_t *d_words, int64_t words);      // one launch (bfs.hip)
 
 static inline int64_t vgl_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workgroups of a grid-stride launch: one per `per_block` units of work, at least 1, at most cap
+static inline unsigned vgl_grid(int64_t work, int64_t per_block, int64_t cap)
+{
+    const int64_t n = vgl_ceil_div(work, per_block);
+    return (unsigned)(n < 1 ? 1 : n > cap ? cap : n);
+}
 
 // ---------------------------------------------------------------------------------------------
 // device helpers (wave = 64 lanes)
@@ -419,6 +397,56 @@ __device__ __forceinline__ T vgl_wave_reduce_add(T v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+__device__ __forceinline__ void vgl_atomic_add64(int64_t *p, int64_t v) { atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v); }
+// every lane of the wave, once, at the end of a kernel: the wave's sum of m goes to *slot by one atomic (none when it is 0)
+__device__ __forceinline__ void vgl_wave_flush_add(unsigned long long *slot, int64_t m)
+{
+    m = vgl_wave_reduce_add(m);
+    if (vgl_lane() == 0 && m) atomicAdd(slot, (unsigned long long)m);
+}
+// Every lane of the wave calls (uniform control flow).  The lanes with `want` append id to lists[cls] (NCLS lists of `cap` entries each): one returning
+// atomic per wave and class.  tail: the NCLS cumulative list lengths, in global memory or in LDS.
+template <int NCLS>
+__device__ __forceinline__ void vgl_wave_append(bool want, int32_t id, int cls, int32_t *const *lists, int32_t cap, unsigned long long *tail)
+{
+    if (!__any(want)) return;
+    const int lane = vgl_lane();
+#pragma unroll
+    for (int c = 0; c < NCLS; c++) {
+        const bool mine = want && cls == c;
+        const unsigned long long m = __ballot(mine);
+        if (!m) continue;                                             // (uniform)
+        const int leader = __ffsll((long long)m) - 1;
+        unsigned long long base = 0;
+        if (lane == leader) base = atomicAdd(tail + c, (unsigned long long)__popcll(m));
+        base = __shfl(base, leader);
+        if (mine) {
+            const unsigned long long pos = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+            if (pos < (unsigned long long)cap) vgl_store_agent(lists[c] + pos, id);
+        }
+    }
+}
+// the row u of a CSR with rp[u] <= e < rp[u + 1] (0 <= e < rp[V])
+__device__ __forceinline__ int32_t vgl_row_of(const int64_t *rp, int32_t V, int64_t e)
+{
+    int32_t lo = 0, hi = V;                     // invariant: rp[lo] <= e < rp[hi]
+    while (hi - lo > 1) {
+        const int32_t mid = lo + (hi - lo) / 2;
+        if (rp[mid] <= e) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the slot of `w` in the ascending entries [lo, hi) of adj, or -1
+__device__ __forceinline__ int64_t vgl_slot_of(const int32_t *adj, int64_t lo, int64_t hi, int32_t w)
+{
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        const int32_t x = adj[mid];
+        if (x < w) lo = mid + 1; else if (x > w) hi = mid; else return mid;
+    }
+    return -1;
 }
 
 // exclusive block scan (add); smem must hold VGL_WAVES elements of T; returns exclusive prefix, *total = block sum
