@@ -19,6 +19,8 @@ struct Parser {
     GraphStorageFormat format = CSR_GRAPH;      // -format csr | vcsr (VECTOR_CSR_GRAPH: degree-renumbered, the reference's default)
     unsigned long long seed = 1;
     std::string dump, graph_file_name;
+    enum Weights { RANDOM_WEIGHTS, INT_WEIGHTS, ZERO_WEIGHTS } weights = RANDOM_WEIGHTS;            // -weights random | ints | zeros
+    bool accepts_weights = false;               // set by the apps that have edge values to choose (sssp, sswp): every other app refuses -weights
     enum ComputeMode { GENERATE_NEW_GRAPH, LOAD_GRAPH_FROM_FILE, IMPORT_EDGES_CONTAINER } compute_mode = GENERATE_NEW_GRAPH;   // cmd_parser.hpp:58-68
     void parse_args(int argc, char **argv)
     {
@@ -36,6 +38,12 @@ struct Parser {
             else if (a == "-sink") sink = atoi(next());
             else if (a == "-sources") sources = atoi(next());               // bc: how many sources (the first vertices with outgoing edges)
             else if (a == "-klimit") k_limit = atoi(next());                // kcore: stop the peel at this k (0: the whole decomposition)
+            else if (a == "-weights") {
+                if (!accepts_weights) throw "-weights is an option of sssp and sswp only";
+                const std::string w = next();
+                if (w != "random" && w != "ints" && w != "zeros") throw "unknown value for -weights (random, ints or zeros)";
+                weights = w == "ints" ? INT_WEIGHTS : w == "zeros" ? ZERO_WEIGHTS : RANDOM_WEIGHTS;
+            }
             else if (a == "-undirected") undirected = true;
             else if (a == "-import") { graph_file_name = next(); compute_mode = IMPORT_EDGES_CONTAINER; }     // .el_container
             else if (a == "-load" || a == "-file" || a == "-f") { graph_file_name = next(); compute_mode = LOAD_GRAPH_FROM_FILE; }   // .csr / .vcsr graph file
@@ -84,6 +92,15 @@ inline void prepare_graph(VGL_Graph &graph, const Parser &p, DirectionType dir =
     if (p.rmat) GraphGenerationAPI::R_MAT(ec, v, e, 57, 19, 19, 5, dir);      // vgl_runtime.hpp:36
     else GraphGenerationAPI::random_uniform(ec, v, e, dir);
     graph.import(ec);
+}
+
+// edge weights / capacities of sssp and sswp: uniform [0, MAX_WEIGHT) as in the reference, or (-weights ints) the same stream quantised to
+// the integers 0 .. 3 -- mass ties, zero-weight edges and cycles -- or (-weights zeros) all zero
+inline void set_edge_weights(EdgesArray<float> &w, const Parser &p)
+{
+    if (p.weights == Parser::INT_WEIGHTS) w.set_all_random_ints(4);
+    else if (p.weights == Parser::ZERO_WEIGHTS) w.set_all_constant(0.0f);
+    else w.set_all_random(MAX_WEIGHT);
 }
 
 // -source / -sink are ORIGINAL vertex ids: refuse ids outside the graph before they index anything (host conversion tables, checkers)

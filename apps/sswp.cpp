@@ -8,12 +8,13 @@ int main(int argc, char **argv)
     try {
         VGL_RUNTIME::init_library(argc, argv);
         Parser parser;
+        parser.accepts_weights = true;
         parser.parse_args(argc, argv);
         VGL_Graph graph(parser.format);
         prepare_graph(graph, parser);
         VerticesArray<float> widths(graph, SCATTER);
         EdgesArray<float> capacities(graph);
-        capacities.set_all_random(MAX_WEIGHT);
+        set_edge_weights(capacities, parser);
         double avg_perf = 0;
         for (int i = 0; i < parser.get_number_of_rounds(); i++) {
             const int source_vertex = graph.reorder(parser.source >= 0 ? checked_vertex(graph, parser.source, "source") : graph.select_random_nz_vertex(ORIGINAL, i), ORIGINAL, SCATTER);

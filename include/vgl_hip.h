@@ -214,12 +214,21 @@ typedef struct {
 #define VGL_HIP_SSSP_DIRECTION_OPT 4     /* push over the compacted frontier of the rows that changed (atomic minima) while they own few edges,
                                             pull while they own many; the switch is on the share of edges whose source changed in the last
                                             super-step (VGL_SSSP_PULL_SHARE, 0.2) */
+/* Domain of d_weights, for every schedule and plan below: finite, non-negative float32 (+0.0; zero-weight edges and cycles included) whose path
+ * sums stay finite.  Nothing else is assumed: weights of 100 and above, denormal weights (kept, not flushed: every candidate is one IEEE
+ * round-to-nearest f32 addition, also where values travel through the blocked layouts) and weights 200 binades apart are served like any other.
+ * On that domain fl(d + w) is monotone in d and never below d, so the fixed point does not depend on the order of evaluation and the distances
+ * of every mode equal the reference's Bellman-Ford and Dijkstra results in every bit; ties change nothing (an update happens only on a strict
+ * improvement).  Unreached vertices keep FLT_MAX.  Negative, NaN and infinite weights are outside the contract and are not checked for. */
 int vgl_hip_sssp_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_weights, int32_t source, int mode,
                      float *d_dist, vgl_hip_sssp_stats *stats);
 /* SSWP::vgl_dijkstra, algorithms/sswp/widest_paths.hpp:5-76 (single-source widest paths): widths[source] = FLT_MAX, others 0;
  * width[dst] = max(width[dst], min(width[src], capacity)) to the fixed point.  Same kernel and modes as vgl_hip_sssp_run with the
  * (max, min) path algebra; only min / max of the inputs occur, so the result is bit-identical to the reference (and to its
- * sequential checker, seq_widest_paths.hpp:5-64).  d_capacities is indexed like the outgoing CSR (global_edge_pos). */
+ * sequential checker, seq_widest_paths.hpp:5-64).  d_capacities is indexed like the outgoing CSR (global_edge_pos).
+ * Domain of d_capacities: non-negative float32 up to and including FLT_MAX, denormals kept.  A capacity of 0 carries nothing: a vertex
+ * reached only through such edges keeps width 0, like an unreached one.  A capacity of FLT_MAX passes its source's width on unchanged, so
+ * vertices other than the source may end at FLT_MAX. */
 /* super-step pieces of the widest-path algorithm for shards (exchange between steps: allreduce(MAX) of the widths) */
 int vgl_hip_sswp_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, float *d_widths);
 int vgl_hip_sswp_relax_owned(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_capacities, float *d_widths, int *changed);
@@ -247,7 +256,11 @@ int vgl_hip_sswp_run_pull(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_cap
 /* Same operators and bit-identical distances, bucketed schedule (delta-stepping with a light/heavy edge split): light
  * edges (w < delta) of a vertex are relaxed whenever it improves inside the current distance bucket, heavy edges once the
  * bucket has settled.  Cuts the per-edge dist[dst] gathers from ~5 E (Bellman-Ford) to ~1.2 E.  stats->iterations = relax
- * launches.  delta > 0, in the unit of the weights (weights in [0,100): 10..25 works well). */
+ * launches (push_steps / pull_steps stay 0).  delta > 0, in the unit of the weights; it only steers the schedule, never the result (for
+ * weights in [0,100): 10..25 works well -- advice, not a limit on the weights).  Every positive float is served: w == delta is heavy; a delta
+ * above every weight (+inf included: one bucket, every edge light) or not above any (every positive edge heavy) gives a plan with an empty
+ * part; a denormal delta makes a bucket of almost every distinct distance -- correct, and slow in proportion.  delta <= 0 or NaN is refused
+ * with a status and vgl_hip_last_error() text before d_dist is touched. */
 int vgl_hip_sssp_run_delta(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_weights, int32_t source, float delta,
                            float *d_dist, vgl_hip_sssp_stats *stats);
 /* The bucketed schedule works on a plan: a copy of the adjacency + weights in which every row's edges are stably

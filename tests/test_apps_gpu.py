@@ -71,6 +71,41 @@ def test_sswp_app(kind, scale, ef, seed, mode, tmp_path, oracle, ctx):
     assert (np.fromfile(dump, np.float32).view(np.int32) == ref.view(np.int32)).all()
 
 
+def app_weights(O, E, seed, kind):
+    """what -weights ints / zeros gives the apps: the random stream quantised to the integers 0 .. 3 (floor(w * 4 / 100) in f32), or zeros"""
+    w = O.gen_weights(E, seed)
+    if kind == "zeros":
+        return np.zeros_like(w)
+    return np.minimum(np.floor(w * (np.float32(4.0) / np.float32(100.0))), np.float32(3.0)).astype(np.float32)
+
+
+@pytest.mark.parametrize("weights,mode", [("ints", []), ("ints", ["-fused"]), ("zeros", ["-fused"])], ids=["ints_operator_api", "ints_fused", "zeros_fused"])
+@pytest.mark.parametrize("app", ["sssp", "sswp"])
+def test_path_apps_with_quantised_weights(app, weights, mode, tmp_path, oracle, ctx):
+    """-check and the oracle on weights full of ties and zeros (zero-weight cycles on RMAT): the random stream never produces either"""
+    O = oracle
+    kind, scale, ef, seed = CASES[0]
+    src, dst, rowptr, adj, perm = graph(O, kind, scale, ef, seed)
+    source = O.pick_source(rowptr, seed)
+    out, dump = run_app(app, ["-s", scale, "-e", ef, "-type", kind, "-seed", seed, "-source", source, "-check", "-weights", weights] + mode, tmp_path)
+    assert "error count: 0" in out
+    w = app_weights(O, len(src), seed, weights)[perm]
+    if weights == "ints":
+        assert set(np.unique(w)) == {0.0, 1.0, 2.0, 3.0}
+    ref, _ = (O.sssp_bellman_ford if app == "sssp" else O.sswp_bellman_ford)(rowptr, adj, w, source)
+    assert (np.fromfile(dump, np.float32).view(np.int32) == ref.view(np.int32)).all()
+
+
+def test_path_apps_refuse_an_unknown_weights_value(tmp_path, ctx):
+    out = subprocess.run([os.path.join(BIN, "sssp_hip"), "-s", "6", "-weights", "halves"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 1 and "unknown value for -weights" in out.stdout
+
+
+def test_weights_is_an_option_of_the_path_apps_only(tmp_path, ctx):
+    out = subprocess.run([os.path.join(BIN, "bfs_hip"), "-s", "6", "-weights", "ints"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 1 and "-weights is an option of sssp and sswp only" in out.stdout
+
+
 @pytest.mark.parametrize("mode", [[], ["-fused"]], ids=["operator_api", "fused"])
 @pytest.mark.parametrize("kind,scale,ef,seed", CASES)
 def test_hits_app(kind, scale, ef, seed, mode, tmp_path, oracle, ctx):

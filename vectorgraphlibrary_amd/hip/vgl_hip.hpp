@@ -517,6 +517,12 @@ __global__ void vgl_k_fill_values(long long n, T v, T *out)
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = v;
 }
 
+// values in [0, max) -> the integers 0 .. levels-1 as floats (EdgesArray::set_all_random_ints)
+__global__ void vgl_k_quantise_values(long long n, float scale, float top, float *v)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) v[i] = fminf(floorf(v[i] * scale), top);
+}
+
 // ParallelPrimitives::copy_if_indexes (vgl_compute_api/common/copy_if: indexes i in [0, size) with cond(i) > 0, in ascending order):
 // per-workgroup counts, a scan of the (at most 4096) counts on the host, ordered writes with wave ballots
 template <class Cond>
@@ -925,6 +931,19 @@ public:
         VGL_RUNTIME::sync();
         MemoryAPI::free_device_array(w_in);
         version_++;
+    }
+    // API extension: set_all_random's stream quantised to the integers 0 .. levels-1 (floor(w * levels / range), as floats): mass ties and
+    // zero weights on the same edges in both CSR orders.  The range is the generator's own (vgl_hip_gen_weights: uniform [0, 100), whatever
+    // set_all_random is asked for), so the quantisation does not depend on a max_rand of the caller's
+    void set_all_random_ints(int levels)
+    {
+        static_assert(std::is_same<_T, float>::value, "float edge properties");
+        constexpr float gen_range = 100.0f;
+        set_all_random((_T)gen_range);     // (bumps version_; the values change once more below, before anything can have read them)
+        hipLaunchKernelGGL(vgl_k_quantise_values, dim3(1024), dim3(VGL_BLOCK), 0, VGL_RUNTIME::stream(), 2 * edges_count, (float)levels / gen_range,
+                           (float)(levels - 1), edges_data);
+        VGL_HIP_RT(hipGetLastError());
+        VGL_RUNTIME::sync();
     }
     void set_all_constant(_T v)            // both halves (csr_edges_array.hpp)
     {
