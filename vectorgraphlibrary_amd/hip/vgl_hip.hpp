@@ -1259,6 +1259,7 @@ public:
         const bool plan = current_traversal_direction == SCATTER;
         vgl_hip_gnf_buffers b;
         VGL_HIP_CALL(vgl_hip_gnf_begin(c, g.get_handle(), f.get_handle(), plan ? 1 : 0, &b));
+        b.out_rowptr = (const int64_t *)v.rowptr;       // the neighbour count sums the degrees of the generation direction (begin hands out the outgoing rows)
         const vgl_pred_user<C> pred{filter_cond, v.rowptr};
         vgl_launch_gnf_count(VGL_RUNTIME::stream(), pred, b);
         VGL_HIP_RT(hipGetLastError());
