@@ -14,6 +14,7 @@
 struct Parser {
     int scale = 10, avg_degree = 5, rounds = 1, source = -1, sink = -1, walk_vertices_percent = 1, sources = 16, k_limit = 0;
     bool rmat = true, check = false, direction_optimising = false, fused = false, undirected = false, bfs_based = false, blocked = false, deterministic = false, declared = false;
+    bool sources_given = false, incoming = false;
     enum Traversal { PUSH_TRAVERSAL, PULL_TRAVERSAL } traversal = PUSH_TRAVERSAL;                   // cmd_parser.hpp (-push / -pull)
     enum FrontierKind { ALL_ACTIVE_KIND, PARTIAL_ACTIVE_KIND } frontier_kind = ALL_ACTIVE_KIND;     // (-all-active / -partial-active)
     GraphStorageFormat format = CSR_GRAPH;      // -format csr | vcsr (VECTOR_CSR_GRAPH: degree-renumbered, the reference's default)
@@ -36,7 +37,8 @@ struct Parser {
             else if (a == "-dump") dump = next();
             else if (a == "-source") source = atoi(next());
             else if (a == "-sink") sink = atoi(next());
-            else if (a == "-sources") sources = atoi(next());               // bc: how many sources (the first vertices with outgoing edges)
+            else if (a == "-sources") { sources = atoi(next()); sources_given = true; }     // bc, closeness: how many sources (the first vertices with outgoing edges)
+            else if (a == "-in") incoming = true;                           // closeness: distances along incoming entries
             else if (a == "-klimit") k_limit = atoi(next());                // kcore: stop the peel at this k (0: the whole decomposition)
             else if (a == "-weights") {
                 if (!accepts_weights) throw "-weights is an option of sssp and sswp only";

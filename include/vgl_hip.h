@@ -593,6 +593,63 @@ int vgl_hip_msf_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected_
 int vgl_hip_msf_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_weights, int32_t *d_edge_u, int32_t *d_edge_v, float *d_edge_weight,
                     uint8_t *d_in_forest, int32_t *d_component, vgl_hip_msf_stats *stats);
 
+/* Multi-source BFS (`msbfs`, bit-parallel: Then et al., VLDB 2014) and the per-source sums that closeness, harmonic centrality and eccentricity are
+ * made of.  The reference has none, so this comment is the contract:
+ *   graph     the stored DIRECTED, unweighted graph of a handle that owns all rows.  Multi-edges and self-loops have no effect on distances.
+ *   direction 0: d(s, v) counts edges along stored outgoing entries, as vgl_hip_bfs_run does.  1: distances run along incoming entries, so d is the
+ *             distance from v to s.  symmetric = 1: the caller vouches that the stored graph is symmetric, and the outgoing CSR serves everything
+ *             (the rule of vgl_hip_lp_run and vgl_hip_bc_run).
+ *   sources   host array of `count` vertex ids in the graph's numbering.  Batch k is sources[64 k .. 64 k + 63], in the given order; the last batch
+ *             may be partial.  A repeated source is a traversal of its own: two bits may start on one vertex.
+ *   per-source outputs (device arrays of `count` entries in source order; each may be NULL, but at least one output must be given):
+ *             d_reached   int64: the number of vertices with a finite d, the source included;
+ *             d_dist_sum  int64: the sum over those vertices of d(s, v);
+ *             d_ecc       int32: the largest finite d;
+ *             d_harmonic  float64:  h = 0; for d = 1 .. ecc ascending: h = h + (double)n_d / (double)d,  n_d = the number of vertices at distance d.
+ *                         Each value has one writer, takes one IEEE division and one addition per level in that fixed order, and no floating-point
+ *                         atomics; the library is built with -ffp-contract=off and without fast-math, so the value is bit-identical from run to
+ *                         run and to the same loop in numpy float64.
+ *   d_levels  (optional) count x V int32, source-major, indexed with int64: row j holds exactly what vgl_hip_bfs_run writes for sources[j] (the source
+ *             gets 1, unreached vertices get -1).
+ *   Closeness, the Wasserman-Faust scaling and any other normalisation are the callers' business, in float64 (the rule of tri's clustering coefficient).
+ * Method: every vertex carries 64-bit words (seen, cur, nxt: 24 bytes per vertex), bit b = source b of the batch, and the frontier is also kept as
+ * vertex lists, one per row class of the traversal direction (VGL_MSBFS_SHORT 32: 8 lanes per row, VGL_MSBFS_WAVE 1024: a wavefront, longer: one
+ * workgroup per VGL_MSBFS_CHUNK 16384 entries).  A push level walks the listed rows: add = cur[v] & ~seen[w] goes to nxt[w] by a 64-bit atomicOr, and
+ * the lane that found the word empty lists w.  A pull level walks all rows of the reverse CSR: want = live bits & ~seen[v]; a row with want == 0 is not
+ * read, the others OR cur[u] over their entries until want is covered.  A level is a pull iff the reverse CSR of the traversal direction is there
+ * (the incoming CSR for direction 0, the outgoing for 1, the outgoing under symmetric) and the frontier's entries exceed VGL_MSBFS_PULL_SHARE (0.05)
+ * of E; VGL_MSBFS_MODE = auto | push | pull forces the schedule (pull without a reverse CSR is an error); all give identical outputs.  Settle runs over
+ * the new lists only, counts per source with wave-64 ballots, and a 64-thread kernel folds the counts into the outputs and publishes the level's
+ * totals: one host read per level.  The row classes per direction are built by vgl_hip_msbfs_prepare or the first run, cached on the handle and freed
+ * with it.
+ * stats: sources = traversals run; batches = ceil(count / 64); max_depth = the largest ecc; levels_total = sum over the batches of (largest ecc in the
+ * batch + 1): every level with a non-empty frontier is expanded, the last one included; levels_push + levels_pull = levels_total;
+ * reached_total = sum of reached; edges_push = sum over the push levels of the traversal-direction degree of every vertex whose frontier word is
+ * non-zero: exact, and a function of the graph and the sources alone when the schedule is forced to push; edges_pull = entries examined in pull
+ * levels (rows exit early: not pinned); prepared_now = this call built row classes;
+ * algorithmic_bytes = 24 V per batch (the words cleared) + 12 per entry walked (the adjacency entry and one word of its far end) + 12 V per pull
+ * level (the row list and the seen word of every vertex) + 76 per (frontier vertex, level) pair (its list entry written and read twice, nxt read,
+ * seen read and written, cur cleared, its row bounds read by the level and by settle, its class) + with d_levels 4 count V + 4 reached_total;
+ * the atomics' traffic is left out: a lower bound.
+ * Fails, before any output is written: a sharded handle, direction 1 without an incoming CSR and without symmetric = 1, a source outside [0, V),
+ * count < 0, all outputs NULL.  direction 0 without an incoming CSR does not fail: it runs push-only.  count == 0 succeeds and writes nothing. */
+typedef struct {
+    int32_t sources;            /* traversals run */
+    int32_t batches;            /* words of 64 sources */
+    int32_t max_depth;          /* largest ecc over all sources */
+    int32_t prepared_now;       /* this call built row classes */
+    int32_t levels_push;        /* levels expanded top-down */
+    int32_t levels_pull;        /* levels expanded bottom-up */
+    int64_t levels_total;       /* sum over batches of frontiers expanded */
+    int64_t reached_total;      /* sum over sources of vertices reached, source included */
+    int64_t edges_push;         /* entries of the frontier vertices of the push levels: exact */
+    int64_t edges_pull;         /* entries examined by the pull levels */
+    int64_t algorithmic_bytes;
+} vgl_hip_msbfs_stats;
+int vgl_hip_msbfs_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction, int symmetric);
+int vgl_hip_msbfs_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int direction, int symmetric, int64_t *d_reached,
+                      int64_t *d_dist_sum, int32_t *d_ecc, double *d_harmonic, int32_t *d_levels, vgl_hip_msbfs_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

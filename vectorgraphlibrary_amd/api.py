@@ -225,6 +225,11 @@ class Graph:
         """the row classes of betweenness_centrality() now, outside any timing (vgl_hip_bc_prepare)"""
         _l.check(self.ctx.L.vgl_hip_bc_prepare(self.ctx.h, self.h, int(bool(symmetric))))
 
+    def prepare_msbfs(self, direction="out", symmetric=False):
+        """the row classes of multi_source_bfs() (and of closeness_centrality(), harmonic_centrality(), eccentricity()) for `direction` now, outside
+        any timing (vgl_hip_msbfs_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_msbfs_prepare(self.ctx.h, self.h, {"out": 0, "in": 1}[direction], int(bool(symmetric))))
+
     def prepare_kcore(self):
         """the symmetric simple CSR of core_numbers() / k_core() now, outside any timing (vgl_hip_kcore_prepare)"""
         _l.check(self.ctx.L.vgl_hip_kcore_prepare(self.ctx.h, self.h))
@@ -563,6 +568,70 @@ def betweenness_centrality(graph, sources=None, symmetric=False, rescale=False, 
     if halve:
         out = out * 0.5
     return (out[idx] if to_orig else out), stats
+
+
+def _source_ids(graph, sources, raw, who):
+    """sources (None = every vertex; ORIGINAL ids unless raw) -> list of ids in the graph's own numbering"""
+    V = graph.V
+    if sources is None:
+        ids = list(range(V))
+    else:
+        ids = [int(s) for s in (sources.tolist() if torch.is_tensor(sources) else sources)]
+    if not raw and graph.fwd is not None and ids:
+        if min(ids) < 0 or max(ids) >= V:
+            raise _l.VglHipError(who + ": source vertex out of range")
+        fwd = graph.fwd.cpu()
+        ids = [int(fwd[s]) for s in ids]
+    return ids
+
+
+def multi_source_bfs(graph, sources=None, direction="out", symmetric=False, want_levels=False, raw=False):
+    """bit-parallel multi-source BFS (the contract of vgl_hip_msbfs_run in include/vgl_hip.h): 64 traversals per pass over the adjacency.
+    sources: None = every vertex, else a sequence / tensor of ORIGINAL vertex ids (raw=True: the graph's own ids); a repeated source is a traversal of
+    its own.  direction "out": d(s, v) along stored outgoing entries; "in": along incoming entries (the distance from v to s).  symmetric=True: the
+    caller vouches that every edge is stored both ways (no incoming CSR needed).  Returns (dict of per-source tensors in source order -- "reached"
+    int64, "dist_sum" int64, "ecc" int32, "harmonic" float64 and, with want_levels, "levels" int32 [len(sources), V] with the columns in ORIGINAL
+    order unless raw -- , stats dict)."""
+    ctx = graph.ctx
+    V = graph.V
+    ids = _source_ids(graph, sources, raw, "multi_source_bfs")
+    n = len(ids)
+    src = (C.c_int32 * max(n, 1))(*ids)
+    res = {"reached": ctx.empty(n, torch.int64), "dist_sum": ctx.empty(n, torch.int64), "ecc": ctx.empty(n, torch.int32),
+           "harmonic": ctx.empty(n, torch.float64)}
+    levels = torch.empty((n, V), dtype=torch.int32, device=ctx.device) if want_levels else None
+    st = _l.MsbfsStats()
+    _l.check(ctx.L.vgl_hip_msbfs_run(ctx.h, graph.h, src, n, {"out": 0, "in": 1}[direction], int(bool(symmetric)), _ptr(res["reached"]),
+                                     _ptr(res["dist_sum"]), _ptr(res["ecc"]), _ptr(res["harmonic"]), _ptr(levels), C.byref(st)))
+    if want_levels:
+        res["levels"] = levels if (raw or graph.fwd is None) else levels[:, graph.fwd.long()]
+    return res, _stats(st)
+
+
+def closeness_centrality(graph, sources=None, direction="in", symmetric=False, wf_improved=True, raw=False):
+    """closeness centrality of `sources` (None = every vertex), float64 in source order: (r - 1) / dist_sum, r = vertices reached, times
+    (r - 1) / (V - 1) when wf_improved (Wasserman and Faust), 0 where dist_sum == 0.  The default direction "in" is networkx's convention on a
+    directed graph (distances TO the vertex).  Returns (closeness, stats dict)."""
+    res, stats = multi_source_bfs(graph, sources, direction, symmetric, raw=raw)
+    r1 = (res["reached"] - 1).to(torch.float64)
+    tot = res["dist_sum"].to(torch.float64)
+    c = torch.where(tot > 0, r1 / torch.clamp(tot, min=1.0), torch.zeros_like(tot))
+    if wf_improved and graph.V > 1:
+        c = c * (r1 / float(graph.V - 1))
+    return c, stats
+
+
+def harmonic_centrality(graph, sources=None, direction="in", symmetric=False, raw=False):
+    """harmonic centrality of `sources` (None = every vertex), float64 in source order: the sum over the other vertices of 1 / d, added level by
+    level in ascending d (bit-identical from run to run).  Returns (harmonic, stats dict)."""
+    res, stats = multi_source_bfs(graph, sources, direction, symmetric, raw=raw)
+    return res["harmonic"], stats
+
+
+def eccentricity(graph, sources=None, direction="out", symmetric=False, raw=False):
+    """the largest finite distance from every source (None = every vertex), int32 in source order.  Returns (eccentricity, stats dict)."""
+    res, stats = multi_source_bfs(graph, sources, direction, symmetric, raw=raw)
+    return res["ecc"], stats
 
 
 def core_numbers(graph, k_limit=0, degree=False, raw=False):

@@ -50,6 +50,12 @@ class TriStats(C.Structure):
                 ("rows_table", C.c_int64), ("rows_huge", C.c_int64)]
 
 
+class MsbfsStats(C.Structure):
+    _fields_ = [("sources", C.c_int32), ("batches", C.c_int32), ("max_depth", C.c_int32), ("prepared_now", C.c_int32),
+                ("levels_push", C.c_int32), ("levels_pull", C.c_int32), ("levels_total", C.c_int64), ("reached_total", C.c_int64),
+                ("edges_push", C.c_int64), ("edges_pull", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class BcStats(C.Structure):
     _fields_ = [("sources", C.c_int32), ("max_depth", C.c_int32), ("sigma_inexact", C.c_int32), ("prepared_now", C.c_int32),
                 ("levels_total", C.c_int64), ("reached_total", C.c_int64), ("edges_forward", C.c_int64), ("edges_backward", C.c_int64),
@@ -154,6 +160,8 @@ _SIGNATURES = {
     "vgl_hip_tri_run": [_p, _p, C.POINTER(_i64), _p, _p, C.POINTER(TriStats)],
     "vgl_hip_bc_prepare": [_p, _p, _int],
     "vgl_hip_bc_run": [_p, _p, C.POINTER(_i32), _i32, _int, _int, _p, _p, _p, _p, C.POINTER(BcStats)],
+    "vgl_hip_msbfs_prepare": [_p, _p, _int, _int],
+    "vgl_hip_msbfs_run": [_p, _p, C.POINTER(_i32), _i32, _int, _int, _p, _p, _p, _p, _p, C.POINTER(MsbfsStats)],
     "vgl_hip_kcore_prepare": [_p, _p],
     "vgl_hip_kcore_run": [_p, _p, _i32, _p, _p, C.POINTER(KcoreStats)],
     "vgl_hip_ktruss_prepare": [_p, _p, C.POINTER(_i64)],
