@@ -650,6 +650,74 @@ int vgl_hip_msbfs_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int direction, int
 int vgl_hip_msbfs_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int direction, int symmetric, int64_t *d_reached,
                       int64_t *d_dist_sum, int32_t *d_ecc, double *d_harmonic, int32_t *d_levels, vgl_hip_msbfs_stats *stats);
 
+/* Biconnectivity (`bicc`): bridges, cut vertices (articulation points), biconnected components (blocks) and 2-edge-connected components of the simple
+ * undirected graph.  The reference has none, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.  Loops,
+ *             parallel entries and antiparallel entries do not matter: an edge stored twice is still a bridge if it is one.
+ *   edges     carry the library's edge numbering of vgl_hip_ktruss_run (ascending (lo, hi) in the graph's own vertex numbering, E' < 2^31), taken from
+ *             the handle's cache (built if absent, shared with ktruss and msf afterwards).  The blocks are a partition of exactly these E' edges.
+ *   outputs   (device; each may be NULL, but at least one must be given; the edge arrays are sized by the caller like k-truss's: E' <= stored entries)
+ *             d_edge_u / d_edge_v      int32, E', both or neither: lo, hi of edge i;
+ *             d_bridge                 uint8, E': 1 iff removing the edge disconnects its component;
+ *             d_edge_component         int32, E': the block of the edge = the SMALLEST EDGE ID in that block; a bridge is a block of its own, its
+ *                                      label is its own id;
+ *             d_articulation           uint8, V: 1 iff removing the vertex disconnects its component; an isolated vertex is no cut vertex;
+ *             d_two_edge_component     int32, V: the SMALLEST VERTEX ID of the vertex's component of (graph minus bridges); an isolated vertex is a
+ *                                      component of its own.
+ *             All ids are in the graph's own numbering.
+ *   The answer does not depend on any VGL_BICC_* switch, on the order of the entries in a row, on which parent a vertex gets in the forest or on the
+ *   order in which the atomics land: every output is an integer and unique.
+ * Method: the Tarjan-Vishkin reduction on a rooted BFS forest of the symmetric simple CSR.  A lock-free union-find over the E'
+ * edges (the larger root hooked under the smaller by compare-and-swap: a find walks strictly decreasing ids, no thread waits for another) makes the
+ * smallest vertex of every component its root.  One level-synchronous top-down BFS from all roots at once -- rows by length: <= VGL_BICC_SHORT (32) 8
+ * lanes per row, <= VGL_BICC_WAVE (1024) a wavefront, longer a workgroup; one host read per level -- records level, parent and the vertices in level
+ * order.  Per level and without host reads: size[v] of the subtrees (deepest level first), pre[v] (top level first; a child takes pre[p] + 1 + what its
+ * earlier siblings took: the sibling order is arbitrary, subtree(v) = [pre[v], pre[v] + size[v]) is all that is used), and low / high[v] = min / max of
+ * pre over subtree(v) and the far ends of its non-tree entries (a row pass with one writer per row, then integer atomicMin / atomicMax up the levels).
+ * Per edge: a tree edge (child c, parent p) is a bridge iff low[c] >= pre[c] and high[c] < pre[c] + size[c]; if p is no root and low[c] < pre[p] or
+ * high[c] >= pre[p] + size[p], the tree edges of c and p are united; a non-tree edge (a, b) unites the tree edges of a and b (in a BFS forest it never
+ * joins a vertex to its ancestor).  The classes of that union-find over the tree edges (named by their child) are the blocks: the block of a tree
+ * edge is that of its child, the block of a non-tree edge that of either end; the label is an atomicMin of the edge ids per class.  A cut vertex is a
+ * row whose entries' edges carry two different labels.  A third union-find over the tree edges that are no bridges gives the 2-edge-connected
+ * components; its roots are the smallest ids.  Work is O(V + E') in O(depth) launches; no cooperative launch, no grid barrier, no wait on a flag.
+ * stats, all exact and the same on every run:
+ *   undirected_edges = E'; components = connected components, isolated vertices included; bridges; articulation_points; biconnected_components;
+ *   two_edge_components (= components + bridges); largest_component_edges = edges of the largest block (0 when E' = 0);
+ *   depth = 1 + the largest BFS level, levels counted from the smallest vertex id of every component (0 when V = 0); prepared_now = this call built the
+ *   edge numbering (stage 2 of the handle's cache).  articulation_points, biconnected_components and largest_component_edges are -1 when neither
+ *   d_edge_component nor d_articulation was asked for: the block pass is then skipped.
+ *   algorithmic_bytes, with nnz = 2 E' the entries of the symmetric CSR:
+ *     92 V + 16 nnz + 24 E' + 104 (depth + 1)
+ *       (V: degree read, union-find, level, size and cursor initialised 20; the root test 4; per BFS vertex its list entry written and read, its row
+ *        bounds, level and parent written 24; pre: list entry, parent, size read, pre written 16; the local pass: list entry, row bounds, parent, pre
+ *        read, low and high written 28.  nnz: the BFS and the local pass each read the entry and one word of its far end.  E': the endpoints read by the
+ *        roots' union-find 8, endpoints and both parents read per edge 16.  depth: the 13 counters published per level and once after the seed.)
+ *     + 16 E' with d_edge_u / d_edge_v (the endpoint arrays copied)  + E' with d_bridge
+ *     + 33 V + 20 E' + 8 nnz when the block pass runs (V: the block union-find initialised and flattened 12, the smallest edge and the edge count per
+ *        class initialised 8, the counts read 4, row bounds read and the flag written 9; E': the naming vertex written, read and replaced by the root,
+ *        read and replaced by the label 20; nnz: the edge id of the slot and its label)
+ *     + 12 V with d_two_edge_component (its union-find initialised, read and the label written).
+ *     The size and low / high passes up the levels, the union-finds' walks, pre / low / high / size read per tree edge and the atomics' traffic are
+ *     left out: a lower bound.  0 when V = 0.
+ * Fails, before anything is written: a sharded handle, all six output pointers NULL, one of d_edge_u / d_edge_v without the other, E' >= 2^31 (from
+ * the cache stage, as k-truss). */
+typedef struct {
+    int32_t depth;                      /* 1 + the largest BFS level from the smallest vertex of every component */
+    int32_t prepared_now;               /* this call built the edge numbering */
+    int64_t undirected_edges;           /* E' */
+    int64_t components;                 /* connected components, isolated vertices included */
+    int64_t bridges;
+    int64_t articulation_points;        /* -1 when the block pass was skipped */
+    int64_t biconnected_components;     /* -1 when the block pass was skipped */
+    int64_t two_edge_components;
+    int64_t largest_component_edges;    /* edges of the largest block; -1 when the block pass was skipped */
+    int64_t algorithmic_bytes;
+} vgl_hip_bicc_stats;
+int vgl_hip_bicc_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected_edges);
+int vgl_hip_bicc_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t *d_edge_u, int32_t *d_edge_v, uint8_t *d_bridge, int32_t *d_edge_component,
+                     uint8_t *d_articulation, int32_t *d_two_edge_component, vgl_hip_bicc_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

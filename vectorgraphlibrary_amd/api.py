@@ -248,6 +248,13 @@ class Graph:
         _l.check(self.ctx.L.vgl_hip_msf_prepare(self.ctx.h, self.h, C.byref(n)))
         return n.value
 
+    def prepare_bicc(self):
+        """the edge numbering of biconnected_components() / bridges() (and the symmetric simple CSR it shares with core_numbers()) now, outside any
+        timing (vgl_hip_bicc_prepare); returns the number of undirected edges"""
+        n = C.c_int64()
+        _l.check(self.ctx.L.vgl_hip_bicc_prepare(self.ctx.h, self.h, C.byref(n)))
+        return n.value
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -731,6 +738,83 @@ def minimum_spanning_forest(graph, weights, component=False, raw=False):
     if component:
         stats["component"] = graph.to_original(graph.bwd[comp.long()]) if to_orig else comp
     return float(st.total_weight), stats
+
+
+def _bicc(graph, raw, edges=False, bridge=False, edge_component=False, articulation=False, two_edge_component=False):
+    """one vgl_hip_bicc_run with the outputs named; what is not named goes as NULL.  Returns the stats dict with the tensors asked for."""
+    ctx = graph.ctx
+    cap = max(graph.E, 1)                                           # E' <= the stored entries: the run itself tells E' (and whether it prepared)
+    eu = ctx.empty(cap, torch.int32) if edges else None
+    ev = ctx.empty(cap, torch.int32) if edges else None
+    br = ctx.empty(cap, torch.uint8) if bridge else None
+    lab = ctx.empty(cap, torch.int32) if edge_component else None
+    art = ctx.empty(graph.V, torch.uint8) if articulation else None
+    two = ctx.empty(graph.V, torch.int32) if two_edge_component else None
+    st = _l.BiccStats()
+    _l.check(ctx.L.vgl_hip_bicc_run(ctx.h, graph.h, _ptr(eu), _ptr(ev), _ptr(br), _ptr(lab), _ptr(art), _ptr(two), C.byref(st)))
+    stats = _stats(st)
+    n = int(st.undirected_edges)
+    to_orig = not raw and graph.bwd is not None
+    order = None
+    if edges:
+        eu, ev = eu[:n], ev[:n]
+        if to_orig and n:
+            a, b = graph.bwd[eu.long()], graph.bwd[ev.long()]
+            eu, ev = torch.minimum(a, b), torch.maximum(a, b)
+            order = torch.argsort(eu.long() * graph.V + ev.long())
+            eu, ev = eu[order], ev[order]
+        stats["edges"] = torch.stack([eu, ev], dim=1)
+    if bridge:
+        br = br[:n].bool()
+        stats["bridge"] = br[order] if order is not None else br
+    if edge_component:
+        lab = lab[:n]
+        if order is not None:                                         # canonical again: the smallest row, in the returned order, of the block
+            lab = lab[order].long()
+            first = torch.full((n,), n, dtype=torch.int64, device=ctx.device)
+            first.scatter_reduce_(0, lab, torch.arange(n, device=ctx.device), "amin")
+            lab = first[lab].to(torch.int32)
+        stats["edge_component"] = lab
+    if articulation:
+        art = art.bool()
+        stats["articulation"] = graph.to_original(art.to(torch.int32)).bool() if to_orig else art
+    if two_edge_component:
+        if to_orig:                                                   # canonical again: the smallest ORIGINAL id of the component
+            lab = two.long()
+            first = torch.full((graph.V,), graph.V, dtype=torch.int64, device=ctx.device)
+            first.scatter_reduce_(0, lab, graph.bwd.long(), "amin")
+            two = graph.to_original(first[lab].to(torch.int32))
+        stats["two_edge_component"] = two
+    return stats
+
+
+def biconnected_components(graph, raw=False):
+    """bridges, cut vertices, biconnected components (blocks) and 2-edge-connected components of the simple undirected graph underlying the stored
+    outgoing CSR (the contract of vgl_hip_bicc_run in include/vgl_hip.h).  Returns (number of blocks, stats dict); of the E' undirected edges:
+    stats["edges"] (int32 [E', 2], lo < hi), stats["edge_component"] (int32 [E']: the block of the edge, named by the smallest row index of an
+    edge of that block), stats["bridge"] (bool [E']); of the vertices: stats["articulation"] (bool [V]) and stats["two_edge_component"] (int32 [V]:
+    the smallest vertex id of the vertex's component once the bridges are removed).  Endpoints and vertex arrays are in ORIGINAL ids, the edges ascend
+    by (lo, hi) and both labellings are canonical in that numbering unless raw=True, which keeps the graph's own numbering and its edge order."""
+    stats = _bicc(graph, raw, edges=True, bridge=True, edge_component=True, articulation=True, two_edge_component=True)
+    return int(stats["biconnected_components"]), stats
+
+
+def bridges(graph, raw=False):
+    """the bridges of that graph: an int32 tensor [n, 2], lo < hi, in the order of biconnected_components(); the block pass is skipped"""
+    stats = _bicc(graph, raw, edges=True, bridge=True)
+    return stats["edges"][stats["bridge"]]
+
+
+def articulation_points(graph, raw=False):
+    """the cut vertices of that graph: ascending vertex ids (int64), ORIGINAL unless raw=True"""
+    stats = _bicc(graph, raw, articulation=True)
+    return torch.nonzero(stats["articulation"]).flatten()
+
+
+def two_edge_connected_components(graph, raw=False):
+    """int32 [V]: the smallest vertex id of every vertex's 2-edge-connected component (ORIGINAL ids and vertex order unless raw=True); the block pass
+    is skipped"""
+    return _bicc(graph, raw, two_edge_component=True)["two_edge_component"]
 
 
 def count_not_equal(ctx, a, b):

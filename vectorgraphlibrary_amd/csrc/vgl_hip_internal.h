@@ -232,7 +232,7 @@ struct vgl_hip_graph {
     vgl_cache<struct vgl_tri_cache> tri;         // triangle counting: the oriented CSR, undirected degrees and row classes (tri.hip, lazy, owned)
     vgl_cache<struct vgl_bc_cache> bc;           // betweenness centrality: the row classes of both directions (bc.hip, lazy, owned)
     vgl_cache<struct vgl_msbfs_cache> msbfs;     // multi-source BFS: the row classes and the rows by class of both directions (msbfs.hip, lazy, owned)
-    vgl_cache<struct vgl_simple_cache> simple;   // k-core, k-truss, minimum spanning forest: the symmetric simple CSR, its edge ids and the edge id of
+    vgl_cache<struct vgl_simple_cache> simple;   // k-core, k-truss, minimum spanning forest, biconnectivity: the symmetric simple CSR, its edge ids and the edge id of
                                                  // every stored entry, in three lazy stages (vgl_simple.h, simple.hip; owned)
 };
 

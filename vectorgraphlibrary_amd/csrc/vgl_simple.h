@@ -1,5 +1,5 @@
 // vgl_simple.h -- the simple undirected graph under the stored outgoing CSR (loops dropped, parallel and antiparallel entries merged), built in
-// simple.hip for tri, kcore, ktruss and msf.  DESIGN section 18.
+// simple.hip for tri, kcore, ktruss, msf and bicc.  DESIGN section 18.
 #pragma once
 #include "vgl_hip_internal.h"
 

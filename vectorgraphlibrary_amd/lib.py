@@ -78,6 +78,12 @@ class MsfStats(C.Structure):
                 ("undirected_edges", C.c_int64), ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64), ("total_weight", C.c_double)]
 
 
+class BiccStats(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("prepared_now", C.c_int32), ("undirected_edges", C.c_int64), ("components", C.c_int64),
+                ("bridges", C.c_int64), ("articulation_points", C.c_int64), ("biconnected_components", C.c_int64),
+                ("two_edge_components", C.c_int64), ("largest_component_edges", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -168,6 +174,8 @@ _SIGNATURES = {
     "vgl_hip_ktruss_run": [_p, _p, _i32, _p, _p, _p, _p, C.POINTER(KtrussStats)],
     "vgl_hip_msf_prepare": [_p, _p, C.POINTER(_i64)],
     "vgl_hip_msf_run": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(MsfStats)],
+    "vgl_hip_bicc_prepare": [_p, _p, C.POINTER(_i64)],
+    "vgl_hip_bicc_run": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(BiccStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
