@@ -103,6 +103,10 @@ int vgl_hip_graph_create(vgl_hip_ctx *ctx, int32_t V, int32_t row_begin, int32_t
                          const int64_t *d_in_rowptr, const int32_t *d_in_adj, int64_t in_edges,
                          vgl_hip_graph **out);
 int vgl_hip_graph_destroy(vgl_hip_ctx *ctx, vgl_hip_graph *g);
+/* what creation derived for the bottom-up BFS: owned rows with incoming edges (one head record each per plane), and whether the head
+ * records are held in the 12-byte form (four 24-bit ids) instead of 16-byte int4 records (VGL_BFS_HEADS=auto|wide|packed at creation;
+ * packed only when every id in a record is below 0xFFFFFF).  Either pointer may be NULL. */
+int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed);
 
 /* ---- frontier (BaseFrontier, base_frontier.h:5-62; sparsity enum framework_types.h:156-160) ---- */
 #define VGL_HIP_FRONTIER_DENSE 0

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B of direction-optimising BFS variants on ONE graph build (GPU box): every argument is a variant "NAME:K=V,K=V" of environment
-switches the library reads per call (DESIGN 'Run-time switches'); each variant runs the bench's sources (4 warm-up + N timed), is checked
+switches the library reads per call (DESIGN 'Run-time switches'; VGL_BFS_HEADS, which is read when a graph handle is created, gives the
+variant a handle of its own over the same CSR arrays, created once); each variant runs the bench's sources (4 warm-up + N timed), is checked
 against the top-down levels of every source, and is timed twice: wall time without event brackets, then per kernel with all brackets.
 usage: python3 profiles/microbench/bfs_ab.py [--scale 24] [--steps 32] base: new:VGL_X=1 ..."""
 import argparse
@@ -29,6 +30,18 @@ src, dst = ctx.gen_rmat(args.scale, 32, 1)
 g = api.Graph.from_coo(ctx, V, src, dst, with_incoming=True, renumber="total")
 E = g.E
 del src, dst
+handles = {None: g}
+
+
+def handle_for(heads):
+    """the handle whose head records were built under VGL_BFS_HEADS=heads (same device CSR, own derived data)"""
+    if heads not in handles:
+        os.environ["VGL_BFS_HEADS"] = heads
+        handles[heads] = api.Graph(ctx, V, g.out_rowptr, g.out_adj, g.in_rowptr, g.in_adj)
+        print(f"handle for VGL_BFS_HEADS={heads}: {handles[heads].info()}", flush=True)
+    return handles[heads]
+
+
 sources = bench.pick_sources(g.out_rowptr, args.steps + args.warmup, 1)
 ref = {}
 for s in sources:
@@ -46,6 +59,7 @@ for rnd in range(args.rounds):
         for k in touched:
             os.environ.pop(k, None)
         os.environ.update(env)
+        g = handle_for(env.get("VGL_BFS_HEADS"))
         bad = 0
         for s in sources[:args.warmup]:
             api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)

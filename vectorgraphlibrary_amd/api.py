@@ -196,6 +196,12 @@ class Graph:
         s.fwd, s.bwd = self.fwd, self.bwd
         return s
 
+    def info(self):
+        """what creation derived for the bottom-up BFS (vgl_hip_graph_info): rows with incoming edges, and the form of their head records"""
+        n, p = C.c_int32(), C.c_int()
+        _l.check(self.ctx.L.vgl_hip_graph_info(self.h, C.byref(n), C.byref(p)))
+        return {"in_nz_rows": n.value, "bfs_heads": "packed" if p.value else "wide"}
+
     def out_edge_range(self, row_begin, row_end):
         return int(self.out_rowptr[row_begin]), int(self.out_rowptr[row_end])
 

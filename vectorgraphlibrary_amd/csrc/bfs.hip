@@ -8,8 +8,9 @@
 // Kernels and what bounds them (all HBM/L2-latency bound gathers, no MFMA):
 //   gnf count/scan/write (vgl_gnf.h)   : V*4 B streamed per pass
 //   vgl_k_td_expand                    : per examined edge 4 B adjacency (coalesced) + bitmap probe (L2) [+4 B levels]
-//   vgl_k_bu_probe                     : per unvisited vertex 16 B row offsets + up to 8 adjacency probes (thread-serial),
-//                                        remaining long rows strip-mined 16 lanes per vertex by the same workgroup
+//   vgl_k_bu_probe / vgl_k_bu_probe_wide: per unvisited vertex one or two head records (12 B each when every head id is below 0xFFFFFF, else 16 B)
+//                                        + up to 8 frontier-bit probes (thread-serial), remaining long rows strip-mined 16 lanes per vertex
+//                                        by the same workgroup
 #include "vgl_hip_internal.h"
 #include <chrono>
 #include "vgl_gnf.h"
@@ -790,13 +791,31 @@ typedef int vgl_int4_u __attribute__((ext_vector_type(4), aligned(4)));     // 1
 // cost ~15 us per level even when it had nothing to scan, three levels per traversal; it dates from the time of contiguous chunks and was
 // removed).  The 64-row groups are dealt round-robin to the wavefronts of the grid, so the deferred rows -- the hubs, i.e. the first ids of a
 // degree-sorted graph -- are spread over all workgroups by construction.  (Only <true> exists; the template keeps the kernel's name.)
-template <bool INLINE_HEAVY>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32_t row_base, int32_t chunk, const int64_t *in_rowptr,
-                                                            const int32_t *in_adj, const uint64_t *visited, const uint64_t *in_nz,
-                                                            const uint64_t *front, uint64_t *next, int32_t *levels, int32_t next_level,
-                                                            int32_t *heavy, int64_t *partials, uint32_t *ticket, const int4 *in_head,
-                                                            const uint64_t *in_long, const int32_t *nz_rank, int32_t nz_rows, int64_t *counters,
-                                                            volatile int64_t *host, int64_t seq)
+// Per-launch durations since the 12-byte records (below): first bottom-up level 45-206 us, second 27-52, third 17-25.
+// PACKED: the head records are 12 bytes -- four 24-bit little-endian ids in three words, 0xFFFFFF = absent (vgl_k_pack_heads; graphs whose head
+// ids are all below 0xFFFFFF) -- loaded as ONE 12-byte load per lane under the condition the 16-byte load has, and decoded into the same
+// u0[] / u1[] values: same probes, same order, same counters, three quarters of the bytes.
+typedef unsigned vgl_uint3_u __attribute__((ext_vector_type(3), aligned(4)));     // 12-byte load from a 4-byte aligned address
+template <bool PACKED>
+__device__ __forceinline__ void vgl_load_head(const int4 *in_head, int64_t rec, int32_t u[4])
+{
+    if constexpr (PACKED) {
+        const vgl_uint3_u w = *reinterpret_cast<const vgl_uint3_u *>(reinterpret_cast<const uint32_t *>(in_head) + 3 * rec);
+        const uint32_t f[4] = {w.x & 0xFFFFFFu, (w.x >> 24) | ((w.y & 0xFFFFu) << 8), (w.y >> 16) | ((w.z & 0xFFu) << 16), w.z >> 8};
+#pragma unroll
+        for (int q = 0; q < 4; q++) u[q] = f[q] == 0xFFFFFFu ? -1 : (int32_t)f[q];
+    } else {
+        const int4 h = in_head[rec];
+        u[0] = h.x; u[1] = h.y; u[2] = h.z; u[3] = h.w;
+    }
+}
+template <bool INLINE_HEAVY, bool PACKED>
+__device__ __forceinline__ void vgl_bu_probe_body(int32_t nrows, int32_t row_base, int32_t chunk, const int64_t *in_rowptr,
+                                                  const int32_t *in_adj, const uint64_t *visited, const uint64_t *in_nz,
+                                                  const uint64_t *front, uint64_t *next, int32_t *levels, int32_t next_level,
+                                                  int32_t *heavy, int64_t *partials, uint32_t *ticket, const int4 *in_head,
+                                                  const uint64_t *in_long, const int32_t *nz_rank, int32_t nz_rows, int64_t *counters,
+                                                  volatile int64_t *host, int64_t seq)
 {
     static_assert(INLINE_HEAVY, "the deferred rows are scanned in the same launch");
     __shared__ int64_t s64[VGL_WAVES];
@@ -842,8 +861,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32
                 // row offsets, no dependent adjacency load): most candidates find their parent among the first four, the rest look
                 // at the next four; a row that still misses and is longer than eight goes to the wavefront pass.  (Requesting the next
                 // group's records before waiting for this group's probes was tried: no change.)
-                const int4 h = in_head[rec];
-                const int32_t u0[4] = {h.x, h.y, h.z, h.w};
+                int32_t u0[4];
+                vgl_load_head<PACKED>(in_head, rec, u0);
                 uint32_t hit = 0;
                 int n = 0;
 #pragma unroll
@@ -860,8 +879,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32
                 }
                 bool longer = false;
                 if (hit == 0 && n == 4) {
-                    const int4 k = in_head[(int64_t)nz_rows + rec];
-                    const int32_t u1[4] = {k.x, k.y, k.z, k.w};
+                    int32_t u1[4];
+                    vgl_load_head<PACKED>(in_head, (int64_t)nz_rows + rec, u1);
 #pragma unroll
                     for (int q = 0; q < 4; q++)
                         if (u1[q] >= 0) { n = 5 + q; hit |= in_front(u1[q]) << (4 + q); }
@@ -925,6 +944,30 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe(int32_t nrows, int32
         if (host) vgl_publish2(counters, host, seq, C_BU_FOUND, f, C_BU_EDGES, pr);
         else { counters[C_BU_FOUND] = f; counters[C_BU_EDGES] = pr; }
     }
+}
+// The two forms are two kernels, and the packed one is held to 80 scalar registers.  The launch is 2048 workgroups = exactly eight wavefronts per SIMD,
+// and it only has them all resident while a wavefront takes at most 80 SGPRs: with both bodies in one kernel (96 SGPRs) EITHER form ran 37 % longer
+// (243 against 177 us of probe kernels per RMAT-24 traversal), and so did the packed body alone as the compiler first allocated it (88 SGPRs, 241 us)
+// although the compiler's own occupancy figure is 8 in all three cases.  At 80 the packed kernel spills one scalar to a lane outside the probe loop.
+// Measured on RMAT-24 (driver's 20 sources, rocprofv3 kernel trace, parent -> packed): first bottom-up level 106.7 -> 99.9 us (50 - 224 -> 45 - 206),
+// second 38.5 -> 36.9, third 21.1 -> 21.2; FETCH_SIZE per launch 68.6 -> 58.3 MiB; traversal 0.318 - 0.321 -> 0.308 - 0.319 ms.
+// The packed form keeps the name vgl_k_bu_probe<true>: it is what runs on every graph whose ids fit, the flagship included.
+#define VGL_BU_PROBE_PARAMS                                                                                                                             \
+    int32_t nrows, int32_t row_base, int32_t chunk, const int64_t *in_rowptr, const int32_t *in_adj, const uint64_t *visited, const uint64_t *in_nz,  \
+        const uint64_t *front, uint64_t *next, int32_t *levels, int32_t next_level, int32_t *heavy, int64_t *partials, uint32_t *ticket,               \
+        const int4 *in_head, const uint64_t *in_long, const int32_t *nz_rank, int32_t nz_rows, int64_t *counters, volatile int64_t *host, int64_t seq
+#define VGL_BU_PROBE_ARGS                                                                                                                               \
+    nrows, row_base, chunk, in_rowptr, in_adj, visited, in_nz, front, next, levels, next_level, heavy, partials, ticket, in_head, in_long, nz_rank,    \
+        nz_rows, counters, host, seq
+template <bool INLINE_HEAVY>
+__global__ __launch_bounds__(VGL_BLOCK) __attribute__((amdgpu_num_sgpr(80))) void vgl_k_bu_probe(VGL_BU_PROBE_PARAMS)            // 12-byte records
+{
+    vgl_bu_probe_body<INLINE_HEAVY, true>(VGL_BU_PROBE_ARGS);
+}
+template <bool INLINE_HEAVY>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe_wide(VGL_BU_PROBE_PARAMS)       // 16-byte records: ids of 24 bits and more (RMAT-27 and its shards)
+{
+    vgl_bu_probe_body<INLINE_HEAVY, false>(VGL_BU_PROBE_ARGS);
 }
 
 // visited |= next; front = next; next = 0 (ready for the next emitting step without a memset)   (one word per thread)
@@ -1160,7 +1203,8 @@ static int vgl_bfs_bu_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, 
     const int64_t seq = vgl_next_seq(c);
     {
         vgl_timed_launch tl(c, "bfs_bottom_up");
-        hipLaunchKernelGGL(vgl_k_bu_probe<true>, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
+        auto *kernel = g->in_head_packed ? vgl_k_bu_probe<true> : vgl_k_bu_probe_wide<true>;
+        hipLaunchKernelGGL(kernel, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
                            g->in.rowptr, g->in.adj, visited, g->bm_in_nz, front, next, levels, next_level, g->heavy, g->bu_partials,
                            g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head.p), g->bm_in_long,
                            (const int32_t *)g->in_nz_rank, g->in_nz_rows, c->d_counters, (volatile int64_t *)c->h_counters, seq);

@@ -100,12 +100,14 @@ struct vgl_small8 {
 // of probes and a quarter as many rows are deferred (tests/studies/bu_head_order.py).  long_bits[v] = row v holds ids that are not in
 // its head; the deferred pass then scans the WHOLE row: the head is a selection, not a prefix.  One
 // wavefront per 64 rows: rows of more than 64 entries are scanned by the whole wavefront (per-lane selections merged by eight wave
-// minima), the others by their own lane.
+// minima), the others by their own lane.  *max_id = the largest id written to any record (ids ascend within a row, so it is the last present
+// entry of some row): what decides whether the records can be repacked with 24-bit ids (vgl_k_pack_heads).
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_row_heads(int32_t nrows, int32_t row_base, const int64_t *rowptr, const int32_t *adj, int4 *head0,
-                                                             int4 *head1, uint64_t *long_bits, const int32_t *nz_rank)
+                                                             int4 *head1, uint64_t *long_bits, const int32_t *nz_rank, int32_t *max_id)
 {
     const int lane = threadIdx.x & 63;
     const int32_t ngroups = (nrows + 63) >> 6;
+    int32_t top = -1;
     for (int32_t grp = blockIdx.x * VGL_WAVES + (threadIdx.x >> 6); grp < ngroups; grp += gridDim.x * VGL_WAVES) {
         const int32_t r = (grp << 6) + lane;
         int64_t b = 0, n = 0;
@@ -136,6 +138,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_row_heads(int32_t nrows, int3
                 head0[rec] = make_int4(out[0], out[1], out[2], out[3]);
                 head1[rec] = make_int4(out[4], out[5], out[6], out[7]);
                 has_more = more;
+#pragma unroll
+                for (int k = 0; k < 8; k++) top = max(top, out[k]);
             }
         }
         if (r < nrows && n > 0 && n <= 64) {
@@ -148,9 +152,36 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_row_heads(int32_t nrows, int3
             head0[rec] = make_int4(out[0], out[1], out[2], out[3]);
             head1[rec] = make_int4(out[4], out[5], out[6], out[7]);
             has_more = s.overflow;
+#pragma unroll
+            for (int k = 0; k < 8; k++) top = max(top, out[k]);
         }
         const unsigned long long m = __ballot(has_more);
         if (lane == 0) long_bits[(row_base + (grp << 6)) >> 6] = m;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) top = max(top, __shfl_xor(top, d));
+    if (lane == 0 && top >= 0) atomicMax(max_id, top);             // one per wavefront, once per graph
+}
+
+// The packed form of the head records (graphs whose head ids are all below 0xFFFFFF): the same four ids per record, in the same order, as
+// 24-bit little-endian fields in three words -- 12 bytes instead of 16 in the one stream the bottom-up probe is bound by.  An absent entry
+// (-1) becomes the field 0xFFFFFF.  `records` counts both planes; the planes stay contiguous (plane 1 starts at record nz_rows).
+__host__ __device__ static inline void vgl_pack_head(const int32_t id[4], uint32_t w[3])
+{
+    uint32_t f[4];
+    for (int q = 0; q < 4; q++) f[q] = id[q] < 0 ? 0xFFFFFFu : (uint32_t)id[q];
+    w[0] = f[0] | (f[1] << 24);
+    w[1] = (f[1] >> 8) | (f[2] << 16);
+    w[2] = (f[2] >> 16) | (f[3] << 8);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_pack_heads(int64_t records, const int4 *wide, uint32_t *packed)
+{
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < records; i += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int4 h = wide[i];
+        const int32_t id[4] = {h.x, h.y, h.z, h.w};
+        uint32_t w[3];
+        vgl_pack_head(id, w);
+        packed[3 * i + 0] = w[0]; packed[3 * i + 1] = w[1]; packed[3 * i + 2] = w[2];
     }
 }
 
@@ -332,11 +363,36 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_hip_memcpy_d2h(c, &g->in_nz_rows, g->in_nz_rank + ngroups, sizeof(int32_t)));
         VGL_TRY(g->in_head.alloc((size_t)std::max(g->in_nz_rows, 1) * 8));
+        vgl_dev<int32_t> head_max;
+        VGL_TRY(head_max.alloc(1));
+        VGL_HIP_TRY(hipMemsetAsync(head_max.p, 0xFF, sizeof(int32_t), c->stream));
         VGL_TRY(g->bm_in_long.alloc(words));
         VGL_HIP_TRY(hipMemsetAsync(g->bm_in_long, 0, words * 8, c->stream));
         hipLaunchKernelGGL(vgl_k_row_heads, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, g->in.rowptr, g->in.adj,
-                           reinterpret_cast<int4 *>(g->in_head.p), reinterpret_cast<int4 *>(g->in_head.p) + g->in_nz_rows, g->bm_in_long, (const int32_t *)g->in_nz_rank);
+                           reinterpret_cast<int4 *>(g->in_head.p), reinterpret_cast<int4 *>(g->in_head.p) + g->in_nz_rows, g->bm_in_long, (const int32_t *)g->in_nz_rank,
+                           head_max.p);
         VGL_HIP_TRY(hipGetLastError());
+        // VGL_BFS_HEADS=auto|wide|packed (read here: the record form is a property of the graph, not of a traversal).  Packed only when every id
+        // that OCCURS in a record is below the absent-entry field -- not decided from V or nrows: a shard holds global ids, and a graph of 2^24
+        // vertices packs as long as id 2^24 - 1 is nobody's in-neighbour.  `packed` on a graph that does not qualify stays wide.
+        const char *form = vgl_env(c, "VGL_BFS_HEADS");
+        const bool want_packed = !(form && std::string(form) == "wide");
+        if (want_packed && g->in_nz_rows > 0) {
+            int32_t top = -1;
+            VGL_TRY(vgl_hip_memcpy_d2h(c, &top, head_max.p, sizeof(int32_t)));
+            if (top < 0xFFFFFF) {
+                const int64_t records = 2 * (int64_t)g->in_nz_rows;
+                vgl_dev<int32_t> packed;
+                VGL_TRY(packed.alloc((size_t)records * 3));
+                const int pgrid = (int)std::min<int64_t>(8192, vgl_ceil_div(records, VGL_BLOCK));
+                hipLaunchKernelGGL(vgl_k_pack_heads, dim3(pgrid), dim3(VGL_BLOCK), 0, c->stream, records, reinterpret_cast<const int4 *>(g->in_head.p),
+                                   reinterpret_cast<uint32_t *>(packed.p));
+                VGL_HIP_TRY(hipGetLastError());
+                VGL_HIP_TRY(hipStreamSynchronize(c->stream));       // the wide records are freed by the assignment below
+                g->in_head = std::move(packed);
+                g->in_head_packed = true;
+            }
+        }
     }
     VGL_HIP_TRY(hipStreamSynchronize(c->stream));
     *out = g.release();
@@ -428,6 +484,13 @@ int vgl_hip_frontier_info(vgl_hip_ctx *c, vgl_hip_frontier *f, int32_t *size, in
     if (size) *size = f->size;
     if (neighbours) *neighbours = f->neighbours;
     if (sparsity) *sparsity = f->sparsity;
+    return 0;
+}
+int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed)
+{
+    if (!g) VGL_FAIL("graph_info: null argument");
+    if (in_nz_rows) *in_nz_rows = g->in.rowptr ? g->in_nz_rows : 0;
+    if (heads_packed) *heads_packed = g->in_head_packed ? 1 : 0;
     return 0;
 }
 int vgl_hip_graph_tile_rows(vgl_hip_graph *g, int direction, const int32_t **d_tile_row, int64_t *ntiles)

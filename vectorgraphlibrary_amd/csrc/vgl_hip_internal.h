@@ -198,6 +198,8 @@ struct vgl_hip_graph {
                                      // OWNED ROW THAT HAS INCOMING EDGES, in row order: record index = in_nz_rank[group] + rank of the row among the set
                                      // bits of its in_nz word -- the rows without incoming edges (45 % of an RMAT graph) are never bottom-up
                                      // candidates and used to take half of every 128-byte line of the planes
+    bool in_head_packed = false;     // the records are 12 bytes (four 24-bit ids, 0xFFFFFF = absent; two planes of in_nz_rows x 12 bytes): chosen once, when
+                                     // the records are built, iff every id in them is below 0xFFFFFF (VGL_BFS_HEADS; graph_frontier.hip)
     vgl_dev<int32_t> in_nz_rank;   // per 64-row group: number of owned rows with incoming edges before the group
     int32_t in_nz_rows = 0;          // owned rows with incoming edges = records per plane
     vgl_dev<int32_t> pr_indeg;     // sharded PageRank: in-degrees minus self loops of ALL vertices, summed over the ranks once per graph handle
