@@ -136,6 +136,28 @@ def test_every_class_with_shrunk_thresholds(ctx, monkeypatch):
     g.close()
 
 
+@pytest.mark.parametrize("d,want", [(4, (2, 0, 0)), (5, (1, 1, 0)), (8, (1, 1, 0)), (9, (1, 0, 1))])
+def test_class_boundary_on_a_star(d, want, ctx, monkeypatch):
+    """The class of a row of length d under short = 4, wave = 8 (d <= short: short, d <= wave: wave, longer: workgroup), one rule for kcore, ktruss,
+    msf, msbfs and bicc.  K(1, d) on the large path: the leaves peel at k = 1 in one short launch, the hub crosses to degree 0 once and the next
+    sub-round expands it in the class of its row."""
+    A = api()
+    for k, v in {"VGL_KCORE_SHORT": "4", "VGL_KCORE_WAVE": "8", "VGL_KCORE_SMALL": "0"}.items():
+        monkeypatch.setenv(k, v)
+    leaves = torch.arange(1, d + 1, dtype=torch.int32, device=ctx.device)
+    g = A.Graph.from_coo(ctx, d + 1, torch.zeros_like(leaves), leaves, with_incoming=False)
+    ctx.timing(True)
+    top, st = A.core_numbers(g)
+    n = launches(ctx)
+    ctx.timing(False)
+    print("K(1, %d)" % d, {k: v for k, v in st.items() if not torch.is_tensor(v)}, n)
+    assert top == 1 and bool((st["core"] == 1).all())
+    assert st["sub_rounds"] == 2
+    assert (n["kcore_short"], n["kcore_wave"], n["kcore_wg"]) == want, n
+    assert n["kcore_small"] == 0, n
+    g.close()
+
+
 def test_sort_cap_zero_makes_every_row_a_piece(ctx, monkeypatch):
     """VGL_KCORE_SORT_CAP_MB=0 leaves one key per piece: every row with a key exceeds it and is sorted as a piece of its own.  The 64-vertex golden
     graph, stored in both directions.  Core numbers and degrees, truss numbers with the edge endpoints (the numbering of the edges needs the rows

@@ -27,6 +27,7 @@
 // INVARIANT: inside one launch a word that another workgroup of that launch writes is read with an agent-scope atomic load or not at all; everything
 // else crosses a kernel boundary.  No cooperative launch, no grid barrier, no wait on a flag: a union-find retry is a new find, never a spin.
 #include "vgl_simple.h"
+#include "vgl_rowclass.h"
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -35,9 +36,6 @@
 namespace {
 
 typedef unsigned long long bi_cnt;
-constexpr int BI_NCLS = 3;
-enum { BI_SHORT = 0, BI_WAVE = 1, BI_WG = 2 };
-constexpr int BI_G = 8;                          // lanes per short row
 constexpr int64_t BI_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
 enum {
     BI_TAIL = 0,        // + class: vertices appended to the class list so far (cumulative)
@@ -53,13 +51,10 @@ enum {
 };
 static_assert(BI_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-struct bi_bounds { int32_t shrt, wave; };
-__device__ __forceinline__ int bi_class_of(int32_t d, bi_bounds b) { return d <= b.shrt ? BI_SHORT : d <= b.wave ? BI_WAVE : BI_WG; }
-
 // the three class lists (cumulative over the levels); cap[c] = vertices of the class
-struct bi_lists { int32_t *rows[BI_NCLS]; int32_t cap[BI_NCLS]; };
+struct bi_lists { int32_t *rows[VGL_RC_N]; int32_t cap[VGL_RC_N]; };
 // one level (or all levels) of the lists: n[c] vertices from rows[c]
-struct bi_slice { const int32_t *rows[BI_NCLS]; int32_t n[BI_NCLS]; };
+struct bi_slice { const int32_t *rows[VGL_RC_N]; int32_t n[VGL_RC_N]; };
 __device__ __forceinline__ int32_t bi_slice_at(const bi_slice &s, int64_t i)
 {
     return i < s.n[0] ? s.rows[0][i] : i < (int64_t)s.n[0] + s.n[1] ? s.rows[1][i - s.n[0]] : s.rows[2][i - s.n[0] - s.n[1]];
@@ -68,7 +63,7 @@ __device__ __forceinline__ int32_t bi_slice_at(const bi_slice &s, int64_t i)
 __device__ __forceinline__ void bi_append(bool want, int32_t v, int cls, const bi_lists &L, bi_cnt *tail)
 {
 #pragma unroll
-    for (int c = 0; c < BI_NCLS; c++) {
+    for (int c = 0; c < VGL_RC_N; c++) {
         int32_t *const one[1] = {L.rows[c]};
         vgl_wave_append<1>(want && cls == c, v, 0, one, L.cap[c], tail + c);
     }
@@ -125,18 +120,18 @@ __device__ __forceinline__ int32_t bi_fetch_add_by_key(bool on, int32_t key, int
 }
 
 // ---- init, roots, seed ----
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_init(int32_t V, const int32_t *deg, bi_bounds b, int32_t *uf, int32_t *level, int32_t *size, int32_t *cursor, bi_cnt *cnt)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_init(int32_t V, const int32_t *deg, vgl_rc_bounds b, int32_t *uf, int32_t *level, int32_t *size, int32_t *cursor, bi_cnt *cnt)
 {
-    int64_t n[BI_NCLS] = {0, 0, 0};
+    int64_t n[VGL_RC_N] = {0, 0, 0};
     for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
         uf[v] = (int32_t)v;
         level[v] = -1;
         size[v] = 1;
         cursor[v] = 0;
-        n[bi_class_of(deg[v], b)]++;
+        n[vgl_rc_class_of(deg[v], b)]++;
     }
 #pragma unroll
-    for (int c = 0; c < BI_NCLS; c++) vgl_wave_flush_add(cnt + BI_ROWS + c, n[c]);
+    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(cnt + BI_ROWS + c, n[c]);
 }
 // what the passes per edge start from: the two union-finds as singletons, no edge counted, no smallest edge known (each may be NULL)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_reset(int32_t V, int32_t *uf_two, int32_t *uf_block, int32_t *edges_of, uint32_t *min_edge)
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_flatten(int32_t V, int32
     if (roots) vgl_wave_flush_add(roots, n);
 }
 // the roots (a vertex that is its own parent after the unite launch) are level 0
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_seed(int32_t V, const int32_t *uf, const int32_t *deg, bi_bounds b, int32_t *level, int32_t *parent, bi_lists L, bi_cnt *cnt)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_seed(int32_t V, const int32_t *uf, const int32_t *deg, vgl_rc_bounds b, int32_t *level, int32_t *parent, bi_lists L, bi_cnt *cnt)
 {
     int64_t n = 0;
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
@@ -173,7 +168,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_seed(int32_t V, const in
         if (root) {
             level[v] = 0;
             parent[v] = -1;
-            cls = bi_class_of(deg[v], b);
+            cls = vgl_rc_class_of(deg[v], b);
             n++;
         }
         bi_append(root, (int32_t)v, cls, L, cnt + BI_TAIL);
@@ -189,7 +184,7 @@ struct bi_bfs {
     int32_t *level, *parent;
     bi_lists L;
     bi_cnt *cnt;
-    bi_bounds b;
+    vgl_rc_bounds b;
     int32_t next_level;
 };
 // one entry (v -> w): true for the lane that claimed w.  level[w] is -1 or the level of its claim, which is final.
@@ -208,22 +203,22 @@ __device__ __forceinline__ void bi_bfs_entry(const bi_bfs &t, int32_t v, int64_t
     if (e < hi) {
         w = t.adj[e];
         app = bi_visit(t, v, w);
-        if (app) cls = bi_class_of(t.deg[w], t.b);
+        if (app) cls = vgl_rc_class_of(t.deg[w], t.b);
     }
     bi_append(app, w, cls, t.L, t.cnt + BI_TAIL);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs_short(bi_bfs t, const int32_t *rows, int32_t n)
 {
-    const int gi = threadIdx.x & (BI_G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / BI_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / BI_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / BI_G;
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         int32_t v = 0;
         int64_t lo = 0, hi = 0;
         if (i < n) {
             v = rows[i];
             lo = t.rowptr[v]; hi = t.rowptr[v + 1];
         }
-        for (int64_t e = lo + gi; __any(e < hi); e += BI_G) bi_bfs_entry(t, v, e, hi);      // (uniform over the wave)
+        for (int64_t e = lo + gi; __any(e < hi); e += VGL_RC_G) bi_bfs_entry(t, v, e, hi);      // (uniform over the wave)
     }
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs_wave(bi_bfs t, const int32_t *rows, int32_t n)
@@ -302,10 +297,10 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_lowhigh(bi_slice s, cons
 template <class OP>
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows_short(OP op, const int32_t *rows, int32_t n)
 {
-    const int gi = threadIdx.x & (BI_G - 1);
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t acc = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / BI_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / BI_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / BI_G;
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         int32_t v = 0, cx = 0, mn = INT_MAX, mx = INT_MIN;
         int64_t lo = 0, hi = 0;
         if (i < n) {
@@ -313,9 +308,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows_short(OP op, const 
             cx = op.ctx(v);
             lo = op.rowptr[v]; hi = op.rowptr[v + 1];
         }
-        for (int64_t e = lo + gi; e < hi; e += BI_G) op.entry(v, cx, e, mn, mx);
+        for (int64_t e = lo + gi; e < hi; e += VGL_RC_G) op.entry(v, cx, e, mn, mx);
 #pragma unroll
-        for (int o = BI_G / 2; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
+        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
         if (gi == 0 && i < n) acc += op.finish(v, mn, mx);
     }
     if (op.counter()) vgl_wave_flush_add(op.counter(), acc);
@@ -493,7 +488,7 @@ int bi_validate(const char *who, vgl_hip_ctx *c, vgl_hip_graph *g)
     return 0;
 }
 
-struct bi_level { int64_t off[BI_NCLS]; int32_t n[BI_NCLS]; };
+struct bi_level { int64_t off[VGL_RC_N]; int32_t n[VGL_RC_N]; };
 
 }  // namespace
 
@@ -525,9 +520,7 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     const int32_t ne = (int32_t)sg->ne;
     const int64_t nnz = sg->csr.nnz;
     hipStream_t st = c->stream;
-    bi_bounds b;
-    b.shrt = (int32_t)vgl_env_int(c, "VGL_BICC_SHORT", 32, 0, 1 << 20);
-    b.wave = (int32_t)vgl_env_int(c, "VGL_BICC_WAVE", 1024, b.shrt, 1 << 24);
+    const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_BICC_SHORT", "VGL_BICC_WAVE");
     const bool blocks = d_edge_component || d_articulation;
     vgl_hip_bicc_stats out;
     memset(&out, 0, sizeof(out));
@@ -582,13 +575,15 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
     bi_lists L;
+    int64_t cap[VGL_RC_N];
     {
         int64_t off = 0;
-        for (int k = 0; k < BI_NCLS; k++) {
+        for (int k = 0; k < VGL_RC_N; k++) {
             const int64_t rows = c->h_counters[BI_ROWS + k];
             if (rows < 0 || rows > V) VGL_FAIL("bicc_run: internal error (more rows in a class than vertices)");
             L.rows[k] = lists.p + off;
             L.cap[k] = (int32_t)rows;
+            cap[k] = rows;
             off += rows;
         }
         if (off != V) VGL_FAIL("bicc_run: internal error (the row classes do not add up to the vertices)");
@@ -605,41 +600,36 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     bi_bfs t;
     t.rowptr = sg->csr.rowptr; t.adj = sg->csr.adj; t.deg = sg->csr.deg; t.level = level; t.parent = parent; t.L = L; t.cnt = cnt; t.b = b;
     std::vector<bi_level> levels;
-    int64_t lo[BI_NCLS] = {0, 0, 0}, hi[BI_NCLS];
-    for (int k = 0; k < BI_NCLS; k++) hi[k] = c->h_counters[BI_TAIL + k];
+    const char *const bfs_slot[VGL_RC_N] = {"bicc_bfs_short", "bicc_bfs_wave", "bicc_bfs_wg"};
+    const char *const list_msg = "bicc_run: internal error (a class list longer than its class)";
+    vgl_rc_window w;                             // the level: [head, tail) of the cumulative class lists
+    VGL_TRY(w.advance(c->h_counters + BI_TAIL, cap, list_msg));
     for (;;) {
         bi_level lv;
-        int64_t total = 0;
-        for (int k = 0; k < BI_NCLS; k++) {
-            if (hi[k] < lo[k] || hi[k] > L.cap[k]) VGL_FAIL("bicc_run: internal error (a class list longer than its class)");
-            lv.off[k] = lo[k];
-            lv.n[k] = (int32_t)(hi[k] - lo[k]);
-            total += lv.n[k];
+        for (int k = 0; k < VGL_RC_N; k++) {
+            lv.off[k] = w.head[k];
+            lv.n[k] = (int32_t)w.n(k);
         }
+        const int64_t total = w.live();
         if (total == 0) break;
         if ((int64_t)levels.size() >= V) VGL_FAIL("bicc_run: internal error (more levels than vertices)");
         levels.push_back(lv);
         t.next_level = (int32_t)levels.size();
-        if (lv.n[BI_SHORT] > 0) {
-            vgl_timed_launch tl(c, "bicc_bfs_short");
-            hipLaunchKernelGGL(vgl_k_bicc_bfs_short, dim3(vgl_grid((int64_t)lv.n[BI_SHORT] * BI_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)L.rows[BI_SHORT] + lv.off[BI_SHORT],
-                               lv.n[BI_SHORT]);
-        }
-        if (lv.n[BI_WAVE] > 0) {
-            vgl_timed_launch tl(c, "bicc_bfs_wave");
-            hipLaunchKernelGGL(vgl_k_bicc_bfs_wave, dim3(vgl_grid(lv.n[BI_WAVE], VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)L.rows[BI_WAVE] + lv.off[BI_WAVE], lv.n[BI_WAVE]);
-        }
-        if (lv.n[BI_WG] > 0) {
-            vgl_timed_launch tl(c, "bicc_bfs_wg");
-            hipLaunchKernelGGL(vgl_k_bicc_bfs_wg, dim3(vgl_grid(lv.n[BI_WG], 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)L.rows[BI_WG] + lv.off[BI_WG], lv.n[BI_WG]);
-        }
-        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_rc_launch(c, bfs_slot, w, [&](int cls, int64_t n) {
+            const int32_t *rows = L.rows[cls] + w.head[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(vgl_k_bicc_bfs_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(vgl_k_bicc_bfs_wave, dim3(vgl_grid(n, VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
+            else
+                hipLaunchKernelGGL(vgl_k_bicc_bfs_wg, dim3(vgl_grid(n, 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
+        }));
         VGL_TRY(read());
-        for (int k = 0; k < BI_NCLS; k++) { lo[k] = hi[k]; hi[k] = c->h_counters[BI_TAIL + k]; }
+        VGL_TRY(w.advance(c->h_counters + BI_TAIL, cap, list_msg));
     }
-    if (lo[0] + lo[1] + lo[2] != V) {
+    if (w.total() != V) {
         static thread_local std::string msg;
-        msg = "bicc_run: internal error (the forest does not reach every vertex): " + std::to_string(lo[0]) + " + " + std::to_string(lo[1]) + " + " + std::to_string(lo[2]) + " of " +
+        msg = "bicc_run: internal error (the forest does not reach every vertex): " + std::to_string(w.head[0]) + " + " + std::to_string(w.head[1]) + " + " + std::to_string(w.head[2]) + " of " +
               std::to_string(V) + " listed in " + std::to_string(levels.size()) + " levels from " + std::to_string(components) + " roots; the classes hold " + std::to_string(L.cap[0]) + ", " +
               std::to_string(L.cap[1]) + ", " + std::to_string(L.cap[2]) + "; listed per level:";
         for (const bi_level &lv : levels) msg += " " + std::to_string((int64_t)lv.n[0] + lv.n[1] + lv.n[2]);
@@ -648,7 +638,7 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     const int32_t depth = (int32_t)levels.size();
     auto slice_of = [&](const bi_level &lv) {
         bi_slice s;
-        for (int k = 0; k < BI_NCLS; k++) { s.rows[k] = L.rows[k] + lv.off[k]; s.n[k] = lv.n[k]; }
+        for (int k = 0; k < VGL_RC_N; k++) { s.rows[k] = L.rows[k] + lv.off[k]; s.n[k] = lv.n[k]; }
         return s;
     };
     auto grid_of = [&](const bi_level &lv) { return dim3(vgl_grid((int64_t)lv.n[0] + lv.n[1] + lv.n[2], VGL_BLOCK, BI_MAX_GRID)); };
@@ -666,27 +656,23 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     VGL_HIP_TRY(hipGetLastError());
 
     // ---- low / high: the rows by class, then the levels ----
-    const char *const local_slot[BI_NCLS] = {"bicc_local_short", "bicc_local_wave", "bicc_local_wg"};
-    const char *const art_slot[BI_NCLS] = {"bicc_art_short", "bicc_art_wave", "bicc_art_wg"};
-    auto rows_by_class = [&](auto op, const char *const *slot) {
-        if (L.cap[BI_SHORT] > 0) {
-            vgl_timed_launch tl(c, slot[BI_SHORT]);
-            hipLaunchKernelGGL(vgl_k_bicc_rows_short<decltype(op)>, dim3(vgl_grid((int64_t)L.cap[BI_SHORT] * BI_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, (const int32_t *)L.rows[BI_SHORT],
-                               L.cap[BI_SHORT]);
-        }
-        if (L.cap[BI_WAVE] > 0) {
-            vgl_timed_launch tl(c, slot[BI_WAVE]);
-            hipLaunchKernelGGL(vgl_k_bicc_rows_wave<decltype(op)>, dim3(vgl_grid(L.cap[BI_WAVE], VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, (const int32_t *)L.rows[BI_WAVE], L.cap[BI_WAVE]);
-        }
-        if (L.cap[BI_WG] > 0) {
-            vgl_timed_launch tl(c, slot[BI_WG]);
-            hipLaunchKernelGGL(vgl_k_bicc_rows_wg<decltype(op)>, dim3(vgl_grid(L.cap[BI_WG], 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, (const int32_t *)L.rows[BI_WG], L.cap[BI_WG]);
-        }
+    const char *const local_slot[VGL_RC_N] = {"bicc_local_short", "bicc_local_wave", "bicc_local_wg"};
+    const char *const art_slot[VGL_RC_N] = {"bicc_art_short", "bicc_art_wave", "bicc_art_wg"};
+    auto rows_by_class = [&](auto op, const char *const *slot) -> int {
+        return vgl_rc_launch(c, slot, cap, [&](int cls, int64_t n) {
+            const int32_t *rows = L.rows[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(vgl_k_bicc_rows_short<decltype(op)>, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(vgl_k_bicc_rows_wave<decltype(op)>, dim3(vgl_grid(n, VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
+            else
+                hipLaunchKernelGGL(vgl_k_bicc_rows_wg<decltype(op)>, dim3(vgl_grid(n, 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
+        });
     };
     {
         bi_local_op op;
         op.rowptr = sg->csr.rowptr; op.adj = sg->csr.adj; op.parent = parent; op.pre = pre; op.low = low; op.high = high;
-        rows_by_class(op, local_slot);
+        VGL_TRY(rows_by_class(op, local_slot));
     }
     for (int32_t l = depth - 1; l >= 1; l--) {
         vgl_timed_launch tl(c, "bicc_lowhigh");
@@ -732,8 +718,7 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
         }
         bi_art_op op;
         op.rowptr = sg->csr.rowptr; op.eid = sg->eid; op.label = label; op.art = d_articulation; op.cnt = cnt;
-        rows_by_class(op, art_slot);
-        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(rows_by_class(op, art_slot));
     }
     if (d_two_edge_component) {                                       // (a flatten too, under the name of its pass)
         vgl_timed_launch tl(c, "bicc_twoecc");

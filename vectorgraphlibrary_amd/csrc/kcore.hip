@@ -17,15 +17,13 @@
 // or the graph is exhausted, and reports through the pinned mirror what it did.  No cooperative launch, no workgroup waits for another.
 // The host reads the pinned mirror once per sub-round of the large path (list tails, entry total, k); no allocation inside the loop.
 #include "vgl_simple.h"
+#include "vgl_rowclass.h"
 #include <cstring>
 #include <algorithm>
 #include <climits>
 
 namespace {
 
-constexpr int KC_NCLS = 3;
-enum { KC_SHORT = 0, KC_WAVE = 1, KC_WG = 2 };
-constexpr int KC_G = 8;                         // lanes per short row
 constexpr int KC_MAX_CHUNKS = 32768;            // grid.y of the workgroup kernel
 constexpr int KC_SMALL_THREADS = 1024;
 constexpr int KC_SMALL_F = 2048;                // vertices of a frontier the one-workgroup kernel takes
@@ -45,16 +43,13 @@ enum {
 enum { KC_ST_BIG = 0, KC_ST_NEED_K = 1, KC_ST_DONE = 2, KC_ST_LIMIT = 3 };
 static_assert(KC_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-struct kc_bounds { int32_t shrt, wave; };
-__host__ __device__ inline int kc_class_of(int64_t d, kc_bounds b) { return d <= b.shrt ? KC_SHORT : d <= b.wave ? KC_WAVE : KC_WG; }
-
-struct kc_lists { int32_t *list[KC_NCLS]; int32_t cap; };      // one list per class, `cap` entries each
+struct kc_lists { int32_t *list[VGL_RC_N]; int32_t cap; };      // one list per class, `cap` entries each
 struct kc_graph {
     const int64_t *rowptr;       // the symmetric CSR
     const int32_t *adj;
     int32_t *deg;                // working degrees
     int32_t *core;
-    kc_bounds b;
+    vgl_rc_bounds b;
     kc_lists L;
 };
 
@@ -72,11 +67,11 @@ __device__ __forceinline__ void kc_relax(bool active, int32_t u, int32_t k, cons
         if (old == k + 1) {
             const int64_t len = g.rowptr[u + 1] - g.rowptr[u];
             want = true;
-            cls = kc_class_of(len, g.b);
+            cls = vgl_rc_class_of(len, g.b);
             m_acc += len;
         } else if (old <= k) atomicAdd(g.deg + u, 1);
     }
-    vgl_wave_append<KC_NCLS>(want, u, cls, g.L.list, g.L.cap, tail);
+    vgl_wave_append<VGL_RC_N>(want, u, cls, g.L.list, g.L.cap, tail);
 }
 // the entries [lo, hi) of one row, `stride` lanes of which this is lane `li`; uniform over the wave as long as every lane of the wave calls
 __device__ __forceinline__ void kc_walk(int64_t lo, int64_t hi, int li, int stride, int32_t k, const kc_graph &g, unsigned long long *tail, int64_t &m_acc)
@@ -121,11 +116,11 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_scan(const int32_t *ids
             if (d > k_prev && d <= k) {
                 const int64_t len = g.rowptr[v + 1] - g.rowptr[v];
                 want = true;
-                cls = kc_class_of(len, g.b);
+                cls = vgl_rc_class_of(len, g.b);
                 m_acc += len;
             }
         }
-        vgl_wave_append<KC_NCLS>(want, v, cls, g.L.list, g.L.cap, cnt + KC_TAIL);
+        vgl_wave_append<VGL_RC_N>(want, v, cls, g.L.list, g.L.cap, cnt + KC_TAIL);
     }
     vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
@@ -137,20 +132,20 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_compact(int32_t V, cons
     L.cap = cap;
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t v = base + threadIdx.x;
-        vgl_wave_append<KC_NCLS>(v < V && deg[v] > k_prev, (int32_t)v, 0, L.list, L.cap, cnt + KC_ALIVE);
+        vgl_wave_append<VGL_RC_N>(v < V && deg[v] > k_prev, (int32_t)v, 0, L.list, L.cap, cnt + KC_ALIVE);
     }
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_short(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
 {
-    const int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / KC_G;
-    const int gi = threadIdx.x & (KC_G - 1);
+    const int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / VGL_RC_G;
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t lo = 0, hi = 0, m_acc = 0;
     if (i < n) {
         const int32_t v = rows[i];
         lo = g.rowptr[v]; hi = g.rowptr[v + 1];
         if (gi == 0) g.core[v] = k;
     }
-    kc_walk(lo, hi, gi, KC_G, k, g, cnt + KC_TAIL, m_acc);
+    kc_walk(lo, hi, gi, VGL_RC_G, k, g, cnt + KC_TAIL, m_acc);
     vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wave(kc_graph g, const int32_t *rows, int32_t n, int32_t k, unsigned long long *cnt)
@@ -193,21 +188,21 @@ __global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g
                                                                       volatile int64_t *host, int64_t seq)
 {
     constexpr int NT = KC_SMALL_THREADS, NW = NT / 64;
-    __shared__ unsigned long long s_tail[KC_NCLS];
+    __shared__ unsigned long long s_tail[VGL_RC_N];
     __shared__ unsigned long long s_m;
     __shared__ int s_min;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int64_t head[KC_NCLS] = {head0, head1, head2};
+    int64_t head[VGL_RC_N] = {head0, head1, head2};
     int64_t rounds = 0, subs = 0, m_total = 0;
     int state = KC_ST_BIG;
-    if (tid < KC_NCLS) s_tail[tid] = cnt[KC_TAIL + tid];
+    if (tid < VGL_RC_N) s_tail[tid] = cnt[KC_TAIL + tid];
     if (tid == 0) s_m = 0;
     for (;;) {
         __syncthreads();                                              // the lists, s_tail and s_m = 0 are in place; s_min has been read
-        int64_t tail[KC_NCLS];
+        int64_t tail[VGL_RC_N];
         int64_t F = 0;
 #pragma unroll
-        for (int c = 0; c < KC_NCLS; c++) { tail[c] = (int64_t)s_tail[c]; F += tail[c] - head[c]; }
+        for (int c = 0; c < VGL_RC_N; c++) { tail[c] = (int64_t)s_tail[c]; F += tail[c] - head[c]; }
         int64_t m_acc = 0;
         if (F == 0) {                                                 // ---- k change ----
             if (dom_n <= 0) { state = KC_ST_NEED_K; break; }
@@ -236,39 +231,39 @@ __global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g
                     if (d > k && d <= kn) {
                         const int64_t len = g.rowptr[v + 1] - g.rowptr[v];
                         want = true;
-                        cls = kc_class_of(len, g.b);
+                        cls = vgl_rc_class_of(len, g.b);
                         m_acc += len;
                     }
                 }
-                vgl_wave_append<KC_NCLS>(want, v, cls, g.L.list, g.L.cap, s_tail);
+                vgl_wave_append<VGL_RC_N>(want, v, cls, g.L.list, g.L.cap, s_tail);
             }
             k = kn;
             rounds++;
         } else {                                                      // ---- one sub-round ----
             if (F > KC_SMALL_F || cur_m > cap_m) { state = KC_ST_BIG; break; }
             {                                                         // short rows: 8 lanes each
-                const int64_t n = tail[KC_SHORT] - head[KC_SHORT];
-                for (int64_t i0 = 0; i0 < n; i0 += NT / KC_G) {       // (uniform over the workgroup)
-                    const int64_t i = i0 + tid / KC_G;
+                const int64_t n = tail[VGL_RC_SHORT] - head[VGL_RC_SHORT];
+                for (int64_t i0 = 0; i0 < n; i0 += NT / VGL_RC_G) {       // (uniform over the workgroup)
+                    const int64_t i = i0 + tid / VGL_RC_G;
                     int64_t lo = 0, hi = 0;
                     if (i < n) {
-                        const int32_t v = vgl_load_agent(g.L.list[KC_SHORT] + head[KC_SHORT] + i);
+                        const int32_t v = vgl_load_agent(g.L.list[VGL_RC_SHORT] + head[VGL_RC_SHORT] + i);
                         lo = g.rowptr[v]; hi = g.rowptr[v + 1];
-                        if ((tid & (KC_G - 1)) == 0) g.core[v] = k;
+                        if ((tid & (VGL_RC_G - 1)) == 0) g.core[v] = k;
                     }
-                    kc_walk(lo, hi, tid & (KC_G - 1), KC_G, k, g, s_tail, m_acc);
+                    kc_walk(lo, hi, tid & (VGL_RC_G - 1), VGL_RC_G, k, g, s_tail, m_acc);
                 }
             }
             {                                                         // longer rows: a wavefront each (cur_m <= cap_m bounds them)
-                const int64_t n1 = tail[KC_WAVE] - head[KC_WAVE], n = n1 + tail[KC_WG] - head[KC_WG];
+                const int64_t n1 = tail[VGL_RC_WAVE] - head[VGL_RC_WAVE], n = n1 + tail[VGL_RC_WG] - head[VGL_RC_WG];
                 for (int64_t j = wave; j < n; j += NW) {              // (uniform over the wave)
-                    const int32_t v = j < n1 ? vgl_load_agent(g.L.list[KC_WAVE] + head[KC_WAVE] + j) : vgl_load_agent(g.L.list[KC_WG] + head[KC_WG] + (j - n1));
+                    const int32_t v = j < n1 ? vgl_load_agent(g.L.list[VGL_RC_WAVE] + head[VGL_RC_WAVE] + j) : vgl_load_agent(g.L.list[VGL_RC_WG] + head[VGL_RC_WG] + (j - n1));
                     if (lane == 0) g.core[v] = k;
                     kc_walk(g.rowptr[v], g.rowptr[v + 1], lane, 64, k, g, s_tail, m_acc);
                 }
             }
 #pragma unroll
-            for (int c = 0; c < KC_NCLS; c++) head[c] = tail[c];
+            for (int c = 0; c < VGL_RC_N; c++) head[c] = tail[c];
             subs++;
         }
         m_acc = vgl_wave_reduce_add(m_acc);
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(KC_SMALL_THREADS) void vgl_k_kcore_small(kc_graph g
     // (the breaks above are uniform over the workgroup and come right after a barrier: nobody is still appending)
     if (tid == 0) {
 #pragma unroll
-        for (int c = 0; c < KC_NCLS; c++) {
+        for (int c = 0; c < VGL_RC_N; c++) {
             cnt[KC_TAIL + c] = s_tail[c];
             host[KC_TAIL + c] = (int64_t)s_tail[c];
             host[KC_HEAD + c] = head[c];
@@ -306,23 +301,17 @@ struct kc_run {
     vgl_hip_ctx *c;
     kc_graph g;
     unsigned long long *cnt;
-    int64_t head[KC_NCLS] = {0, 0, 0}, tail[KC_NCLS] = {0, 0, 0};
+    vgl_rc_window w;                     // the frontier: [head, tail) of the class lists
     int64_t m_cum = 0, cur_m = 0;        // entries of every frontier so far / of the current one
     int32_t k = -1;                      // the current level, or the last finished one while the frontier is empty
     int32_t rounds = 0;
     int64_t subs = 0;
 
-    int64_t frontier() const { return tail[0] - head[0] + tail[1] - head[1] + tail[2] - head[2]; }
-    int64_t removed() const { return tail[0] + tail[1] + tail[2]; }
     // the one host-visible read of a sub-round of the large path: list tails and entry total
     int read()
     {
         VGL_TRY(vgl_publish_counters(c, "kcore_publish", cnt, KC_NCNT));
-        for (int k_ = 0; k_ < KC_NCLS; k_++) {
-            head[k_] = tail[k_];
-            tail[k_] = c->h_counters[KC_TAIL + k_];
-            if (tail[k_] < head[k_] || tail[k_] > g.L.cap) VGL_FAIL("kcore_run: internal error (a frontier list ran past its end)");
-        }
+        VGL_TRY(w.advance(c->h_counters + KC_TAIL, g.L.cap, "kcore_run: internal error (a frontier list ran past its end)"));
         cur_m = c->h_counters[KC_M] - m_cum;
         m_cum = c->h_counters[KC_M];
         return 0;
@@ -356,8 +345,6 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     const vgl_simple_csr *kc = &sc->csr;
     const int32_t V = g->V;
     hipStream_t st = c->stream;
-    const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_KCORE_SHORT", 32, 0, 1 << 20);
-    const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_KCORE_WAVE", 1024, b_short, 1 << 24);
     const int64_t chunk_env = vgl_env_int(c, "VGL_KCORE_CHUNK", 16384, 16, 1 << 28);
     const int64_t small_m = vgl_env_int(c, "VGL_KCORE_SMALL", 8192, 0, 1 << 20);
     vgl_hip_kcore_stats out;
@@ -375,7 +362,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     vgl_dev<int32_t> deg, lists, alive;
     vgl_dev<unsigned long long> cnt;
     VGL_TRY(deg.alloc(st, (size_t)V));
-    VGL_TRY(lists.alloc(st, (size_t)V * KC_NCLS));
+    VGL_TRY(lists.alloc(st, (size_t)V * VGL_RC_N));
     VGL_TRY(alive.alloc(st, (size_t)std::min<int32_t>(V, KC_SMALL_SCAN)));
     VGL_TRY(cnt.alloc(st, KC_NCNT));
     VGL_HIP_TRY(hipMemcpyAsync(deg, kc->deg, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToDevice, st));
@@ -385,30 +372,31 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     r.c = c;
     r.cnt = cnt;
     r.g.rowptr = kc->rowptr; r.g.adj = kc->adj; r.g.deg = deg; r.g.core = d_core;
-    r.g.b = kc_bounds{b_short, b_wave};
-    for (int k_ = 0; k_ < KC_NCLS; k_++) r.g.L.list[k_] = lists.p + (size_t)V * k_;
+    r.g.b = vgl_rc_env_bounds(c, "VGL_KCORE_SHORT", "VGL_KCORE_WAVE");
+    for (int k_ = 0; k_ < VGL_RC_N; k_++) r.g.L.list[k_] = lists.p + (size_t)V * k_;
     r.g.L.cap = V;
     const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(kc->max_deg, 1), KC_MAX_CHUNKS));
     const unsigned max_chunks = (unsigned)std::max<int64_t>(1, vgl_ceil_div(std::max(kc->max_deg, 1), chunk));
     const int32_t *dom_ids = nullptr;                                 // the scan domain: every vertex, or the compacted alive list
     int32_t dom_n = V;
     bool limited = false;
+    const char *const slot[VGL_RC_N] = {"kcore_short", "kcore_wave", "kcore_wg"};
 
     // one launch of the one-workgroup kernel and the read of what it did
     auto small = [&]() -> int {
         const int64_t seq = vgl_next_seq(c);
         {
             vgl_timed_launch tl(c, "kcore_small");
-            hipLaunchKernelGGL(vgl_k_kcore_small, dim3(1), dim3(KC_SMALL_THREADS), 0, st, r.g, dom_ids, dom_n <= KC_SMALL_SCAN ? dom_n : 0, r.head[0], r.head[1], r.head[2], r.cur_m,
+            hipLaunchKernelGGL(vgl_k_kcore_small, dim3(1), dim3(KC_SMALL_THREADS), 0, st, r.g, dom_ids, dom_n <= KC_SMALL_SCAN ? dom_n : 0, r.w.head[0], r.w.head[1], r.w.head[2], r.cur_m,
                                r.k, k_limit, small_m, cnt.p, (volatile int64_t *)c->h_counters, seq);
         }
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_wait_counters(c, seq));
         const int64_t *h = c->h_counters;
-        for (int k_ = 0; k_ < KC_NCLS; k_++) {
-            r.head[k_] = h[KC_HEAD + k_];
-            r.tail[k_] = h[KC_TAIL + k_];
-            if (r.head[k_] < 0 || r.tail[k_] < r.head[k_] || r.tail[k_] > V) VGL_FAIL("kcore_run: internal error (a frontier list ran past its end)");
+        for (int k_ = 0; k_ < VGL_RC_N; k_++) {
+            r.w.head[k_] = h[KC_HEAD + k_];
+            r.w.tail[k_] = h[KC_TAIL + k_];
+            if (r.w.head[k_] < 0 || r.w.tail[k_] < r.w.head[k_] || r.w.tail[k_] > V) VGL_FAIL("kcore_run: internal error (a frontier list ran past its end)");
         }
         r.m_cum = h[KC_M];
         r.cur_m = h[KC_CUR_M];
@@ -419,9 +407,9 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     };
 
     for (;;) {
-        const int64_t F = r.frontier();
+        const int64_t F = r.w.live();
         if (F == 0) {                                                 // ---- k change ----
-            const int64_t left = V - r.removed();
+            const int64_t left = V - r.w.total();
             if (left == 0) break;
             if (small_m > 0 && !dom_ids && V > KC_SMALL_SCAN && left <= KC_SMALL_SCAN) {      // few are left: from now on the scans read their list
                 {
@@ -455,7 +443,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
             if (k_limit > 0 && kn >= k_limit) { limited = true; break; }
             r.k = (int32_t)kn;
             r.rounds++;
-            if (r.frontier() == 0) VGL_FAIL("kcore_run: internal error (the shell of the smallest remaining degree is empty)");
+            if (r.w.live() == 0) VGL_FAIL("kcore_run: internal error (the shell of the smallest remaining degree is empty)");
             continue;
         }
         if (small_m > 0 && F <= KC_SMALL_F && r.cur_m <= small_m) {   // ---- small frontier: several sub-rounds in one workgroup ----
@@ -465,24 +453,15 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
             continue;
         }
         // ---- one sub-round of the large path: a launch per class that has rows, then the read ----
-        if (r.tail[KC_SHORT] > r.head[KC_SHORT]) {
-            const int64_t n = r.tail[KC_SHORT] - r.head[KC_SHORT];
-            vgl_timed_launch tl(c, "kcore_short");
-            hipLaunchKernelGGL(vgl_k_kcore_short, dim3(vgl_grid(n * KC_G, VGL_BLOCK, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_SHORT] + r.head[KC_SHORT]), (int32_t)n,
-                               r.k, cnt.p);
-        }
-        if (r.tail[KC_WAVE] > r.head[KC_WAVE]) {
-            const int64_t n = r.tail[KC_WAVE] - r.head[KC_WAVE];
-            vgl_timed_launch tl(c, "kcore_wave");
-            hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(vgl_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WAVE] + r.head[KC_WAVE]),
-                               (int32_t)n, r.k, cnt.p);
-        }
-        if (r.tail[KC_WG] > r.head[KC_WG]) {
-            const int64_t n = r.tail[KC_WG] - r.head[KC_WG];
-            vgl_timed_launch tl(c, "kcore_wg");
-            hipLaunchKernelGGL(vgl_k_kcore_wg, dim3((unsigned)n, max_chunks), dim3(VGL_BLOCK), 0, st, r.g, (const int32_t *)(r.g.L.list[KC_WG] + r.head[KC_WG]), chunk, r.k, cnt.p);
-        }
-        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_rc_launch(c, slot, r.w, [&](int cls, int64_t n) {
+            const int32_t *rows = r.g.L.list[cls] + r.w.head[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(vgl_k_kcore_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, rows, (int32_t)n, r.k, cnt.p);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(vgl_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, rows, (int32_t)n, r.k, cnt.p);
+            else
+                hipLaunchKernelGGL(vgl_k_kcore_wg, dim3((unsigned)n, max_chunks), dim3(VGL_BLOCK), 0, st, r.g, rows, chunk, r.k, cnt.p);
+        }));
         VGL_TRY(r.read());
         r.subs++;
     }

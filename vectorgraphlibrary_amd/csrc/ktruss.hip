@@ -20,15 +20,13 @@
 // one returning atomic).  The host reads the pinned mirror once per sub-round.  No cooperative launch, no grid barrier, no workgroup waits for another:
 // every turn of the host loop expands a non-empty frontier or changes k.
 #include "vgl_simple.h"
+#include "vgl_rowclass.h"
 #include <cstring>
 #include <algorithm>
 #include <climits>
 
 namespace {
 
-constexpr int KT_NCLS = 3;
-enum { KT_SHORT = 0, KT_WAVE = 1, KT_WG = 2 };
-constexpr int KT_G = 8;                         // lanes per short edge
 constexpr int64_t KT_MAX_GRID = 8192;           // workgroups of a grid-stride kernel: bounds the per-wave atomics on the shared counters
 constexpr int64_t KT_NO_K = 0x7F7F7F7F7F7F7F7Fll;      // "no alive edge" in KT_K (a byte pattern: one memset arms the min kernel)
 enum {
@@ -42,7 +40,7 @@ enum {
 };
 static_assert(KT_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-struct kt_lists { int32_t *list[KT_NCLS]; int32_t cap; };      // one list of edge ids per class, `cap` entries each
+struct kt_lists { int32_t *list[VGL_RC_N]; int32_t cap; };      // one list of edge ids per class, `cap` entries each
 struct kt_graph {
     const int64_t *rowptr;       // the symmetric CSR
     const int32_t *adj;
@@ -52,10 +50,9 @@ struct kt_graph {
     int32_t *sup;                // working supports
     int32_t *stamp;              // sub-round at which the edge entered a frontier; 0: never
     int32_t *truss;
-    int32_t b_short, b_wave;
+    vgl_rc_bounds b;             // classes of the shorter row's length
     kt_lists L;
 };
-__device__ __forceinline__ int kt_class_of(int32_t d, const kt_graph &g) { return d <= g.b_short ? KT_SHORT : d <= g.b_wave ? KT_WAVE : KT_WG; }
 __device__ __forceinline__ int32_t kt_shorter(int32_t e, const kt_graph &g) { return min(g.deg[g.eu[e]], g.deg[g.ev[e]]); }
 
 // ---- shared device pieces ----
@@ -92,20 +89,20 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_classify(int32_t ne, k
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < ne; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t e = base + threadIdx.x;
         const bool want = e < ne;
-        vgl_wave_append<KT_NCLS>(want, (int32_t)e, want ? kt_class_of(kt_shorter((int32_t)e, g), g) : 0, g.L.list, g.L.cap, cnt + KT_TAIL);
+        vgl_wave_append<VGL_RC_N>(want, (int32_t)e, want ? vgl_rc_class_of(kt_shorter((int32_t)e, g), g.b) : 0, g.L.list, g.L.cap, cnt + KT_TAIL);
     }
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup_short(kt_graph g, const int32_t *edges, int32_t n, unsigned long long *cnt)
 {
-    const int gi = threadIdx.x & (KT_G - 1);
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t sum = 0, walk = 0;
     int32_t mx = 0;
-    for (int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / KT_G; i < n; i += (int64_t)gridDim.x * (VGL_BLOCK / KT_G)) {
+    for (int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / VGL_RC_G; i < n; i += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {
         const int32_t e = edges[i];
         const kt_rows r = kt_rows_of(e, g);
-        int32_t t = kt_count(r, gi, KT_G, g.adj);
+        int32_t t = kt_count(r, gi, VGL_RC_G, g.adj);
 #pragma unroll
-        for (int o = KT_G / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);      // (the 8 lanes of a group leave the loop together)
+        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);      // (the 8 lanes of a group leave the loop together)
         if (gi == 0) { g.sup[e] = t; sum += t; walk += r.a_hi - r.a_lo; mx = max(mx, t); }
     }
     kt_support_done(cnt, sum, walk, mx);
@@ -149,11 +146,11 @@ __device__ __forceinline__ void kt_dec(bool active, int32_t e, int32_t k, int32_
             vgl_store_agent(g.stamp + e, s + 1);
             g.truss[e] = k;
             want = true;
-            cls = kt_class_of(len, g);
+            cls = vgl_rc_class_of(len, g.b);
             m_acc += len;
         } else if (old <= k - 2) atomicAdd(g.sup + e, 1);
     }
-    vgl_wave_append<KT_NCLS>(want, e, cls, g.L.list, g.L.cap, tail);
+    vgl_wave_append<VGL_RC_N>(want, e, cls, g.L.list, g.L.cap, tail);
 }
 // The frontier edge e1 with rows r, lane `li` of `stride`.  Uniform over the wave as long as every lane of the wave calls (has = this lane has an edge).
 __device__ __forceinline__ void kt_expand(bool has, int32_t e1, const kt_rows &r, int li, int stride, int32_t k, int32_t s, const kt_graph &g,
@@ -208,24 +205,24 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_scan(int32_t ne, kt_gr
             g.stamp[e] = s_next;
             g.truss[e] = k;
             want = true;
-            cls = kt_class_of(len, g);
+            cls = vgl_rc_class_of(len, g.b);
             m_acc += len;
         }
-        vgl_wave_append<KT_NCLS>(want, (int32_t)e, cls, g.L.list, g.L.cap, cnt + KT_TAIL);
+        vgl_wave_append<VGL_RC_N>(want, (int32_t)e, cls, g.L.list, g.L.cap, cnt + KT_TAIL);
     }
     vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_short(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
 {
-    const int gi = threadIdx.x & (KT_G - 1);
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t m_acc = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / KT_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / KT_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / KT_G;
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         const bool has = i < n;
         const int32_t e = has ? edges[i] : 0;
         kt_rows r{0, 0, 0, 0};
         if (has) r = kt_rows_of(e, g);
-        kt_expand(has, e, r, gi, KT_G, k, s, g, cnt + KT_TAIL, m_acc);
+        kt_expand(has, e, r, gi, VGL_RC_G, k, s, g, cnt + KT_TAIL, m_acc);
     }
     vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
@@ -282,8 +279,6 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     bool built = false;
     VGL_TRY(vgl_simple_ensure_edge_ids(c, g, &kt, &built));
     hipStream_t st = c->stream;
-    const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_KTRUSS_SHORT", 32, 0, 1 << 20);
-    const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_KTRUSS_WAVE", 1024, b_short, 1 << 24);
     vgl_hip_ktruss_stats out;
     memset(&out, 0, sizeof(out));
     out.prepared_now = built ? 1 : 0;
@@ -303,7 +298,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     vgl_dev<unsigned long long> cnt;
     VGL_TRY(sup.alloc(st, (size_t)ne));
     VGL_TRY(stamp.alloc(st, (size_t)ne));
-    VGL_TRY(lists.alloc(st, (size_t)ne * KT_NCLS));
+    VGL_TRY(lists.alloc(st, (size_t)ne * VGL_RC_N));
     VGL_TRY(cnt.alloc(st, KT_NCNT));
     VGL_HIP_TRY(hipMemsetAsync(stamp, 0, sizeof(int32_t) * (size_t)ne, st));
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * KT_NCNT, st));
@@ -312,43 +307,33 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     kg.rowptr = kt->csr.rowptr; kg.adj = kt->csr.adj; kg.deg = kt->csr.deg;
     kg.eid = kt->eid; kg.eu = kt->eu; kg.ev = kt->ev;
     kg.sup = sup; kg.stamp = stamp; kg.truss = d_truss;
-    kg.b_short = b_short; kg.b_wave = b_wave;
-    for (int k_ = 0; k_ < KT_NCLS; k_++) kg.L.list[k_] = lists.p + (size_t)ne * k_;
+    kg.b = vgl_rc_env_bounds(c, "VGL_KTRUSS_SHORT", "VGL_KTRUSS_WAVE");
+    for (int k_ = 0; k_ < VGL_RC_N; k_++) kg.L.list[k_] = lists.p + (size_t)ne * k_;
     kg.L.cap = ne;
 
-    int64_t head[KT_NCLS] = {0, 0, 0}, tail[KT_NCLS] = {0, 0, 0}, m_cum = 0;
+    vgl_rc_window w;                             // the edges of the step: [head, tail) of the class lists
+    int64_t m_cum = 0;
     // the one host-visible read of a step: the counters through the pinned mirror; the lists' new tails
     auto read = [&]() -> int {
         VGL_TRY(vgl_publish_counters(c, "ktruss_publish", cnt, KT_NCNT));
-        for (int k_ = 0; k_ < KT_NCLS; k_++) {
-            head[k_] = tail[k_];
-            tail[k_] = c->h_counters[KT_TAIL + k_];
-            if (tail[k_] < head[k_] || tail[k_] > ne) VGL_FAIL("ktruss_run: internal error (an edge list ran past its end)");
-        }
+        VGL_TRY(w.advance(c->h_counters + KT_TAIL, ne, "ktruss_run: internal error (an edge list ran past its end)"));
         m_cum = c->h_counters[KT_M];
         return 0;
     };
-    // a launch per class that has edges in [head, tail)
-#define KT_PER_CLASS(slot_short, k_short, slot_wave, k_wave, slot_wg, k_wg, ...)                                                                     \
-    do {                                                                                                                                             \
-        if (tail[KT_SHORT] > head[KT_SHORT]) {                                                                                                       \
-            const int64_t n = tail[KT_SHORT] - head[KT_SHORT];                                                                                       \
-            vgl_timed_launch tl(c, slot_short);                                                                                                      \
-            hipLaunchKernelGGL(k_short, dim3(vgl_grid(n * KT_G, VGL_BLOCK, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_SHORT] + head[KT_SHORT]), (int32_t)n, \
-                               __VA_ARGS__);                                                                                                         \
-        }                                                                                                                                            \
-        if (tail[KT_WAVE] > head[KT_WAVE]) {                                                                                                         \
-            const int64_t n = tail[KT_WAVE] - head[KT_WAVE];                                                                                         \
-            vgl_timed_launch tl(c, slot_wave);                                                                                                       \
-            hipLaunchKernelGGL(k_wave, dim3(vgl_grid(n, VGL_WAVES, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WAVE] + head[KT_WAVE]), (int32_t)n, __VA_ARGS__); \
-        }                                                                                                                                            \
-        if (tail[KT_WG] > head[KT_WG]) {                                                                                                             \
-            const int64_t n = tail[KT_WG] - head[KT_WG];                                                                                             \
-            vgl_timed_launch tl(c, slot_wg);                                                                                                         \
-            hipLaunchKernelGGL(k_wg, dim3(vgl_grid(n, 1, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, (const int32_t *)(kg.L.list[KT_WG] + head[KT_WG]), (int32_t)n, __VA_ARGS__); \
-        }                                                                                                                                            \
-        VGL_HIP_TRY(hipGetLastError());                                                                                                              \
-    } while (0)
+    // a launch per class that has edges in [head, tail): the support pass and the peel have the same grids
+    auto per_class = [&](const char *const *slot, auto k_short, auto k_wave, auto k_wg, auto... args) -> int {
+        return vgl_rc_launch(c, slot, w, [&](int cls, int64_t n) {
+            const int32_t *edges = kg.L.list[cls] + w.head[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(k_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(k_wave, dim3(vgl_grid(n, VGL_WAVES, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
+            else
+                hipLaunchKernelGGL(k_wg, dim3(vgl_grid(n, 1, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
+        });
+    };
+    const char *const sup_slot[VGL_RC_N] = {"ktruss_sup_short", "ktruss_sup_wave", "ktruss_sup_wg"};
+    const char *const peel_slot[VGL_RC_N] = {"ktruss_short", "ktruss_wave", "ktruss_wg"};
 
     // ---- the initial supports ----
     {
@@ -357,10 +342,10 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     }
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
-    if (tail[0] + tail[1] + tail[2] != ne) VGL_FAIL("ktruss_run: internal error (the classes do not add up to the edges)");
-    KT_PER_CLASS("ktruss_sup_short", vgl_k_ktruss_sup_short, "ktruss_sup_wave", vgl_k_ktruss_sup_wave, "ktruss_sup_wg", vgl_k_ktruss_sup_wg, cnt.p);
-    VGL_HIP_TRY(hipMemsetAsync(cnt.p + KT_TAIL, 0, sizeof(unsigned long long) * KT_NCLS, st));      // the lists are the peel's from here on
-    for (int k_ = 0; k_ < KT_NCLS; k_++) head[k_] = tail[k_] = 0;
+    if (w.total() != ne) VGL_FAIL("ktruss_run: internal error (the classes do not add up to the edges)");
+    VGL_TRY(per_class(sup_slot, vgl_k_ktruss_sup_short, vgl_k_ktruss_sup_wave, vgl_k_ktruss_sup_wg, cnt.p));
+    VGL_HIP_TRY(hipMemsetAsync(cnt.p + KT_TAIL, 0, sizeof(unsigned long long) * VGL_RC_N, st));      // the lists are the peel's from here on
+    w = vgl_rc_window{};
     VGL_TRY(read());
     out.triangles = c->h_counters[KT_SUM] / 3;
     out.support_elements = c->h_counters[KT_WALK];
@@ -373,9 +358,8 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     int64_t subs = 0;
     bool limited = false;
     for (;;) {
-        const int64_t F = tail[0] - head[0] + tail[1] - head[1] + tail[2] - head[2];
-        if (F == 0) {                                                 // ---- k change ----
-            if (tail[0] + tail[1] + tail[2] == ne) break;
+        if (w.live() == 0) {                                                 // ---- k change ----
+            if (w.total() == ne) break;
             VGL_HIP_TRY(hipMemsetAsync(cnt.p + KT_K, 0x7F, sizeof(unsigned long long), st));      // KT_NO_K
             {
                 vgl_timed_launch tl(c, "ktruss_scan");
@@ -394,17 +378,16 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
             k = (int32_t)m + 2;
             s++;
             rounds++;
-            if (tail[0] + tail[1] + tail[2] == head[0] + head[1] + head[2]) VGL_FAIL("ktruss_run: internal error (the level of the smallest remaining support is empty)");
+            if (w.live() == 0) VGL_FAIL("ktruss_run: internal error (the level of the smallest remaining support is empty)");
             continue;
         }
         // ---- one sub-round: a launch per class that has edges, then the read ----
         if (s == INT_MAX) VGL_FAIL("ktruss_run: more than 2^31 sub-rounds");
-        KT_PER_CLASS("ktruss_short", vgl_k_ktruss_short, "ktruss_wave", vgl_k_ktruss_wave, "ktruss_wg", vgl_k_ktruss_wg, k, s, cnt.p);
+        VGL_TRY(per_class(peel_slot, vgl_k_ktruss_short, vgl_k_ktruss_wave, vgl_k_ktruss_wg, k, s, cnt.p));
         VGL_TRY(read());
         s++;
         subs++;
     }
-#undef KT_PER_CLASS
     if (limited) {
         hipLaunchKernelGGL(vgl_k_ktruss_fill_limit, dim3(vgl_grid(ne, VGL_BLOCK, 4096)), dim3(VGL_BLOCK), 0, st, ne, (const int32_t *)stamp.p, k_limit, d_truss);
         VGL_HIP_TRY(hipGetLastError());

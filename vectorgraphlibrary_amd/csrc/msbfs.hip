@@ -24,7 +24,7 @@
 // and pull; nxt is touched only by atomics in push, and in pull only by its single writer (short and wave rows) or only by atomics (chunked rows);
 // settle reads nxt and the list tails, which the launch before it wrote, writes seen[v] for the listed v alone, and clears the OTHER word array.
 // Everything else crosses a kernel boundary.  No cooperative launch, no grid barrier, no spin on a flag.
-#include "vgl_hip_internal.h"
+#include "vgl_rowclass.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -33,13 +33,9 @@
 namespace {
 
 typedef unsigned long long ms_word;
-constexpr int MS_NCLS = 3;
-enum { MS_SHORT = 0, MS_WAVE = 1, MS_WG = 2 };
-constexpr int MS_G = 8;                          // lanes per short row
 constexpr int MS_BATCH = 64;                     // sources per batch: one bit each
 constexpr int MS_MAX_CHUNKS = 32768;             // chunks of the longest row
 constexpr int64_t MS_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
-constexpr int MS_STAGE = 128;                    // LDS slots per wave and class of the append staging (fewer than 64 wait, at most 64 arrive)
 enum {
     MS_TAIL = 0,        // + class: vertices appended to the next list of the class by this level
     MS_ENTRIES = 3,     // traversal-direction degrees of the next frontier's vertices
@@ -51,11 +47,8 @@ enum {
 };
 static_assert(MS_NPUB <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-struct ms_bounds { int32_t shrt, wave; };
-__host__ __device__ inline int ms_class_of(int64_t d, ms_bounds b) { return d <= b.shrt ? MS_SHORT : d <= b.wave ? MS_WAVE : MS_WG; }
-
 // the lists of one frontier: one per row class of the traversal direction, cap[c] = rows of the class
-struct ms_lists { int32_t *rows[MS_NCLS]; int32_t cap[MS_NCLS]; };
+struct ms_lists { int32_t *rows[VGL_RC_N]; int32_t cap[VGL_RC_N]; };
 // where a level appends: the next lists, the class of every vertex in the traversal direction, the counters
 struct ms_out { ms_lists next; const uint8_t *cls; ms_word *cnt; };
 // one level: the CSR it walks (push: the traversal direction; pull: its reverse) and the words
@@ -69,13 +62,13 @@ struct ms_level {
 };
 
 // ---- prepare: the class of every row of one direction, the class sizes, the longest row; then the rows by class ----
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_classify(int32_t V, const int64_t *rowptr, ms_bounds b, uint8_t *cls, ms_word *sizes, ms_word *max_row)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_classify(int32_t V, const int64_t *rowptr, vgl_rc_bounds b, uint8_t *cls, ms_word *sizes, ms_word *max_row)
 {
-    int64_t n[MS_NCLS] = {0, 0, 0};
+    int64_t n[VGL_RC_N] = {0, 0, 0};
     ms_word m = 0;
     for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
         const int64_t d = rowptr[v + 1] - rowptr[v];
-        const int k = ms_class_of(d, b);
+        const int k = vgl_rc_class_of(d, b);
         cls[v] = (uint8_t)k;
         n[k]++;
         m = max(m, (ms_word)max(d, (int64_t)0));
@@ -84,60 +77,33 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_classify(int32_t V, con
     for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
     if (vgl_lane() == 0 && m) atomicMax(max_row, m);
 #pragma unroll
-    for (int c = 0; c < MS_NCLS; c++) vgl_wave_flush_add(sizes + c, n[c]);
+    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(sizes + c, n[c]);
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_rows(int32_t V, const uint8_t *cls, int32_t *r0, int32_t *r1, int32_t *r2, ms_word *tail)
 {
-    int32_t *const lists[MS_NCLS] = {r0, r1, r2};
+    int32_t *const lists[VGL_RC_N] = {r0, r1, r2};
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t v = base + threadIdx.x;
         const bool want = v < V;
-        vgl_wave_append<MS_NCLS>(want, (int32_t)v, want ? (int)cls[v] : 0, lists, V, tail);
+        vgl_wave_append<VGL_RC_N>(want, (int32_t)v, want ? (int)cls[v] : 0, lists, V, tail);
     }
 }
 
-// ---- the append staging: `n` (uniform over the wave) vertices wait in `buf` (LDS, MS_STAGE slots, this wave's own) ----
-struct ms_stage { int32_t *buf; int n; };
-__device__ __forceinline__ void ms_flush(ms_stage &s, int32_t *rows, int32_t cap, ms_word *tail)      // every lane of the wave
-{
-    if (s.n == 0) return;                                             // (uniform)
-    ms_word base = 0;
-    if (vgl_lane() == 0) base = atomicAdd(tail, (ms_word)s.n);
-    base = __shfl(base, 0);
-    for (int j = vgl_lane(); j < s.n; j += 64) {
-        const ms_word pos = base + (ms_word)j;
-        if (pos < (ms_word)cap) rows[pos] = s.buf[j];
-    }
-    __builtin_amdgcn_wave_barrier();
-    s.n = 0;
-}
-__device__ __forceinline__ void ms_keep(ms_stage &s, bool want, int32_t v, int32_t *rows, int32_t cap, ms_word *tail)      // every lane of the wave
-{
-    const ms_word m = __ballot(want);
-    if (!m) return;                                                   // (uniform)
-    if (want) s.buf[s.n + __popcll(m & ((1ull << vgl_lane()) - 1ull))] = v;
-    s.n += __popcll(m);
-    __builtin_amdgcn_wave_barrier();
-    if (s.n >= 64) ms_flush(s, rows, cap, tail);
-}
-struct ms_stages { ms_stage c[MS_NCLS]; };
+// ---- the append staging: one vgl_rc_stage per class, onto the next lists (a list drops what runs past its end) ----
+__device__ __forceinline__ vgl_rc_bounded ms_next(const ms_out &o, int c) { return vgl_rc_bounded{o.next.rows[c], o.next.cap[c]}; }
 // every lane of the wave: the lanes with `app` append v to the next list of v's class
-__device__ __forceinline__ void ms_append(ms_stages &st, bool app, int32_t v, const ms_out &o)
+__device__ __forceinline__ void ms_append(vgl_rc_stage *st, bool app, int32_t v, const ms_out &o)
 {
     if (!__any(app)) return;                                          // (uniform)
     const int k = app ? (int)o.cls[v] : -1;
 #pragma unroll
-    for (int c = 0; c < MS_NCLS; c++) ms_keep(st.c[c], k == c, v, o.next.rows[c], o.next.cap[c], o.cnt + MS_TAIL + c);
+    for (int c = 0; c < VGL_RC_N; c++) st[c].keep(k == c, v, ms_next(o, c), o.cnt + MS_TAIL + c);
 }
-__device__ __forceinline__ void ms_flush_all(ms_stages &st, const ms_out &o)
+__device__ __forceinline__ void ms_flush_all(vgl_rc_stage *st, const ms_out &o)
 {
 #pragma unroll
-    for (int c = 0; c < MS_NCLS; c++) ms_flush(st.c[c], o.next.rows[c], o.next.cap[c], o.cnt + MS_TAIL + c);
+    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(ms_next(o, c), o.cnt + MS_TAIL + c);
 }
-#define MS_STAGES(st)                                                   \
-    __shared__ int32_t s_keep[MS_NCLS][VGL_WAVES][MS_STAGE];            \
-    ms_stages st;                                                       \
-    _Pragma("unroll") for (int c_ = 0; c_ < MS_NCLS; c_++) st.c[c_] = ms_stage{s_keep[c_][vgl_wave()], 0}
 
 __device__ __forceinline__ ms_word ms_wave_or(ms_word m)
 {
@@ -150,10 +116,10 @@ __device__ __forceinline__ ms_word ms_wave_or(ms_word m)
 __global__ __launch_bounds__(MS_BATCH) void vgl_k_msbfs_seed(const int32_t *src, int32_t nb, int32_t base, int32_t V, const int64_t *rowptr, ms_word *cur, ms_word *seen, ms_lists first,
                                                               const uint8_t *cls, ms_word *cnt, int64_t *reached, int64_t *dist_sum, int32_t *ecc, double *harmonic, int32_t *levels)
 {
-    __shared__ int s_tail[MS_NCLS];
+    __shared__ int s_tail[VGL_RC_N];
     __shared__ ms_word s_entries;
     const int b = threadIdx.x;
-    if (b < MS_NCLS) s_tail[b] = 0;
+    if (b < VGL_RC_N) s_tail[b] = 0;
     if (b == 0) s_entries = 0;
     __syncthreads();
     if (b < nb) {
@@ -164,7 +130,7 @@ __global__ __launch_bounds__(MS_BATCH) void vgl_k_msbfs_seed(const int32_t *src,
         if (old == 0) {                                               // the first bit on this vertex lists it
             const int k = cls[v];
 #pragma unroll
-            for (int c = 0; c < MS_NCLS; c++)
+            for (int c = 0; c < VGL_RC_N; c++)
                 if (k == c) {
                     const int pos = atomicAdd(&s_tail[c], 1);
                     if (pos < first.cap[c]) first.rows[c][pos] = v;
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(MS_BATCH) void vgl_k_msbfs_seed(const int32_t *src,
         if (levels) levels[(int64_t)(base + b) * V + v] = 1;
     }
     __syncthreads();
-    if (b < MS_NCLS) cnt[MS_TAIL + b] = (ms_word)s_tail[b];
+    if (b < VGL_RC_N) cnt[MS_TAIL + b] = (ms_word)s_tail[b];
     if (b == 0) cnt[MS_ENTRIES] = s_entries;
 }
 
@@ -191,10 +157,11 @@ __device__ __forceinline__ bool ms_push_entry(const ms_level &t, ms_word cv, int
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_short(ms_level t, const int32_t *rows, int32_t n)
 {
-    MS_STAGES(st);
-    const int gi = threadIdx.x & (MS_G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / MS_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / MS_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / MS_G;
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         ms_word cv = 0;
         int64_t lo = 0, hi = 0;
         if (i < n) {
@@ -202,7 +169,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_short(ms_level t, 
             cv = t.cur[v];
             lo = t.rowptr[v]; hi = t.rowptr[v + 1];
         }
-        for (int64_t e = lo + gi; __any(e < hi); e += MS_G) {        // (uniform over the wave)
+        for (int64_t e = lo + gi; __any(e < hi); e += VGL_RC_G) {        // (uniform over the wave)
             int32_t w = 0;
             bool app = false;
             if (e < hi) { w = t.adj[e]; app = ms_push_entry(t, cv, w); }
@@ -213,7 +180,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_short(ms_level t, 
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wave(ms_level t, const int32_t *rows, int32_t n)
 {
-    MS_STAGES(st);
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
     const int lane = vgl_lane();
     for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
         const int32_t v = rows[i];
@@ -232,7 +200,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wave(ms_level t, c
 // work item (row i / nchunks of the list, chunk i % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wg(ms_level t, const int32_t *rows, int32_t n, int32_t chunk, int32_t nchunks)
 {
-    MS_STAGES(st);
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
     const int lane = vgl_lane();
     const int64_t total = (int64_t)n * nchunks;
     for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {     // (uniform over the workgroup)
@@ -255,11 +224,12 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wg(ms_level t, con
 // ---- pull ----
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_short(ms_level t, const int32_t *rows, int32_t n)
 {
-    MS_STAGES(st);
-    const int gi = threadIdx.x & (MS_G - 1);
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
+    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t examined = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / MS_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / MS_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / MS_G;
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         int32_t v = 0;
         ms_word want = 0, acc = 0;
         if (i < n) {
@@ -268,14 +238,14 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_short(ms_level t, 
         }
         if (want) {
             const int64_t hi = t.rowptr[v + 1];
-            for (int64_t e = t.rowptr[v] + gi; e < hi; e += MS_G) {
+            for (int64_t e = t.rowptr[v] + gi; e < hi; e += VGL_RC_G) {
                 acc |= t.cur[t.adj[e]];
                 examined++;
                 if ((acc & want) == want) break;
             }
         }
 #pragma unroll
-        for (int o = MS_G / 2; o > 0; o >>= 1) acc |= __shfl_xor(acc, o);
+        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) acc |= __shfl_xor(acc, o);
         const ms_word nw = acc & want;
         const bool app = gi == 0 && nw != 0;
         if (app) t.nxt[v] = nw;
@@ -286,7 +256,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_short(ms_level t, 
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wave(ms_level t, const int32_t *rows, int32_t n)
 {
-    MS_STAGES(st);
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
     const int lane = vgl_lane();
     int64_t examined = 0;
     for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
@@ -342,7 +313,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wg(ms_level t, con
             if (nw != 0 && atomicOr(t.nxt + v, nw) == 0) {
                 const int k = t.out.cls[v];
 #pragma unroll
-                for (int c = 0; c < MS_NCLS; c++)
+                for (int c = 0; c < VGL_RC_N; c++)
                     if (k == c) {
                         const ms_word pos = atomicAdd(t.out.cnt + MS_TAIL + c, 1ull);
                         if (pos < (ms_word)t.out.next.cap[c]) t.out.next.rows[c][pos] = v;
@@ -356,7 +327,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wg(ms_level t, con
 // ---- settle ----
 struct ms_settle {
     ms_lists next, old;
-    int32_t old_n[MS_NCLS];      // the old lists' lengths (the host knows them); the next lists' are read from cnt
+    int32_t old_n[VGL_RC_N];      // the old lists' lengths (the host knows them); the next lists' are read from cnt
     ms_word *cnt;
     ms_word *seen;
     const ms_word *nxt;          // the words of the new frontier: cur from the next level on
@@ -432,12 +403,12 @@ struct vgl_msbfs_cache {
     struct dir_classes {
         vgl_dev<uint8_t> cls;                        // V
         vgl_dev<int32_t> rows;                       // V: the rows of class 0, then 1, then 2
-        int64_t size[MS_NCLS] = {};
+        int64_t size[VGL_RC_N] = {};
         int64_t max_row = 0;
         bool ready = false;
     } dir[2];                                        // 0 = outgoing, 1 = incoming
     int64_t key[2] = {-1, -1};
-    ms_bounds b{};
+    vgl_rc_bounds b{};
 };
 
 template <> void vgl_cache_free(vgl_msbfs_cache *p) { delete p; }
@@ -467,7 +438,7 @@ int ms_classify_dir(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_msbfs_cache *k, int d)
         VGL_HIP_TRY(hipGetLastError());
         VGL_HIP_TRY(hipStreamSynchronize(st));
     }
-    for (int i = 0; i < MS_NCLS; i++) dc.size[i] = (int64_t)h[i];
+    for (int i = 0; i < VGL_RC_N; i++) dc.size[i] = (int64_t)h[i];
     dc.max_row = (int64_t)h[3];
     dc.ready = true;
     return 0;
@@ -495,16 +466,15 @@ int ms_validate(const char *who, vgl_hip_ctx *c, vgl_hip_graph *g, int direction
 // the classes of the directions `plan` reads, under the switches as they stand; *built: something was built now
 int ms_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, ms_plan plan, vgl_msbfs_cache **out, bool *built)
 {
-    int64_t key[2];
-    key[0] = vgl_env_int(c, "VGL_MSBFS_SHORT", 32, 0, 1 << 20);
-    key[1] = vgl_env_int(c, "VGL_MSBFS_WAVE", 1024, key[0], 1 << 24);
+    const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_MSBFS_SHORT", "VGL_MSBFS_WAVE");
+    const int64_t key[2] = {b.shrt, b.wave};
     *built = false;
     if (!g->msbfs) g->msbfs.reset(new vgl_msbfs_cache());
     vgl_msbfs_cache *k = g->msbfs.get();
     if (!std::equal(key, key + 2, k->key)) {
         VGL_HIP_TRY(hipStreamSynchronize(c->stream));               // (kernels of an earlier run may still read the classes)
         k->dir[0].ready = k->dir[1].ready = false;
-        k->b = ms_bounds{(int32_t)key[0], (int32_t)key[1]};
+        k->b = b;
         std::copy(key, key + 2, k->key);
     }
     for (int d = 0; d < 2; d++)
@@ -531,7 +501,7 @@ ms_lists ms_lists_of(int32_t *rows, const int64_t *size)
 {
     ms_lists l;
     int64_t off = 0;
-    for (int k = 0; k < MS_NCLS; k++) {
+    for (int k = 0; k < VGL_RC_N; k++) {
         l.rows[k] = rows + off;
         l.cap[k] = (int32_t)size[k];
         off += size[k];
@@ -624,6 +594,8 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
         return vgl_wait_counters(c, seq);
     };
 
+    const char *const push_slot[VGL_RC_N] = {"msbfs_push_short", "msbfs_push_wave", "msbfs_push_wg"};
+    const char *const pull_slot[VGL_RC_N] = {"msbfs_pull_short", "msbfs_pull_wave", "msbfs_pull_wg"};
     int64_t words_total = 0;                                          // (vertex, level) pairs: the lengths of all frontiers
     for (int32_t base = 0; base < count; base += MS_BATCH) {
         const int32_t nb = std::min<int32_t>(MS_BATCH, count - base);
@@ -637,13 +609,13 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
                            d_reached, d_dist_sum, d_ecc, d_harmonic, d_levels);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(publish(nb, base, 0));
-        int64_t n[MS_NCLS], entries = c->h_counters[MS_ENTRIES];
-        for (int i = 0; i < MS_NCLS; i++) n[i] = c->h_counters[MS_TAIL + i];
+        int64_t n[VGL_RC_N], entries = c->h_counters[MS_ENTRIES];
+        for (int i = 0; i < VGL_RC_N; i++) n[i] = c->h_counters[MS_TAIL + i];
         out.reached_total += nb;
         int32_t expanded = 0;
         for (int32_t d = 1;; d++) {                                   // the frontier at distance d - 1 is expanded
             const int64_t total = n[0] + n[1] + n[2];
-            for (int i = 0; i < MS_NCLS; i++)
+            for (int i = 0; i < VGL_RC_N; i++)
                 if (n[i] < 0 || n[i] > now.cap[i]) VGL_FAIL("msbfs_run: internal error (a frontier list longer than its row class)");
             if (total == 0) break;
             if (d > V) VGL_FAIL("msbfs_run: internal error (more levels than vertices)");
@@ -654,43 +626,34 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
             t.out.next = next; t.out.cls = push_cls.cls; t.out.cnt = cnt;
             if (!pull) {
                 t.rowptr = push_csr.rowptr; t.adj = push_csr.adj;
-                if (n[MS_SHORT] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_push_short");
-                    hipLaunchKernelGGL(vgl_k_msbfs_push_short, dim3(vgl_grid(n[MS_SHORT] * MS_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)now.rows[MS_SHORT], (int32_t)n[MS_SHORT]);
-                }
-                if (n[MS_WAVE] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_push_wave");
-                    hipLaunchKernelGGL(vgl_k_msbfs_push_wave, dim3(vgl_grid(n[MS_WAVE], VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)now.rows[MS_WAVE], (int32_t)n[MS_WAVE]);
-                }
-                if (n[MS_WG] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_push_wg");
-                    hipLaunchKernelGGL(vgl_k_msbfs_push_wg, dim3(vgl_grid(n[MS_WG] * push_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)now.rows[MS_WG], (int32_t)n[MS_WG],
-                                       push_chunk, push_nchunks);
-                }
+                VGL_TRY(vgl_rc_launch(c, push_slot, n, [&](int cls, int64_t m) {
+                    const int32_t *rows = now.rows[cls];
+                    if (cls == VGL_RC_SHORT)
+                        hipLaunchKernelGGL(vgl_k_msbfs_push_short, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
+                    else if (cls == VGL_RC_WAVE)
+                        hipLaunchKernelGGL(vgl_k_msbfs_push_wave, dim3(vgl_grid(m, VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
+                    else
+                        hipLaunchKernelGGL(vgl_k_msbfs_push_wg, dim3(vgl_grid(m * push_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m, push_chunk, push_nchunks);
+                }));
                 out.levels_push++;
                 out.edges_push += entries;
             } else {
                 t.rowptr = pull_csr->rowptr; t.adj = pull_csr->adj;
-                const int64_t *m = pull_cls->size;
-                if (m[MS_SHORT] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_pull_short");
-                    hipLaunchKernelGGL(vgl_k_msbfs_pull_short, dim3(vgl_grid(m[MS_SHORT] * MS_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)pull_rows.rows[MS_SHORT], (int32_t)m[MS_SHORT]);
-                }
-                if (m[MS_WAVE] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_pull_wave");
-                    hipLaunchKernelGGL(vgl_k_msbfs_pull_wave, dim3(vgl_grid(m[MS_WAVE], VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)pull_rows.rows[MS_WAVE], (int32_t)m[MS_WAVE]);
-                }
-                if (m[MS_WG] > 0) {
-                    vgl_timed_launch tl(c, "msbfs_pull_wg");
-                    hipLaunchKernelGGL(vgl_k_msbfs_pull_wg, dim3(vgl_grid(m[MS_WG] * pull_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, (const int32_t *)pull_rows.rows[MS_WG], (int32_t)m[MS_WG],
-                                       pull_chunk, pull_nchunks);
-                }
+                VGL_TRY(vgl_rc_launch(c, pull_slot, pull_cls->size, [&](int cls, int64_t m) {
+                    const int32_t *rows = pull_rows.rows[cls];
+                    if (cls == VGL_RC_SHORT)
+                        hipLaunchKernelGGL(vgl_k_msbfs_pull_short, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
+                    else if (cls == VGL_RC_WAVE)
+                        hipLaunchKernelGGL(vgl_k_msbfs_pull_wave, dim3(vgl_grid(m, VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
+                    else
+                        hipLaunchKernelGGL(vgl_k_msbfs_pull_wg, dim3(vgl_grid(m * pull_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m, pull_chunk, pull_nchunks);
+                }));
                 out.levels_pull++;
             }
             {
                 ms_settle a;
                 a.next = next; a.old = now;
-                for (int i = 0; i < MS_NCLS; i++) a.old_n[i] = (int32_t)n[i];
+                for (int i = 0; i < VGL_RC_N; i++) a.old_n[i] = (int32_t)n[i];
                 a.cnt = cnt; a.seen = seen; a.nxt = nxt; a.old_cur = cur; a.rowptr = push_csr.rowptr; a.levels = d_levels;
                 a.V = V; a.level = d + 1; a.base = base; a.nb = nb;
                 // the next frontier has at most one vertex per entry of this one (push) or V (pull)
@@ -701,7 +664,7 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
             VGL_HIP_TRY(hipGetLastError());
             VGL_TRY(publish(nb, base, d));
             expanded++;
-            for (int i = 0; i < MS_NCLS; i++) n[i] = c->h_counters[MS_TAIL + i];
+            for (int i = 0; i < VGL_RC_N; i++) n[i] = c->h_counters[MS_TAIL + i];
             entries = c->h_counters[MS_ENTRIES];
             out.reached_total += c->h_counters[MS_BITS];
             out.edges_pull += c->h_counters[MS_PULLED];

@@ -20,18 +20,15 @@
 // The live lists are one ring per class of twice the class's rows: a round reads [head, tail) and appends behind tail, positions taken modulo the
 // capacity; appends are staged per wave in LDS and cost one returning atomic per 64 or more rows.  No cooperative launch, no grid barrier.
 #include "vgl_simple.h"
+#include "vgl_rowclass.h"
 #include <cstring>
 #include <algorithm>
 #include <climits>
 
 namespace {
 
-constexpr int MSF_NCLS = 3;
-enum { MSF_SHORT = 0, MSF_WAVE = 1, MSF_WG = 2 };
-constexpr int MSF_G = 8;                          // lanes per short row
 constexpr int MSF_MAX_CHUNKS = 32768;             // chunks of the longest row
 constexpr int64_t MSF_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
-constexpr int MSF_STAGE = 128;                    // LDS slots per wave of the append staging (fewer than 64 wait, at most 64 arrive)
 constexpr int MSF_MAX_ROUNDS = 64;                // (a run has at most ceil(log2 V) <= 31 rounds that add an edge, plus the empty one)
 constexpr int MSF_SUM_GRID = 1024;                // partials of the weight sum at most
 constexpr unsigned long long MSF_NONE = ~0ull;    // "no crossing edge" in best (a byte pattern: one memset arms the array)
@@ -45,7 +42,6 @@ enum {
 };
 static_assert(MSF_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-struct msf_ring { int32_t *rows; uint32_t cap; };      // positions are cumulative: slot = position % cap
 struct msf_graph {
     const int64_t *rowptr;       // the symmetric CSR
     const int32_t *adj;
@@ -54,7 +50,6 @@ struct msf_graph {
     const int32_t *comp;
     unsigned long long *best;
 };
-__device__ __forceinline__ int msf_class_of(int32_t d, int32_t b_short, int32_t b_wave) { return d <= b_short ? MSF_SHORT : d <= b_wave ? MSF_WAVE : MSF_WG; }
 
 // float -> uint32 that orders as the numbers do (-0.0 == +0.0; -inf smallest, +inf largest), and back
 __device__ __forceinline__ uint32_t msf_key_of(float w)
@@ -91,57 +86,35 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_edge_weight(int32_t ne, c
 }
 
 // ---- the live lists ----
-// A wave's staged appends: `n` (uniform over the wave) rows wait in `buf` (LDS, MSF_STAGE slots, this wave's own).
-struct msf_stage { int32_t *buf; int n; };
-__device__ __forceinline__ void msf_flush(msf_stage &s, const msf_ring &R, unsigned long long *tail)      // every lane of the wave
-{
-    if (s.n == 0) return;                                             // (uniform)
-    unsigned long long base = 0;
-    if (vgl_lane() == 0) base = atomicAdd(tail, (unsigned long long)s.n);
-    base = __shfl(base, 0);
-    for (int j = vgl_lane(); j < s.n; j += 64) R.rows[(base + (unsigned long long)j) % R.cap] = s.buf[j];
-    __builtin_amdgcn_wave_barrier();
-    s.n = 0;
-}
-__device__ __forceinline__ void msf_keep(msf_stage &s, bool want, int32_t v, const msf_ring &R, unsigned long long *tail)      // every lane of the wave
-{
-    const unsigned long long m = __ballot(want);
-    if (!m) return;                                                   // (uniform)
-    if (want) s.buf[s.n + __popcll(m & ((1ull << vgl_lane()) - 1ull))] = v;
-    s.n += __popcll(m);
-    __builtin_amdgcn_wave_barrier();
-    if (s.n >= 64) msf_flush(s, R, tail);
-}
+// (appends: vgl_rc_stage onto the ring of the class, one returning atomic per 64 or more rows)
 // rows with an entry, per class
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_count(int32_t V, const int32_t *deg, int32_t b_short, int32_t b_wave, unsigned long long *cnt)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_count(int32_t V, const int32_t *deg, vgl_rc_bounds b, unsigned long long *cnt)
 {
-    int64_t n[MSF_NCLS] = {0, 0, 0};
+    int64_t n[VGL_RC_N] = {0, 0, 0};
     for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
         const int32_t d = deg[v];
-        if (d > 0) n[msf_class_of(d, b_short, b_wave)]++;
+        if (d > 0) n[vgl_rc_class_of(d, b)]++;
     }
 #pragma unroll
-    for (int c = 0; c < MSF_NCLS; c++) vgl_wave_flush_add(cnt + MSF_ROWS + c, n[c]);
+    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(cnt + MSF_ROWS + c, n[c]);
 }
 // comp[v] = v; the rows with an entry into the ring of their class
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_init(int32_t V, const int32_t *deg, int32_t b_short, int32_t b_wave, int32_t *comp, msf_ring R0, msf_ring R1, msf_ring R2,
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_init(int32_t V, const int32_t *deg, vgl_rc_bounds b, int32_t *comp, vgl_rc_ring R0, vgl_rc_ring R1, vgl_rc_ring R2,
                                                              unsigned long long *cnt)
 {
-    __shared__ int32_t s_keep[MSF_NCLS][VGL_WAVES][MSF_STAGE];
-    const msf_ring R[MSF_NCLS] = {R0, R1, R2};
-    msf_stage st[MSF_NCLS];
-#pragma unroll
-    for (int c = 0; c < MSF_NCLS; c++) st[c] = msf_stage{s_keep[c][vgl_wave()], 0};
+    const vgl_rc_ring R[VGL_RC_N] = {R0, R1, R2};
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
     for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
         const int64_t v = base + threadIdx.x;
         int32_t d = 0;
         if (v < V) { d = deg[v]; comp[v] = (int32_t)v; }
-        const int cls = msf_class_of(d, b_short, b_wave);
+        const int cls = vgl_rc_class_of(d, b);
 #pragma unroll
-        for (int c = 0; c < MSF_NCLS; c++) msf_keep(st[c], d > 0 && cls == c, (int32_t)v, R[c], cnt + MSF_TAIL + c);
+        for (int c = 0; c < VGL_RC_N; c++) st[c].keep(d > 0 && cls == c, (int32_t)v, R[c], cnt + MSF_TAIL + c);
     }
 #pragma unroll
-    for (int c = 0; c < MSF_NCLS; c++) msf_flush(st[c], R[c], cnt + MSF_TAIL + c);
+    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(R[c], cnt + MSF_TAIL + c);
 }
 
 // ---- the min-edge pass ----
@@ -161,14 +134,14 @@ __device__ __forceinline__ void msf_offer(unsigned long long *slot, unsigned lon
 {
     if (vgl_load_agent(slot) > key) atomicMin(slot, key);
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, msf_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
 {
-    __shared__ int32_t s_keep[VGL_WAVES][MSF_STAGE];
-    msf_stage st{s_keep[vgl_wave()], 0};
-    const int gi = threadIdx.x & (MSF_G - 1), lane = vgl_lane();
+    vgl_rc_stage st[1];
+    vgl_rc_stage_open(st);
+    const int gi = threadIdx.x & (VGL_RC_G - 1), lane = vgl_lane();
     int64_t walked = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / MSF_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / MSF_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / MSF_G;
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
         int32_t v = 0, cv = 0;
         int64_t lo = 0, hi = 0;
         if (i < n) {
@@ -176,9 +149,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, ms
             cv = g.comp[v];
             lo = g.rowptr[v]; hi = g.rowptr[v + 1];
         }
-        unsigned long long m = msf_walk(lo + gi, hi, MSF_G, cv, g);
+        unsigned long long m = msf_walk(lo + gi, hi, VGL_RC_G, cv, g);
 #pragma unroll
-        for (int o = MSF_G / 2; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
+        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
         if (gi == 0) walked += hi - lo;
         const bool found = gi == 0 && m != MSF_NONE;
         // the rows of this wave that share the first found row's component go to its slot as one
@@ -191,15 +164,15 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, ms
             if (lane == leader) msf_offer(g.best + c0, k0);
             else if (found && !same) msf_offer(g.best + cv, m);
         }
-        msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_SHORT);
+        st[0].keep(found, v, R, cnt + MSF_TAIL + VGL_RC_SHORT);
     }
-    msf_flush(st, R, cnt + MSF_TAIL + MSF_SHORT);
+    st[0].flush(R, cnt + MSF_TAIL + VGL_RC_SHORT);
     vgl_wave_flush_add(cnt + MSF_WALK, walked);
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, msf_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, unsigned long long *cnt)
 {
-    __shared__ int32_t s_keep[VGL_WAVES][MSF_STAGE];
-    msf_stage st{s_keep[vgl_wave()], 0};
+    vgl_rc_stage st[1];
+    vgl_rc_stage_open(st);
     const int lane = vgl_lane();
     int64_t walked = 0;
     for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
@@ -210,14 +183,14 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, msf
         const bool found = lane == 0 && m != MSF_NONE;
         if (lane == 0) walked += hi - lo;
         if (found) msf_offer(g.best + cv, m);
-        msf_keep(st, found, v, R, cnt + MSF_TAIL + MSF_WAVE);
+        st[0].keep(found, v, R, cnt + MSF_TAIL + VGL_RC_WAVE);
     }
-    msf_flush(st, R, cnt + MSF_TAIL + MSF_WAVE);
+    st[0].flush(R, cnt + MSF_TAIL + VGL_RC_WAVE);
     vgl_wave_flush_add(cnt + MSF_WALK, walked);
 }
 // work item w = (row w / nchunks of the segment, chunk w % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do.
 // A row is appended by the first of its chunks that finds a crossing entry: stamp[position in the segment] = the round.
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, msf_ring R, unsigned long long head, int32_t n, int32_t chunk, int32_t nchunks, int32_t round, int32_t *stamp,
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, int32_t chunk, int32_t nchunks, int32_t round, int32_t *stamp,
                                                                unsigned long long *cnt)
 {
     __shared__ unsigned long long s_red[VGL_WAVES];
@@ -241,7 +214,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, msf_r
             if (m != MSF_NONE) {
                 msf_offer(g.best + cv, m);
                 if (atomicExch(stamp + i, round) != round) {
-                    const unsigned long long pos = atomicAdd(cnt + MSF_TAIL + MSF_WG, 1ull);
+                    const unsigned long long pos = atomicAdd(cnt + MSF_TAIL + VGL_RC_WG, 1ull);
                     R.rows[pos % R.cap] = v;
                 }
             }
@@ -378,8 +351,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     const int32_t V = g->V;
     const int64_t E = g->out.edges;
     hipStream_t st = c->stream;
-    const int32_t b_short = (int32_t)vgl_env_int(c, "VGL_MSF_SHORT", 32, 0, 1 << 20);
-    const int32_t b_wave = (int32_t)vgl_env_int(c, "VGL_MSF_WAVE", 1024, b_short, 1 << 24);
+    const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_MSF_SHORT", "VGL_MSF_WAVE");
     const int64_t chunk_env = vgl_env_int(c, "VGL_MSF_CHUNK", 16384, 16, 1 << 28);
     vgl_hip_msf_stats out;
     memset(&out, 0, sizeof(out));
@@ -440,56 +412,53 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     VGL_TRY(best.alloc(st, (size_t)V));
     VGL_TRY(partials.alloc(st, (size_t)sum_grid + 1));
     VGL_HIP_TRY(hipMemsetAsync(best, 0xFF, sizeof(unsigned long long) * (size_t)V, st));      // MSF_NONE
-    hipLaunchKernelGGL(vgl_k_msf_count, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b_short, b_wave, cnt.p);
+    hipLaunchKernelGGL(vgl_k_msf_count, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b, cnt.p);
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
-    int64_t rows[MSF_NCLS], rows_total = 0;
-    for (int k = 0; k < MSF_NCLS; k++) {
+    int64_t rows[VGL_RC_N], rows_total = 0;
+    for (int k = 0; k < VGL_RC_N; k++) {
         rows[k] = c->h_counters[MSF_ROWS + k];
         if (rows[k] < 0 || rows[k] > V) VGL_FAIL("msf_run: internal error (more rows in a class than vertices)");
         rows_total += rows[k];
     }
     if (rows_total < 2 || rows_total > V) VGL_FAIL("msf_run: internal error (the classes do not add up to the rows that have an entry)");
     VGL_TRY(lists.alloc(st, (size_t)(2 * rows_total)));
-    VGL_TRY(stamp.alloc(st, (size_t)rows[MSF_WG]));
-    VGL_HIP_TRY(hipMemsetAsync(stamp, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(rows[MSF_WG], 1), st));
-    msf_ring R[MSF_NCLS];
+    VGL_TRY(stamp.alloc(st, (size_t)rows[VGL_RC_WG]));
+    VGL_HIP_TRY(hipMemsetAsync(stamp, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(rows[VGL_RC_WG], 1), st));
+    vgl_rc_ring R[VGL_RC_N];
     {
         int64_t off = 0;
-        for (int k = 0; k < MSF_NCLS; k++) {
+        for (int k = 0; k < VGL_RC_N; k++) {
             R[k].rows = lists.p + off;
             R[k].cap = (uint32_t)(2 * rows[k]);
             off += 2 * rows[k];
         }
     }
-    hipLaunchKernelGGL(vgl_k_msf_init, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b_short, b_wave, comp.p, R[0], R[1], R[2], cnt.p);
+    hipLaunchKernelGGL(vgl_k_msf_init, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b, comp.p, R[0], R[1], R[2], cnt.p);
     VGL_HIP_TRY(hipGetLastError());
 
     msf_graph mg;
     mg.rowptr = sg->csr.rowptr; mg.adj = sg->csr.adj; mg.eid = sg->eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;
     const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(sg->csr.max_deg, 1), MSF_MAX_CHUNKS));
     const int32_t nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max(sg->csr.max_deg, 1), chunk));
-    int64_t head[MSF_NCLS] = {0, 0, 0}, tail[MSF_NCLS] = {rows[0], rows[1], rows[2]}, picks = 0;
+    vgl_rc_window w;                             // the live rows: [head, tail) of the rings, cumulative positions
+    for (int k = 0; k < VGL_RC_N; k++) w.tail[k] = rows[k];
+    const char *const slot[VGL_RC_N] = {"msf_min_short", "msf_min_wave", "msf_min_wg"};
+    int64_t picks = 0;
     int32_t rounds = 0;
     for (int32_t round = 1;; round++) {
         if (round > MSF_MAX_ROUNDS) VGL_FAIL("msf_run: internal error (more rounds than a forest can take)");
         // ---- the min-edge pass: a launch per class that has live rows ----
-        if (tail[MSF_SHORT] > head[MSF_SHORT]) {
-            const int64_t n = tail[MSF_SHORT] - head[MSF_SHORT];
-            vgl_timed_launch tl(c, "msf_min_short");
-            hipLaunchKernelGGL(vgl_k_msf_min_short, dim3(vgl_grid(n * MSF_G, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_SHORT], (unsigned long long)head[MSF_SHORT], (int32_t)n, cnt.p);
-        }
-        if (tail[MSF_WAVE] > head[MSF_WAVE]) {
-            const int64_t n = tail[MSF_WAVE] - head[MSF_WAVE];
-            vgl_timed_launch tl(c, "msf_min_wave");
-            hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(vgl_grid(n, VGL_WAVES, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WAVE], (unsigned long long)head[MSF_WAVE], (int32_t)n, cnt.p);
-        }
-        if (tail[MSF_WG] > head[MSF_WG]) {
-            const int64_t n = tail[MSF_WG] - head[MSF_WG];
-            vgl_timed_launch tl(c, "msf_min_wg");
-            hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(vgl_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[MSF_WG], (unsigned long long)head[MSF_WG], (int32_t)n, chunk,
-                               nchunks, round, stamp.p, cnt.p);
-        }
+        VGL_TRY(vgl_rc_launch(c, slot, w, [&](int cls, int64_t n) {
+            const unsigned long long head = (unsigned long long)w.head[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(vgl_k_msf_min_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, cnt.p);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(vgl_grid(n, VGL_WAVES, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, cnt.p);
+            else
+                hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(vgl_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, chunk, nchunks, round, stamp.p,
+                                   cnt.p);
+        }));
         {
             vgl_timed_launch tl(c, "msf_hook");
             hipLaunchKernelGGL(vgl_k_msf_hook, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const unsigned long long *)best.p, sg->eu, sg->ev, parent.p,
@@ -505,20 +474,16 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
         }
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(read());
-        int64_t live = 0;
-        for (int k = 0; k < MSF_NCLS; k++) {
-            const int64_t was = tail[k] - head[k];
-            head[k] = tail[k];
-            tail[k] = c->h_counters[MSF_TAIL + k];
-            if (tail[k] < head[k] || tail[k] - head[k] > was) VGL_FAIL("msf_run: internal error (a live list grew)");
-            live += tail[k] - head[k];
-        }
+        const int64_t was[VGL_RC_N] = {w.n(0), w.n(1), w.n(2)};
+        VGL_TRY(w.advance(c->h_counters + MSF_TAIL, INT64_MAX, "msf_run: internal error (a live list grew)"));      // (a ring: positions have no end)
+        for (int k = 0; k < VGL_RC_N; k++)
+            if (w.n(k) > was[k]) VGL_FAIL("msf_run: internal error (a live list grew)");
         const int64_t now = c->h_counters[MSF_PICKS];
         if (now < picks || now >= V) VGL_FAIL("msf_run: internal error (more forest edges than a forest has)");
         if (now == picks) break;                                      // a round with no pick: every live row saw its own component only
         picks = now;
         rounds++;
-        if (live == 0) break;                                         // no row has a crossing entry left
+        if (w.live() == 0) break;                                         // no row has a crossing entry left
     }
 
     // ---- the smallest vertex id of every component; the weight of the forest ----
