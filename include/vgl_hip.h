@@ -744,6 +744,10 @@ int vgl_hip_bitmap_or_parts(vgl_hip_ctx *ctx, int64_t words, int parts, const ui
 int vgl_hip_bfs_step_bottom_up(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t *d_levels, int32_t level,
                                const uint64_t *d_visited_bits, const uint64_t *d_front_bits, uint64_t *d_next_bits,
                                int64_t *found, int64_t *probed);
+/* The frontier bitmap folded onto 2^17 bits, as the fused traversal's filtered bottom-up probe reads it (VGL_BFS_FILTER_F):
+ * d_fold[j] = OR over k of d_front[j + 2048 * k] for j in 0 .. 2047; words of d_front at and past `words` count as 0.  All 2048 words of
+ * d_fold are written.  Asynchronous on the context's stream. */
+int vgl_hip_bfs_front_fold(vgl_hip_ctx *ctx, int64_t words, const uint64_t *d_front, uint64_t *d_fold);
 /* bitmap (V bits, little-endian within uint64 words) of vertices with d_levels == level */
 int vgl_hip_levels_to_bitmap(vgl_hip_ctx *ctx, int32_t V, const int32_t *d_levels, int32_t level, uint64_t *d_bits);
 /* OR `parts` bitmaps (each V/64 words, contiguous) and set levels[v] = level where a bit is set and v is unvisited.

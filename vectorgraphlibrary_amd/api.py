@@ -65,6 +65,14 @@ class Context:
         _l.check(self.L.vgl_hip_timing_get(self.h, name.encode(), C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
+    def bfs_front_fold(self, front, words=None):
+        """vgl_hip_bfs_front_fold: the first `words` 64-bit words of the frontier bitmap `front` (int64 tensor) folded onto 2048 words, as the
+        filtered bottom-up probe of bfs() reads it"""
+        words = front.numel() if words is None else int(words)
+        fold = self.empty(2048, torch.int64)
+        _l.check(self.L.vgl_hip_bfs_front_fold(self.h, words, _ptr(front), _ptr(fold)))
+        return fold
+
     # ---- synthetic inputs ----
     def gen_rmat(self, scale, edge_factor, seed, relabel=True, first_edge=0, count=None):
         E = (1 << scale) * edge_factor if count is None else count

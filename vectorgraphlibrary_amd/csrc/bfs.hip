@@ -11,6 +11,8 @@
 //   vgl_k_bu_probe / vgl_k_bu_probe_wide: per unvisited vertex one or two head records (12 B each when every head id is below 0xFFFFFF, else 16 B)
 //                                        + up to 8 frontier-bit probes (thread-serial), remaining long rows strip-mined 16 lanes per vertex
 //                                        by the same workgroup
+//   vgl_k_front_fold + vgl_k_bu_probe_filtered / _wide_filtered: the same step on a level with a small frontier -- the frontier folded onto
+//                                        2^17 bits sits in LDS and answers most "not in the frontier" probes without a load
 #include "vgl_hip_internal.h"
 #include <chrono>
 #include "vgl_gnf.h"
@@ -809,20 +811,46 @@ __device__ __forceinline__ void vgl_load_head(const int4 *in_head, int64_t rec, 
         u[0] = h.x; u[1] = h.y; u[2] = h.z; u[3] = h.w;
     }
 }
-template <bool INLINE_HEAVY, bool PACKED>
+// FILTER: `fold` is the frontier bitmap folded onto VGL_FOLD_WORDS words (vgl_k_front_fold: bit id & 0x1FFFF is set when ANY frontier id maps to it,
+// so a clear bit says "not in the frontier" for certain).  The workgroup copies it to LDS and asks it first; only an id whose folded bit is set
+// costs the divergent load of its frontier word.  Same probes in the same order, same counters: the filter only answers some of them sooner.
+template <bool INLINE_HEAVY, bool PACKED, bool FILTER = false>
 __device__ __forceinline__ void vgl_bu_probe_body(int32_t nrows, int32_t row_base, int32_t chunk, const int64_t *in_rowptr,
                                                   const int32_t *in_adj, const uint64_t *visited, const uint64_t *in_nz,
                                                   const uint64_t *front, uint64_t *next, int32_t *levels, int32_t next_level,
                                                   int32_t *heavy, int64_t *partials, uint32_t *ticket, const int4 *in_head,
                                                   const uint64_t *in_long, const int32_t *nz_rank, int32_t nz_rows, int64_t *counters,
-                                                  volatile int64_t *host, int64_t seq)
+                                                  volatile int64_t *host, int64_t seq, const uint64_t *fold = nullptr)
 {
     static_assert(INLINE_HEAVY, "the deferred rows are scanned in the same launch");
     __shared__ int64_t s64[VGL_WAVES];
     __shared__ int s_nheavy;
+    __shared__ uint64_t s_fold[FILTER ? VGL_FOLD_WORDS : 1];        // (never referenced without FILTER: takes no LDS there)
     if (threadIdx.x == 0) s_nheavy = 0;
+    if constexpr (FILTER) {
+#pragma unroll
+        for (int i = 0; i < VGL_FOLD_WORDS / VGL_BLOCK; i++) s_fold[i * VGL_BLOCK + threadIdx.x] = fold[i * VGL_BLOCK + threadIdx.x];   // (launched with VGL_BLOCK threads)
+    }
     __syncthreads();
-    auto in_front = [&](int32_t u) -> uint32_t { return (uint32_t)((front[u >> 6] >> (u & 63)) & 1ULL); };
+    [[maybe_unused]] auto folded = [&](int32_t u) -> bool { return (s_fold[(u >> 6) & (VGL_FOLD_WORDS - 1)] >> (u & 63)) & 1ULL; };   // u = -1 reads word 2047: in bounds
+    auto in_front = [&](int32_t u) -> uint32_t {
+        if constexpr (FILTER) {
+            if (!folded(u)) return 0u;
+        }
+        return (uint32_t)((front[u >> 6] >> (u & 63)) & 1ULL);
+    };
+    // entries q0 .. 3 of a head record through the filter: all the LDS tests first, then the frontier words of the entries that passed are
+    // requested together and looked at only afterwards (a wavefront does not wait for one guarded load before it issues the next)
+    [[maybe_unused]] auto in_front4 = [&](const int32_t u[4], int q0) -> uint32_t {
+        uint64_t w[4] = {0ULL, 0ULL, 0ULL, 0ULL};
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (q >= q0 && u[q] >= 0 && folded(u[q])) w[q] = front[u[q] >> 6];
+        uint32_t hit = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) hit |= (uint32_t)((w[q] >> (u[q] & 63)) & 1ULL) << q;
+        return hit;
+    };
     int64_t found_cnt = 0, probes = 0;
     // The 64-row groups are dealt round-robin to the wavefronts of the grid (candidates cluster -- in a degree-sorted graph the unvisited
     // vertices of the later levels are the low-degree tail -- so contiguous chunks would leave most workgroups idle), and a wavefront
@@ -873,17 +901,26 @@ __device__ __forceinline__ void vgl_bu_probe_body(int32_t nrows, int32_t row_bas
                 // 59.2 us per launch, RMAT-27 533 against 517 -- its time does not follow a wavefront's dependent chain, see above.)
                 if (u0[0] >= 0) hit = in_front(u0[0]);
                 if (hit == 0) {
+                    if constexpr (FILTER) hit = in_front4(u0, 1);
+                    else {
 #pragma unroll
-                    for (int q = 1; q < 4; q++)
-                        if (u0[q] >= 0) hit |= in_front(u0[q]) << q;
+                        for (int q = 1; q < 4; q++)
+                            if (u0[q] >= 0) hit |= in_front(u0[q]) << q;
+                    }
                 }
                 bool longer = false;
                 if (hit == 0 && n == 4) {
                     int32_t u1[4];
                     vgl_load_head<PACKED>(in_head, (int64_t)nz_rows + rec, u1);
+                    if constexpr (FILTER) {
 #pragma unroll
-                    for (int q = 0; q < 4; q++)
-                        if (u1[q] >= 0) { n = 5 + q; hit |= in_front(u1[q]) << (4 + q); }
+                        for (int q = 0; q < 4; q++) if (u1[q] >= 0) n = 5 + q;
+                        hit = in_front4(u1, 0) << 4;
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < 4; q++)
+                            if (u1[q] >= 0) { n = 5 + q; hit |= in_front(u1[q]) << (4 + q); }
+                    }
                     longer = (in_long[v >> 6] >> (v & 63)) & 1ULL;
                 }
                 found = hit != 0;
@@ -916,7 +953,7 @@ __device__ __forceinline__ void vgl_bu_probe_body(int32_t nrows, int32_t row_bas
         while (!__all(done)) {
             const int64_t q = p + ql;
             bool hit = false;
-            if (!done && q < e) { const int32_t u = in_adj[q]; hit = (front[u >> 6] >> (u & 63)) & 1ULL; }
+            if (!done && q < e) hit = in_front(in_adj[q]) != 0;
             const unsigned long long hm = __ballot(hit);
             const unsigned qm = (unsigned)(hm >> (quarter * G)) & (G >= 32 ? 0xFFFFFFFFu : ((1u << (G & 31)) - 1u));
             if (!done) {
@@ -969,6 +1006,55 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe_wide(VGL_BU_PROBE_PA
 {
     vgl_bu_probe_body<INLINE_HEAVY, false>(VGL_BU_PROBE_ARGS);
 }
+// The filtered forms (FILTER above) are kernels of their own, launched only on the levels whose frontier is small (vgl_bfs_params::filter_f):
+// the two kernels above stay exactly what they were, and the packed filtered one is held to the same 80 scalar registers.  Compiler's figures
+// (profiles/r07_resource_usage.txt; the parent's in r07_resource_usage_parent.txt): vgl_k_bu_probe<true> 78 SGPRs / 40 VGPRs / 40 B LDS and
+// vgl_k_bu_probe_wide<true> 74 / 40 / 40 B, no scratch, occupancy 8 -- as in the parent; vgl_k_bu_probe_filtered<true> 78 SGPRs (12 scalars
+// kept in lanes of one VGPR, written before the probe loop and read after it), 50 VGPRs, 16 424 B LDS (8 workgroups per CU: 128 of 160 KiB), no
+// scratch, occupancy 8; vgl_k_bu_probe_wide_filtered<true> 86 / 48 / 16 424 B (it runs on graphs of 2^24 ids and more, where the bound of the
+// rule is rarely met); vgl_k_front_fold 18 / 14 / 512 B.
+// Measured on RMAT-24 (driver's 20 sources, rocprofv3 kernel trace, profiles/r07_bfs_launches_*.log, parent -> this, bound 65536: nine of the
+// 20 first levels are filtered, frontiers of 4.8 K - 54 K vertices): first bottom-up levels 185 / 164 / 104 / 109 / 196 / 137 / 136 / 209 / 98 us
+// -> 154 / 133 / 90 / 95 / 159 / 113 / 113 / 169 / 87, the other eleven and every second and third level unchanged (mean of the first level
+// 100.1 -> 89.2 us, second 37.1 -> 36.8, third 20.8 -> 20.7); the fold itself 5.7 - 6.5 us per launch.  That is a sixth to a fifth of those
+// levels, not the two thirds that the line "48 us + 6 ns per probe" promised: the filter answers most of their gathers from LDS (at F = 6 K at
+// most one non-member in twenty passes it) and the level still takes 80 % of its time, so the probes are not what it is made of (as the
+// LDS-window kernel of round 2 already said, above) -- what remains is the head records of ~5 M candidates that find nothing (both planes) and
+// the whole-row scans of the deferred ones, whose adjacency entries are still read.
+template <bool INLINE_HEAVY>
+__global__ __launch_bounds__(VGL_BLOCK) __attribute__((amdgpu_num_sgpr(80))) void vgl_k_bu_probe_filtered(VGL_BU_PROBE_PARAMS, const uint64_t *fold)
+{
+    vgl_bu_probe_body<INLINE_HEAVY, true, true>(VGL_BU_PROBE_ARGS, fold);
+}
+template <bool INLINE_HEAVY>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bu_probe_wide_filtered(VGL_BU_PROBE_PARAMS, const uint64_t *fold)
+{
+    vgl_bu_probe_body<INLINE_HEAVY, false, true>(VGL_BU_PROBE_ARGS, fold);
+}
+
+// fold[j] = OR over k of front[j + VGL_FOLD_WORDS * k] (words past `words` count as 0): the frontier bitmap folded onto 2^17 bits.  A workgroup
+// owns 16 consecutive output words (one 128-byte line per k); its 16 slices of 16 lanes take k = slice, slice + 16, ...; the slices are combined
+// by two shuffles and one pass through LDS.  No atomics, every output word is written.
+constexpr int VGL_FOLD_COLS = 16, VGL_FOLD_SLICES = VGL_BLOCK / VGL_FOLD_COLS;
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_front_fold(int64_t words, const uint64_t *front, uint64_t *fold)
+{
+    __shared__ uint64_t s_part[VGL_WAVES][VGL_FOLD_COLS];
+    const int col = threadIdx.x % VGL_FOLD_COLS, slice = threadIdx.x / VGL_FOLD_COLS;
+    const int64_t j = (int64_t)blockIdx.x * VGL_FOLD_COLS + col;
+    uint64_t acc = 0;
+    for (int64_t w = j + (int64_t)slice * VGL_FOLD_WORDS; w < words; w += (int64_t)VGL_FOLD_SLICES * VGL_FOLD_WORDS) acc |= front[w];
+    acc |= __shfl_xor(acc, 16);
+    acc |= __shfl_xor(acc, 32);
+    if (vgl_lane() < VGL_FOLD_COLS) s_part[vgl_wave()][col] = acc;
+    __syncthreads();
+    if (threadIdx.x < VGL_FOLD_COLS) {
+        uint64_t r = 0;
+#pragma unroll
+        for (int w = 0; w < VGL_WAVES; w++) r |= s_part[w][threadIdx.x];
+        fold[j] = r;
+    }
+}
+static_assert(VGL_FOLD_WORDS % VGL_FOLD_COLS == 0 && VGL_FOLD_COLS == 16 && VGL_BLOCK == 256, "vgl_k_front_fold: 16 columns, 4 slices per wavefront");
 
 // visited |= next; front = next; next = 0 (ready for the next emitting step without a memset)   (one word per thread)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bm_advance(int64_t words, uint64_t *visited, uint64_t *front, uint64_t *next)
@@ -1196,12 +1282,29 @@ int vgl_bfs_bm_gnf(vgl_hip_ctx *c, vgl_hip_graph *g, const uint64_t *front, bool
 
 // one bottom-up step over the owned rows, deferred long rows included, with the fold of the counters C_BU_FOUND / C_BU_EDGES (published
 // to the host under sequence number *seq_out: vgl_wait_counters when they are needed)
+// filtered (the fused traversal, on levels with a small frontier): `front` is folded into g->bm_fold first and the filtered kernel probes -- two
+// launches back to back, no host wait between them
+static int vgl_front_fold_launch(vgl_hip_ctx *c, int64_t words, const uint64_t *front, uint64_t *fold)
+{
+    vgl_timed_launch tl(c, "bfs_front_fold");
+    hipLaunchKernelGGL(vgl_k_front_fold, dim3(VGL_FOLD_WORDS / VGL_FOLD_COLS), dim3(VGL_BLOCK), 0, c->stream, words, front, fold);
+    return 0;
+}
 static int vgl_bfs_bu_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *levels, int32_t next_level, const uint64_t *visited,
-                             const uint64_t *front, uint64_t *next, int64_t *seq_out)
+                             const uint64_t *front, uint64_t *next, int64_t *seq_out, bool filtered = false)
 {
     const int32_t chunk = (int32_t)(vgl_ceil_div(vgl_ceil_div(g->nrows, VGL_BU_BLOCKS), VGL_BLOCK) * VGL_BLOCK);
     const int64_t seq = vgl_next_seq(c);
-    {
+    if (filtered) {
+        VGL_TRY(vgl_front_fold_launch(c, vgl_ceil_div(g->V, 64), front, g->bm_fold));
+        vgl_timed_launch tl(c, "bfs_bottom_up");
+        auto *kernel = g->in_head_packed ? vgl_k_bu_probe_filtered<true> : vgl_k_bu_probe_wide_filtered<true>;
+        hipLaunchKernelGGL(kernel, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
+                           g->in.rowptr, g->in.adj, visited, g->bm_in_nz, front, next, levels, next_level, g->heavy, g->bu_partials,
+                           g->tickets + 1 * VGL_TICKET_WORDS, reinterpret_cast<const int4 *>(g->in_head.p), g->bm_in_long,
+                           (const int32_t *)g->in_nz_rank, g->in_nz_rows, c->d_counters, (volatile int64_t *)c->h_counters, seq,
+                           (const uint64_t *)g->bm_fold);
+    } else {
         vgl_timed_launch tl(c, "bfs_bottom_up");
         auto *kernel = g->in_head_packed ? vgl_k_bu_probe<true> : vgl_k_bu_probe_wide<true>;
         hipLaunchKernelGGL(kernel, dim3(VGL_BU_BLOCKS), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, chunk,
@@ -1279,6 +1382,7 @@ struct vgl_bfs_params {
     double blocked_share;       // top-down levels with at least this share of the edges take the blocked pass (when prepared)
     int64_t small_m;            // edge bound of the list kernel (0: not used)
     int64_t bm_expand_f;        // frontiers up to this size are expanded from the bitmap when the list kernel is to follow
+    int64_t filter_f;           // bottom-up levels whose frontier has at most this many vertices fold it and probe through the LDS filter (0: never)
     bool use_hints, scan_bound, trace;
 };
 static vgl_bfs_params vgl_bfs_params_of(const vgl_bfs_tunables &tn, int64_t V, int mode)
@@ -1301,6 +1405,13 @@ static vgl_bfs_params vgl_bfs_params_of(const vgl_bfs_tunables &tn, int64_t V, i
     if (p.small_m < 64) p.small_m = 0;                       // not worth a launch of its own
     p.bm_expand_f = tn.bm_expand >= 0 ? tn.bm_expand : 262144;
     if (vgl_ceil_div(vgl_ceil_div(V, 64), VGL_BLOCK) > 8192) p.bm_expand_f = 0;     // (edge partials live in g->bu_partials: 4 * VGL_BU_BLOCKS slots)
+    // VGL_BFS_FILTER_F: with F frontier vertices at most F of the filter's 2^17 bits are set, so a non-member passes with probability <= F / 2^17
+    // (two in five at the default); a large frontier sets every bit and the filter only costs its fill.  RMAT-24, bottom-up kernels per traversal,
+    // two sweeps on one graph build each (profiles/r07_bfs_ab_filter_sweep.log: never 175 us, 4096 174, 16384 163, 65536 160, every level 162;
+    // r07_bfs_ab_filter_sweep_wide.log: never 179, 16384 167, 65536 163, 131072 162, 262144 162).  Every level is no faster than never on the
+    // wall clock (0.308 - 0.313 ms against 0.308 - 0.312: two more fold launches per traversal); 65536 .. 262144 measure the same (0.298 - 0.303
+    // against 0.311 - 0.314), so the bound is the smallest of them
+    p.filter_f = tn.filter_f >= 0 ? tn.filter_f : 65536;
     p.use_hints = do_mode && !tn.no_hint;
     p.scan_bound = do_mode && !tn.no_scan_bound;
     p.trace = tn.trace;
@@ -1522,7 +1633,9 @@ struct vgl_bfs_traversal {
         if (front == vgl_bfs_front::levels || front == vgl_bfs_front::pending) VGL_FAIL("bfs_run: internal error (bitmaps missing)");
         int64_t seq = 0;
         trace("-> bottom-up");
-        VGL_TRY(vgl_bfs_bu_launch(c, g, levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq));
+        const bool filtered = F <= p.filter_f;                              // F: the frontier the level probes against (known on every path here)
+        if (filtered) trace("bottom-up through the folded frontier");
+        VGL_TRY(vgl_bfs_bu_launch(c, g, levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq, filtered));
         hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited, g->bm_front, g->bm_next);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_wait_counters(c, seq));
@@ -1701,6 +1814,15 @@ int vgl_hip_bfs_step_bottom_up(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_leve
         if (found) *found = c->h_counters[C_BU_FOUND];
         if (probed) *probed = c->h_counters[C_BU_EDGES];
     }
+    return 0;
+}
+
+int vgl_hip_bfs_front_fold(vgl_hip_ctx *c, int64_t words, const uint64_t *d_front, uint64_t *d_fold)
+{
+    if (!c || !d_fold || (!d_front && words > 0)) VGL_FAIL("bfs_front_fold: null argument");
+    if (words < 0) VGL_FAIL("bfs_front_fold: bad size");
+    VGL_TRY(vgl_front_fold_launch(c, words, d_front, d_fold));
+    VGL_HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -80,6 +80,7 @@ void vgl_ctx_refresh_env(vgl_hip_ctx *c)
     if (const char *v = str("VGL_TD_EMIT_EDGES")) t.td_emit_edges = atoll(v);
     if (const char *v = str("VGL_BFS_SMALL_M")) t.small_m = atoll(v);
     if (const char *v = str("VGL_BFS_BM_EXPAND")) t.bm_expand = atoll(v);
+    if (const char *v = str("VGL_BFS_FILTER_F")) t.filter_f = atoll(v);
     if (const char *v = str("VGL_SHARD_TD_EMIT_EDGES")) t.shard_td_emit_edges = atoll(v);
     if (const char *v = str("VGL_TD_FILTER_SHARE")) t.td_filter_share = atof(v);
     if (const char *v = str("VGL_TD_LATE_SHARE")) t.td_late_share = atof(v);

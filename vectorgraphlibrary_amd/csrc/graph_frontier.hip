@@ -330,6 +330,7 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
     VGL_TRY(g->bm_visited.alloc(words));
     VGL_TRY(g->bm_front.alloc(words));
     VGL_TRY(g->bm_next.alloc(words));
+    VGL_TRY(g->bm_fold.alloc((size_t)VGL_FOLD_WORDS));
     VGL_TRY(g->bm_in_nz.alloc(words));
     VGL_TRY(g->ids.alloc((size_t)g->nrows));
     VGL_TRY(g->offs.alloc((size_t)g->nrows + 1));

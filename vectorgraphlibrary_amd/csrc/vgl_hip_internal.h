@@ -15,6 +15,7 @@ constexpr int VGL_BLOCK = 256;
 constexpr int VGL_EPT = 8;
 constexpr int VGL_TILE = VGL_BLOCK * VGL_EPT;      // 2048 edges (or vertices) per workgroup tile
 constexpr int VGL_WAVES = VGL_BLOCK / 64;
+constexpr int VGL_FOLD_WORDS = 2048;     // the folded frontier of the filtered bottom-up probe: 2^17 bits = 16 KiB of LDS per workgroup
 
 int vgl_set_error(const char *file, int line, const char *msg);
 #define VGL_FAIL(msg) return vgl_set_error(__FILE__, __LINE__, (msg))
@@ -51,7 +52,7 @@ struct vgl_timing_slot {
 // process environment has changed since (vgl_ctx_refresh_env: one pass over the pointers of `environ`, no string is looked at) -- not a dozen
 // getenv() per traversal.  A negative / NaN value = "not set": the traversal derives its default from the graph.
 struct vgl_bfs_tunables {
-    int64_t td_emit_edges = -1, small_m = -1, bm_expand = -1, shard_td_emit_edges = -1;
+    int64_t td_emit_edges = -1, small_m = -1, bm_expand = -1, shard_td_emit_edges = -1, filter_f = -1;
     double td_filter_share = -1.0, td_late_share = -1.0, blocked_share = -1.0;
     int shard_sparse_cap = -1;
     bool no_hint = false, no_scan_bound = false, trace = false;
@@ -193,6 +194,7 @@ struct vgl_hip_graph {
     vgl_dir_csr out, in;
     // scratch shared by the fused algorithms (allocated at creation, sized by V / nrows / edges)
     vgl_dev<uint64_t> bm_visited, bm_front, bm_next; // ceil(V/64)+1 words each
+    vgl_dev<uint64_t> bm_fold;     // VGL_FOLD_WORDS words: bm_front folded onto 2^17 bits for the filtered bottom-up probe (vgl_k_front_fold, bfs.hip)
     vgl_dev<uint64_t> bm_in_nz;    // bit v = owned vertex v has incoming edges (bottom-up candidates)
     vgl_dev<int32_t> in_head;      // two planes of 16-byte records (in-neighbours 0-3 and 4-7 of the eight smallest ids, -1 padded), ONE RECORD PER
                                      // OWNED ROW THAT HAS INCOMING EDGES, in row order: record index = in_nz_rank[group] + rank of the row among the set
