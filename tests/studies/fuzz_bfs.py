@@ -1,9 +1,13 @@
 """BFS-only fuzz at larger sizes: random graph shapes (skewed / uniform, sparse / dense, isolated vertices, self loops, multi-edges),
 both traversal modes, random settings of the small-level / bitmap-expand bounds, all three renumberings -- levels against the CPU
-oracle, and identical statistics between the settings.  usage: fuzz_bfs.py <first seed> <last seed>"""
+oracle, identical statistics between the settings, and the statistics the schedule fixes against its restatement
+(tests/bfs_schedule_reference.py; tests/test_bfs_schedule_gpu.py runs twelve seeds of this generator at V < 2^15 in the suite).
+usage: fuzz_bfs.py <first seed> <last seed>"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
+import bfs_schedule_reference as R
 from oracle import oracle as O
 from vectorgraphlibrary_amd import api
 ctx = api.Context(0)
@@ -24,7 +28,9 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
     try:
         for source in {int(rng.integers(0, V)), int(np.argmax(np.diff(rowptr))), 0}:
             ref = O.bfs_top_down(rowptr, adj, source)[0]
+            rec = R.schedule(V, src, dst, source)[1]                # (either mode expands the same frontiers: top-down mode = every record top-down)
             for mode in (api.BFS_TOP_DOWN, api.BFS_DIRECTION_OPT):
+                want = R.expected(rec if mode == api.BFS_DIRECTION_OPT else [r._replace(direction=R.TOP_DOWN) for r in rec])
                 seen = []
                 for k in range(3):
                     env = {} if k == 0 else {"VGL_BFS_SMALL_M": str(int(rng.choice([0, 64, 300, 8192, 1000000]))), "VGL_BFS_BM_EXPAND": str(int(rng.choice([0, 100, 262144, 1 << 30])))}
@@ -38,6 +44,7 @@ for seed in range(int(sys.argv[1]), int(sys.argv[2])):
                     finally:
                         for name in env: os.environ.pop(name, None)
                     assert (lv.cpu().numpy() == ref).all(), f"levels source {source} mode {mode} env {env}"
+                    assert {k: st[k] for k in R.STATS} == want, f"schedule source {source} mode {mode} env {env}: {R.directions(rec)} {st}"
                     seen.append((st["levels"], st["edges_examined"], st["frontier_total"], st["discovered"], st["td_steps"], st["bu_steps"]))
                 assert seen[0] == seen[1] == seen[2], f"stats differ source {source} mode {mode}: {seen}"
     except AssertionError as e:
