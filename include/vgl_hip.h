@@ -722,6 +722,82 @@ int vgl_hip_bicc_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected
 int vgl_hip_bicc_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t *d_edge_u, int32_t *d_edge_v, uint8_t *d_bridge, int32_t *d_edge_component,
                      uint8_t *d_articulation, int32_t *d_two_edge_component, vgl_hip_bicc_stats *stats);
 
+/* Maximal independent set (`mis`) and maximal matching (`matching`): the LEXICOGRAPHICALLY FIRST one under a fixed priority order, which is what the
+ * sequential greedy algorithm returns when it takes the vertices (edges) in ascending order.  The reference has neither, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *   key       key(i, seed) = fmix32(i ^ fmix32(seed + 0x9e3779b9)), all in uint32 arithmetic; fmix32 is the murmur3 finaliser
+ *             (h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16), a bijection of uint32: default keys never tie.
+ *   order     ascending (key, id), the smaller first; an equal key of a caller's array goes to the smaller id IN THE GRAPH'S OWN NUMBERING.
+ *   The answer is unique, an integer, and does not depend on any VGL_MIS_* switch, on the order of the entries in a row or on the order in which the
+ *   stores land (Blelloch, Fineman, Shun, SPAA 2012: the synchronous rounds below compute the greedy set).
+ * vgl_hip_mis_run:  d_priority (uint32, V, device) or NULL = key(v, seed).  Outputs, either may be NULL but not both:
+ *   d_in_set  uint8, V: 1 iff v is in the greedy set under the order;
+ *   d_round   int32, V: +r if v entered the set in round r, -r if it was excluded in round r (never 0), under these SYNCHRONOUS rounds: in round r an
+ *             undecided v goes OUT if a neighbour before it in the order is IN since a round < r; it goes IN if every neighbour before it is OUT since
+ *             a round < r (an isolated vertex is IN in round 1); otherwise it stays undecided.  In closed form: round(IN v) = 1 + max |round(w)| over
+ *             the neighbours w before v (1 if there are none); round(OUT v) = 1 + min round(w) over the IN neighbours w before v.
+ *   Method: one int32 array holds the signed round (d_round itself when given); a reader treats |state| == r as undecided, so there is no double buffer
+ *   and a store of the same launch is harmless.  The undecided rows are kept per row class of the symmetric simple CSR (<= VGL_MIS_SHORT (32): 8 lanes
+ *   per row, <= VGL_MIS_WAVE (1024): a wavefront that stops at the first IN neighbour before v, longer: a workgroup); the key of an entry is computed
+ *   (or gathered) first and the state read only for the entries before v.  One host read of the pinned mirror per round.  vgl_hip_mis_prepare (or the
+ *   first run) builds stage 1 of the handle's cache, the symmetric simple CSR shared with kcore, ktruss, msf and bicc.
+ *   timing slots: mis_init, mis_short, mis_wave, mis_wg, mis_publish, mis_finish.
+ *   stats, all exact and the same on every run: rounds (0 when V = 0); set_size; prepared_now = this call built the symmetric CSR;
+ *   live_total = the sum over the rounds of the number of undecided vertices at the start of the round (round 1: V);
+ *   entries_walked = the sum over the rounds of the FULL row lengths of those vertices (an upper bound of what the early exit reads, exact by definition);
+ *   algorithmic_bytes = 12 V (degree read, state cleared, list entry written) + 24 live_total (list entry read, row bounds read, state or list entry
+ *   written) + 8 entries_walked (the adjacency entry and the state of its far end; a caller's priority array is left out) + 64 (rounds + 1) (the 8
+ *   counters published after the classes are counted and after every round) + 5 V with d_in_set (state read, flag written): a lower bound; 0 when V = 0.
+ * vgl_hip_matching_run:  edges carry the library's edge numbering of vgl_hip_ktruss_run (ascending (lo, hi) in the graph's own vertex numbering,
+ *   E' < 2^31; stage 2 of the handle's cache, shared with ktruss, msf and bicc; vgl_hip_matching_prepare or the first run builds it and
+ *   *undirected_edges (host, may be NULL) receives E').  d_edge_priority (uint32, E', device) or NULL = key(edge id, seed).  Outputs, each may be NULL
+ *   but at least one must be given (the edge arrays are sized by the caller like k-truss's: E' <= stored entries):
+ *   d_edge_u / d_edge_v  int32, E', both or neither: lo, hi of edge i;
+ *   d_in_matching        uint8, E': 1 iff the edge is in the greedy matching over the edges ascending by (key, edge id);
+ *   d_mate               int32, V: the partner of v, or -1;
+ *   d_round              int32, V: the round in which v was matched, or 0.
+ *   Rounds, two passes each.  Pass 1: every live vertex v takes best[v] = the minimum over its entries whose far end is unmatched of
+ *   (key(e) << 32 | e); a vertex with no such entry leaves the worklist for good.  Pass 2: edge e = (u, v) is matched iff best[u] == best[v] == e;
+ *   both ends write their mate, the lower end writes d_in_matching[e]; the unmatched vertices that have a best are live in the next round.  In round 1
+ *   every vertex is live.  Method: pass 1 runs per row class (as above; the minimum is a 64-bit shuffle reduce per row group, the default key of an
+ *   entry is computed, not gathered) and lists the vertices with a best; pass 2 is one launch over that list, whose length it reads from the device.
+ *   timing slots: mm_init, mm_best_short, mm_best_wave, mm_best_wg, mm_match, mm_publish.
+ *   stats, all exact and the same on every run: rounds (0 when V = 0); matched_edges; matched_vertices = 2 matched_edges; undirected_edges = E';
+ *   prepared_now = this call built the edge numbering; live_total = the sum over the rounds of the live vertices of pass 1; entries_walked = the sum
+ *   over the rounds of their full row lengths (pass 1 only);
+ *   algorithmic_bytes = 20 V (degree read, mate and best initialised, list entry written) + 28 live_total (list entry read, row bounds read, best
+ *   written) + 12 entries_walked (the adjacency entry, its edge id, the mate of its far end; a caller's priority array is left out) + 72 (rounds + 1)
+ *   (the 9 counters published) + 16 E' with d_edge_u / d_edge_v (copied) + E' with d_in_matching (cleared) + 4 V with d_round (cleared); pass 2 is left
+ *   out: a lower bound; 0 when V = 0.
+ * Both fail, before anything is written: a sharded handle, all outputs NULL, one of d_edge_u / d_edge_v without the other, E' >= 2^31 (from the cache
+ * stage, as k-truss).  V == 0 succeeds with rounds = 0 and writes nothing (vgl_hip_graph_create hands out no such handle: the smallest graph is one vertex
+ * without an edge, rounds = 1). */
+typedef struct {
+    int32_t rounds;             /* synchronous rounds until every vertex is decided */
+    int32_t prepared_now;       /* this call built the symmetric simple CSR */
+    int64_t set_size;
+    int64_t live_total;         /* sum over rounds of undecided vertices */
+    int64_t entries_walked;     /* sum over rounds of their full row lengths */
+    int64_t algorithmic_bytes;
+} vgl_hip_mis_stats;
+int vgl_hip_mis_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
+int vgl_hip_mis_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const uint32_t *d_priority, uint32_t seed, uint8_t *d_in_set, int32_t *d_round,
+                    vgl_hip_mis_stats *stats);
+typedef struct {
+    int32_t rounds;             /* two-pass rounds until no vertex is live */
+    int32_t prepared_now;       /* this call built the edge numbering */
+    int64_t matched_edges;
+    int64_t matched_vertices;   /* 2 matched_edges */
+    int64_t undirected_edges;   /* E' */
+    int64_t live_total;         /* sum over rounds of live vertices */
+    int64_t entries_walked;     /* sum over rounds of their full row lengths, first pass */
+    int64_t algorithmic_bytes;
+} vgl_hip_matching_stats;
+int vgl_hip_matching_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undirected_edges);
+int vgl_hip_matching_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const uint32_t *d_edge_priority, uint32_t seed, int32_t *d_edge_u, int32_t *d_edge_v,
+                         uint8_t *d_in_matching, int32_t *d_mate, int32_t *d_round, vgl_hip_matching_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

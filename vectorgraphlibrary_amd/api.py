@@ -269,6 +269,17 @@ class Graph:
         _l.check(self.ctx.L.vgl_hip_bicc_prepare(self.ctx.h, self.h, C.byref(n)))
         return n.value
 
+    def prepare_mis(self):
+        """the symmetric simple CSR of maximal_independent_set() (shared with core_numbers()) now, outside any timing (vgl_hip_mis_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_mis_prepare(self.ctx.h, self.h))
+
+    def prepare_matching(self):
+        """the edge numbering of maximal_matching() / vertex_cover() (shared with truss_numbers(), minimum_spanning_forest() and
+        biconnected_components()) now, outside any timing (vgl_hip_matching_prepare); returns the number of undirected edges"""
+        n = C.c_int64()
+        _l.check(self.ctx.L.vgl_hip_matching_prepare(self.ctx.h, self.h, C.byref(n)))
+        return n.value
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -829,6 +840,99 @@ def two_edge_connected_components(graph, raw=False):
     """int32 [V]: the smallest vertex id of every vertex's 2-edge-connected component (ORIGINAL ids and vertex order unless raw=True); the block pass
     is skipped"""
     return _bicc(graph, raw, two_edge_component=True)["two_edge_component"]
+
+
+def _fmix32(h):
+    """the murmur3 finaliser on an int64 tensor of uint32 values"""
+    m = 0xFFFFFFFF
+    h = h ^ (h >> 16)
+    h = (h * 0x85ebca6b) & m
+    h = h ^ (h >> 13)
+    h = (h * 0xc2b2ae35) & m
+    return h ^ (h >> 16)
+
+
+def priority_key(ids, seed=0):
+    """key(i, seed) = fmix32(i ^ fmix32(seed + 0x9e3779b9)) of include/vgl_hip.h for an integer tensor of ids: int64 values in [0, 2^32)"""
+    mix = _fmix32(torch.tensor([(int(seed) + 0x9e3779b9) & 0xFFFFFFFF], dtype=torch.int64, device=ids.device))
+    return _fmix32((ids.to(torch.int64) & 0xFFFFFFFF) ^ mix)
+
+
+def _as_u32(ctx, values, n, who):
+    """n uint32 priorities as the int32 tensor of their bit patterns, on the context's device"""
+    p = torch.as_tensor(values).to(ctx.device).to(torch.int64).flatten()
+    if p.numel() != n:
+        raise _l.VglHipError("%s: %d priorities for %d items" % (who, p.numel(), n))
+    if n and (int(p.min()) < 0 or int(p.max()) > 0xFFFFFFFF):
+        raise _l.VglHipError("%s: priorities are uint32 values" % who)
+    return torch.where(p >= (1 << 31), p - (1 << 32), p).to(torch.int32).contiguous()
+
+
+def maximal_independent_set(graph, priority=None, seed=0, rounds=False, raw=False):
+    """the lexicographically first maximal independent set of the simple undirected graph underlying the stored outgoing CSR, under the order
+    (priority, id) ascending (the contract of vgl_hip_mis_run in include/vgl_hip.h): what the sequential greedy algorithm returns.  Returns
+    (size, stats dict); stats["in_set"] is a bool tensor [V]; rounds=True adds stats["round"] (int32 [V]: +r entered in round r, -r excluded in round
+    r).  priority: V uint32 values (any integer tensor or array), smaller first, ties to the smaller id in the graph's own numbering; None: the
+    library's key(id, seed).  priority and both outputs are in ORIGINAL vertex order, and the default keys are those of the ORIGINAL ids (built here
+    and passed for a renumbered graph), so the default result does not depend on renumber=; raw=True keeps the graph's own numbering throughout."""
+    ctx = graph.ctx
+    to_orig = not raw and graph.bwd is not None
+    prio = None
+    if priority is not None:
+        prio = _as_u32(ctx, priority, graph.V, "maximal_independent_set")
+        if to_orig:
+            prio = prio[graph.bwd.long()].contiguous()
+    elif to_orig:
+        prio = _as_u32(ctx, priority_key(graph.bwd, seed), graph.V, "maximal_independent_set")
+    in_set = ctx.empty(max(graph.V, 1), torch.uint8)[:graph.V]      # (never a NULL pointer: an empty graph is no refusal)
+    rnd = ctx.empty(max(graph.V, 1), torch.int32)[:graph.V] if rounds else None
+    st = _l.MisStats()
+    _l.check(ctx.L.vgl_hip_mis_run(ctx.h, graph.h, _ptr(prio), int(seed) & 0xFFFFFFFF, _ptr(in_set), _ptr(rnd), C.byref(st)))
+    stats = _stats(st)
+    stats["in_set"] = graph.to_original(in_set.to(torch.int32)).bool() if to_orig else in_set.bool()
+    if rounds:
+        stats["round"] = graph.to_original(rnd) if to_orig else rnd
+    return int(st.set_size), stats
+
+
+def maximal_matching(graph, edge_priority=None, seed=0, raw=False):
+    """the lexicographically first maximal matching of that graph under the order (priority, edge id) ascending over the library's edge numbering
+    (the contract of vgl_hip_matching_run in include/vgl_hip.h): what the sequential greedy algorithm over the edges returns.  Returns
+    (matched edges, stats dict); stats["edges"] is an int32 tensor [E', 2], lo < hi, stats["in_matching"] a bool tensor [E'], stats["mate"] an int32
+    tensor [V] (the partner, or -1) and stats["round"] an int32 tensor [V] (the round in which the vertex was matched, or 0).  Endpoints and mates are
+    ORIGINAL vertex ids, the edges ascend by (lo, hi) and the vertex arrays are in ORIGINAL order unless raw=True.  edge_priority (E' uint32 values)
+    and the default keys key(edge id, seed) follow THE GRAPH'S OWN edge numbering -- the row order of stats["edges"] under raw=True -- so on a renumbered
+    graph the default matching differs from that of the same graph without renumber=; it is the greedy matching either way."""
+    ctx = graph.ctx
+    cap = max(graph.E, 1)                                           # E' <= the stored entries: the run itself tells E' (and whether it prepared)
+    prio = None
+    if edge_priority is not None:
+        prio = _as_u32(ctx, edge_priority, graph.prepare_matching(), "maximal_matching")
+    eu, ev, mask = ctx.empty(cap, torch.int32), ctx.empty(cap, torch.int32), ctx.empty(cap, torch.uint8)
+    mate, rnd = ctx.empty(max(graph.V, 1), torch.int32)[:graph.V], ctx.empty(max(graph.V, 1), torch.int32)[:graph.V]
+    st = _l.MatchingStats()
+    _l.check(ctx.L.vgl_hip_matching_run(ctx.h, graph.h, _ptr(prio), int(seed) & 0xFFFFFFFF, _ptr(eu), _ptr(ev), _ptr(mask), _ptr(mate), _ptr(rnd), C.byref(st)))
+    stats = _stats(st)
+    n = int(st.undirected_edges)
+    eu, ev, mask = eu[:n], ev[:n], mask[:n].bool()
+    if not raw and graph.bwd is not None:
+        if n:
+            a, b = graph.bwd[eu.long()], graph.bwd[ev.long()]
+            eu, ev = torch.minimum(a, b), torch.maximum(a, b)
+            order = torch.argsort(eu.long() * graph.V + ev.long())
+            eu, ev, mask = eu[order], ev[order], mask[order]
+        partner = torch.where(mate >= 0, graph.bwd[mate.clamp(min=0).long()], mate)
+        mate, rnd = graph.to_original(partner.contiguous()), graph.to_original(rnd)
+    stats["edges"] = torch.stack([eu, ev], dim=1)
+    stats["in_matching"] = mask
+    stats["mate"] = mate
+    stats["round"] = rnd
+    return int(st.matched_edges), stats
+
+
+def vertex_cover(graph, edge_priority=None, seed=0, raw=False):
+    """a vertex cover of that graph of at most twice the minimum size: the matched vertices (mate >= 0) of maximal_matching(); a bool tensor [V]"""
+    return maximal_matching(graph, edge_priority=edge_priority, seed=seed, raw=raw)[1]["mate"] >= 0
 
 
 def count_not_equal(ctx, a, b):

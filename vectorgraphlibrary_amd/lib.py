@@ -84,6 +84,16 @@ class BiccStats(C.Structure):
                 ("two_edge_components", C.c_int64), ("largest_component_edges", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class MisStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("prepared_now", C.c_int32), ("set_size", C.c_int64), ("live_total", C.c_int64),
+                ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
+class MatchingStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("prepared_now", C.c_int32), ("matched_edges", C.c_int64), ("matched_vertices", C.c_int64),
+                ("undirected_edges", C.c_int64), ("live_total", C.c_int64), ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -177,6 +187,10 @@ _SIGNATURES = {
     "vgl_hip_msf_run": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(MsfStats)],
     "vgl_hip_bicc_prepare": [_p, _p, C.POINTER(_i64)],
     "vgl_hip_bicc_run": [_p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(BiccStats)],
+    "vgl_hip_mis_prepare": [_p, _p],
+    "vgl_hip_mis_run": [_p, _p, _p, C.c_uint32, _p, _p, C.POINTER(MisStats)],
+    "vgl_hip_matching_prepare": [_p, _p, C.POINTER(_i64)],
+    "vgl_hip_matching_run": [_p, _p, _p, C.c_uint32, _p, _p, _p, _p, _p, C.POINTER(MatchingStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
