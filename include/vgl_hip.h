@@ -798,6 +798,98 @@ int vgl_hip_matching_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int64_t *undire
 int vgl_hip_matching_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const uint32_t *d_edge_priority, uint32_t seed, int32_t *d_edge_u, int32_t *d_edge_v,
                          uint8_t *d_in_matching, int32_t *d_mate, int32_t *d_round, vgl_hip_matching_stats *stats);
 
+/* Vertex similarity and link prediction (`sim`): the common neighbours of vertex pairs, and for a query vertex the k most similar vertices of its 2-hop
+ * neighbourhood.  The reference has no such algorithm, so this comment is the contract:
+ *   input     any handle that owns all rows; only the stored outgoing CSR is read.
+ *   graph     the simple undirected graph of triangle counting's contract: u ~ v iff u != v and at least one of (u, v), (v, u) is stored.
+ *   notation  N(u) = the neighbours of u (u is never in N(u)); d(u) = |N(u)|; c(u, v) = |N(u) & N(v)|; work2(u) = the sum of d(v) over v in N(u), the
+ *             number of 2-paths that leave u.
+ * vgl_hip_sim_prepare builds what is missing and nothing else: stage 1 of the handle's cache (the symmetric simple CSR, shared with kcore, ktruss, msf,
+ *   bicc and mis) and work2 (int64, V; one pass, kept on the handle and freed with it).  Every entry below does the same on its first call.
+ * vgl_hip_sim_pairs:  d_u / d_v (int32, n, device): n pairs in the graph's own numbering, in any order, repeated or not; u == v is allowed, c = d(u).
+ *   d_common    int32, n: d_common[i] = c(u_i, v_i);
+ *   d_weighted  float64, n: the sum of d_weight[w] over w in N(u_i) & N(v_i); needs d_weight (float64, V, device: finite values >= 0);
+ *   d_degree    int32, V, optional: d(v), a copy of the cache's degrees (the rule of vgl_hip_tri_run).
+ *   At least one of d_common / d_weighted must be given.  Jaccard c / (d(u) + d(v) - c), overlap c / min(d(u), d(v)), Sorensen 2 c / (d(u) + d(v)), the
+ *   Adamic-Adar weights 1 / ln d(w), the resource-allocation weights 1 / d(w) and every other normalisation are the caller's business, in float64 (the
+ *   rule of tri's clustering coefficient and msbfs's closeness).
+ *   Method: the pairs are classified by the length of their SHORTER row (<= VGL_SIM_SHORT (32): 8 lanes per pair, <= VGL_SIM_WAVE (1024): a wavefront,
+ *   longer: a workgroup) into one list per class (one counting pass that also validates, one appending pass; at most VGL_SIM_PAIR_CHUNK (2^28) pairs
+ *   per list build); the lanes stride over the shorter row (u's when both are equally long) and binary-search the longer one.  Every pair has one
+ *   owner: no atomic touches an output, and the outputs are written in the pairs' input order.
+ *   Floating point: no floating-point atomics; every d_weighted[i] has one writer; lane l of L (8, 64, 256) adds the weights of its hits among the
+ *   entries l, l + L, l + 2 L, ... of the shorter row in that order, starting from 0; the L partial sums are folded by the xor-shuffle tree (offsets
+ *   L / 2, ..., 1 inside a wavefront; a workgroup adds its four wavefronts' sums in wavefront order).  The shape depends on the pair and the class
+ *   bounds alone: the value is bit-identical from run to run under the same switches.  The library is built with -ffp-contract=off, without fast-math.
+ *   timing slots: sim_work2, sim_classify, sim_publish, sim_pairs_short, sim_pairs_wave, sim_pairs_wg.
+ *   stats, all exact and the same on every run: pairs = n; pairs_short / pairs_wave / pairs_wg; elements_examined = the sum of min(d(u), d(v)) over the
+ *   pairs; common_total = the sum of c; prepared_now = this call built work2;
+ *   algorithmic_bytes = 64 n (per pair: u, v and both degrees read by the counting pass 16, the list entry written and read 8, u, v read again 8, the
+ *   bounds of both rows 32) + 4 elements_examined (the entries of the shorter rows; the searches in the longer rows are left out) + 4 n with d_common
+ *   + 8 n + 8 common_total + 8 V with d_weighted (the sum written, the weights of the hits gathered, the weights validated) + 8 V with d_degree
+ *   (copied): a lower bound.
+ *   Fails, before anything is written: a NULL ctx or graph, a sharded handle, n < 0, a vertex outside [0, V) (found by the counting pass), d_weighted
+ *   without d_weight, a NaN, infinite or negative weight (one pass over V), both outputs NULL.  n == 0 succeeds and writes nothing but d_degree.
+ * vgl_hip_sim_topk:  d_queries (int32, n, device): vertex ids, repeats allowed, each a row of its own; NULL = all V vertices in id order (n must equal V).
+ *   The candidates of a query u are the vertices w != u with c(u, w) >= 1; unless include_neighbours is 1 the members of N(u) are excluded (link
+ *   prediction).  metric, the score of a candidate:
+ *     VGL_HIP_SIM_COMMON   c;   VGL_HIP_SIM_JACCARD  c / (d(u) + d(w) - c);   VGL_HIP_SIM_OVERLAP  c / min(d(u), d(w)).
+ *   Sorensen 2 c / (d(u) + d(w)) = 2 J / (1 + J) is monotone in the Jaccard score J and so ranks exactly as Jaccard: it has no code of its own.
+ *   Scores are compared AS FRACTIONS in int64: a beats b iff num_a den_b > num_b den_a (no overflow: num, den < 2^31).  Equal scores go to the smaller
+ *   d_label[w] (int32, V, device, distinct; NULL = the vertex id itself; a caller that renumbered the graph passes the original ids, so the answer does
+ *   not depend on the numbering).  The order is strict and total: the output is unique.
+ *   d_ids / d_common  int32, n x k, row-major, indexed with int64: row i holds the best min(k, candidates) candidates of query i, best first, in the
+ *   graph's own numbering, and their c; the remaining slots hold -1 and 0.  d_common may be NULL.  1 <= k <= VGL_HIP_SIM_MAX_K.
+ *   Method: one workgroup per query, classified by work2(u), the upper bound of its distinct candidates: <= VGL_SIM_TABLE_SMALL (1024) an LDS
+ *   open-addressing table of 2048 (id, count) slots; <= VGL_SIM_TABLE (8192) one of 16384 slots (128 KiB: one workgroup per CU, which is why there are
+ *   two table classes); beyond, a dense int32 counter array of V entries and a touched list of V entries in a scratch slot.  A scratch slot belongs to
+ *   one resident workgroup; there are min(VGL_SIM_SCRATCH_MB (4096) MiB / 8 V bytes, global rows, 1024) of them, at least 1.  The row is expanded by
+ *   walking N(v) for every v in N(u) and counting w; a counter whose atomic add returns 0 appends w to the touched list, which is what gets scored
+ *   and what clears the counters for the slot's next row.  u and (by default) N(u) are struck out after the count.  Selection, the same in all
+ *   classes: k rounds of a workgroup arg-max over the candidates that come strictly after the previous pick in the order above: stateless and exact,
+ *   k x candidates comparisons.
+ *   timing slots: sim_work2, sim_classify, sim_publish, sim_topk_small, sim_topk_table, sim_topk_global.
+ *   stats, all exact and the same on every run: queries = n; rows_small / rows_table / rows_global; two_paths_walked = the sum of work2 over the
+ *   queries; candidates_total = the distinct candidates summed over the queries, after the exclusion; filled = the output slots that hold a vertex;
+ *   scratch_slots (0 when no row is global); prepared_now = this call built work2;
+ *   algorithmic_bytes = 36 n (per query: its id and work2 read by the counting pass 12, the list entry written and read 8, its row bounds 16)
+ *   + 4 two_paths_walked (the entries of the neighbours' rows) + 4 n k (d_ids) + 4 n k with d_common; the query's own row, the neighbours' row bounds,
+ *   the counters, the touched lists and the k selection rounds are left out: a lower bound.
+ *   Fails, before anything is written: a NULL ctx or graph, a sharded handle, k out of range, an unknown metric, a query outside [0, V), n < 0,
+ *   d_queries == NULL with n != V, d_ids == NULL.  n == 0 succeeds and writes nothing.
+ * No output depends on any VGL_SIM_* switch except the last bits of d_weighted, whose summation shape follows the class bounds. */
+#define VGL_HIP_SIM_COMMON 0
+#define VGL_HIP_SIM_JACCARD 1
+#define VGL_HIP_SIM_OVERLAP 2
+#define VGL_HIP_SIM_MAX_K 64
+typedef struct {
+    int64_t pairs;
+    int64_t pairs_short;        /* pairs per class of the shorter row */
+    int64_t pairs_wave;
+    int64_t pairs_wg;
+    int64_t elements_examined;  /* sum of min(d(u), d(v)) */
+    int64_t common_total;       /* sum of c */
+    int64_t algorithmic_bytes;
+    int32_t prepared_now;       /* this call built work2 */
+} vgl_hip_sim_pairs_stats;
+typedef struct {
+    int64_t queries;
+    int64_t rows_small;         /* queries per class of work2 */
+    int64_t rows_table;
+    int64_t rows_global;
+    int64_t two_paths_walked;   /* sum of work2 over the queries */
+    int64_t candidates_total;   /* distinct candidates after the exclusion */
+    int64_t filled;             /* output slots that hold a vertex */
+    int64_t scratch_slots;      /* resident workgroups of the global class */
+    int64_t algorithmic_bytes;
+    int32_t prepared_now;       /* this call built work2 */
+} vgl_hip_sim_topk_stats;
+int vgl_hip_sim_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g);
+int vgl_hip_sim_pairs(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_u, const int32_t *d_v, int64_t n, const double *d_weight, int32_t *d_common,
+                      double *d_weighted, int32_t *d_degree, vgl_hip_sim_pairs_stats *stats);
+int vgl_hip_sim_topk(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_queries, int32_t n, int metric, int32_t k, int include_neighbours,
+                     const int32_t *d_label, int32_t *d_ids, int32_t *d_common, vgl_hip_sim_topk_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

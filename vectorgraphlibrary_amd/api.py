@@ -280,6 +280,11 @@ class Graph:
         _l.check(self.ctx.L.vgl_hip_matching_prepare(self.ctx.h, self.h, C.byref(n)))
         return n.value
 
+    def prepare_similarity(self):
+        """the symmetric simple CSR (shared with core_numbers()) and the 2-path counts of common_neighbors() / similarity() / link_prediction() now,
+        outside any timing (vgl_hip_sim_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_sim_prepare(self.ctx.h, self.h))
+
     def prepare_blocked_bfs(self):
         """one-time layout for the blocked top-down BFS levels (vgl_hip_bfs_prepare_blocked); bfs() results do not change"""
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
@@ -933,6 +938,154 @@ def maximal_matching(graph, edge_priority=None, seed=0, raw=False):
 def vertex_cover(graph, edge_priority=None, seed=0, raw=False):
     """a vertex cover of that graph of at most twice the minimum size: the matched vertices (mate >= 0) of maximal_matching(); a bool tensor [V]"""
     return maximal_matching(graph, edge_priority=edge_priority, seed=seed, raw=raw)[1]["mate"] >= 0
+
+
+SIM_COMMON, SIM_JACCARD, SIM_OVERLAP, SIM_MAX_K = 0, 1, 2, 64
+_SIM_CODES = {"common": SIM_COMMON, "jaccard": SIM_JACCARD, "overlap": SIM_OVERLAP, "sorensen": SIM_JACCARD}      # Sorensen ranks exactly as Jaccard
+
+
+def _pair_ids(graph, pairs, raw, who):
+    """pairs ([n, 2]: tensor, array or sequence; ORIGINAL ids unless raw) -> (u, v), int32 device tensors in the graph's own numbering"""
+    p = torch.as_tensor(pairs).to(graph.ctx.device).to(torch.int64).reshape(-1, 2)
+    if p.numel():
+        lo, hi = int(p.min()), int(p.max())
+        if lo < -(1 << 31) or hi >= (1 << 31) or (not raw and graph.fwd is not None and (lo < 0 or hi >= graph.V)):
+            raise _l.VglHipError(who + ": a vertex of a pair is out of range")
+        if not raw and graph.fwd is not None:
+            p = graph.fwd[p]
+    return p[:, 0].to(torch.int32).contiguous(), p[:, 1].to(torch.int32).contiguous()
+
+
+def _sim_pairs(graph, u, v, weight=None, common=True, degree=False):
+    """one vgl_hip_sim_pairs over pairs in the graph's own numbering; returns (common or None, weighted or None, degree or None, stats dict)"""
+    ctx = graph.ctx
+    n = int(u.numel())
+    c = ctx.empty(max(n, 1), torch.int32) if common else None        # (never a NULL pointer: no pairs is no refusal)
+    w = ctx.empty(max(n, 1), torch.float64) if weight is not None else None
+    deg = ctx.empty(graph.V, torch.int32) if degree else None
+    st = _l.SimPairsStats()
+    _l.check(ctx.L.vgl_hip_sim_pairs(ctx.h, graph.h, _ptr(u), _ptr(v), n, _ptr(weight), _ptr(c), _ptr(w), _ptr(deg), C.byref(st)))
+    return c[:n] if common else None, w[:n] if weight is not None else None, deg, _stats(st)
+
+
+def _sim_degree(graph):
+    """d(v) in the graph's own numbering: a vgl_hip_sim_pairs call without pairs writes nothing else"""
+    none = graph.ctx.empty(0, torch.int32)
+    return _sim_pairs(graph, none, none, degree=True)[2]
+
+
+def _sim_score(metric, c, du, dv):
+    """the float64 score of `metric` from the common neighbours and the two degrees; 0 where the denominator is 0"""
+    c, du, dv = c.to(torch.float64), du.to(torch.float64), dv.to(torch.float64)
+    if metric == "common":
+        return c
+    if metric == "jaccard":
+        num, den = c, du + dv - c
+    elif metric == "overlap":
+        num, den = c, torch.minimum(du, dv)
+    elif metric == "sorensen":
+        num, den = 2.0 * c, du + dv
+    else:
+        raise _l.VglHipError("similarity: unknown metric %r" % (metric,))
+    return torch.where(den > 0, num / torch.clamp(den, min=1.0), torch.zeros_like(den))
+
+
+def common_neighbors(graph, pairs, raw=False):
+    """c(u, v) = |N(u) & N(v)| in the simple undirected graph underlying the stored outgoing CSR (the contract of vgl_hip_sim_pairs in
+    include/vgl_hip.h) for every row of pairs ([n, 2], ORIGINAL vertex ids unless raw=True; any order, repeats and u == v allowed): int32 [n]"""
+    u, v = _pair_ids(graph, pairs, raw, "common_neighbors")
+    return _sim_pairs(graph, u, v)[0]
+
+
+def similarity(graph, pairs, metric="jaccard", raw=False):
+    """the similarity of every pair: "jaccard" c / (d(u) + d(v) - c), "overlap" c / min(d(u), d(v)), "sorensen" 2 c / (d(u) + d(v)), float64 [n], built
+    with torch from the library's common-neighbour counts and degrees, 0 where the denominator is 0.  Returns (scores, stats dict); stats["common"]
+    is the int32 [n] count per pair, stats["degree"] the int32 [V] degrees (ORIGINAL vertex order unless raw=True)."""
+    if metric not in ("jaccard", "overlap", "sorensen"):
+        raise _l.VglHipError("similarity: unknown metric %r" % (metric,))
+    u, v = _pair_ids(graph, pairs, raw, "similarity")
+    c, _, deg, stats = _sim_pairs(graph, u, v, degree=True)
+    stats["common"] = c
+    stats["degree"] = deg if raw else graph.to_original(deg)
+    return _sim_score(metric, c, deg[u.long()], deg[v.long()]), stats
+
+
+def _weighted_common(graph, pairs, raw, who, weight_of_degree):
+    u, v = _pair_ids(graph, pairs, raw, who)
+    deg = _sim_degree(graph)
+    c, w, _, stats = _sim_pairs(graph, u, v, weight=weight_of_degree(deg.to(torch.float64)).contiguous())
+    stats["common"] = c
+    stats["degree"] = deg if raw else graph.to_original(deg)
+    return w, stats
+
+
+def adamic_adar(graph, pairs, raw=False):
+    """the Adamic-Adar index of every pair: the sum over the common neighbours w of 1 / ln d(w) (a vertex with d(w) < 2 weighs 0; a common neighbour
+    has d >= 2 unless u == v), float64 [n].  The weights are built here in float64 from the library's degrees; the sum is the library's
+    (vgl_hip_sim_pairs, d_weighted: one writer per pair, a fixed summation shape).  Returns (scores, stats dict) as similarity() does."""
+    return _weighted_common(graph, pairs, raw, "adamic_adar",
+                            lambda d: torch.where(d >= 2, 1.0 / torch.log(torch.clamp(d, min=2.0)), torch.zeros_like(d)))
+
+
+def resource_allocation(graph, pairs, raw=False):
+    """the resource-allocation index of every pair: the sum over the common neighbours w of 1 / d(w) (0 where d(w) < 1), float64 [n]; see adamic_adar()"""
+    return _weighted_common(graph, pairs, raw, "resource_allocation",
+                            lambda d: torch.where(d >= 1, 1.0 / torch.clamp(d, min=1.0), torch.zeros_like(d)))
+
+
+def edge_similarity(graph, metric="jaccard", raw=False):
+    """the similarity of the two ends of all E' undirected edges, in the library's edge numbering (taken from truss_numbers(), whose peel stops at
+    once).  metric: "common", "jaccard", "overlap" or "sorensen".  Returns (scores float64 [E'], stats dict); stats["edges"] is the int32 [E', 2]
+    tensor of the endpoints lo < hi and stats["common"] the int32 [E'] counts (the triangle support of the edge), ordered like truss_numbers():
+    ORIGINAL ids ascending by (lo, hi) unless raw=True."""
+    edges = truss_numbers(graph, k_limit=2, raw=True)[1]["edges"]
+    eu, ev = edges[:, 0].contiguous(), edges[:, 1].contiguous()
+    c, _, deg, stats = _sim_pairs(graph, eu, ev, degree=True)
+    score = _sim_score(metric, c, deg[eu.long()], deg[ev.long()])
+    if not raw and graph.bwd is not None and eu.numel():
+        a, b = graph.bwd[eu.long()], graph.bwd[ev.long()]
+        eu, ev = torch.minimum(a, b), torch.maximum(a, b)
+        order = torch.argsort(eu.long() * graph.V + ev.long())
+        eu, ev, c, score = eu[order], ev[order], c[order], score[order]
+    stats["edges"] = torch.stack([eu, ev], dim=1)
+    stats["common"] = c
+    return score, stats
+
+
+def link_prediction(graph, k=10, metric="jaccard", vertices=None, include_neighbors=False, raw=False):
+    """for every query vertex the k most similar vertices of its 2-hop neighbourhood (the contract of vgl_hip_sim_topk in include/vgl_hip.h): the
+    candidates are the w != u with a common neighbour, without N(u) unless include_neighbors; metric "common", "jaccard", "overlap" or "sorensen"
+    (which ranks as Jaccard); the scores are compared as exact fractions and equal scores go to the smaller ORIGINAL id (raw=True: the smaller id of
+    the graph's own numbering), so the answer does not depend on renumber=.  vertices: None = every vertex in id order, else ORIGINAL ids (raw=True:
+    the graph's own), repeats allowed.  Returns (ids int32 [n, k] best first, padded with -1; common int32 [n, k], padded with 0; score float64
+    [n, k], 0 in the padding; stats dict)."""
+    ctx = graph.ctx
+    if metric not in _SIM_CODES:
+        raise _l.VglHipError("link_prediction: unknown metric %r" % (metric,))
+    to_orig = not raw and graph.bwd is not None
+    if vertices is None:
+        q = graph.fwd.contiguous() if to_orig else None              # row i is ORIGINAL vertex i
+        n = graph.V
+    else:
+        ids = _source_ids(graph, vertices, raw, "link_prediction")
+        n = len(ids)
+        q = torch.tensor(ids, dtype=torch.int32, device=ctx.device) if n else ctx.empty(1, torch.int32)
+    kk = int(k)
+    cells = max(n * max(kk, 1), 1)
+    ids_out, common = ctx.empty(cells, torch.int32), ctx.empty(cells, torch.int32)
+    st = _l.SimTopkStats()
+    _l.check(ctx.L.vgl_hip_sim_topk(ctx.h, graph.h, _ptr(q), n, _SIM_CODES[metric], kk, int(bool(include_neighbors)),
+                                    _ptr(graph.bwd.contiguous()) if to_orig else None, _ptr(ids_out), _ptr(common), C.byref(st)))
+    ids_out, common = ids_out[:n * kk].reshape(n, kk), common[:n * kk].reshape(n, kk)
+    deg = _sim_degree(graph)
+    own = (graph.fwd if to_orig else torch.arange(graph.V, dtype=torch.int32, device=ctx.device)) if q is None else q[:n]
+    held = ids_out >= 0
+    du = deg[own.long()][:, None].expand(n, kk)
+    dw = deg[ids_out.clamp(min=0).long()]
+    score = torch.where(held, _sim_score(metric, common, du, dw), torch.zeros((n, kk), dtype=torch.float64, device=ctx.device))
+    if to_orig:
+        ids_out = torch.where(held, graph.bwd[ids_out.clamp(min=0).long()], ids_out)
+    return ids_out, common, score, _stats(st)
 
 
 def count_not_equal(ctx, a, b):

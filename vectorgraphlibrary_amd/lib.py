@@ -94,6 +94,17 @@ class MatchingStats(C.Structure):
                 ("undirected_edges", C.c_int64), ("live_total", C.c_int64), ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class SimPairsStats(C.Structure):
+    _fields_ = [("pairs", C.c_int64), ("pairs_short", C.c_int64), ("pairs_wave", C.c_int64), ("pairs_wg", C.c_int64),
+                ("elements_examined", C.c_int64), ("common_total", C.c_int64), ("algorithmic_bytes", C.c_int64), ("prepared_now", C.c_int32)]
+
+
+class SimTopkStats(C.Structure):
+    _fields_ = [("queries", C.c_int64), ("rows_small", C.c_int64), ("rows_table", C.c_int64), ("rows_global", C.c_int64),
+                ("two_paths_walked", C.c_int64), ("candidates_total", C.c_int64), ("filled", C.c_int64), ("scratch_slots", C.c_int64),
+                ("algorithmic_bytes", C.c_int64), ("prepared_now", C.c_int32)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -191,6 +202,9 @@ _SIGNATURES = {
     "vgl_hip_mis_run": [_p, _p, _p, C.c_uint32, _p, _p, C.POINTER(MisStats)],
     "vgl_hip_matching_prepare": [_p, _p, C.POINTER(_i64)],
     "vgl_hip_matching_run": [_p, _p, _p, C.c_uint32, _p, _p, _p, _p, _p, C.POINTER(MatchingStats)],
+    "vgl_hip_sim_prepare": [_p, _p],
+    "vgl_hip_sim_pairs": [_p, _p, _p, _p, _i64, _p, _p, _p, _p, C.POINTER(SimPairsStats)],
+    "vgl_hip_sim_topk": [_p, _p, _p, _i32, _int, _i32, _int, _p, _p, _p, C.POINTER(SimTopkStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
