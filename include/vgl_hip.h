@@ -890,6 +890,120 @@ int vgl_hip_sim_pairs(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_u, co
 int vgl_hip_sim_topk(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_queries, int32_t n, int metric, int32_t k, int include_neighbours,
                      const int32_t *d_label, int32_t *d_ids, int32_t *d_common, vgl_hip_sim_topk_stats *stats);
 
+/* Subgraph extraction (`subgraph`), bounded multi-seed reach (`khop`) and fixed-fanout neighbour sampling (`sample`): the part of a graph that a mask,
+ * a neighbourhood or a sample selects, handed back as CSR.  The reference has nothing of the kind, so this comment is the contract:
+ *   input     any handle that owns all rows.  Every id is in the graph's own numbering.  Direction 0 is the stored outgoing CSR, direction 1 the stored
+ *             incoming CSR; direction 1 on a handle without an incoming CSR is an error.  The stored entries are taken as they are: self-loops and
+ *             repeated entries are entries like any other (this is NOT the simple graph of triangle counting's contract).
+ * The stable row filter, vgl_hip_subgraph_plan_create / _info / _vertex_maps / _fill / _destroy:
+ *   d_keep_vertex  uint8, V, device: nonzero = keep the vertex; NULL = keep all.
+ *   d_keep_entry   uint8, one per stored OUTGOING entry in CSR order (as sssp takes weights), device: nonzero = keep; NULL = keep all.  Borrowed until
+ *                  the last fill of the plan.  At least one of the two masks must be given.
+ *   new_id[v] (int32, V) = the number of kept vertices below v for a kept v, -1 for a dropped one; old_id (int32, V') is its inverse.  The relabelling is
+ *   MONOTONE.  In direction d, row new_id[v] of the result holds exactly those entries of row v whose far end is kept and, in direction 0, whose entry
+ *   flag is nonzero, relabelled, IN THEIR STORED ORDER.  d_origin (int64, optional) receives the position in the parent's adjacency array of that
+ *   direction of every surviving entry: weights follow with vgl_hip_gather_u32.  With d_keep_entry only direction 0 can be filled (the flags are per
+ *   outgoing entry); the caller builds the incoming CSR of such a result by the transposition Graph.from_coo uses.  With a vertex mask alone both
+ *   directions are filled by the same kernels.  Because the relabelling is monotone and both filters are stable, the result is BIT-IDENTICAL, rowptr
+ *   and adj of both directions, to what the stable COO -> CSR build (vgl_hip_coo_to_csr, then the same build over the transposed list taken in
+ *   outgoing CSR order) makes of the filtered, relabelled edge list taken in the parent's outgoing CSR order -- provided the parent's incoming CSR was
+ *   built that way too.
+ *   Method: the plan validates, scans the vertex mask (tile sums, their scan, an apply pass), counts and lists the kept rows per class of their FULL
+ *   length and per direction (<= VGL_SUB_SHORT (32): 8 lanes per row, <= VGL_SUB_WAVE (1024): a wavefront, longer: a workgroup), counts the survivors
+ *   of every kept row with one kernel per class, and scans the counts into the new int64 rowptr.  The host reads the pinned counter mirror twice (the
+ *   list sizes; V', E'out, E'in) and the plan synchronises the stream once, at its end.  _info hands V', E'out, E'in (-1 when direction 1 cannot be
+ *   filled) and the stats to the host; _vertex_maps copies new_id / old_id (either may be NULL); _fill(direction) copies the plan's rowptr into d_rowptr
+ *   (int64, V' + 1) and writes d_adj (int32, E') and d_origin (int64, E', optional) -- buffers of the caller, which a handle made of them borrows as
+ *   vgl_hip_graph_create always does -- and is left enqueued on the context's stream.  The fill is an ORDERED compaction: every row has one owner, a
+ *   survivor's position is the row's new start + the survivors of the chunks before (a running base) + the survivors before it in its chunk (ballot
+ *   and popcount of the lanes below within the 8-lane group or the wavefront; across the four wavefronts of a workgroup an LDS scan).  No atomic
+ *   touches an output.  V' == 0 is a valid plan; its fill writes nothing.
+ *   timing slots: sub_scan (scans, classification, lists), sub_count_short / _wave / _wg, sub_publish, sub_fill_short / _wave / _wg.
+ *   stats, all exact and the same on every run: vertices_kept = V'; rows_{short,wave,wg}_{out,in} = kept rows per class of their full length (the only
+ *   stats that follow VGL_SUB_SHORT / VGL_SUB_WAVE); entries_read_{out,in} = the sum of the full lengths of the kept rows; entries_kept_{out,in} = E' of
+ *   the direction; the _in fields are 0 when direction 1 is not planned;
+ *   algorithmic_bytes = V with d_keep_vertex (the mask read) + 4 V (new_id written) + 4 V' (old_id written) + for every planned direction
+ *   56 V' (counting and filling each: list entry 4, row bounds 16, count written or new row start read 8) + 32 (V' + 1) (the counts scanned: read and
+ *   written; the rowptr copied out: read and written) + 16 read (counting and filling each: the adjacency entry and the new id of its far end)
+ *   + 2 read with d_keep_entry (the flag, twice) + 4 kept (the new adjacency written); the classification pass over V and d_origin are left out: a lower
+ *   bound of a plan followed by one fill per planned direction.
+ *   Fails, before anything is written: a NULL ctx, graph or out pointer, a sharded handle, both masks NULL; _fill: a direction other than 0 / 1,
+ *   direction 1 on a plan with an entry mask or without an incoming CSR, a NULL d_rowptr (or d_adj while E' > 0) unless V' == 0.
+ * vgl_hip_khop_run:  d_seeds (int32, n, device; repeats allowed; n == 0 succeeds with every d_hop = -1), hops >= 0, direction, symmetric (nonzero: follow
+ *   the stored entries of BOTH directions; needs the incoming CSR, direction is then ignored).
+ *   d_hop[v] (int32, V, device) = the smallest number of steps from any seed to v if that is <= hops, else -1; hops == 0 marks the seeds alone.  Direction 1
+ *   steps along incoming entries (d_hop[v] = the steps from v to the nearest seed along stored edges).  An integer, unique.
+ *   Method: the seeds are validated by one pass, d_hop is set to -1 and the seeds to 0, then level-synchronous top-down steps
+ *   (vgl_hip_bfs_step_top_down and its frontier compaction) on the handle, on the handle with the two directions swapped (built on first use and kept
+ *   on the handle, as scc does) or on both, until `hops` levels were expanded or a level is empty.
+ *   timing slots: khop_init, khop_publish, khop_count and those of the top-down step.
+ *   stats, all exact: reached = the entries of d_hop that are >= 0; levels_run = the non-empty levels that were expanded (at most hops);
+ *   frontier_total = the sum of their sizes; edges_examined = the sum of the full row lengths of their vertices in every followed direction.
+ *   Fails, before anything is written: a NULL ctx, graph or d_hop, a sharded handle, n < 0, hops < 0, a seed outside [0, V), a direction other than
+ *   0 / 1, direction 1 or symmetric without the incoming CSR.
+ * vgl_hip_sample_neighbors:  d_seeds (int32, n, device; repeats allowed, each a row of its own), fanout >= 1, direction, seed (uint32).
+ *   Row i of the output holds the min(fanout, degree) entries of the row of d_seeds[i] with the smallest key(p mod 2^32, seed), p = the entry's
+ *   position in the adjacency array of that direction; key is mis's key(i, seed) above.  fmix32 is a bijection, so the keys of an array of fewer than
+ *   2^32 entries never tie; a longer array is refused.  The chosen entries are written IN ASCENDING POSITION.  The answer is unique and depends on
+ *   no switch; it DOES depend on the graph's numbering (the positions are those of this handle's arrays).  Sampling is without replacement over the
+ *   stored entries: a repeated entry can be drawn once per copy.
+ *   d_rowptr (int64, n + 1; d_rowptr[n] = the total), d_adj (int32, capacity n * fanout, indexed with int64), d_origin (int64, same capacity, optional:
+ *   the positions p).
+ *   Method: the key is a function of the position alone, so the selection reads no memory; only the emit gathers adj[p].  One pass validates the seeds
+ *   and writes min(fanout, degree) per seed, a scan makes d_rowptr, the seeds are listed per class of their degree (<= VGL_SAMPLE_SHORT (32): 8 lanes,
+ *   <= VGL_SAMPLE_WAVE (1024): a wavefront, longer: a workgroup).  A row of at most fanout entries is copied.  Short and wave rows rank-count: an entry
+ *   is taken when fewer than fanout entries of its row have a smaller key (degree^2 / lanes key evaluations per lane at most).  Workgroup rows find the
+ *   fanout-th smallest key by a 4 x 8-bit radix select over recomputed keys (LDS histograms, 5 passes over the positions in all).  The emit is the
+ *   ordered compaction of the filter above.
+ *   timing slots: sample_count (validation, scan, lists), sample_publish, sample_short, sample_wave, sample_wg.
+ *   stats, all exact and the same on every run: seeds = n; rows_short / rows_wave / rows_wg (the only stats that follow the two switches);
+ *   entries_examined = the sum of the seeds' degrees; sampled_total = d_rowptr[n];
+ *   algorithmic_bytes = 60 n (per seed: its id and row bounds read and the count written 28, the list entry, the id, the row bounds and the new row
+ *   start read 32) + 16 (n + 1) (the counts scanned) + 8 sampled_total (adj[p] read, d_adj written); the list build and d_origin are left out: a lower bound.
+ *   Fails, before anything is written: a NULL ctx, graph, d_rowptr (or d_adj while n > 0), a sharded handle, n < 0 or n >= 2^31, fanout < 1, a seed
+ *   outside [0, V), a direction other than 0 / 1, direction 1 without the incoming CSR, an adjacency array of 2^32 entries or more.
+ * No output depends on VGL_SUB_* or VGL_SAMPLE_*. */
+typedef struct vgl_hip_subgraph_plan vgl_hip_subgraph_plan;
+typedef struct {
+    int64_t vertices_kept;      /* V' */
+    int64_t rows_short_out;     /* kept rows per class of their full length, outgoing */
+    int64_t rows_wave_out;
+    int64_t rows_wg_out;
+    int64_t rows_short_in;      /* ... incoming (0 when direction 1 is not planned) */
+    int64_t rows_wave_in;
+    int64_t rows_wg_in;
+    int64_t entries_read_out;   /* sum of the full lengths of the kept rows */
+    int64_t entries_read_in;
+    int64_t entries_kept_out;   /* E' of the direction */
+    int64_t entries_kept_in;
+    int64_t algorithmic_bytes;
+} vgl_hip_subgraph_stats;
+int vgl_hip_subgraph_plan_create(vgl_hip_ctx *ctx, vgl_hip_graph *g, const uint8_t *d_keep_vertex, const uint8_t *d_keep_entry,
+                                 vgl_hip_subgraph_plan **out);
+int vgl_hip_subgraph_plan_info(vgl_hip_subgraph_plan *plan, int32_t *vertices, int64_t *out_entries, int64_t *in_entries, vgl_hip_subgraph_stats *stats);
+int vgl_hip_subgraph_plan_vertex_maps(vgl_hip_ctx *ctx, vgl_hip_subgraph_plan *plan, int32_t *d_new_id, int32_t *d_old_id);
+int vgl_hip_subgraph_plan_fill(vgl_hip_ctx *ctx, vgl_hip_subgraph_plan *plan, int direction, int64_t *d_rowptr, int32_t *d_adj, int64_t *d_origin);
+int vgl_hip_subgraph_plan_destroy(vgl_hip_ctx *ctx, vgl_hip_subgraph_plan *plan);
+typedef struct {
+    int64_t reached;            /* entries of d_hop that are >= 0 */
+    int64_t frontier_total;     /* sum of the sizes of the expanded levels */
+    int64_t edges_examined;     /* sum of their full row lengths, every followed direction */
+    int32_t levels_run;         /* non-empty levels expanded */
+} vgl_hip_khop_stats;
+int vgl_hip_khop_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_seeds, int64_t n, int32_t hops, int direction, int symmetric, int32_t *d_hop,
+                     vgl_hip_khop_stats *stats);
+typedef struct {
+    int64_t seeds;
+    int64_t rows_short;         /* seeds per class of their degree */
+    int64_t rows_wave;
+    int64_t rows_wg;
+    int64_t entries_examined;   /* sum of the seeds' degrees */
+    int64_t sampled_total;      /* d_rowptr[n] */
+    int64_t algorithmic_bytes;
+} vgl_hip_sample_stats;
+int vgl_hip_sample_neighbors(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_seeds, int64_t n, int32_t fanout, int direction, uint32_t seed,
+                             int64_t *d_rowptr, int32_t *d_adj, int64_t *d_origin, vgl_hip_sample_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -1088,6 +1088,171 @@ def link_prediction(graph, k=10, metric="jaccard", vertices=None, include_neighb
     return ids_out, common, score, _stats(st)
 
 
+def _seed_ids(graph, seeds, raw, who):
+    """seeds (tensor, array or sequence; ORIGINAL ids unless raw; repeats allowed) -> int32 device tensor in the graph's own numbering (never an empty
+    allocation) and their number"""
+    s = torch.as_tensor(seeds).to(graph.ctx.device).to(torch.int64).flatten()
+    n = int(s.numel())
+    if n:
+        lo, hi = int(s.min()), int(s.max())
+        if lo < -(1 << 31) or hi >= (1 << 31) or (not raw and graph.fwd is not None and (lo < 0 or hi >= graph.V)):
+            raise _l.VglHipError(who + ": a seed is out of range")
+        if not raw and graph.fwd is not None:
+            s = graph.fwd[s]
+    return (s.to(torch.int32).contiguous() if n else graph.ctx.empty(1, torch.int32)), n
+
+
+def _vertex_keep(graph, vertices_or_mask, raw, who):
+    """a bool tensor of V flags or a list of vertex ids (ORIGINAL unless raw) -> uint8 [V] flags in the graph's own numbering"""
+    ctx, V = graph.ctx, graph.V
+    t = torch.as_tensor(vertices_or_mask).to(ctx.device)
+    to_own = not raw and graph.fwd is not None
+    if t.dtype == torch.bool:
+        if t.numel() != V:
+            raise _l.VglHipError("%s: a mask of %d flags for %d vertices" % (who, t.numel(), V))
+        keep = t.flatten().to(torch.uint8)
+        return (keep[graph.bwd.long()] if to_own else keep).contiguous()
+    ids = t.to(torch.int64).flatten()
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= V):
+        raise _l.VglHipError(who + ": a vertex is out of range")
+    keep = torch.zeros(V, dtype=torch.uint8, device=ctx.device)
+    keep[graph.fwd[ids].long() if to_own else ids] = 1
+    return keep
+
+
+def _row_filter(graph, keep_vertex, keep_entry, with_incoming, origin, raw, who):
+    """one plan and its fills (vgl_hip_subgraph_plan_* in include/vgl_hip.h) over masks in the graph's own numbering; returns the new Graph"""
+    ctx = graph.ctx
+    want_in = (graph.in_rowptr is not None) if with_incoming is None else bool(with_incoming)
+    if want_in and graph.in_rowptr is None and keep_entry is None:
+        raise _l.VglHipError(who + ": with_incoming needs the incoming CSR of the parent")
+    plan = C.c_void_p()
+    _l.check(ctx.L.vgl_hip_subgraph_plan_create(ctx.h, graph.h, _ptr(keep_vertex), _ptr(keep_entry), C.byref(plan)))
+    try:
+        vk, eo, ei, st = C.c_int32(), C.c_int64(), C.c_int64(), _l.SubgraphStats()
+        _l.check(ctx.L.vgl_hip_subgraph_plan_info(plan, C.byref(vk), C.byref(eo), C.byref(ei), C.byref(st)))
+        vk, eo, ei = vk.value, eo.value, ei.value
+        if vk == 0:
+            raise _l.VglHipError(who + ": no vertex is kept (a graph handle holds at least one vertex)")
+        old = ctx.empty(vk, torch.int32)
+        _l.check(ctx.L.vgl_hip_subgraph_plan_vertex_maps(ctx.h, plan, None, _ptr(old)))
+        rowptr, adj = ctx.empty(vk + 1, torch.int64), ctx.empty(max(eo, 1), torch.int32)
+        org = ctx.empty(max(eo, 1), torch.int64) if origin else None
+        _l.check(ctx.L.vgl_hip_subgraph_plan_fill(ctx.h, plan, 0, _ptr(rowptr), _ptr(adj), _ptr(org)))
+        adj = adj[:eo]
+        in_rowptr = in_adj = None
+        if want_in and keep_entry is None:
+            in_rowptr, in_adj = ctx.empty(vk + 1, torch.int64), ctx.empty(max(ei, 1), torch.int32)
+            _l.check(ctx.L.vgl_hip_subgraph_plan_fill(ctx.h, plan, 1, _ptr(in_rowptr), _ptr(in_adj), None))
+            in_adj = in_adj[:ei]
+        elif want_in:                                                 # an entry mask: the transposition of Graph.from_coo
+            csr_src = torch.repeat_interleave(torch.arange(vk, device=ctx.device, dtype=torch.int32), rowptr[1:] - rowptr[:-1])
+            in_rowptr, in_adj, _ = ctx.coo_to_csr(vk, adj, csr_src)
+    finally:
+        ctx.L.vgl_hip_subgraph_plan_destroy(ctx.h, plan)
+    sub = Graph(ctx, vk, rowptr, adj, in_rowptr, in_adj)
+    sub.parent_ids = old if raw or graph.bwd is None else graph.bwd[old.long()]
+    sub.origin = org[:eo] if origin else None
+    sub.stats = _stats(st)
+    return sub
+
+
+def induced_subgraph(graph, vertices_or_mask, with_incoming=None, origin=False, raw=False):
+    """the subgraph induced by a vertex set (the contract of vgl_hip_subgraph_plan_create in include/vgl_hip.h): a bool tensor of V flags or a list of
+    vertex ids, ORIGINAL unless raw=True.  Returns a Graph that owns its tensors; its vertex i is the i-th kept vertex in the PARENT'S OWN numbering,
+    its rows hold the parent's entries between kept vertices in their stored order (self-loops and repeated entries included), bit-identical to
+    Graph.from_coo on the filtered edge list.  sub.parent_ids (int32 [V']) holds the parent's ORIGINAL id of every vertex (its own id under raw=True);
+    sub.origin (int64 [E'], with origin=True) the position of every outgoing entry in the parent's out_adj (weights follow with ctx.gather_u32);
+    sub.stats the plan's stats; sub.fwd / sub.bwd are None.  with_incoming: None = as the parent.  Raises VglHipError when no vertex is kept."""
+    return _row_filter(graph, _vertex_keep(graph, vertices_or_mask, raw, "induced_subgraph"), None, with_incoming, origin, raw, "induced_subgraph")
+
+
+def edge_subgraph(graph, entry_mask, with_incoming=None, origin=False, raw=False):
+    """the subgraph of an entry mask: one flag per stored outgoing entry in CSR order (bool or integer, nonzero = keep), as sssp() takes weights.  All V
+    vertices stay and keep their ids; see induced_subgraph() for what is returned.  The incoming CSR is rebuilt from the result by the transposition
+    of Graph.from_coo (with_incoming: None = as the parent)."""
+    ctx = graph.ctx
+    keep = torch.as_tensor(entry_mask).to(ctx.device).flatten()
+    if keep.numel() != graph.E:
+        raise _l.VglHipError("edge_subgraph: a mask of %d flags for %d entries" % (keep.numel(), graph.E))
+    keep = (keep != 0).to(torch.uint8).contiguous()
+    if graph.E == 0:
+        keep = torch.zeros(1, dtype=torch.uint8, device=ctx.device)   # (never a NULL pointer)
+    return _row_filter(graph, None, keep, with_incoming, origin, raw, "edge_subgraph")
+
+
+def _k_hop_raw(graph, s, n, hops, direction, symmetric):
+    ctx = graph.ctx
+    hop = ctx.empty(graph.V, torch.int32)
+    st = _l.KhopStats()
+    _l.check(ctx.L.vgl_hip_khop_run(ctx.h, graph.h, _ptr(s), n, int(hops), {"out": 0, "in": 1}[direction], int(bool(symmetric)), _ptr(hop), C.byref(st)))
+    return hop, _stats(st)
+
+
+def k_hop(graph, seeds, hops, direction="out", symmetric=False, raw=False, with_stats=False):
+    """bounded multi-seed reach (the contract of vgl_hip_khop_run in include/vgl_hip.h): int32 [V], the smallest number of steps from any seed to the
+    vertex if that is <= hops, else -1.  seeds: ORIGINAL ids unless raw=True, repeats allowed, may be empty; direction "out" follows stored outgoing
+    entries, "in" incoming ones; symmetric=True follows both (needs the incoming CSR).  The array is in ORIGINAL vertex order unless raw=True.
+    with_stats=True returns (hop, stats dict)."""
+    s, n = _seed_ids(graph, seeds, raw, "k_hop")
+    hop, stats = _k_hop_raw(graph, s, n, hops, direction, symmetric)
+    hop = hop if raw else graph.to_original(hop)
+    return (hop, stats) if with_stats else hop
+
+
+def ego_graph(graph, seeds, hops, direction="out", symmetric=False, with_incoming=None, origin=False, raw=False):
+    """the k-hop (ego) network of a seed set: k_hop() followed by induced_subgraph() on the vertices it reaches.  Returns the Graph of
+    induced_subgraph(); sub.hop (int32 [V']) is the hop count of every kept vertex."""
+    s, n = _seed_ids(graph, seeds, raw, "ego_graph")
+    hop, _ = _k_hop_raw(graph, s, n, hops, direction, symmetric)
+    sub = _row_filter(graph, (hop >= 0).to(torch.uint8), None, with_incoming, origin, raw, "ego_graph")
+    own = sub.parent_ids if raw or graph.fwd is None else graph.fwd[sub.parent_ids.long()]
+    sub.hop = hop[own.long()]
+    return sub
+
+
+def _sample_raw(graph, s, n, fanout, seed, direction, origin):
+    ctx = graph.ctx
+    cap = max(n * max(int(fanout), 1), 1)
+    rowptr, adj = ctx.empty(n + 1, torch.int64), ctx.empty(cap, torch.int32)
+    org = ctx.empty(cap, torch.int64) if origin else None
+    st = _l.SampleStats()
+    _l.check(ctx.L.vgl_hip_sample_neighbors(ctx.h, graph.h, _ptr(s), n, int(fanout), {"out": 0, "in": 1}[direction], int(seed) & 0xFFFFFFFF, _ptr(rowptr),
+                                            _ptr(adj), _ptr(org), C.byref(st)))
+    total = int(st.sampled_total)
+    return rowptr, adj[:total], (org[:total] if origin else None), _stats(st)
+
+
+def sample_neighbors(graph, seeds, fanout, seed=0, direction="out", origin=False, raw=False):
+    """fixed-fanout neighbour sampling without replacement (the contract of vgl_hip_sample_neighbors in include/vgl_hip.h): row i holds the
+    min(fanout, degree) entries of the row of seeds[i] with the smallest priority_key(position, seed), in ascending position.  seeds: ORIGINAL ids
+    unless raw=True, repeats allowed (each a row of its own).  Returns (rowptr int64 [n + 1], adj int32 [rowptr[n]][, origin int64], stats dict); adj is
+    in ORIGINAL ids unless raw=True, origin (with origin=True) the positions in the graph's out_adj / in_adj.  The sample is unique for a given graph
+    object but follows ITS numbering: a renumbered graph draws another sample."""
+    s, n = _seed_ids(graph, seeds, raw, "sample_neighbors")
+    rowptr, adj, org, stats = _sample_raw(graph, s, n, fanout, seed, direction, origin)
+    if not raw and graph.bwd is not None:
+        adj = graph.bwd[adj.long()]
+    return (rowptr, adj, org, stats) if origin else (rowptr, adj, stats)
+
+
+def sample_blocks(graph, seeds, fanouts, seed=0, direction="out", raw=False):
+    """layered sampling for mini-batches: hop h samples fanouts[h] neighbours with the seed `seed + h` for every vertex of its frontier; frontier 0 is
+    `seeds` as given, frontier h + 1 the sorted unique union (in the graph's own numbering) of frontier h and its samples.  Returns one dict per hop:
+    "seeds" (int32, the frontier), "rowptr" (int64), "adj" (int32) and "stats"; ids are ORIGINAL unless raw=True."""
+    front, n = _seed_ids(graph, seeds, raw, "sample_blocks")
+    front = front[:n]
+    to_orig = not raw and graph.bwd is not None
+    blocks = []
+    for h, fanout in enumerate(fanouts):
+        n = int(front.numel())
+        rowptr, adj, _, stats = _sample_raw(graph, front if n else graph.ctx.empty(1, torch.int32), n, fanout, int(seed) + h, direction, False)
+        blocks.append({"seeds": graph.bwd[front.long()] if to_orig else front, "rowptr": rowptr, "adj": graph.bwd[adj.long()] if to_orig else adj,
+                       "stats": stats})
+        front = torch.unique(torch.cat([front, adj])).to(torch.int32).contiguous()
+    return blocks
+
+
 def count_not_equal(ctx, a, b):
     r = C.c_int64()
     _l.check(ctx.L.vgl_hip_count_not_equal_u32(ctx.h, a.numel(), _ptr(a), _ptr(b), C.byref(r)))

@@ -1,0 +1,796 @@
+// subgraph.hip -- subgraph extraction (a stable filter of adjacency rows under a vertex mask and / or an entry mask), bounded multi-seed reach (k-hop)
+// and fixed-fanout neighbour sampling without replacement.  The contract is written out in include/vgl_hip.h; DESIGN section 24 has the kernels, their
+// bounds and the bytes models.
+//
+// Filter plan: an exclusive scan of the vertex mask gives new_id (three launches: tile sums, their scan, the apply pass); the kept rows are counted
+// and listed per row class (vgl_rowclass.h: short 8 lanes per row, wave, workgroup) and per direction; one counting kernel per class writes the
+// number of surviving entries of every kept row, and the same scan turns the counts into the new int64 rowptr.  Two reads of the pinned counter
+// mirror (sizes of the lists; V', E'out, E'in) and one stream synchronise at the end.
+//
+// Fill: the counting kernels again, now writing.  The compaction is ORDERED: every row has one owner (an 8-lane group, a wavefront, a workgroup),
+// the position of a survivor is the row's new start + the survivors of the chunks before (a running base in a register) + the survivors before it
+// in its chunk (ballot and popcount of the lanes below; the workgroup adds an LDS scan over its four wavefronts).  No atomic touches an output.
+//
+// k-hop: seeds validated, then marked 0 in a level array of -1; level-synchronous top-down steps (vgl_hip_bfs_step_top_down on the handle, on the
+// cached transposed handle, or on both) until `hops` levels were expanded or a frontier is empty.
+//
+// Sampling: key(p, seed) is a function of the position alone, so selection reads no memory.  Short and wave rows rank-count (an entry is taken when
+// fewer than `fanout` entries of its row have a smaller key); workgroup rows find the fanout-th smallest key by a 4 x 8-bit radix select over
+// recomputed keys (LDS histograms).  The emit is the ordered compaction of the filter.
+#include "vgl_rowclass.h"
+#include <cstring>
+#include <algorithm>
+
+struct vgl_hip_subgraph_plan {
+    vgl_hip_graph *g = nullptr;
+    int32_t V = 0, Vk = 0;
+    bool planned[2] = {false, false};
+    const uint8_t *keep_entry = nullptr;         // borrowed until the fill (direction 0 only)
+    vgl_dev<int32_t> new_id, old_id, lists;      // V; V'; the kept rows (parent ids) per direction and class
+    vgl_dev<int64_t> rowptr[2];                  // V' + 1 each
+    int64_t rows[2][VGL_RC_N] = {{0, 0, 0}, {0, 0, 0}}, off[2][VGL_RC_N] = {{0, 0, 0}, {0, 0, 0}};
+    vgl_hip_subgraph_stats st;
+};
+
+namespace {
+
+constexpr int64_t SUB_MAX_GRID = 2048;           // workgroups of a grid-stride kernel
+enum {
+    SUB_VK = 0,         // kept vertices
+    SUB_ROWS = 1,       // + 3 * direction + class: kept rows per class
+    SUB_READ = 7,       // + direction: full lengths of the kept rows
+    SUB_KEPT = 9,       // + direction: surviving entries
+    SUB_TAIL = 11,      // + 3 * direction + class: rows appended to the class list so far
+    SUB_NCNT = 17
+};
+enum {
+    SMP_TAIL = 0,       // + class: rows appended to the class list so far
+    SMP_ROWS = 3,       // + class: seeds per class
+    SMP_BAD = 6,        // seeds outside [0, V)
+    SMP_EXAM = 7,       // sum of the seeds' degrees
+    SMP_TOTAL = 8,      // sampled entries
+    SMP_NCNT = 9
+};
+enum { KH_BAD = 0, KH_REACHED = 1, KH_NCNT = 2 };
+static_assert(SUB_NCNT <= C_NSLOTS && SMP_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
+
+bool sub_sharded(const vgl_hip_graph *g) { return g->row_begin != 0 || g->row_end != g->V; }
+int sub_open_counters(vgl_hip_ctx *c, vgl_dev<unsigned long long> *cnt, int n)
+{
+    VGL_TRY(cnt->alloc(c->stream, (size_t)n));
+    VGL_HIP_TRY(hipMemsetAsync(cnt->p, 0, sizeof(unsigned long long) * (size_t)n, c->stream));
+    return 0;
+}
+
+// ---- exclusive scan of n values of a source S into S (int64 sums): tile sums, the scan of the tile sums by one workgroup, the apply pass ----
+struct sub_mask_src {           // the vertex mask (nullptr: every vertex is kept) -> new_id
+    const uint8_t *keep; int32_t *new_id;
+    __device__ __forceinline__ int64_t load(int64_t i) const { return keep ? (keep[i] != 0) : 1; }
+    __device__ __forceinline__ void store(int64_t i, int64_t ex, int64_t v) const { new_id[i] = v ? (int32_t)ex : -1; }
+};
+struct sub_i64_src {            // counts -> offsets (in == out is allowed: every element is read and written by the same thread)
+    const int64_t *in; int64_t *out;
+    __device__ __forceinline__ int64_t load(int64_t i) const { return in[i]; }
+    __device__ __forceinline__ void store(int64_t i, int64_t ex, int64_t) const { out[i] = ex; }
+};
+template <class S>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_sums(S s, int64_t n, int64_t tiles, int64_t *bsum)
+{
+    __shared__ int64_t sm[VGL_WAVES];
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {         // (uniform over the workgroup)
+        int64_t sum = 0;
+#pragma unroll
+        for (int j = 0; j < VGL_EPT; j++) {
+            const int64_t i = t * VGL_TILE + j * VGL_BLOCK + threadIdx.x;
+            if (i < n) sum += s.load(i);
+        }
+        sum = vgl_block_reduce_add(sum, sm);
+        if (threadIdx.x == 0) bsum[t] = sum;
+    }
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_top(int64_t tiles, int64_t *bsum, unsigned long long *total)
+{
+    __shared__ int64_t sm[VGL_WAVES];
+    int64_t carry = 0;
+    for (int64_t base = 0; base < tiles; base += VGL_BLOCK) {         // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x;
+        const int64_t v = i < tiles ? bsum[i] : 0;
+        int64_t tot = 0;
+        const int64_t ex = vgl_block_excl_add(v, sm, &tot);
+        if (i < tiles) bsum[i] = carry + ex;
+        carry += tot;
+    }
+    if (threadIdx.x == 0) *total = (unsigned long long)carry;
+}
+template <class S>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_apply(S s, int64_t n, int64_t tiles, const int64_t *bsum)
+{
+    __shared__ int64_t sm[VGL_WAVES];
+    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {         // (uniform over the workgroup)
+        const int64_t i0 = t * VGL_TILE + (int64_t)threadIdx.x * VGL_EPT;
+        int64_t v[VGL_EPT], sum = 0;
+#pragma unroll
+        for (int j = 0; j < VGL_EPT; j++) {
+            v[j] = i0 + j < n ? s.load(i0 + j) : 0;
+            sum += v[j];
+        }
+        int64_t tot = 0;
+        int64_t ex = vgl_block_excl_add(sum, sm, &tot) + bsum[t];
+#pragma unroll
+        for (int j = 0; j < VGL_EPT; j++) {
+            if (i0 + j < n) s.store(i0 + j, ex, v[j]);
+            ex += v[j];
+        }
+    }
+}
+// n >= 1 values; *total receives their sum; bsum is scratch of ceil(n / VGL_TILE) entries
+template <class S>
+int sub_scan(vgl_hip_ctx *c, const char *slot, const S &s, int64_t n, int64_t *bsum, unsigned long long *total)
+{
+    const int64_t tiles = vgl_ceil_div(n, VGL_TILE);
+    const unsigned grid = vgl_grid(tiles, 1, 4 * SUB_MAX_GRID);
+    {
+        vgl_timed_launch tl(c, slot);
+        hipLaunchKernelGGL(vgl_k_sub_scan_sums<S>, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, s, n, tiles, bsum);
+    }
+    {
+        vgl_timed_launch tl(c, slot);
+        hipLaunchKernelGGL(vgl_k_sub_scan_top, dim3(1), dim3(VGL_BLOCK), 0, c->stream, tiles, bsum, total);
+    }
+    {
+        vgl_timed_launch tl(c, slot);
+        hipLaunchKernelGGL(vgl_k_sub_scan_apply<S>, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, s, n, tiles, (const int64_t *)bsum);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the kept rows per direction and class ----
+struct sub_rows_src {
+    int32_t V;
+    const int32_t *new_id;
+    const int64_t *rowptr[2];    // nullptr: the direction is not planned
+    vgl_rc_bounds b;
+};
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_classify(sub_rows_src s, unsigned long long *cnt)
+{
+    int64_t rows[2][VGL_RC_N] = {{0, 0, 0}, {0, 0, 0}}, read[2] = {0, 0};
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < s.V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+        if (s.new_id[v] < 0) continue;
+#pragma unroll
+        for (int d = 0; d < 2; d++)
+            if (s.rowptr[d]) {
+                const int64_t len = s.rowptr[d][v + 1] - s.rowptr[d][v];
+                const int k = vgl_rc_class_of(len, s.b);
+#pragma unroll
+                for (int q = 0; q < VGL_RC_N; q++) rows[d][q] += k == q;
+                read[d] += len;
+            }
+    }
+#pragma unroll
+    for (int d = 0; d < 2; d++) {
+#pragma unroll
+        for (int q = 0; q < VGL_RC_N; q++) vgl_wave_flush_add(cnt + SUB_ROWS + 3 * d + q, rows[d][q]);
+        vgl_wave_flush_add(cnt + SUB_READ + d, read[d]);
+    }
+}
+struct sub_lists { vgl_rc_bounded l[2][VGL_RC_N]; };
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_lists(sub_rows_src s, sub_lists L, int32_t *old_id, unsigned long long *tail)
+{
+    vgl_rc_stage st[2 * VGL_RC_N];
+    vgl_rc_stage_open(st);
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < s.V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t v = base + threadIdx.x;
+        const int32_t nid = v < s.V ? s.new_id[v] : -1;
+        if (nid >= 0) old_id[nid] = (int32_t)v;
+#pragma unroll
+        for (int d = 0; d < 2; d++) {
+            if (!s.rowptr[d]) continue;                               // (uniform)
+            const int k = nid >= 0 ? vgl_rc_class_of(s.rowptr[d][v + 1] - s.rowptr[d][v], s.b) : -1;
+#pragma unroll
+            for (int q = 0; q < VGL_RC_N; q++) st[3 * d + q].keep(k == q, (int32_t)v, L.l[d][q], tail + 3 * d + q);
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 2; d++)
+#pragma unroll
+        for (int q = 0; q < VGL_RC_N; q++) st[3 * d + q].flush(L.l[d][q], tail + 3 * d + q);
+}
+
+// ---- the filter: FILL = false counts the survivors of every listed row, FILL = true writes them in their stored order ----
+struct sub_dir {
+    const int64_t *rowptr;       // the parent's, of this direction
+    const int32_t *adj;
+    const int32_t *new_id;
+    const uint8_t *keep_entry;   // nullptr: every entry is kept (always nullptr for direction 1)
+    // does entry e survive, and under which id does its far end
+    __device__ __forceinline__ bool keep(int64_t e, int32_t &far) const
+    {
+        far = new_id[adj[e]];
+        return far >= 0 && (!keep_entry || keep_entry[e] != 0);
+    }
+};
+struct sub_out {
+    int64_t *count;              // counting: by new id
+    const int64_t *rowptr;       // filling: the new row starts; a position at or past the row's new end is never stored to
+    int32_t *adj;
+    int64_t *origin;             // may be nullptr
+};
+// the listed row i: its first entry, its length, its new id
+struct sub_row { int64_t s, len; int32_t nid; };
+__device__ __forceinline__ sub_row sub_row_of(const sub_dir &a, const int32_t *list, int64_t i, int64_t n)
+{
+    if (i >= n) return sub_row{0, 0, 0};
+    const int32_t v = list[i];
+    const int64_t s = a.rowptr[v];
+    return sub_row{s, a.rowptr[v + 1] - s, a.new_id[v]};
+}
+template <bool FILL>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_short(sub_dir a, const int32_t *list, int32_t n, sub_out o)
+{
+    const int gi = threadIdx.x & (VGL_RC_G - 1), gshift = vgl_lane() & ~(VGL_RC_G - 1);
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x / VGL_RC_G;
+        const sub_row r = sub_row_of(a, list, i, n);
+        const int64_t at = FILL && i < n ? o.rowptr[r.nid] : 0, end = FILL && i < n ? o.rowptr[r.nid + 1] : 0;
+        int64_t kept = 0;                                             // survivors of the chunks before: the running base
+        for (int64_t j0 = 0; __any(j0 < r.len); j0 += VGL_RC_G) {     // (uniform over the wave: the longest row of its eight decides)
+            const int64_t e = r.s + j0 + gi;
+            int32_t far = -1;
+            const bool k = j0 + gi < r.len && a.keep(e, far);
+            const unsigned sub = (unsigned)(__ballot(k) >> gshift) & ((1u << VGL_RC_G) - 1u);      // the group's 8 bits of the 64-bit ballot
+            if (FILL && k) {
+                const int64_t pos = at + kept + __popc(sub & ((1u << gi) - 1u));
+                if (pos < end) {
+                    o.adj[pos] = far;
+                    if (o.origin) o.origin[pos] = e;
+                }
+            }
+            kept += __popc(sub);
+        }
+        if (!FILL && gi == 0 && i < n) o.count[r.nid] = kept;
+    }
+}
+template <bool FILL>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_wave(sub_dir a, const int32_t *list, int32_t n, sub_out o)
+{
+    const int lane = vgl_lane();
+    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
+        const sub_row r = sub_row_of(a, list, i, n);
+        const int64_t at = FILL ? o.rowptr[r.nid] : 0, end = FILL ? o.rowptr[r.nid + 1] : 0;
+        int64_t kept = 0;
+        for (int64_t j0 = 0; j0 < r.len; j0 += 64) {
+            const int64_t e = r.s + j0 + lane;
+            int32_t far = -1;
+            const bool k = j0 + lane < r.len && a.keep(e, far);
+            const unsigned long long m = __ballot(k);
+            if (FILL && k) {
+                const int64_t pos = at + kept + __popcll(m & ((1ull << lane) - 1ull));
+                if (pos < end) {
+                    o.adj[pos] = far;
+                    if (o.origin) o.origin[pos] = e;
+                }
+            }
+            kept += __popcll(m);
+        }
+        if (!FILL && lane == 0) o.count[r.nid] = kept;
+    }
+}
+// the ordered position of a survivor inside a workgroup chunk: the survivors of the wavefronts before (LDS) + those of the lanes below (ballot);
+// *total = the chunk's survivors.  Every thread of the workgroup calls; s_cnt: VGL_WAVES ints.
+__device__ __forceinline__ int sub_wg_rank(bool k, int *s_cnt, int *total)
+{
+    const unsigned long long m = __ballot(k);
+    __syncthreads();                                                  // the counts of the chunk before have been read
+    if (vgl_lane() == 0) s_cnt[vgl_wave()] = __popcll(m);
+    __syncthreads();
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < VGL_WAVES; w++) {
+        const int x = s_cnt[w];
+        if (w < vgl_wave()) pre += x;
+        tot += x;
+    }
+    *total = tot;
+    return pre + __popcll(m & ((1ull << vgl_lane()) - 1ull));
+}
+template <bool FILL>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_wg(sub_dir a, const int32_t *list, int32_t n, sub_out o)
+{
+    __shared__ int s_cnt[VGL_WAVES];
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
+        const sub_row r = sub_row_of(a, list, i, n);
+        const int64_t at = FILL ? o.rowptr[r.nid] : 0, end = FILL ? o.rowptr[r.nid + 1] : 0;
+        int64_t kept = 0;
+        for (int64_t j0 = 0; j0 < r.len; j0 += VGL_BLOCK) {
+            const int64_t e = r.s + j0 + threadIdx.x;
+            int32_t far = -1;
+            const bool k = j0 + threadIdx.x < r.len && a.keep(e, far);
+            int tot = 0;
+            const int rank = sub_wg_rank(k, s_cnt, &tot);
+            if (FILL && k) {
+                const int64_t pos = at + kept + rank;
+                if (pos < end) {
+                    o.adj[pos] = far;
+                    if (o.origin) o.origin[pos] = e;
+                }
+            }
+            kept += tot;
+        }
+        if (!FILL && threadIdx.x == 0) o.count[r.nid] = kept;
+    }
+}
+template <bool FILL>
+int sub_launch(vgl_hip_ctx *c, const vgl_hip_subgraph_plan *p, int d, const sub_dir &a, const sub_out &o)
+{
+    const char *const count_slot[VGL_RC_N] = {"sub_count_short", "sub_count_wave", "sub_count_wg"};
+    const char *const fill_slot[VGL_RC_N] = {"sub_fill_short", "sub_fill_wave", "sub_fill_wg"};
+    hipStream_t st = c->stream;
+    return vgl_rc_launch(c, FILL ? fill_slot : count_slot, p->rows[d], [&](int cls, int64_t n) {
+        const int32_t *list = p->lists.p + p->off[d][cls];
+        if (cls == VGL_RC_SHORT)
+            hipLaunchKernelGGL(vgl_k_sub_short<FILL>, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
+        else if (cls == VGL_RC_WAVE)
+            hipLaunchKernelGGL(vgl_k_sub_wave<FILL>, dim3(vgl_grid(n, VGL_WAVES, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
+        else
+            hipLaunchKernelGGL(vgl_k_sub_wg<FILL>, dim3(vgl_grid(n, 1, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
+    });
+}
+sub_dir sub_dir_of(const vgl_hip_subgraph_plan *p, int d)
+{
+    const vgl_dir_csr &csr = d == 0 ? p->g->out : p->g->in;
+    return sub_dir{csr.rowptr, csr.adj, p->new_id.p, d == 0 ? p->keep_entry : nullptr};
+}
+
+// ---- k-hop ----
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_khop_check(int32_t V, const int32_t *seeds, int64_t n, unsigned long long *cnt)
+{
+    int64_t bad = 0;
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) bad += seeds[i] < 0 || seeds[i] >= V;
+    vgl_wave_flush_add(cnt + KH_BAD, bad);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_khop_seed(const int32_t *seeds, int64_t n, int32_t *hop)
+{
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) hop[seeds[i]] = 0;      // (repeats store the same value)
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_khop_fill(int32_t V, int32_t *hop)
+{
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) hop[v] = -1;
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_khop_reached(int32_t V, const int32_t *hop, unsigned long long *cnt)
+{
+    int64_t r = 0;
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) r += hop[v] >= 0;
+    vgl_wave_flush_add(cnt + KH_REACHED, r);
+}
+
+// ---- sampling ----
+__host__ __device__ inline uint32_t sub_fmix32(uint32_t h)
+{
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
+struct smp_src {
+    int32_t V;
+    const int64_t *rowptr;
+    const int32_t *seeds;
+    int32_t fanout;
+    vgl_rc_bounds b;
+};
+// validates the seeds; count[i] = min(fanout, degree) (0 for a seed out of range); rows per class, the degrees' sum
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_count(smp_src s, int64_t n, int64_t *count, unsigned long long *cnt)
+{
+    int64_t rows[VGL_RC_N] = {0, 0, 0}, bad = 0, exam = 0;
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t v = s.seeds[i];
+        int64_t take = 0;
+        if (v < 0 || v >= s.V) bad++;
+        else {
+            const int64_t deg = s.rowptr[v + 1] - s.rowptr[v];
+            const int k = vgl_rc_class_of(deg, s.b);
+#pragma unroll
+            for (int q = 0; q < VGL_RC_N; q++) rows[q] += k == q;
+            exam += deg;
+            take = deg < s.fanout ? deg : s.fanout;
+        }
+        count[i] = take;
+    }
+#pragma unroll
+    for (int q = 0; q < VGL_RC_N; q++) vgl_wave_flush_add(cnt + SMP_ROWS + q, rows[q]);
+    vgl_wave_flush_add(cnt + SMP_BAD, bad);
+    vgl_wave_flush_add(cnt + SMP_EXAM, exam);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_lists(smp_src s, int64_t n, vgl_rc_bounded L0, vgl_rc_bounded L1, vgl_rc_bounded L2, unsigned long long *tail)
+{
+    const vgl_rc_bounded L[VGL_RC_N] = {L0, L1, L2};
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x;
+        int k = -1;
+        if (i < n) {
+            const int32_t v = s.seeds[i];                             // (validated by the counting pass)
+            k = vgl_rc_class_of(s.rowptr[v + 1] - s.rowptr[v], s.b);
+        }
+#pragma unroll
+        for (int q = 0; q < VGL_RC_N; q++) st[q].keep(k == q, (int32_t)i, L[q], tail + q);
+    }
+#pragma unroll
+    for (int q = 0; q < VGL_RC_N; q++) st[q].flush(L[q], tail + q);
+}
+struct smp_args {
+    const int64_t *rowptr;       // of the sampled direction
+    const int32_t *adj;
+    const int32_t *seeds;
+    const int64_t *out_rowptr;
+    int32_t *out_adj;
+    int64_t *out_origin;         // may be nullptr
+    int32_t fanout;
+    uint32_t mix;                // fmix32(seed + 0x9e3779b9)
+    __device__ __forceinline__ uint32_t key(int64_t p) const { return sub_fmix32((uint32_t)p ^ mix); }
+};
+struct smp_row { int64_t s, len, at, end; };      // the row's entries; its slots [at, end) of the output, never stored past
+__device__ __forceinline__ smp_row smp_row_of(const smp_args &a, const int32_t *list, int64_t i, int64_t n)
+{
+    if (i >= n) return smp_row{0, 0, 0, 0};
+    const int32_t r = list[i], v = a.seeds[r];
+    const int64_t s = a.rowptr[v];
+    return smp_row{s, a.rowptr[v + 1] - s, a.out_rowptr[r], a.out_rowptr[r + 1]};
+}
+// G lanes per row (8 or 64): an entry is taken when fewer than fanout entries of the row have a smaller key
+template <int G>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_group(smp_args a, const int32_t *list, int32_t n)
+{
+    const int gi = threadIdx.x & (G - 1), gshift = vgl_lane() & ~(G - 1);
+    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / G)) {      // (uniform over the workgroup)
+        const smp_row r = smp_row_of(a, list, base + threadIdx.x / G, n);
+        const bool all = r.len <= a.fanout;
+        int64_t kept = 0;
+        for (int64_t j0 = 0; __any(j0 < r.len); j0 += G) {            // (uniform over the wave)
+            const int64_t j = j0 + gi;
+            bool k = j < r.len;
+            if (k && !all) {
+                const uint32_t mine = a.key(r.s + j);
+                int32_t rank = 0;
+                for (int64_t t = 0; t < r.len && rank < a.fanout; t++) rank += a.key(r.s + t) < mine;
+                k = rank < a.fanout;
+            }
+            const unsigned long long m = __ballot(k);
+            const unsigned long long sub = G == 64 ? m : (m >> gshift) & ((1ull << (G & 63)) - 1ull);
+            if (k) {
+                const int64_t pos = r.at + kept + __popcll(sub & ((1ull << gi) - 1ull));
+                if (pos < r.end) {
+                    a.out_adj[pos] = a.adj[r.s + j];
+                    if (a.out_origin) a.out_origin[pos] = r.s + j;
+                }
+            }
+            kept += __popcll(sub);
+        }
+    }
+}
+// a workgroup per row: the fanout-th smallest key by four 8-bit radix passes (most significant byte first), then every entry whose key is not larger
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_wg(smp_args a, const int32_t *list, int32_t n)
+{
+    __shared__ unsigned s_hist[256];
+    __shared__ int64_t s_scan[VGL_WAVES];
+    __shared__ unsigned s_bin, s_k;
+    __shared__ int s_cnt[VGL_WAVES];
+    static_assert(VGL_BLOCK == 256, "one histogram bin per thread");
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
+        const smp_row r = smp_row_of(a, list, i, n);
+        uint32_t limit = 0xffffffffu;                                 // the largest key taken
+        if (r.len > a.fanout) {                                       // (uniform)
+            uint32_t prefix = 0;
+            unsigned want = (unsigned)a.fanout;                       // the rank sought among the keys that share the prefix, from 1
+            for (int pass = 0; pass < 4; pass++) {
+                const int shift = 24 - 8 * pass;
+                __syncthreads();                                      // s_bin / s_k / the histogram of the pass before have been read
+                s_hist[threadIdx.x] = 0;
+                __syncthreads();
+                for (int64_t j = threadIdx.x; j < r.len; j += VGL_BLOCK) {
+                    const uint32_t key = a.key(r.s + j);
+                    if (((uint64_t)key >> (shift + 8)) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
+                }
+                __syncthreads();
+                const int64_t h = s_hist[threadIdx.x];
+                int64_t tot = 0;
+                const int64_t ex = vgl_block_excl_add(h, s_scan, &tot);
+                if (ex < (int64_t)want && (int64_t)want <= ex + h) { s_bin = threadIdx.x; s_k = (unsigned)((int64_t)want - ex); }
+                __syncthreads();
+                prefix = (prefix << 8) | s_bin;
+                want = s_k;
+            }
+            limit = prefix;
+        }
+        int64_t kept = 0;
+        for (int64_t j0 = 0; j0 < r.len; j0 += VGL_BLOCK) {
+            const int64_t j = j0 + threadIdx.x;
+            const bool k = j < r.len && a.key(r.s + j) <= limit;
+            int tot = 0;
+            const int rank = sub_wg_rank(k, s_cnt, &tot);
+            if (k) {
+                const int64_t pos = r.at + kept + rank;
+                if (pos < r.end) {
+                    a.out_adj[pos] = a.adj[r.s + j];
+                    if (a.out_origin) a.out_origin[pos] = r.s + j;
+                }
+            }
+            kept += tot;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vgl_hip_subgraph_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const uint8_t *d_keep_vertex, const uint8_t *d_keep_entry, vgl_hip_subgraph_plan **out)
+{
+    if (!c || !g || !out) VGL_FAIL("subgraph_plan_create: null argument");
+    if (sub_sharded(g)) VGL_FAIL("subgraph_plan_create: graph handle must own all rows (subgraph extraction has no sharded form)");
+    if (!d_keep_vertex && !d_keep_entry) VGL_FAIL("subgraph_plan_create: both masks are NULL (give at least one of d_keep_vertex, d_keep_entry)");
+    const int32_t V = g->V;
+    hipStream_t st = c->stream;
+    const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_SUB_SHORT", "VGL_SUB_WAVE");
+    vgl_building<vgl_hip_subgraph_plan> p(new vgl_hip_subgraph_plan(), vgl_synced_delete<vgl_hip_subgraph_plan>{c});
+    p->g = g;
+    p->V = V;
+    p->keep_entry = d_keep_entry;
+    p->planned[0] = true;
+    p->planned[1] = g->in.rowptr != nullptr && !d_keep_entry;
+    memset(&p->st, 0, sizeof(p->st));
+
+    vgl_dev<unsigned long long> cnt;
+    vgl_dev<int64_t> bsum;
+    VGL_TRY(sub_open_counters(c, &cnt, SUB_NCNT));
+    VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div((int64_t)V + 1, VGL_TILE)));
+    VGL_TRY(p->new_id.alloc(st, (size_t)V));
+    VGL_TRY(sub_scan(c, "sub_scan", sub_mask_src{d_keep_vertex, p->new_id.p}, (int64_t)V, bsum.p, cnt + SUB_VK));
+    const sub_rows_src src{V, p->new_id.p, {g->out.rowptr, p->planned[1] ? g->in.rowptr : nullptr}, b};
+    {
+        vgl_timed_launch tl(c, "sub_scan");
+        hipLaunchKernelGGL(vgl_k_sub_classify, dim3(vgl_grid(V, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, cnt.p);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_TRY(vgl_publish_counters(c, "sub_publish", cnt, SUB_NCNT));
+    const int64_t Vk = c->h_counters[SUB_VK];
+    if (Vk < 0 || Vk > V) VGL_FAIL("subgraph_plan_create: internal error (the kept vertices exceed V)");
+    p->Vk = (int32_t)Vk;
+    int64_t at = 0;
+    for (int d = 0; d < 2; d++) {
+        int64_t total = 0;
+        for (int k = 0; k < VGL_RC_N; k++) {
+            p->rows[d][k] = c->h_counters[SUB_ROWS + 3 * d + k];
+            p->off[d][k] = at;
+            at += p->rows[d][k];
+            total += p->rows[d][k];
+        }
+        if (total != (p->planned[d] ? Vk : 0)) VGL_FAIL("subgraph_plan_create: internal error (the classes do not add up to the kept rows)");
+    }
+    vgl_hip_subgraph_stats &s = p->st;
+    s.vertices_kept = Vk;
+    s.rows_short_out = p->rows[0][0]; s.rows_wave_out = p->rows[0][1]; s.rows_wg_out = p->rows[0][2];
+    s.rows_short_in = p->rows[1][0]; s.rows_wave_in = p->rows[1][1]; s.rows_wg_in = p->rows[1][2];
+    s.entries_read_out = c->h_counters[SUB_READ + 0];
+    s.entries_read_in = c->h_counters[SUB_READ + 1];
+    if (Vk > 0) {
+        VGL_TRY(p->old_id.alloc(st, (size_t)Vk));
+        VGL_TRY(p->lists.alloc(st, (size_t)at));
+        sub_lists L;
+        for (int d = 0; d < 2; d++)
+            for (int k = 0; k < VGL_RC_N; k++) L.l[d][k] = vgl_rc_bounded{p->lists.p + p->off[d][k], (int32_t)p->rows[d][k]};
+        {
+            vgl_timed_launch tl(c, "sub_scan");
+            hipLaunchKernelGGL(vgl_k_sub_lists, dim3(vgl_grid(V, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, L, p->old_id.p, cnt + SUB_TAIL);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        for (int d = 0; d < 2; d++) {
+            if (!p->planned[d]) continue;
+            VGL_TRY(p->rowptr[d].alloc(st, (size_t)Vk + 1));
+            VGL_HIP_TRY(hipMemsetAsync(p->rowptr[d].p + Vk, 0, sizeof(int64_t), st));      // (every other entry is written by its row's owner)
+            VGL_TRY(sub_launch<false>(c, p.get(), d, sub_dir_of(p.get(), d), sub_out{p->rowptr[d].p, nullptr, nullptr, nullptr}));
+            VGL_TRY(sub_scan(c, "sub_scan", sub_i64_src{p->rowptr[d].p, p->rowptr[d].p}, Vk + 1, bsum.p, cnt + SUB_KEPT + d));
+        }
+        VGL_TRY(vgl_publish_counters(c, "sub_publish", cnt, SUB_NCNT));
+        s.entries_kept_out = c->h_counters[SUB_KEPT + 0];
+        s.entries_kept_in = c->h_counters[SUB_KEPT + 1];
+    }
+    const int64_t me = d_keep_entry ? 1 : 0;
+    s.algorithmic_bytes = (d_keep_vertex ? (int64_t)V : 0) + 4 * (int64_t)V + 4 * Vk;
+    for (int d = 0; d < 2; d++)
+        if (p->planned[d]) {
+            const int64_t read = d == 0 ? s.entries_read_out : s.entries_read_in, kept = d == 0 ? s.entries_kept_out : s.entries_kept_in;
+            s.algorithmic_bytes += 56 * Vk + 32 * (Vk + 1) + (16 + 2 * me) * read + 4 * kept;
+        }
+    VGL_HIP_TRY(hipStreamSynchronize(st));
+    *out = p.release();
+    return 0;
+}
+
+int vgl_hip_subgraph_plan_info(vgl_hip_subgraph_plan *p, int32_t *vertices, int64_t *out_entries, int64_t *in_entries, vgl_hip_subgraph_stats *stats)
+{
+    if (!p) VGL_FAIL("subgraph_plan_info: null argument");
+    if (vertices) *vertices = p->Vk;
+    if (out_entries) *out_entries = p->st.entries_kept_out;
+    if (in_entries) *in_entries = p->planned[1] ? p->st.entries_kept_in : -1;
+    if (stats) *stats = p->st;
+    return 0;
+}
+
+int vgl_hip_subgraph_plan_vertex_maps(vgl_hip_ctx *c, vgl_hip_subgraph_plan *p, int32_t *d_new_id, int32_t *d_old_id)
+{
+    if (!c || !p) VGL_FAIL("subgraph_plan_vertex_maps: null argument");
+    if (d_new_id && p->V > 0) VGL_HIP_TRY(hipMemcpyAsync(d_new_id, p->new_id.p, sizeof(int32_t) * (size_t)p->V, hipMemcpyDeviceToDevice, c->stream));
+    if (d_old_id && p->Vk > 0) VGL_HIP_TRY(hipMemcpyAsync(d_old_id, p->old_id.p, sizeof(int32_t) * (size_t)p->Vk, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+int vgl_hip_subgraph_plan_fill(vgl_hip_ctx *c, vgl_hip_subgraph_plan *p, int direction, int64_t *d_rowptr, int32_t *d_adj, int64_t *d_origin)
+{
+    if (!c || !p) VGL_FAIL("subgraph_plan_fill: null argument");
+    if (direction != 0 && direction != 1) VGL_FAIL("subgraph_plan_fill: direction must be 0 (outgoing) or 1 (incoming)");
+    if (!p->planned[direction])
+        VGL_FAIL(p->keep_entry ? "subgraph_plan_fill: with an entry mask only direction 0 can be filled (transpose the result for its incoming CSR)"
+                               : "subgraph_plan_fill: direction 1 needs the incoming CSR");
+    const int64_t kept = direction == 0 ? p->st.entries_kept_out : p->st.entries_kept_in;
+    if (p->Vk == 0) return 0;                                         // nothing to write
+    if (!d_rowptr || (kept > 0 && !d_adj)) VGL_FAIL("subgraph_plan_fill: d_rowptr and d_adj must not be NULL");
+    VGL_HIP_TRY(hipMemcpyAsync(d_rowptr, p->rowptr[direction].p, sizeof(int64_t) * ((size_t)p->Vk + 1), hipMemcpyDeviceToDevice, c->stream));
+    if (kept == 0) return 0;
+    return sub_launch<true>(c, p, direction, sub_dir_of(p, direction), sub_out{nullptr, p->rowptr[direction].p, d_adj, d_origin});
+}
+
+int vgl_hip_subgraph_plan_destroy(vgl_hip_ctx *c, vgl_hip_subgraph_plan *p)
+{
+    if (!c) VGL_FAIL("subgraph_plan_destroy: null argument");
+    if (!p) return 0;
+    (void)hipStreamSynchronize(c->stream);
+    delete p;
+    return 0;
+}
+
+int vgl_hip_khop_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_seeds, int64_t n, int32_t hops, int direction, int symmetric, int32_t *d_hop,
+                     vgl_hip_khop_stats *stats)
+{
+    if (!c || !g) VGL_FAIL("khop_run: null argument");
+    if (sub_sharded(g)) VGL_FAIL("khop_run: graph handle must own all rows (k-hop has no sharded form)");
+    if (!d_hop) VGL_FAIL("khop_run: d_hop must not be NULL");
+    if (n < 0) VGL_FAIL("khop_run: n is negative");
+    if (n > 0 && !d_seeds) VGL_FAIL("khop_run: d_seeds must not be NULL");
+    if (hops < 0) VGL_FAIL("khop_run: hops is negative");
+    if (direction != 0 && direction != 1) VGL_FAIL("khop_run: direction must be 0 (outgoing) or 1 (incoming)");
+    if ((symmetric || direction == 1) && !g->in.rowptr) VGL_FAIL(symmetric ? "khop_run: symmetric needs the incoming CSR" : "khop_run: direction 1 needs the incoming CSR");
+    const int32_t V = g->V;
+    hipStream_t st = c->stream;
+    vgl_hip_khop_stats out;
+    memset(&out, 0, sizeof(out));
+    vgl_dev<unsigned long long> cnt;
+    VGL_TRY(sub_open_counters(c, &cnt, KH_NCNT));
+    if (n > 0) {
+        {
+            vgl_timed_launch tl(c, "khop_init");
+            hipLaunchKernelGGL(vgl_k_khop_check, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_seeds, n, cnt.p);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_publish_counters(c, "khop_publish", cnt, KH_NCNT));
+        if (c->h_counters[KH_BAD] != 0) VGL_FAIL("khop_run: a seed is outside [0, V)");
+    }
+    if ((symmetric || direction == 1) && !g->transposed) {            // the handle with the two directions swapped, as scc keeps it
+        vgl_hip_graph *t = nullptr;
+        VGL_TRY(vgl_hip_graph_create(c, V, 0, V, g->in.rowptr, g->in.adj, g->in.edges, g->out.rowptr, g->out.adj, g->out.edges, &t));
+        g->transposed.reset(t);
+    }
+    {
+        vgl_timed_launch tl(c, "khop_init");
+        hipLaunchKernelGGL(vgl_k_khop_fill, dim3(vgl_grid(V, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_hop);
+    }
+    if (n > 0) {
+        vgl_timed_launch tl(c, "khop_init");
+        hipLaunchKernelGGL(vgl_k_khop_seed, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, d_seeds, n, d_hop);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    vgl_hip_graph *follow[2] = {nullptr, nullptr};
+    int nfollow = 0;
+    if (symmetric || direction == 0) follow[nfollow++] = g;
+    if (symmetric || direction == 1) follow[nfollow++] = g->transposed.get();
+    for (int32_t level = 0; level < hops && n > 0; level++) {
+        int64_t F = 0, M = 0;
+        for (int k = 0; k < nfollow; k++) {                           // (a vertex the first step reaches holds level + 1: it is no frontier of the second)
+            int64_t f = 0, m = 0;
+            VGL_TRY(vgl_hip_bfs_step_top_down(c, follow[k], d_hop, level, nullptr, &f, &m));
+            F = f;
+            M += m;
+        }
+        if (F == 0) break;
+        out.levels_run++;
+        out.frontier_total += F;
+        out.edges_examined += M;
+    }
+    {
+        vgl_timed_launch tl(c, "khop_count");
+        hipLaunchKernelGGL(vgl_k_khop_reached, dim3(vgl_grid(V, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)d_hop, cnt.p);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_TRY(vgl_publish_counters(c, "khop_publish", cnt, KH_NCNT));
+    VGL_HIP_TRY(hipStreamSynchronize(st));
+    out.reached = c->h_counters[KH_REACHED];
+    if (stats) *stats = out;
+    return 0;
+}
+
+int vgl_hip_sample_neighbors(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_seeds, int64_t n, int32_t fanout, int direction, uint32_t seed, int64_t *d_rowptr,
+                             int32_t *d_adj, int64_t *d_origin, vgl_hip_sample_stats *stats)
+{
+    if (!c || !g) VGL_FAIL("sample_neighbors: null argument");
+    if (sub_sharded(g)) VGL_FAIL("sample_neighbors: graph handle must own all rows (sampling has no sharded form)");
+    if (n < 0 || n >= ((int64_t)1 << 31)) VGL_FAIL("sample_neighbors: n must be in [0, 2^31)");
+    if (n > 0 && !d_seeds) VGL_FAIL("sample_neighbors: d_seeds must not be NULL");
+    if (fanout < 1) VGL_FAIL("sample_neighbors: fanout must be at least 1");
+    if (direction != 0 && direction != 1) VGL_FAIL("sample_neighbors: direction must be 0 (outgoing) or 1 (incoming)");
+    if (direction == 1 && !g->in.rowptr) VGL_FAIL("sample_neighbors: direction 1 needs the incoming CSR");
+    if (!d_rowptr || (n > 0 && !d_adj)) VGL_FAIL("sample_neighbors: d_rowptr and d_adj must not be NULL");
+    const vgl_dir_csr &csr = direction == 0 ? g->out : g->in;
+    if (csr.edges >= ((int64_t)1 << 32)) VGL_FAIL("sample_neighbors: the adjacency array has 2^32 entries or more (the keys of its positions would tie)");
+    hipStream_t st = c->stream;
+    const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_SAMPLE_SHORT", "VGL_SAMPLE_WAVE");
+    vgl_hip_sample_stats out;
+    memset(&out, 0, sizeof(out));
+    out.seeds = n;
+    vgl_dev<unsigned long long> cnt;
+    vgl_dev<int64_t> count, bsum;
+    vgl_dev<int32_t> list;
+    VGL_TRY(sub_open_counters(c, &cnt, SMP_NCNT));
+    VGL_TRY(count.alloc(st, (size_t)n + 1));
+    VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div(n + 1, VGL_TILE)));
+    VGL_HIP_TRY(hipMemsetAsync(count.p + n, 0, sizeof(int64_t), st));
+    const smp_src src{g->V, csr.rowptr, d_seeds, fanout, b};
+    if (n > 0) {
+        {
+            vgl_timed_launch tl(c, "sample_count");
+            hipLaunchKernelGGL(vgl_k_sample_count, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, n, count.p, cnt.p);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+    }
+    VGL_TRY(vgl_publish_counters(c, "sample_publish", cnt, SMP_NCNT));
+    if (c->h_counters[SMP_BAD] != 0) VGL_FAIL("sample_neighbors: a seed is outside [0, V)");
+    const int64_t rows[VGL_RC_N] = {c->h_counters[SMP_ROWS + 0], c->h_counters[SMP_ROWS + 1], c->h_counters[SMP_ROWS + 2]};
+    if (rows[0] + rows[1] + rows[2] != n) VGL_FAIL("sample_neighbors: internal error (the classes do not add up to the seeds)");
+    out.rows_short = rows[0]; out.rows_wave = rows[1]; out.rows_wg = rows[2];
+    out.entries_examined = c->h_counters[SMP_EXAM];
+    // from here on the outputs are written
+    VGL_TRY(sub_scan(c, "sample_count", sub_i64_src{count.p, d_rowptr}, n + 1, bsum.p, cnt + SMP_TOTAL));
+    if (n > 0) {
+        VGL_TRY(list.alloc(st, (size_t)n));
+        vgl_rc_bounded L[VGL_RC_N];
+        int64_t off[VGL_RC_N], at = 0;
+        for (int k = 0; k < VGL_RC_N; k++) {
+            off[k] = at;
+            L[k] = vgl_rc_bounded{list.p + at, (int32_t)rows[k]};
+            at += rows[k];
+        }
+        {
+            vgl_timed_launch tl(c, "sample_count");
+            hipLaunchKernelGGL(vgl_k_sample_lists, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, n, L[0], L[1], L[2], cnt + SMP_TAIL);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        const smp_args a{csr.rowptr, csr.adj, d_seeds, d_rowptr, d_adj, d_origin, fanout, sub_fmix32(seed + 0x9e3779b9u)};
+        const char *const slot[VGL_RC_N] = {"sample_short", "sample_wave", "sample_wg"};
+        VGL_TRY(vgl_rc_launch(c, slot, rows, [&](int cls, int64_t m) {
+            const int32_t *l = list.p + off[cls];
+            if (cls == VGL_RC_SHORT)
+                hipLaunchKernelGGL(vgl_k_sample_group<VGL_RC_G>, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
+            else if (cls == VGL_RC_WAVE)
+                hipLaunchKernelGGL(vgl_k_sample_group<64>, dim3(vgl_grid(m, VGL_WAVES, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
+            else
+                hipLaunchKernelGGL(vgl_k_sample_wg, dim3(vgl_grid(m, 1, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
+        }));
+    }
+    VGL_TRY(vgl_publish_counters(c, "sample_publish", cnt, SMP_NCNT));
+    VGL_HIP_TRY(hipStreamSynchronize(st));
+    out.sampled_total = c->h_counters[SMP_TOTAL];
+    out.algorithmic_bytes = 60 * n + 16 * (n + 1) + 8 * out.sampled_total;
+    if (stats) *stats = out;
+    return 0;
+}
+
+}  // extern "C"

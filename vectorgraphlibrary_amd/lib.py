@@ -105,6 +105,21 @@ class SimTopkStats(C.Structure):
                 ("algorithmic_bytes", C.c_int64), ("prepared_now", C.c_int32)]
 
 
+class SubgraphStats(C.Structure):
+    _fields_ = [("vertices_kept", C.c_int64), ("rows_short_out", C.c_int64), ("rows_wave_out", C.c_int64), ("rows_wg_out", C.c_int64),
+                ("rows_short_in", C.c_int64), ("rows_wave_in", C.c_int64), ("rows_wg_in", C.c_int64), ("entries_read_out", C.c_int64),
+                ("entries_read_in", C.c_int64), ("entries_kept_out", C.c_int64), ("entries_kept_in", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
+class KhopStats(C.Structure):
+    _fields_ = [("reached", C.c_int64), ("frontier_total", C.c_int64), ("edges_examined", C.c_int64), ("levels_run", C.c_int32)]
+
+
+class SampleStats(C.Structure):
+    _fields_ = [("seeds", C.c_int64), ("rows_short", C.c_int64), ("rows_wave", C.c_int64), ("rows_wg", C.c_int64),
+                ("entries_examined", C.c_int64), ("sampled_total", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class ExchangeStats(C.Structure):
     _fields_ = [("collectives", C.c_int64), ("bytes_received", C.c_int64), ("list_steps", C.c_int32), ("dense_steps", C.c_int32),
                 ("sparse_levels", C.c_int32), ("exchanges", C.c_int32)]
@@ -205,6 +220,13 @@ _SIGNATURES = {
     "vgl_hip_sim_prepare": [_p, _p],
     "vgl_hip_sim_pairs": [_p, _p, _p, _p, _i64, _p, _p, _p, _p, C.POINTER(SimPairsStats)],
     "vgl_hip_sim_topk": [_p, _p, _p, _i32, _int, _i32, _int, _p, _p, _p, C.POINTER(SimTopkStats)],
+    "vgl_hip_subgraph_plan_create": [_p, _p, _p, _p, _pp],
+    "vgl_hip_subgraph_plan_info": [_p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(SubgraphStats)],
+    "vgl_hip_subgraph_plan_vertex_maps": [_p, _p, _p, _p],
+    "vgl_hip_subgraph_plan_fill": [_p, _p, _int, _p, _p, _p],
+    "vgl_hip_subgraph_plan_destroy": [_p, _p],
+    "vgl_hip_khop_run": [_p, _p, _p, _i64, _i32, _int, _int, _p, C.POINTER(KhopStats)],
+    "vgl_hip_sample_neighbors": [_p, _p, _p, _i64, _i32, _int, C.c_uint32, _p, _p, _p, C.POINTER(SampleStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
