@@ -163,6 +163,31 @@ def _complete(n):
     return [(a, b) for a in range(n) for b in range(a + 1, n)]
 
 
+TEAM_EDGE_BOUNDS = (4, 20)                                                       # VGL_MIS_SHORT, VGL_MIS_WAVE of the graph below
+TEAM_EDGE_ROWS = (33, 5, 2)                                                      # its rows per class under those bounds
+
+
+def rows_at_the_team_edges():
+    """(V, src, dst) of 40 vertices whose rows fill the classes under TEAM_EDGE_BOUNDS to one item past a full workgroup of the kernels: 33 short rows
+    (32 per workgroup + 1), 5 wave rows (4 + 1), 2 workgroup rows; the row lengths sit on the bounds: 0 (vertex 7, isolated) and 4 among the short
+    rows, 5 and 20 among the wave rows, 21 for a workgroup row.  A graph of 40 vertices cannot hold a row longer than 39: hence the small wave bound.
+    Vertices 0, 1: workgroup rows (21, 25 entries); 2 .. 6: wave rows (5, 20, 6, 7, 8); 8 .. 39: short rows that the hubs share out in turn (2 or 3
+    each), two of them joined to make a row of exactly 4."""
+    shrt, wave = TEAM_EDGE_BOUNDS
+    hubs = {0: wave + 1, 1: wave + 5, 2: shrt + 1, 3: wave, 4: shrt + 2, 5: shrt + 3, 6: shrt + 4}
+    leaves = np.arange(8, 40)
+    src, dst, at = [], [], 0
+    for h, d in hubs.items():
+        src.append(np.full(d, h))
+        dst.append(leaves[(at + np.arange(d)) % leaves.size])
+        at += d
+    hits = np.bincount(np.concatenate(dst), minlength=40)
+    a, b = np.flatnonzero(hits == 3)[:2]                                         # two leaves of three hubs each: one more entry makes 4
+    src.append(np.array([a, 8]))                                                 # (and a stored duplicate of an entry, a loop: the simple graph drops them)
+    dst.append(np.array([b, 8]))
+    return 40, np.concatenate(src), np.concatenate(dst)
+
+
 # name -> (V, stored entries, vertex priorities, edge priorities (one per undirected edge, ascending (lo, hi)), expected set, expected matching)
 HAND_CASES = {
     "empty": (0, [], [], [], [], []),

@@ -107,6 +107,19 @@ def test_round_closed_form(seed):
             assert -rnd[v] == 1 + int(rnd[nb][rnd[nb] > 0].min())
 
 
+def test_team_edge_graph_fills_the_classes_as_it_says():
+    """the graph of the GPU test of the kernels' item-count edges: 33 / 5 / 2 rows per class, row lengths on the bounds"""
+    V, src, dst = R.rows_at_the_team_edges()
+    shrt, wave = R.TEAM_EDGE_BOUNDS
+    deg = R.simple_graph(V, src, dst)["deg"]
+    cls = np.where(deg <= shrt, 0, np.where(deg <= wave, 1, 2))
+    assert tuple(np.bincount(cls, minlength=3).tolist()) == R.TEAM_EDGE_ROWS == (33, 5, 2)
+    assert 33 == 32 + 1 and 5 == 4 + 1                                           # a full workgroup of 8-lane teams, of wavefronts, and one more
+    for want in (0, shrt, shrt + 1, wave, wave + 1):
+        assert (deg == want).any(), (want, deg.tolist())
+    assert deg[7] == 0 and deg.max() <= V - 1
+
+
 def test_path_64_closed_forms():
     G = R.simple_graph(64, np.arange(63), np.arange(1, 64))
     m = R.mis_rounds(G, np.arange(64))

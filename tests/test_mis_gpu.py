@@ -300,6 +300,31 @@ def test_rows_at_the_class_bounds_and_shrunk_thresholds(ctx, monkeypatch):
     g.close()
 
 
+def test_item_counts_one_past_a_full_workgroup(ctx, monkeypatch):
+    """33 short rows (a workgroup of 32 eight-lane teams and one more: 31 teams of the last workgroup have no row), 5 wave rows (4 + 1), 2 workgroup rows,
+    row lengths on the bounds (tests/test_mis_cpu.py checks that the graph is that); the set, the matching, their rounds and statistics are the
+    restatement's, under default keys and under priorities that decide the seven long rows last, so every class works until the last round"""
+    V, src, dst, G = graph_of("team_edges", R.rows_at_the_team_edges)
+    for k, v in zip(("VGL_MIS_SHORT", "VGL_MIS_WAVE"), R.TEAM_EDGE_BOUNDS):
+        monkeypatch.setenv(k, str(v))
+    g = api().Graph.from_coo(ctx, V, *coo(ctx, src, dst))
+    hubs_last = np.arange(V) + 1
+    hubs_last[:7] = V + 1 + np.arange(7)
+    ctx.timing(True)
+    check_mis(g, G, None, seed=5, what="team edges, default keys")
+    check_mis(g, G, hubs_last, what="team edges, the long rows last")
+    n = launches(ctx, MIS_SLOTS)
+    check_matching(g, V, src, dst, None, seed=5, what="team edges, default keys")
+    edges = list(zip(G["eu"].tolist(), G["ev"].tolist()))
+    check_matching(g, V, src, dst, {e: len(edges) - i for i, e in enumerate(edges)}, what="team edges, the edges in reverse")
+    m = launches(ctx, MM_SLOTS)
+    ctx.timing(False)
+    print("launches", n, m)
+    assert n["mis_short"] >= 1 and n["mis_wave"] >= 1 and n["mis_wg"] >= 1, n
+    assert m["mm_best_short"] >= 1 and m["mm_best_wave"] >= 1 and m["mm_best_wg"] >= 1, m
+    g.close()
+
+
 @pytest.mark.parametrize("kind,scale,ef,seed", [("rmat", 12, 16, 1), ("uniform", 14, 8, 1)])
 def test_generated_graphs(kind, scale, ef, seed, ctx):
     A = api()

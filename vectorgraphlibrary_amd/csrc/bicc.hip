@@ -207,36 +207,19 @@ __device__ __forceinline__ void bi_bfs_entry(const bi_bfs &t, int32_t v, int64_t
     }
     bi_append(app, w, cls, t.L, t.cnt + BI_TAIL);
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs_short(bi_bfs t, const int32_t *rows, int32_t n)
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs(const int32_t *rows, int32_t n, bi_bfs t)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    using T = vgl_rc_team<CLS>;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
         int32_t v = 0;
         int64_t lo = 0, hi = 0;
         if (i < n) {
             v = rows[i];
             lo = t.rowptr[v]; hi = t.rowptr[v + 1];
         }
-        for (int64_t e = lo + gi; __any(e < hi); e += VGL_RC_G) bi_bfs_entry(t, v, e, hi);      // (uniform over the wave)
-    }
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs_wave(bi_bfs t, const int32_t *rows, int32_t n)
-{
-    const int lane = vgl_lane();
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = rows[i];
-        const int64_t lo = t.rowptr[v], hi = t.rowptr[v + 1];
-        for (int64_t e0 = lo; e0 < hi; e0 += 64) bi_bfs_entry(t, v, e0 + lane, hi);
-    }
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_bfs_wg(bi_bfs t, const int32_t *rows, int32_t n)
-{
-    const int lane = vgl_lane();
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int32_t v = rows[i];
-        const int64_t lo = t.rowptr[v], hi = t.rowptr[v + 1];
-        for (int64_t e0 = lo + vgl_wave() * 64; e0 < hi; e0 += VGL_BLOCK) bi_bfs_entry(t, v, e0 + lane, hi);      // (uniform over the wave)
+        for (int64_t e = lo + T::lane(); __any(e < hi); e += T::LANES) bi_bfs_entry(t, v, e, hi);      // (uniform over the wave)
     }
 }
 
@@ -294,63 +277,25 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_lowhigh(bi_slice s, cons
 // ---- rows by class, the smallest and the largest of a value over the row's entries, one writer per row ----
 // OP: ctx(v) -> what entry() needs of the row; entry(v, ctx, slot, mn, mx) folds one entry; finish(v, mn, mx) writes and returns what is counted;
 // counter() -> where the counts go, or NULL.
-template <class OP>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows_short(OP op, const int32_t *rows, int32_t n)
+template <int CLS, class OP>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows(const int32_t *rows, int32_t n, OP op)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    using T = vgl_rc_team<CLS>;
     int64_t acc = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
         int32_t v = 0, cx = 0, mn = INT_MAX, mx = INT_MIN;
         int64_t lo = 0, hi = 0;
-        if (i < n) {
+        if (has) {
             v = rows[i];
             cx = op.ctx(v);
             lo = op.rowptr[v]; hi = op.rowptr[v + 1];
         }
-        for (int64_t e = lo + gi; e < hi; e += VGL_RC_G) op.entry(v, cx, e, mn, mx);
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
-        if (gi == 0 && i < n) acc += op.finish(v, mn, mx);
-    }
-    if (op.counter()) vgl_wave_flush_add(op.counter(), acc);
-}
-template <class OP>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows_wave(OP op, const int32_t *rows, int32_t n)
-{
-    const int lane = vgl_lane();
-    int64_t acc = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = rows[i], cx = op.ctx(v);
-        const int64_t lo = op.rowptr[v], hi = op.rowptr[v + 1];
-        int32_t mn = INT_MAX, mx = INT_MIN;
-        for (int64_t e = lo + lane; e < hi; e += 64) op.entry(v, cx, e, mn, mx);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
-        if (lane == 0) acc += op.finish(v, mn, mx);
-    }
-    if (op.counter()) vgl_wave_flush_add(op.counter(), acc);
-}
-template <class OP>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bicc_rows_wg(OP op, const int32_t *rows, int32_t n)
-{
-    __shared__ int32_t s_mn[VGL_WAVES], s_mx[VGL_WAVES];
-    int64_t acc = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int32_t v = rows[i], cx = op.ctx(v);
-        const int64_t lo = op.rowptr[v], hi = op.rowptr[v + 1];
-        int32_t mn = INT_MAX, mx = INT_MIN;
-        for (int64_t e = lo + threadIdx.x; e < hi; e += VGL_BLOCK) op.entry(v, cx, e, mn, mx);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { mn = min(mn, __shfl_xor(mn, o)); mx = max(mx, __shfl_xor(mx, o)); }
-        __syncthreads();
-        if (vgl_lane() == 0) { s_mn[vgl_wave()] = mn; s_mx[vgl_wave()] = mx; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < VGL_WAVES; k++) { mn = min(mn, s_mn[k]); mx = max(mx, s_mx[k]); }
-            acc += op.finish(v, mn, mx);
-        }
+        for (int64_t e = lo + T::lane(); e < hi; e += T::LANES) op.entry(v, cx, e, mn, mx);
+        mn = T::min_of(mn);
+        mx = T::max_of(mx);
+        if (T::lead() && has) acc += op.finish(v, mn, mx);
     }
     if (op.counter()) vgl_wave_flush_add(op.counter(), acc);
 }
@@ -602,6 +547,7 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     std::vector<bi_level> levels;
     const char *const bfs_slot[VGL_RC_N] = {"bicc_bfs_short", "bicc_bfs_wave", "bicc_bfs_wg"};
     const char *const list_msg = "bicc_run: internal error (a class list longer than its class)";
+    const int64_t grid_cap[VGL_RC_N] = {BI_MAX_GRID, BI_MAX_GRID, BI_MAX_GRID};
     vgl_rc_window w;                             // the level: [head, tail) of the cumulative class lists
     VGL_TRY(w.advance(c->h_counters + BI_TAIL, cap, list_msg));
     for (;;) {
@@ -615,15 +561,8 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
         if ((int64_t)levels.size() >= V) VGL_FAIL("bicc_run: internal error (more levels than vertices)");
         levels.push_back(lv);
         t.next_level = (int32_t)levels.size();
-        VGL_TRY(vgl_rc_launch(c, bfs_slot, w, [&](int cls, int64_t n) {
-            const int32_t *rows = L.rows[cls] + w.head[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(vgl_k_bicc_bfs_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(vgl_k_bicc_bfs_wave, dim3(vgl_grid(n, VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
-            else
-                hipLaunchKernelGGL(vgl_k_bicc_bfs_wg, dim3(vgl_grid(n, 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)n);
-        }));
+        const int32_t *const rows[VGL_RC_N] = {L.rows[0] + w.head[0], L.rows[1] + w.head[1], L.rows[2] + w.head[2]};
+        VGL_TRY(vgl_rc_launch_trio(c, bfs_slot, w, grid_cap, vgl_k_bicc_bfs<VGL_RC_SHORT>, vgl_k_bicc_bfs<VGL_RC_WAVE>, vgl_k_bicc_bfs<VGL_RC_WG>, rows, t));
         VGL_TRY(read());
         VGL_TRY(w.advance(c->h_counters + BI_TAIL, cap, list_msg));
     }
@@ -659,15 +598,9 @@ int vgl_hip_bicc_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_edge_u, int32_
     const char *const local_slot[VGL_RC_N] = {"bicc_local_short", "bicc_local_wave", "bicc_local_wg"};
     const char *const art_slot[VGL_RC_N] = {"bicc_art_short", "bicc_art_wave", "bicc_art_wg"};
     auto rows_by_class = [&](auto op, const char *const *slot) -> int {
-        return vgl_rc_launch(c, slot, cap, [&](int cls, int64_t n) {
-            const int32_t *rows = L.rows[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(vgl_k_bicc_rows_short<decltype(op)>, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(vgl_k_bicc_rows_wave<decltype(op)>, dim3(vgl_grid(n, VGL_WAVES, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
-            else
-                hipLaunchKernelGGL(vgl_k_bicc_rows_wg<decltype(op)>, dim3(vgl_grid(n, 1, BI_MAX_GRID)), dim3(VGL_BLOCK), 0, st, op, rows, (int32_t)n);
-        });
+        using OP = decltype(op);
+        const int32_t *const rows[VGL_RC_N] = {L.rows[0], L.rows[1], L.rows[2]};
+        return vgl_rc_launch_trio(c, slot, cap, grid_cap, vgl_k_bicc_rows<VGL_RC_SHORT, OP>, vgl_k_bicc_rows<VGL_RC_WAVE, OP>, vgl_k_bicc_rows<VGL_RC_WG, OP>, rows, op);
     };
     {
         bi_local_op op;

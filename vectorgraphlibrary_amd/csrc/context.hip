@@ -269,7 +269,7 @@ static hipEvent_t vgl_get_event(vgl_hip_ctx *c)
 
 vgl_timed_launch::vgl_timed_launch(vgl_hip_ctx *c, const char *name) : ctx(c), slot(nullptr), a(nullptr), b(nullptr)
 {
-    if (!c->timing) return;
+    if (!c->timing || !name) return;                                     // (a launch without a slot is not timed)
     if (!c->timing_only.empty() && c->timing_only != name) return;      // only the named kernel pays for its two event records
     if (c->timing_stride > 1 && (c->timing_seen++ % c->timing_stride) != 0) return;          // ... and only every stride-th of its launches
     slot = &c->slots[name];

@@ -92,43 +92,21 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_classify(int32_t ne, k
         vgl_wave_append<VGL_RC_N>(want, (int32_t)e, want ? vgl_rc_class_of(kt_shorter((int32_t)e, g), g.b) : 0, g.L.list, g.L.cap, cnt + KT_TAIL);
     }
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup_short(kt_graph g, const int32_t *edges, int32_t n, unsigned long long *cnt)
+// a team per edge: its triangles
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup(const int32_t *edges, int32_t n, kt_graph g, unsigned long long *cnt)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    using T = vgl_rc_team<CLS>;
     int64_t sum = 0, walk = 0;
     int32_t mx = 0;
-    for (int64_t i = ((int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x) / VGL_RC_G; i < n; i += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {
-        const int32_t e = edges[i];
-        const kt_rows r = kt_rows_of(e, g);
-        int32_t t = kt_count(r, gi, VGL_RC_G, g.adj);
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) t += __shfl_xor(t, o);      // (the 8 lanes of a group leave the loop together)
-        if (gi == 0) { g.sup[e] = t; sum += t; walk += r.a_hi - r.a_lo; mx = max(mx, t); }
-    }
-    kt_support_done(cnt, sum, walk, mx);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup_wave(kt_graph g, const int32_t *edges, int32_t n, unsigned long long *cnt)
-{
-    int64_t sum = 0, walk = 0;
-    int32_t mx = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t e = edges[i];
-        const kt_rows r = kt_rows_of(e, g);
-        const int32_t t = vgl_wave_reduce_add(kt_count(r, vgl_lane(), 64, g.adj));
-        if (vgl_lane() == 0) { g.sup[e] = t; sum += t; walk += r.a_hi - r.a_lo; mx = max(mx, t); }
-    }
-    kt_support_done(cnt, sum, walk, mx);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_sup_wg(kt_graph g, const int32_t *edges, int32_t n, unsigned long long *cnt)
-{
-    __shared__ int32_t s_red[VGL_WAVES];
-    int64_t sum = 0, walk = 0;
-    int32_t mx = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int32_t e = edges[i];
-        const kt_rows r = kt_rows_of(e, g);
-        const int32_t t = vgl_block_reduce_add(kt_count(r, (int)threadIdx.x, VGL_BLOCK, g.adj), s_red);
-        if (threadIdx.x == 0) { g.sup[e] = t; sum += t; walk += r.a_hi - r.a_lo; mx = max(mx, t); }
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        const int32_t e = has ? edges[i] : 0;
+        kt_rows r{0, 0, 0, 0};
+        if (has) r = kt_rows_of(e, g);
+        const int32_t t = T::sum_of(kt_count(r, T::lane(), T::LANES, g.adj));
+        if (T::lead() && has) { g.sup[e] = t; sum += t; walk += r.a_hi - r.a_lo; mx = max(mx, t); }
     }
     kt_support_done(cnt, sum, walk, mx);
 }
@@ -212,35 +190,19 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_scan(int32_t ne, kt_gr
     }
     vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_short(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
+// a team per frontier edge
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_peel(const int32_t *edges, int32_t n, kt_graph g, int32_t k, int32_t s, unsigned long long *cnt)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    using T = vgl_rc_team<CLS>;
     int64_t m_acc = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
         const bool has = i < n;
         const int32_t e = has ? edges[i] : 0;
         kt_rows r{0, 0, 0, 0};
         if (has) r = kt_rows_of(e, g);
-        kt_expand(has, e, r, gi, VGL_RC_G, k, s, g, cnt + KT_TAIL, m_acc);
-    }
-    vgl_wave_flush_add(cnt + KT_M, m_acc);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wave(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
-{
-    int64_t m_acc = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t e = edges[i];
-        kt_expand(true, e, kt_rows_of(e, g), vgl_lane(), 64, k, s, g, cnt + KT_TAIL, m_acc);
-    }
-    vgl_wave_flush_add(cnt + KT_M, m_acc);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_ktruss_wg(kt_graph g, const int32_t *edges, int32_t n, int32_t k, int32_t s, unsigned long long *cnt)
-{
-    int64_t m_acc = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int32_t e = edges[i];
-        kt_expand(true, e, kt_rows_of(e, g), (int)threadIdx.x, VGL_BLOCK, k, s, g, cnt + KT_TAIL, m_acc);
+        kt_expand(has, e, r, T::lane(), T::LANES, k, s, g, cnt + KT_TAIL, m_acc);
     }
     vgl_wave_flush_add(cnt + KT_M, m_acc);
 }
@@ -321,16 +283,10 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
         return 0;
     };
     // a launch per class that has edges in [head, tail): the support pass and the peel have the same grids
+    const int64_t cap[VGL_RC_N] = {KT_MAX_GRID, KT_MAX_GRID, KT_MAX_GRID};
     auto per_class = [&](const char *const *slot, auto k_short, auto k_wave, auto k_wg, auto... args) -> int {
-        return vgl_rc_launch(c, slot, w, [&](int cls, int64_t n) {
-            const int32_t *edges = kg.L.list[cls] + w.head[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(k_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(k_wave, dim3(vgl_grid(n, VGL_WAVES, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
-            else
-                hipLaunchKernelGGL(k_wg, dim3(vgl_grid(n, 1, KT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, kg, edges, (int32_t)n, args...);
-        });
+        const int32_t *const edges[VGL_RC_N] = {kg.L.list[0] + w.head[0], kg.L.list[1] + w.head[1], kg.L.list[2] + w.head[2]};
+        return vgl_rc_launch_trio(c, slot, w, cap, k_short, k_wave, k_wg, edges, kg, args...);
     };
     const char *const sup_slot[VGL_RC_N] = {"ktruss_sup_short", "ktruss_sup_wave", "ktruss_sup_wg"};
     const char *const peel_slot[VGL_RC_N] = {"ktruss_short", "ktruss_wave", "ktruss_wg"};
@@ -343,7 +299,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(read());
     if (w.total() != ne) VGL_FAIL("ktruss_run: internal error (the classes do not add up to the edges)");
-    VGL_TRY(per_class(sup_slot, vgl_k_ktruss_sup_short, vgl_k_ktruss_sup_wave, vgl_k_ktruss_sup_wg, cnt.p));
+    VGL_TRY(per_class(sup_slot, vgl_k_ktruss_sup<VGL_RC_SHORT>, vgl_k_ktruss_sup<VGL_RC_WAVE>, vgl_k_ktruss_sup<VGL_RC_WG>, cnt.p));
     VGL_HIP_TRY(hipMemsetAsync(cnt.p + KT_TAIL, 0, sizeof(unsigned long long) * VGL_RC_N, st));      // the lists are the peel's from here on
     w = vgl_rc_window{};
     VGL_TRY(read());
@@ -383,7 +339,7 @@ int vgl_hip_ktruss_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_
         }
         // ---- one sub-round: a launch per class that has edges, then the read ----
         if (s == INT_MAX) VGL_FAIL("ktruss_run: more than 2^31 sub-rounds");
-        VGL_TRY(per_class(peel_slot, vgl_k_ktruss_short, vgl_k_ktruss_wave, vgl_k_ktruss_wg, k, s, cnt.p));
+        VGL_TRY(per_class(peel_slot, vgl_k_ktruss_peel<VGL_RC_SHORT>, vgl_k_ktruss_peel<VGL_RC_WAVE>, vgl_k_ktruss_peel<VGL_RC_WG>, k, s, cnt.p));
         VGL_TRY(read());
         s++;
         subs++;

@@ -41,40 +41,22 @@ enum {
 };
 static_assert(MIS_NCNT <= C_NSLOTS && MM_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-// the murmur3 finaliser: a bijection of uint32
-__host__ __device__ inline uint32_t mis_fmix32(uint32_t h)
-{
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
 // key(i, seed) = fmix32(i ^ mix), mix = fmix32(seed + 0x9e3779b9); or the caller's array
 struct mis_keys {
     const uint32_t *prio; uint32_t mix;
-    __device__ __forceinline__ uint32_t of(int32_t i) const { return prio ? prio[i] : mis_fmix32((uint32_t)i ^ mix); }
+    __device__ __forceinline__ uint32_t of(int32_t i) const { return prio ? prio[i] : vgl_fmix32((uint32_t)i ^ mix); }
 };
 
 // ---- the live lists: every vertex, by the length of its row ----
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis_count(int32_t V, const int32_t *deg, vgl_rc_bounds b, unsigned long long *rows)
-{
-    int64_t n[VGL_RC_N] = {0, 0, 0};
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) n[vgl_rc_class_of(deg[v], b)]++;
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(rows + c, n[c]);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis_fill(int32_t V, const int32_t *deg, vgl_rc_bounds b, vgl_rc_ring R0, vgl_rc_ring R1, vgl_rc_ring R2, unsigned long long *tail)
-{
-    const vgl_rc_ring R[VGL_RC_N] = {R0, R1, R2};
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
-        const int64_t v = base + threadIdx.x;
-        const int cls = v < V ? vgl_rc_class_of(deg[v], b) : -1;
-#pragma unroll
-        for (int c = 0; c < VGL_RC_N; c++) st[c].keep(cls == c, (int32_t)v, R[c], tail + c);
-    }
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(R[c], tail + c);
-}
+struct mis_row_src {
+    const int32_t *deg; vgl_rc_bounds b;
+    __device__ __forceinline__ int cls(int64_t v, int64_t &) const { return vgl_rc_class_of(deg[v], b); }
+};
+// the live rows of a class in a round: positions head, head + 1, ... of its ring
+struct mis_live {
+    vgl_rc_ring R; unsigned long long head;
+    __device__ __forceinline__ int32_t at(int64_t i) const { return R.rows[(head + (unsigned long long)i) % R.cap]; }
+};
 
 // ---- maximal independent set ----
 struct mis_graph {
@@ -101,93 +83,42 @@ __device__ __forceinline__ bool mis_decide(const mis_graph &g, int32_t v, int bi
     in++;
     return false;
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis_short(mis_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, int32_t r, unsigned long long *cnt)
+// a team per row; the wave's scan stops at the first earlier neighbour that is IN
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis(mis_live l, int32_t n, mis_graph g, int32_t r, unsigned long long *cnt)
 {
+    using T = vgl_rc_team<CLS>;
     vgl_rc_stage st[1];
     vgl_rc_stage_open(st);
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t walked = 0, in = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
         int32_t v = 0;
         uint32_t kv = 0;
         int64_t lo = 0, hi = 0;
-        if (i < n) {
-            v = R.rows[(head + (unsigned long long)i) % R.cap];
+        if (has) {
+            v = l.at(i);
             kv = g.key.of(v);
             lo = g.rowptr[v]; hi = g.rowptr[v + 1];
         }
         int bits = 0;
-        for (int64_t e = lo + gi; e < hi; e += VGL_RC_G) bits |= mis_look(g, v, kv, g.adj[e], r);
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) bits |= __shfl_xor(bits, o);
+        if constexpr (CLS == VGL_RC_WAVE) {
+            for (int64_t e = lo; e < hi; e += T::LANES) {             // (uniform over the wave)
+                if (e + T::lane() < hi) bits |= mis_look(g, v, kv, g.adj[e + T::lane()], r);
+                if (__any(bits & 1)) break;
+            }
+        } else
+            for (int64_t e = lo + T::lane(); e < hi; e += T::LANES) bits |= mis_look(g, v, kv, g.adj[e], r);
+        bits = T::or_of(bits, 2);
         bool again = false;
-        if (gi == 0 && i < n) {
+        if (T::lead() && has) {
             walked += hi - lo;
             again = mis_decide(g, v, bits, r, in);
         }
-        st[0].keep(again, v, R, cnt + MIS_TAIL + VGL_RC_SHORT);
+        st[0].keep(again, v, l.R, cnt + MIS_TAIL + CLS);
     }
-    st[0].flush(R, cnt + MIS_TAIL + VGL_RC_SHORT);
-    vgl_wave_flush_add(cnt + MIS_WALK, walked);
-    vgl_wave_flush_add(cnt + MIS_IN, in);
-}
-// a wavefront per row; the scan stops at the first earlier neighbour that is IN
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis_wave(mis_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, int32_t r, unsigned long long *cnt)
-{
-    vgl_rc_stage st[1];
-    vgl_rc_stage_open(st);
-    const int lane = vgl_lane();
-    int64_t walked = 0, in = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
-        const uint32_t kv = g.key.of(v);
-        const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
-        int bits = 0;
-        for (int64_t e = lo; e < hi; e += 64) {                       // (uniform over the wave)
-            if (e + lane < hi) bits |= mis_look(g, v, kv, g.adj[e + lane], r);
-            if (__any(bits & 1)) break;
-        }
-        bits = (__any(bits & 1) ? 1 : 0) | (__any(bits & 2) ? 2 : 0);
-        bool again = false;
-        if (lane == 0) {
-            walked += hi - lo;
-            again = mis_decide(g, v, bits, r, in);
-        }
-        st[0].keep(again, v, R, cnt + MIS_TAIL + VGL_RC_WAVE);
-    }
-    st[0].flush(R, cnt + MIS_TAIL + VGL_RC_WAVE);
-    vgl_wave_flush_add(cnt + MIS_WALK, walked);
-    vgl_wave_flush_add(cnt + MIS_IN, in);
-}
-// a workgroup per row
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mis_wg(mis_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, int32_t r, unsigned long long *cnt)
-{
-    __shared__ int s_bits;
-    vgl_rc_stage st[1];
-    vgl_rc_stage_open(st);
-    int64_t walked = 0, in = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        if (threadIdx.x == 0) s_bits = 0;
-        __syncthreads();
-        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
-        const uint32_t kv = g.key.of(v);
-        const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
-        int bits = 0;
-        for (int64_t e = lo + threadIdx.x; e < hi; e += VGL_BLOCK) bits |= mis_look(g, v, kv, g.adj[e], r);
-        bits = (__any(bits & 1) ? 1 : 0) | (__any(bits & 2) ? 2 : 0);
-        if (vgl_lane() == 0 && bits) atomicOr(&s_bits, bits);
-        __syncthreads();
-        bits = s_bits;
-        __syncthreads();
-        bool again = false;
-        if (threadIdx.x == 0) {
-            walked += hi - lo;
-            again = mis_decide(g, v, bits, r, in);
-        }
-        st[0].keep(again, v, R, cnt + MIS_TAIL + VGL_RC_WG);
-    }
-    st[0].flush(R, cnt + MIS_TAIL + VGL_RC_WG);
+    st[0].flush(l.R, cnt + MIS_TAIL + CLS);
     vgl_wave_flush_add(cnt + MIS_WALK, walked);
     vgl_wave_flush_add(cnt + MIS_IN, in);
 }
@@ -205,12 +136,6 @@ struct mm_graph {
     const int32_t *mate;
     unsigned long long *best;
 };
-__device__ __forceinline__ unsigned long long mm_wave_min(unsigned long long m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
-    return m;
-}
 // the smallest  key << 32 | edge  over the entries lo, lo + stride, ... < hi whose far end is unmatched
 __device__ __forceinline__ unsigned long long mm_walk(int64_t lo, int64_t hi, int stride, const mm_graph &g)
 {
@@ -222,72 +147,28 @@ __device__ __forceinline__ unsigned long long mm_walk(int64_t lo, int64_t hi, in
         }
     return m;
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mm_best_short(mm_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, vgl_rc_ring cand, unsigned long long *cnt)
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mm_best(mis_live l, int32_t n, mm_graph g, vgl_rc_ring cand, unsigned long long *cnt)
 {
+    using T = vgl_rc_team<CLS>;
     vgl_rc_stage st[1];
     vgl_rc_stage_open(st);
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
     int64_t walked = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n, lead = T::lead() && has;
         int32_t v = 0;
         int64_t lo = 0, hi = 0;
-        if (i < n) {
-            v = R.rows[(head + (unsigned long long)i) % R.cap];
+        if (has) {
+            v = l.at(i);
             lo = g.rowptr[v]; hi = g.rowptr[v + 1];
         }
-        unsigned long long m = mm_walk(lo + gi, hi, VGL_RC_G, g);
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
-        const bool lead = gi == 0 && i < n;
+        const unsigned long long m = T::min_of(mm_walk(lo + T::lane(), hi, T::LANES, g));
         if (lead) {
             walked += hi - lo;
             g.best[v] = m;
         }
         st[0].keep(lead && m != MM_NONE, v, cand, cnt + MM_CAND);
-    }
-    st[0].flush(cand, cnt + MM_CAND);
-    vgl_wave_flush_add(cnt + MM_WALK, walked);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mm_best_wave(mm_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, vgl_rc_ring cand, unsigned long long *cnt)
-{
-    vgl_rc_stage st[1];
-    vgl_rc_stage_open(st);
-    const int lane = vgl_lane();
-    int64_t walked = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
-        const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
-        const unsigned long long m = mm_wave_min(mm_walk(lo + lane, hi, 64, g));
-        if (lane == 0) {
-            walked += hi - lo;
-            g.best[v] = m;
-        }
-        st[0].keep(lane == 0 && m != MM_NONE, v, cand, cnt + MM_CAND);
-    }
-    st[0].flush(cand, cnt + MM_CAND);
-    vgl_wave_flush_add(cnt + MM_WALK, walked);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mm_best_wg(mm_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, vgl_rc_ring cand, unsigned long long *cnt)
-{
-    __shared__ unsigned long long s_red[VGL_WAVES];
-    vgl_rc_stage st[1];
-    vgl_rc_stage_open(st);
-    int64_t walked = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
-        const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
-        unsigned long long m = mm_wave_min(mm_walk(lo + threadIdx.x, hi, VGL_BLOCK, g));
-        __syncthreads();
-        if (vgl_lane() == 0) s_red[vgl_wave()] = m;
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < VGL_WAVES; k++) m = min(m, s_red[k]);
-        if (threadIdx.x == 0) {
-            walked += hi - lo;
-            g.best[v] = m;
-        }
-        st[0].keep(threadIdx.x == 0 && m != MM_NONE, v, cand, cnt + MM_CAND);
     }
     st[0].flush(cand, cnt + MM_CAND);
     vgl_wave_flush_add(cnt + MM_WALK, walked);
@@ -331,41 +212,26 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_mm_match(int32_t r, const uns
 
 // ---- host: the rings of a run ----
 struct mis_lists {
-    vgl_dev<int32_t> mem;
-    vgl_rc_ring R[VGL_RC_N];
+    vgl_rc_lists<vgl_rc_ring> L;
     vgl_rc_window w;
+    // the live rows of the round, per class
+    void live(mis_live (&l)[VGL_RC_N]) const
+    {
+        for (int k = 0; k < VGL_RC_N; k++) l[k] = mis_live{L.l[k], (unsigned long long)w.head[k]};
+    }
 };
+const int64_t mis_grid_cap[VGL_RC_N] = {MIS_MAX_GRID, MIS_MAX_GRID, 4 * MIS_MAX_GRID};      // workgroups of a class's launch at most
 // every vertex into the ring of its class (cnt + tail0: the three tails; cnt + rows0: the three row counts); one host read
 int mis_open_lists(vgl_hip_ctx *c, int32_t V, const int32_t *deg, vgl_rc_bounds b, unsigned long long *cnt, int tail0, int rows0, int ncnt, const char *slot_init, const char *slot_publish,
-                   mis_lists *L)
+                   mis_lists *M)
 {
-    hipStream_t st = c->stream;
-    {
-        vgl_timed_launch tl(c, slot_init);
-        hipLaunchKernelGGL(vgl_k_mis_count, dim3(vgl_grid(V, VGL_BLOCK, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, deg, b, cnt + rows0);
-    }
-    VGL_HIP_TRY(hipGetLastError());
-    VGL_TRY(vgl_publish_counters(c, slot_publish, cnt, ncnt));
-    int64_t rows[VGL_RC_N], total = 0;
-    for (int k = 0; k < VGL_RC_N; k++) {
-        rows[k] = c->h_counters[rows0 + k];
-        if (rows[k] < 0 || rows[k] > V) VGL_FAIL("mis: internal error (more rows in a class than vertices)");
-        total += rows[k];
-    }
-    if (total != V) VGL_FAIL("mis: internal error (the classes do not add up to the vertices)");
-    VGL_TRY(L->mem.alloc(st, (size_t)(2 * total)));
-    int64_t off = 0;
-    for (int k = 0; k < VGL_RC_N; k++) {
-        L->R[k].rows = L->mem.p + off;
-        L->R[k].cap = (uint32_t)(2 * rows[k]);
-        off += 2 * rows[k];
-        L->w.tail[k] = rows[k];
-    }
-    {
-        vgl_timed_launch tl(c, slot_init);
-        hipLaunchKernelGGL(vgl_k_mis_fill, dim3(vgl_grid(V, VGL_BLOCK, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, deg, b, L->R[0], L->R[1], L->R[2], cnt + tail0);
-    }
-    VGL_HIP_TRY(hipGetLastError());
+    const mis_row_src src{deg, b};
+    VGL_TRY(M->L.count(c, slot_init, slot_publish, src, V, MIS_MAX_GRID, cnt, ncnt, rows0, -1, -1, -1, nullptr, "mis: internal error (the classes do not add up to the vertices)"));
+    for (int k = 0; k < VGL_RC_N; k++)
+        if (M->L.rows[k] > V) VGL_FAIL("mis: internal error (more rows in a class than vertices)");
+    if (M->L.rows[0] + M->L.rows[1] + M->L.rows[2] != V) VGL_FAIL("mis: internal error (the classes do not add up to the vertices)");
+    VGL_TRY(M->L.fill(c, slot_init, src, V, MIS_MAX_GRID, 2, nullptr, cnt + tail0));
+    for (int k = 0; k < VGL_RC_N; k++) M->w.tail[k] = M->L.rows[k];
     return 0;
 }
 // the round is done: the new tails from the mirror; a live list never grows
@@ -427,7 +293,7 @@ int vgl_hip_mis_run(vgl_hip_ctx *c, vgl_hip_graph *g, const uint32_t *d_priority
     VGL_TRY(mis_open_lists(c, V, csr->deg, b, cnt, MIS_TAIL, MIS_ROWS, MIS_NCNT, "mis_init", "mis_publish", &L));
 
     mis_graph mg;
-    mg.rowptr = csr->rowptr; mg.adj = csr->adj; mg.key = mis_keys{d_priority, mis_fmix32(seed + 0x9e3779b9u)}; mg.state = state;
+    mg.rowptr = csr->rowptr; mg.adj = csr->adj; mg.key = mis_keys{d_priority, vgl_fmix32(seed + 0x9e3779b9u)}; mg.state = state;
     const char *const slot[VGL_RC_N] = {"mis_short", "mis_wave", "mis_wg"};
     int32_t rounds = 0;
     int64_t live_total = 0;
@@ -435,15 +301,9 @@ int vgl_hip_mis_run(vgl_hip_ctx *c, vgl_hip_graph *g, const uint32_t *d_priority
         if (rounds >= V) VGL_FAIL("mis_run: internal error (more rounds than vertices)");
         rounds++;
         live_total += L.w.live();
-        VGL_TRY(vgl_rc_launch(c, slot, L.w, [&](int cls, int64_t n) {
-            const unsigned long long head = (unsigned long long)L.w.head[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(vgl_k_mis_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, rounds, cnt.p);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(vgl_k_mis_wave, dim3(vgl_grid(n, VGL_WAVES, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, rounds, cnt.p);
-            else
-                hipLaunchKernelGGL(vgl_k_mis_wg, dim3(vgl_grid(n, 1, 4 * MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, rounds, cnt.p);
-        }));
+        mis_live rows[VGL_RC_N];
+        L.live(rows);
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.w, mis_grid_cap, vgl_k_mis<VGL_RC_SHORT>, vgl_k_mis<VGL_RC_WAVE>, vgl_k_mis<VGL_RC_WG>, rows, mg, rounds, cnt.p));
         VGL_TRY(vgl_publish_counters(c, "mis_publish", cnt, MIS_NCNT));
         VGL_TRY(mis_advance(c, L.w, MIS_TAIL));
     }
@@ -522,7 +382,7 @@ int vgl_hip_matching_run(vgl_hip_ctx *c, vgl_hip_graph *g, const uint32_t *d_edg
     VGL_TRY(mis_open_lists(c, V, csr->deg, b, cnt, MM_TAIL, MM_ROWS, MM_NCNT, "mm_init", "mm_publish", &L));
 
     mm_graph mg;
-    mg.rowptr = csr->rowptr; mg.adj = csr->adj; mg.eid = sg->eid; mg.key = mis_keys{d_edge_priority, mis_fmix32(seed + 0x9e3779b9u)}; mg.mate = mate; mg.best = best;
+    mg.rowptr = csr->rowptr; mg.adj = csr->adj; mg.eid = sg->eid; mg.key = mis_keys{d_edge_priority, vgl_fmix32(seed + 0x9e3779b9u)}; mg.mate = mate; mg.best = best;
     const vgl_rc_ring cand{cand_mem.p, (uint32_t)V};
     const mm_out mo{mate, d_round, d_in_matching};
     const char *const slot[VGL_RC_N] = {"mm_best_short", "mm_best_wave", "mm_best_wg"};
@@ -533,19 +393,13 @@ int vgl_hip_matching_run(vgl_hip_ctx *c, vgl_hip_graph *g, const uint32_t *d_edg
         rounds++;
         const int64_t live = L.w.live();
         live_total += live;
-        VGL_TRY(vgl_rc_launch(c, slot, L.w, [&](int cls, int64_t n) {
-            const unsigned long long head = (unsigned long long)L.w.head[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(vgl_k_mm_best_short, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, cand, cnt.p);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(vgl_k_mm_best_wave, dim3(vgl_grid(n, VGL_WAVES, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, cand, cnt.p);
-            else
-                hipLaunchKernelGGL(vgl_k_mm_best_wg, dim3(vgl_grid(n, 1, 4 * MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, L.R[cls], head, (int32_t)n, cand, cnt.p);
-        }));
+        mis_live rows[VGL_RC_N];
+        L.live(rows);
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.w, mis_grid_cap, vgl_k_mm_best<VGL_RC_SHORT>, vgl_k_mm_best<VGL_RC_WAVE>, vgl_k_mm_best<VGL_RC_WG>, rows, mg, cand, cnt.p));
         {
             vgl_timed_launch tl(c, "mm_match");
             hipLaunchKernelGGL(vgl_k_mm_match, dim3(vgl_grid(live, VGL_BLOCK, MIS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, rounds, (const unsigned long long *)best.p, sg->eu, sg->ev, csr->deg, b, mo,
-                               cand, (unsigned long long)cand_head, L.R[0], L.R[1], L.R[2], cnt.p);
+                               cand, (unsigned long long)cand_head, L.L.l[0], L.L.l[1], L.L.l[2], cnt.p);
         }
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_publish_counters(c, "mm_publish", cnt, MM_NCNT));

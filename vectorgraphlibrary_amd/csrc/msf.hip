@@ -60,13 +60,6 @@ __device__ __forceinline__ uint32_t msf_key_of(float w)
 }
 __device__ __forceinline__ float msf_weight_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-__device__ __forceinline__ unsigned long long msf_wave_min(unsigned long long m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o));
-    return m;
-}
-
 // ---- fold ----
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_fold(int64_t E, const int32_t *slot_eid, const float *w, uint32_t *wkey, unsigned long long *cnt)
 {
@@ -87,35 +80,16 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_edge_weight(int32_t ne, c
 
 // ---- the live lists ----
 // (appends: vgl_rc_stage onto the ring of the class, one returning atomic per 64 or more rows)
-// rows with an entry, per class
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_count(int32_t V, const int32_t *deg, vgl_rc_bounds b, unsigned long long *cnt)
-{
-    int64_t n[VGL_RC_N] = {0, 0, 0};
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
+// the rows with an entry, by their length; the filling pass (comp != nullptr) also sets comp[v] = v for every vertex
+struct msf_row_src {
+    const int32_t *deg; vgl_rc_bounds b; int32_t *comp;
+    __device__ __forceinline__ int cls(int64_t v, int64_t &) const
+    {
+        if (comp) comp[v] = (int32_t)v;
         const int32_t d = deg[v];
-        if (d > 0) n[vgl_rc_class_of(d, b)]++;
+        return d > 0 ? vgl_rc_class_of(d, b) : -1;
     }
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(cnt + MSF_ROWS + c, n[c]);
-}
-// comp[v] = v; the rows with an entry into the ring of their class
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_init(int32_t V, const int32_t *deg, vgl_rc_bounds b, int32_t *comp, vgl_rc_ring R0, vgl_rc_ring R1, vgl_rc_ring R2,
-                                                             unsigned long long *cnt)
-{
-    const vgl_rc_ring R[VGL_RC_N] = {R0, R1, R2};
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < V; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
-        const int64_t v = base + threadIdx.x;
-        int32_t d = 0;
-        if (v < V) { d = deg[v]; comp[v] = (int32_t)v; }
-        const int cls = vgl_rc_class_of(d, b);
-#pragma unroll
-        for (int c = 0; c < VGL_RC_N; c++) st[c].keep(d > 0 && cls == c, (int32_t)v, R[c], cnt + MSF_TAIL + c);
-    }
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(R[c], cnt + MSF_TAIL + c);
-}
+};
 
 // ---- the min-edge pass ----
 // the smallest key over the entries lo, lo + stride, ... < hi whose far end lies in another component than cv
@@ -160,7 +134,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_short(msf_graph g, vg
             const int leader = __ffsll((long long)f) - 1;
             const int32_t c0 = __shfl(cv, leader);
             const bool same = found && cv == c0;
-            const unsigned long long k0 = msf_wave_min(same ? m : MSF_NONE);
+            const unsigned long long k0 = vgl_rc_team<VGL_RC_WAVE>::min_of(same ? m : MSF_NONE);
             if (lane == leader) msf_offer(g.best + c0, k0);
             else if (found && !same) msf_offer(g.best + cv, m);
         }
@@ -179,7 +153,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, vgl
         const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
         const int32_t cv = g.comp[v];
         const int64_t lo = g.rowptr[v], hi = g.rowptr[v + 1];
-        const unsigned long long m = msf_wave_min(msf_walk(lo + lane, hi, 64, cv, g));
+        const unsigned long long m = vgl_rc_team<VGL_RC_WAVE>::min_of(msf_walk(lo + lane, hi, 64, cv, g));
         const bool found = lane == 0 && m != MSF_NONE;
         if (lane == 0) walked += hi - lo;
         if (found) msf_offer(g.best + cv, m);
@@ -203,7 +177,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, vgl_r
         if (lo >= end) continue;
         const int64_t hi = min(end, lo + chunk);
         const int32_t cv = g.comp[v];
-        unsigned long long m = msf_wave_min(msf_walk(lo + threadIdx.x, hi, VGL_BLOCK, cv, g));
+        unsigned long long m = vgl_rc_team<VGL_RC_WAVE>::min_of(msf_walk(lo + threadIdx.x, hi, VGL_BLOCK, cv, g));
         __syncthreads();
         if (vgl_lane() == 0) s_red[vgl_wave()] = m;
         __syncthreads();
@@ -402,7 +376,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     VGL_HIP_TRY(hipMemsetAsync(d_in_forest, 0, (size_t)ne, st));
 
     // ---- scratch of the call, all of it drawn before the loop ----
-    vgl_dev<int32_t> comp, parent, root, lists, stamp;
+    vgl_dev<int32_t> comp, parent, root, stamp;
     vgl_dev<unsigned long long> best;
     vgl_dev<double> partials;
     const int sum_grid = (int)vgl_grid(ne, VGL_BLOCK, MSF_SUM_GRID);
@@ -412,30 +386,19 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     VGL_TRY(best.alloc(st, (size_t)V));
     VGL_TRY(partials.alloc(st, (size_t)sum_grid + 1));
     VGL_HIP_TRY(hipMemsetAsync(best, 0xFF, sizeof(unsigned long long) * (size_t)V, st));      // MSF_NONE
-    hipLaunchKernelGGL(vgl_k_msf_count, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b, cnt.p);
-    VGL_HIP_TRY(hipGetLastError());
-    VGL_TRY(read());
-    int64_t rows[VGL_RC_N], rows_total = 0;
-    for (int k = 0; k < VGL_RC_N; k++) {
-        rows[k] = c->h_counters[MSF_ROWS + k];
-        if (rows[k] < 0 || rows[k] > V) VGL_FAIL("msf_run: internal error (more rows in a class than vertices)");
-        rows_total += rows[k];
-    }
+    vgl_rc_lists<vgl_rc_ring> L;                 // one ring per class, of twice the class's rows
+    msf_row_src src{sg->csr.deg, b, nullptr};
+    VGL_TRY(L.count(c, nullptr, "msf_publish", src, V, MSF_MAX_GRID, cnt.p, MSF_NCNT, MSF_ROWS, -1, -1, -1, nullptr,
+                    "msf_run: internal error (the classes do not add up to the rows that have an entry)"));
+    const int64_t *rows = L.rows, rows_total = rows[0] + rows[1] + rows[2];
+    for (int k = 0; k < VGL_RC_N; k++)
+        if (rows[k] > V) VGL_FAIL("msf_run: internal error (more rows in a class than vertices)");
     if (rows_total < 2 || rows_total > V) VGL_FAIL("msf_run: internal error (the classes do not add up to the rows that have an entry)");
-    VGL_TRY(lists.alloc(st, (size_t)(2 * rows_total)));
     VGL_TRY(stamp.alloc(st, (size_t)rows[VGL_RC_WG]));
     VGL_HIP_TRY(hipMemsetAsync(stamp, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(rows[VGL_RC_WG], 1), st));
-    vgl_rc_ring R[VGL_RC_N];
-    {
-        int64_t off = 0;
-        for (int k = 0; k < VGL_RC_N; k++) {
-            R[k].rows = lists.p + off;
-            R[k].cap = (uint32_t)(2 * rows[k]);
-            off += 2 * rows[k];
-        }
-    }
-    hipLaunchKernelGGL(vgl_k_msf_init, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, sg->csr.deg, b, comp.p, R[0], R[1], R[2], cnt.p);
-    VGL_HIP_TRY(hipGetLastError());
+    src.comp = comp.p;
+    VGL_TRY(L.fill(c, nullptr, src, V, MSF_MAX_GRID, 2, nullptr, cnt + MSF_TAIL));
+    const vgl_rc_ring *R = L.l;
 
     msf_graph mg;
     mg.rowptr = sg->csr.rowptr; mg.adj = sg->csr.adj; mg.eid = sg->eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;

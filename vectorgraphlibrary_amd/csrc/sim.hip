@@ -64,7 +64,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_check_weights(int32_t V, 
     vgl_wave_flush_add(bad, n);
 }
 
-// ---- the class lists: items 0 .. n - 1 of a source S; S::cls(i, work) = the class of item i and its work, or -1 for a vertex out of range ----
+// ---- the class lists (vgl_rc_lists): cls(i, work) = the class of item i and its work, or -1 for a vertex out of range ----
 struct sim_pair_src {
     const int32_t *u, *v;
     int32_t V;
@@ -91,37 +91,6 @@ struct sim_query_src {
         return work <= small ? SIM_SMALL : work <= table ? SIM_TABLE : SIM_GLOBAL;
     }
 };
-template <class S>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_count(S s, int64_t n, unsigned long long *cnt)
-{
-    int64_t rows[VGL_RC_N] = {0, 0, 0}, bad = 0, work = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
-        int64_t w = 0;
-        const int c = s.cls(i, w);
-        if (c < 0) bad++;
-        else { rows[c]++; work += w; }
-    }
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(cnt + SIM_ROWS + c, rows[c]);
-    vgl_wave_flush_add(cnt + SIM_BAD, bad);
-    vgl_wave_flush_add(cnt + SIM_WORK, work);
-}
-template <class S>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_fill(S s, int64_t n, vgl_rc_bounded L0, vgl_rc_bounded L1, vgl_rc_bounded L2, unsigned long long *tail)
-{
-    const vgl_rc_bounded L[VGL_RC_N] = {L0, L1, L2};
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x;
-        int64_t w = 0;
-        const int cls = i < n ? s.cls(i, w) : -1;
-#pragma unroll
-        for (int c = 0; c < VGL_RC_N; c++) st[c].keep(cls == c, (int32_t)i, L[c], tail + c);
-    }
-#pragma unroll
-    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(L[c], tail + c);
-}
 
 // ---- pairs ----
 struct sim_pairs_args {
@@ -133,16 +102,6 @@ struct sim_pairs_args {
     double *weighted;            // of this chunk, or nullptr
     unsigned long long *cnt;
 };
-// x in adj[s, s + n) (ascending, no duplicates)?
-__device__ __forceinline__ bool sim_contains(const int32_t *adj, int64_t s, int n, int32_t x)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (adj[s + mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo < n && adj[s + lo] == x;
-}
 // the rows of pair p: the shorter one (ss, sn) and the longer one (ls, ln); u's row is the shorter one when they are equally long
 struct sim_rows { int64_t ss, ls; int sn, ln; };
 __device__ __forceinline__ sim_rows sim_rows_of(const sim_pairs_args &a, int64_t p)
@@ -158,77 +117,32 @@ __device__ __forceinline__ void sim_walk(const sim_pairs_args &a, const sim_rows
 {
     for (int i = first; i < r.sn; i += stride) {
         const int32_t x = a.adj[r.ss + i];
-        if (sim_contains(a.adj, r.ls, r.ln, x)) {
+        if (vgl_contains(a.adj, r.ls, r.ln, x)) {
             hits++;
             if (W) sum += a.weight[x];
         }
     }
 }
-template <bool W>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_pairs_short(sim_pairs_args a, const int32_t *list, int32_t n)
+template <int CLS, bool W>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_pairs(const int32_t *list, int32_t n, sim_pairs_args a)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    using T = vgl_rc_team<CLS>;
     int64_t total = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
         int64_t p = 0;
         sim_rows r{0, 0, 0, 0};
-        if (i < n) {
+        if (has) {
             p = list[i];
             r = sim_rows_of(a, p);
         }
         int hits = 0;
         double sum = 0.0;
-        sim_walk<W>(a, r, gi, VGL_RC_G, hits, sum);
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) {
-            hits += __shfl_xor(hits, o);
-            if (W) sum += __shfl_xor(sum, o);
-        }
-        if (gi == 0 && i < n) {
-            total += hits;
-            if (a.common) a.common[p] = hits;
-            if (W) a.weighted[p] = sum;
-        }
-    }
-    vgl_wave_flush_add(a.cnt + SIM_COMMON, total);
-}
-template <bool W>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_pairs_wave(sim_pairs_args a, const int32_t *list, int32_t n)
-{
-    const int lane = vgl_lane();
-    int64_t total = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int64_t p = list[i];
-        const sim_rows r = sim_rows_of(a, p);
-        int hits = 0;
-        double sum = 0.0;
-        sim_walk<W>(a, r, lane, 64, hits, sum);
-        hits = vgl_wave_reduce_add(hits);
-        if (W) sum = vgl_wave_reduce_add(sum);
-        if (lane == 0) {
-            total += hits;
-            if (a.common) a.common[p] = hits;
-            if (W) a.weighted[p] = sum;
-        }
-    }
-    vgl_wave_flush_add(a.cnt + SIM_COMMON, total);
-}
-template <bool W>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_pairs_wg(sim_pairs_args a, const int32_t *list, int32_t n)
-{
-    __shared__ int s_hits[VGL_WAVES];
-    __shared__ double s_sum[VGL_WAVES];
-    int64_t total = 0;
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const int64_t p = list[i];
-        const sim_rows r = sim_rows_of(a, p);
-        int hits = 0;
-        double sum = 0.0;
-        sim_walk<W>(a, r, (int)threadIdx.x, VGL_BLOCK, hits, sum);
-        hits = vgl_block_reduce_add(hits, s_hits);
-        if (W) sum = vgl_block_reduce_add(sum, s_sum);                // (the waves' sums, added in wave order)
-        if (threadIdx.x == 0) {
+        sim_walk<W>(a, r, T::lane(), T::LANES, hits, sum);
+        hits = T::sum_of(hits);
+        if (W) sum = T::sum_of(sum);                                  // (the workgroup: the waves' sums, added in wave order)
+        if (T::lead() && has) {
             total += hits;
             if (a.common) a.common[p] = hits;
             if (W) a.weighted[p] = sum;
@@ -264,7 +178,6 @@ __device__ __forceinline__ sim_cand sim_cand_of(const sim_topk_args &a, int32_t 
     const int32_t den = a.metric == VGL_HIP_SIM_COMMON ? 1 : a.metric == VGL_HIP_SIM_JACCARD ? du + dw - c : min(du, dw);
     return sim_cand{c, den, a.label ? a.label[w] : w, w};
 }
-__device__ __forceinline__ uint32_t sim_hash(int32_t x, int bits) { return ((uint32_t)x * 0x9E3779B1u) >> (32 - bits); }
 
 // where the counted candidates of a row live: entry i of n is the vertex w with c common neighbours (c <= 0: no candidate)
 struct sim_table_src {
@@ -356,7 +269,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_topk_table(sim_topk_args 
             const int64_t sv = a.rowptr[v], dv = a.rowptr[v + 1] - sv;
             for (int64_t p = gi; p < dv; p += SIM_TG) {
                 const int32_t w = a.adj[sv + p];
-                uint32_t h = sim_hash(w, bits);
+                uint32_t h = vgl_hash(w, bits);
                 for (uint32_t t = 0; t <= mask; t++) {                // (the table is at most half full: a free slot comes long before the bound)
                     const int32_t old = atomicCAS(&s_id[h], -1, w);
                     if (old == -1 || old == w) { atomicAdd(&s_cnt[h], 1); break; }
@@ -368,7 +281,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sim_topk_table(sim_topk_args 
         // struck out: u itself (a 2-path u - v - u per neighbour) and, for link prediction, the neighbours
         for (int64_t j = (int64_t)threadIdx.x - 1; j < (a.include ? 0 : du); j += VGL_BLOCK) {
             const int32_t w = j < 0 ? u : a.adj[su + j];
-            uint32_t h = sim_hash(w, bits);
+            uint32_t h = vgl_hash(w, bits);
             for (uint32_t t = 0; t <= mask; t++) {
                 const int32_t x = s_id[h];
                 if (x == -1) break;
@@ -458,49 +371,8 @@ int sim_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, const vgl_simple_cache **sc, co
     return 0;
 }
 
-// the counters of a call, all 0
-int sim_open_counters(vgl_hip_ctx *c, vgl_dev<unsigned long long> *cnt)
-{
-    VGL_TRY(cnt->alloc(c->stream, SIM_NCNT));
-    VGL_HIP_TRY(hipMemsetAsync(cnt->p, 0, sizeof(unsigned long long) * SIM_NCNT, c->stream));
-    return 0;
-}
-
-// items 0 .. n - 1 of `src` into the three lists at mem + off[k] (rows[k] of them each, as the counting pass found)
-template <class S>
-int sim_fill_lists(vgl_hip_ctx *c, const S &src, int64_t n, int32_t *mem, const int64_t rows[VGL_RC_N], int64_t off[VGL_RC_N], unsigned long long *cnt)
-{
-    VGL_HIP_TRY(hipMemsetAsync(cnt + SIM_TAIL, 0, sizeof(unsigned long long) * VGL_RC_N, c->stream));
-    vgl_rc_bounded L[VGL_RC_N];
-    int64_t at = 0;
-    for (int k = 0; k < VGL_RC_N; k++) {
-        off[k] = at;
-        L[k] = vgl_rc_bounded{mem + at, (int32_t)rows[k]};
-        at += rows[k];
-    }
-    {
-        vgl_timed_launch tl(c, "sim_classify");
-        hipLaunchKernelGGL(vgl_k_sim_fill<S>, dim3(vgl_grid(n, VGL_BLOCK, SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, src, n, L[0], L[1], L[2], cnt + SIM_TAIL);
-    }
-    VGL_HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-template <bool W>
-int sim_pairs_launch(vgl_hip_ctx *c, const sim_pairs_args &a, const int32_t *mem, const int64_t rows[VGL_RC_N], const int64_t off[VGL_RC_N])
-{
-    const char *const slot[VGL_RC_N] = {"sim_pairs_short", "sim_pairs_wave", "sim_pairs_wg"};
-    hipStream_t st = c->stream;
-    return vgl_rc_launch(c, slot, rows, [&](int cls, int64_t n) {
-        const int32_t *list = mem + off[cls];
-        if (cls == VGL_RC_SHORT)
-            hipLaunchKernelGGL(vgl_k_sim_pairs_short<W>, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, 4 * SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n);
-        else if (cls == VGL_RC_WAVE)
-            hipLaunchKernelGGL(vgl_k_sim_pairs_wave<W>, dim3(vgl_grid(n, VGL_WAVES, 4 * SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n);
-        else
-            hipLaunchKernelGGL(vgl_k_sim_pairs_wg<W>, dim3(vgl_grid(n, 1, 4 * SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n);
-    });
-}
+const int64_t sim_pairs_cap[VGL_RC_N] = {4 * SIM_MAX_GRID, 4 * SIM_MAX_GRID, 4 * SIM_MAX_GRID};
+const char *const sim_pairs_slot[VGL_RC_N] = {"sim_pairs_short", "sim_pairs_wave", "sim_pairs_wg"};
 
 }  // namespace
 
@@ -542,7 +414,7 @@ int vgl_hip_sim_pairs(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_u, cons
     out.prepared_now = built ? 1 : 0;
 
     vgl_dev<unsigned long long> cnt;
-    VGL_TRY(sim_open_counters(c, &cnt));
+    VGL_TRY(vgl_open_counters(c, &cnt, SIM_NCNT));
     // pass 1, nothing written yet: the weights, then every chunk of pairs validated and counted per class
     if (d_weighted && V > 0) {
         {
@@ -555,19 +427,10 @@ int vgl_hip_sim_pairs(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_u, cons
     for (int64_t base = 0; base < n; base += chunk) {
         const int64_t m = std::min(chunk, n - base);
         const sim_pair_src src{d_u + base, d_v + base, V, csr->deg, b};
-        {
-            vgl_timed_launch tl(c, "sim_classify");
-            hipLaunchKernelGGL(vgl_k_sim_count<sim_pair_src>, dim3(vgl_grid(m, VGL_BLOCK, SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, m, cnt.p);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        VGL_TRY(vgl_publish_counters(c, "sim_publish", cnt, SIM_NCNT));
-        int64_t total = 0;
-        for (int k = 0; k < VGL_RC_N; k++) {
-            rows.push_back(c->h_counters[SIM_ROWS + k]);
-            total += c->h_counters[SIM_ROWS + k];
-        }
-        if (c->h_counters[SIM_BAD] != 0) VGL_FAIL("sim_pairs: a vertex of a pair is outside [0, V)");
-        if (total != m) VGL_FAIL("sim_pairs: internal error (the classes do not add up to the pairs)");
+        vgl_rc_lists<vgl_rc_bounded> L;
+        VGL_TRY(L.count(c, "sim_classify", "sim_publish", src, m, SIM_MAX_GRID, cnt.p, SIM_NCNT, SIM_ROWS, SIM_BAD, SIM_WORK, m, "sim_pairs: a vertex of a pair is outside [0, V)",
+                        "sim_pairs: internal error (the classes do not add up to the pairs)"));
+        rows.insert(rows.end(), L.rows, L.rows + VGL_RC_N);
         VGL_HIP_TRY(hipMemsetAsync(cnt + SIM_ROWS, 0, sizeof(unsigned long long) * VGL_RC_N, st));
     }
     if (n == 0) VGL_TRY(vgl_publish_counters(c, "sim_publish", cnt, SIM_NCNT));
@@ -581,11 +444,16 @@ int vgl_hip_sim_pairs(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_u, cons
     for (int64_t base = 0, at = 0; base < n; base += chunk, at += VGL_RC_N) {
         const int64_t m = std::min(chunk, n - base);
         const sim_pair_src src{d_u + base, d_v + base, V, csr->deg, b};
-        int64_t off[VGL_RC_N];
-        VGL_TRY(sim_fill_lists(c, src, m, list.p, &rows[(size_t)at], off, cnt.p));
+        vgl_rc_lists<vgl_rc_bounded> L;
+        std::copy(&rows[(size_t)at], &rows[(size_t)at] + VGL_RC_N, L.rows);
+        VGL_HIP_TRY(hipMemsetAsync(cnt + SIM_TAIL, 0, sizeof(unsigned long long) * VGL_RC_N, st));
+        VGL_TRY(L.fill(c, "sim_classify", src, m, SIM_MAX_GRID, 1, list.p, cnt + SIM_TAIL));
+        const int32_t *const of[VGL_RC_N] = {L.l[0].rows, L.l[1].rows, L.l[2].rows};
         const sim_pairs_args a{csr->rowptr, csr->adj, d_u + base, d_v + base, d_weight, d_common ? d_common + base : nullptr, d_weighted ? d_weighted + base : nullptr, cnt.p};
-        if (d_weighted) VGL_TRY(sim_pairs_launch<true>(c, a, list.p, &rows[(size_t)at], off));
-        else VGL_TRY(sim_pairs_launch<false>(c, a, list.p, &rows[(size_t)at], off));
+        if (d_weighted)
+            VGL_TRY(vgl_rc_launch_trio(c, sim_pairs_slot, L.rows, sim_pairs_cap, vgl_k_sim_pairs<VGL_RC_SHORT, true>, vgl_k_sim_pairs<VGL_RC_WAVE, true>, vgl_k_sim_pairs<VGL_RC_WG, true>, of, a));
+        else
+            VGL_TRY(vgl_rc_launch_trio(c, sim_pairs_slot, L.rows, sim_pairs_cap, vgl_k_sim_pairs<VGL_RC_SHORT, false>, vgl_k_sim_pairs<VGL_RC_WAVE, false>, vgl_k_sim_pairs<VGL_RC_WG, false>, of, a));
         out.pairs_short += rows[(size_t)at + VGL_RC_SHORT];
         out.pairs_wave += rows[(size_t)at + VGL_RC_WAVE];
         out.pairs_wg += rows[(size_t)at + VGL_RC_WG];
@@ -628,26 +496,19 @@ int vgl_hip_sim_topk(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_queries,
     }
 
     vgl_dev<unsigned long long> cnt;
-    VGL_TRY(sim_open_counters(c, &cnt));
+    VGL_TRY(vgl_open_counters(c, &cnt, SIM_NCNT));
     const sim_query_src src{d_queries, V, sm->work2, small, table};
-    {
-        vgl_timed_launch tl(c, "sim_classify");
-        hipLaunchKernelGGL(vgl_k_sim_count<sim_query_src>, dim3(vgl_grid(n, VGL_BLOCK, SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, (int64_t)n, cnt.p);
-    }
-    VGL_HIP_TRY(hipGetLastError());
-    VGL_TRY(vgl_publish_counters(c, "sim_publish", cnt, SIM_NCNT));
-    if (c->h_counters[SIM_BAD] != 0) VGL_FAIL("sim_topk: a query is outside [0, V)");
-    const int64_t rows[VGL_RC_N] = {c->h_counters[SIM_ROWS + 0], c->h_counters[SIM_ROWS + 1], c->h_counters[SIM_ROWS + 2]};
-    if (rows[0] + rows[1] + rows[2] != n) VGL_FAIL("sim_topk: internal error (the classes do not add up to the queries)");
+    vgl_rc_lists<vgl_rc_bounded> L;
+    VGL_TRY(L.count(c, "sim_classify", "sim_publish", src, (int64_t)n, SIM_MAX_GRID, cnt.p, SIM_NCNT, SIM_ROWS, SIM_BAD, SIM_WORK, n, "sim_topk: a query is outside [0, V)",
+                    "sim_topk: internal error (the classes do not add up to the queries)"));
+    const int64_t *rows = L.rows;
     out.rows_small = rows[SIM_SMALL];
     out.rows_table = rows[SIM_TABLE];
     out.rows_global = rows[SIM_GLOBAL];
     out.two_paths_walked = c->h_counters[SIM_WORK];
 
-    vgl_dev<int32_t> list, scratch;
-    VGL_TRY(list.alloc(st, (size_t)n));
-    int64_t off[VGL_RC_N];
-    VGL_TRY(sim_fill_lists(c, src, n, list.p, rows, off, cnt.p));
+    vgl_dev<int32_t> scratch;
+    VGL_TRY(L.fill(c, "sim_classify", src, (int64_t)n, SIM_MAX_GRID, 1, nullptr, cnt + SIM_TAIL));
     int64_t slots = 0;
     if (rows[SIM_GLOBAL] > 0) {                                       // a slot: V counters and V list entries; as many as the budget holds, at least 1
         slots = std::max<int64_t>(1, std::min((scratch_mb << 20) / (8 * (int64_t)V), std::min(rows[SIM_GLOBAL], SIM_MAX_SLOTS)));
@@ -658,7 +519,7 @@ int vgl_hip_sim_topk(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_queries,
     const sim_topk_args a{csr->rowptr, csr->adj, csr->deg, sm->work2, d_queries, d_label, d_ids, d_common, metric, k, include_neighbours ? 1 : 0, cnt.p};
     const char *const slot[VGL_RC_N] = {"sim_topk_small", "sim_topk_table", "sim_topk_global"};
     VGL_TRY(vgl_rc_launch(c, slot, rows, [&](int cls, int64_t m) {
-        const int32_t *l = list.p + off[cls];
+        const int32_t *l = L.l[cls].rows;
         if (cls == SIM_SMALL)
             hipLaunchKernelGGL(vgl_k_sim_topk_table<SIM_SLOTS_S>, dim3(vgl_grid(m, 1, 4 * SIM_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
         else if (cls == SIM_TABLE)

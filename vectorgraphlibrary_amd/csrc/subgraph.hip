@@ -55,12 +55,6 @@ enum { KH_BAD = 0, KH_REACHED = 1, KH_NCNT = 2 };
 static_assert(SUB_NCNT <= C_NSLOTS && SMP_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
 bool sub_sharded(const vgl_hip_graph *g) { return g->row_begin != 0 || g->row_end != g->V; }
-int sub_open_counters(vgl_hip_ctx *c, vgl_dev<unsigned long long> *cnt, int n)
-{
-    VGL_TRY(cnt->alloc(c->stream, (size_t)n));
-    VGL_HIP_TRY(hipMemsetAsync(cnt->p, 0, sizeof(unsigned long long) * (size_t)n, c->stream));
-    return 0;
-}
 
 // ---- exclusive scan of n values of a source S into S (int64 sums): tile sums, the scan of the tile sums by one workgroup, the apply pass ----
 struct sub_mask_src {           // the vertex mask (nullptr: every vertex is kept) -> new_id
@@ -225,89 +219,22 @@ __device__ __forceinline__ sub_row sub_row_of(const sub_dir &a, const int32_t *l
     const int64_t s = a.rowptr[v];
     return sub_row{s, a.rowptr[v + 1] - s, a.new_id[v]};
 }
-template <bool FILL>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_short(sub_dir a, const int32_t *list, int32_t n, sub_out o)
+template <int CLS, bool FILL>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub(const int32_t *list, int32_t n, sub_dir a, sub_out o)
 {
-    const int gi = threadIdx.x & (VGL_RC_G - 1), gshift = vgl_lane() & ~(VGL_RC_G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    using T = vgl_rc_team<CLS>;
+    for (int64_t at0 = T::begin(); at0 < n; at0 += T::stride()) {
+        const int64_t i = T::item(at0);
+        const bool has = i < n;
         const sub_row r = sub_row_of(a, list, i, n);
-        const int64_t at = FILL && i < n ? o.rowptr[r.nid] : 0, end = FILL && i < n ? o.rowptr[r.nid + 1] : 0;
+        const int64_t at = FILL && has ? o.rowptr[r.nid] : 0, end = FILL && has ? o.rowptr[r.nid + 1] : 0;
         int64_t kept = 0;                                             // survivors of the chunks before: the running base
-        for (int64_t j0 = 0; __any(j0 < r.len); j0 += VGL_RC_G) {     // (uniform over the wave: the longest row of its eight decides)
-            const int64_t e = r.s + j0 + gi;
+        for (int64_t j0 = 0; T::together(j0 < r.len); j0 += T::LANES) {
+            const int64_t e = r.s + j0 + T::lane();
             int32_t far = -1;
-            const bool k = j0 + gi < r.len && a.keep(e, far);
-            const unsigned sub = (unsigned)(__ballot(k) >> gshift) & ((1u << VGL_RC_G) - 1u);      // the group's 8 bits of the 64-bit ballot
-            if (FILL && k) {
-                const int64_t pos = at + kept + __popc(sub & ((1u << gi) - 1u));
-                if (pos < end) {
-                    o.adj[pos] = far;
-                    if (o.origin) o.origin[pos] = e;
-                }
-            }
-            kept += __popc(sub);
-        }
-        if (!FILL && gi == 0 && i < n) o.count[r.nid] = kept;
-    }
-}
-template <bool FILL>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_wave(sub_dir a, const int32_t *list, int32_t n, sub_out o)
-{
-    const int lane = vgl_lane();
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const sub_row r = sub_row_of(a, list, i, n);
-        const int64_t at = FILL ? o.rowptr[r.nid] : 0, end = FILL ? o.rowptr[r.nid + 1] : 0;
-        int64_t kept = 0;
-        for (int64_t j0 = 0; j0 < r.len; j0 += 64) {
-            const int64_t e = r.s + j0 + lane;
-            int32_t far = -1;
-            const bool k = j0 + lane < r.len && a.keep(e, far);
-            const unsigned long long m = __ballot(k);
-            if (FILL && k) {
-                const int64_t pos = at + kept + __popcll(m & ((1ull << lane) - 1ull));
-                if (pos < end) {
-                    o.adj[pos] = far;
-                    if (o.origin) o.origin[pos] = e;
-                }
-            }
-            kept += __popcll(m);
-        }
-        if (!FILL && lane == 0) o.count[r.nid] = kept;
-    }
-}
-// the ordered position of a survivor inside a workgroup chunk: the survivors of the wavefronts before (LDS) + those of the lanes below (ballot);
-// *total = the chunk's survivors.  Every thread of the workgroup calls; s_cnt: VGL_WAVES ints.
-__device__ __forceinline__ int sub_wg_rank(bool k, int *s_cnt, int *total)
-{
-    const unsigned long long m = __ballot(k);
-    __syncthreads();                                                  // the counts of the chunk before have been read
-    if (vgl_lane() == 0) s_cnt[vgl_wave()] = __popcll(m);
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < VGL_WAVES; w++) {
-        const int x = s_cnt[w];
-        if (w < vgl_wave()) pre += x;
-        tot += x;
-    }
-    *total = tot;
-    return pre + __popcll(m & ((1ull << vgl_lane()) - 1ull));
-}
-template <bool FILL>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_wg(sub_dir a, const int32_t *list, int32_t n, sub_out o)
-{
-    __shared__ int s_cnt[VGL_WAVES];
-    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
-        const sub_row r = sub_row_of(a, list, i, n);
-        const int64_t at = FILL ? o.rowptr[r.nid] : 0, end = FILL ? o.rowptr[r.nid + 1] : 0;
-        int64_t kept = 0;
-        for (int64_t j0 = 0; j0 < r.len; j0 += VGL_BLOCK) {
-            const int64_t e = r.s + j0 + threadIdx.x;
-            int32_t far = -1;
-            const bool k = j0 + threadIdx.x < r.len && a.keep(e, far);
+            const bool k = j0 + T::lane() < r.len && a.keep(e, far);
             int tot = 0;
-            const int rank = sub_wg_rank(k, s_cnt, &tot);
+            const int rank = T::rank(k, &tot);
             if (FILL && k) {
                 const int64_t pos = at + kept + rank;
                 if (pos < end) {
@@ -317,24 +244,17 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_wg(sub_dir a, const int32
             }
             kept += tot;
         }
-        if (!FILL && threadIdx.x == 0) o.count[r.nid] = kept;
+        if (!FILL && T::lead() && has) o.count[r.nid] = kept;
     }
 }
+const int64_t sub_grid_cap[VGL_RC_N] = {4 * SUB_MAX_GRID, 4 * SUB_MAX_GRID, 4 * SUB_MAX_GRID};
 template <bool FILL>
 int sub_launch(vgl_hip_ctx *c, const vgl_hip_subgraph_plan *p, int d, const sub_dir &a, const sub_out &o)
 {
     const char *const count_slot[VGL_RC_N] = {"sub_count_short", "sub_count_wave", "sub_count_wg"};
     const char *const fill_slot[VGL_RC_N] = {"sub_fill_short", "sub_fill_wave", "sub_fill_wg"};
-    hipStream_t st = c->stream;
-    return vgl_rc_launch(c, FILL ? fill_slot : count_slot, p->rows[d], [&](int cls, int64_t n) {
-        const int32_t *list = p->lists.p + p->off[d][cls];
-        if (cls == VGL_RC_SHORT)
-            hipLaunchKernelGGL(vgl_k_sub_short<FILL>, dim3(vgl_grid(n * VGL_RC_G, VGL_BLOCK, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
-        else if (cls == VGL_RC_WAVE)
-            hipLaunchKernelGGL(vgl_k_sub_wave<FILL>, dim3(vgl_grid(n, VGL_WAVES, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
-        else
-            hipLaunchKernelGGL(vgl_k_sub_wg<FILL>, dim3(vgl_grid(n, 1, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, list, (int32_t)n, o);
-    });
+    const int32_t *const list[VGL_RC_N] = {p->lists.p + p->off[d][0], p->lists.p + p->off[d][1], p->lists.p + p->off[d][2]};
+    return vgl_rc_launch_trio(c, FILL ? fill_slot : count_slot, p->rows[d], sub_grid_cap, vgl_k_sub<VGL_RC_SHORT, FILL>, vgl_k_sub<VGL_RC_WAVE, FILL>, vgl_k_sub<VGL_RC_WG, FILL>, list, a, o);
 }
 sub_dir sub_dir_of(const vgl_hip_subgraph_plan *p, int d)
 {
@@ -365,59 +285,23 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_khop_reached(int32_t V, const
 }
 
 // ---- sampling ----
-__host__ __device__ inline uint32_t sub_fmix32(uint32_t h)
-{
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
+// item i is seed i: its class by its degree; a counting pass (count != nullptr) also stores count[i] = min(fanout, degree), 0 for a seed out of range
 struct smp_src {
     int32_t V;
     const int64_t *rowptr;
     const int32_t *seeds;
     int32_t fanout;
     vgl_rc_bounds b;
+    int64_t *count;
+    __device__ __forceinline__ int cls(int64_t i, int64_t &work) const
+    {
+        const int32_t v = seeds[i];
+        const bool in = v >= 0 && v < V;
+        if (in) work = rowptr[v + 1] - rowptr[v];
+        if (count) count[i] = work < fanout ? work : fanout;
+        return in ? vgl_rc_class_of(work, b) : -1;
+    }
 };
-// validates the seeds; count[i] = min(fanout, degree) (0 for a seed out of range); rows per class, the degrees' sum
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_count(smp_src s, int64_t n, int64_t *count, unsigned long long *cnt)
-{
-    int64_t rows[VGL_RC_N] = {0, 0, 0}, bad = 0, exam = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
-        const int32_t v = s.seeds[i];
-        int64_t take = 0;
-        if (v < 0 || v >= s.V) bad++;
-        else {
-            const int64_t deg = s.rowptr[v + 1] - s.rowptr[v];
-            const int k = vgl_rc_class_of(deg, s.b);
-#pragma unroll
-            for (int q = 0; q < VGL_RC_N; q++) rows[q] += k == q;
-            exam += deg;
-            take = deg < s.fanout ? deg : s.fanout;
-        }
-        count[i] = take;
-    }
-#pragma unroll
-    for (int q = 0; q < VGL_RC_N; q++) vgl_wave_flush_add(cnt + SMP_ROWS + q, rows[q]);
-    vgl_wave_flush_add(cnt + SMP_BAD, bad);
-    vgl_wave_flush_add(cnt + SMP_EXAM, exam);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_lists(smp_src s, int64_t n, vgl_rc_bounded L0, vgl_rc_bounded L1, vgl_rc_bounded L2, unsigned long long *tail)
-{
-    const vgl_rc_bounded L[VGL_RC_N] = {L0, L1, L2};
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x;
-        int k = -1;
-        if (i < n) {
-            const int32_t v = s.seeds[i];                             // (validated by the counting pass)
-            k = vgl_rc_class_of(s.rowptr[v + 1] - s.rowptr[v], s.b);
-        }
-#pragma unroll
-        for (int q = 0; q < VGL_RC_N; q++) st[q].keep(k == q, (int32_t)i, L[q], tail + q);
-    }
-#pragma unroll
-    for (int q = 0; q < VGL_RC_N; q++) st[q].flush(L[q], tail + q);
-}
 struct smp_args {
     const int64_t *rowptr;       // of the sampled direction
     const int32_t *adj;
@@ -427,7 +311,7 @@ struct smp_args {
     int64_t *out_origin;         // may be nullptr
     int32_t fanout;
     uint32_t mix;                // fmix32(seed + 0x9e3779b9)
-    __device__ __forceinline__ uint32_t key(int64_t p) const { return sub_fmix32((uint32_t)p ^ mix); }
+    __device__ __forceinline__ uint32_t key(int64_t p) const { return vgl_fmix32((uint32_t)p ^ mix); }
 };
 struct smp_row { int64_t s, len, at, end; };      // the row's entries; its slots [at, end) of the output, never stored past
 __device__ __forceinline__ smp_row smp_row_of(const smp_args &a, const int32_t *list, int64_t i, int64_t n)
@@ -437,17 +321,18 @@ __device__ __forceinline__ smp_row smp_row_of(const smp_args &a, const int32_t *
     const int64_t s = a.rowptr[v];
     return smp_row{s, a.rowptr[v + 1] - s, a.out_rowptr[r], a.out_rowptr[r + 1]};
 }
-// G lanes per row (8 or 64): an entry is taken when fewer than fanout entries of the row have a smaller key
-template <int G>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_group(smp_args a, const int32_t *list, int32_t n)
+// short and wave rows: an entry is taken when fewer than fanout entries of the row have a smaller key
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_group(const int32_t *list, int32_t n, smp_args a)
 {
-    const int gi = threadIdx.x & (G - 1), gshift = vgl_lane() & ~(G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / G)) {      // (uniform over the workgroup)
-        const smp_row r = smp_row_of(a, list, base + threadIdx.x / G, n);
+    using T = vgl_rc_team<CLS>;
+    static_assert(CLS != VGL_RC_WG, "workgroup rows select by radix (vgl_k_sample_wg)");
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const smp_row r = smp_row_of(a, list, T::item(at), n);
         const bool all = r.len <= a.fanout;
         int64_t kept = 0;
-        for (int64_t j0 = 0; __any(j0 < r.len); j0 += G) {            // (uniform over the wave)
-            const int64_t j = j0 + gi;
+        for (int64_t j0 = 0; T::together(j0 < r.len); j0 += T::LANES) {
+            const int64_t j = j0 + T::lane();
             bool k = j < r.len;
             if (k && !all) {
                 const uint32_t mine = a.key(r.s + j);
@@ -455,26 +340,25 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_group(smp_args a, cons
                 for (int64_t t = 0; t < r.len && rank < a.fanout; t++) rank += a.key(r.s + t) < mine;
                 k = rank < a.fanout;
             }
-            const unsigned long long m = __ballot(k);
-            const unsigned long long sub = G == 64 ? m : (m >> gshift) & ((1ull << (G & 63)) - 1ull);
+            int tot = 0;
+            const int before = T::rank(k, &tot);
             if (k) {
-                const int64_t pos = r.at + kept + __popcll(sub & ((1ull << gi) - 1ull));
+                const int64_t pos = r.at + kept + before;
                 if (pos < r.end) {
                     a.out_adj[pos] = a.adj[r.s + j];
                     if (a.out_origin) a.out_origin[pos] = r.s + j;
                 }
             }
-            kept += __popcll(sub);
+            kept += tot;
         }
     }
 }
 // a workgroup per row: the fanout-th smallest key by four 8-bit radix passes (most significant byte first), then every entry whose key is not larger
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_wg(smp_args a, const int32_t *list, int32_t n)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_wg(const int32_t *list, int32_t n, smp_args a)
 {
     __shared__ unsigned s_hist[256];
     __shared__ int64_t s_scan[VGL_WAVES];
     __shared__ unsigned s_bin, s_k;
-    __shared__ int s_cnt[VGL_WAVES];
     static_assert(VGL_BLOCK == 256, "one histogram bin per thread");
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {             // (uniform over the workgroup)
         const smp_row r = smp_row_of(a, list, i, n);
@@ -507,7 +391,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sample_wg(smp_args a, const i
             const int64_t j = j0 + threadIdx.x;
             const bool k = j < r.len && a.key(r.s + j) <= limit;
             int tot = 0;
-            const int rank = sub_wg_rank(k, s_cnt, &tot);
+            const int rank = vgl_rc_team<VGL_RC_WG>::rank(k, &tot);
             if (k) {
                 const int64_t pos = r.at + kept + rank;
                 if (pos < r.end) {
@@ -542,7 +426,7 @@ int vgl_hip_subgraph_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const uint8_t
 
     vgl_dev<unsigned long long> cnt;
     vgl_dev<int64_t> bsum;
-    VGL_TRY(sub_open_counters(c, &cnt, SUB_NCNT));
+    VGL_TRY(vgl_open_counters(c, &cnt, SUB_NCNT));
     VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div((int64_t)V + 1, VGL_TILE)));
     VGL_TRY(p->new_id.alloc(st, (size_t)V));
     VGL_TRY(sub_scan(c, "sub_scan", sub_mask_src{d_keep_vertex, p->new_id.p}, (int64_t)V, bsum.p, cnt + SUB_VK));
@@ -665,7 +549,7 @@ int vgl_hip_khop_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_seeds, i
     vgl_hip_khop_stats out;
     memset(&out, 0, sizeof(out));
     vgl_dev<unsigned long long> cnt;
-    VGL_TRY(sub_open_counters(c, &cnt, KH_NCNT));
+    VGL_TRY(vgl_open_counters(c, &cnt, KH_NCNT));
     if (n > 0) {
         {
             vgl_timed_launch tl(c, "khop_init");
@@ -738,52 +622,26 @@ int vgl_hip_sample_neighbors(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_
     out.seeds = n;
     vgl_dev<unsigned long long> cnt;
     vgl_dev<int64_t> count, bsum;
-    vgl_dev<int32_t> list;
-    VGL_TRY(sub_open_counters(c, &cnt, SMP_NCNT));
+    vgl_rc_lists<vgl_rc_bounded> L;
+    VGL_TRY(vgl_open_counters(c, &cnt, SMP_NCNT));
     VGL_TRY(count.alloc(st, (size_t)n + 1));
     VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div(n + 1, VGL_TILE)));
     VGL_HIP_TRY(hipMemsetAsync(count.p + n, 0, sizeof(int64_t), st));
-    const smp_src src{g->V, csr.rowptr, d_seeds, fanout, b};
-    if (n > 0) {
-        {
-            vgl_timed_launch tl(c, "sample_count");
-            hipLaunchKernelGGL(vgl_k_sample_count, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, n, count.p, cnt.p);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-    }
-    VGL_TRY(vgl_publish_counters(c, "sample_publish", cnt, SMP_NCNT));
-    if (c->h_counters[SMP_BAD] != 0) VGL_FAIL("sample_neighbors: a seed is outside [0, V)");
-    const int64_t rows[VGL_RC_N] = {c->h_counters[SMP_ROWS + 0], c->h_counters[SMP_ROWS + 1], c->h_counters[SMP_ROWS + 2]};
-    if (rows[0] + rows[1] + rows[2] != n) VGL_FAIL("sample_neighbors: internal error (the classes do not add up to the seeds)");
+    smp_src src{g->V, csr.rowptr, d_seeds, fanout, b, count.p};
+    VGL_TRY(L.count(c, "sample_count", "sample_publish", src, n, SUB_MAX_GRID, cnt.p, SMP_NCNT, SMP_ROWS, SMP_BAD, SMP_EXAM, n, "sample_neighbors: a seed is outside [0, V)",
+                    "sample_neighbors: internal error (the classes do not add up to the seeds)"));
+    const int64_t *rows = L.rows;
     out.rows_short = rows[0]; out.rows_wave = rows[1]; out.rows_wg = rows[2];
     out.entries_examined = c->h_counters[SMP_EXAM];
     // from here on the outputs are written
     VGL_TRY(sub_scan(c, "sample_count", sub_i64_src{count.p, d_rowptr}, n + 1, bsum.p, cnt + SMP_TOTAL));
     if (n > 0) {
-        VGL_TRY(list.alloc(st, (size_t)n));
-        vgl_rc_bounded L[VGL_RC_N];
-        int64_t off[VGL_RC_N], at = 0;
-        for (int k = 0; k < VGL_RC_N; k++) {
-            off[k] = at;
-            L[k] = vgl_rc_bounded{list.p + at, (int32_t)rows[k]};
-            at += rows[k];
-        }
-        {
-            vgl_timed_launch tl(c, "sample_count");
-            hipLaunchKernelGGL(vgl_k_sample_lists, dim3(vgl_grid(n, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, src, n, L[0], L[1], L[2], cnt + SMP_TAIL);
-        }
-        VGL_HIP_TRY(hipGetLastError());
-        const smp_args a{csr.rowptr, csr.adj, d_seeds, d_rowptr, d_adj, d_origin, fanout, sub_fmix32(seed + 0x9e3779b9u)};
+        src.count = nullptr;                                          // (the seeds are validated and counted)
+        VGL_TRY(L.fill(c, "sample_count", src, n, SUB_MAX_GRID, 1, nullptr, cnt + SMP_TAIL));
+        const smp_args a{csr.rowptr, csr.adj, d_seeds, d_rowptr, d_adj, d_origin, fanout, vgl_fmix32(seed + 0x9e3779b9u)};
         const char *const slot[VGL_RC_N] = {"sample_short", "sample_wave", "sample_wg"};
-        VGL_TRY(vgl_rc_launch(c, slot, rows, [&](int cls, int64_t m) {
-            const int32_t *l = list.p + off[cls];
-            if (cls == VGL_RC_SHORT)
-                hipLaunchKernelGGL(vgl_k_sample_group<VGL_RC_G>, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
-            else if (cls == VGL_RC_WAVE)
-                hipLaunchKernelGGL(vgl_k_sample_group<64>, dim3(vgl_grid(m, VGL_WAVES, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
-            else
-                hipLaunchKernelGGL(vgl_k_sample_wg, dim3(vgl_grid(m, 1, 4 * SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, l, (int32_t)m);
-        }));
+        const int32_t *const list[VGL_RC_N] = {L.l[0].rows, L.l[1].rows, L.l[2].rows};
+        VGL_TRY(vgl_rc_launch_trio(c, slot, rows, sub_grid_cap, vgl_k_sample_group<VGL_RC_SHORT>, vgl_k_sample_group<VGL_RC_WAVE>, vgl_k_sample_wg, list, a));
     }
     VGL_TRY(vgl_publish_counters(c, "sample_publish", cnt, SMP_NCNT));
     VGL_HIP_TRY(hipStreamSynchronize(st));

@@ -44,8 +44,6 @@ __host__ __device__ inline int tri_class_of(int64_t d, tri_bounds b)
     return TRI_HUGE;
 }
 
-__device__ __forceinline__ uint32_t tri_hash(int32_t x, int bits) { return ((uint32_t)x * 0x9E3779B1u) >> (32 - bits); }
-
 // every lane of the wave, once, at the end of a count kernel
 __device__ __forceinline__ void tri_flush(int64_t *cnt, int64_t tri, int64_t work)
 {
@@ -80,17 +78,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_row_degrees(int32_t n, co
 }
 
 // ---- count: light rows ----
-// x in adj[s, s + n) (ascending, no duplicates)?
-__device__ __forceinline__ bool tri_contains(const int32_t *adj, int64_t s, int n, int32_t x)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (adj[s + mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo < n && adj[s + lo] == x;
-}
-
 template <int G, bool PV>
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_light(const int32_t *rows, int32_t n, const int64_t *rowptr, const int32_t *adj, int64_t *cnt, int64_t *pv)
 {
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_light(const int32_t *rows
                 if (gi == 0) work += sn;
                 for (int i = gi; i < sn; i += G) {
                     const int32_t x = adj[ss + i];
-                    if (tri_contains(adj, ls, ln, x)) {
+                    if (vgl_contains(adj, ls, ln, x)) {
                         hits++;
                         if (PV) vgl_atomic_add64(pv + x, 1);
                     }
@@ -175,7 +162,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit
         __syncthreads();
         for (int i = threadIdx.x; i < cn; i += VGL_BLOCK) {
             const int32_t x = adj[sa + c0 + i];
-            uint32_t h = tri_hash(x, bits);
+            uint32_t h = vgl_hash(x, bits);
             while (atomicCAS(&s_tab[h], -1, x) != -1) h = (h + 1) & mask;      // (no duplicates in a row: a taken slot holds another id)
         }
         __syncthreads();
@@ -186,7 +173,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tri_table(const int32_t *unit
             int hits = 0;
             for (int64_t p = gi; p < db; p += TRI_TG) {
                 const int32_t x = adj[sb + p];
-                uint32_t h = tri_hash(x, bits);
+                uint32_t h = vgl_hash(x, bits);
                 for (int32_t y = s_tab[h]; y != -1; y = s_tab[h]) {
                     if (y == x) {
                         hits++;

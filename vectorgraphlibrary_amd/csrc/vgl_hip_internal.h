@@ -281,6 +281,19 @@ int vgl_wait_counters(vgl_hip_ctx *ctx, int64_t seq);
 // counters of an algorithm's own (n <= C_NSLOTS): cnt[0 .. n) into h_counters by one launch under the timing slot `slot`, then waits for them
 int vgl_publish_counters(vgl_hip_ctx *ctx, const char *slot, const unsigned long long *cnt, int n);
 int vgl_zero_counters(vgl_hip_ctx *ctx, int first, int count);
+// the n device counters of a call, all 0
+static inline int vgl_open_counters(vgl_hip_ctx *ctx, vgl_dev<unsigned long long> *cnt, int n)
+{
+    VGL_TRY(cnt->alloc(ctx->stream, (size_t)n));
+    VGL_HIP_TRY(hipMemsetAsync(cnt->p, 0, sizeof(unsigned long long) * (size_t)n, ctx->stream));
+    return 0;
+}
+// the murmur3 finaliser: a bijection of uint32
+__host__ __device__ inline uint32_t vgl_fmix32(uint32_t h)
+{
+    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
+    return h;
+}
 int vgl_ensure_partials(vgl_hip_ctx *ctx, size_t n);
 int vgl_build_tile_rows(vgl_hip_ctx *ctx, struct vgl_dir_csr &d, int32_t nrows);     // d.tile_row / d.ntiles from d.rowptr / d.edges (owned by the caller)
 // The direction rule itself (gpu_change_state, change_state.hpp:100-141), for the host loops and the count launch alike: the same exact int64_t
@@ -454,6 +467,18 @@ __device__ __forceinline__ int64_t vgl_slot_of(const int32_t *adj, int64_t lo, i
     }
     return -1;
 }
+// x in adj[s, s + n) (ascending, no duplicates)?
+__device__ __forceinline__ bool vgl_contains(const int32_t *adj, int64_t s, int n, int32_t x)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (adj[s + mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo < n && adj[s + lo] == x;
+}
+// the multiplicative hash of a vertex id into a table of 2^bits slots
+__device__ __forceinline__ uint32_t vgl_hash(int32_t x, int bits) { return ((uint32_t)x * 0x9E3779B1u) >> (32 - bits); }
 
 // exclusive block scan (add); smem must hold VGL_WAVES elements of T; returns exclusive prefix, *total = block sum
 template <class T>

@@ -1,7 +1,12 @@
-// vgl_rowclass.h -- the short / wave / workgroup row-class layer of the worklist algorithms (kcore, ktruss, msf, msbfs, bicc).  DESIGN section 21.
-// A row (or an edge's shorter row) falls into one of three classes by its length; items are appended to one list per class; the host keeps a
-// [head, tail) window per list, read from the pinned counter mirror, and every step launches one kernel per class that has items.  What is here is
-// what the five files share; their kernels, grids and counters are their own.  bc (four classes), tri and lp (plan-owned sorted lists) are other schemes.
+// vgl_rowclass.h -- the short / wave / workgroup row-class layer of the worklist algorithms (kcore, ktruss, msf, msbfs, bicc, mis, sim, subgraph).
+// DESIGN section 21.  A row (or an edge's shorter row) falls into one of three classes by its length; items are appended to one list per class; the
+// host keeps a [head, tail) window per list, read from the pinned counter mirror, and every step launches one kernel per class that has items.
+// Here: the bounds, the windows, the per-class launch, the append staging, the class-list builder (count, check, carve, fill) and the team: what a
+// kernel that serves all three classes from one body needs of its class.  bc (four classes), tri and lp (plan-owned sorted lists) are other schemes.
+// Not on the team, because their three forms are three structures: kcore_short / wave (no grid stride, early return) and kcore_wg (2-D grid);
+// msf_min_* (offer combining in the short form, chunked workgroup rows); msbfs_push / pull_* (chunked workgroup rows).  Not on the builder:
+// vgl_k_sub_classify / _lists (two directions and old_id in one pass), vgl_k_bicc_init / _seed (union-find and level set-up in the same pass),
+// ktruss / kcore / msbfs (vgl_wave_append lists that grow during the run).
 #pragma once
 #include "vgl_hip_internal.h"
 
@@ -62,6 +67,24 @@ static inline int vgl_rc_launch(vgl_hip_ctx *c, const char *const *slot, const v
     const int64_t n[VGL_RC_N] = {w.n(0), w.n(1), w.n(2)};
     return vgl_rc_launch(c, slot, n, launch);
 }
+// the three instantiations of a team kernel `k<CLS>(LIST list, int32_t n, args...)`: class k runs over list[k] under slot[k], on at most cap[k] workgroups
+template <class LIST, class... KA, class... A>
+static inline int vgl_rc_launch_trio(vgl_hip_ctx *c, const char *const *slot, const int64_t *n, const int64_t *cap, void (*k_short)(LIST, int32_t, KA...),
+                                     void (*k_wave)(LIST, int32_t, KA...), void (*k_wg)(LIST, int32_t, KA...), const LIST *list, const A &...args)
+{
+    void (*const k[VGL_RC_N])(LIST, int32_t, KA...) = {k_short, k_wave, k_wg};
+    const int64_t items_per_wg[VGL_RC_N] = {VGL_BLOCK / VGL_RC_G, VGL_WAVES, 1};
+    return vgl_rc_launch(c, slot, n, [&](int cls, int64_t m) {
+        hipLaunchKernelGGL(k[cls], dim3(vgl_grid(m, items_per_wg[cls], cap[cls])), dim3(VGL_BLOCK), 0, c->stream, list[cls], (int32_t)m, args...);
+    });
+}
+template <class LIST, class... KA, class... A>
+static inline int vgl_rc_launch_trio(vgl_hip_ctx *c, const char *const *slot, const vgl_rc_window &w, const int64_t *cap, void (*k_short)(LIST, int32_t, KA...),
+                                     void (*k_wave)(LIST, int32_t, KA...), void (*k_wg)(LIST, int32_t, KA...), const LIST *list, const A &...args)
+{
+    const int64_t n[VGL_RC_N] = {w.n(0), w.n(1), w.n(2)};
+    return vgl_rc_launch_trio(c, slot, n, cap, k_short, k_wave, k_wg, list, args...);
+}
 
 #ifdef __HIPCC__
 // ---- append staging: a wave collects its appends in LDS and takes one returning atomic per 64 or more of them ----
@@ -107,4 +130,185 @@ __device__ __forceinline__ void vgl_rc_stage_open(vgl_rc_stage (&st)[NST])
 #pragma unroll
     for (int c = 0; c < NST; c++) st[c] = vgl_rc_stage{s_keep[c][vgl_wave()], 0};
 }
+
+// ---- the team: the lanes that share an item in the kernel of class CLS (8 of a wave, a wave, the workgroup) ----
+// The item loop is   for (int64_t at = T::begin(); at < n; at += T::stride()) { const int64_t i = T::item(at); const bool has = i < n; ... }
+// Short: `at` is the workgroup's first item, so every lane of the workgroup makes the same trips, and a lane whose team has no item (has == false)
+// walks an empty row: barriers, ballots and staged appends in the body see whole waves.  Wave: uniform over the wave.  Workgroup: uniform over the
+// workgroup.  There i == at and `has` is always true.
+// The reductions and rank() are called by every lane of the team's wave(s) in uniform control flow; each workgroup form keeps its LDS itself.
+template <int CLS>
+struct vgl_rc_team {
+    static constexpr int LANES = CLS == VGL_RC_SHORT ? VGL_RC_G : CLS == VGL_RC_WAVE ? 64 : VGL_BLOCK;
+    static constexpr int ITEMS_PER_WG = VGL_BLOCK / LANES;
+    static __device__ __forceinline__ int lane() { return CLS == VGL_RC_WG ? threadIdx.x : threadIdx.x & (LANES - 1); }
+    static __device__ __forceinline__ bool lead() { return lane() == 0; }
+    static __device__ __forceinline__ int team() { return CLS == VGL_RC_WG ? 0 : threadIdx.x / LANES; }      // of the workgroup's
+    static __device__ __forceinline__ int64_t begin() { return (int64_t)blockIdx.x * ITEMS_PER_WG + (CLS == VGL_RC_SHORT ? 0 : team()); }
+    static __device__ __forceinline__ int64_t stride() { return (int64_t)gridDim.x * ITEMS_PER_WG; }
+    static __device__ __forceinline__ int64_t item(int64_t at) { return at + (CLS == VGL_RC_SHORT ? team() : 0); }
+    // a loop condition over the team's row that keeps the wave together: the eight teams of a short wave leave with the longest of their rows
+    static __device__ __forceinline__ bool together(bool go_on) { return CLS == VGL_RC_SHORT ? __any(go_on) : go_on; }
+
+    // the combine of v over the team by OP, in every lane: an xor-butterfly over the team's lanes of a wave; the workgroup then folds the four
+    // waves' results from LDS in wave order
+    template <class T, class OP>
+    static __device__ __forceinline__ T butterfly(T v, OP op)
+    {
+#pragma unroll
+        for (int o = (LANES < 64 ? LANES : 64) / 2; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+        if constexpr (CLS == VGL_RC_WG) {
+            __shared__ T s_red[VGL_WAVES];
+            __syncthreads();                                          // the results of the item before have been read
+            if (vgl_lane() == 0) s_red[vgl_wave()] = v;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < VGL_WAVES; w++) v = op(v, s_red[w]);
+        }
+        return v;
+    }
+    template <class T> static __device__ __forceinline__ T min_of(T v) { return butterfly(v, [](T a, T b) { return a < b ? a : b; }); }
+    template <class T> static __device__ __forceinline__ T max_of(T v) { return butterfly(v, [](T a, T b) { return a > b ? a : b; }); }
+    // the sum: the workgroup's is 0 + wave 0 + wave 1 + wave 2 + wave 3 (a floating-point sum keeps this shape)
+    template <class T>
+    static __device__ __forceinline__ T sum_of(T v)
+    {
+        if constexpr (CLS == VGL_RC_WG) {
+            __shared__ T s_sum[VGL_WAVES];
+            return vgl_block_reduce_add(v, s_sum);
+        } else return butterfly(v, [](T a, T b) { return a + b; });
+    }
+    // the bitwise or of the low `nbits` bits
+    static __device__ __forceinline__ int or_of(int bits, int nbits)
+    {
+        if constexpr (CLS == VGL_RC_SHORT) return butterfly(bits, [](int a, int b) { return a | b; });
+        else {
+            int all = 0;
+#pragma unroll
+            for (int b = 0; b < nbits; b++) all |= __any(bits & (1 << b)) ? 1 << b : 0;
+            if constexpr (CLS == VGL_RC_WG) {
+                __shared__ int s_bits;
+                if (threadIdx.x == 0) s_bits = 0;
+                __syncthreads();
+                if (vgl_lane() == 0 && all) atomicOr(&s_bits, all);
+                __syncthreads();
+                all = s_bits;
+                __syncthreads();                                      // read before the next item clears it
+            }
+            return all;
+        }
+    }
+    // the ordered rank of a predicate: how many lanes of the team below this one hold k; *total = how many of the team do
+    static __device__ __forceinline__ int rank(bool k, int *total)
+    {
+        const unsigned long long m = __ballot(k);
+        if constexpr (CLS == VGL_RC_SHORT) {
+            const unsigned sub = (unsigned)(m >> (vgl_lane() & ~(LANES - 1))) & ((1u << LANES) - 1u);      // the team's 8 bits of the 64-bit ballot
+            *total = __popc(sub);
+            return __popc(sub & ((1u << lane()) - 1u));
+        } else {
+            int pre = 0, tot = __popcll(m);
+            if constexpr (CLS == VGL_RC_WG) {
+                __shared__ int s_cnt[VGL_WAVES];
+                __syncthreads();                                      // the counts of the chunk before have been read
+                if (vgl_lane() == 0) s_cnt[vgl_wave()] = tot;
+                __syncthreads();
+                tot = 0;
+#pragma unroll
+                for (int w = 0; w < VGL_WAVES; w++) {
+                    const int x = s_cnt[w];
+                    if (w < vgl_wave()) pre += x;
+                    tot += x;
+                }
+            }
+            *total = tot;
+            return pre + __popcll(m & ((1ull << vgl_lane()) - 1ull));
+        }
+    }
+};
+
+// ---- the class-list builder: items 0 .. n - 1 of a source S into one list per class ----
+// S::cls(i, work) = the class of item i and its work, or -1 for "not an item"; it may store what the algorithm wants of the item on the way
+template <class S>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_rc_count(S s, int64_t n, unsigned long long *rows, unsigned long long *bad, unsigned long long *work)
+{
+    int64_t r[VGL_RC_N] = {0, 0, 0}, b = 0, w = 0;
+    for (int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * VGL_BLOCK) {
+        int64_t x = 0;
+        const int c = s.cls(i, x);
+        if (c < 0) b++;
+        else { r[c]++; w += x; }
+    }
+#pragma unroll
+    for (int c = 0; c < VGL_RC_N; c++) vgl_wave_flush_add(rows + c, r[c]);
+    if (bad) vgl_wave_flush_add(bad, b);
+    if (work) vgl_wave_flush_add(work, w);
+}
+template <class S, class LIST>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_rc_fill(S s, int64_t n, LIST L0, LIST L1, LIST L2, unsigned long long *tail)
+{
+    const LIST L[VGL_RC_N] = {L0, L1, L2};
+    vgl_rc_stage st[VGL_RC_N];
+    vgl_rc_stage_open(st);
+    for (int64_t base = (int64_t)blockIdx.x * VGL_BLOCK; base < n; base += (int64_t)gridDim.x * VGL_BLOCK) {      // (uniform over the workgroup)
+        const int64_t i = base + threadIdx.x;
+        int64_t x = 0;
+        const int cls = i < n ? s.cls(i, x) : -1;
+#pragma unroll
+        for (int c = 0; c < VGL_RC_N; c++) st[c].keep(cls == c, (int32_t)i, L[c], tail + c);
+    }
+#pragma unroll
+    for (int c = 0; c < VGL_RC_N; c++) st[c].flush(L[c], tail + c);
+}
+// the lists of a run (LIST: vgl_rc_ring or vgl_rc_bounded): count() finds rows[], fill() carves a block into l[] and appends the items
+template <class LIST>
+struct vgl_rc_lists {
+    vgl_dev<int32_t> mem;                        // the block, unless the caller gives its own to fill()
+    LIST l[VGL_RC_N];
+    int64_t rows[VGL_RC_N] = {0, 0, 0};
+    // One launch under `slot` (none for n == 0; untimed for nullptr) and one publish of the `ncnt` counters: rows[] from cnt[rows0 ..]; cnt[bad0]
+    // items that are none (bad_msg) and cnt[work0] the work, where the index is >= 0; the classes must add up to `expect` where that is >= 0 (sum_msg).
+    template <class S>
+    int count(vgl_hip_ctx *c, const char *slot, const char *publish, const S &src, int64_t n, int64_t max_grid, unsigned long long *cnt, int ncnt, int rows0, int bad0, int work0,
+              int64_t expect, const char *bad_msg, const char *sum_msg)
+    {
+        if (n > 0) {
+            {
+                vgl_timed_launch tl(c, slot);
+                hipLaunchKernelGGL(vgl_k_rc_count<S>, dim3(vgl_grid(n, VGL_BLOCK, max_grid)), dim3(VGL_BLOCK), 0, c->stream, src, n, cnt + rows0, bad0 < 0 ? nullptr : cnt + bad0,
+                                   work0 < 0 ? nullptr : cnt + work0);
+            }
+            VGL_HIP_TRY(hipGetLastError());
+        }
+        VGL_TRY(vgl_publish_counters(c, publish, cnt, ncnt));
+        if (bad0 >= 0 && c->h_counters[bad0] != 0) VGL_FAIL(bad_msg);
+        int64_t total = 0;
+        for (int k = 0; k < VGL_RC_N; k++) {
+            rows[k] = c->h_counters[rows0 + k];
+            if (rows[k] < 0) VGL_FAIL(sum_msg);
+            total += rows[k];
+        }
+        if (expect >= 0 && total != expect) VGL_FAIL(sum_msg);
+        return 0;
+    }
+    // One launch under `slot`: list k gets factor * rows[k] entries of `block` (nullptr: of mem, drawn here) and the items of class k; tail: its 3 counters
+    template <class S>
+    int fill(vgl_hip_ctx *c, const char *slot, const S &src, int64_t n, int64_t max_grid, int factor, int32_t *block, unsigned long long *tail)
+    {
+        if (!block) {
+            VGL_TRY(mem.alloc(c->stream, (size_t)(factor * (rows[0] + rows[1] + rows[2]))));
+            block = mem.p;
+        }
+        for (int k = 0; k < VGL_RC_N; k++) {
+            l[k] = LIST{block, (decltype(LIST::cap))(factor * rows[k])};
+            block += factor * rows[k];
+        }
+        {
+            vgl_timed_launch tl(c, slot);
+            hipLaunchKernelGGL((vgl_k_rc_fill<S, LIST>), dim3(vgl_grid(n, VGL_BLOCK, max_grid)), dim3(VGL_BLOCK), 0, c->stream, src, n, l[0], l[1], l[2], tail);
+        }
+        VGL_HIP_TRY(hipGetLastError());
+        return 0;
+    }
+};
 #endif
