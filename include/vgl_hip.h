@@ -1004,6 +1004,92 @@ typedef struct {
 int vgl_hip_sample_neighbors(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_seeds, int64_t n, int32_t fanout, int direction, uint32_t seed,
                              int64_t *d_rowptr, int32_t *d_adj, int64_t *d_origin, vgl_hip_sample_stats *stats);
 
+/* The quotient graph of a vertex labelling (`quotient`): the vertices of a class merge into one coarse vertex, the stored entries between two classes
+ * into one coarse entry that carries their summed weight.  The row MERGE next to the row filter above; the condensation of the SCC labels, the
+ * coarsening step of a multilevel method, the numbers behind modularity.  The reference has nothing of the kind, so this comment is the contract:
+ *   input     any handle that owns all rows.  d_label: int32, V entries, device, in the graph's own numbering; every value >= 0; the values are opaque.
+ *             The stored entries are taken as they are: self-loops and repeated entries are entries like any other (as for the row filter; this is
+ *             NOT the simple graph of triangle counting's contract).
+ *   coarse vertices   V' = the number of distinct label values; c(v) = the rank of d_label[v] among the distinct values in ascending order, so the
+ *             numbering is a function of the label values alone, independent of the graph's vertex numbering.  cluster_of[v] = c(v) (int32, V);
+ *             label_of[c] (int32, V', ascending); size[c] (int32, V'); members (int32, V: the vertices grouped by cluster, ascending id within a
+ *             cluster) and member_ptr (int64, V' + 1).
+ *   coarse entries in direction d (0 = the stored outgoing CSR, 1 = the stored incoming CSR; direction 1 on a handle without one is an error):
+ *             row c holds one entry per distinct c(w) over the stored entries (v, w) of that direction with c(v) = c, ASCENDING and free of repeats;
+ *             with drop_loops nonzero the entries with c(v) == c(w) are left out.  d_count[i] (int64, E') = the sum over the merged stored entries p
+ *             of d_weight[p] (int64, optional, one per stored entry of THAT direction in CSR order; NULL = 1 each: the multiplicity).  Sums are
+ *             two's-complement int64; the caller keeps the totals below 2^63 (not checked).  Integer addition is associative, so the answer is unique
+ *             and depends on no switch, launch order or atomic order.  Because every row ascends, the result is BIT-IDENTICAL, rowptr and adj of both
+ *             directions, to Graph.from_coo (the stable COO -> CSR build) on the ascending list of the distinct coarse pairs.
+ *   vgl_hip_quotient_plan_create / _info / _vertex_maps / _members / _fill / _destroy, after vgl_hip_subgraph_plan_*:  _info hands V', E'out, E'in (-1
+ *             without an incoming CSR) and the stats to the host; _vertex_maps copies cluster_of / label_of / size, _members copies members /
+ *             member_ptr (every pointer optional); _fill(direction, d_weight) copies the plan's rowptr into d_rowptr (int64, V' + 1) and writes d_adj
+ *             (int32, E') and d_count (int64, E') -- buffers of the caller -- and is left enqueued on the context's stream.  A coarse row without
+ *             entries is valid (the last row, a cluster whose members are all isolated).
+ *   Method, vertex side: one validation pass (negative labels, the largest label); rocprim::radix_sort_pairs on (label, vertex) over the bits the
+ *             largest label needs (stable: the sorted vertices are `members`); head flags, their inclusive scan and a scatter give cluster_of,
+ *             label_of, member_ptr and size.  Per planned direction member_off = the exclusive scan of the members' row lengths in member order: flat
+ *             entry j of coarse row c finds its member by a binary search of member_off within the cluster (a cluster of many short rows costs no
+ *             trip per member); the row's VOLUME (the stored entries of its members) is a difference of two member_off values.
+ *   Method, entry side: coarse rows are classified by volume and listed per class (rows of volume 0 are no items):
+ *             <= VGL_QUOT_SHORT (32; at most 256): 8 lanes per row, rank-counting over the gathered coarse far ends, 8 at a time in registers and
+ *               exchanged by shuffles: an entry is a head when no equal key sits at an earlier flat position, its output position is the number of
+ *               heads with a smaller key, its count the sum over the equal keys;
+ *             <= VGL_QUOT_WAVE (1024; at most 1024): a wavefront per row;  <= VGL_QUOT_TABLE (4096; at most 4096): a workgroup per row: the coarse
+ *               far ends are gathered through cluster_of into LDS and sorted there (bitonic), the distinct keys are compacted in place with the
+ *               team's rank, and the fill adds every entry's weight to the LDS int64 sum of its key (binary search, LDS atomic add), then writes
+ *               keys and sums in order.  A row at the bound always fits: the LDS arrays hold one key and one sum per ENTRY;
+ *             larger: keys  c << 32 | c(w)  paired with the weight, rocprim::radix_sort_pairs then rocprim::reduce_by_key, in pieces of consecutive
+ *               rows whose buffers (32 bytes per key) stay under VGL_QUOT_SORT_CAP_MB (4096; 0 = no cap; a row above the cap is a piece of its own);
+ *               the runs of row c are placed at the row's start.
+ *             A count pass (the kernels with FILL = false) gives the distinct entries per row, a scan the int64 rowptr; the fill pass (FILL = true)
+ *             writes adj and count.  Every row has one owner; no atomic touches an output array; no floating point, no cooperative launch, no wait
+ *             on a flag.  The host reads the pinned counter mirror FOUR times per plan (the label check; V'; the class sizes of both directions; E'
+ *             of both directions) and copies the volumes of the sorted rows once per direction that has any (to cut the pieces).
+ *   timing slots: quot_check, quot_vertex (sort, heads, scan, scatter, sizes), quot_member_off, quot_classify, quot_lists, quot_count_short / _wave /
+ *             _table / _sorted, quot_scan, quot_publish, quot_fill_short / _wave / _table / _sorted (one _sorted bracket per piece).
+ *   stats, all exact and the same on every run: vertices = V'; rows_{short,wave,table,sorted}_{out,in} = coarse rows of volume > 0 per class;
+ *             entries_read_{out,in} = the stored entries of the direction; entries_{out,in} = E'; sorted_keys_{out,in} = the volumes of the sorted
+ *             rows; sort_pieces_{out,in}.  Only rows_*, sorted_keys_* and sort_pieces_* follow the switches; the _in fields are 0 when direction 1 is
+ *             not planned.
+ *             algorithmic_bytes = 32 V (labels read by the check 4; label and vertex read and written once by the sort 16, a lower bound of its
+ *             passes; cluster_of written 4; members read by the scatter 4; head and rank of the position 4) + 8 V' (label_of, size) + 8 (V' + 1)
+ *             (member_ptr) + for every planned direction 28 V (member_off: the member 4, its row bounds 16, the offset written 8) + 40 (V' + 1)
+ *             (the counts written 8, scanned: read 8 and written 8; the rowptr copied out: read 8 and written 8) + 16 read (counting and filling each:
+ *             the adjacency entry 4 and the cluster of its far end 4) + 12 E' (adj 4 and count 8 written); the binary searches, the lists, the sort
+ *             buffers and d_weight are left out: a lower bound of a plan followed by one fill per planned direction.
+ *   Fails, before anything is written: a NULL ctx, graph, label or out pointer, a sharded handle, a negative label; _fill: a direction other than
+ *             0 / 1, direction 1 without the incoming CSR, a NULL d_rowptr, a NULL d_adj or d_count while E' > 0.
+ * No output depends on VGL_QUOT_*. */
+typedef struct vgl_hip_quotient_plan vgl_hip_quotient_plan;
+typedef struct {
+    int64_t vertices;           /* V' */
+    int64_t rows_short_out;     /* coarse rows of volume > 0 per class, outgoing */
+    int64_t rows_wave_out;
+    int64_t rows_table_out;
+    int64_t rows_sorted_out;
+    int64_t rows_short_in;      /* ... incoming (0 when direction 1 is not planned) */
+    int64_t rows_wave_in;
+    int64_t rows_table_in;
+    int64_t rows_sorted_in;
+    int64_t entries_read_out;   /* the stored entries of the direction */
+    int64_t entries_read_in;
+    int64_t entries_out;        /* E' of the direction */
+    int64_t entries_in;
+    int64_t sorted_keys_out;    /* the volumes of the sorted rows */
+    int64_t sorted_keys_in;
+    int64_t sort_pieces_out;
+    int64_t sort_pieces_in;
+    int64_t algorithmic_bytes;
+} vgl_hip_quotient_stats;
+int vgl_hip_quotient_plan_create(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_label, int drop_loops, vgl_hip_quotient_plan **out);
+int vgl_hip_quotient_plan_info(vgl_hip_quotient_plan *plan, int32_t *vertices, int64_t *out_entries, int64_t *in_entries, vgl_hip_quotient_stats *stats);
+int vgl_hip_quotient_plan_vertex_maps(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan, int32_t *d_cluster_of, int32_t *d_label_of, int32_t *d_size);
+int vgl_hip_quotient_plan_members(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan, int32_t *d_members, int64_t *d_member_ptr);
+int vgl_hip_quotient_plan_fill(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan, int direction, const int64_t *d_weight, int64_t *d_rowptr, int32_t *d_adj,
+                               int64_t *d_count);
+int vgl_hip_quotient_plan_destroy(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -1253,6 +1253,115 @@ def sample_blocks(graph, seeds, fanouts, seed=0, direction="out", raw=False):
     return blocks
 
 
+def _own_labels(graph, labels, raw, who):
+    """labels (integer tensor or sequence of V entries, in ORIGINAL vertex order unless raw) -> int32 [V] in the graph's own order"""
+    lab = torch.as_tensor(labels).to(graph.ctx.device).flatten()
+    if lab.is_floating_point() or lab.dtype == torch.bool:
+        raise _l.VglHipError(who + ": labels must be integers")
+    if lab.numel() != graph.V:
+        raise _l.VglHipError("%s: %d labels for %d vertices" % (who, lab.numel(), graph.V))
+    lab = lab.to(torch.int64)
+    if int(lab.min()) < 0 or int(lab.max()) >= (1 << 31):
+        raise _l.VglHipError(who + ": a label is negative or does not fit int32")
+    lab = lab.to(torch.int32).contiguous()
+    return lab if raw or graph.bwd is None else graph.ctx.permute(graph.bwd, lab)
+
+
+def quotient_graph(graph, labels, weights=None, self_loops=True, with_incoming=None, raw=False):
+    """the quotient graph of a labelling (the contract of vgl_hip_quotient_plan_create in include/vgl_hip.h): the vertices with one label merge into
+    one coarse vertex, the stored entries between two labels into one coarse entry.  labels: an integer tensor of V entries >= 0 in ORIGINAL vertex
+    order unless raw=True -- the order in which connected_components, strongly_connected_components and label_propagation hand theirs back; coarse
+    vertex c stands for the c-th smallest label value.  weights: int64 per stored outgoing entry in CSR order (as sssp takes weights); None = 1
+    each.  self_loops=False leaves out the entries inside a cluster.  Returns a Graph that owns its tensors, every row ascending and free of repeats,
+    bit-identical to Graph.from_coo on the ascending list of distinct coarse pairs; q.count (int64 [E']) the summed weight (the multiplicity) of every
+    outgoing entry, q.in_count of every incoming one when the incoming CSR is built (with_incoming: None = as the parent); q.label_of (int32 [V']),
+    q.size (int32 [V']), q.cluster_of (int32 [V], in ORIGINAL order unless raw=True), q.stats; q.fwd / q.bwd are None.  Without weights the incoming
+    CSR is filled by the same kernels over the parent's incoming CSR; with weights, or when the parent has none, it is the transposition
+    Graph.from_coo uses and in_count follows its permutation."""
+    ctx = graph.ctx
+    lab = _own_labels(graph, labels, raw, "quotient_graph")
+    want_in = (graph.in_rowptr is not None) if with_incoming is None else bool(with_incoming)
+    w = None
+    if weights is not None:
+        w = torch.as_tensor(weights).to(ctx.device).flatten()
+        if w.is_floating_point():
+            raise _l.VglHipError("quotient_graph: weights must be integers")
+        if w.numel() != graph.E:
+            raise _l.VglHipError("quotient_graph: %d weights for %d entries" % (w.numel(), graph.E))
+        w = w.to(torch.int64).contiguous() if graph.E else torch.zeros(1, dtype=torch.int64, device=ctx.device)
+    plan = C.c_void_p()
+    _l.check(ctx.L.vgl_hip_quotient_plan_create(ctx.h, graph.h, _ptr(lab), int(not self_loops), C.byref(plan)))
+    try:
+        vc, eo, ei, st = C.c_int32(), C.c_int64(), C.c_int64(), _l.QuotientStats()
+        _l.check(ctx.L.vgl_hip_quotient_plan_info(plan, C.byref(vc), C.byref(eo), C.byref(ei), C.byref(st)))
+        vc, eo, ei = vc.value, eo.value, ei.value
+        cluster_of, label_of, size = ctx.empty(graph.V, torch.int32), ctx.empty(vc, torch.int32), ctx.empty(vc, torch.int32)
+        _l.check(ctx.L.vgl_hip_quotient_plan_vertex_maps(ctx.h, plan, _ptr(cluster_of), _ptr(label_of), _ptr(size)))
+        rowptr, adj, count = ctx.empty(vc + 1, torch.int64), ctx.empty(max(eo, 1), torch.int32), ctx.empty(max(eo, 1), torch.int64)
+        _l.check(ctx.L.vgl_hip_quotient_plan_fill(ctx.h, plan, 0, _ptr(w), _ptr(rowptr), _ptr(adj), _ptr(count)))
+        adj, count = adj[:eo], count[:eo]
+        in_rowptr = in_adj = in_count = None
+        if want_in and w is None and ei >= 0:
+            in_rowptr, in_adj, in_count = ctx.empty(vc + 1, torch.int64), ctx.empty(max(ei, 1), torch.int32), ctx.empty(max(ei, 1), torch.int64)
+            _l.check(ctx.L.vgl_hip_quotient_plan_fill(ctx.h, plan, 1, None, _ptr(in_rowptr), _ptr(in_adj), _ptr(in_count)))
+            in_adj, in_count = in_adj[:ei], in_count[:ei]
+        elif want_in:                                                 # the transposition of Graph.from_coo; the counts follow its permutation
+            csr_src = torch.repeat_interleave(torch.arange(vc, device=ctx.device, dtype=torch.int32), rowptr[1:] - rowptr[:-1])
+            in_rowptr, in_adj, perm = ctx.coo_to_csr(vc, adj, csr_src, want_perm=True)
+            in_count = count[perm]
+        ctx.sync()                                                    # the fills read the plan's arrays
+    finally:
+        ctx.L.vgl_hip_quotient_plan_destroy(ctx.h, plan)
+    q = Graph(ctx, vc, rowptr, adj, in_rowptr, in_adj)
+    q.count, q.in_count, q.label_of, q.size = count, in_count, label_of, size
+    q.cluster_of = cluster_of if raw else graph.to_original(cluster_of)
+    q.stats = _stats(st)
+    return q
+
+
+def partition_quality(graph, labels, weights=None, raw=False):
+    """how good a partition is, derived from quotient_graph() in torch (no further kernel).  Returns a dict: label_of (int32 [V']), size (int32 [V']),
+    internal (int64 [V'], the diagonal counts: the weight of the stored entries inside the cluster), volume_out / volume_in (int64 [V'], the weight of
+    the stored entries that leave / enter the cluster's vertices, the internal ones included), total (m, the weight of all stored entries),
+    cut = m - sum(internal) and coverage = sum(internal) / m (1.0 for m = 0) as a Python int, int and float, and
+    modularity = sum over c of (internal_c / m - volume_out_c * volume_in_c / m^2) in float64, 0.0 for m = 0.  On a graph that stores both directions
+    of every edge this is Newman's undirected modularity with 2m = the stored total; on a directed graph it is the directed modularity of Leicht
+    and Newman."""
+    q = quotient_graph(graph, labels, weights=weights, self_loops=True, raw=raw)
+    dev = graph.ctx.device
+    vc = q.V
+    rows = torch.repeat_interleave(torch.arange(vc, device=dev), q.out_rowptr[1:] - q.out_rowptr[:-1])
+    cols = q.out_adj.long()
+    zeros = torch.zeros(vc, dtype=torch.int64, device=dev)
+    internal = zeros.clone().index_add_(0, rows, torch.where(rows == cols, q.count, torch.zeros_like(q.count)))
+    volume_out = zeros.clone().index_add_(0, rows, q.count)
+    if q.in_rowptr is not None:
+        in_rows = torch.repeat_interleave(torch.arange(vc, device=dev), q.in_rowptr[1:] - q.in_rowptr[:-1])
+        volume_in = zeros.clone().index_add_(0, in_rows, q.in_count)
+    else:
+        volume_in = zeros.clone().index_add_(0, cols, q.count)
+    m = int(volume_out.sum())
+    inside = int(internal.sum())
+    if m == 0:
+        mod = 0.0
+    else:
+        mod = float((internal.double() / m - volume_out.double() * volume_in.double() / (float(m) * float(m))).sum())
+    return {"label_of": q.label_of, "size": q.size, "internal": internal, "volume_out": volume_out, "volume_in": volume_in, "total": m,
+            "cut": m - inside, "coverage": (inside / m) if m else 1.0, "modularity": mod}
+
+
+def modularity(graph, labels, weights=None, raw=False):
+    """the modularity of a partition: partition_quality(...)["modularity"]"""
+    return partition_quality(graph, labels, weights=weights, raw=raw)["modularity"]
+
+
+def condensation(graph, raw=False):
+    """the condensation of a directed graph: quotient_graph() by the labels of strongly_connected_components() with self_loops=False -- one vertex per
+    strongly connected component, acyclic.  dag.cluster_of maps every vertex (ORIGINAL order unless raw=True) to its component's vertex."""
+    comp, _ = strongly_connected_components(graph, raw=raw)
+    return quotient_graph(graph, comp, self_loops=False, raw=raw)
+
+
 def count_not_equal(ctx, a, b):
     r = C.c_int64()
     _l.check(ctx.L.vgl_hip_count_not_equal_u32(ctx.h, a.numel(), _ptr(a), _ptr(b), C.byref(r)))

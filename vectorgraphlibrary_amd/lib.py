@@ -111,6 +111,14 @@ class SubgraphStats(C.Structure):
                 ("entries_read_in", C.c_int64), ("entries_kept_out", C.c_int64), ("entries_kept_in", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class QuotientStats(C.Structure):
+    _fields_ = [("vertices", C.c_int64), ("rows_short_out", C.c_int64), ("rows_wave_out", C.c_int64), ("rows_table_out", C.c_int64),
+                ("rows_sorted_out", C.c_int64), ("rows_short_in", C.c_int64), ("rows_wave_in", C.c_int64), ("rows_table_in", C.c_int64),
+                ("rows_sorted_in", C.c_int64), ("entries_read_out", C.c_int64), ("entries_read_in", C.c_int64), ("entries_out", C.c_int64),
+                ("entries_in", C.c_int64), ("sorted_keys_out", C.c_int64), ("sorted_keys_in", C.c_int64), ("sort_pieces_out", C.c_int64),
+                ("sort_pieces_in", C.c_int64), ("algorithmic_bytes", C.c_int64)]
+
+
 class KhopStats(C.Structure):
     _fields_ = [("reached", C.c_int64), ("frontier_total", C.c_int64), ("edges_examined", C.c_int64), ("levels_run", C.c_int32)]
 
@@ -227,6 +235,12 @@ _SIGNATURES = {
     "vgl_hip_subgraph_plan_destroy": [_p, _p],
     "vgl_hip_khop_run": [_p, _p, _p, _i64, _i32, _int, _int, _p, C.POINTER(KhopStats)],
     "vgl_hip_sample_neighbors": [_p, _p, _p, _i64, _i32, _int, C.c_uint32, _p, _p, _p, C.POINTER(SampleStats)],
+    "vgl_hip_quotient_plan_create": [_p, _p, _p, _int, _pp],
+    "vgl_hip_quotient_plan_info": [_p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(QuotientStats)],
+    "vgl_hip_quotient_plan_vertex_maps": [_p, _p, _p, _p, _p],
+    "vgl_hip_quotient_plan_members": [_p, _p, _p, _p],
+    "vgl_hip_quotient_plan_fill": [_p, _p, _int, _p, _p, _p, _p],
+    "vgl_hip_quotient_plan_destroy": [_p, _p],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
