@@ -105,8 +105,9 @@ int vgl_hip_graph_create(vgl_hip_ctx *ctx, int32_t V, int32_t row_begin, int32_t
 int vgl_hip_graph_destroy(vgl_hip_ctx *ctx, vgl_hip_graph *g);
 /* what creation derived for the bottom-up BFS: owned rows with incoming edges (one head record each per plane), and whether the head
  * records are held in the 12-byte form (four 24-bit ids) instead of 16-byte int4 records (VGL_BFS_HEADS=auto|wide|packed at creation;
- * packed only when every id in a record is below 0xFFFFFF).  Either pointer may be NULL. */
-int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed);
+ * packed only when every id in a record is below 0xFFFFFF).  reach_rows: 1 + the largest owned vertex that has an incoming edge (0 when none
+ * has one, V when the incoming CSR is not stored) -- the fused BFS scans and re-initialises only the levels below it.  Any pointer may be NULL. */
+int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed, int32_t *reach_rows);
 
 /* ---- frontier (BaseFrontier, base_frontier.h:5-62; sparsity enum framework_types.h:156-160) ---- */
 #define VGL_HIP_FRONTIER_DENSE 0
@@ -194,7 +195,9 @@ typedef struct {
 int vgl_hip_bfs_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t source, int mode,
                     int32_t *d_levels, vgl_hip_bfs_stats *stats);
 /* `count` traversals from HOST source ids one after the other behind one call (the rounds loop of apps/bfs/bfs.cpp:36-50): d_levels is reused
- * and holds the levels of the last source afterwards; stats (optional) has `count` entries.  Stops at the first failing traversal. */
+ * and holds the levels of the last source afterwards; stats (optional) has `count` entries.  Stops at the first failing traversal.
+ * d_levels may hold anything on entry and belongs to the call until it returns: from the second traversal on only the entries a traversal can
+ * have written (those below the graph's reach_rows, and the previous source's) are re-initialised. */
 int vgl_hip_bfs_run_batch(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int mode, int32_t *d_levels,
                           vgl_hip_bfs_stats *stats);
 /* Optional graph preparation for repeated top-down traversals (the counterpart of the reference's offline graph import,

@@ -205,10 +205,11 @@ class Graph:
         return s
 
     def info(self):
-        """what creation derived for the bottom-up BFS (vgl_hip_graph_info): rows with incoming edges, and the form of their head records"""
-        n, p = C.c_int32(), C.c_int()
-        _l.check(self.ctx.L.vgl_hip_graph_info(self.h, C.byref(n), C.byref(p)))
-        return {"in_nz_rows": n.value, "bfs_heads": "packed" if p.value else "wide"}
+        """what creation derived for the BFS (vgl_hip_graph_info): rows with incoming edges, the form of their head records, and reach_rows =
+        1 + the largest owned vertex with an incoming edge (0: none; V without the incoming CSR), below which a traversal's writes stay"""
+        n, p, r = C.c_int32(), C.c_int(), C.c_int32()
+        _l.check(self.ctx.L.vgl_hip_graph_info(self.h, C.byref(n), C.byref(p), C.byref(r)))
+        return {"in_nz_rows": n.value, "bfs_heads": "packed" if p.value else "wide", "reach_rows": r.value}
 
     def out_edge_range(self, row_begin, row_end):
         return int(self.out_rowptr[row_begin]), int(self.out_rowptr[row_end])

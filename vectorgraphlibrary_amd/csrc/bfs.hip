@@ -28,12 +28,19 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init(int32_t V, int32_t s
         levels[v] = (v == source) ? 1 : -1;      // FIRST_LEVEL_VERTEX / UNVISITED_VERTEX (change_state.h:21-23)
 }
 
-// start of a fused traversal: levels, the three bitmaps (visited = front = {source}, next = 0) and the tickets in one launch
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init_all(int32_t V, int32_t source, int32_t *levels, int64_t words, uint64_t *visited,
+// start of a fused traversal: levels, the three bitmaps (visited = front = {source}, next = 0) and the tickets in one launch.
+// fill: the levels [0, fill) are stored.  V for a buffer that may hold anything; the graph's reach_rows when the buffer comes straight from a
+// traversal from `prev` on the same handle (vgl_hip_bfs_run_batch): that traversal wrote below reach_rows and at `prev` only, so the other
+// entries still hold the -1 of an earlier full fill.  prev = -1: none.
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init_all(int32_t fill, int32_t source, int32_t prev, int32_t *levels, int64_t words, uint64_t *visited,
                                                                 uint64_t *front, uint64_t *next, uint32_t *tickets, unsigned long long *list_count)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *list_count = 0ULL;
-    for (int32_t v = blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += gridDim.x * VGL_BLOCK)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *list_count = 0ULL;
+        if (prev >= fill) levels[prev] = -1;     // (before the source's: the two may be the same vertex; the loop below stores neither)
+        if (source >= fill) levels[source] = 1;
+    }
+    for (int32_t v = blockIdx.x * VGL_BLOCK + threadIdx.x; v < fill; v += gridDim.x * VGL_BLOCK)
         levels[v] = (v == source) ? 1 : -1;      // FIRST_LEVEL_VERTEX / UNVISITED_VERTEX (change_state.h:21-23)
     for (int64_t w = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; w < words; w += (int64_t)gridDim.x * VGL_BLOCK) {
         const uint64_t bit = (w == (source >> 6)) ? (1ULL << (source & 63)) : 0ULL;
@@ -407,32 +414,59 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bm_gnf_count(int64_t nwords, 
 // the tile (vt_min_deg; on a degree-sorted graph the rows of a tile have similar degrees, so the bound is tight where the edges are).
 // When the bound already satisfies the rule the traversal goes on bottom-up; otherwise the exact sizes are taken from the bitmap just built
 // (vgl_k_bm_gnf_count), not from a second scan of the levels.  Frontier generations 24.5 -> 17.5 us per RMAT-24 traversal.
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_scan_bound(int32_t nrows, int32_t row_base, const int32_t *levels, int32_t level,
+// The launch covers the vertex tiles that reach below the graph's reach_rows only (nrows = their rows): beyond them `levels` holds -1
+// everywhere but at the source (level 1, never the level scanned for), so the bitmaps there are right as they stand -- visited = the
+// source's bit, front = nothing -- but for the front bit that vgl_k_bfs_init_all gave the source, which the scan of all rows used to
+// overwrite.  stale_front: that source when it lies beyond the scanned rows (-1 otherwise); its byte of bm_front holds no other bit.
+// Shape (profiles/r08_scan_forms.log): at most VGL_SCAN_BLOCKS workgroups stride over the tiles, two full tiles per trip -- four independent
+// 16-byte loads in flight per thread -- with one reduction, one pair of partials and one ticket per WORKGROUP.  One workgroup per tile with two
+// loads per thread (the form up to round 7) took 19.2 us over the same rows, this one 13.6.  The sums are the same integers: sum over threads of
+// count x vt_min_deg[tile] = sum over tiles of tile count x vt_min_deg[tile].
+constexpr int VGL_SCAN_BLOCKS = 1024;       // 512 .. 1024 measure the same (13.3 - 13.6 us), 1536 13.9, 2048 15.2
+__device__ inline uint32_t vgl_match8(const int4 a, const int4 c, int32_t value)
+{
+    return (a.x == value) | ((a.y == value) << 1) | ((a.z == value) << 2) | ((a.w == value) << 3) |
+           ((c.x == value) << 4) | ((c.y == value) << 5) | ((c.z == value) << 6) | ((c.w == value) << 7);
+}
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_scan_bound(int32_t nrows, int32_t ntiles, int32_t row_base, const int32_t *levels, int32_t level,
                                                                  const int32_t *vt_min_deg, uint8_t *front_bytes, uint8_t *visited_bytes,
                                                                  int64_t *partials, uint32_t *ticket, int64_t *counters,
-                                                                 volatile int64_t *host, int64_t seq)
+                                                                 volatile int64_t *host, int64_t seq, int32_t stale_front)
 {
-    __shared__ int s32[VGL_WAVES];
     __shared__ int64_t s64[VGL_WAVES];
-    const int32_t r0 = blockIdx.x * VGL_TILE + threadIdx.x * VGL_EPT;
-    int cnt = 0;
-    if (r0 < nrows) {
-        const int nvalid = min(VGL_EPT, nrows - r0);
+    if (stale_front >= 0 && blockIdx.x == 0 && threadIdx.x == 0) front_bytes[stale_front >> 3] = 0;
+    int64_t f = 0, m = 0;
+    const int32_t stride = (int32_t)gridDim.x;
+    int32_t t = (int32_t)blockIdx.x;
+    for (; t + stride < ntiles && (t + stride + 1) * VGL_TILE <= nrows; t += 2 * stride) {      // both tiles have all their rows
+        const int32_t va = row_base + t * VGL_TILE + (int32_t)threadIdx.x * VGL_EPT, vb = va + stride * VGL_TILE;
+        const int4 a0 = *reinterpret_cast<const int4 *>(levels + va), a1 = *reinterpret_cast<const int4 *>(levels + va + 4);
+        const int4 b0 = *reinterpret_cast<const int4 *>(levels + vb), b1 = *reinterpret_cast<const int4 *>(levels + vb + 4);
+        const uint32_t fa = vgl_match8(a0, a1, level), fb = vgl_match8(b0, b1, level);
+        front_bytes[va >> 3] = (uint8_t)fa; visited_bytes[va >> 3] = (uint8_t)(0xFFu ^ vgl_match8(a0, a1, -1));
+        front_bytes[vb >> 3] = (uint8_t)fb; visited_bytes[vb >> 3] = (uint8_t)(0xFFu ^ vgl_match8(b0, b1, -1));
+        f += __popc(fa) + __popc(fb);
+        m += (int64_t)__popc(fa) * vt_min_deg[t] + (int64_t)__popc(fb) * vt_min_deg[t + stride];
+    }
+    for (; t < ntiles; t += stride) {                                                          // a tile on its own: the last trip, the ragged end
+        const int32_t r0 = t * VGL_TILE + (int32_t)threadIdx.x * VGL_EPT;
+        if (r0 >= nrows) continue;
         const int32_t v0 = row_base + r0;
         uint32_t aux;
         const vgl_pred_equal_i32 pred{levels, level};
-        const uint32_t bits = pred.bits8(v0, nvalid, &aux);
-        cnt = __popc(bits);
+        const uint32_t bits = pred.bits8(v0, min(VGL_EPT, nrows - r0), &aux);
         front_bytes[v0 >> 3] = (uint8_t)bits;
         visited_bytes[v0 >> 3] = (uint8_t)aux;
+        f += __popc(bits);
+        m += (int64_t)__popc(bits) * vt_min_deg[t];
     }
-    const int tc = vgl_block_reduce_add(cnt, s32);
+    f = vgl_block_reduce_add(f, s64);
+    m = vgl_block_reduce_add(m, s64);
     uint32_t dep = 0;
-    if (threadIdx.x == 0)
-        dep = vgl_put_agent(partials + 2 * blockIdx.x, (int64_t)tc) ^ vgl_put_agent(partials + 2 * blockIdx.x + 1, (int64_t)tc * (int64_t)vt_min_deg[blockIdx.x]);
+    if (threadIdx.x == 0) dep = vgl_put_agent(partials + 2 * blockIdx.x, f) ^ vgl_put_agent(partials + 2 * blockIdx.x + 1, m);
     if (!vgl_last_block(ticket, dep)) return;
-    int64_t f = 0, m = 0;
-    for (int t = threadIdx.x; t < (int)gridDim.x; t += VGL_BLOCK) { f += vgl_load_agent(partials + 2 * t); m += vgl_load_agent(partials + 2 * t + 1); }
+    f = 0; m = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += VGL_BLOCK) { f += vgl_load_agent(partials + 2 * b); m += vgl_load_agent(partials + 2 * b + 1); }
     f = vgl_block_reduce_add(f, s64);
     m = vgl_block_reduce_add(m, s64);
     if (threadIdx.x == 0) vgl_publish2(counters, host, seq, C_FRONT, f, C_NEIGH, m);
@@ -1442,6 +1476,7 @@ struct vgl_bfs_traversal {
     unsigned long long *list_count;     // list length of vgl_k_bm_expand: a counter slot the fused traversal does not use otherwise
     std::chrono::steady_clock::time_point t0;
 
+    int32_t source = -1;
     int32_t cur = 1;
     vgl_bfs_front front = vgl_bfs_front::bitmap;
     bool bottom_up = false;             // the direction that PROCESSES level `cur`
@@ -1493,13 +1528,17 @@ struct vgl_bfs_traversal {
             VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, advance, hinted ? &hint : nullptr));
             skipped = hinted && c->h_counters[C_SKIPPED] != 0;
             front = skipped ? vgl_bfs_front::bitmap : vgl_bfs_front::counted_bitmap;
-        } else if (p.scan_bound && g->nvtiles <= 8192) {         // (per-tile partials live in g->bu_partials: 4 * 4096 slots)
+        } else if (p.scan_bound && g->nvtiles <= 8192) {         // (the kernel's row arithmetic is 32-bit; its partials live in g->bu_partials)
             const int64_t seq = vgl_next_seq(c);
+            // the vertex tiles that reach below reach_rows (the bound rounded UP to a tile; at least one, the kernel publishes from its last workgroup)
+            const int64_t scan_tiles = std::max<int64_t>(1, std::min<int64_t>(g->nvtiles, vgl_ceil_div(g->reach_rows, VGL_TILE)));
+            const int32_t scan_rows = (int32_t)std::min<int64_t>(g->nrows, scan_tiles * VGL_TILE);
             {
                 vgl_timed_launch tl(c, "gnf");
-                hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, (const int32_t *)levels,
-                                   cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front.p, (uint8_t *)g->bm_visited.p, g->bu_partials,
-                                   g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters, (volatile int64_t *)c->h_counters, seq);
+                hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)std::min<int64_t>(scan_tiles, VGL_SCAN_BLOCKS)), dim3(VGL_BLOCK), 0, c->stream, scan_rows,
+                                   (int32_t)scan_tiles, g->row_begin, (const int32_t *)levels, cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front.p,
+                                   (uint8_t *)g->bm_visited.p, g->bu_partials, g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters,
+                                   (volatile int64_t *)c->h_counters, seq, source >= scan_rows ? source : -1);
             }
             VGL_HIP_TRY(hipGetLastError());
             VGL_TRY(vgl_wait_counters(c, seq));
@@ -1647,10 +1686,13 @@ struct vgl_bfs_traversal {
         return 0;
     }
 
-    int run(int32_t source)
+    // prev >= 0: `levels` comes straight from this handle's traversal from `prev` (a batch): only what that one can have written is stored anew
+    int run(int32_t source_, int32_t prev = -1)
     {
-        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(V, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, V, source, levels, words, g->bm_visited, g->bm_front,
-                           g->bm_next, g->tickets, list_count);
+        source = source_;
+        const int32_t fill = prev >= 0 ? g->reach_rows : V;
+        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(std::max<int64_t>(fill, words), VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, fill, source, prev,
+                           levels, words, g->bm_visited, g->bm_front, g->bm_next, g->tickets, list_count);
         t0 = std::chrono::steady_clock::now();
         if (p.small_m > 0) {                                                // level 1 = {source}
             VGL_TRY(small_levels(1, source, false));
@@ -1722,7 +1764,8 @@ int vgl_hip_bfs_init(vgl_hip_ctx *c, int32_t V, int32_t source, int32_t *d_level
     return 0;
 }
 
-int vgl_hip_bfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
+// prev: -1, or the source of the traversal on this handle that left d_levels as they are (vgl_bfs_traversal::run)
+static int vgl_bfs_run_from(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int32_t prev, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
 {
     if (!c || !g || !d_levels) VGL_FAIL("bfs_run: null argument");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("bfs_run: graph handle must own all rows (use the step API for shards)");
@@ -1731,17 +1774,29 @@ int vgl_hip_bfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int mode, 
     if (source < 0 || source >= g->V) VGL_FAIL("bfs_run: source vertex out of range");
     vgl_ctx_refresh_env(c);                                  // (a pass over the pointers of `environ`; the strings are parsed only when something was set since)
     vgl_bfs_traversal t(c, g, mode, d_levels);
-    VGL_TRY(t.run(source));
+    VGL_TRY(t.run(source, prev));
     if (stats) *stats = t.st;
     return 0;
 }
 
+// one traversal into a buffer that may hold anything: every entry of d_levels is stored
+int vgl_hip_bfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
+{
+    return vgl_bfs_run_from(c, g, source, -1, mode, d_levels, stats);
+}
+
 // `count` traversals one after the other (the rounds loop of apps/bfs/bfs.cpp:36-50 behind one call): d_levels is reused and holds the levels
 // of the last source afterwards, stats[i] (optional) those of traversal i.  Stops at the first failing traversal.
+// The first traversal stores all V levels (the caller's buffer may hold anything).  Between its traversals the buffer is the batch's alone --
+// nobody else can write it before this call returns -- and a traversal writes levels[v] only for vertices with an incoming edge (all below
+// the handle's reach_rows) and for its source, so from the second traversal on the entries at or beyond reach_rows still hold -1, but for the
+// previous source's: only [0, reach_rows), that entry and the new source's are stored (vgl_k_bfs_init_all).  On a graph whose rows without
+// incoming edges are not numbered last reach_rows is about V and nothing changes.
 int vgl_hip_bfs_run_batch(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, int32_t count, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
 {
     if (!sources || count < 0) VGL_FAIL("bfs_run_batch: null argument");
-    for (int32_t i = 0; i < count; i++) VGL_TRY(vgl_hip_bfs_run(c, g, sources[i], mode, d_levels, stats ? stats + i : nullptr));
+    for (int32_t i = 0; i < count; i++)
+        VGL_TRY(vgl_bfs_run_from(c, g, sources[i], i > 0 ? sources[i - 1] : -1, mode, d_levels, stats ? stats + i : nullptr));
     return 0;
 }
 

@@ -47,6 +47,17 @@ __global__ __launch_bounds__(1024) void vgl_k_nz_rank(int64_t ngroups, const uin
     if (threadIdx.x == 0) rank[ngroups] = total;
 }
 
+// *top = max(*top, 1 + the largest vertex whose bit is set in words [word0, word0 + nwords)): vgl_hip_graph::reach_rows off bm_in_nz
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_reach_rows(int64_t nwords, int64_t word0, const uint64_t *bits, int32_t *top)
+{
+    int64_t mine = 0;
+    for (int64_t w = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; w < nwords; w += (int64_t)gridDim.x * VGL_BLOCK) {
+        const uint64_t b = bits[word0 + w];
+        if (b) mine = max(mine, ((word0 + w) << 6) + 64 - __clzll((long long)b));
+    }
+    if (mine) atomicMax(top, (int32_t)mine);
+}
+
 // vt_min[t] = smallest degree among the rows of vertex tile t (2048 rows)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tile_min_degree(int32_t nrows, const int64_t *rowptr, int32_t *vt_min)
 {
@@ -355,6 +366,7 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
     VGL_HIP_TRY(hipMemsetAsync(g->bm_front, 0, words * 8, c->stream));
     VGL_HIP_TRY(hipMemsetAsync(g->bm_next, 0, words * 8, c->stream));
     VGL_HIP_TRY(hipMemsetAsync(g->bm_in_nz, 0, words * 8, c->stream));
+    g->reach_rows = V;                                       // (nothing is known about the incoming edges without their CSR)
     if (g->in.rowptr) {
         int grid = (int)std::min<int64_t>(8192, std::max<int64_t>(1, vgl_ceil_div(g->nrows, VGL_BLOCK)));
         hipLaunchKernelGGL(vgl_k_nonempty_rows, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, g->nrows, g->row_begin, g->in.rowptr, g->bm_in_nz);
@@ -363,6 +375,13 @@ int vgl_hip_graph_create(vgl_hip_ctx *c, int32_t V, int32_t row_begin, int32_t r
         hipLaunchKernelGGL(vgl_k_nz_rank, dim3(1), dim3(1024), 0, c->stream, ngroups, (const uint64_t *)(g->bm_in_nz + (row_begin >> 6)), g->in_nz_rank);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_hip_memcpy_d2h(c, &g->in_nz_rows, g->in_nz_rank + ngroups, sizeof(int32_t)));
+        vgl_dev<int32_t> reach;
+        VGL_TRY(reach.alloc(1));
+        VGL_HIP_TRY(hipMemsetAsync(reach.p, 0, sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(vgl_k_reach_rows, dim3((unsigned)std::min<int64_t>(1024, vgl_ceil_div(ngroups, VGL_BLOCK))), dim3(VGL_BLOCK), 0, c->stream, ngroups,
+                           (int64_t)(row_begin >> 6), (const uint64_t *)g->bm_in_nz.p, reach.p);
+        VGL_HIP_TRY(hipGetLastError());
+        VGL_TRY(vgl_hip_memcpy_d2h(c, &g->reach_rows, reach.p, sizeof(int32_t)));
         VGL_TRY(g->in_head.alloc((size_t)std::max(g->in_nz_rows, 1) * 8));
         vgl_dev<int32_t> head_max;
         VGL_TRY(head_max.alloc(1));
@@ -487,11 +506,12 @@ int vgl_hip_frontier_info(vgl_hip_ctx *c, vgl_hip_frontier *f, int32_t *size, in
     if (sparsity) *sparsity = f->sparsity;
     return 0;
 }
-int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed)
+int vgl_hip_graph_info(vgl_hip_graph *g, int32_t *in_nz_rows, int *heads_packed, int32_t *reach_rows)
 {
     if (!g) VGL_FAIL("graph_info: null argument");
     if (in_nz_rows) *in_nz_rows = g->in.rowptr ? g->in_nz_rows : 0;
     if (heads_packed) *heads_packed = g->in_head_packed ? 1 : 0;
+    if (reach_rows) *reach_rows = g->reach_rows;
     return 0;
 }
 int vgl_hip_graph_tile_rows(vgl_hip_graph *g, int direction, const int32_t **d_tile_row, int64_t *ntiles)

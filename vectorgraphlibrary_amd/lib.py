@@ -163,7 +163,7 @@ _SIGNATURES = {
     "vgl_hip_partition_rows": [_p, _i32, _p, _int, C.POINTER(_i32)],
     "vgl_hip_graph_create": [_p, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _i64, _pp],
     "vgl_hip_graph_destroy": [_p, _p],
-    "vgl_hip_graph_info": [_p, C.POINTER(_i32), C.POINTER(_int)],
+    "vgl_hip_graph_info": [_p, C.POINTER(_i32), C.POINTER(_int), C.POINTER(_i32)],
     "vgl_hip_frontier_create": [_p, _p, _pp],
     "vgl_hip_frontier_destroy": [_p, _p],
     "vgl_hip_frontier_create_on": [_p, _p, _p, _p, _pp],
