@@ -418,7 +418,32 @@ def test_condensation(ctx):
         check_quot(ctx, g, comp, None, False, what="condensation")
 
 
-# ---- 11. determinism and hygiene ----
+# ---- 11. the key bits of the two sorts at their edges ----
+def test_sort_key_bits_at_their_edges(ctx, monkeypatch):
+    # the vertex sort runs over the bits of the largest label: its top used bit at position 0 (none for the label 0 alone), 1, 15 and 30, with
+    # labels one below the top value, whose low bits all count
+    V = 300
+    v = np.arange(V)
+    src, dst = np.concatenate([v, [0, 7, 7, 150, 299]]), np.concatenate([(v * 11 + 1) % V, [299, 7, 8, 3, 0]])
+    tops = {"0": 0, "0, 1": 1, "up to 2": 2, "up to 3": 3, "up to 32768": 1 << 15, "up to 2^30": 1 << 30}
+    for renumber in (None, "total"):
+        g = graph(ctx, V, src, dst, renumber)
+        for name, top in tops.items():
+            labels = np.array([top, max(top - 1, 0), top // 2, 0])[R.hashed_labels(V, 4, 5)]
+            q = check_quot(ctx, g, labels, None, True, what="labels " + name)
+            assert q.label_of.tolist() == sorted({top, max(top - 1, 0), top // 2, 0})
+    # more than 2^16 clusters with every row in the sorted class: the 64-bit keys  c << 32 | c(w)  need 49 bits
+    V = (1 << 16) + 4465
+    v = np.arange(V)
+    chord = v[v % 5 == 0]
+    b = set_switches(monkeypatch, 0, 0, 0)
+    q = check_quot(ctx, graph(ctx, V, np.concatenate([v, chord]), np.concatenate([(v + 1) % V, (chord * 7 + 3) % V])), V - 1 - v, bounds=b,
+                   what="70001 clusters, sorted")
+    set_switches(monkeypatch)
+    assert q.V == V and q.stats["rows_sorted_out"] == V and q.stats["rows_short_out"] == 0
+
+
+# ---- 12. determinism and hygiene ----
 def test_determinism_and_launches(ctx, monkeypatch):
     A = api()
     V, src, dst = scale_edges(ctx, "rmat")

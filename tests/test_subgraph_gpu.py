@@ -425,7 +425,62 @@ def test_refusals_write_nothing(ctx):
             call()
 
 
-# ---- 7. the app ----
+# ---- 7. the scans: new_id from the vertex mask, rowptr from the row counts, the sampling rowptr, at the sizes around a scan's tile bounds ----
+@pytest.mark.parametrize("V", [1, 2, 255, 256, 257, 2047, 2048, 2049, 70001])
+def test_scans_across_sizes(V, ctx):
+    A = api()
+    L = ctx.L
+    p = lambda t: C.c_void_p(t.data_ptr())
+    v = np.arange(V, dtype=np.int64)
+    chord = v[v % 5 == 0]
+    src, dst = np.concatenate([v, chord]), np.concatenate([(v + 1) % V, (chord * 7 + 3) % V])      # a ring with a few chords
+    g = A.Graph.from_coo(ctx, V, *coo(ctx, src, dst))
+    rowptr, adj, in_rowptr, in_adj = host(g)
+    last = np.zeros(V, dtype=np.uint8)
+    last[V - 1] = 1
+    masks = {"all": np.ones(V, dtype=np.uint8), "none": np.zeros(V, dtype=np.uint8), "every third": (v % 3 == 0).astype(np.uint8), "the last": last}
+    for name, keep in masks.items():
+        what = "V = %d, keep %s" % (V, name)
+        want_new = np.where(keep != 0, np.cumsum(keep) - keep, -1).astype(np.int32)
+        want_old = np.nonzero(keep)[0].astype(np.int32)
+        assert np.array_equal(want_new, R.vertex_maps(V, keep)[0])
+        plan = C.c_void_p()
+        A._l.check(L.vgl_hip_subgraph_plan_create(ctx.h, g.h, p(dev(ctx, keep, np.uint8)), None, C.byref(plan)))
+        try:
+            vk, eo, ei = C.c_int32(-1), C.c_int64(-1), C.c_int64(-1)
+            A._l.check(L.vgl_hip_subgraph_plan_info(plan, C.byref(vk), C.byref(eo), C.byref(ei), None))
+            assert vk.value == len(want_old), what
+            new_id = torch.full((V,), 7, dtype=torch.int32, device=ctx.device)
+            old_id = torch.full((max(vk.value, 1),), 7, dtype=torch.int32, device=ctx.device)
+            A._l.check(L.vgl_hip_subgraph_plan_vertex_maps(ctx.h, plan, p(new_id), p(old_id)))
+            assert np.array_equal(new_id.cpu().numpy(), want_new), what
+            assert np.array_equal(old_id.cpu().numpy()[:vk.value], want_old), what
+            for d, (rp_, ad_, kept) in enumerate(((rowptr, adj, eo.value), (in_rowptr, in_adj, ei.value))):
+                row = R.rows_of(rp_)
+                counts = np.bincount(want_new[row[(want_new[row] >= 0) & (want_new[ad_] >= 0)]], minlength=len(want_old))
+                want_rp = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+                assert kept == want_rp[-1], (what, d)
+                if vk.value == 0:
+                    continue                                          # (a fill of V' = 0 writes nothing: test_refusals_write_nothing)
+                assert np.array_equal(want_rp, R.filter_rows(rp_, ad_, keep)[0]), (what, d)
+                rp = torch.full((vk.value + 1,), 7, dtype=torch.int64, device=ctx.device)
+                ad = torch.full((max(kept, 1),), 7, dtype=torch.int32, device=ctx.device)
+                A._l.check(L.vgl_hip_subgraph_plan_fill(ctx.h, plan, d, p(rp), p(ad), None))
+                assert np.array_equal(rp.cpu().numpy(), want_rp), (what, d)
+        finally:
+            L.vgl_hip_subgraph_plan_destroy(ctx.h, plan)
+    # V seeds, fanout 2: the sampling rowptr is the scan of min(degree, 2)
+    seeds = ((v * 3 + 1) % V).astype(np.int32)
+    for direction, rp_ in (("out", rowptr), ("in", in_rowptr)):
+        if V <= 2049:
+            rp = check_sample(g, seeds.tolist(), 2, 11, direction, what="V = %d" % V)[0]
+        else:
+            rp = A.sample_neighbors(g, seeds, 2, seed=11, direction=direction, raw=True)[0]
+        deg = rp_[seeds.astype(np.int64) + 1] - rp_[seeds]
+        assert np.array_equal(rp.cpu().numpy(), np.concatenate([[0], np.cumsum(np.minimum(deg, 2))])), (V, direction)
+
+
+# ---- 8. the app ----
 @pytest.mark.parametrize("mode", ["mask", "kcore", "hops", "sample"])
 def test_subgraph_app(mode, tmp_path, ctx):
     dump = str(tmp_path / "subgraph.bin")

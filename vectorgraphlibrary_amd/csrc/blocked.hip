@@ -1,9 +1,9 @@
 // blocked.hip -- builds the layout of the blocked advance (vgl_blocked.h) from one CSR direction.  Offline, like the reference's
-// graph import (vgl_graph.hpp:57-68): the edge keys (accumulate block, gather block) are sorted with rocPRIM's stable radix sort,
+// graph import (vgl_graph.hpp:57-68): the edge keys (accumulate block, gather block) are sorted with the stable radix sort of vgl_prim.h,
 // segments are padded to 64-entry chunks and laid out twice (gather order / accumulate order).
 #include "vgl_blocked.h"
+#include "vgl_prim.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -253,7 +253,7 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
     // temporaries of the build: freed when it leaves, error or not
     vgl_dev<uint32_t> keys, keys2, keys3, packed, packed2, seg_first, seg_end, nch_a, nch_m, a_start, m_start, picked, count16, d_chunk0, d_key;
     vgl_dev<uint32_t> idx2;                                         // CSR positions in sorted order (layouts with edge values)
-    vgl_dev<char> sort_tmp, scan_tmp;
+    vgl_scratch sort_tmp, scan_tmp;
     VGL_TRY(seg_first.alloc(st, (size_t)nkeys + 1));
     VGL_TRY(seg_end.alloc(st, (size_t)nkeys + 1));
     VGL_TRY(nch_a.alloc(st, (size_t)nseg + 1));
@@ -286,23 +286,15 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
                            row_base, gather_rows, skip_self, nG, nseg, a_bits, keys, packed, (const uint32_t *)count16, (uint32_t)std::max(fuse_min_edges, 1), nA16, (uint32_t)row_off);
         VGL_HIP_TRY(hipGetLastError());
         trace.mark("keys kernel");
-        int bits = 1;
-        while ((1ull << bits) <= (unsigned long long)nkeys) bits++;      // every key, the sentinel nseg and the fused range behind it, must be representable
-        size_t need = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys.p, keys2.p, packed.p, packed2.p, (size_t)E, 0, bits, st));
-        VGL_TRY(sort_tmp.alloc(st, std::max<size_t>(need, 16)));
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, need, keys.p, keys2.p, packed.p, packed2.p, (size_t)E, 0, bits, st));
+        const int bits = vgl_key_bits(nkeys);                        // every key, the sentinel nseg and the fused range behind it, must be representable
+        VGL_TRY(vgl_sort_pairs(c, sort_tmp, keys.p, keys2.p, packed.p, packed2.p, (size_t)E, 0, bits));
         trace.mark("sort (block pair, packed ids)");
         if (keep_edge_index) {                                      // same keys, same stable sort: the CSR positions land in the order of the entries
             VGL_HIP_TRY(hipStreamSynchronize(st));
             packed.reset();
             VGL_TRY(idx2.alloc(st, (size_t)E));
-            size_t need2 = 0;
             VGL_TRY(keys3.alloc(st, (size_t)E));
-            rocprim::counting_iterator<uint32_t> positions(0);
-            VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need2, keys.p, keys3.p, positions, idx2.p, (size_t)E, 0, bits, st));
-            if (need2 > need) VGL_FAIL("blocked_plan_build: radix sort scratch grew between two calls of the same size");
-            VGL_HIP_TRY(rocprim::radix_sort_pairs(sort_tmp.p, need2, keys.p, keys3.p, positions, idx2.p, (size_t)E, 0, bits, st));
+            VGL_TRY(vgl_sort_pairs(c, sort_tmp, keys.p, keys3.p, vgl_counting<uint32_t>(0), idx2.p, (size_t)E, 0, bits));
             VGL_HIP_TRY(hipStreamSynchronize(st));
             keys3.reset();
             trace.mark("sort edge positions");
@@ -314,13 +306,8 @@ static int vgl_blocked_build_piece(vgl_hip_ctx *c, const vgl_dir_csr &dir, int32
     hipLaunchKernelGGL(vgl_k_blk_nchunks, dim3((unsigned)std::min<int64_t>(4096, vgl_ceil_div((int64_t)nseg + 1, VGL_BLOCK))), dim3(VGL_BLOCK), 0, st, nG, nA,
                        (const uint32_t *)seg_first, (const uint32_t *)seg_end, nch_a, nch_m);
     VGL_HIP_TRY(hipGetLastError());
-    {
-        size_t need = 0;
-        VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, nch_a.p, a_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
-        VGL_TRY(scan_tmp.alloc(st, std::max<size_t>(need, 16)));
-        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, need, nch_a.p, a_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
-        VGL_HIP_TRY(rocprim::exclusive_scan(scan_tmp.p, need, nch_m.p, m_start.p, 0u, (size_t)nseg + 1, rocprim::plus<uint32_t>(), st));
-    }
+    VGL_TRY(vgl_exclusive_scan(c, scan_tmp, nch_a.p, a_start.p, (size_t)nseg + 1));
+    VGL_TRY(vgl_exclusive_scan(c, scan_tmp, nch_m.p, m_start.p, (size_t)nseg + 1));
     trace.mark("runs, chunk counts, scans");
     // chunk ranges of the blocks on both sides -> host
     hipLaunchKernelGGL(vgl_k_blk_pick, dim3(8), dim3(256), 0, st, (int)nA + 1, nG, (const uint32_t *)a_start, picked);

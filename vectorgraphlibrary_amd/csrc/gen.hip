@@ -1,10 +1,9 @@
 // gen.hip -- device-side synthetic inputs (RMAT / uniform / weights), COO->CSR build, row partitioning.
 // Graph construction is offline in the reference (import is not part of any timed region,
-// vgl_runtime.hpp:27-60), so the sort/scan/select here use rocPRIM library primitives; the hot-path
+// vgl_runtime.hpp:27-60), so the sort/scan/select here are the library primitives of vgl_prim.h; the hot-path
 // kernels (advance / GNF / reduce / fused algorithm steps) are hand-written in the other files.
-#include "vgl_hip_internal.h"
+#include "vgl_prim.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 // ---- counter-based RNG: identical integer arithmetic on host and device (spec in DESIGN.md) ----
 __host__ __device__ static inline uint64_t vgl_splitmix64(uint64_t x)
@@ -218,17 +217,11 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
     // (first touch, ~14 ms per GB, and the allocator's stalls) in front of 60 ms of kernels while the build before it took and returned device memory directly
     vgl_dev<int64_t> b_kept, b_sorted, b_nkept;
     vgl_dev<int32_t> b_keys, b_keys_sorted;
-    vgl_dev<char> b_temp;
-    size_t temp_bytes = 0, need = 0;
+    vgl_scratch temp;                                                 // one block, grown across the select, the sort and the scan
     VGL_TRY(b_kept.alloc(st, (size_t)count));
     VGL_TRY(b_nkept.alloc(st, 1));
     int64_t *kept_idx = b_kept, *d_nkept = b_nkept;
-    rocprim::counting_iterator<int64_t> iota(0);
-    vgl_in_range pred{d_src, row_begin, row_end};
-    VGL_HIP_TRY(rocprim::select(nullptr, need, iota, kept_idx, (size_t *)d_nkept, (size_t)count, pred, st));
-    temp_bytes = need;
-    VGL_TRY(b_temp.alloc(st, temp_bytes ? temp_bytes : 16));
-    VGL_HIP_TRY(rocprim::select(b_temp.p, temp_bytes, iota, kept_idx, (size_t *)d_nkept, (size_t)count, pred, st));
+    VGL_TRY(vgl_select(c, temp, vgl_counting<int64_t>(0), kept_idx, (size_t *)d_nkept, (size_t)count, vgl_in_range{d_src, row_begin, row_end}));
     int64_t nkept = 0;
     VGL_HIP_TRY(hipMemcpyAsync(&nkept, d_nkept, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     VGL_HIP_TRY(hipStreamSynchronize(st));
@@ -244,21 +237,13 @@ int vgl_hip_coo_to_csr(vgl_hip_ctx *c, int32_t V, int64_t count, const int32_t *
                            keys, (unsigned long long *)(d_rowptr + 1));
         VGL_HIP_TRY(hipGetLastError());
         // 3. stable radix sort by row (LSD radix sort is stable => adjacency keeps input order)
-        int bits = 1;
-        while (bits < 31 && (1LL << bits) < (int64_t)nrows) bits++;
-        need = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys, keys_sorted, kept_idx, sorted_idx, (size_t)nkept, 0, bits, st));
-        if (need > temp_bytes) { temp_bytes = need; VGL_TRY(b_temp.alloc(st, temp_bytes)); }
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(b_temp.p, need, keys, keys_sorted, kept_idx, sorted_idx, (size_t)nkept, 0, bits, st));
+        VGL_TRY(vgl_sort_pairs(c, temp, keys, keys_sorted, kept_idx, sorted_idx, (size_t)nkept, 0, vgl_index_bits(nrows)));
         // 4. adjacency + optional permutation
         hipLaunchKernelGGL(vgl_k_gather<int32_t>, dim3(vgl_grid_for(nkept)), dim3(VGL_BLOCK), 0, st, nkept, sorted_idx, d_dst, d_adj);
         VGL_HIP_TRY(hipGetLastError());
         if (d_perm) VGL_HIP_TRY(hipMemcpyAsync(d_perm, sorted_idx, sizeof(int64_t) * (size_t)nkept, hipMemcpyDeviceToDevice, st));
         // 5. row offsets: inclusive scan of the histogram stored at rowptr[1..nrows]
-        need = 0;
-        VGL_HIP_TRY(rocprim::inclusive_scan(nullptr, need, d_rowptr + 1, d_rowptr + 1, (size_t)nrows, rocprim::plus<int64_t>(), st));
-        if (need > temp_bytes) { temp_bytes = need; VGL_TRY(b_temp.alloc(st, temp_bytes)); }
-        VGL_HIP_TRY(rocprim::inclusive_scan(b_temp.p, need, d_rowptr + 1, d_rowptr + 1, (size_t)nrows, rocprim::plus<int64_t>(), st));
+        VGL_TRY(vgl_inclusive_scan(c, temp, d_rowptr + 1, d_rowptr + 1, (size_t)nrows));
     }
     VGL_HIP_TRY(hipStreamSynchronize(st));
     return 0;
@@ -292,16 +277,13 @@ int vgl_hip_degree_order_from_degrees(vgl_hip_ctx *c, int32_t V, const uint32_t 
     hipStream_t st = c->stream;
     vgl_dev<uint32_t> keys, keys_out;
     vgl_dev<int32_t> ids;
-    vgl_dev<char> temp;
-    size_t need = 0;
+    vgl_scratch temp;
     VGL_TRY(keys.alloc(st, (size_t)V));
     VGL_TRY(keys_out.alloc(st, (size_t)V));
     VGL_TRY(ids.alloc(st, (size_t)V));
     hipLaunchKernelGGL(vgl_k_order_keys, dim3(vgl_grid_for(V)), dim3(VGL_BLOCK), 0, st, V, deg, keys, ids);
     VGL_HIP_TRY(hipGetLastError());
-    VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, keys.p, keys_out.p, ids.p, d_bwd, (size_t)V, 0, 32, st));
-    VGL_TRY(temp.alloc(st, need ? need : 16));
-    VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, need, keys.p, keys_out.p, ids.p, d_bwd, (size_t)V, 0, 32, st));
+    VGL_TRY(vgl_sort_pairs(c, temp, keys.p, keys_out.p, ids.p, d_bwd, (size_t)V, 0, 32));
     hipLaunchKernelGGL(vgl_k_invert, dim3(vgl_grid_for(V)), dim3(VGL_BLOCK), 0, st, V, d_bwd, d_fwd);
     VGL_HIP_TRY(hipGetLastError());
     VGL_HIP_TRY(hipStreamSynchronize(st));

@@ -21,6 +21,7 @@
 // capacity; appends are staged per wave in LDS and cost one returning atomic per 64 or more rows.  No cooperative launch, no grid barrier.
 #include "vgl_simple.h"
 #include "vgl_rowclass.h"
+#include "vgl_prim.h"
 #include <cstring>
 #include <algorithm>
 #include <climits>
@@ -243,10 +244,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_relabel(int32_t V, int32_
     }
 }
 // ---- after the loop ----
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_iota(int32_t V, int32_t *out)
-{
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) out[v] = (int32_t)v;
-}
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_id(int32_t V, const int32_t *comp, int32_t *minid)      // minid[c] starts as c
 {
     for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) {
@@ -357,7 +354,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     }
 
     if (V > 0 && ne == 0 && d_component) {
-        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_component);
+        hipLaunchKernelGGL(vgl_k_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_component);
         VGL_HIP_TRY(hipGetLastError());
     }
     if (ne == 0) {
@@ -451,7 +448,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
 
     // ---- the smallest vertex id of every component; the weight of the forest ----
     if (d_component) {
-        hipLaunchKernelGGL(vgl_k_msf_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, root.p);
+        hipLaunchKernelGGL(vgl_k_iota, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, root.p);
         hipLaunchKernelGGL(vgl_k_msf_min_id, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, root.p);
         hipLaunchKernelGGL(vgl_k_msf_component, dim3(vgl_grid(V, VGL_BLOCK, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)comp.p, (const int32_t *)root.p, d_component);
         VGL_HIP_TRY(hipGetLastError());

@@ -2,7 +2,7 @@
 // classes merge into one coarse entry that carries the sum of their weights (their number without weights).  The row merge next to the row filter of
 // subgraph.hip.  The contract is written out in include/vgl_hip.h; DESIGN section 25 has the kernels, their bounds and the bytes model.
 //
-// Vertex side: one validation pass (negative labels, the largest label), a stable rocprim radix sort of (label, vertex) over the bits the largest
+// Vertex side: one validation pass (negative labels, the largest label), a stable radix sort of (label, vertex) over the bits the largest
 // label needs, head flags and their inclusive scan (the coarse id = the rank of the label), a scatter (cluster_of, label_of, member_ptr; the sorted
 // vertices ARE `members`) and the sizes.  Per planned direction member_off = the exclusive scan of the members' row lengths in member order: flat
 // entry j of coarse row c finds its member by a binary search of member_off within the cluster, the row's volume is a difference of two of its values.
@@ -11,13 +11,13 @@
 //   short   8 lanes per row: rank-counting among the gathered coarse far ends, a chunk of 8 in registers at a time, shuffles within the team
 //   wave    a wavefront per row, table: a workgroup per row: the far ends staged in LDS, a bitonic sort, an in-place compaction of the distinct keys
 //           with the team's rank, then (fill) one LDS int64 sum per distinct key, added to with LDS atomics after a binary search of the key
-//   sorted  64-bit keys  c << 32 | c(w)  paired with the weight: rocprim radix_sort_pairs + reduce_by_key in pieces of consecutive rows under
+//   sorted  64-bit keys  c << 32 | c(w)  paired with the weight: a radix sort of pairs + a reduce by key (vgl_prim.h) in pieces of consecutive rows under
 //           VGL_QUOT_SORT_CAP_MB (a row above the cap is a piece of its own); the runs of row c are placed at the row's start
 // FILL = false counts the distinct entries of every row (a scan makes the rowptr), FILL = true writes adj and count.  Every row has one owner; no atomic
 // touches an output array; integer sums only.
 #include "vgl_rowclass.h"
+#include "vgl_prim.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <vector>
 
@@ -90,10 +90,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_quot_check(int32_t V, const i
         mx = x > mx ? x : mx;
     }
     if (vgl_lane() == 0 && mx > 0) atomicMax(cnt + QC_MAXL, (unsigned long long)mx);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_quot_iota(int32_t V, int32_t *ids)
-{
-    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK) ids[v] = (int32_t)v;
 }
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_quot_heads(int32_t V, const uint32_t *sorted_label, int32_t *head)
 {
@@ -433,21 +429,17 @@ int quot_sorted(vgl_hip_ctx *c, const vgl_hip_quotient_plan *p, int d, const quo
     hipStream_t st = c->stream;
     const char *slot = FILL ? "quot_fill_sorted" : "quot_count_sorted";
     const size_t cap = (size_t)std::max<int64_t>(D.piece_keys, 1);
-    int end_bit = 32;
-    while (end_bit < 64 && ((int64_t)p->Vc >> (end_bit - 32)) != 0) end_bit++;
+    const int end_bit = 32 + vgl_key_bits((uint64_t)p->Vc);         // (the row of a dropped loop's key is V' itself)
     vgl_dev<uint64_t> keys_a, keys_b;
     vgl_dev<int64_t> vals_a, vals_b, n_unique;
-    vgl_dev<char> temp;
+    vgl_scratch temp;                                                 // sized for the largest piece here: the loop allocates nothing
     VGL_TRY(keys_a.alloc(st, cap));
     VGL_TRY(keys_b.alloc(st, cap));
     VGL_TRY(vals_a.alloc(st, cap));
     VGL_TRY(vals_b.alloc(st, cap));
     VGL_TRY(n_unique.alloc(st, 1));
-    size_t temp_sort = 0, temp_reduce = 0;
-    VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_sort, keys_a.p, keys_b.p, vals_a.p, vals_b.p, cap, 0u, (unsigned)end_bit, st));
-    VGL_HIP_TRY(rocprim::reduce_by_key(nullptr, temp_reduce, keys_b.p, vals_b.p, cap, keys_a.p, vals_a.p, n_unique.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), st));
-    const size_t temp_bytes = std::max(temp_sort, temp_reduce);
-    VGL_TRY(temp.alloc(st, temp_bytes));
+    VGL_TRY(vgl_sort_pairs(c, temp, keys_a.p, keys_b.p, vals_a.p, vals_b.p, cap, 0, end_bit, VGL_SIZE_ONLY));
+    VGL_TRY(vgl_reduce_by_key(c, temp, keys_b.p, vals_b.p, cap, keys_a.p, vals_a.p, n_unique.p, VGL_SIZE_ONLY));
     const quot_view a = quot_view_of(p, d);
     for (size_t k = 0; k + 1 < D.piece.size(); k++) {
         const int64_t i0 = D.piece[k], i1 = D.piece[k + 1], nk = D.soff_h[(size_t)i1] - D.soff_h[(size_t)i0];
@@ -455,27 +447,12 @@ int quot_sorted(vgl_hip_ctx *c, const vgl_hip_quotient_plan *p, int d, const quo
         vgl_timed_launch tl(c, slot);
         hipLaunchKernelGGL(vgl_k_quot_emit, dim3(vgl_grid(nk, VGL_BLOCK, 4 * QUOT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, a, (const int32_t *)D.srows.p, (const int64_t *)D.soff.p, i0, i1, nk,
                            o.weight, keys_a.p, vals_a.p);
-        size_t need = temp_bytes;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, need, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (size_t)nk, 0u, (unsigned)end_bit, st));
-        need = temp_bytes;
-        VGL_HIP_TRY(rocprim::reduce_by_key(temp.p, need, keys_b.p, vals_b.p, (size_t)nk, keys_a.p, vals_a.p, n_unique.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), st));
+        VGL_TRY(vgl_sort_pairs(c, temp, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (size_t)nk, 0, end_bit));
+        VGL_TRY(vgl_reduce_by_key(c, temp, keys_b.p, vals_b.p, (size_t)nk, keys_a.p, vals_a.p, n_unique.p));
         hipLaunchKernelGGL(vgl_k_quot_place<FILL>, dim3(vgl_grid(nk, VGL_BLOCK, 4 * QUOT_MAX_GRID)), dim3(VGL_BLOCK), 0, st, (const uint64_t *)keys_a.p, (const int64_t *)vals_a.p,
                            (const int64_t *)n_unique.p, nk, p->Vc, o);
         VGL_HIP_TRY(hipGetLastError());
     }
-    return 0;
-}
-
-// out[0 .. n) = the exclusive scan of in[0 .. n)
-template <class T>
-int quot_excl_scan(vgl_hip_ctx *c, const char *slot, const T *in, T *out, int64_t n)
-{
-    size_t bytes = 0;
-    vgl_dev<char> temp;
-    VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), c->stream));
-    VGL_TRY(temp.alloc(c->stream, bytes));
-    vgl_timed_launch tl(c, slot);
-    VGL_HIP_TRY(rocprim::exclusive_scan(temp.p, bytes, in, out, (T)0, (size_t)n, rocprim::plus<T>(), c->stream));
     return 0;
 }
 
@@ -513,8 +490,7 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
     VGL_HIP_TRY(hipGetLastError());
     VGL_TRY(vgl_publish_counters(c, "quot_publish", cnt, QC_NCNT));
     if (c->h_counters[QC_BAD] != 0) VGL_FAIL("quotient_plan_create: a label is negative");
-    int end_bit = 1;
-    while (end_bit < 32 && (c->h_counters[QC_MAXL] >> end_bit) != 0) end_bit++;
+    const int end_bit = vgl_key_bits((uint64_t)c->h_counters[QC_MAXL]);
 
     // the stable sort of (label, vertex); the sorted vertices are `members`
     vgl_dev<uint32_t> sorted_label;
@@ -526,17 +502,15 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
     VGL_TRY(p->members.alloc(st, (size_t)V));
     VGL_TRY(p->cluster_of.alloc(st, (size_t)V));
     {
-        size_t temp_sort = 0, temp_scan = 0;
         const uint32_t *keys_in = reinterpret_cast<const uint32_t *>(d_label);
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_sort, keys_in, sorted_label.p, ids.p, p->members.p, (size_t)V, 0u, (unsigned)end_bit, st));
-        VGL_HIP_TRY(rocprim::inclusive_scan(nullptr, temp_scan, head.p, cid.p, (size_t)V, rocprim::plus<int32_t>(), st));
-        vgl_dev<char> temp;
-        VGL_TRY(temp.alloc(st, std::max(temp_sort, temp_scan)));
+        vgl_scratch temp;
+        VGL_TRY(vgl_sort_pairs(c, temp, keys_in, sorted_label.p, ids.p, p->members.p, (size_t)V, 0, end_bit, VGL_SIZE_ONLY));
+        VGL_TRY(vgl_inclusive_scan(c, temp, head.p, cid.p, (size_t)V, VGL_SIZE_ONLY));
         vgl_timed_launch tl(c, "quot_vertex");
-        hipLaunchKernelGGL(vgl_k_quot_iota, dim3(grid_v), dim3(VGL_BLOCK), 0, st, V, ids.p);
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, temp_sort, keys_in, sorted_label.p, ids.p, p->members.p, (size_t)V, 0u, (unsigned)end_bit, st));
+        hipLaunchKernelGGL(vgl_k_iota, dim3(grid_v), dim3(VGL_BLOCK), 0, st, V, ids.p);
+        VGL_TRY(vgl_sort_pairs(c, temp, keys_in, sorted_label.p, ids.p, p->members.p, (size_t)V, 0, end_bit));
         hipLaunchKernelGGL(vgl_k_quot_heads, dim3(grid_v), dim3(VGL_BLOCK), 0, st, V, (const uint32_t *)sorted_label.p, head.p);
-        VGL_HIP_TRY(rocprim::inclusive_scan(temp.p, temp_scan, head.p, cid.p, (size_t)V, rocprim::plus<int32_t>(), st));
+        VGL_TRY(vgl_inclusive_scan(c, temp, head.p, cid.p, (size_t)V));
         VGL_HIP_TRY(hipMemcpyAsync(cnt.p + QC_VC, cid.p + (V - 1), sizeof(int32_t), hipMemcpyDeviceToDevice, st));      // (the slot's upper half stays 0)
         VGL_HIP_TRY(hipGetLastError());
     }
@@ -568,7 +542,10 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
             hipLaunchKernelGGL(vgl_k_quot_member_len, dim3(grid_v), dim3(VGL_BLOCK), 0, st, V, (const int32_t *)p->members.p, csr.rowptr, scratch.p);
         }
         VGL_HIP_TRY(hipGetLastError());
-        VGL_TRY(quot_excl_scan<int64_t>(c, "quot_member_off", scratch.p, p->d[d].member_off.p, (int64_t)V + 1));
+        vgl_scratch tmp;
+        VGL_TRY(vgl_exclusive_scan(c, tmp, scratch.p, p->d[d].member_off.p, (size_t)V + 1, VGL_SIZE_ONLY));
+        vgl_timed_launch tl(c, "quot_member_off");
+        VGL_TRY(vgl_exclusive_scan(c, tmp, scratch.p, p->d[d].member_off.p, (size_t)V + 1));
     }
     {
         const quot_two two{(int32_t)Vc, p->member_ptr.p, {p->d[0].member_off.p, p->planned[1] ? p->d[1].member_off.p : nullptr}, p->b, p->table};
@@ -615,7 +592,12 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
                 vgl_timed_launch tl(c, "quot_lists");
                 hipLaunchKernelGGL(vgl_k_quot_sorted_flag, dim3(grid_c), dim3(VGL_BLOCK), 0, st, src, (int32_t)Vc, flag.p);
             }
-            VGL_TRY(quot_excl_scan<int32_t>(c, "quot_lists", flag.p, pos.p, Vc + 1));
+            {
+                vgl_scratch tmp;
+                VGL_TRY(vgl_exclusive_scan(c, tmp, flag.p, pos.p, (size_t)Vc + 1, VGL_SIZE_ONLY));
+                vgl_timed_launch tl(c, "quot_lists");
+                VGL_TRY(vgl_exclusive_scan(c, tmp, flag.p, pos.p, (size_t)Vc + 1));
+            }
             VGL_HIP_TRY(hipMemsetAsync(svol.p + D.nsorted, 0, sizeof(int64_t), st));
             {
                 vgl_timed_launch tl(c, "quot_lists");
@@ -623,21 +605,18 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
                                    svol.p);
             }
             VGL_HIP_TRY(hipGetLastError());
-            VGL_TRY(quot_excl_scan<int64_t>(c, "quot_lists", svol.p, D.soff.p, D.nsorted + 1));
+            {
+                vgl_scratch tmp;
+                VGL_TRY(vgl_exclusive_scan(c, tmp, svol.p, D.soff.p, (size_t)D.nsorted + 1, VGL_SIZE_ONLY));
+                vgl_timed_launch tl(c, "quot_lists");
+                VGL_TRY(vgl_exclusive_scan(c, tmp, svol.p, D.soff.p, (size_t)D.nsorted + 1));
+            }
             // the pieces: consecutive sorted rows under the cap; a row above the cap is a piece of its own
             D.soff_h.assign((size_t)D.nsorted + 1, 0);
             VGL_HIP_TRY(hipMemcpyAsync(D.soff_h.data(), D.soff.p, sizeof(int64_t) * ((size_t)D.nsorted + 1), hipMemcpyDeviceToHost, st));
             VGL_HIP_TRY(hipStreamSynchronize(st));
             if (D.soff_h[(size_t)D.nsorted] != skeys[d]) VGL_FAIL("quotient_plan_create: internal error (the sorted volumes do not add up)");
-            D.piece.assign(1, 0);
-            int64_t acc = 0;
-            for (int64_t i = 0; i < D.nsorted; i++) {
-                const int64_t v = D.soff_h[(size_t)i + 1] - D.soff_h[(size_t)i];
-                if (acc > 0 && acc + v > p->cap_keys) { D.piece.push_back(i); D.piece_keys = std::max(D.piece_keys, acc); acc = 0; }
-                acc += v;
-            }
-            D.piece.push_back(D.nsorted);
-            D.piece_keys = std::max(D.piece_keys, acc);
+            D.piece_keys = vgl_plan_pieces(D.nsorted, [&](int64_t i) { return D.soff_h[(size_t)i + 1] - D.soff_h[(size_t)i]; }, p->cap_keys, &D.piece);
         }
         (d == 0 ? s.sort_pieces_out : s.sort_pieces_in) = D.nsorted > 0 ? (int64_t)D.piece.size() - 1 : 0;
         // the distinct entries of every coarse row, then the rowptr
@@ -646,7 +625,12 @@ int vgl_hip_quotient_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t
         const quot_out o{scratch.p, nullptr, nullptr, nullptr, nullptr};
         VGL_TRY(quot_launch<false>(c, p.get(), d, quot_view_of(p.get(), d), o));
         VGL_TRY(quot_sorted<false>(c, p.get(), d, o));
-        VGL_TRY(quot_excl_scan<int64_t>(c, "quot_scan", scratch.p, D.rowptr.p, Vc + 1));
+        {
+            vgl_scratch tmp;
+            VGL_TRY(vgl_exclusive_scan(c, tmp, scratch.p, D.rowptr.p, (size_t)Vc + 1, VGL_SIZE_ONLY));
+            vgl_timed_launch tl(c, "quot_scan");
+            VGL_TRY(vgl_exclusive_scan(c, tmp, scratch.p, D.rowptr.p, (size_t)Vc + 1));
+        }
         VGL_HIP_TRY(hipMemcpyAsync(cnt.p + QC_E + d, D.rowptr.p + Vc, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     }
     VGL_TRY(vgl_publish_counters(c, "quot_publish", cnt, QC_NCNT));

@@ -1,8 +1,8 @@
 // simple.hip -- the simple undirected graph under the stored outgoing CSR: the one key-sort CSR builder (oriented for tri, symmetric for kcore, ktruss
 // and msf) and the handle's cache of the symmetric CSR, its edge numbering and the edge of every stored entry.  vgl_simple.h; DESIGN section 18.
 //
-// Builder: every stored entry (u, v), u != v, yields 64-bit keys  row << 32 | entry  (which ones: the key functor).  The keys are sorted (rocprim radix
-// sort) and deduplicated (rocprim unique), in pieces of consecutive rows when all of them would need more scratch than the cap; a row with more keys
+// Builder: every stored entry (u, v), u != v, yields 64-bit keys  row << 32 | entry  (which ones: the key functor).  The keys are sorted and
+// deduplicated (vgl_prim.h), in pieces of consecutive rows when all of them would need more scratch than the cap; a row with more keys
 // than the cap is a piece of its own.  The sorted keys ARE the CSR: row = high half, entry = low half, every row ascending and free of duplicates,
 // the pieces appended in row order.
 //
@@ -10,8 +10,8 @@
 // lower endpoint is u, and eid[slot]: a slot (u, v), u < v, is edge up_off[u] + its rank among the upper entries of row u; a slot (v, u) finds the slot
 // (u, v) by a binary search of row u.  eu / ev are written by the upper slots.  slot_eid: a stored entry (r, c) is found in row r by a binary search.
 #include "vgl_simple.h"
+#include "vgl_prim.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -199,7 +199,7 @@ int sg_build(vgl_hip_ctx *c, vgl_hip_graph *g, const KEYS &keys_of, int64_t cap_
     }
     const int64_t cap_keys = std::max<int64_t>(1, cap_mb * (1 << 20) / 16);
     const unsigned grid_e = vgl_grid(E, VGL_BLOCK, SG_MAX_GRID);
-    std::vector<int32_t> bounds{0, V};                                // pieces of consecutive rows
+    std::vector<int64_t> bounds{0, V};                                // pieces of consecutive rows (vgl_pieces.h)
     int64_t piece_keys = max_keys;
     if (max_keys > cap_keys) {
         vgl_dev<int32_t> per_row;
@@ -211,15 +211,7 @@ int sg_build(vgl_hip_ctx *c, vgl_hip_graph *g, const KEYS &keys_of, int64_t cap_
         VGL_HIP_TRY(hipMemcpyAsync(h.data(), per_row, sizeof(int32_t) * (size_t)V, hipMemcpyDeviceToHost, st));
         VGL_HIP_TRY(hipStreamSynchronize(st));
         per_row.reset();
-        bounds.assign(1, 0);
-        int64_t acc = 0;
-        piece_keys = 0;
-        for (int32_t v = 0; v < V; v++) {                             // greedy; a row with more keys than the cap is a piece of its own
-            if (acc > 0 && acc + h[(size_t)v] > cap_keys) { bounds.push_back(v); piece_keys = std::max(piece_keys, acc); acc = 0; }
-            acc += h[(size_t)v];
-        }
-        bounds.push_back(V);
-        piece_keys = std::max<int64_t>(std::max(piece_keys, acc), 1);
+        piece_keys = std::max<int64_t>(vgl_plan_pieces(V, [&](int64_t v) { return (int64_t)h[(size_t)v]; }, cap_keys, &bounds), 1);
     }
     vgl_dev<uint64_t> keys_a, keys_b;
     vgl_dev<unsigned long long> n_keys;
@@ -230,17 +222,13 @@ int sg_build(vgl_hip_ctx *c, vgl_hip_graph *g, const KEYS &keys_of, int64_t cap_
     VGL_TRY(n_keys.alloc(st, 1));
     VGL_TRY(n_unique.alloc(st, 1));
     VGL_TRY(adj_tmp.alloc(st, (size_t)max_keys));
-    int end_bit = 33;
-    while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < V) end_bit++;
-    size_t temp_sort = 0, temp_unique = 0;
-    VGL_HIP_TRY(rocprim::radix_sort_keys(nullptr, temp_sort, keys_a.p, keys_b.p, (size_t)piece_keys, 0, (unsigned)end_bit, st));
-    VGL_HIP_TRY(rocprim::unique(nullptr, temp_unique, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, rocprim::equal_to<uint64_t>(), st));
-    const size_t temp_bytes = std::max(temp_sort, temp_unique);
-    vgl_dev<char> temp;
-    VGL_TRY(temp.alloc(st, temp_bytes));
+    const int end_bit = 32 + vgl_index_bits(V);
+    vgl_scratch temp;                                                 // sized for the largest piece here: the loop allocates nothing
+    VGL_TRY(vgl_sort_keys(c, temp, keys_a.p, keys_b.p, (size_t)piece_keys, 0, end_bit, VGL_SIZE_ONLY));
+    VGL_TRY(vgl_unique(c, temp, keys_b.p, keys_a.p, n_unique.p, (size_t)piece_keys, VGL_SIZE_ONLY));
     int64_t base = 0;
     for (size_t pc = 0; pc + 1 < bounds.size(); pc++) {
-        const int32_t v0 = bounds[pc], v1 = bounds[pc + 1];
+        const int32_t v0 = (int32_t)bounds[pc], v1 = (int32_t)bounds[pc + 1];
         VGL_HIP_TRY(hipMemsetAsync(n_keys, 0, sizeof(unsigned long long), st));
         hipLaunchKernelGGL(vgl_k_simple_emit<KEYS>, dim3(grid_e), dim3(VGL_BLOCK), 0, st, V, E, d.rowptr, d.adj, keys_of, v0, v1, keys_a.p, n_keys.p, piece_keys);
         VGL_HIP_TRY(hipGetLastError());
@@ -250,10 +238,8 @@ int sg_build(vgl_hip_ctx *c, vgl_hip_graph *g, const KEYS &keys_of, int64_t cap_
         if ((int64_t)nk > piece_keys) VGL_FAIL((std::string(who) + ": a piece holds more keys than were counted for it").c_str());
         size_t nu = 0;
         if (nk) {
-            size_t need = temp_bytes;
-            VGL_HIP_TRY(rocprim::radix_sort_keys(temp.p, need, keys_a.p, keys_b.p, (size_t)nk, 0, (unsigned)end_bit, st));
-            need = temp_bytes;
-            VGL_HIP_TRY(rocprim::unique(temp.p, need, keys_b.p, keys_a.p, n_unique.p, (size_t)nk, rocprim::equal_to<uint64_t>(), st));
+            VGL_TRY(vgl_sort_keys(c, temp, keys_a.p, keys_b.p, (size_t)nk, 0, end_bit));
+            VGL_TRY(vgl_unique(c, temp, keys_b.p, keys_a.p, n_unique.p, (size_t)nk));
             VGL_HIP_TRY(hipMemcpyAsync(&nu, n_unique, sizeof(nu), hipMemcpyDeviceToHost, st));
             VGL_HIP_TRY(hipStreamSynchronize(st));
         }
@@ -294,19 +280,16 @@ int sg_build_edge_ids(vgl_hip_ctx *c, int32_t V, vgl_simple_cache &k)
     VGL_TRY(k.ev.alloc((size_t)ne));
     if (ne == 0) return 0;
     vgl_dev<int32_t> up, up_off;
-    vgl_dev<char> temp;
+    vgl_scratch temp;
     VGL_TRY(up.alloc(st, (size_t)V + 1));
     VGL_TRY(up_off.alloc(st, (size_t)V + 1));
-    size_t temp_bytes = 0;
-    VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, temp_bytes, up.p, up_off.p, (int32_t)0, (size_t)V + 1, rocprim::plus<int32_t>(), st));
-    VGL_TRY(temp.alloc(st, temp_bytes));
     VGL_HIP_TRY(hipMemsetAsync(k.eid, 0, sizeof(int32_t) * (size_t)(2 * ne), st));
     {
         vgl_timed_launch tl(c, "ktruss_prepare");
         hipLaunchKernelGGL(vgl_k_simple_upper, dim3(vgl_grid((int64_t)V + 1, VGL_BLOCK, SG_IDS_GRID)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)csr.rowptr.p, (const int32_t *)csr.adj.p, up.p);
     }
     VGL_HIP_TRY(hipGetLastError());
-    VGL_HIP_TRY(rocprim::exclusive_scan(temp.p, temp_bytes, up.p, up_off.p, (int32_t)0, (size_t)V + 1, rocprim::plus<int32_t>(), st));
+    VGL_TRY(vgl_exclusive_scan(c, temp, up.p, up_off.p, (size_t)V + 1));
     {
         vgl_timed_launch tl(c, "ktruss_prepare");
         hipLaunchKernelGGL(vgl_k_simple_eid, dim3(vgl_grid(csr.nnz, VGL_BLOCK, SG_IDS_GRID)), dim3(VGL_BLOCK), 0, st, V, csr.nnz, (const int64_t *)csr.rowptr.p, (const int32_t *)csr.adj.p,

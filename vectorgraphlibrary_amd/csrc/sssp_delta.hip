@@ -31,8 +31,8 @@
 #include <ctime>
 #include <cstdio>
 #include <cstdlib>
-#include <rocprim/rocprim.hpp>
 #include "vgl_blocked.h"
+#include "vgl_prim.h"
 
 constexpr int VGL_DS_BLOCKS = 2048;       // persistent grid of the relax kernel
 
@@ -734,16 +734,13 @@ int vgl_hip_sssp_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_we
     VGL_TRY(p->tickets.alloc(2 * VGL_TICKET_WORDS));
     VGL_HIP_TRY(hipMemsetAsync(p->tickets, 0, sizeof(uint32_t) * 2 * VGL_TICKET_WORDS, st));
     vgl_dev<uint32_t> flags, S;
-    vgl_dev<char> temp;
-    size_t need = 0;
+    vgl_scratch temp;
     // (the multi-gigabyte temporaries and part arrays come from the library's stream-ordered pool: fresh hipMalloc / hipFree calls of that size
     // stalled for hundreds of milliseconds in the bench, where another plan had just been released -- 357 ms for a 42 ms build)
     VGL_TRY(flags.alloc(st, (size_t)E + 1));
     VGL_TRY(S.alloc(st, (size_t)E + 1));
     hipLaunchKernelGGL(vgl_k_ds_light_flags, dim3(vgl_ds_grid(std::max<int64_t>(E, 1), 16384)), dim3(VGL_BLOCK), 0, st, E, d_weights, delta, flags);
-    VGL_HIP_TRY(rocprim::exclusive_scan(nullptr, need, flags.p, S.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
-    VGL_TRY(temp.alloc(st, need ? need : 16));
-    VGL_HIP_TRY(rocprim::exclusive_scan(temp.p, need, flags.p, S.p, 0u, (size_t)E + 1, rocprim::plus<uint32_t>(), st));
+    VGL_TRY(vgl_exclusive_scan(c, temp, flags.p, S.p, (size_t)E + 1));
     uint32_t n_light = 0;                                   // S[E] = number of light edges: sizes of the two parts
     VGL_TRY(vgl_hip_memcpy_d2h(c, &n_light, S + E, sizeof(uint32_t)));
     const int64_t part_edges[2] = {(int64_t)n_light, E - (int64_t)n_light};

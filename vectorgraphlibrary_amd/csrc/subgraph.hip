@@ -2,7 +2,7 @@
 // and fixed-fanout neighbour sampling without replacement.  The contract is written out in include/vgl_hip.h; DESIGN section 24 has the kernels, their
 // bounds and the bytes models.
 //
-// Filter plan: an exclusive scan of the vertex mask gives new_id (three launches: tile sums, their scan, the apply pass); the kept rows are counted
+// Filter plan: an exclusive scan of the vertex mask (vgl_prim.h) and a pass that marks the dropped vertices give new_id; the kept rows are counted
 // and listed per row class (vgl_rowclass.h: short 8 lanes per row, wave, workgroup) and per direction; one counting kernel per class writes the
 // number of surviving entries of every kept row, and the same scan turns the counts into the new int64 rowptr.  Two reads of the pinned counter
 // mirror (sizes of the lists; V', E'out, E'in) and one stream synchronise at the end.
@@ -18,6 +18,7 @@
 // fewer than `fanout` entries of its row have a smaller key); workgroup rows find the fanout-th smallest key by a 4 x 8-bit radix select over
 // recomputed keys (LDS histograms).  The emit is the ordered compaction of the filter.
 #include "vgl_rowclass.h"
+#include "vgl_prim.h"
 #include <cstring>
 #include <algorithm>
 
@@ -26,7 +27,7 @@ struct vgl_hip_subgraph_plan {
     int32_t V = 0, Vk = 0;
     bool planned[2] = {false, false};
     const uint8_t *keep_entry = nullptr;         // borrowed until the fill (direction 0 only)
-    vgl_dev<int32_t> new_id, old_id, lists;      // V; V'; the kept rows (parent ids) per direction and class
+    vgl_dev<int32_t> new_id, old_id, lists;      // V (+ 1: V', where the scan ends); V'; the kept rows (parent ids) per direction and class
     vgl_dev<int64_t> rowptr[2];                  // V' + 1 each
     int64_t rows[2][VGL_RC_N] = {{0, 0, 0}, {0, 0, 0}}, off[2][VGL_RC_N] = {{0, 0, 0}, {0, 0, 0}};
     vgl_hip_subgraph_stats st;
@@ -56,87 +57,15 @@ static_assert(SUB_NCNT <= C_NSLOTS && SMP_NCNT <= C_NSLOTS, "the counters are mi
 
 bool sub_sharded(const vgl_hip_graph *g) { return g->row_begin != 0 || g->row_end != g->V; }
 
-// ---- exclusive scan of n values of a source S into S (int64 sums): tile sums, the scan of the tile sums by one workgroup, the apply pass ----
-struct sub_mask_src {           // the vertex mask (nullptr: every vertex is kept) -> new_id
-    const uint8_t *keep; int32_t *new_id;
-    __device__ __forceinline__ int64_t load(int64_t i) const { return keep ? (keep[i] != 0) : 1; }
-    __device__ __forceinline__ void store(int64_t i, int64_t ex, int64_t v) const { new_id[i] = v ? (int32_t)ex : -1; }
+// ---- new_id: the exclusive scan of the vertex mask (nullptr: every vertex is kept), then -1 for the dropped vertices ----
+struct sub_keep_src {           // element v of the scan's input; element V is 0, so that the scan's last output is the number of kept vertices
+    const uint8_t *keep; int32_t V;
+    __device__ __forceinline__ int32_t operator()(int64_t v) const { return v < V && (!keep || keep[v] != 0); }
 };
-struct sub_i64_src {            // counts -> offsets (in == out is allowed: every element is read and written by the same thread)
-    const int64_t *in; int64_t *out;
-    __device__ __forceinline__ int64_t load(int64_t i) const { return in[i]; }
-    __device__ __forceinline__ void store(int64_t i, int64_t ex, int64_t) const { out[i] = ex; }
-};
-template <class S>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_sums(S s, int64_t n, int64_t tiles, int64_t *bsum)
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_drop(int32_t V, const uint8_t *keep, int32_t *new_id)
 {
-    __shared__ int64_t sm[VGL_WAVES];
-    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {         // (uniform over the workgroup)
-        int64_t sum = 0;
-#pragma unroll
-        for (int j = 0; j < VGL_EPT; j++) {
-            const int64_t i = t * VGL_TILE + j * VGL_BLOCK + threadIdx.x;
-            if (i < n) sum += s.load(i);
-        }
-        sum = vgl_block_reduce_add(sum, sm);
-        if (threadIdx.x == 0) bsum[t] = sum;
-    }
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_top(int64_t tiles, int64_t *bsum, unsigned long long *total)
-{
-    __shared__ int64_t sm[VGL_WAVES];
-    int64_t carry = 0;
-    for (int64_t base = 0; base < tiles; base += VGL_BLOCK) {         // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x;
-        const int64_t v = i < tiles ? bsum[i] : 0;
-        int64_t tot = 0;
-        const int64_t ex = vgl_block_excl_add(v, sm, &tot);
-        if (i < tiles) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = (unsigned long long)carry;
-}
-template <class S>
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_sub_scan_apply(S s, int64_t n, int64_t tiles, const int64_t *bsum)
-{
-    __shared__ int64_t sm[VGL_WAVES];
-    for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {         // (uniform over the workgroup)
-        const int64_t i0 = t * VGL_TILE + (int64_t)threadIdx.x * VGL_EPT;
-        int64_t v[VGL_EPT], sum = 0;
-#pragma unroll
-        for (int j = 0; j < VGL_EPT; j++) {
-            v[j] = i0 + j < n ? s.load(i0 + j) : 0;
-            sum += v[j];
-        }
-        int64_t tot = 0;
-        int64_t ex = vgl_block_excl_add(sum, sm, &tot) + bsum[t];
-#pragma unroll
-        for (int j = 0; j < VGL_EPT; j++) {
-            if (i0 + j < n) s.store(i0 + j, ex, v[j]);
-            ex += v[j];
-        }
-    }
-}
-// n >= 1 values; *total receives their sum; bsum is scratch of ceil(n / VGL_TILE) entries
-template <class S>
-int sub_scan(vgl_hip_ctx *c, const char *slot, const S &s, int64_t n, int64_t *bsum, unsigned long long *total)
-{
-    const int64_t tiles = vgl_ceil_div(n, VGL_TILE);
-    const unsigned grid = vgl_grid(tiles, 1, 4 * SUB_MAX_GRID);
-    {
-        vgl_timed_launch tl(c, slot);
-        hipLaunchKernelGGL(vgl_k_sub_scan_sums<S>, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, s, n, tiles, bsum);
-    }
-    {
-        vgl_timed_launch tl(c, slot);
-        hipLaunchKernelGGL(vgl_k_sub_scan_top, dim3(1), dim3(VGL_BLOCK), 0, c->stream, tiles, bsum, total);
-    }
-    {
-        vgl_timed_launch tl(c, slot);
-        hipLaunchKernelGGL(vgl_k_sub_scan_apply<S>, dim3(grid), dim3(VGL_BLOCK), 0, c->stream, s, n, tiles, (const int64_t *)bsum);
-    }
-    VGL_HIP_TRY(hipGetLastError());
-    return 0;
+    for (int64_t v = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; v < V; v += (int64_t)gridDim.x * VGL_BLOCK)
+        if (keep[v] == 0) new_id[v] = -1;
 }
 
 // ---- the kept rows per direction and class ----
@@ -425,11 +354,20 @@ int vgl_hip_subgraph_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const uint8_t
     memset(&p->st, 0, sizeof(p->st));
 
     vgl_dev<unsigned long long> cnt;
-    vgl_dev<int64_t> bsum;
+    vgl_scratch tmp;                                                  // of the scans
     VGL_TRY(vgl_open_counters(c, &cnt, SUB_NCNT));
-    VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div((int64_t)V + 1, VGL_TILE)));
-    VGL_TRY(p->new_id.alloc(st, (size_t)V));
-    VGL_TRY(sub_scan(c, "sub_scan", sub_mask_src{d_keep_vertex, p->new_id.p}, (int64_t)V, bsum.p, cnt + SUB_VK));
+    VGL_TRY(p->new_id.alloc(st, (size_t)V + 1));
+    const auto kept = vgl_computed(sub_keep_src{d_keep_vertex, V});
+    VGL_TRY(vgl_exclusive_scan(c, tmp, kept, p->new_id.p, (size_t)V + 1, VGL_SIZE_ONLY));
+    {
+        vgl_timed_launch tl(c, "sub_scan");
+        VGL_TRY(vgl_exclusive_scan(c, tmp, kept, p->new_id.p, (size_t)V + 1));
+    }
+    VGL_HIP_TRY(hipMemcpyAsync(cnt.p + SUB_VK, p->new_id.p + V, sizeof(int32_t), hipMemcpyDeviceToDevice, st));      // (the slot's upper half stays 0)
+    if (d_keep_vertex) {
+        vgl_timed_launch tl(c, "sub_scan");
+        hipLaunchKernelGGL(vgl_k_sub_drop, dim3(vgl_grid(V, VGL_BLOCK, SUB_MAX_GRID)), dim3(VGL_BLOCK), 0, st, V, d_keep_vertex, p->new_id.p);
+    }
     const sub_rows_src src{V, p->new_id.p, {g->out.rowptr, p->planned[1] ? g->in.rowptr : nullptr}, b};
     {
         vgl_timed_launch tl(c, "sub_scan");
@@ -473,7 +411,12 @@ int vgl_hip_subgraph_plan_create(vgl_hip_ctx *c, vgl_hip_graph *g, const uint8_t
             VGL_TRY(p->rowptr[d].alloc(st, (size_t)Vk + 1));
             VGL_HIP_TRY(hipMemsetAsync(p->rowptr[d].p + Vk, 0, sizeof(int64_t), st));      // (every other entry is written by its row's owner)
             VGL_TRY(sub_launch<false>(c, p.get(), d, sub_dir_of(p.get(), d), sub_out{p->rowptr[d].p, nullptr, nullptr, nullptr}));
-            VGL_TRY(sub_scan(c, "sub_scan", sub_i64_src{p->rowptr[d].p, p->rowptr[d].p}, Vk + 1, bsum.p, cnt + SUB_KEPT + d));
+            VGL_TRY(vgl_exclusive_scan(c, tmp, p->rowptr[d].p, p->rowptr[d].p, (size_t)Vk + 1, VGL_SIZE_ONLY));
+            {
+                vgl_timed_launch tl(c, "sub_scan");
+                VGL_TRY(vgl_exclusive_scan(c, tmp, p->rowptr[d].p, p->rowptr[d].p, (size_t)Vk + 1));
+            }
+            VGL_HIP_TRY(hipMemcpyAsync(cnt.p + SUB_KEPT + d, p->rowptr[d].p + Vk, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         }
         VGL_TRY(vgl_publish_counters(c, "sub_publish", cnt, SUB_NCNT));
         s.entries_kept_out = c->h_counters[SUB_KEPT + 0];
@@ -621,11 +564,11 @@ int vgl_hip_sample_neighbors(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_
     memset(&out, 0, sizeof(out));
     out.seeds = n;
     vgl_dev<unsigned long long> cnt;
-    vgl_dev<int64_t> count, bsum;
+    vgl_dev<int64_t> count;
+    vgl_scratch tmp;
     vgl_rc_lists<vgl_rc_bounded> L;
     VGL_TRY(vgl_open_counters(c, &cnt, SMP_NCNT));
     VGL_TRY(count.alloc(st, (size_t)n + 1));
-    VGL_TRY(bsum.alloc(st, (size_t)vgl_ceil_div(n + 1, VGL_TILE)));
     VGL_HIP_TRY(hipMemsetAsync(count.p + n, 0, sizeof(int64_t), st));
     smp_src src{g->V, csr.rowptr, d_seeds, fanout, b, count.p};
     VGL_TRY(L.count(c, "sample_count", "sample_publish", src, n, SUB_MAX_GRID, cnt.p, SMP_NCNT, SMP_ROWS, SMP_BAD, SMP_EXAM, n, "sample_neighbors: a seed is outside [0, V)",
@@ -634,7 +577,12 @@ int vgl_hip_sample_neighbors(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *d_
     out.rows_short = rows[0]; out.rows_wave = rows[1]; out.rows_wg = rows[2];
     out.entries_examined = c->h_counters[SMP_EXAM];
     // from here on the outputs are written
-    VGL_TRY(sub_scan(c, "sample_count", sub_i64_src{count.p, d_rowptr}, n + 1, bsum.p, cnt + SMP_TOTAL));
+    VGL_TRY(vgl_exclusive_scan(c, tmp, count.p, d_rowptr, (size_t)n + 1, VGL_SIZE_ONLY));
+    {
+        vgl_timed_launch tl(c, "sample_count");
+        VGL_TRY(vgl_exclusive_scan(c, tmp, count.p, d_rowptr, (size_t)n + 1));
+    }
+    VGL_HIP_TRY(hipMemcpyAsync(cnt.p + SMP_TOTAL, d_rowptr + n, sizeof(int64_t), hipMemcpyDeviceToDevice, st));
     if (n > 0) {
         src.count = nullptr;                                          // (the seeds are validated and counted)
         VGL_TRY(L.fill(c, "sample_count", src, n, SUB_MAX_GRID, 1, nullptr, cnt + SMP_TAIL));

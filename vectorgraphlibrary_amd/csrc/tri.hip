@@ -17,8 +17,8 @@
 // Hits are summed in registers, per wave, then one 64-bit atomic per wave.  With per-vertex counts (template parameter) the witness takes one atomic
 // per hit, b one per edge, a one per edge (light) or per unit (table, huge); without them none of these atomics exist in the kernel.
 #include "vgl_simple.h"
+#include "vgl_prim.h"
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -242,11 +242,8 @@ int tri_build_classes(vgl_hip_ctx *c, vgl_tri_cache *p, const int64_t key[4])
         VGL_HIP_TRY(hipMemsetAsync(sizes, 0, sizeof(int32_t) * TRI_NCLS, st));
         hipLaunchKernelGGL(vgl_k_tri_classify, dim3(vgl_grid(V, VGL_BLOCK, 16384)), dim3(VGL_BLOCK), 0, st, V, (const int64_t *)p->csr.rowptr.p, p->b, k_in, ids, sizes);
         VGL_HIP_TRY(hipGetLastError());
-        size_t need = 0;
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32, st));
-        vgl_dev<char> temp;
-        VGL_TRY(temp.alloc(st, need));
-        VGL_HIP_TRY(rocprim::radix_sort_pairs(temp.p, need, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32, st));
+        vgl_scratch temp;
+        VGL_TRY(vgl_sort_pairs(c, temp, k_in.p, k_out.p, ids.p, p->rows.p, (size_t)V, 0, 32));
         VGL_HIP_TRY(hipMemcpyAsync(p->size, sizes, sizeof(p->size), hipMemcpyDeviceToHost, st));
         VGL_HIP_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < TRI_NCLS; k++) p->off[k + 1] = p->off[k] + p->size[k];
