@@ -1093,6 +1093,83 @@ int vgl_hip_quotient_plan_fill(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan, in
                                int64_t *d_count);
 int vgl_hip_quotient_plan_destroy(vgl_hip_ctx *ctx, vgl_hip_quotient_plan *plan);
 
+/* Louvain move rounds (`louvain`): one level of a search for a partition of high modularity by synchronous INTEGER move rounds.  The reference has
+ * nothing of the kind, so this comment is the contract.  No floating point takes part in any decision; no result depends on an atomic or launch
+ * order; every loop has a bound; every output is a function of the graph in its own numbering, the weights, seed, max_rounds and min_gain_den, and
+ * of no switch.  Unlike mis the result is NOT invariant under renumbering: ties and the swap guard go by the graph's own ids.  Only the level is
+ * here: the multi-level run (the quotient of a level's graph by its result as the next level's graph) is not part of the library yet.
+ *   one level (vgl_hip_louvain_move, on any handle whose stored outgoing CSR the caller vouches is symmetric): the stored CSR as it is, repeats and
+ *             loops allowed, int64 weights per stored entry (NULL = 1 each; negative or m >= 2^31 fails).  k_v = the weight of row v, loops
+ *             included; m = sum k_v; a SELF ENTRY is an entry (v, v).  Start: comm[v] = v (a community is named by a vertex id);
+ *             tot[c] = sum of k_v over the members, size[c] = their number.  Round r = 1, 2, ... <= max_rounds does, in order:
+ *             1. every vertex is evaluated against the snapshot (comm, tot, size): k(v, C) = the weight of v's non-self entries whose far end is
+ *                in C; the candidates are the communities of the non-self neighbours and A = comm[v] (k(v, A) may be 0);
+ *                score(C) = k(v, C) m - k_v tot'(C) with tot'(A) = tot[A] - k_v and tot'(C) = tot[C] otherwise; best(v) = the candidate of greatest
+ *                score, a tie to the smallest community id; v WANTS to move when best != A, score(best) > score(A) and not (size[A] == 1 and
+ *                size[best] == 1 and best > A) -- the swap guard: of two singletons that would trade places only the larger id moves.
+ *                W_r = the vertices that want to move; I_r = sum over v of k(v, A) + the weight of v's self entries;
+ *                N_r = m I_r - sum over c of tot[c]^2, the exact modularity numerator: Q = N_r / m^2.
+ *             2. if round r - 1 applied at least one move and N_r <= N_kept: the result is the kept assignment (the one before those moves),
+ *                outcome REVERTED, stop.
+ *             3. kept = comm, N_kept = N_r.  If min_gain_den D > 0, round r - 1 applied a move and N_r - N_{r-1} < floor(m^2 / D): outcome
+ *                SMALL_GAIN, the result is comm, stop (D = 0 disables the test).
+ *             4. W_r == 0: outcome CONVERGED, the result is comm, stop.
+ *             5. r == max_rounds: outcome CAPPED, the result is comm (this round's moves are not applied), stop.
+ *             6. comm[v] = best(v) for the vertices that want to move and are ACTIVE in round r: active(v, r) = key(v, seed + r) & 1 with mis's
+ *                key(i, s) = fmix32(i ^ fmix32(s + 0x9e3779b9)), uint32 arithmetic.  All moves of a round read the same snapshot; tot and size are
+ *                recounted.  A round may apply no move although W_r > 0; the next round is then not judged in step 2.
+ *             N_kept strictly increases over the judged rounds, so a level ends and its result is never worse than the singletons.
+ *             vgl_hip_louvain_move writes d_label (int32, V): the vertex that names v's community.  m == 0: every vertex is its own community,
+ *             CONVERGED after one round, N = 0.
+ *   Method    rows are classified once per level by length: <= VGL_LOUVAIN_SHORT (32) 8 lanes per row, rank-counting over the gathered comm[adj]
+ *             in chunks of 8 exchanged by shuffles (a head has no equal key before it, k(v, C) at a head is the sum over the equal keys);
+ *             <= VGL_LOUVAIN_WAVE (1024, at most 1024) a wavefront and <= VGL_LOUVAIN_WG (4096, at most 4096) a workgroup per row: keys staged in
+ *             LDS, a bitonic sort, the distinct keys compacted with the team's rank, one LDS int64 sum per distinct key (binary search, LDS integer
+ *             add), 12 bytes per entry; longer rows: keys  row << 32 | comm[w]  (a self entry's low half is 0xffffffff) paired with the weight,
+ *             rocprim::radix_sort_pairs and rocprim::reduce_by_key in pieces of consecutive rows whose buffers (32 bytes per key) stay under
+ *             VGL_LOUVAIN_SORT_CAP_MB (4096; 0 = no cap), then a wavefront per row scores the row's runs.  Every class picks with the team's
+ *             reductions: the greatest score, then the smallest id among the equal scores.  I and W go to int64 counters, one atomic per wave.
+ *             The apply is double-buffered (kept is the other buffer); the host reads the pinned counter mirror once per round (I, sum tot^2, W,
+ *             applied) and twice more per level; the sort scratch is sized for the largest piece before the round loop (it grows there only if a smaller
+ *             piece asks for more).
+ *   timing slots: louvain_prepare, louvain_eval_short / _wave / _wg / _sorted (one _sorted bracket per piece), louvain_reduce, louvain_apply,
+ *             louvain_publish (the counter mirror).
+ *   stats, all exact and the same on every run (the struct has room for the levels of a run; the move fills level 0): levels = 1; prepared_now = 0;
+ *             total_weight = m; modularity_num = N of the result; entries_walked = rounds x entries; rows_short / _wave / _wg / _sorted, sorted_keys, sort_pieces: the
+ *             rows of length > 0 per class, the entries of the sorted rows and their pieces at level 0 (only these follow the switches);
+ *             per level l < levels: vertices, entries, communities (of the result), rounds (evaluated), outcome, level_modularity_num = N_kept.
+ *             algorithmic_bytes = sum over the levels of [ 8 (V_l + 1) (rowptr read for k) + (4 + wb) E_l (adj, weight) + 24 V_l (k 8, comm 4,
+ *             tot 8, size 4 written) + rounds_l ((8 + wb) E_l (adj 4, the far end's comm 4, weight wb) + 44 V_l (row bounds 8, k 8, comm 4, tot 8,
+ *             size 4, best written 4; tot read by the reduce 8)) + (rounds_l - 1) 32 V_l (the apply: best 4, comm read 4 and written 4, k 8, tot 8
+ *             and size 4 recounted) ], wb = 8 where the level reads weights (iff d_weight) and 0 otherwise.
+ *             Scratch, lists and sort buffers are left out: a lower bound.
+ *   Fails, before anything is written: a NULL ctx, graph or output pointer, a sharded handle, max_rounds < 1 or > 65535, min_gain_den < 0, a
+ *             negative weight, m >= 2^31. */
+#define VGL_HIP_LOUVAIN_MAX_LEVELS 32
+enum { VGL_HIP_LOUVAIN_CONVERGED = 0, VGL_HIP_LOUVAIN_REVERTED = 1, VGL_HIP_LOUVAIN_SMALL_GAIN = 2, VGL_HIP_LOUVAIN_CAPPED = 3 };
+typedef struct {
+    int32_t levels;
+    int32_t prepared_now;       /* this call built the cache stage it needs */
+    int64_t total_weight;       /* m */
+    int64_t modularity_num;     /* N of the result: Q = N / m^2 */
+    int64_t entries_walked;     /* sum over levels of rounds x entries */
+    int64_t algorithmic_bytes;
+    int64_t rows_short;         /* level 0: rows of length > 0 per class */
+    int64_t rows_wave;
+    int64_t rows_wg;
+    int64_t rows_sorted;
+    int64_t sorted_keys;        /* level 0: the entries of the sorted rows */
+    int64_t sort_pieces;
+    int64_t vertices[VGL_HIP_LOUVAIN_MAX_LEVELS];
+    int64_t entries[VGL_HIP_LOUVAIN_MAX_LEVELS];
+    int64_t communities[VGL_HIP_LOUVAIN_MAX_LEVELS];
+    int64_t level_modularity_num[VGL_HIP_LOUVAIN_MAX_LEVELS];
+    int32_t rounds[VGL_HIP_LOUVAIN_MAX_LEVELS];
+    int32_t outcome[VGL_HIP_LOUVAIN_MAX_LEVELS];
+} vgl_hip_louvain_stats;
+int vgl_hip_louvain_move(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int64_t *d_weight, int32_t max_rounds, int64_t min_gain_den, uint32_t seed,
+                         int32_t *d_label, vgl_hip_louvain_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -1363,6 +1363,47 @@ def condensation(graph, raw=False):
     return quotient_graph(graph, comp, self_loops=False, raw=raw)
 
 
+LOUVAIN_OUTCOMES = ("converged", "reverted", "small_gain", "capped")
+
+
+def _louvain_weights(graph, weights, who):
+    if weights is None:
+        return None
+    w = torch.as_tensor(weights).to(graph.ctx.device).flatten()
+    if w.is_floating_point() or w.dtype == torch.bool:
+        raise _l.VglHipError(who + ": weights must be integers")
+    if w.numel() != graph.E:
+        raise _l.VglHipError("%s: %d weights for %d entries" % (who, w.numel(), graph.E))
+    return w.to(torch.int64).contiguous() if graph.E else torch.zeros(1, dtype=torch.int64, device=graph.ctx.device)
+
+
+def _louvain_info(st):
+    n = int(st.levels)
+    info = {k: getattr(st, k) for k, t in st._fields_ if not issubclass(t, C.Array)}
+    for k, t in st._fields_:
+        if issubclass(t, C.Array):
+            info[k] = [int(x) for x in getattr(st, k)[:n]]
+    info["outcome"] = [LOUVAIN_OUTCOMES[x] for x in info["outcome"]]
+    m = int(st.total_weight)
+    info["modularity"] = (int(st.modularity_num) / (m * m)) if m else 0.0
+    return info
+
+
+def louvain_move(graph, weights=None, max_rounds=64, min_gain_den=0, seed=0, raw=False):
+    """one level of move rounds on the stored outgoing CSR as it is (the contract of vgl_hip_louvain_move; the caller vouches that it is symmetric;
+    repeats and loops allowed).  weights: int64 per stored entry, None = 1 each.  Returns (labels, info): labels int32 [V], the ORIGINAL id of the
+    vertex that names the community, in ORIGINAL vertex order (own ids and own order with raw=True)."""
+    ctx = graph.ctx
+    w = _louvain_weights(graph, weights, "louvain_move")
+    label = ctx.empty(max(graph.V, 1), torch.int32)[:graph.V]
+    st = _l.LouvainStats()
+    _l.check(ctx.L.vgl_hip_louvain_move(ctx.h, graph.h, _ptr(w), int(max_rounds), int(min_gain_den), int(seed) & 0xFFFFFFFF, _ptr(label), C.byref(st)))
+    info = _louvain_info(st)
+    if not raw and graph.fwd is not None:
+        label = graph.to_original(graph.bwd[label.long()].to(torch.int32).contiguous())
+    return label, info
+
+
 def count_not_equal(ctx, a, b):
     r = C.c_int64()
     _l.check(ctx.L.vgl_hip_count_not_equal_u32(ctx.h, a.numel(), _ptr(a), _ptr(b), C.byref(r)))

@@ -119,6 +119,14 @@ class QuotientStats(C.Structure):
                 ("sort_pieces_in", C.c_int64), ("algorithmic_bytes", C.c_int64)]
 
 
+class LouvainStats(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("prepared_now", C.c_int32), ("total_weight", C.c_int64), ("modularity_num", C.c_int64),
+                ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64), ("rows_short", C.c_int64), ("rows_wave", C.c_int64),
+                ("rows_wg", C.c_int64), ("rows_sorted", C.c_int64), ("sorted_keys", C.c_int64), ("sort_pieces", C.c_int64),
+                ("vertices", C.c_int64 * 32), ("entries", C.c_int64 * 32), ("communities", C.c_int64 * 32),
+                ("level_modularity_num", C.c_int64 * 32), ("rounds", C.c_int32 * 32), ("outcome", C.c_int32 * 32)]
+
+
 class KhopStats(C.Structure):
     _fields_ = [("reached", C.c_int64), ("frontier_total", C.c_int64), ("edges_examined", C.c_int64), ("levels_run", C.c_int32)]
 
@@ -241,6 +249,7 @@ _SIGNATURES = {
     "vgl_hip_quotient_plan_members": [_p, _p, _p, _p],
     "vgl_hip_quotient_plan_fill": [_p, _p, _int, _p, _p, _p, _p],
     "vgl_hip_quotient_plan_destroy": [_p, _p],
+    "vgl_hip_louvain_move": [_p, _p, _p, _i32, _i64, C.c_uint32, _p, C.POINTER(LouvainStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
