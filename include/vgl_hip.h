@@ -1170,6 +1170,72 @@ typedef struct {
 int vgl_hip_louvain_move(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int64_t *d_weight, int32_t max_rounds, int64_t min_gain_den, uint32_t seed,
                          int32_t *d_label, vgl_hip_louvain_stats *stats);
 
+/* Batched personalised PageRank (`ppr`): rank with restart at a seed set, for many seed sets per pass over the adjacency, float64, with the damping
+ * and the stopping tolerance of the caller's choice; the empty seed list is plain PageRank as networkx and cuGraph define it.  vgl_hip_pr_run above is
+ * the reference's benchmark kernel (float32, damping 0.85, a fixed iteration count, one vector) and stays as it is.  The reference has no
+ * counterpart, so this comment is the contract:
+ *   graph     the stored DIRECTED graph of a handle that owns all rows.  Every stored entry counts: a multi-edge with its multiplicity, a self entry
+ *             as an edge like any other.  outdeg(u) = the number of stored outgoing entries of u.  Rank flows along outgoing entries and is PULLED
+ *             over the incoming CSR; symmetric = 1: the caller vouches that the stored graph is symmetric, and the outgoing CSR serves as both (the
+ *             rule of vgl_hip_lp_run, vgl_hip_bc_run and vgl_hip_msbfs_run).
+ *   problems  `count` seed lists on the host: list j is seeds[seed_ptr[j] .. seed_ptr[j + 1]) in the graph's numbering.  p_j = seed_weight over the
+ *             list divided by its sum, the sum added in list order in float64 (seed_weight NULL: 1 each); a vertex listed twice gets both weights.
+ *             An EMPTY list means p_j = 1 / V on every vertex: plain PageRank.
+ *   iteration from x_0 = p:   y[u] = x[u] / (double)outdeg(u), 0 for a dangling u (outdeg 0);   D = the sum of x[u] over the dangling u;
+ *                             x'[v] = alpha * (the sum of y[u] over the incoming entries (u -> v)) + (alpha * D + 1 - alpha) * p[v];
+ *             err = the sum over v of |x'[v] - x[v]|.  This is networkx's pagerank with dangling = personalization.
+ *   stopping  problems run in batches of up to 16, in the given order: batch k is list 16 k .. 16 k + 15, the last may be partial.  tol == 0: a batch
+ *             runs exactly max_iterations iterations and nothing is read back between them.  tol > 0: a batch stops after the first iteration
+ *             whose largest err over its columns is <= tol, or at max_iterations: one read of the pinned counter mirror per iteration.  Columns
+ *             that converge early keep iterating with their batch.  max_iterations == 0 returns p.
+ *   outputs   d_rank: count x V float64, source-major, indexed with int64 (like d_levels of vgl_hip_msbfs_run); d_err (optional, count float64): each
+ *             problem's last err (0 without an iteration); d_iterations (optional, count int32): the iterations its batch ran.
+ *   floating point: float64 throughout, -ffp-contract=off, no fast-math, NO floating-point atomic anywhere.  Every value has one writer, and every
+ *             sum (a row's pull, D, err) has a fixed shape that is a function of the graph, the position of the column in its batch, the batch's
+ *             width and the run-time switches only: the same call returns the same bits on every run.  Across switches, batch widths and
+ *             positions in a batch the results agree within the tolerance below, NOT bit for bit.
+ *   tolerance all terms are non-negative, so one evaluation of the map has a relative error of at most gamma_k = k u / (1 - k u) per component,
+ *             u = 2^-53, k = max(largest in-degree, number of dangling vertices) + 6 (the roundings on the longest chain into one value: the sum, and
+ *             the division, the scaling by alpha, alpha * D, + (1 - alpha), * p[v] and the teleport addition); the map contracts by alpha in L1 on
+ *             vectors of mass 1, so after t iterations  |computed - exact|_1 <= gamma_k (1 - alpha^t) / (1 - alpha).  Two float64 evaluations differ by
+ *             at most twice that.
+ * Method: per batch the state is VERTEX-MAJOR, V x W float64 with W in {1, 4, 16} the smallest width that holds the batch (unused columns are 0), so a
+ * vertex's W values are contiguous (W = 16: one 128-byte line) and a lane loads 16 bytes (two columns) where W >= 2.  One pull kernel per row class
+ * of the pull direction (VGL_PPR_SHORT 32: 8 lanes per row, VGL_PPR_WAVE 1024: a wavefront, longer: one workgroup per VGL_PPR_CHUNK 16384 entries; the
+ * lanes are entry slot x column pair, the slots folded by shuffles and, across a workgroup, in LDS in wave order; the chunk sums of a row of more than
+ * one chunk are added in chunk order by one writer).  The writer of (v, column) scales by alpha, stores x', stores y' = x' / outdeg by one IEEE
+ * division and takes the terms of err and D.  A listed p is added at the batch's seed vertices alone; the uniform p is added in the epilogue.  Every
+ * workgroup leaves its err and D terms at a place of its own, and one workgroup folds them in a fixed order, leaves alpha D + 1 - alpha for the next
+ * iteration and publishes the largest err.  A last kernel transposes the batch into d_rank.  The class lists (in ascending order inside a class) and
+ * the chunk table are built per direction by vgl_hip_ppr_prepare or the first run, cached on the handle and freed with it.
+ * stats: sources = problems run; batches = ceil(count / 16); iterations_total = the sum over the batches of the iterations run, iterations_max the
+ * largest; batches_converged = batches that the tolerance stopped (tol > 0 and the largest err <= tol, at max_iterations too); prepared_now = this call
+ * built lists; entries_walked = the sum over the batches of iterations x incoming entries: exact; max_err = the largest last err of a problem;
+ * algorithmic_bytes = per batch (16 W + 9) V (x and y = p written, the outgoing row bounds and the seed mark read) + per iteration
+ * E (4 + 8 W) (the adjacency entry and the W values of its far end) + V (21 + 24 W) (the list entry 4, the row bounds of both directions 8 + 8, the
+ * seed mark 1, x read, x' and y' written) + 8 V (W + nb) (the transpose: the batch read, nb rows written); the seeds, the partial sums and what the
+ * caches serve are left out: a lower bound.
+ * Fails, before any output is written: a sharded handle, no incoming CSR without symmetric = 1, alpha not finite or outside [0, 1), tol not finite or
+ * < 0, max_iterations < 0, count < 0, a seed_ptr that decreases, a seed outside [0, V), a seed weight that is not finite or <= 0, d_rank NULL.
+ * count == 0 succeeds and writes nothing.
+ * Not here: edge weights (the handle keeps no map from an outgoing entry to its incoming position), reverse PageRank, top-k extraction, forward push
+ * and other local methods, freezing converged columns, more than one GPU. */
+typedef struct {
+    int32_t sources;            /* problems run */
+    int32_t batches;            /* groups of up to 16 problems */
+    int32_t iterations_max;     /* most iterations of a batch */
+    int32_t batches_converged;  /* batches that the tolerance stopped */
+    int32_t prepared_now;       /* this call built the class lists */
+    int64_t iterations_total;   /* sum over the batches of the iterations run */
+    int64_t entries_walked;     /* sum over the batches of iterations x incoming entries: exact */
+    int64_t algorithmic_bytes;
+    double max_err;             /* largest last err of a problem */
+} vgl_hip_ppr_stats;
+int vgl_hip_ppr_prepare(vgl_hip_ctx *ctx, vgl_hip_graph *g, int symmetric);
+int vgl_hip_ppr_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *seeds, const int64_t *seed_ptr, const double *seed_weight, int32_t count,
+                    double alpha, int32_t max_iterations, double tol, int symmetric, double *d_rank, double *d_err, int32_t *d_iterations,
+                    vgl_hip_ppr_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

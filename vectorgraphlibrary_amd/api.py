@@ -245,6 +245,10 @@ class Graph:
         any timing (vgl_hip_msbfs_prepare)"""
         _l.check(self.ctx.L.vgl_hip_msbfs_prepare(self.ctx.h, self.h, {"out": 0, "in": 1}[direction], int(bool(symmetric))))
 
+    def prepare_ppr(self, symmetric=False):
+        """the sorted row-class lists and the chunk table of personalized_pagerank() / pagerank() now, outside any timing (vgl_hip_ppr_prepare)"""
+        _l.check(self.ctx.L.vgl_hip_ppr_prepare(self.ctx.h, self.h, int(bool(symmetric))))
+
     def prepare_kcore(self):
         """the symmetric simple CSR of core_numbers() / k_core() now, outside any timing (vgl_hip_kcore_prepare)"""
         _l.check(self.ctx.L.vgl_hip_kcore_prepare(self.ctx.h, self.h))
@@ -670,6 +674,60 @@ def eccentricity(graph, sources=None, direction="out", symmetric=False, raw=Fals
     """the largest finite distance from every source (None = every vertex), int32 in source order.  Returns (eccentricity, stats dict)."""
     res, stats = multi_source_bfs(graph, sources, direction, symmetric, raw=raw)
     return res["ecc"], stats
+
+
+def personalized_pagerank(graph, seeds, weights=None, alpha=0.85, max_iterations=100, tol=0.0, symmetric=False, raw=False, with_stats=False):
+    """batched personalised PageRank (the contract of vgl_hip_ppr_run in include/vgl_hip.h): float64 power iteration with restart at a seed set, up to
+    16 seed sets per pass over the incoming entries, dangling mass returned along the teleport vector (networkx's pagerank with
+    dangling = personalization).  seeds: a list of lists of ORIGINAL vertex ids (raw=True: the graph's own ids), one list per problem; one flat list
+    of ints means one problem per vertex; an EMPTY list is the uniform teleport, i.e. plain PageRank.  weights: None (1 each) or positive numbers in
+    the shape of seeds; a vertex listed twice gets both.  tol == 0 runs exactly max_iterations iterations; tol > 0 stops a batch of 16 once its
+    largest L1 change is <= tol.  symmetric=True: the caller vouches that every edge is stored both ways (no incoming CSR needed).  page_rank() is
+    the reference's float32 benchmark kernel and another function.  Returns rank, float64 [len(seeds), V] with the columns in ORIGINAL order unless
+    raw; with_stats: (rank, dict of the stats plus "err" float64 and "iterations" int32 per problem)."""
+    ctx = graph.ctx
+    V = graph.V
+    seeds = seeds.tolist() if torch.is_tensor(seeds) else list(seeds)
+    flat = all(not isinstance(s, (list, tuple)) and not torch.is_tensor(s) for s in seeds)
+    lists = [[int(s)] for s in seeds] if flat else [[int(v) for v in (s.tolist() if torch.is_tensor(s) else s)] for s in seeds]
+    wl = None
+    if weights is not None:
+        weights = weights.tolist() if torch.is_tensor(weights) else list(weights)
+        wl = [[float(w)] for w in weights] if flat else [[float(x) for x in (w.tolist() if torch.is_tensor(w) else w)] for w in weights]
+        if [len(w) for w in wl] != [len(s) for s in lists]:
+            raise _l.VglHipError("personalized_pagerank: weights must have the shape of seeds")
+    ids = [v for s in lists for v in s]
+    if not raw and graph.fwd is not None and ids:
+        if min(ids) < 0 or max(ids) >= V:
+            raise _l.VglHipError("personalized_pagerank: seed vertex out of range")
+        fwd = graph.fwd.cpu()
+        ids = [int(fwd[v]) for v in ids]
+    n = len(lists)
+    ptr = [0]
+    for s in lists:
+        ptr.append(ptr[-1] + len(s))
+    c_ids = (C.c_int32 * max(len(ids), 1))(*ids)
+    c_ptr = (C.c_int64 * (n + 1))(*ptr)
+    c_w = None if wl is None else (C.c_double * max(len(ids), 1))(*[x for w in wl for x in w])
+    rank = torch.empty((n, V), dtype=torch.float64, device=ctx.device)
+    err = ctx.empty(n, torch.float64)
+    its = ctx.empty(n, torch.int32)
+    st = _l.PprStats()
+    _l.check(ctx.L.vgl_hip_ppr_run(ctx.h, graph.h, c_ids, c_ptr, c_w, n, float(alpha), int(max_iterations), float(tol), int(bool(symmetric)),
+                                   _ptr(rank), _ptr(err), _ptr(its), C.byref(st)))
+    if not raw and graph.fwd is not None:
+        rank = rank[:, graph.fwd.long()]
+    if not with_stats:
+        return rank
+    info = _stats(st)
+    info["err"], info["iterations"] = err, its
+    return rank, info
+
+
+def pagerank(graph, alpha=0.85, max_iterations=100, tol=1e-10, symmetric=False, raw=False):
+    """plain PageRank as networkx defines it (uniform teleport, dangling mass spread uniformly): the empty-list problem of personalized_pagerank().
+    Returns one float64 vector of V values in ORIGINAL order unless raw.  Not page_rank(), the reference's float32 benchmark kernel."""
+    return personalized_pagerank(graph, [[]], alpha=alpha, max_iterations=max_iterations, tol=tol, symmetric=symmetric, raw=raw)[0]
 
 
 def core_numbers(graph, k_limit=0, degree=False, raw=False):

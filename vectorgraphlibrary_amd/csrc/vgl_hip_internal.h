@@ -243,6 +243,7 @@ struct vgl_hip_graph {
     vgl_cache<struct vgl_simple_cache> simple;   // k-core, k-truss, minimum spanning forest, biconnectivity: the symmetric simple CSR, its edge ids and the edge id of
                                                  // every stored entry, in three lazy stages (vgl_simple.h, simple.hip; owned)
     vgl_cache<struct vgl_sim_cache> sim;         // vertex similarity: the 2-paths that leave every vertex (sim.hip, lazy, owned)
+    vgl_cache<struct vgl_ppr_cache> ppr;         // personalised PageRank: the sorted row-class lists and the chunks of the pull directions (ppr.hip, lazy, owned)
 };
 
 struct vgl_hip_frontier {

@@ -127,6 +127,12 @@ class LouvainStats(C.Structure):
                 ("level_modularity_num", C.c_int64 * 32), ("rounds", C.c_int32 * 32), ("outcome", C.c_int32 * 32)]
 
 
+class PprStats(C.Structure):
+    _fields_ = [("sources", C.c_int32), ("batches", C.c_int32), ("iterations_max", C.c_int32), ("batches_converged", C.c_int32),
+                ("prepared_now", C.c_int32), ("iterations_total", C.c_int64), ("entries_walked", C.c_int64), ("algorithmic_bytes", C.c_int64),
+                ("max_err", C.c_double)]
+
+
 class KhopStats(C.Structure):
     _fields_ = [("reached", C.c_int64), ("frontier_total", C.c_int64), ("edges_examined", C.c_int64), ("levels_run", C.c_int32)]
 
@@ -250,6 +256,8 @@ _SIGNATURES = {
     "vgl_hip_quotient_plan_fill": [_p, _p, _int, _p, _p, _p, _p],
     "vgl_hip_quotient_plan_destroy": [_p, _p],
     "vgl_hip_louvain_move": [_p, _p, _p, _i32, _i64, C.c_uint32, _p, C.POINTER(LouvainStats)],
+    "vgl_hip_ppr_prepare": [_p, _p, _int],
+    "vgl_hip_ppr_run": [_p, _p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_dbl), _i32, _dbl, _i32, _dbl, _int, _p, _p, _p, C.POINTER(PprStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
