@@ -17,6 +17,7 @@
 // one wavefront), workgroup (<= VGL_BC_WG: 256 threads), hub (longer: one workgroup per VGL_BC_CHUNK entries, partial sums folded in chunk order by
 // a second kernel).  Every (level, class) pair is one contiguous range of the order and one launch (two for hubs).
 #include "vgl_hip_internal.h"
+#include "vgl_chunks.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -28,7 +29,6 @@ enum { BC_SHORT = 0, BC_WAVE = 1, BC_WG = 2, BC_HUB = 3 };
 constexpr int BC_G = 8;                         // lanes per short row
 constexpr int BC_LDS_BUCKETS = 4096;            // (level, class) buckets a workgroup histograms in LDS: 1024 levels
 constexpr int BC_ORDER_BLOCKS = 1024;           // workgroups of the count / scatter kernels: one contiguous vertex range each
-constexpr int BC_MAX_CHUNKS = 32768;            // grid.y of the hub kernel
 constexpr double BC_TWO53 = 9007199254740992.0;
 enum { BC_C_FWD = 0, BC_C_BWD = 1, BC_C_OVERFLOW = 2, BC_NCNT = 3 };
 
@@ -152,8 +152,8 @@ struct bc_sweep {
     double *coef, *bc, *delta_out;      // backward only (delta_out may be NULL)
     int32_t source;
     int32_t *inexact;            // forward: set when a sigma reaches 2^53
-    double *partial;             // hub kernels: n * max_chunks chunk sums
-    int32_t chunk, max_chunks;
+    double *partial;             // hub kernels: n * ch.nchunks chunk sums
+    vgl_rc_chunks ch;
 };
 
 // lane `lane` of `stride` lanes: its share of the entries [lo, hi), four entries in flight, added in entry order
@@ -227,15 +227,15 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_wg(bc_sweep a)
     if (threadIdx.x == 0) bc_finish<FWD>(a, v, sum);
 }
 
-// hub rows: workgroup (i, k) sums chunk k of row order[i] into partial[i * max_chunks + k]; grid = (n, max_chunks)
+// hub rows: workgroup (i, k) sums chunk k of row order[i] into partial[i * nchunks + k]; grid = (n, nchunks)
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_hub(bc_sweep a)
 {
     __shared__ double s_red[VGL_WAVES];
     const int32_t v = a.order[blockIdx.x];
-    const int64_t lo = a.rowptr[v] + (int64_t)blockIdx.y * a.chunk, end = a.rowptr[v + 1];
-    if (lo >= end) return;                                    // (uniform over the workgroup)
-    const double sum = vgl_block_reduce_add(bc_row_sum(a, lo, min(end, lo + a.chunk), (int)threadIdx.x, VGL_BLOCK), s_red);
-    if (threadIdx.x == 0) a.partial[(int64_t)blockIdx.x * a.max_chunks + blockIdx.y] = sum;
+    int64_t lo, hi;
+    if (!a.ch.range(a.rowptr[v], a.rowptr[v + 1], blockIdx.y, &lo, &hi)) return;      // (uniform over the workgroup)
+    const double sum = vgl_block_reduce_add(bc_row_sum(a, lo, hi, (int)threadIdx.x, VGL_BLOCK), s_red);
+    if (threadIdx.x == 0) a.partial[(int64_t)blockIdx.x * a.ch.nchunks + blockIdx.y] = sum;
 }
 // ... and one thread per hub row folds its chunk sums in chunk order
 template <bool FWD>
@@ -244,9 +244,9 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bc_hub_fold(bc_sweep a)
     const int64_t i = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x;
     if (i >= a.n) return;
     const int32_t v = a.order[i];
-    const int64_t chunks = min((int64_t)a.max_chunks, (a.rowptr[v + 1] - a.rowptr[v] + a.chunk - 1) / a.chunk);
+    const int64_t chunks = a.ch.pieces(a.rowptr[v + 1] - a.rowptr[v]);
     double sum = 0.0;
-    for (int64_t k = 0; k < chunks; k++) sum += a.partial[i * a.max_chunks + k];
+    for (int64_t k = 0; k < chunks; k++) sum += a.partial[i * a.ch.nchunks + k];
     bc_finish<FWD>(a, v, sum);
 }
 
@@ -314,7 +314,7 @@ int bc_ensure(vgl_hip_ctx *c, vgl_hip_graph *g, bool symmetric, vgl_bc_cache **o
     key[0] = vgl_env_int(c, "VGL_BC_SHORT", 32, 0, 1 << 20);
     key[1] = vgl_env_int(c, "VGL_BC_WAVE", 1024, key[0], 1 << 24);
     key[2] = vgl_env_int(c, "VGL_BC_WG", 32768, key[1], 1 << 28);
-    key[3] = vgl_env_int(c, "VGL_BC_CHUNK", 16384, 16, 1 << 28);
+    key[3] = vgl_rc_env_chunk(c, "VGL_BC_CHUNK");
     *built = false;
     if (!g->bc) g->bc.reset(new vgl_bc_cache());
     vgl_bc_cache *k = g->bc.get();
@@ -349,7 +349,7 @@ struct bc_side {
     const vgl_bc_cache::dir_classes *cls;
     int32_t *order;                     // V
     int32_t *hist, *cursor;             // bucket capacity each
-    int32_t chunk, max_chunks;          // hub rows
+    vgl_rc_chunks ch;                   // hub rows
 };
 
 template <bool FWD>
@@ -358,7 +358,7 @@ int bc_sweep_level(vgl_hip_ctx *c, const bc_side &s, bc_sweep a, const int64_t *
     static const char *const names[2][BC_NCLS] = {{"bc_backward_short", "bc_backward_wave", "bc_backward_wg", "bc_backward_hub"},
                                                   {"bc_forward_short", "bc_forward_wave", "bc_forward_wg", "bc_forward_hub"}};
     a.rowptr = s.csr->rowptr; a.adj = s.csr->adj;
-    a.chunk = s.chunk; a.max_chunks = s.max_chunks;
+    a.ch = s.ch;
     for (int k = 0; k < BC_NCLS; k++) {
         const int64_t n = start[k + 1] - start[k];
         if (n <= 0) continue;
@@ -369,7 +369,7 @@ int bc_sweep_level(vgl_hip_ctx *c, const bc_side &s, bc_sweep a, const int64_t *
         else if (k == BC_WAVE) hipLaunchKernelGGL(vgl_k_bc_wave<FWD>, dim3(bc_grid(n, VGL_WAVES)), dim3(VGL_BLOCK), 0, c->stream, a);
         else if (k == BC_WG) hipLaunchKernelGGL(vgl_k_bc_wg<FWD>, dim3((unsigned)n), dim3(VGL_BLOCK), 0, c->stream, a);
         else {
-            hipLaunchKernelGGL(vgl_k_bc_hub, dim3((unsigned)n, (unsigned)s.max_chunks), dim3(VGL_BLOCK), 0, c->stream, a);
+            hipLaunchKernelGGL(vgl_k_bc_hub, dim3((unsigned)n, (unsigned)s.ch.nchunks), dim3(VGL_BLOCK), 0, c->stream, a);
             hipLaunchKernelGGL(vgl_k_bc_hub_fold<FWD>, dim3(bc_grid(n, VGL_BLOCK)), dim3(VGL_BLOCK), 0, c->stream, a);
         }
     }
@@ -438,10 +438,8 @@ int vgl_hip_bc_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, int
         side[d].csr = d == 0 ? &g->out : &g->in;
         side[d].cls = &k->dir[d];
         side[d].order = order[d];
-        const int64_t longest = std::max<int64_t>(side[d].cls->max_row, 1);
-        side[d].chunk = (int32_t)std::max<int64_t>(k->chunk, vgl_ceil_div(longest, BC_MAX_CHUNKS));
-        side[d].max_chunks = (int32_t)vgl_ceil_div(longest, side[d].chunk);
-        partial_need = std::max(partial_need, (int64_t)side[d].cls->size[BC_HUB] * side[d].max_chunks);
+        side[d].ch = vgl_rc_chunks::of(k->chunk, side[d].cls->max_row);
+        partial_need = std::max(partial_need, (int64_t)side[d].cls->size[BC_HUB] * side[d].ch.nchunks);
     }
     if (ndir == 1) side[1] = side[0];
     VGL_TRY(partial.alloc(st, (size_t)partial_need));

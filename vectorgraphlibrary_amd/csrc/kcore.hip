@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int KC_MAX_CHUNKS = 32768;            // grid.y of the workgroup kernel
 constexpr int KC_SMALL_THREADS = 1024;
 constexpr int KC_SMALL_F = 2048;                // vertices of a frontier the one-workgroup kernel takes
 constexpr int KC_SMALL_SCAN = 65536;            // vertices it scans itself on a k change (64 per thread)
@@ -158,15 +157,16 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wave(kc_graph g, const 
     kc_walk(g.rowptr[v], g.rowptr[v + 1], vgl_lane(), 64, k, g, cnt + KC_TAIL, m_acc);
     vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
-// workgroup (row blockIdx.x, chunk blockIdx.y): `chunk` entries of the row; a workgroup past the end of its row has nothing to do
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wg(kc_graph g, const int32_t *rows, int32_t chunk, int32_t k, unsigned long long *cnt)
+// workgroup (row blockIdx.x, piece blockIdx.y of its chunks): a workgroup past the end of its row has nothing to do
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_kcore_wg(kc_graph g, const int32_t *rows, vgl_rc_chunks ch, int32_t k, unsigned long long *cnt)
 {
     const int32_t v = rows[blockIdx.x];
-    const int64_t end = g.rowptr[v + 1], lo = g.rowptr[v] + (int64_t)blockIdx.y * chunk;
+    int64_t lo, hi;
+    const bool any = ch.range(g.rowptr[v], g.rowptr[v + 1], blockIdx.y, &lo, &hi);
     if (blockIdx.y == 0 && threadIdx.x == 0) g.core[v] = k;
-    if (lo >= end) return;                                            // (uniform over the workgroup)
+    if (!any) return;                                                 // (uniform over the workgroup)
     int64_t m_acc = 0;
-    kc_walk(lo, min(end, lo + chunk), (int)threadIdx.x, VGL_BLOCK, k, g, cnt + KC_TAIL, m_acc);
+    kc_walk(lo, hi, (int)threadIdx.x, VGL_BLOCK, k, g, cnt + KC_TAIL, m_acc);
     vgl_wave_flush_add(cnt + KC_M, m_acc);
 }
 // the peel stopped at k_limit: what is still alive gets k_limit
@@ -345,7 +345,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     const vgl_simple_csr *kc = &sc->csr;
     const int32_t V = g->V;
     hipStream_t st = c->stream;
-    const int64_t chunk_env = vgl_env_int(c, "VGL_KCORE_CHUNK", 16384, 16, 1 << 28);
+    const int64_t chunk_env = vgl_rc_env_chunk(c, "VGL_KCORE_CHUNK");
     const int64_t small_m = vgl_env_int(c, "VGL_KCORE_SMALL", 8192, 0, 1 << 20);
     vgl_hip_kcore_stats out;
     memset(&out, 0, sizeof(out));
@@ -375,8 +375,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
     r.g.b = vgl_rc_env_bounds(c, "VGL_KCORE_SHORT", "VGL_KCORE_WAVE");
     for (int k_ = 0; k_ < VGL_RC_N; k_++) r.g.L.list[k_] = lists.p + (size_t)V * k_;
     r.g.L.cap = V;
-    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(kc->max_deg, 1), KC_MAX_CHUNKS));
-    const unsigned max_chunks = (unsigned)std::max<int64_t>(1, vgl_ceil_div(std::max(kc->max_deg, 1), chunk));
+    const vgl_rc_chunks ch = vgl_rc_chunks::of(chunk_env, kc->max_deg);      // grid.y of the workgroup kernel: at most VGL_RC_MAX_CHUNKS
     const int32_t *dom_ids = nullptr;                                 // the scan domain: every vertex, or the compacted alive list
     int32_t dom_n = V;
     bool limited = false;
@@ -460,7 +459,7 @@ int vgl_hip_kcore_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t k_limit, int32_t
             else if (cls == VGL_RC_WAVE)
                 hipLaunchKernelGGL(vgl_k_kcore_wave, dim3(vgl_grid(n, VGL_WAVES, (int64_t)1 << 30)), dim3(VGL_BLOCK), 0, st, r.g, rows, (int32_t)n, r.k, cnt.p);
             else
-                hipLaunchKernelGGL(vgl_k_kcore_wg, dim3((unsigned)n, max_chunks), dim3(VGL_BLOCK), 0, st, r.g, rows, chunk, r.k, cnt.p);
+                hipLaunchKernelGGL(vgl_k_kcore_wg, dim3((unsigned)n, (unsigned)ch.nchunks), dim3(VGL_BLOCK), 0, st, r.g, rows, ch, r.k, cnt.p);
         }));
         VGL_TRY(r.read());
         r.subs++;

@@ -34,7 +34,6 @@ namespace {
 
 typedef unsigned long long ms_word;
 constexpr int MS_BATCH = 64;                     // sources per batch: one bit each
-constexpr int MS_MAX_CHUNKS = 32768;             // chunks of the longest row
 constexpr int64_t MS_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
 enum {
     MS_TAIL = 0,        // + class: vertices appended to the next list of the class by this level
@@ -55,6 +54,7 @@ struct ms_out { ms_lists next; const uint8_t *cls; ms_word *cnt; };
 struct ms_level {
     const int64_t *rowptr;
     const int32_t *adj;
+    vgl_rc_chunks ch;            // of that CSR's workgroup rows
     const ms_word *cur, *seen;
     ms_word *nxt;
     ms_word active;              // pull: the batch's live bits
@@ -105,13 +105,6 @@ __device__ __forceinline__ void ms_flush_all(vgl_rc_stage *st, const ms_out &o)
     for (int c = 0; c < VGL_RC_N; c++) st[c].flush(ms_next(o, c), o.cnt + MS_TAIL + c);
 }
 
-__device__ __forceinline__ ms_word ms_wave_or(ms_word m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o);
-    return m;
-}
-
 // ---- seed ----
 __global__ __launch_bounds__(MS_BATCH) void vgl_k_msbfs_seed(const int32_t *src, int32_t nb, int32_t base, int32_t V, const int64_t *rowptr, ms_word *cur, ms_word *seen, ms_lists first,
                                                               const uint8_t *cls, ms_word *cnt, int64_t *reached, int64_t *dist_sum, int32_t *ecc, double *harmonic, int32_t *levels)
@@ -148,28 +141,32 @@ __global__ __launch_bounds__(MS_BATCH) void vgl_k_msbfs_seed(const int32_t *src,
     if (b == 0) cnt[MS_ENTRIES] = s_entries;
 }
 
-// ---- push ----
+// ---- push and pull: one team kernel each (short: 8 lanes per row, wave: a wavefront, workgroup: a workgroup per chunk of the row) ----
 // one entry of row v (its frontier word cv): the bits the far end has not seen go to its nxt word; true for the lane that found the word empty
 __device__ __forceinline__ bool ms_push_entry(const ms_level &t, ms_word cv, int32_t w)
 {
     const ms_word add = cv & ~t.seen[w];
     return add != 0 && atomicOr(t.nxt + w, add) == 0;
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_short(ms_level t, const int32_t *rows, int32_t n)
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push(const int32_t *rows, int32_t n, ms_level t)
 {
+    using T = vgl_rc_team<CLS>;
     vgl_rc_stage st[VGL_RC_N];
     vgl_rc_stage_open(st);
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    const int64_t items = T::items(n, t.ch);
+    for (int64_t at = T::begin(); at < items; at += T::stride()) {
+        const int64_t i = T::item(at);
         ms_word cv = 0;
         int64_t lo = 0, hi = 0;
-        if (i < n) {
-            const int32_t v = rows[i];
-            cv = t.cur[v];
-            lo = t.rowptr[v]; hi = t.rowptr[v + 1];
+        if (i < items) {
+            int64_t row;
+            const int64_t k = T::piece(i, t.ch, &row);
+            const int32_t v = rows[row];
+            if (T::range(t.ch, t.rowptr[v], t.rowptr[v + 1], k, &lo, &hi)) cv = t.cur[v];
         }
-        for (int64_t e = lo + gi; __any(e < hi); e += VGL_RC_G) {        // (uniform over the wave)
+        for (int64_t e0 = lo; T::together(e0 < hi); e0 += T::LANES) {  // (uniform over the wave)
+            const int64_t e = e0 + T::lane();
             int32_t w = 0;
             bool app = false;
             if (e < hi) { w = t.adj[e]; app = ms_push_entry(t, cv, w); }
@@ -178,139 +175,51 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_short(ms_level t, 
     }
     ms_flush_all(st, t.out);
 }
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wave(ms_level t, const int32_t *rows, int32_t n)
+// Short and wave rows have one writer and a staged append.  The pieces of a chunked row combine on its nxt word by atomicOr, and the one that found the
+// word empty appends the row.  A wave leaves its row as soon as it covers `want`: the short form lane by lane, the others after the wave's or.
+template <int CLS>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull(const int32_t *rows, int32_t n, ms_level t)
 {
+    using T = vgl_rc_team<CLS>;
+    const auto word_or = [](ms_word a, ms_word b) { return a | b; };
     vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    const int lane = vgl_lane();
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = rows[i];
-        const ms_word cv = t.cur[v];
-        const int64_t lo = t.rowptr[v], hi = t.rowptr[v + 1];
-        for (int64_t e0 = lo; e0 < hi; e0 += 64) {
-            const int64_t e = e0 + lane;
-            int32_t w = 0;
-            bool app = false;
-            if (e < hi) { w = t.adj[e]; app = ms_push_entry(t, cv, w); }
-            ms_append(st, app, w, t.out);
-        }
-    }
-    ms_flush_all(st, t.out);
-}
-// work item (row i / nchunks of the list, chunk i % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_push_wg(ms_level t, const int32_t *rows, int32_t n, int32_t chunk, int32_t nchunks)
-{
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    const int lane = vgl_lane();
-    const int64_t total = (int64_t)n * nchunks;
-    for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {     // (uniform over the workgroup)
-        const int32_t v = rows[it / nchunks];
-        const int64_t end = t.rowptr[v + 1], lo = t.rowptr[v] + (it % nchunks) * chunk;
-        if (lo >= end) continue;
-        const int64_t hi = min(end, lo + chunk);
-        const ms_word cv = t.cur[v];
-        for (int64_t e0 = lo + vgl_wave() * 64; e0 < hi; e0 += VGL_BLOCK) {      // (uniform over the wave)
-            const int64_t e = e0 + lane;
-            int32_t w = 0;
-            bool app = false;
-            if (e < hi) { w = t.adj[e]; app = ms_push_entry(t, cv, w); }
-            ms_append(st, app, w, t.out);
-        }
-    }
-    ms_flush_all(st, t.out);
-}
-
-// ---- pull ----
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_short(ms_level t, const int32_t *rows, int32_t n)
-{
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    const int gi = threadIdx.x & (VGL_RC_G - 1);
+    if constexpr (CLS != VGL_RC_WG) vgl_rc_stage_open(st);
+    const int64_t items = T::items(n, t.ch);
     int64_t examined = 0;
-    for (int64_t base = (int64_t)blockIdx.x * (VGL_BLOCK / VGL_RC_G); base < n; base += (int64_t)gridDim.x * (VGL_BLOCK / VGL_RC_G)) {      // (uniform over the workgroup)
-        const int64_t i = base + threadIdx.x / VGL_RC_G;
+    for (int64_t at = T::begin(); at < items; at += T::stride()) {
+        const int64_t i = T::item(at);
         int32_t v = 0;
         ms_word want = 0, acc = 0;
-        if (i < n) {
-            v = rows[i];
+        int64_t k = 0, lo, hi;
+        if (i < items) {
+            int64_t row;
+            k = T::piece(i, t.ch, &row);
+            v = rows[row];
             want = t.active & ~t.seen[v];
         }
-        if (want) {
-            const int64_t hi = t.rowptr[v + 1];
-            for (int64_t e = t.rowptr[v] + gi; e < hi; e += VGL_RC_G) {
-                acc |= t.cur[t.adj[e]];
-                examined++;
-                if ((acc & want) == want) break;
+        const bool walk = want != 0 && T::range(t.ch, t.rowptr[v], t.rowptr[v + 1], k, &lo, &hi);
+        if constexpr (CLS == VGL_RC_WG)
+            if (!walk) continue;                                      // (uniform over the workgroup)
+        if (walk) {
+            if constexpr (CLS == VGL_RC_SHORT) {
+                for (int64_t e = lo + T::lane(); e < hi; e += T::LANES) {      // (lane by lane)
+                    acc |= t.cur[t.adj[e]];
+                    examined++;
+                    if ((acc & want) == want) break;
+                }
+            } else {
+                for (int64_t e0 = lo; e0 < hi; e0 += T::LANES) {       // (uniform over the wave)
+                    const int64_t e = e0 + T::lane();
+                    if (e < hi) { acc |= t.cur[t.adj[e]]; examined++; }
+                    acc = vgl_rc_team<VGL_RC_WAVE>::butterfly(acc, word_or);
+                    if ((acc & want) == want) break;
+                }
             }
         }
-#pragma unroll
-        for (int o = VGL_RC_G / 2; o > 0; o >>= 1) acc |= __shfl_xor(acc, o);
+        if constexpr (CLS != VGL_RC_WAVE) acc = T::butterfly(acc, word_or);      // (a wave's is whole already)
         const ms_word nw = acc & want;
-        const bool app = gi == 0 && nw != 0;
-        if (app) t.nxt[v] = nw;
-        ms_append(st, app, v, t.out);
-    }
-    ms_flush_all(st, t.out);
-    vgl_wave_flush_add(t.out.cnt + MS_PULLED, examined);
-}
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wave(ms_level t, const int32_t *rows, int32_t n)
-{
-    vgl_rc_stage st[VGL_RC_N];
-    vgl_rc_stage_open(st);
-    const int lane = vgl_lane();
-    int64_t examined = 0;
-    for (int64_t i = (int64_t)blockIdx.x * VGL_WAVES + vgl_wave(); i < n; i += (int64_t)gridDim.x * VGL_WAVES) {      // (uniform over the wave)
-        const int32_t v = rows[i];
-        const ms_word want = t.active & ~t.seen[v];
-        ms_word acc = 0;
-        if (want) {                                                   // (uniform)
-            const int64_t lo = t.rowptr[v], hi = t.rowptr[v + 1];
-            for (int64_t e0 = lo; e0 < hi; e0 += 64) {
-                const int64_t e = e0 + lane;
-                if (e < hi) { acc |= t.cur[t.adj[e]]; examined++; }
-                acc = ms_wave_or(acc);
-                if ((acc & want) == want) break;
-            }
-        }
-        const ms_word nw = acc & want;
-        const bool app = lane == 0 && nw != 0;
-        if (app) t.nxt[v] = nw;
-        ms_append(st, app, v, t.out);
-    }
-    ms_flush_all(st, t.out);
-    vgl_wave_flush_add(t.out.cnt + MS_PULLED, examined);
-}
-// chunked rows: the workgroups of a row combine on its nxt word by atomicOr, and the one that found the word empty appends the row
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wg(ms_level t, const int32_t *rows, int32_t n, int32_t chunk, int32_t nchunks)
-{
-    __shared__ ms_word s_red[VGL_WAVES];
-    const int lane = vgl_lane();
-    const int64_t total = (int64_t)n * nchunks;
-    int64_t examined = 0;
-    for (int64_t it = blockIdx.x; it < total; it += gridDim.x) {     // (uniform over the workgroup)
-        const int32_t v = rows[it / nchunks];
-        const ms_word want = t.active & ~t.seen[v];
-        if (!want) continue;
-        const int64_t end = t.rowptr[v + 1], lo = t.rowptr[v] + (it % nchunks) * chunk;
-        if (lo >= end) continue;
-        const int64_t hi = min(end, lo + chunk);
-        ms_word acc = 0;
-        for (int64_t e0 = lo + vgl_wave() * 64; e0 < hi; e0 += VGL_BLOCK) {      // (uniform over the wave)
-            const int64_t e = e0 + lane;
-            if (e < hi) { acc |= t.cur[t.adj[e]]; examined++; }
-            acc = ms_wave_or(acc);
-            if ((acc & want) == want) break;
-        }
-        acc = ms_wave_or(acc);
-        __syncthreads();
-        if (lane == 0) s_red[vgl_wave()] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int k = 0; k < VGL_WAVES; k++) acc |= s_red[k];
-            const ms_word nw = acc & want;
-            if (nw != 0 && atomicOr(t.nxt + v, nw) == 0) {
+        if constexpr (CLS == VGL_RC_WG) {
+            if (T::lead() && nw != 0 && atomicOr(t.nxt + v, nw) == 0) {
                 const int k = t.out.cls[v];
 #pragma unroll
                 for (int c = 0; c < VGL_RC_N; c++)
@@ -319,8 +228,13 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msbfs_pull_wg(ms_level t, con
                         if (pos < (ms_word)t.out.next.cap[c]) t.out.next.rows[c][pos] = v;
                     }
             }
+        } else {
+            const bool app = T::lead() && nw != 0;
+            if (app) t.nxt[v] = nw;
+            ms_append(st, app, v, t.out);
         }
     }
+    if constexpr (CLS != VGL_RC_WG) ms_flush_all(st, t.out);
     vgl_wave_flush_add(t.out.cnt + MS_PULLED, examined);
 }
 
@@ -541,7 +455,7 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
     if (mode == MS_MODE_PULL && plan.pull < 0) VGL_FAIL("msbfs_run: VGL_MSBFS_MODE=pull needs the reverse CSR of the traversal direction (the incoming CSR, or symmetric = 1)");
     const char *share_env = vgl_env(c, "VGL_MSBFS_PULL_SHARE");
     const double share = (share_env && *share_env) ? atof(share_env) : 0.05;
-    const int64_t chunk_env = vgl_env_int(c, "VGL_MSBFS_CHUNK", 16384, 16, 1 << 28);
+    const int64_t chunk_env = vgl_rc_env_chunk(c, "VGL_MSBFS_CHUNK");
     vgl_msbfs_cache *k = nullptr;
     bool built = false;
     VGL_TRY(ms_ensure(c, g, plan, &k, &built));
@@ -575,15 +489,9 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
     VGL_HIP_TRY(hipStreamSynchronize(st));                            // (the caller's array is free again)
     VGL_HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(ms_word) * MS_NCNT, st));
     if (d_levels) VGL_HIP_TRY(hipMemsetAsync(d_levels, 0xFF, sizeof(int32_t) * (size_t)count * (size_t)V, st));      // -1: unreached
-    const int32_t push_chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max<int64_t>(push_cls.max_row, 1), MS_MAX_CHUNKS));
-    const int32_t push_nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max<int64_t>(push_cls.max_row, 1), push_chunk));
-    int32_t pull_chunk = 0, pull_nchunks = 0;
-    ms_lists pull_rows{};
-    if (pull_cls) {
-        pull_chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max<int64_t>(pull_cls->max_row, 1), MS_MAX_CHUNKS));
-        pull_nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max<int64_t>(pull_cls->max_row, 1), pull_chunk));
-        pull_rows = ms_lists_of(pull_cls->rows.p, pull_cls->size);
-    }
+    const vgl_rc_chunks push_ch = vgl_rc_chunks::of(chunk_env, push_cls.max_row), pull_ch = vgl_rc_chunks::of(chunk_env, pull_cls ? pull_cls->max_row : 0);
+    const ms_lists pull_rows = pull_cls ? ms_lists_of(pull_cls->rows.p, pull_cls->size) : ms_lists{};
+    const int64_t grid_cap[VGL_RC_N] = {MS_MAX_GRID, MS_MAX_GRID, 4 * MS_MAX_GRID};
     auto publish = [&](int32_t nb, int32_t base, int32_t d) -> int {
         const int64_t seq = vgl_next_seq(c);
         {
@@ -624,30 +532,16 @@ int vgl_hip_msbfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, 
             ms_level t;
             t.cur = cur; t.seen = seen; t.nxt = nxt; t.active = active;
             t.out.next = next; t.out.cls = push_cls.cls; t.out.cnt = cnt;
+            const ms_lists &from = pull ? pull_rows : now;
+            const int32_t *const rows[VGL_RC_N] = {from.rows[0], from.rows[1], from.rows[2]};
             if (!pull) {
-                t.rowptr = push_csr.rowptr; t.adj = push_csr.adj;
-                VGL_TRY(vgl_rc_launch(c, push_slot, n, [&](int cls, int64_t m) {
-                    const int32_t *rows = now.rows[cls];
-                    if (cls == VGL_RC_SHORT)
-                        hipLaunchKernelGGL(vgl_k_msbfs_push_short, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
-                    else if (cls == VGL_RC_WAVE)
-                        hipLaunchKernelGGL(vgl_k_msbfs_push_wave, dim3(vgl_grid(m, VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
-                    else
-                        hipLaunchKernelGGL(vgl_k_msbfs_push_wg, dim3(vgl_grid(m * push_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m, push_chunk, push_nchunks);
-                }));
+                t.rowptr = push_csr.rowptr; t.adj = push_csr.adj; t.ch = push_ch;
+                VGL_TRY(vgl_rc_launch_trio(c, push_slot, n, grid_cap, t.ch, vgl_k_msbfs_push<VGL_RC_SHORT>, vgl_k_msbfs_push<VGL_RC_WAVE>, vgl_k_msbfs_push<VGL_RC_WG>, rows, t));
                 out.levels_push++;
                 out.edges_push += entries;
             } else {
-                t.rowptr = pull_csr->rowptr; t.adj = pull_csr->adj;
-                VGL_TRY(vgl_rc_launch(c, pull_slot, pull_cls->size, [&](int cls, int64_t m) {
-                    const int32_t *rows = pull_rows.rows[cls];
-                    if (cls == VGL_RC_SHORT)
-                        hipLaunchKernelGGL(vgl_k_msbfs_pull_short, dim3(vgl_grid(m * VGL_RC_G, VGL_BLOCK, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
-                    else if (cls == VGL_RC_WAVE)
-                        hipLaunchKernelGGL(vgl_k_msbfs_pull_wave, dim3(vgl_grid(m, VGL_WAVES, MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m);
-                    else
-                        hipLaunchKernelGGL(vgl_k_msbfs_pull_wg, dim3(vgl_grid(m * pull_nchunks, 1, 4 * MS_MAX_GRID)), dim3(VGL_BLOCK), 0, st, t, rows, (int32_t)m, pull_chunk, pull_nchunks);
-                }));
+                t.rowptr = pull_csr->rowptr; t.adj = pull_csr->adj; t.ch = pull_ch;
+                VGL_TRY(vgl_rc_launch_trio(c, pull_slot, pull_cls->size, grid_cap, t.ch, vgl_k_msbfs_pull<VGL_RC_SHORT>, vgl_k_msbfs_pull<VGL_RC_WAVE>, vgl_k_msbfs_pull<VGL_RC_WG>, rows, t));
                 out.levels_pull++;
             }
             {

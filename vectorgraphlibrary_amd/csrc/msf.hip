@@ -28,7 +28,6 @@
 
 namespace {
 
-constexpr int MSF_MAX_CHUNKS = 32768;             // chunks of the longest row
 constexpr int64_t MSF_MAX_GRID = 2048;            // workgroups of a grid-stride kernel
 constexpr int MSF_MAX_ROUNDS = 64;                // (a run has at most ceil(log2 V) <= 31 rounds that add an edge, plus the empty one)
 constexpr int MSF_SUM_GRID = 1024;                // partials of the weight sum at most
@@ -163,20 +162,19 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wave(msf_graph g, vgl
     st[0].flush(R, cnt + MSF_TAIL + VGL_RC_WAVE);
     vgl_wave_flush_add(cnt + MSF_WALK, walked);
 }
-// work item w = (row w / nchunks of the segment, chunk w % nchunks): `chunk` entries of the row; an item past the end of its row has nothing to do.
+// work item w = (row i of the segment, piece k of its chunks): an item past the end of its row has nothing to do.
 // A row is appended by the first of its chunks that finds a crossing entry: stamp[position in the segment] = the round.
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, int32_t chunk, int32_t nchunks, int32_t round, int32_t *stamp,
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_msf_min_wg(msf_graph g, vgl_rc_ring R, unsigned long long head, int32_t n, vgl_rc_chunks ch, int32_t round, int32_t *stamp,
                                                                unsigned long long *cnt)
 {
     __shared__ unsigned long long s_red[VGL_WAVES];
-    const int64_t total = (int64_t)n * nchunks;
+    const int64_t total = (int64_t)n * ch.nchunks;
     int64_t walked = 0;
     for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {         // (uniform over the workgroup)
-        const int64_t i = w / nchunks;
+        int64_t i, k, lo, hi;
+        ch.split(w, &i, &k);
         const int32_t v = R.rows[(head + (unsigned long long)i) % R.cap];
-        const int64_t end = g.rowptr[v + 1], lo = g.rowptr[v] + (w % nchunks) * chunk;
-        if (lo >= end) continue;
-        const int64_t hi = min(end, lo + chunk);
+        if (!ch.range(g.rowptr[v], g.rowptr[v + 1], k, &lo, &hi)) continue;
         const int32_t cv = g.comp[v];
         unsigned long long m = vgl_rc_team<VGL_RC_WAVE>::min_of(msf_walk(lo + threadIdx.x, hi, VGL_BLOCK, cv, g));
         __syncthreads();
@@ -323,7 +321,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
     const int64_t E = g->out.edges;
     hipStream_t st = c->stream;
     const vgl_rc_bounds b = vgl_rc_env_bounds(c, "VGL_MSF_SHORT", "VGL_MSF_WAVE");
-    const int64_t chunk_env = vgl_env_int(c, "VGL_MSF_CHUNK", 16384, 16, 1 << 28);
+    const int64_t chunk_env = vgl_rc_env_chunk(c, "VGL_MSF_CHUNK");
     vgl_hip_msf_stats out;
     memset(&out, 0, sizeof(out));
     out.prepared_now = built ? 1 : 0;
@@ -399,8 +397,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
 
     msf_graph mg;
     mg.rowptr = sg->csr.rowptr; mg.adj = sg->csr.adj; mg.eid = sg->eid; mg.wkey = wkey; mg.comp = comp; mg.best = best;
-    const int32_t chunk = (int32_t)std::max<int64_t>(chunk_env, vgl_ceil_div(std::max(sg->csr.max_deg, 1), MSF_MAX_CHUNKS));
-    const int32_t nchunks = (int32_t)std::max<int64_t>(1, vgl_ceil_div(std::max(sg->csr.max_deg, 1), chunk));
+    const vgl_rc_chunks ch = vgl_rc_chunks::of(chunk_env, sg->csr.max_deg);
     vgl_rc_window w;                             // the live rows: [head, tail) of the rings, cumulative positions
     for (int k = 0; k < VGL_RC_N; k++) w.tail[k] = rows[k];
     const char *const slot[VGL_RC_N] = {"msf_min_short", "msf_min_wave", "msf_min_wg"};
@@ -416,7 +413,7 @@ int vgl_hip_msf_run(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_weights, in
             else if (cls == VGL_RC_WAVE)
                 hipLaunchKernelGGL(vgl_k_msf_min_wave, dim3(vgl_grid(n, VGL_WAVES, MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, cnt.p);
             else
-                hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(vgl_grid(n * nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, chunk, nchunks, round, stamp.p,
+                hipLaunchKernelGGL(vgl_k_msf_min_wg, dim3(vgl_grid(n * ch.nchunks, 1, 4 * MSF_MAX_GRID)), dim3(VGL_BLOCK), 0, st, mg, R[cls], head, (int32_t)n, ch, round, stamp.p,
                                    cnt.p);
         }));
         {

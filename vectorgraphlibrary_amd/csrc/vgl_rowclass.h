@@ -4,11 +4,12 @@
 // Here: the bounds, the windows, the per-class launch, the append staging, the class-list builder (count, check, carve, fill) and the team: what a
 // kernel that serves all three classes from one body needs of its class.  bc (four classes), tri and lp (plan-owned sorted lists) are other schemes.
 // Not on the team, because their three forms are three structures: kcore_short / wave (no grid stride, early return) and kcore_wg (2-D grid);
-// msf_min_* (offer combining in the short form, chunked workgroup rows); msbfs_push / pull_* (chunked workgroup rows).  Not on the builder:
+// msf_min_* (offer combining in the short form).  Chunked workgroup rows (vgl_chunks.h) are the team's workgroup items in msbfs_push / pull.  Not on the builder:
 // vgl_k_sub_classify / _lists (two directions and old_id in one pass), vgl_k_bicc_init / _seed (union-find and level set-up in the same pass),
 // ktruss / kcore / msbfs (vgl_wave_append lists that grow during the run).
 #pragma once
 #include "vgl_hip_internal.h"
+#include "vgl_chunks.h"
 
 // ---- classes and bounds ----
 constexpr int VGL_RC_N = 3;
@@ -67,16 +68,23 @@ static inline int vgl_rc_launch(vgl_hip_ctx *c, const char *const *slot, const v
     const int64_t n[VGL_RC_N] = {w.n(0), w.n(1), w.n(2)};
     return vgl_rc_launch(c, slot, n, launch);
 }
-// the three instantiations of a team kernel `k<CLS>(LIST list, int32_t n, args...)`: class k runs over list[k] under slot[k], on at most cap[k] workgroups
+// the three instantiations of a team kernel `k<CLS>(LIST list, int32_t n, args...)`: class k runs over list[k] under slot[k], on at most cap[k] workgroups.
+// A kernel whose workgroup rows are chunked by `wg` (it finds the chunks among its args) has wg.nchunks workgroup items per row.
+template <class LIST, class... KA, class... A>
+static inline int vgl_rc_launch_trio(vgl_hip_ctx *c, const char *const *slot, const int64_t *n, const int64_t *cap, vgl_rc_chunks wg, void (*k_short)(LIST, int32_t, KA...),
+                                     void (*k_wave)(LIST, int32_t, KA...), void (*k_wg)(LIST, int32_t, KA...), const LIST *list, const A &...args)
+{
+    void (*const k[VGL_RC_N])(LIST, int32_t, KA...) = {k_short, k_wave, k_wg};
+    const int64_t items_per_wg[VGL_RC_N] = {VGL_BLOCK / VGL_RC_G, VGL_WAVES, 1}, items_per_row[VGL_RC_N] = {1, 1, wg.nchunks};
+    return vgl_rc_launch(c, slot, n, [&](int cls, int64_t m) {
+        hipLaunchKernelGGL(k[cls], dim3(vgl_grid(m * items_per_row[cls], items_per_wg[cls], cap[cls])), dim3(VGL_BLOCK), 0, c->stream, list[cls], (int32_t)m, args...);
+    });
+}
 template <class LIST, class... KA, class... A>
 static inline int vgl_rc_launch_trio(vgl_hip_ctx *c, const char *const *slot, const int64_t *n, const int64_t *cap, void (*k_short)(LIST, int32_t, KA...),
                                      void (*k_wave)(LIST, int32_t, KA...), void (*k_wg)(LIST, int32_t, KA...), const LIST *list, const A &...args)
 {
-    void (*const k[VGL_RC_N])(LIST, int32_t, KA...) = {k_short, k_wave, k_wg};
-    const int64_t items_per_wg[VGL_RC_N] = {VGL_BLOCK / VGL_RC_G, VGL_WAVES, 1};
-    return vgl_rc_launch(c, slot, n, [&](int cls, int64_t m) {
-        hipLaunchKernelGGL(k[cls], dim3(vgl_grid(m, items_per_wg[cls], cap[cls])), dim3(VGL_BLOCK), 0, c->stream, list[cls], (int32_t)m, args...);
-    });
+    return vgl_rc_launch_trio(c, slot, n, cap, vgl_rc_chunks::whole(), k_short, k_wave, k_wg, list, args...);
 }
 template <class LIST, class... KA, class... A>
 static inline int vgl_rc_launch_trio(vgl_hip_ctx *c, const char *const *slot, const vgl_rc_window &w, const int64_t *cap, void (*k_short)(LIST, int32_t, KA...),
@@ -149,6 +157,25 @@ struct vgl_rc_team {
     static __device__ __forceinline__ int64_t item(int64_t at) { return at + (CLS == VGL_RC_SHORT ? team() : 0); }
     // a loop condition over the team's row that keeps the wave together: the eight teams of a short wave leave with the longest of their rows
     static __device__ __forceinline__ bool together(bool go_on) { return CLS == VGL_RC_SHORT ? __any(go_on) : go_on; }
+    // Chunked workgroup rows: the workgroup form's items are the (row, piece) pairs of `ch`, the other forms' the rows of the list.  The item loop
+    // runs to items(n, ch); item i is piece k = piece(i, ch, &row) of list entry `row`; range() is that piece of the row [row_lo, row_end), false
+    // when it is empty (then *lo == *hi).  Short and wave: statically the whole row, `ch` is not read.
+    static __device__ __forceinline__ int64_t items(int32_t n, const vgl_rc_chunks &ch) { if constexpr (CLS == VGL_RC_WG) return (int64_t)n * ch.nchunks; else return n; }
+    static __device__ __forceinline__ int64_t piece(int64_t i, const vgl_rc_chunks &ch, int64_t *row)
+    {
+        int64_t k = 0;
+        if constexpr (CLS == VGL_RC_WG) ch.split(i, row, &k);
+        else *row = i;
+        return k;
+    }
+    static __device__ __forceinline__ bool range(const vgl_rc_chunks &ch, int64_t row_lo, int64_t row_end, int64_t k, int64_t *lo, int64_t *hi)
+    {
+        if constexpr (CLS == VGL_RC_WG) {
+            if (ch.range(row_lo, row_end, k, lo, hi)) return true;
+            *hi = *lo;
+            return false;
+        } else { *lo = row_lo; *hi = row_end; return true; }
+    }
 
     // the combine of v over the team by OP, in every lane: an xor-butterfly over the team's lanes of a wave; the workgroup then folds the four
     // waves' results from LDS in wave order
