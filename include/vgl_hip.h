@@ -196,8 +196,11 @@ int vgl_hip_bfs_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, int32_t source, int mode
                     int32_t *d_levels, vgl_hip_bfs_stats *stats);
 /* `count` traversals from HOST source ids one after the other behind one call (the rounds loop of apps/bfs/bfs.cpp:36-50): d_levels is reused
  * and holds the levels of the last source afterwards; stats (optional) has `count` entries.  Stops at the first failing traversal.
- * d_levels may hold anything on entry and belongs to the call until it returns: from the second traversal on only the entries a traversal can
- * have written (those below the graph's reach_rows, and the previous source's) are re-initialised. */
+ * d_levels may hold anything on entry and belongs to the call until it returns: the first traversal stores every entry, the last one
+ * re-initialises the entries a traversal can have written (those below the graph's reach_rows, and the previous source's), and the ones in
+ * between re-initialise nothing -- they store their levels above an offset that grows from traversal to traversal and take every smaller value
+ * for unvisited.  While the call runs, and after a traversal of it has failed, d_levels therefore holds an internal encoding; on success it holds
+ * the levels of the last source (-1 = not reached), as it always did.  VGL_BFS_BATCH_REFILL=1 re-initialises before every traversal. */
 int vgl_hip_bfs_run_batch(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *sources, int32_t count, int mode, int32_t *d_levels,
                           vgl_hip_bfs_stats *stats);
 /* Optional graph preparation for repeated top-down traversals (the counterpart of the reference's offline graph import,

@@ -3,7 +3,9 @@
 switches the library reads per call (DESIGN 'Run-time switches'; VGL_BFS_HEADS, which is read when a graph handle is created, gives the
 variant a handle of its own over the same CSR arrays, created once); each variant runs the bench's sources (4 warm-up + N timed), is checked
 against the top-down levels of every source, and is timed twice: wall time without event brackets, then per kernel with all brackets.
-usage: python3 profiles/microbench/bfs_ab.py [--scale 24] [--steps 32] base: new:VGL_X=1 ..."""
+--batch: the timed region is ONE api.bfs_batch call over the timed sources, as in bench.py (vgl_hip_bfs_run_batch: the switches of the batch
+itself show only here, e.g. `offsets: refill:VGL_BFS_BATCH_REFILL=1`); the levels it leaves are checked against the last source's.
+usage: python3 profiles/microbench/bfs_ab.py [--scale 24] [--steps 32] [--batch] base: new:VGL_X=1 ..."""
 import argparse
 import os
 import sys
@@ -21,6 +23,7 @@ ap.add_argument("--steps", type=int, default=32)
 ap.add_argument("--warmup", type=int, default=4)
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--per-source", action="store_true")
+ap.add_argument("--batch", action="store_true")
 ap.add_argument("variants", nargs="+")
 args = ap.parse_args()
 
@@ -47,6 +50,7 @@ ref = {}
 for s in sources:
     lv, _ = api.bfs(g, s, api.BFS_TOP_DOWN, raw=True)
     ref[s] = lv.clone()
+lv_buf = ctx.empty(V, torch.int32)           # --batch: one levels array for every batch, as in bench.py
 KERNELS = ("bfs_bottom_up", "bfs_bottom_up_heavy", "bfs_top_down", "bfs_small_levels", "bfs_bitmap_expand", "gnf")
 variants = []
 for v in args.variants:
@@ -65,10 +69,15 @@ for rnd in range(args.rounds):
             api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for s in sources[args.warmup:]:
-            api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
+        if args.batch:
+            lv_batch, _ = api.bfs_batch(g, sources[args.warmup:], api.BFS_DIRECTION_OPT, levels=lv_buf)
+        else:
+            for s in sources[args.warmup:]:
+                api.bfs(g, s, api.BFS_DIRECTION_OPT, raw=True)
         torch.cuda.synchronize()
         ms = (time.perf_counter() - t0) / args.steps * 1e3
+        if args.batch:
+            bad += int(api.count_not_equal(ctx, lv_batch, ref[sources[-1]]) != 0)
         ctx.timing(True)
         stats = []
         prev = {k: 0.0 for k in KERNELS}

@@ -30,18 +30,21 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init(int32_t V, int32_t s
 
 // start of a fused traversal: levels, the three bitmaps (visited = front = {source}, next = 0) and the tickets in one launch.
 // fill: the levels [0, fill) are stored.  V for a buffer that may hold anything; the graph's reach_rows when the buffer comes straight from a
-// traversal from `prev` on the same handle (vgl_hip_bfs_run_batch): that traversal wrote below reach_rows and at `prev` only, so the other
-// entries still hold the -1 of an earlier full fill.  prev = -1: none.
-__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init_all(int32_t fill, int32_t source, int32_t prev, int32_t *levels, int64_t words, uint64_t *visited,
-                                                                uint64_t *front, uint64_t *next, uint32_t *tickets, unsigned long long *list_count)
+// traversal on the same handle (vgl_hip_bfs_run_batch): that traversal wrote below reach_rows and at its source only, so the other entries
+// still hold the -1 of an earlier full fill; 0 for a traversal of a batch that tells stale entries from its own by their value (`first` is
+// its offset + 1: vgl_bfs_traversal::off) and stores none.  reset: the previous traversal's source when it lies at or beyond reach_rows, where
+// no fill and no traversal overwrites it (-1: nothing to put back).
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_init_all(int32_t fill, int32_t source, int32_t first, int32_t reset, int32_t *levels, int64_t words,
+                                                                uint64_t *visited, uint64_t *front, uint64_t *next, uint32_t *tickets,
+                                                                unsigned long long *list_count)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         *list_count = 0ULL;
-        if (prev >= fill) levels[prev] = -1;     // (before the source's: the two may be the same vertex; the loop below stores neither)
-        if (source >= fill) levels[source] = 1;
+        if (reset >= fill) levels[reset] = -1;   // (before the source's: the two may be the same vertex; the loop below stores neither)
+        if (source >= fill) levels[source] = first;
     }
     for (int32_t v = blockIdx.x * VGL_BLOCK + threadIdx.x; v < fill; v += gridDim.x * VGL_BLOCK)
-        levels[v] = (v == source) ? 1 : -1;      // FIRST_LEVEL_VERTEX / UNVISITED_VERTEX (change_state.h:21-23)
+        levels[v] = (v == source) ? first : -1;  // FIRST_LEVEL_VERTEX / UNVISITED_VERTEX (change_state.h:21-23)
     for (int64_t w = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; w < words; w += (int64_t)gridDim.x * VGL_BLOCK) {
         const uint64_t bit = (w == (source >> 6)) ? (1ULL << (source & 63)) : 0ULL;
         visited[w] = bit; front[w] = bit; next[w] = 0;
@@ -65,6 +68,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_tile_first(int32_t F, const i
 
 // top-down advance over a sparse frontier, edge-balanced: workgroup = 2048 consecutive frontier edges.
 // edge_op of bfs.hpp:28-36: if levels[dst] == UNVISITED then levels[dst] = cur+1 (benign race, same value).
+// floor: an entry counts as unvisited when it is <= floor.  0 keeps the meaning "-1 and nothing else" (levels start at 1); a traversal of a
+// batch passes its offset, below which lie the -1 and whatever the traversals before it left (vgl_bfs_traversal::off).
 // EMIT: every newly discovered vertex also sets its bit in the next-frontier bitmap (idempotent atomicOr), so that the next
 // level's frontier can be generated from 2 MiB of bitmap instead of a 64 MiB scan of levels.  Used for small frontiers only.
 // (levels[dst] == -1 is what keeps the atomics few: asking the next-frontier bitmap instead -- 2 MiB in L2 against a random sector of
@@ -81,7 +86,8 @@ template <bool EMIT, bool COUNT, bool FILTER = true>
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_td_expand(const int32_t *ids, const int64_t *offs, const int32_t *tile_first,
                                                              int32_t F, int64_t M, const int64_t *rowptr, const int32_t *adj,
                                                              int32_t row_base, const uint64_t *visited, int32_t *levels,
-                                                             int32_t next_level, uint64_t *next, int64_t *partials, uint32_t *ticket, int64_t *counters)
+                                                             int32_t next_level, int32_t floor, uint64_t *next, int64_t *partials, uint32_t *ticket,
+                                                             int64_t *counters)
 {
     __shared__ int s_map[VGL_TILE];
     __shared__ int64_t s_base[VGL_TILE];
@@ -141,10 +147,10 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_td_expand(const int32_t *ids,
 #pragma unroll
     for (int j = 0; j < VGL_EPT; j++) lv[j] = levels[unvis[j] ? dsts[j] : 0];
 #pragma unroll
-    for (int j = 0; j < VGL_EPT; j++) fresh[j] = unvis[j] && lv[j] == -1;
+    for (int j = 0; j < VGL_EPT; j++) fresh[j] = unvis[j] && lv[j] <= floor;
 #else
 #pragma unroll
-    for (int j = 0; j < VGL_EPT; j++) fresh[j] = unvis[j] && levels[dsts[j]] == -1;
+    for (int j = 0; j < VGL_EPT; j++) fresh[j] = unvis[j] && levels[dsts[j]] <= floor;
 #endif
     if (!COUNT) {
 #pragma unroll
@@ -418,6 +424,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bm_gnf_count(int64_t nwords, 
 // everywhere but at the source (level 1, never the level scanned for), so the bitmaps there are right as they stand -- visited = the
 // source's bit, front = nothing -- but for the front bit that vgl_k_bfs_init_all gave the source, which the scan of all rows used to
 // overwrite.  stale_front: that source when it lies beyond the scanned rows (-1 otherwise); its byte of bm_front holds no other bit.
+// level / floor: the value scanned for and the bound above which an entry is visited -- offset + cur and offset (vgl_bfs_traversal::off; with
+// offset 0 "above 0" is "not -1").
 // Shape (profiles/r08_scan_forms.log): at most VGL_SCAN_BLOCKS workgroups stride over the tiles, two full tiles per trip -- four independent
 // 16-byte loads in flight per thread -- with one reduction, one pair of partials and one ticket per WORKGROUP.  One workgroup per tile with two
 // loads per thread (the form up to round 7) took 19.2 us over the same rows, this one 13.6.  The sums are the same integers: sum over threads of
@@ -428,10 +436,15 @@ __device__ inline uint32_t vgl_match8(const int4 a, const int4 c, int32_t value)
     return (a.x == value) | ((a.y == value) << 1) | ((a.z == value) << 2) | ((a.w == value) << 3) |
            ((c.x == value) << 4) | ((c.y == value) << 5) | ((c.z == value) << 6) | ((c.w == value) << 7);
 }
+__device__ inline uint32_t vgl_above8(const int4 a, const int4 c, int32_t floor)
+{
+    return (a.x > floor) | ((a.y > floor) << 1) | ((a.z > floor) << 2) | ((a.w > floor) << 3) |
+           ((c.x > floor) << 4) | ((c.y > floor) << 5) | ((c.z > floor) << 6) | ((c.w > floor) << 7);
+}
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_scan_bound(int32_t nrows, int32_t ntiles, int32_t row_base, const int32_t *levels, int32_t level,
                                                                  const int32_t *vt_min_deg, uint8_t *front_bytes, uint8_t *visited_bytes,
                                                                  int64_t *partials, uint32_t *ticket, int64_t *counters,
-                                                                 volatile int64_t *host, int64_t seq, int32_t stale_front)
+                                                                 volatile int64_t *host, int64_t seq, int32_t stale_front, int32_t floor)
 {
     __shared__ int64_t s64[VGL_WAVES];
     if (stale_front >= 0 && blockIdx.x == 0 && threadIdx.x == 0) front_bytes[stale_front >> 3] = 0;
@@ -443,8 +456,8 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_scan_bound(int32_t nrows,
         const int4 a0 = *reinterpret_cast<const int4 *>(levels + va), a1 = *reinterpret_cast<const int4 *>(levels + va + 4);
         const int4 b0 = *reinterpret_cast<const int4 *>(levels + vb), b1 = *reinterpret_cast<const int4 *>(levels + vb + 4);
         const uint32_t fa = vgl_match8(a0, a1, level), fb = vgl_match8(b0, b1, level);
-        front_bytes[va >> 3] = (uint8_t)fa; visited_bytes[va >> 3] = (uint8_t)(0xFFu ^ vgl_match8(a0, a1, -1));
-        front_bytes[vb >> 3] = (uint8_t)fb; visited_bytes[vb >> 3] = (uint8_t)(0xFFu ^ vgl_match8(b0, b1, -1));
+        front_bytes[va >> 3] = (uint8_t)fa; visited_bytes[va >> 3] = (uint8_t)vgl_above8(a0, a1, floor);
+        front_bytes[vb >> 3] = (uint8_t)fb; visited_bytes[vb >> 3] = (uint8_t)vgl_above8(b0, b1, floor);
         f += __popc(fa) + __popc(fb);
         m += (int64_t)__popc(fa) * vt_min_deg[t] + (int64_t)__popc(fb) * vt_min_deg[t + stride];
     }
@@ -453,7 +466,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_bfs_scan_bound(int32_t nrows,
         if (r0 >= nrows) continue;
         const int32_t v0 = row_base + r0;
         uint32_t aux;
-        const vgl_pred_equal_i32 pred{levels, level};
+        const vgl_pred_level_i32 pred{levels, level, floor};
         const uint32_t bits = pred.bits8(v0, min(VGL_EPT, nrows - r0), &aux);
         front_bytes[v0 >> 3] = (uint8_t)bits;
         visited_bytes[v0 >> 3] = (uint8_t)aux;
@@ -1253,26 +1266,26 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_apply_fold(int n, const int64
 // the next frontier in the device counters
 template <bool EMIT, bool COUNT>
 static void vgl_td_expand_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_t M, const uint64_t *visited, int32_t *levels,
-                                 int32_t next_level, uint64_t *next, bool filter = true)
+                                 int32_t next_level, int32_t floor, uint64_t *next, bool filter = true)
 {
     const auto kernel = filter ? vgl_k_td_expand<EMIT, COUNT, true> : vgl_k_td_expand<EMIT, COUNT, false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)vgl_ceil_div(M, VGL_TILE)), dim3(VGL_BLOCK), 0, c->stream, g->ids, g->offs, g->tile_first, F, M,
-                       g->out.rowptr, g->out.adj, g->row_begin, visited, levels, next_level, next, COUNT ? g->bu_partials : (int64_t *)nullptr,
+                       g->out.rowptr, g->out.adj, g->row_begin, visited, levels, next_level, floor, next, COUNT ? g->bu_partials : (int64_t *)nullptr,
                        COUNT ? g->tickets + 3 * VGL_TICKET_WORDS : (uint32_t *)nullptr, COUNT ? c->d_counters : (int64_t *)nullptr);
 }
 
 // expand frontier (ids/offs with F vertices, M edges already produced by a frontier-generation write pass)
 constexpr int64_t VGL_TD_COUNT_TILES = 8192;           // (the counting level's partial sums live in g->bu_partials: 4 * 4096 slots)
-static int vgl_bfs_td_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_t M, int32_t *levels, int32_t next_level, bool emit,
+static int vgl_bfs_td_launch(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t F, int64_t M, int32_t *levels, int32_t next_level, int32_t floor, bool emit,
                              bool have_tile_first, bool count = false, bool filter = true)
 {
     if (F <= 0 || M <= 0) return 0;
     if (!have_tile_first) hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, F, g->offs, g->tile_first);
     {
         vgl_timed_launch tl(c, "bfs_top_down");
-        if (emit && count) vgl_td_expand_launch<true, true>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
-        else if (emit) vgl_td_expand_launch<true, false>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
-        else vgl_td_expand_launch<false, false>(c, g, F, M, g->bm_visited, levels, next_level, g->bm_next, filter);
+        if (emit && count) vgl_td_expand_launch<true, true>(c, g, F, M, g->bm_visited, levels, next_level, floor, g->bm_next, filter);
+        else if (emit) vgl_td_expand_launch<true, false>(c, g, F, M, g->bm_visited, levels, next_level, floor, g->bm_next, filter);
+        else vgl_td_expand_launch<false, false>(c, g, F, M, g->bm_visited, levels, next_level, floor, g->bm_next, filter);
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;
@@ -1478,6 +1491,10 @@ struct vgl_bfs_traversal {
 
     int32_t source = -1;
     int32_t cur = 1;
+    // What the kernels store and compare is off + level; an entry <= off is unvisited.  0 outside a batch and for its first and last traversal
+    // (-1 alone is unvisited, the buffer ends up holding plain levels); a traversal in between runs above every value the ones before it left
+    // (vgl_hip_bfs_run_batch), so nothing has to be stored to make them unvisited.  `cur`, the statistics and the rule never see it.
+    int32_t off = 0;
     vgl_bfs_front front = vgl_bfs_front::bitmap;
     bool bottom_up = false;             // the direction that PROCESSES level `cur`
     // hint_ready: the launch that produced the frontier about to be counted left its F and M on the device (a counting top-down level, or the
@@ -1536,9 +1553,9 @@ struct vgl_bfs_traversal {
             {
                 vgl_timed_launch tl(c, "gnf");
                 hipLaunchKernelGGL(vgl_k_bfs_scan_bound, dim3((unsigned)std::min<int64_t>(scan_tiles, VGL_SCAN_BLOCKS)), dim3(VGL_BLOCK), 0, c->stream, scan_rows,
-                                   (int32_t)scan_tiles, g->row_begin, (const int32_t *)levels, cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front.p,
+                                   (int32_t)scan_tiles, g->row_begin, (const int32_t *)levels, off + cur, (const int32_t *)g->vt_min_deg, (uint8_t *)g->bm_front.p,
                                    (uint8_t *)g->bm_visited.p, g->bu_partials, g->tickets + 0 * VGL_TICKET_WORDS, c->d_counters,
-                                   (volatile int64_t *)c->h_counters, seq, source >= scan_rows ? source : -1);
+                                   (volatile int64_t *)c->h_counters, seq, source >= scan_rows ? source : -1, off);
             }
             VGL_HIP_TRY(hipGetLastError());
             VGL_TRY(vgl_wait_counters(c, seq));
@@ -1553,7 +1570,7 @@ struct vgl_bfs_traversal {
             VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, true, false, -1, false, nullptr));      // exact sizes off the bitmap
             front = vgl_bfs_front::counted_bitmap;
         } else {
-            vgl_pred_equal_i32 pred{levels, cur};
+            vgl_pred_level_i32 pred{levels, off + cur, off};
             VGL_TRY(vgl_gnf_run(c, g, pred, g->ids, g->offs, (uint8_t *)g->bm_front.p, (uint8_t *)g->bm_visited.p, nullptr, false, true));
             front = vgl_bfs_front::counted_scan;
             done = "count done (levels scan)";
@@ -1571,13 +1588,13 @@ struct vgl_bfs_traversal {
         if (from_bitmap) {
             vgl_timed_launch tl(c, "bfs_bitmap_expand");
             hipLaunchKernelGGL(vgl_k_bm_expand, dim3(bm_blocks), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_front, g->out.rowptr, g->out.adj, g->bm_visited,
-                               g->bm_next, levels, cur + 1, g->ids, list_count, (int32_t)VGL_SMALL_F, g->bu_partials);
+                               g->bm_next, levels, off + cur + 1, g->ids, list_count, (int32_t)VGL_SMALL_F, g->bu_partials);
         }
         const int64_t seq = vgl_next_seq(c);
         {
             vgl_timed_launch tl(c, "bfs_small_levels");
             hipLaunchKernelGGL(vgl_k_bfs_small_levels, dim3(1), dim3(VGL_SMALL_THREADS), 0, c->stream, g->ids, listF, src, g->out.rowptr, g->out.adj,
-                               g->bm_visited, g->bm_next, levels, from_bitmap ? cur + 1 : cur, p.small_m, c->d_counters, (volatile int64_t *)c->h_counters,
+                               g->bm_visited, g->bm_next, levels, off + (from_bitmap ? cur + 1 : cur), p.small_m, c->d_counters, (volatile int64_t *)c->h_counters,
                                seq, from_bitmap ? list_count : (unsigned long long *)nullptr, (const int64_t *)g->bu_partials, from_bitmap ? (int)bm_blocks : 0,
                                g->bm_front, g->offs, g->tile_first);
         }
@@ -1624,7 +1641,7 @@ struct vgl_bfs_traversal {
     int blocked_level()
     {
         trace("counted -> blocked level");
-        VGL_TRY(vgl_bfs_blocked_level(c, g, levels, cur + 1));
+        VGL_TRY(vgl_bfs_blocked_level(c, g, levels, off + cur + 1));
         trace("blocked level done");
         front = vgl_bfs_front::pending;
         book_top_down(F, M);
@@ -1637,9 +1654,9 @@ struct vgl_bfs_traversal {
         case vgl_bfs_front::ids: break;                                     // written by the list kernel
         case vgl_bfs_front::counted_bitmap: VGL_TRY(vgl_bfs_bm_gnf(c, g, g->bm_front, false, true, M)); break;
         case vgl_bfs_front::counted_scan: {
-            vgl_pred_equal_i32 pred{levels, cur};
+            vgl_pred_level_i32 pred{levels, off + cur, off};
             vgl_timed_launch tl(c, "gnf");
-            hipLaunchKernelGGL(vgl_k_gnf_write<vgl_pred_equal_i32>, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, pred,
+            hipLaunchKernelGGL(vgl_k_gnf_write<vgl_pred_level_i32>, dim3((unsigned)g->nvtiles), dim3(VGL_BLOCK), 0, c->stream, pred,
                                g->nrows, g->row_begin, g->out.rowptr, g->vt_cnt_off, g->vt_deg_off, g->ids, g->offs, (int32_t *)nullptr, (int64_t)0);
             break;
         }
@@ -1659,7 +1676,7 @@ struct vgl_bfs_traversal {
         const bool td_counts = emit && p.use_hints && vgl_ceil_div(M, VGL_TILE) <= VGL_TD_COUNT_TILES;
         const bool filter = is_late || (double)visited_total >= p.td_filter_share * (double)V;
         trace(emit ? "counted + ids -> top-down (emitting)" : "counted + ids -> top-down (levels only)");
-        VGL_TRY(vgl_bfs_td_launch(c, g, (int32_t)F, M, levels, cur + 1, emit, have_tile_first, td_counts, filter));
+        VGL_TRY(vgl_bfs_td_launch(c, g, (int32_t)F, M, levels, off + cur + 1, off, emit, have_tile_first, td_counts, filter));
         trace("top-down done");
         hint_ready = td_counts && F > 0 && M > 0;     // (a level without edges launches nothing: C_NEXT_* would be another traversal's)
         front = emit ? vgl_bfs_front::pending : vgl_bfs_front::levels;      // a top-down level is always followed by a count (or the loop ends)
@@ -1674,7 +1691,7 @@ struct vgl_bfs_traversal {
         trace("-> bottom-up");
         const bool filtered = F <= p.filter_f;                              // F: the frontier the level probes against (known on every path here)
         if (filtered) trace("bottom-up through the folded frontier");
-        VGL_TRY(vgl_bfs_bu_launch(c, g, levels, cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq, filtered));
+        VGL_TRY(vgl_bfs_bu_launch(c, g, levels, off + cur + 1, g->bm_visited, g->bm_front, g->bm_next, &seq, filtered));
         hipLaunchKernelGGL(vgl_k_bm_advance, dim3(vgl_grid(words, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, words, g->bm_visited, g->bm_front, g->bm_next);
         VGL_HIP_TRY(hipGetLastError());
         VGL_TRY(vgl_wait_counters(c, seq));
@@ -1686,13 +1703,17 @@ struct vgl_bfs_traversal {
         return 0;
     }
 
-    // prev >= 0: `levels` comes straight from this handle's traversal from `prev` (a batch): only what that one can have written is stored anew
-    int run(int32_t source_, int32_t prev = -1)
+    // prev >= 0: `levels` comes straight from this handle's traversal from `prev` (a batch).  refill: only what that one can have written is
+    // stored anew, [0, reach_rows) and the entry of `prev`; otherwise nothing is, and the traversal runs at offset off_ (>= every value below
+    // reach_rows; beyond it only `prev` is not -1, and is put back)
+    int run(int32_t source_, int32_t prev = -1, bool refill = true, int32_t off_ = 0)
     {
         source = source_;
-        const int32_t fill = prev >= 0 ? g->reach_rows : V;
-        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(std::max<int64_t>(fill, words), VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, fill, source, prev,
-                           levels, words, g->bm_visited, g->bm_front, g->bm_next, g->tickets, list_count);
+        off = off_;
+        const int32_t fill = prev < 0 ? V : refill ? g->reach_rows : 0;
+        const int32_t reset = prev >= g->reach_rows ? prev : -1;
+        hipLaunchKernelGGL(vgl_k_bfs_init_all, dim3(vgl_grid(std::max<int64_t>(fill, words), VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, fill, source, off + 1,
+                           reset, levels, words, g->bm_visited, g->bm_front, g->bm_next, g->tickets, list_count);
         t0 = std::chrono::steady_clock::now();
         if (p.small_m > 0) {                                                // level 1 = {source}
             VGL_TRY(small_levels(1, source, false));
@@ -1764,17 +1785,17 @@ int vgl_hip_bfs_init(vgl_hip_ctx *c, int32_t V, int32_t source, int32_t *d_level
     return 0;
 }
 
-// prev: -1, or the source of the traversal on this handle that left d_levels as they are (vgl_bfs_traversal::run)
-static int vgl_bfs_run_from(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int32_t prev, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
+// prev: -1, or the source of the traversal on this handle that left d_levels as they are; refill / off: vgl_bfs_traversal::run
+static int vgl_bfs_run_from(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int32_t prev, bool refill, int32_t off, int mode, int32_t *d_levels,
+                            vgl_hip_bfs_stats *stats)
 {
     if (!c || !g || !d_levels) VGL_FAIL("bfs_run: null argument");
     if (g->row_begin != 0 || g->row_end != g->V) VGL_FAIL("bfs_run: graph handle must own all rows (use the step API for shards)");
     if (mode != VGL_HIP_BFS_TOP_DOWN && mode != VGL_HIP_BFS_DIRECTION_OPT) VGL_FAIL("bfs_run: unknown mode");
     if (mode == VGL_HIP_BFS_DIRECTION_OPT && !g->in.rowptr) VGL_FAIL("bfs_run: direction-optimising mode needs the incoming CSR");
     if (source < 0 || source >= g->V) VGL_FAIL("bfs_run: source vertex out of range");
-    vgl_ctx_refresh_env(c);                                  // (a pass over the pointers of `environ`; the strings are parsed only when something was set since)
     vgl_bfs_traversal t(c, g, mode, d_levels);
-    VGL_TRY(t.run(source, prev));
+    VGL_TRY(t.run(source, prev, refill, off));
     if (stats) *stats = t.st;
     return 0;
 }
@@ -1782,21 +1803,40 @@ static int vgl_bfs_run_from(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, in
 // one traversal into a buffer that may hold anything: every entry of d_levels is stored
 int vgl_hip_bfs_run(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t source, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
 {
-    return vgl_bfs_run_from(c, g, source, -1, mode, d_levels, stats);
+    if (c) vgl_ctx_refresh_env(c);                           // (a pass over the pointers of `environ`; the strings are parsed only when something was set since)
+    return vgl_bfs_run_from(c, g, source, -1, true, 0, mode, d_levels, stats);
 }
 
 // `count` traversals one after the other (the rounds loop of apps/bfs/bfs.cpp:36-50 behind one call): d_levels is reused and holds the levels
 // of the last source afterwards, stats[i] (optional) those of traversal i.  Stops at the first failing traversal.
 // The first traversal stores all V levels (the caller's buffer may hold anything).  Between its traversals the buffer is the batch's alone --
 // nobody else can write it before this call returns -- and a traversal writes levels[v] only for vertices with an incoming edge (all below
-// the handle's reach_rows) and for its source, so from the second traversal on the entries at or beyond reach_rows still hold -1, but for the
-// previous source's: only [0, reach_rows), that entry and the new source's are stored (vgl_k_bfs_init_all).  On a graph whose rows without
-// incoming edges are not numbered last reach_rows is about V and nothing changes.
+// the handle's reach_rows) and for its source.  So the entries at or beyond reach_rows hold -1 but for the previous source's, which every
+// later traversal puts back, and those below it need no store either as long as a traversal can tell what the earlier ones left from what it
+// wrote itself: traversal k stores o_k + level and takes every entry <= o_k for unvisited, with o_0 = 0 and o_(k+1) = o_k + the number of
+// levels traversal k ran (the largest value it stored is o_k + that number, and -1 lies below every offset).  Such a traversal starts with the
+// bitmaps, the tickets and its source's entry alone (vgl_k_bfs_init_all with fill = 0): 43 MB of stores less on RMAT-24.
+// The LAST traversal runs at offset 0 behind a fill of [0, reach_rows), as every traversal but the first did before the offsets: what the
+// caller gets back are plain levels, and a batch of one or two sources does exactly what it always did.  A traversal whose offset has passed
+// `limit` (so that o + V + 1 might not fit an int32; VGL_BFS_OFFSET_LIMIT lowers it) is run the same way and the offsets start again from
+// its level count.  VGL_BFS_BATCH_REFILL=1: every traversal is.
+// While the call runs, and after a traversal of it has failed, d_levels therefore holds offset levels, not the levels of any one source.
 int vgl_hip_bfs_run_batch(vgl_hip_ctx *c, vgl_hip_graph *g, const int32_t *sources, int32_t count, int mode, int32_t *d_levels, vgl_hip_bfs_stats *stats)
 {
     if (!sources || count < 0) VGL_FAIL("bfs_run_batch: null argument");
-    for (int32_t i = 0; i < count; i++)
-        VGL_TRY(vgl_bfs_run_from(c, g, sources[i], i > 0 ? sources[i - 1] : -1, mode, d_levels, stats ? stats + i : nullptr));
+    if (c) vgl_ctx_refresh_env(c);                           // once per call: the switches hold for the whole batch
+    const bool offsets = c && g && !c->bfs.batch_refill;     // (null arguments: the first traversal says so)
+    int64_t limit = offsets ? (int64_t)INT32_MAX - g->V - 2 : 0;
+    if (offsets && c->bfs.offset_limit >= 0) limit = std::min(limit, c->bfs.offset_limit);
+    int64_t off = 0;                                         // o_i
+    for (int32_t i = 0; i < count; i++) {
+        const bool refill = i == 0 || i == count - 1 || !offsets || off > limit;
+        if (refill) off = 0;
+        vgl_hip_bfs_stats st;
+        VGL_TRY(vgl_bfs_run_from(c, g, sources[i], i > 0 ? sources[i - 1] : -1, refill, (int32_t)off, mode, d_levels, &st));
+        if (stats) stats[i] = st;
+        off += st.levels;
+    }
     return 0;
 }
 
@@ -1819,7 +1859,7 @@ int vgl_hip_bfs_step_top_down(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_level
     if (F > 0 && M > 0) {
         hipLaunchKernelGGL(vgl_k_tile_first, dim3(vgl_grid(F, VGL_BLOCK, 8192)), dim3(VGL_BLOCK), 0, c->stream, (int32_t)F, g->offs, g->tile_first);
         vgl_timed_launch tl(c, "bfs_top_down");
-        vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, visited, d_levels, level + 1, nullptr);
+        vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, visited, d_levels, level + 1, 0, nullptr);
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;                                    // enqueued; the caller's next call on this context orders after it
@@ -1844,8 +1884,8 @@ int vgl_hip_bfs_step_top_down_bits(vgl_hip_ctx *c, vgl_hip_graph *g, int32_t *d_
     if (emit) VGL_TRY(vgl_zero_words(c, d_next_bits, words));
     if (F > 0 && M > 0) {                                        // tile_first came with the write pass
         vgl_timed_launch tl(c, "bfs_top_down");
-        if (emit) vgl_td_expand_launch<true, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, d_next_bits);
-        else vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, d_next_bits);
+        if (emit) vgl_td_expand_launch<true, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, 0, d_next_bits);
+        else vgl_td_expand_launch<false, false>(c, g, (int32_t)F, M, d_visited_bits, d_levels, level + 1, 0, d_next_bits);
     }
     if (!emit) {
         vgl_timed_launch tl(c, "gnf");

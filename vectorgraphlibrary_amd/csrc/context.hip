@@ -86,7 +86,9 @@ void vgl_ctx_refresh_env(vgl_hip_ctx *c)
     if (const char *v = str("VGL_TD_LATE_SHARE")) t.td_late_share = atof(v);
     if (const char *v = str("VGL_BFS_BLOCKED_SHARE")) t.blocked_share = atof(v);
     if (const char *v = str("VGL_SHARD_SPARSE_CAP")) t.shard_sparse_cap = std::max(0, atoi(v));
+    if (const char *v = str("VGL_BFS_OFFSET_LIMIT")) t.offset_limit = atoll(v);
     t.no_hint = on("VGL_BFS_NO_HINT"); t.no_scan_bound = on("VGL_BFS_NO_SCAN_BOUND"); t.trace = on("VGL_BFS_TRACE");
+    t.batch_refill = on("VGL_BFS_BATCH_REFILL");
     c->bfs = t;
 }
 const char *vgl_env(vgl_hip_ctx *c, const char *name)

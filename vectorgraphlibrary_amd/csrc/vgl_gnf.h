@@ -10,7 +10,7 @@
 #ifdef __HIPCC__
 // A predicate functor provides:  __device__ uint32_t bits8(int32_t v0, int nvalid, uint32_t *aux) const
 // returning bit j set iff global vertex v0+j is active (only j < nvalid are evaluated).  *aux receives a second bit set
-// derived from the same loads (the fused BFS uses it for "visited": values[v] != -1), so the count pass reads 4 B/vertex.
+// derived from the same loads (the fused BFS uses it for "visited": values[v] != -1, or above a floor), so the count pass reads 4 B/vertex.
 
 struct vgl_pred_equal_i32 {                 // values[v] == value   (BFS on_next_level, bfs.hpp:40-45)
     const int32_t *values; int32_t value;
@@ -29,6 +29,32 @@ struct vgl_pred_equal_i32 {                 // values[v] == value   (BFS on_next
                 const int32_t x = values[v0 + j];
                 b |= (uint32_t)(x == value) << j;
                 n |= (uint32_t)(x != -1) << j;
+            }
+        }
+        *aux = n;
+        return b;
+    }
+};
+// values[v] == value, aux: values[v] > floor.  The fused BFS inside a batch (vgl_hip_bfs_run_batch): value = offset + level, floor = offset, and
+// an entry at or below the offset -- the -1, or what an earlier traversal of the batch left -- is unvisited.  With floor 0 the same bits as
+// vgl_pred_equal_i32 on a buffer of -1 and levels >= 1.
+struct vgl_pred_level_i32 {
+    const int32_t *values; int32_t value, floor;
+    __device__ uint32_t bits8(int32_t v0, int nvalid, uint32_t *aux) const
+    {
+        uint32_t b = 0, n = 0;
+        if (nvalid == 8) {                  // v0 is a multiple of 8 => 32-byte aligned, two 16-byte loads
+            const int4 a = *reinterpret_cast<const int4 *>(values + v0);
+            const int4 c = *reinterpret_cast<const int4 *>(values + v0 + 4);
+            b = (a.x == value) | ((a.y == value) << 1) | ((a.z == value) << 2) | ((a.w == value) << 3) |
+                ((c.x == value) << 4) | ((c.y == value) << 5) | ((c.z == value) << 6) | ((c.w == value) << 7);
+            n = (a.x > floor) | ((a.y > floor) << 1) | ((a.z > floor) << 2) | ((a.w > floor) << 3) |
+                ((c.x > floor) << 4) | ((c.y > floor) << 5) | ((c.z > floor) << 6) | ((c.w > floor) << 7);
+        } else {
+            for (int j = 0; j < nvalid; j++) {
+                const int32_t x = values[v0 + j];
+                b |= (uint32_t)(x == value) << j;
+                n |= (uint32_t)(x > floor) << j;
             }
         }
         *aux = n;

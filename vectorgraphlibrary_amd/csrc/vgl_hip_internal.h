@@ -56,6 +56,10 @@ struct vgl_bfs_tunables {
     double td_filter_share = -1.0, td_late_share = -1.0, blocked_share = -1.0;
     int shard_sparse_cap = -1;
     bool no_hint = false, no_scan_bound = false, trace = false;
+    // vgl_hip_bfs_run_batch: 1 = every traversal after the first re-initialises [0, reach_rows) instead of running at a level offset; the offset
+    // beyond which a traversal does so anyway (default INT32_MAX - V - 2; the tests lower it)
+    bool batch_refill = false;
+    int64_t offset_limit = -1;
 };
 
 struct vgl_hip_ctx {
