@@ -1239,6 +1239,79 @@ int vgl_hip_ppr_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *seeds, co
                     double alpha, int32_t max_iterations, double tol, int symmetric, double *d_rank, double *d_err, int32_t *d_iterations,
                     vgl_hip_ppr_stats *stats);
 
+/* Neighbour aggregation with gradients (`agg`): for every row of a CSR, the sum, mean, max or min of the feature rows of its entries, float32, any
+ * width, optionally weighted per entry, and the exact backward of that step.  It is what consumes the blocks of vgl_hip_sample_neighbors, and the
+ * general form of the fixed-width pull of vgl_hip_ppr_run.  The reference has no counterpart, so this comment is the contract:
+ *   plan      vgl_hip_agg_plan_create BORROWS a device CSR: d_rowptr int64 [n_rows + 1] with rowptr[0] = 0 that does not decrease, d_adj int32
+ *             [rowptr[n_rows]] with every entry in [0, n_cols).  The CSR need not belong to a handle: the stored arrays of either direction of a
+ *             graph serve as they are (n_rows = n_cols = V), and so do the rowptr / adj of a sampled block.  Entries are taken AS STORED: a repeated
+ *             entry counts as often as it is stored, a self entry is an entry like any other.  The arrays must outlive the plan and must not change.
+ *             The plan checks its input (a count over the rows, a count over the entries), classifies the rows once (VGL_AGG_SHORT 32: 8 lanes per
+ *             row, empty rows among them; VGL_AGG_WAVE 1024: a wavefront; longer: a workgroup per chunk of VGL_AGG_CHUNK 16384 entries, the chunk
+ *             raised until the longest row has at most 32768), and keeps each class list in ascending order.  At most 2^31 - 16 entries.
+ *             vgl_hip_agg_plan_info returns the stats of the plan (the run fields 0); _destroy frees what the plan owns, nothing that it borrowed.
+ *   transpose built by the first vgl_hip_agg_run_transposed of a plan and kept in it: the CSR with n_cols rows whose row u lists, IN ASCENDING ENTRY
+ *             POSITION p, the entries with adj[p] = u; for each it holds row(p) and the origin p.  It comes from the stable vgl_hip_coo_to_csr (with
+ *             d_perm) over the entry list in CSR order, and has class lists and chunks of its own.
+ *   forward   vgl_hip_agg_run: x is n_cols x F float32, row-major with leading dimension ldx >= F (in elements), out n_rows x F with ldo >= F,
+ *             d_weight one float32 per entry in CSR order or NULL (1 each), F >= 1 without an upper limit besides memory.
+ *               VGL_HIP_AGG_SUM   out[i, f] = the sum over the entries p of row i of w_p * x[adj[p], f]
+ *               VGL_HIP_AGG_MEAN  that sum divided once by (float) len(i); an empty row gives 0
+ *               VGL_HIP_AGG_MAX / _MIN  the extreme of x[adj[p], f] over the row; d_arg[i, f] (int32, n_rows x F, leading dimension F, optional) = the
+ *                                 SMALLEST position p that attains it; an empty row gives 0 and -1.  No weights.  With a NaN in x the result of MAX /
+ *                                 MIN (value and arg) is UNSPECIFIED.
+ *   backward  vgl_hip_agg_run_transposed: g is n_rows x F (ldg), gx n_cols x F (ldgx);  gx[u, f] = the sum over the transposed row of u, in its order,
+ *             of coefficient(p) * g[row(p), f], with coefficient w_p (1 without weights) for SUM, w_p / (float) len(row(p)) for MEAN (one division,
+ *             then one product), and for MAX / MIN 1 if d_arg[row(p), f] == p else 0 (d_arg: what the forward run wrote).  The weight and the arg are
+ *             read through the origin p: no permuted copy of the weights is made.  This is the gradient of the forward with respect to x.
+ *   floating point: float32 accumulation, -ffp-contract=off, no fast-math, IEEE division, NO floating-point atomic; every output value has one
+ *             writer.  Every sum has a shape that is a function of (row length, F, VEC, the three switches) only, where VEC is 4 when F, every
+ *             leading dimension and every base address of the call are multiples of 4 elements / 16 bytes and 1 otherwise: the same call returns
+ *             the same bits on every run.  Across switch settings and VEC results agree within the tolerance, NOT bit for bit; on data whose partial
+ *             sums are all exact in float32 (small integers) every shape gives the same bits.  The arg does not depend on the shape at all.
+ *   tolerance per output value, with d terms c_p * v_p:  |computed - exact| <= gamma_k * the sum of |c_p * v_p|, k = d + 2, gamma_k = k u / (1 - k u),
+ *             u = 2^-24: one rounding per product, at most d - 1 additions on a chain whatever the shape, one division for MEAN and one more
+ *             product for its backward.
+ * Method: one team kernel for both passes; a team's lanes are (entry slot x column group): NQ lanes (a power of two, at most 8 in the short class and
+ * 64 in the others) cover a tile of NQ * VEC columns, slot s adds entries s, s + SLOTS, ... in row order with four gathers in flight, the slots of a
+ * column group are folded by an xor butterfly and a workgroup's four waves from LDS in wave order.  A wider F walks the row once per column tile and
+ * reads adj again.  A row of more than one chunk leaves a partial per chunk (for MAX / MIN a value and a position per column), and one writer per
+ * (row, column) finishes them in chunk order, the smaller position winning a tie.
+ * stats: rows, entries = of the CSR walked (the plan's, or the transpose: n_cols rows); rows_short / _wave / _wg its rows per class; chunks = the
+ * workgroup class's items; hub_rows = rows of more than one chunk; column_tiles[class] = walks per row; vec; transposed = 1 for the backward run (in
+ * _plan_info: the transpose exists).  algorithmic_bytes = per class entries x column_tiles x (4 adjacency + 4 with weights [+ 4 origin, + 16 the
+ * bounds of row(p) for MEAN, in the transposed run]): what is REQUESTED, the walks after the first are served by the caches, so this term is an upper
+ * bound of what memory sees; + entries x 4 F gathered (twice with the arg of a transposed MAX / MIN): requested bytes, a lower bound where rows are
+ * not aligned to lines and an upper bound of the memory traffic where a feature row is re-read from cache; + rows x (8 bounds + 4 F written + 4 F with
+ * d_arg): exact; + the list entry, 4 per short or wave row and 8 per chunk: exact.  The chunk partials are left out.
+ * Fails, before anything is written: a NULL argument, a negative size, a rowptr that does not start at 0 or decreases, an entry outside [0, n_cols),
+ * more than 2^31 - 16 entries; F < 1, a leading dimension below F, an op outside the four, a weight with MAX / MIN, a transposed MAX / MIN run without
+ * d_arg, a plan of another context.
+ * Threads: every entry point makes the context's device current itself (a backward pass arrives on a thread of its own).  The pinned counter mirror
+ * is per context: one call at a time per context.
+ * Not here: float16 / bfloat16 features, gradients with respect to the entry weights (SDDMM), a fused dense transform, more than one GPU. */
+enum { VGL_HIP_AGG_SUM = 0, VGL_HIP_AGG_MEAN = 1, VGL_HIP_AGG_MAX = 2, VGL_HIP_AGG_MIN = 3 };
+typedef struct vgl_hip_agg_plan vgl_hip_agg_plan;
+typedef struct {
+    int64_t rows;               /* rows of the CSR walked */
+    int64_t entries;
+    int64_t rows_short, rows_wave, rows_wg;
+    int64_t chunks;             /* items of the workgroup class */
+    int64_t hub_rows;           /* rows of more than one chunk */
+    int64_t algorithmic_bytes;
+    int32_t column_tiles[3];    /* walks per row of the short, wave and workgroup class */
+    int32_t vec;                /* 4: 16-byte loads and stores; 1: scalar */
+    int32_t transposed;         /* the run walked the transpose (plan_info: it exists) */
+    int32_t reserved;
+} vgl_hip_agg_stats;
+int vgl_hip_agg_plan_create(vgl_hip_ctx *ctx, const int64_t *d_rowptr, const int32_t *d_adj, int32_t n_rows, int32_t n_cols, vgl_hip_agg_plan **out);
+int vgl_hip_agg_plan_info(vgl_hip_agg_plan *plan, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_plan_destroy(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan);
+int vgl_hip_agg_run(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, const float *d_x, int64_t ldx, int32_t F, float *d_out,
+                    int64_t ldo, int32_t *d_arg, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_run_transposed(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, const int32_t *d_arg, const float *d_g,
+                               int64_t ldg, int32_t F, float *d_gx, int64_t ldgx, vgl_hip_agg_stats *stats);
+
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */
 int vgl_hip_bfs_init(vgl_hip_ctx *ctx, int32_t V, int32_t source, int32_t *d_levels);

@@ -295,6 +295,8 @@ class Graph:
         _l.check(self.ctx.L.vgl_hip_bfs_prepare_blocked(self.ctx.h, self.h))
 
     def close(self):
+        for plan in self.__dict__.pop("_agg_plans", {}).values():      # the plans of aggregate_neighbors borrow this graph's arrays
+            plan.close()
         if self.h:
             self.ctx.L.vgl_hip_graph_destroy(self.ctx.h, self.h)
             self.h = None
@@ -1466,3 +1468,170 @@ def count_not_equal(ctx, a, b):
     r = C.c_int64()
     _l.check(ctx.L.vgl_hip_count_not_equal_u32(ctx.h, a.numel(), _ptr(a), _ptr(b), C.byref(r)))
     return r.value
+
+
+# ---- neighbour aggregation with gradients (the contract of vgl_hip_agg_* in include/vgl_hip.h) ----
+AGG_OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3}
+
+
+def _agg_stats(st):
+    d = {k: getattr(st, k) for k, _ in st._fields_ if k not in ("column_tiles", "reserved")}
+    d["column_tiles"] = list(st.column_tiles)
+    return d
+
+
+class AggregationPlan:
+    """A device CSR (rowptr int64 [n_rows + 1], adj int32 [E] with entries in [0, n_cols)) prepared for aggregate(): checked, its rows classified and
+    chunked once; the transpose that the backward pass walks is built by the first backward and kept.  The plan BORROWS the two tensors (it keeps a
+    reference, they must not be modified).  Entries are taken as stored: repeats count, self entries are entries.  last_stats / last_backward_stats
+    hold the stats of the latest forward / backward run."""
+
+    def __init__(self, ctx, rowptr, adj, n_cols):
+        if rowptr.dtype != torch.int64 or adj.dtype != torch.int32:
+            raise _l.VglHipError("AggregationPlan: rowptr must be int64 and adj int32, got %s and %s" % (rowptr.dtype, adj.dtype))
+        if rowptr.dim() != 1 or rowptr.numel() < 1 or adj.dim() != 1:
+            raise _l.VglHipError("AggregationPlan: rowptr must hold n_rows + 1 offsets and adj be one-dimensional")
+        if rowptr.device != ctx.device or adj.device != ctx.device:
+            raise _l.VglHipError("AggregationPlan: rowptr and adj must live on the context's device")
+        self.ctx, self.rowptr, self.adj = ctx, rowptr.contiguous(), adj.contiguous()
+        self.n_rows, self.n_cols, self.E = int(rowptr.numel()) - 1, int(n_cols), int(adj.numel())
+        if int(self.rowptr[-1]) != self.E:
+            raise _l.VglHipError("AggregationPlan: rowptr ends at %d but adj has %d entries" % (int(self.rowptr[-1]), self.E))
+        self.last_stats = self.last_backward_stats = None
+        h = C.c_void_p()
+        keep = self.adj if self.E else ctx.empty(1, torch.int32)
+        _l.check(ctx.L.vgl_hip_agg_plan_create(ctx.h, _ptr(self.rowptr), _ptr(keep), self.n_rows, self.n_cols, C.byref(h)))
+        self.h = h
+
+    @classmethod
+    def from_graph(cls, graph, direction="in"):
+        """the stored CSR of `direction` in the graph's OWN numbering: n_rows = n_cols = V, row v aggregates over the incoming ("in") or outgoing
+        ("out") entries of v"""
+        if direction not in ("in", "out"):
+            raise _l.VglHipError("AggregationPlan.from_graph: direction must be 'in' or 'out'")
+        rowptr, adj = (graph.in_rowptr, graph.in_adj) if direction == "in" else (graph.out_rowptr, graph.out_adj)
+        if rowptr is None:
+            raise _l.VglHipError("AggregationPlan.from_graph: the graph has no incoming CSR")
+        if graph.row_begin != 0 or graph.row_end != graph.V:
+            raise _l.VglHipError("AggregationPlan.from_graph: graph handle must own all rows")
+        return cls(graph.ctx, rowptr, adj, graph.V)
+
+    @classmethod
+    def from_block(cls, ctx, block):
+        """a dict of sample_blocks -> (plan, cols): cols is the sorted unique union of the block's seeds and samples (what sample_blocks takes as its
+        next frontier when its ids are the graph's own: raw=True or no renumbering), the plan's adj the position of each sample in cols: row i of the
+        block aggregates rows of a len(cols) x F input"""
+        seeds, adj = block["seeds"], block["adj"]
+        cols = torch.unique(torch.cat([seeds, adj])).to(torch.int32).contiguous()
+        pos = torch.searchsorted(cols, adj).to(torch.int32).contiguous()
+        return cls(ctx, block["rowptr"], pos, int(cols.numel())), cols
+
+    def info(self):
+        st = _l.AggStats()
+        _l.check(self.ctx.L.vgl_hip_agg_plan_info(self.h, C.byref(st)))
+        return _agg_stats(st)
+
+    def close(self):
+        if self.h:
+            self.ctx.L.vgl_hip_agg_plan_destroy(self.ctx.h, self.h)
+            self.h = None
+
+    @staticmethod
+    def _rows(t, who):
+        """(tensor to pass, leading dimension): a view whose rows are strided by elements goes as it is"""
+        if t.dim() != 2:
+            raise _l.VglHipError("%s must be two-dimensional (rows x F)" % who)
+        F = int(t.shape[1])
+        if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < F):
+            t = t.contiguous()
+        elif t.shape[0] <= 1 and t.stride(1) != 1:
+            t = t.contiguous()
+        return t, (int(t.stride(0)) if t.shape[0] > 1 else F)
+
+    def _forward(self, x, op, weight):
+        ctx, F = self.ctx, int(x.shape[1])
+        ext = op >= 2
+        out = torch.empty((self.n_rows, F), dtype=torch.float32, device=ctx.device)
+        arg = torch.empty((self.n_rows, F), dtype=torch.int32, device=ctx.device) if ext else None
+        if self.n_rows == 0 or F == 0:
+            return out, arg
+        if self.n_cols == 0:
+            return out.zero_(), (arg.fill_(-1) if ext else None)
+        x, ldx = self._rows(x, "aggregate: x")
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_run(ctx.h, self.h, op, _ptr(weight), _ptr(x), ldx, F, _ptr(out), F, _ptr(arg), C.byref(st)))
+        self.last_stats = _agg_stats(st)
+        return out, arg
+
+    def _backward(self, g, op, weight, arg):
+        ctx, F = self.ctx, int(g.shape[1])
+        gx = torch.empty((self.n_cols, F), dtype=torch.float32, device=ctx.device)
+        if self.n_cols == 0 or F == 0:
+            return gx
+        if self.n_rows == 0:
+            return gx.zero_()
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_run_transposed(ctx.h, self.h, op, _ptr(weight), _ptr(arg), _ptr(g), F, F, _ptr(gx), F, C.byref(st)))
+        self.last_backward_stats = _agg_stats(st)
+        return gx
+
+
+class _Aggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, x, plan, op, weight):
+        out, arg = plan._forward(x.detach(), op, weight)
+        fctx.plan, fctx.op = plan, op
+        fctx.save_for_backward(weight, arg)
+        if arg is not None:
+            fctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(fctx, grad_out, _grad_arg=None):
+        weight, arg = fctx.saved_tensors
+        return fctx.plan._backward(grad_out.contiguous(), fctx.op, weight, arg), None, None, None
+
+
+def aggregate(plan, x, op="sum", weight=None, return_arg=False):
+    """out[i, :] = the sum / mean / max / min over the entries p of row i of the plan of x[adj[p], :] (x: n_cols x F float32 on the plan's device;
+    weight: one float32 per entry in CSR order, sum and mean only).  Returns out (n_rows x F), and with return_arg=True also arg (int32, n_rows x F: the
+    smallest position that attains the extreme, -1 in an empty row; None for sum and mean).  An empty row gives 0.  Differentiable in x ONLY: backward
+    runs the transposed kernel on grad_out.contiguous(), without atomics, so gradients are the same bits on every run; a weight that requires grad is
+    refused.  x may be a column slice or an offset view: a view whose rows are strided by elements is passed with its leading dimension, anything
+    else is made contiguous first.  The pinned counter mirror is per context, so run ONE aggregate (forward or backward) at a time per context."""
+    if not isinstance(plan, AggregationPlan) or not plan.h:
+        raise _l.VglHipError("aggregate: plan must be an open AggregationPlan")
+    if op not in AGG_OPS:
+        raise _l.VglHipError("aggregate: op must be one of 'sum', 'mean', 'max', 'min', got %r" % (op,))
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise _l.VglHipError("aggregate: x must be a float32 tensor, got %s" % (x.dtype if torch.is_tensor(x) else type(x).__name__))
+    if x.dim() != 2 or int(x.shape[0]) != plan.n_cols:
+        raise _l.VglHipError("aggregate: x must be n_cols x F = %d x F, got %s" % (plan.n_cols, tuple(x.shape)))
+    if x.device != plan.ctx.device:
+        raise _l.VglHipError("aggregate: x must live on the plan's device")
+    if weight is not None:
+        if op in ("max", "min"):
+            raise _l.VglHipError("aggregate: max and min take no entry weights")
+        if not torch.is_tensor(weight) or weight.dtype != torch.float32:
+            raise _l.VglHipError("aggregate: weight must be a float32 tensor, got %s" % (weight.dtype if torch.is_tensor(weight) else type(weight).__name__))
+        if weight.requires_grad:
+            raise _l.VglHipError("aggregate: gradients with respect to entry weights (SDDMM) are not in the library; pass weight.detach()")
+        if weight.dim() != 1 or int(weight.numel()) != plan.E or weight.device != plan.ctx.device:
+            raise _l.VglHipError("aggregate: weight must hold one value per entry (%d) on the plan's device" % plan.E)
+        weight = weight.contiguous()
+    out, arg = _Aggregate.apply(x, plan, AGG_OPS[op], weight)
+    return (out, arg) if return_arg else out
+
+
+def aggregate_neighbors(graph, x, op="sum", weight=None, direction="in", raw=False):
+    """aggregate() over the stored CSR of `direction`: x (V x F float32) and the result are in ORIGINAL vertex order unless raw=True; weight is per
+    entry of the graph's stored in_adj / out_adj.  On a renumbered graph this pays one row permutation of x and one of the result; raw=True pays
+    neither.  The plan is cached on the Graph per direction and closed with it."""
+    plans = graph.__dict__.setdefault("_agg_plans", {})
+    if direction not in plans:
+        plans[direction] = AggregationPlan.from_graph(graph, direction)
+    permute = not raw and graph.fwd is not None
+    if permute:
+        x = x[graph.bwd.long()]
+    out = aggregate(plans[direction], x, op, weight)
+    return out[graph.fwd.long()] if permute else out

@@ -133,6 +133,12 @@ class PprStats(C.Structure):
                 ("max_err", C.c_double)]
 
 
+class AggStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("entries", C.c_int64), ("rows_short", C.c_int64), ("rows_wave", C.c_int64), ("rows_wg", C.c_int64),
+                ("chunks", C.c_int64), ("hub_rows", C.c_int64), ("algorithmic_bytes", C.c_int64), ("column_tiles", C.c_int32 * 3), ("vec", C.c_int32),
+                ("transposed", C.c_int32), ("reserved", C.c_int32)]
+
+
 class KhopStats(C.Structure):
     _fields_ = [("reached", C.c_int64), ("frontier_total", C.c_int64), ("edges_examined", C.c_int64), ("levels_run", C.c_int32)]
 
@@ -258,6 +264,11 @@ _SIGNATURES = {
     "vgl_hip_louvain_move": [_p, _p, _p, _i32, _i64, C.c_uint32, _p, C.POINTER(LouvainStats)],
     "vgl_hip_ppr_prepare": [_p, _p, _int],
     "vgl_hip_ppr_run": [_p, _p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_dbl), _i32, _dbl, _i32, _dbl, _int, _p, _p, _p, C.POINTER(PprStats)],
+    "vgl_hip_agg_plan_create": [_p, _p, _p, _i32, _i32, _pp],
+    "vgl_hip_agg_plan_info": [_p, C.POINTER(AggStats)],
+    "vgl_hip_agg_plan_destroy": [_p, _p],
+    "vgl_hip_agg_run": [_p, _p, _int, _p, _p, _i64, _i32, _p, _i64, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_run_transposed": [_p, _p, _int, _p, _p, _p, _i64, _i32, _p, _i64, C.POINTER(AggStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
