@@ -1289,7 +1289,8 @@ int vgl_hip_ppr_run(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *seeds, co
  * d_arg, a plan of another context.
  * Threads: every entry point makes the context's device current itself (a backward pass arrives on a thread of its own).  The pinned counter mirror
  * is per context: one call at a time per context.
- * Not here: float16 / bfloat16 features, gradients with respect to the entry weights (SDDMM), a fused dense transform, more than one GPU. */
+ * Not here: float16 / bfloat16 features, a fused dense transform, more than one GPU.  Gradients with respect to the entry weights are
+ * vgl_hip_agg_sddmm below (the section on edge scores). */
 enum { VGL_HIP_AGG_SUM = 0, VGL_HIP_AGG_MEAN = 1, VGL_HIP_AGG_MAX = 2, VGL_HIP_AGG_MIN = 3 };
 typedef struct vgl_hip_agg_plan vgl_hip_agg_plan;
 typedef struct {
@@ -1311,6 +1312,56 @@ int vgl_hip_agg_run(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const floa
                     int64_t ldo, int32_t *d_arg, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_run_transposed(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, const int32_t *d_arg, const float *d_g,
                                int64_t ldg, int32_t F, float *d_gx, int64_t ldgx, vgl_hip_agg_stats *stats);
+
+/* Edge scores, edge softmax (`edge`): one float32 per stored entry of a vgl_hip_agg_plan, in CSR order.  With vgl_hip_agg_run / _run_transposed they
+ * close the gradients of a weighted aggregation and make graph attention three calls.  The reference has no counterpart, so this comment is the
+ * contract:
+ *   sddmm     vgl_hip_agg_sddmm: a is n_rows x F float32 (leading dimension lda >= F, in elements), b n_cols x F (ldb >= F), e one float32 per entry;
+ *             e[p] = the sum over f of a[row(p), f] * b[adj[p], f]; with mean = 1 that sum divided once by (float) len(row(p)).  It is the score of
+ *             dot-product attention, and the gradient of vgl_hip_agg_run with respect to d_weight: a = the gradient of out, b = x, mean = 1 for
+ *             VGL_HIP_AGG_MEAN.  Its own gradients need no further kernel: with ge per entry, ga = vgl_hip_agg_run(SUM, weight = ge, x = b) and
+ *             gb = vgl_hip_agg_run_transposed(SUM, weight = ge, g = a).
+ *   softmax   vgl_hip_agg_edge_softmax: per row i, over the entries p of the row, m = the largest e[p], s = the sum of expf(e[p] - m),
+ *             y[p] = expf(e[p] - m) / s: ONE DIVISION per entry, no reciprocal, so a row of d equal scores gives exactly 1 / (float) d.  An entry at
+ *             -inf gets y = 0 exactly; a row whose entries are all -inf gets y = 0 everywhere; an empty row writes nothing.  With a NaN or +inf in e the
+ *             result is UNSPECIFIED.  d_y must not overlap d_e.
+ *   backward  vgl_hip_agg_edge_softmax_backward: ge[p] = y[p] * (gy[p] - d), d = the sum over the row's entries q of y[q] * gy[q].  It is this formula
+ *             on ANY y, a softmax output or not.  d_ge must not overlap d_y or d_gy.
+ *   floating point: as above (float32, -ffp-contract=off, expf of the device library, IEEE division, NO floating-point atomic, one writer per value).
+ *             A dot product has the shape: a lane adds its VEC products in column order, tile after tile; the NQ lanes of an entry are folded by an
+ *             xor butterfly at offsets 1, 2, ... NQ / 2.  It depends on (F, VEC, the entry's class) only: chunks and slots only divide the work.  A
+ *             row sum of the softmax and of its backward has the shape: lane s of the team (8 / 64 / 256 lanes) adds entries s, s + LANES, ... of the
+ *             row or chunk in order; an xor butterfly at offsets 1, 2, ... folds the lanes of a wave; a workgroup adds its four waves in wave order; a
+ *             row of more than one chunk leaves (m_c, s_c) per chunk and ONE thread merges them in chunk order, M = max m_c,
+ *             S = the sum of s_c * expf(m_c - M) (a chunk whose entries are all -inf has s_c = 0 and contributes 0; no -inf - -inf is formed); the
+ *             backward's d is the sum of the d_c in chunk order.  The same call returns the same bits on every run.
+ *   tolerance  dot: gamma_(F + 2) * the sum of |a b|.  backward: gamma_(d + 3) * |y_p| * (|gy_p| + the sum of |y_q gy_q|), d the row
+ *             length.  forward, relative to the exact y_p: 3 (R u + eps_exp) + gamma_(d + 3), plus 2^-126 absolute, R = the largest |e - m| of the row,
+ *             eps_exp the measured error of expf (tests/studies/expf_ulps.hip).
+ * Method: vgl_k_edge_dot<CLS, VEC> runs over the plan's forward class lists with the lane layout of the aggregation (entry slot x column group, four
+ * gathers of b in flight); the row's a stays in registers with one column tile and is re-read per tile from cache with more.  No fold over slots, no
+ * chunk partials.  vgl_k_edge_rows<CLS, BWD>: every lane an entry slot; rows of one chunk finish in one launch (walks: max, sum, write; backward: sum,
+ * write); rows of more chunks take three: partials, vgl_k_edge_hubs (one thread per hub row), vgl_k_edge_hub_write over the workgroup items.
+ * VEC = 4 when F, lda, ldb are multiples of 4 and d_a, d_b are 16-byte aligned, else 1.
+ * stats: rows, entries, rows_short / _wave / _wg, chunks, hub_rows = of the plan's CSR; column_tiles, vec as in vgl_hip_agg_run (softmax: 1, 1);
+ * transposed = 0.  algorithmic_bytes:
+ *   sddmm    per class entries x column_tiles x 4 (adjacency; requested: the tiles after the first come from cache, an upper bound)
+ *            + entries x 4 F (b gathered; requested, as for vgl_hip_agg_run) + entries x 4 (e written; exact)
+ *            + rows x (8 bounds + 4 F of a) (a lower bound with more than one tile or slot group: a is re-read from cache) + the list entries (4 per
+ *            short or wave row, 8 per chunk; exact).
+ *   softmax  entries x (4 x 3 walks of e + 4 written): the walks after the first are requested, not memory traffic (a chunk is 64 KiB): upper bound
+ *            + rows x 8 + the list entries (exact).  The hub partials are left out.
+ *   backward entries x (8 x 2 walks of y and gy + 4 written) + rows x 8 + the list entries; the same remarks.
+ * Fails, before anything is written: a NULL argument (stats may be NULL), a plan of another context, F < 1, a leading dimension below F, mean outside
+ * {0, 1}.  Threads: as above.
+ * Not here: heads (call per column slice: one adjacency walk per head); the u_add_v score of the original GAT (s[row] + t[adj], two gathers in any
+ * tensor library); a fused attention that never materialises the E scalars (they are 12 bytes per entry against 8 F); a softmax grouped by column;
+ * float16 / bfloat16. */
+int vgl_hip_agg_sddmm(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int mean,
+                      float *d_e, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_edge_softmax(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_e, float *d_y, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_edge_softmax_backward(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_y, const float *d_gy, float *d_ge,
+                                      vgl_hip_agg_stats *stats);
 
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */

@@ -1497,7 +1497,7 @@ class AggregationPlan:
         self.n_rows, self.n_cols, self.E = int(rowptr.numel()) - 1, int(n_cols), int(adj.numel())
         if int(self.rowptr[-1]) != self.E:
             raise _l.VglHipError("AggregationPlan: rowptr ends at %d but adj has %d entries" % (int(self.rowptr[-1]), self.E))
-        self.last_stats = self.last_backward_stats = None
+        self.last_stats = self.last_backward_stats = self.last_edge_stats = None
         h = C.c_void_p()
         keep = self.adj if self.E else ctx.empty(1, torch.int32)
         _l.check(ctx.L.vgl_hip_agg_plan_create(ctx.h, _ptr(self.rowptr), _ptr(keep), self.n_rows, self.n_cols, C.byref(h)))
@@ -1575,6 +1575,39 @@ class AggregationPlan:
         self.last_backward_stats = _agg_stats(st)
         return gx
 
+    # one float32 per entry (vgl_hip_agg_sddmm / _edge_softmax in include/vgl_hip.h); last_edge_stats: the stats of the latest call
+    def _sddmm(self, a, b, mean=0):
+        ctx, F = self.ctx, int(a.shape[1])
+        e = torch.empty(self.E, dtype=torch.float32, device=ctx.device)
+        if self.E == 0:
+            return e
+        if F == 0:
+            return e.zero_()
+        a, lda = self._rows(a, "sddmm: a")
+        b, ldb = self._rows(b, "sddmm: b")
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_sddmm(ctx.h, self.h, _ptr(a), lda, _ptr(b), ldb, F, int(mean), _ptr(e), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return e
+
+    def _edge_softmax(self, e):
+        y = torch.empty(self.E, dtype=torch.float32, device=self.ctx.device)
+        if self.E == 0:
+            return y
+        st = _l.AggStats()
+        _l.check(self.ctx.L.vgl_hip_agg_edge_softmax(self.ctx.h, self.h, _ptr(e), _ptr(y), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return y
+
+    def _edge_softmax_backward(self, y, gy):
+        ge = torch.empty(self.E, dtype=torch.float32, device=self.ctx.device)
+        if self.E == 0:
+            return ge
+        st = _l.AggStats()
+        _l.check(self.ctx.L.vgl_hip_agg_edge_softmax_backward(self.ctx.h, self.h, _ptr(y), _ptr(gy), _ptr(ge), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return ge
+
 
 class _Aggregate(torch.autograd.Function):
     @staticmethod
@@ -1615,7 +1648,7 @@ def aggregate(plan, x, op="sum", weight=None, return_arg=False):
         if not torch.is_tensor(weight) or weight.dtype != torch.float32:
             raise _l.VglHipError("aggregate: weight must be a float32 tensor, got %s" % (weight.dtype if torch.is_tensor(weight) else type(weight).__name__))
         if weight.requires_grad:
-            raise _l.VglHipError("aggregate: gradients with respect to entry weights (SDDMM) are not in the library; pass weight.detach()")
+            raise _l.VglHipError("aggregate: differentiable in x only; for gradients with respect to entry weights (SDDMM) call api.spmm, or pass weight.detach()")
         if weight.dim() != 1 or int(weight.numel()) != plan.E or weight.device != plan.ctx.device:
             raise _l.VglHipError("aggregate: weight must hold one value per entry (%d) on the plan's device" % plan.E)
         weight = weight.contiguous()
@@ -1635,3 +1668,121 @@ def aggregate_neighbors(graph, x, op="sum", weight=None, direction="in", raw=Fal
         x = x[graph.bwd.long()]
     out = aggregate(plans[direction], x, op, weight)
     return out[graph.fwd.long()] if permute else out
+
+
+# ---- edge scores, edge softmax and graph attention (the contract of vgl_hip_agg_sddmm / _edge_softmax in include/vgl_hip.h) ----
+def _edge_plan(who, plan):
+    if not isinstance(plan, AggregationPlan) or not plan.h:
+        raise _l.VglHipError("%s: plan must be an open AggregationPlan" % who)
+
+
+def _edge_features(who, name, plan, t, rows, what):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _l.VglHipError("%s: %s must be a float32 tensor, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != 2 or int(t.shape[0]) != rows:
+        raise _l.VglHipError("%s: %s must be %s x F = %d x F, got %s" % (who, name, what, rows, tuple(t.shape)))
+    if t.device != plan.ctx.device:
+        raise _l.VglHipError("%s: %s must live on the plan's device" % (who, name))
+
+
+def _edge_scalars(who, name, plan, t):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _l.VglHipError("%s: %s must be a float32 tensor, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() != 1 or int(t.numel()) != plan.E or t.device != plan.ctx.device:
+        raise _l.VglHipError("%s: %s must hold one value per entry (%d) on the plan's device" % (who, name, plan.E))
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, a, b, plan):
+        fctx.plan = plan
+        fctx.save_for_backward(a, b)
+        return plan._sddmm(a.detach(), b.detach(), 0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, ge):
+        a, b = fctx.saved_tensors
+        ge = ge.contiguous()
+        # the two existing runs with the entry gradient as the weight: ga[i] = sum_p ge[p] b[adj[p]], gb[u] = sum over adj[p] = u of ge[p] a[row(p)]
+        ga = fctx.plan._forward(b, AGG_OPS["sum"], ge)[0] if fctx.needs_input_grad[0] else None
+        gb = fctx.plan._backward(a.contiguous(), AGG_OPS["sum"], ge, None) if fctx.needs_input_grad[1] else None
+        return ga, gb, None
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, e, plan):
+        y = plan._edge_softmax(e.detach().contiguous())
+        fctx.plan = plan
+        fctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gy):
+        (y,) = fctx.saved_tensors
+        return fctx.plan._edge_softmax_backward(y, gy.contiguous()), None
+
+
+class _Spmm(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, weight, x, plan, op):
+        fctx.plan, fctx.op = plan, op
+        fctx.save_for_backward(weight, x)
+        return plan._forward(x.detach(), op, weight.detach())[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g):
+        weight, x = fctx.saved_tensors
+        g = g.contiguous()
+        gw = fctx.plan._sddmm(g, x, 1 if fctx.op == AGG_OPS["mean"] else 0) if fctx.needs_input_grad[0] else None
+        gx = fctx.plan._backward(g, fctx.op, weight, None) if fctx.needs_input_grad[1] else None
+        return gw, gx, None, None
+
+
+def sddmm(plan, a, b):
+    """e[p] = the dot product of a[row(p), :] and b[adj[p], :] for every stored entry p of the plan, in CSR order (a: n_rows x F, b: n_cols x F, float32
+    on the plan's device) -> E float32.  Differentiable in a and b, first order: the backward is aggregate's forward kernel (grad a) and its transposed
+    kernel (grad b) with the entry gradient as the weight, without atomics, the same bits on every run.  Column slices and offset views go with their
+    leading dimension.  One call at a time per context."""
+    _edge_plan("sddmm", plan)
+    _edge_features("sddmm", "a", plan, a, plan.n_rows, "n_rows")
+    _edge_features("sddmm", "b", plan, b, plan.n_cols, "n_cols")
+    if int(a.shape[1]) != int(b.shape[1]):
+        raise _l.VglHipError("sddmm: a and b must have the same width F, got %d and %d" % (int(a.shape[1]), int(b.shape[1])))
+    return _Sddmm.apply(a, b, plan)
+
+
+def edge_softmax(plan, e):
+    """y[p] = exp(e[p] - m) / s over the entries of each row of the plan (m the row's largest score, s the sum; one division per entry) -> E float32.
+    An entry at -inf gets 0, a row of -inf alone 0 everywhere; with NaN or +inf the result is unspecified.  Differentiable, first order:
+    ge[p] = y[p] * (gy[p] - sum_q y[q] gy[q])."""
+    _edge_plan("edge_softmax", plan)
+    _edge_scalars("edge_softmax", "e", plan, e)
+    return _EdgeSoftmax.apply(e, plan)
+
+
+def spmm(plan, weight, x, op="sum"):
+    """aggregate(plan, x, op, weight) for op "sum" or "mean", differentiable in BOTH weight (one float32 per entry) and x (n_cols x F): grad x is the
+    transposed run, grad weight[p] = the dot product of grad_out[row(p), :] and x[adj[p], :] (divided by the row's length for "mean"), first order."""
+    _edge_plan("spmm", plan)
+    if op not in ("sum", "mean"):
+        raise _l.VglHipError("spmm: op must be 'sum' or 'mean', got %r" % (op,))
+    _edge_scalars("spmm", "weight", plan, weight)
+    _edge_features("spmm", "x", plan, x, plan.n_cols, "n_cols")
+    return _Spmm.apply(weight.contiguous(), x, plan, AGG_OPS[op])
+
+
+def graph_attention(plan, q, k, v, scale=None, return_weights=False):
+    """out[i, :] = sum over the entries p of row i of softmax_row(scale * q[i] . k[adj[p]])[p] * v[adj[p], :]: dot-product attention of every row over
+    its stored entries (q: n_rows x F, k: n_cols x F, v: n_cols x Fv; scale F ** -0.5 unless given).  It IS spmm(plan, edge_softmax(plan, sddmm(plan,
+    q, k) * scale), v) and nothing else, so it is differentiable in q, k and v.  One head: call per column slice for more.  With return_weights=True
+    also the E attention weights."""
+    e = sddmm(plan, q, k)
+    if scale is None:
+        scale = float(q.shape[1]) ** -0.5 if int(q.shape[1]) > 0 else 1.0
+    w = edge_softmax(plan, e * scale)
+    out = spmm(plan, w, v)
+    return (out, w) if return_weights else out

@@ -14,8 +14,7 @@
 //   hubs       a row of more than one chunk leaves one partial per chunk; one writer per (row, column) finishes them in chunk order.
 // Every value has one writer and every sum a shape fixed by (row length, F, VEC, the three switches): no floating-point atomic, no scratch memory, no
 // cooperative launch, no wait on a flag, no retry loop.
-#include "vgl_rowclass.h"
-#include "vgl_prim.h"
+#include "vgl_agg.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -23,35 +22,10 @@
 namespace {
 
 enum { AGG_K_SUM = 0, AGG_K_EXT = 1 };           // the kernel's OP: a sum of coefficient x value (sum, mean, every backward), an extreme (max, min)
-constexpr int64_t AGG_MAX_GRID = 1024;           // workgroups of a grid-stride kernel
-const int64_t agg_grid_cap[VGL_RC_N] = {4096, 4096, 4096};
 constexpr int64_t AGG_MAX_ENTRIES = 0x7FFFFFF0LL;  // positions are int32 in d_arg and in the transpose's origin
 enum { AC_ROWS = 0, AC_TAIL = 3, AC_BAD = 6, AC_WORK = 7, AC_ENT = 8, AC_NCNT = 11 };
 static_assert(AC_NCNT <= C_NSLOTS, "the counters are mirrored in the context's pinned slots");
 
-template <int VEC> __device__ __forceinline__ void agg_load(const float *p, float *out)
-{
-    if constexpr (VEC == 4) { const float4 t = *reinterpret_cast<const float4 *>(p); out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w; }
-    else out[0] = p[0];
-}
-template <int VEC> __device__ __forceinline__ void agg_load(const int32_t *p, int32_t *out)
-{
-    if constexpr (VEC == 4) { const int4 t = *reinterpret_cast<const int4 *>(p); out[0] = t.x; out[1] = t.y; out[2] = t.z; out[3] = t.w; }
-    else out[0] = p[0];
-}
-template <int VEC> __device__ __forceinline__ void agg_store(float *p, const float *v)
-{
-    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-template <int VEC> __device__ __forceinline__ void agg_store(int32_t *p, const int32_t *v)
-{
-    if constexpr (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(v[0], v[1], v[2], v[3]);
-    else p[0] = v[0];
-}
-
-// the items of a class: rows; the workgroup class lists chunks: item i is chunk chunk[i] of row rows[i]
-struct agg_list { const int32_t *rows, *chunk; };
 // one pass.  Forward: the CSR is the plan's, a term's source row is adj[p], its coefficient weight[p].  Transposed: the CSR is the transpose, adj[p] is
 // row(o) of the origin o = origin[p], the coefficient is read through o.
 struct agg_args {
@@ -335,35 +309,6 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_agg_narrow(const int64_t *in,
     for (int64_t p = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; p < n; p += (int64_t)gridDim.x * VGL_BLOCK) out[p] = (int32_t)in[p];
 }
 
-}  // namespace
-
-// the rows of a CSR by class in ascending order, the chunks of its workgroup rows and the rows of more than one chunk
-struct vgl_agg_lists {
-    vgl_dev<int32_t> rows;                           // class 0, then 1, then 2
-    vgl_dev<int32_t> item_row, item_chunk;           // the workgroup class's items: (row, chunk)
-    vgl_dev<int32_t> hub_row, hub_first, hub_nch;    // the rows of more than one chunk: row, first item, chunks
-    int64_t n[VGL_RC_N] = {0, 0, 0};                 // items per class
-    int64_t rows_of[VGL_RC_N] = {0, 0, 0}, entries_of[VGL_RC_N] = {0, 0, 0};
-    int64_t nhubs = 0, entries = 0;
-    vgl_rc_chunks ch = vgl_rc_chunks::whole();
-};
-
-struct vgl_hip_agg_plan {
-    vgl_hip_ctx *c = nullptr;
-    const int64_t *rowptr = nullptr;                 // borrowed
-    const int32_t *adj = nullptr;
-    int32_t n_rows = 0, n_cols = 0;
-    int64_t E = 0;
-    vgl_rc_bounds b{};
-    int64_t chunk_env = 0;
-    vgl_agg_lists fwd, tr;
-    bool has_tr = false;
-    vgl_dev<int64_t> t_rowptr;                       // the transpose: n_cols rows
-    vgl_dev<int32_t> t_adj, t_origin;                // row(p) and p of its entries
-};
-
-namespace {
-
 // rowptr: n + 1 bounds on the device.  check: a bad rowptr is the caller's (refused by `bad_msg`), else an internal error.
 int agg_build_lists(vgl_hip_ctx *c, const char *slot, const int64_t *rowptr, int32_t n, vgl_rc_bounds b, int64_t chunk_env, const char *bad_msg, vgl_agg_lists &L)
 {
@@ -484,8 +429,6 @@ int agg_build_transpose(vgl_hip_ctx *c, vgl_hip_agg_plan *p)
     return 0;
 }
 
-bool agg_aligned16(const void *q) { return ((uintptr_t)q & 15u) == 0; }
-
 template <int OP, int VEC, bool TR>
 int agg_pass(vgl_hip_ctx *c, const vgl_agg_lists &L, const agg_args &a)
 {
@@ -500,19 +443,6 @@ int agg_pass(vgl_hip_ctx *c, const vgl_agg_lists &L, const agg_args &a)
     }
     VGL_HIP_TRY(hipGetLastError());
     return 0;
-}
-
-// the lanes per column tile of each class, and the tiles
-void agg_shape(int32_t F, int vec, int32_t *lognq, int32_t *tiles)
-{
-    const int64_t groups = vgl_ceil_div(F, vec);
-    for (int q = 0; q < VGL_RC_N; q++) {
-        const int cap = q == VGL_RC_SHORT ? 3 : 6;                    // 8 lanes of a short team, 64 of a wave (the workgroup folds its four waves)
-        int lg = 0;
-        while (lg < cap && ((int64_t)1 << lg) < groups) lg++;
-        lognq[q] = lg;
-        tiles[q] = (int32_t)vgl_ceil_div(groups, (int64_t)1 << lg);
-    }
 }
 
 // what both runs share once their arguments are checked: the pass over L, the stats

@@ -1,0 +1,327 @@
+// edge.hip -- one float32 per stored entry of an aggregation plan (agg.hip): the dot product of a feature row of the entry's row with a feature row of
+// its column (SDDMM), the softmax of such scalars over each row, and the backward of that softmax.  With the two runs of agg.hip they close the
+// gradients of a weighted aggregation: the gradient with respect to the weights IS the dot product of (grad_out, x), the gradients of the dot product
+// ARE the forward and the transposed run with the incoming entry gradient as the weight.  The contract is written out in include/vgl_hip.h; DESIGN
+// section 30 has the kernels, their resources, the bytes model, the tolerances and the measurements.
+//
+//   dot      the team kernel of the aggregation turned round: the lanes of a team are (entry slot x column group), NQ lanes cover a tile of NQ * VEC
+//            columns, slot s takes entries s, s + SLOTS, ... with four gathers of b in flight; a lane adds its VEC products in column order, tile
+//            after tile, and the NQ lanes of an entry are folded by an xor butterfly at offsets 1, 2, ... NQ / 2; lane q = 0 stores e[p].  The row's
+//            own a stays in registers with one column tile and is re-read per tile (from cache) with more.  Chunks only divide the work.
+//   rows     softmax and its backward: every lane an entry slot.  A row of one chunk is finished by its team (walks: max, sum, write; backward: sum,
+//            write).  A chunk of a longer row leaves (m_c, s_c) (backward: d_c); vgl_k_edge_hubs, a thread per such row, merges them in chunk order
+//            and leaves the row's (M, S) in every one of its chunks' slots; vgl_k_edge_hub_write writes the entries, a workgroup per chunk.
+// Every value has one writer and every sum a shape fixed by (row length, F, VEC, the three switches): no floating-point atomic, no scratch memory, no
+// cooperative launch, no wait on a flag, no retry loop.
+#include "vgl_agg.h"
+#include <cmath>
+#include <cstring>
+#include <string>
+
+namespace {
+
+struct edge_dot_args {
+    const int64_t *rowptr;
+    const int32_t *adj;
+    const float *a, *b;          // n_rows x F (lda), n_cols x F (ldb)
+    float *e;                    // one per entry
+    int64_t lda, ldb;
+    int32_t F, chunk;
+    int32_t lognq[VGL_RC_N], tiles[VGL_RC_N];
+    int32_t mean;                // divide the finished dot by the row's length
+};
+
+template <int CLS, int VEC>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_dot(agg_list l, int32_t n, edge_dot_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    const int lognq = a.lognq[CLS], nq = 1 << lognq, slots = T::LANES >> lognq;
+    const int q = T::lane() & (nq - 1), slot = T::lane() >> lognq;
+    const bool one = a.tiles[CLS] == 1;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        int32_t v = 0;
+        int64_t lo = 0, hi = 0, len = 0;
+        if (has) {
+            v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            len = hi - lo;
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const float *arow = a.a + (int64_t)v * a.lda;
+        float av[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; k++) av[k] = 0.0f;
+        if (one && q * VEC < a.F && lo < hi) agg_load<VEC>(arow + q * VEC, av);     // one tile: the row's values stay in registers
+        int64_t p = lo + slot;
+        // the NQ lanes of a slot share p: they stay together through the loops and the butterfly, a lane past the last column loads nothing
+        for (; p + 3 * (int64_t)slots < hi; p += 4 * (int64_t)slots) {                 // four gathers in flight
+            int32_t u[4];
+            float acc[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) { u[j] = a.adj[p + j * (int64_t)slots]; acc[j] = 0.0f; }
+            for (int base = 0; base < a.F; base += nq * VEC) {
+                const int c0 = base + q * VEC;
+                if (c0 < a.F) {
+                    float t[4][VEC];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) agg_load<VEC>(a.b + (int64_t)u[j] * a.ldb + c0, t[j]);
+                    if (!one) agg_load<VEC>(arow + c0, av);
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+#pragma unroll
+                        for (int k = 0; k < VEC; k++) acc[j] = acc[j] + av[k] * t[j][k];
+                }
+            }
+            for (int o = 1; o < nq; o <<= 1)
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = acc[j] + __shfl_xor(acc[j], o);
+            if (q == 0)
+#pragma unroll
+                for (int j = 0; j < 4; j++) a.e[p + j * (int64_t)slots] = a.mean ? acc[j] / (float)len : acc[j];
+        }
+        for (; p < hi; p += slots) {
+            const int32_t u = a.adj[p];
+            float acc = 0.0f;
+            for (int base = 0; base < a.F; base += nq * VEC) {
+                const int c0 = base + q * VEC;
+                if (c0 < a.F) {
+                    float t[VEC];
+                    agg_load<VEC>(a.b + (int64_t)u * a.ldb + c0, t);
+                    if (!one) agg_load<VEC>(arow + c0, av);
+#pragma unroll
+                    for (int k = 0; k < VEC; k++) acc = acc + av[k] * t[k];
+                }
+            }
+            for (int o = 1; o < nq; o <<= 1) acc = acc + __shfl_xor(acc, o);
+            if (q == 0) a.e[p] = a.mean ? acc / (float)len : acc;
+        }
+    }
+}
+
+// ---- softmax over the rows and its backward ----
+struct edge_rows_args {
+    const int64_t *rowptr;
+    const float *x, *g;          // forward: x = e; backward: x = y, g = gy
+    float *out;                  // y; backward: ge
+    float2 *part;                // per workgroup item, for the rows of more than one chunk: (m_c, s_c); backward (d_c, 0); then the row's (M, S) / (d, 0)
+    int32_t chunk;
+};
+
+// the sum of v over the team, in every lane: an xor butterfly at offsets 1, 2, ... inside the wave, then the workgroup's waves in wave order
+template <int CLS>
+__device__ __forceinline__ float edge_team_sum(float v)
+{
+    constexpr int FOLD = vgl_rc_team<CLS>::LANES < 64 ? vgl_rc_team<CLS>::LANES : 64;
+#pragma unroll
+    for (int o = 1; o < FOLD; o <<= 1) v = v + __shfl_xor(v, o);
+    if constexpr (CLS == VGL_RC_WG) {
+        __shared__ float s_sum[VGL_WAVES];
+        __syncthreads();                                              // the sums of the item before have been read
+        if (vgl_lane() == 0) s_sum[vgl_wave()] = v;
+        __syncthreads();
+        v = s_sum[0];
+#pragma unroll
+        for (int w = 1; w < VGL_WAVES; w++) v = v + s_sum[w];
+    }
+    return v;
+}
+
+// the entries first, first + step, ... below hi, given the row's (m, s) (backward: d in s)
+template <bool BWD>
+__device__ __forceinline__ void edge_write(const edge_rows_args &a, int64_t first, int64_t hi, int step, float m, float s)
+{
+    if constexpr (BWD) {
+        for (int64_t p = first; p < hi; p += step) a.out[p] = a.x[p] * (a.g[p] - s);
+    } else {
+        const bool dead = m == -INFINITY;                             // every entry of the row is at -inf
+        for (int64_t p = first; p < hi; p += step) a.out[p] = dead ? 0.0f : expf(a.x[p] - m) / s;
+    }
+}
+
+template <int CLS, bool BWD>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_rows(agg_list l, int32_t n, edge_rows_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        int64_t lo = 0, hi = 0;
+        bool whole = true;
+        if (has) {
+            const int32_t v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                whole = hi - lo <= a.chunk;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const int64_t first = lo + T::lane();
+        float m = 0.0f, acc = 0.0f;
+        if constexpr (BWD) {
+            for (int64_t p = first; p < hi; p += T::LANES) acc = acc + a.x[p] * a.g[p];
+        } else {
+            float mx = -INFINITY;
+            for (int64_t p = first; p < hi; p += T::LANES) { const float x = a.x[p]; mx = x > mx ? x : mx; }
+            m = T::max_of(mx);
+            if (m != -INFINITY)                                       // (else every term is 0, and -inf - -inf is not formed)
+                for (int64_t p = first; p < hi; p += T::LANES) acc = acc + expf(a.x[p] - m);
+        }
+        const float s = edge_team_sum<CLS>(acc);
+        if (CLS == VGL_RC_WG && !whole) {
+            if (T::lead() && has) a.part[i] = make_float2(BWD ? s : m, BWD ? 0.0f : s);
+        } else edge_write<BWD>(a, first, hi, T::LANES, m, s);
+    }
+}
+
+// the rows of more than one chunk: a thread per row merges its chunks' partials in chunk order and leaves the row's pair in each of their slots
+struct edge_hubs { const int32_t *first, *nch; int32_t n; };
+template <bool BWD>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_hubs(edge_hubs h, float2 *part)
+{
+    for (int64_t k = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; k < h.n; k += (int64_t)gridDim.x * VGL_BLOCK) {
+        float2 *mine = part + h.first[k];
+        const int32_t nch = h.nch[k];
+        float m = 0.0f, s = 0.0f;
+        if constexpr (BWD) {
+            s = mine[0].x;
+            for (int32_t j = 1; j < nch; j++) s = s + mine[j].x;
+        } else {
+            m = mine[0].x;
+            for (int32_t j = 1; j < nch; j++) m = mine[j].x > m ? mine[j].x : m;
+            for (int32_t j = 0; j < nch; j++) {
+                const float2 c = mine[j];
+                if (c.x != -INFINITY) s = s + c.y * expf(c.x - m);    // a chunk of -inf alone contributes nothing
+            }
+        }
+        for (int32_t j = 0; j < nch; j++) mine[j] = make_float2(BWD ? s : m, BWD ? 0.0f : s);
+    }
+}
+// ... and a workgroup per chunk of such a row writes its entries (the items of rows of one chunk were finished by vgl_k_edge_rows)
+template <bool BWD>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_hub_write(agg_list l, int32_t n, edge_rows_args a)
+{
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int32_t v = l.rows[i];
+        const int64_t row_lo = a.rowptr[v], end = a.rowptr[v + 1];
+        if (end - row_lo <= a.chunk) continue;                        // (uniform over the workgroup)
+        const int64_t lo = row_lo + (int64_t)l.chunk[i] * a.chunk, hi = min(end, lo + a.chunk);
+        const float2 ms = a.part[i];
+        edge_write<BWD>(a, lo + threadIdx.x, hi, VGL_BLOCK, ms.x, BWD ? ms.x : ms.y);      // (M, S); backward: d in the first
+    }
+}
+
+// the stats of a run over the plan's CSR; `per_entry` bytes per entry beside the adjacency walks, `per_row` per row beside the list entries
+void edge_stats(const vgl_hip_agg_plan *p, const int32_t *tiles, int vec, int64_t adj_bytes, int64_t per_entry, int64_t per_row, vgl_hip_agg_stats *stats)
+{
+    const vgl_agg_lists &L = p->fwd;
+    vgl_hip_agg_stats s;
+    memset(&s, 0, sizeof(s));
+    s.rows = p->n_rows; s.entries = L.entries;
+    s.rows_short = L.rows_of[0]; s.rows_wave = L.rows_of[1]; s.rows_wg = L.rows_of[2];
+    s.chunks = L.n[VGL_RC_WG]; s.hub_rows = L.nhubs;
+    s.transposed = 0; s.vec = vec;
+    int64_t bytes = 0;
+    for (int q = 0; q < VGL_RC_N; q++) { s.column_tiles[q] = tiles[q]; bytes += L.entries_of[q] * tiles[q] * adj_bytes; }
+    bytes += L.entries * per_entry + (int64_t)p->n_rows * per_row;
+    bytes += 4 * (L.rows_of[0] + L.rows_of[1]) + 8 * L.n[VGL_RC_WG];
+    s.algorithmic_bytes = bytes;
+    *stats = s;
+}
+
+int edge_check_call(const char *who, vgl_hip_ctx *c, vgl_hip_agg_plan *p, const void *x, const void *y, const void *z)
+{
+    static thread_local std::string msg;
+    auto fail = [&](const char *what) { msg = std::string(who) + ": " + what; return vgl_set_error(__FILE__, __LINE__, msg.c_str()); };
+    if (!c || !p || !x || !y || !z) return fail("null argument");
+    if (p->c != c) return fail("the plan belongs to another context");
+    return 0;
+}
+
+template <bool BWD>
+int edge_rows_run(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_x, const float *d_g, float *d_out, vgl_hip_agg_stats *stats)
+{
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const vgl_agg_lists &L = p->fwd;
+    edge_rows_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.x = d_x; a.g = d_g; a.out = d_out;
+    a.chunk = L.ch.chunk;
+    vgl_dev<float> part;
+    if (L.nhubs > 0) VGL_TRY(part.alloc(st, 2 * (size_t)L.n[VGL_RC_WG]));
+    a.part = reinterpret_cast<float2 *>(part.p);
+    const char *const slot[VGL_RC_N] = {"edge_short", "edge_wave", "edge_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_rows<VGL_RC_SHORT, BWD>, vgl_k_edge_rows<VGL_RC_WAVE, BWD>, vgl_k_edge_rows<VGL_RC_WG, BWD>, list, a));
+    if (L.nhubs > 0) {
+        const edge_hubs hubs{L.hub_first.p, L.hub_nch.p, (int32_t)L.nhubs};
+        {
+            vgl_timed_launch tl(c, "edge_hubs");
+            hipLaunchKernelGGL(vgl_k_edge_hubs<BWD>, dim3(vgl_grid(L.nhubs, VGL_BLOCK, AGG_MAX_GRID)), dim3(VGL_BLOCK), 0, st, hubs, a.part);
+        }
+        vgl_timed_launch tl(c, "edge_hub_write");
+        hipLaunchKernelGGL(vgl_k_edge_hub_write<BWD>, dim3(vgl_grid(L.n[VGL_RC_WG], 1, agg_grid_cap[VGL_RC_WG])), dim3(VGL_BLOCK), 0, st, list[VGL_RC_WG], (int32_t)L.n[VGL_RC_WG], a);
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_HIP_TRY(hipStreamSynchronize(st));                            // (the partials are free again; the result is there when the call returns)
+    if (stats) {
+        const int32_t tiles[VGL_RC_N] = {1, 1, 1};
+        // forward: three walks of e and y written; backward: two walks of y and gy and ge written; 8 bytes of bounds per row
+        edge_stats(p, tiles, 1, 0, BWD ? 8 * 2 + 4 : 4 * 3 + 4, 8, stats);
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vgl_hip_agg_sddmm(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int mean, float *d_e, vgl_hip_agg_stats *stats)
+{
+    // every refusal comes before the first write to an output
+    VGL_TRY(edge_check_call("agg_sddmm", c, p, d_a, d_b, d_e));
+    if (F < 1) VGL_FAIL("agg_sddmm: F must be at least 1");
+    if (lda < F || ldb < F) VGL_FAIL("agg_sddmm: a leading dimension must not be below F");
+    if (mean != 0 && mean != 1) VGL_FAIL("agg_sddmm: mean must be 0 or 1");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    const vgl_agg_lists &L = p->fwd;
+    edge_dot_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.adj = p->adj;
+    a.a = d_a; a.lda = lda; a.b = d_b; a.ldb = ldb; a.e = d_e;
+    a.F = F; a.chunk = L.ch.chunk; a.mean = mean;
+    const int vec = F % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && agg_aligned16(d_a) && agg_aligned16(d_b) ? 4 : 1;
+    agg_shape(F, vec, a.lognq, a.tiles);
+    const char *const slot[VGL_RC_N] = {"edge_dot_short", "edge_dot_wave", "edge_dot_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    if (vec == 4)
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_dot<VGL_RC_SHORT, 4>, vgl_k_edge_dot<VGL_RC_WAVE, 4>, vgl_k_edge_dot<VGL_RC_WG, 4>, list, a));
+    else
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_dot<VGL_RC_SHORT, 1>, vgl_k_edge_dot<VGL_RC_WAVE, 1>, vgl_k_edge_dot<VGL_RC_WG, 1>, list, a));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));                     // (the result is there when the call returns)
+    // per entry: 4 F of b gathered and e written; per row: the bounds and 4 F of a; the adjacency once per column tile
+    if (stats) edge_stats(p, a.tiles, vec, 4, 4 * (int64_t)F + 4, 8 + 4 * (int64_t)F, stats);
+    return 0;
+}
+
+int vgl_hip_agg_edge_softmax(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_e, float *d_y, vgl_hip_agg_stats *stats)
+{
+    VGL_TRY(edge_check_call("agg_edge_softmax", c, p, d_e, d_y, d_y));
+    return edge_rows_run<false>(c, p, d_e, nullptr, d_y, stats);
+}
+
+int vgl_hip_agg_edge_softmax_backward(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_y, const float *d_gy, float *d_ge, vgl_hip_agg_stats *stats)
+{
+    VGL_TRY(edge_check_call("agg_edge_softmax_backward", c, p, d_y, d_gy, d_ge));
+    return edge_rows_run<true>(c, p, d_y, d_gy, d_ge, stats);
+}
+
+}  // extern "C"
