@@ -1425,10 +1425,23 @@ int vgl_hip_pr_setup(vgl_hip_ctx *ctx, int32_t V, const int32_t *d_indeg_noloops
 /* The sum-type all-active advance of PR::vgl_page_rank (algorithms/pr/pr.hpp:105-124: `page_ranks[src] += contribution[dst]` over every edge
  * src -> dst with dst != src) with the caller's own arrays: d_sums[src] = sum over those edges of d_values[dst], for the rows the handle owns.
  * Runs as the blocked pass (values read from LDS windows, exact 64-bit fixed-point accumulation, rounded to f32 once: the same bits for any
- * schedule; it differs from an f32 `+=` chain in adjacency order by the chain's own rounding).  d_values must be non-negative and every
- * per-vertex sum at most sum_bound (the unit of the fixed point is derived from it; PageRank contributions: 1).  The layout is the one
- * vgl_hip_pr_prepare(BLOCKED) builds (built here on first use).  Asynchronous on the context's stream. */
+ * schedule; it differs from an f32 `+=` chain in adjacency order by the chain's own rounding).  The layout is the one
+ * vgl_hip_pr_prepare(BLOCKED) builds (built here on first use).  Asynchronous on the context's stream.
+ * The fixed point: with sum_bound = m * 2^e, 0.5 <= m < 1, the unit is 2^(e + 1 - 62) and the CAPACITY of a sum 2^(e + 1), at least twice the
+ * bound.  A value converts exactly while it is a multiple of the unit, loses less than one unit otherwise (truncation) and contributes
+ * nothing below 2^-23 units; a subnormal RESULT is outside the contract.
+ * The contract, enforced: every value is +-0 or a positive finite number below the capacity, and every per-vertex sum stays below the
+ * capacity.  A value that breaks it contributes nothing, the sums that it or an overflow touches are unspecified, and the call leaves a
+ * VGL_HIP_SUM_* bit for vgl_hip_sum_over_edges_check.  The values of a gather block are checked when an edge reads from the block, the sums
+ * in the epilogue.  Not detectable: a sum that wrapped past 2^64 units (more than four times the capacity) and came back below 2^62. */
 int vgl_hip_sum_over_edges_f32(vgl_hip_ctx *ctx, vgl_hip_graph *g, const float *d_values, float sum_bound, float *d_sums);
+#define VGL_HIP_SUM_NEGATIVE 1u        /* a value below zero (-0.0 is a zero) */
+#define VGL_HIP_SUM_NOT_FINITE 2u      /* a NaN or an infinity */
+#define VGL_HIP_SUM_VALUE_TOO_LARGE 4u /* a value at or above the capacity */
+#define VGL_HIP_SUM_TOTAL_TOO_LARGE 8u /* a per-vertex sum at or above the capacity */
+/* Waits for the context's stream; *violations = the VGL_HIP_SUM_* bits left by the vgl_hip_sum_over_edges_f32 calls on this context since
+ * the last check (0: every one of them kept the contract), which are cleared.  Returns non-zero only when the check itself fails. */
+int vgl_hip_sum_over_edges_check(vgl_hip_ctx *ctx, unsigned *violations);
 int vgl_hip_pr_iteration_owned(vgl_hip_ctx *ctx, vgl_hip_graph *g, const int32_t *d_indeg_noloops, const float *d_rdeg,
                                float *d_ranks, float *d_contrib_scratch);
 /* "Recently changed" exchange of a replicated 4-byte vertex array (EXCHANGE_RECENTLY_CHANGED, common/mpi_exchange.hpp:110-150): instead

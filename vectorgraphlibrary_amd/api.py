@@ -18,6 +18,8 @@ BFS_TOP_DOWN, BFS_DIRECTION_OPT = 0, 1
 SSSP_ALL_ACTIVE, SSSP_ACTIVE_TILES, SSSP_DELTA_STEPPING, SSSP_PULL, SSSP_DIRECTION_OPT = 0, 1, 2, 3, 4
 DENSE, SPARSE, ALL_ACTIVE = 0, 1, 2    # framework_types.h:156-160
 PR_EXACT_ORDER, PR_BLOCKED, PR_AUTO = 0, 1, 2
+# VGL_HIP_SUM_* of include/vgl_hip.h: what vgl_hip_sum_over_edges_check reports
+SUM_VIOLATIONS = ((1, "negative value"), (2, "value not finite"), (4, "value at or above the capacity"), (8, "sum at or above the capacity"))
 LP_ALL_ACTIVE, LP_FRONTIER, LP_AUTO = 0, 1, 2
 
 
@@ -470,11 +472,17 @@ def page_rank(graph, iterations, indeg_noloops=None, ranks=None, raw=False, mode
 
 def sum_over_edges(graph, values, bound=1.0):
     """sums[src] = sum of values[dst] over the edges src -> dst with dst != src (graph's own numbering; the declared operator VGL_SUM_OVER_EDGES):
-    exact fixed-point sums rounded to f32 once.  values: non-negative f32, every per-vertex sum at most `bound`."""
+    exact fixed-point sums rounded to f32 once.  values: non-negative finite f32 (-0.0 is a zero), every per-vertex sum at most `bound`.
+    Raises VglHipError naming what broke that contract (include/vgl_hip.h: the capacity of a value and of a sum is a power of two, at
+    least twice the bound); a sum that wrapped past four times the capacity cannot be detected."""
     ctx = graph.ctx
     sums = ctx.empty(graph.V, torch.float32)
     _l.check(ctx.L.vgl_hip_sum_over_edges_f32(ctx.h, graph.h, _ptr(values), C.c_float(float(bound)), _ptr(sums)))
-    ctx.sync()
+    bits = C.c_uint(0)
+    _l.check(ctx.L.vgl_hip_sum_over_edges_check(ctx.h, C.byref(bits)))      # waits for the stream
+    if bits.value:
+        kinds = [name for bit, name in SUM_VIOLATIONS if bits.value & bit]
+        raise _l.VglHipError("sum_over_edges: " + ", ".join(kinds) + f" (bound {float(bound)!r})")
     return sums
 
 

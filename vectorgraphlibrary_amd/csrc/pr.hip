@@ -263,6 +263,18 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
     return 0;
 }
 
+// 64-bit fixed point -> f32 with ONE rounding: acc * 2^exp2.  Through a double it would be two (a u64 with more than 53 significant bits is
+// rounded to double, then again to f32: 2^59 + 2^35 + 1 lands on the f32 tie after the first and goes down to even instead of up).  So the
+// integer is normalised, its top 32 bits keep everything below them as a sticky bit 0 -- far under the f32 rounding position, bit 7 -- the
+// one rounding is that of u32 -> f32, and the scaling by a power of two is exact (normal results).  No f64 instruction.
+static __device__ __forceinline__ float vgl_fixed_to_f32(unsigned long long acc, int exp2)
+{
+    const int top = 64 - __clzll((long long)acc);                                           // significant bits (acc = 0: clz = 64, top = 0)
+    const unsigned long long norm = acc << ((64 - top) & 63);                                // leading bit at 63 (acc = 0 stays 0)
+    const uint32_t m = (uint32_t)(norm >> 32) | (uint32_t)((uint32_t)norm != 0u);
+    return ldexpf((float)m, top - 32 + exp2);
+}
+
 // Blocked pull (vgl_blocked.h): contrib[dst] is read from a 128 KiB LDS window instead of one L2 line per edge and the per-row sums
 // are kept in 64-bit FIXED POINT (unit 2^-62; LDS float atomics are ~30x slower than integer ones on this chip): every contribution
 // of at least 2^-39 converts exactly, smaller ones lose less than 2^-62 each, integer addition is associative -- so the sum is the
@@ -273,6 +285,7 @@ int vgl_pull_find_hubs(vgl_hip_ctx *c, vgl_hip_graph *g, vgl_dir_csr &dir)
 struct vgl_pr_blk_op {
     typedef unsigned long long acc_t;
     static constexpr bool MARK = false;
+    static constexpr bool CHECKED = false;
     const float *contrib;
     const float *dangling;
     float k, d;
@@ -297,7 +310,7 @@ struct vgl_pr_blk_op {
     __device__ __forceinline__ bool partial(int32_t, acc_t) const { return false; }
     __device__ __forceinline__ void finish(int32_t i, acc_t acc) const
     {
-        const float sum = (float)((double)acc * 0x1p-62);           // 53 of the 64 bits, then f32: the double rounding is below 2^-53 relative
+        const float sum = vgl_fixed_to_f32(acc, -62);               // the exact sum, rounded once
         ranks_out[a_base + i] = __fadd_rn(k, __fmul_rn(d, __fadd_rn(sum, *dangling)));
     }
 };
@@ -305,14 +318,33 @@ struct vgl_pr_blk_op {
 // The declared operator VGL_SUM_OVER_EDGES (hip/vgl_hip.hpp): sums[src] = sum of values[dst] over the edges src -> dst, dst != src -- the pull of
 // pr.hpp:109-123 with the caller's own arrays.  Same fixed-point accumulation as vgl_pr_blk_op, the unit scaled by the caller's bound on a
 // per-vertex sum (rounded up to a power of two, so the scaling is exact); the epilogue stores the sum, the caller's post operator does the rest.
+// The caller's values are not PageRank's products: check() and finish() enforce the contract of include/vgl_hip.h, the per-edge code is the same.
 struct vgl_sum_blk_op {
     typedef unsigned long long acc_t;
     static constexpr bool MARK = false;
+    static constexpr bool CHECKED = true;                   // check(), finish(i, acc, flags), raise()
     const float *values;
     float *sums;
     int32_t a_base;
-    int bound_exp;                                          // per-vertex sums stay below 2^bound_exp
+    int bound_exp;                                          // per-vertex sums stay below 2^bound_exp: 2^62 units, the CAPACITY of an accumulator
+    unsigned long long *violations;                         // VGL_HIP_SUM_* bits of the values and sums that broke the contract (a context counter slot)
+    uint32_t cap_bits;                                      // the f32 bits of the capacity (never above those of +Inf)
+    // The value check, once per id and gather unit (never per edge): a negative, non-finite or too-large value is reported and travels as
+    // zero bits, so what reaches the shift of accumulate() is non-negative and below the capacity: less than 2^62 units, no shift by 64 or
+    // more for any input bits (sh <= 38 with the hidden bit set; a subnormal has none).  -0.0 is a zero like +0.0.
+    // The kinds are collected in the thread's `flags` and raised once per thread by raise() (OP::CHECKED in vgl_blocked.h).
     __device__ __forceinline__ uint32_t load(int32_t i) const { return __float_as_uint(values[i]); }
+    __device__ __forceinline__ uint32_t check(uint32_t bits, unsigned &flags) const
+    {
+        if (__builtin_expect(bits < cap_bits, 1)) return bits;      // +0.0 and the positive finite values below the capacity, in the order of their bits
+        if (bits == 0x80000000u) return 0u;                         // -0.0
+        flags |= (bits & 0x7F800000u) == 0x7F800000u ? VGL_HIP_SUM_NOT_FINITE : (bits >> 31) ? VGL_HIP_SUM_NEGATIVE : VGL_HIP_SUM_VALUE_TOO_LARGE;
+        return 0u;
+    }
+    __device__ __forceinline__ void raise(unsigned flags) const
+    {
+        if (flags) atomicOr(violations, (unsigned long long)flags);
+    }
     __device__ __forceinline__ uint32_t edge(uint32_t x, float) const { return x; }
     __device__ __forceinline__ acc_t identity() const { return 0ull; }
     __device__ __forceinline__ void accumulate(acc_t *p, uint32_t bits) const
@@ -324,7 +356,12 @@ struct vgl_sum_blk_op {
     }
     __device__ __forceinline__ acc_t combine(acc_t a, acc_t b) const { return a + b; }
     __device__ __forceinline__ bool partial(int32_t, acc_t) const { return false; }
-    __device__ __forceinline__ void finish(int32_t i, acc_t acc) const { sums[a_base + i] = (float)ldexp((double)acc, bound_exp - 62); }
+    // the sum check: an accumulator at or above the capacity (one that wrapped past 2^64 units cannot be told from a small one)
+    __device__ __forceinline__ void finish(int32_t i, acc_t acc, unsigned &flags) const
+    {
+        flags |= (acc >> 62) ? VGL_HIP_SUM_TOTAL_TOO_LARGE : 0u;
+        sums[a_base + i] = vgl_fixed_to_f32(acc, bound_exp - 62);
+    }
 };
 
 // VGL_PR_MODE=0|1 overrides AUTO (anything else is refused)
@@ -450,8 +487,20 @@ int vgl_hip_sum_over_edges_f32(vgl_hip_ctx *c, vgl_hip_graph *g, const float *d_
     (void)frexpf(sum_bound, &bound_exp);                    // sum_bound = m * 2^bound_exp, 0.5 <= m < 1: sums < 2^bound_exp, one spare bit on top
     bound_exp += 1;
     VGL_TRY(vgl_pr_layout(c, g));
-    const vgl_sum_blk_op op{d_values, d_sums, g->row_begin, bound_exp};
+    // 2^bound_exp as f32 bits: -147 <= bound_exp <= 62, so it is a normal or a subnormal f32
+    const uint32_t cap_bits = bound_exp >= -126 ? (uint32_t)(bound_exp + 127) << 23 : 1u << (bound_exp + 149);
+    const vgl_sum_blk_op op{d_values, d_sums, g->row_begin, bound_exp, (unsigned long long *)(c->d_counters + C_SUM_CHECK), cap_bits};
     return vgl_blocked_pass<vgl_sum_blk_op, false, true>(c, *g->blk_pr, nullptr, op, "sum_blk_gather", "sum_blk_accumulate");
+}
+
+int vgl_hip_sum_over_edges_check(vgl_hip_ctx *c, unsigned *violations)
+{
+    if (!c || !violations) VGL_FAIL("sum_over_edges_check: null argument");
+    unsigned long long bits = 0;
+    VGL_TRY(vgl_hip_memcpy_d2h(c, &bits, c->d_counters + C_SUM_CHECK, sizeof(bits)));      // waits for the stream
+    if (bits) VGL_TRY(vgl_zero_counters(c, C_SUM_CHECK, 1));                               // (stream-ordered before any later pass)
+    *violations = (unsigned)bits;
+    return 0;
 }
 
 int vgl_hip_pr_setup(vgl_hip_ctx *c, int32_t V, const int32_t *d_indeg, float *d_ranks, float *d_rdeg)

@@ -171,6 +171,7 @@ template <class Path>
 struct vgl_path_blk_op {
     typedef uint32_t acc_t;
     static constexpr bool MARK = true;
+    static constexpr bool CHECKED = false;
     float *dist;
     uint64_t *changed;           // bitmap of the vertices this step improved = the frontier of the next step
     int32_t g_base;

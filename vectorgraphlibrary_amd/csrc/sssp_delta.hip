@@ -62,6 +62,7 @@ struct vgl_hip_sssp_plan {
 struct vgl_ds_blk_op {
     typedef uint32_t acc_t;
     static constexpr bool MARK = true;
+    static constexpr bool CHECKED = false;
     float *dist;
     uint8_t *state;
     const uint8_t *active;

@@ -133,6 +133,8 @@ int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan &p, const flo
 // ---------------------------------------------------------------------------------------------------------------------------
 // kernels (templates over the edge operator; instantiated by pr.hip / sssp.hip / cc.hip)
 //   OP::load(i)            -> uint32 bits of x[i] (i = index on the gather side, < g_count)
+//   OP::CHECKED            true (two-pass scheme only): the operator checks its input and its results -- check(bits, flags) -> the bits that enter
+//                          the window, finish(i, acc, flags) instead of finish(i, acc), raise(flags) once per thread after its loop
 //   OP::edge(xbits, w)     -> uint32 bits of the value that travels to the accumulate side (w = 0 without edge values)
 //   OP::acc_t              accumulator type in LDS: uint32_t (blocks of 32768 on the accumulate side) or uint64_t (16384)
 //   OP::identity()         -> value the accumulators start from
@@ -144,6 +146,32 @@ int vgl_blocked_plan_load_weights(vgl_hip_ctx *c, vgl_blocked_plan &p, const flo
 //                          atomic), or return false to have the unit write its accumulators to a slab (sum-type operators);
 //                          vgl_k_blk_finish_slabs then adds the slabs in unit order and calls finish
 // ---------------------------------------------------------------------------------------------------------------------------
+// the x window of a gather unit.  A CHECKED operator's check(bits, flags) returns the bits that enter the window; the flags stay in a register
+// and are raised once per thread, and the loads are issued sixteen at a time ahead of their checks, as many as the plain loop keeps in flight
+// ("blocked sums", has the measurements)
+template <class OP>
+static __device__ __forceinline__ void vgl_blk_load_window(const OP &op, uint32_t *s_x, int32_t base, int n)
+{
+    if constexpr (OP::CHECKED) {
+        constexpr int AHEAD = 16;
+        unsigned flags = 0;
+        for (int i0 = threadIdx.x; i0 < n; i0 += AHEAD * VGL_BTHREADS) {
+            uint32_t raw[AHEAD];
+#pragma unroll
+            for (int k = 0; k < AHEAD; k++) raw[k] = op.load(base + min(i0 + k * VGL_BTHREADS, n - 1));   // (past the end: id n - 1 again, not stored)
+#pragma unroll
+            for (int k = 0; k < AHEAD; k++) {
+                const int i = i0 + k * VGL_BTHREADS;
+                const uint32_t x = op.check(raw[k], flags);
+                if (i < n) s_x[i] = x;
+            }
+        }
+        op.raise(flags);
+    } else {
+        for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) s_x[i] = op.load(base + i);
+    }
+}
+
 template <class OP, bool WEIGHTED>
 __global__ __launch_bounds__(VGL_BTHREADS) void vgl_k_blk_gather(const vgl_blk_unit *units, const uint16_t *g_lo, const float *w_mid,
                                                                  const uint32_t *mid_to_a, uint32_t *vals, int32_t g_count, OP op)
@@ -152,7 +180,7 @@ __global__ __launch_bounds__(VGL_BTHREADS) void vgl_k_blk_gather(const vgl_blk_u
     const vgl_blk_unit u = units[blockIdx.x];
     const int32_t base = u.block << VGL_BLK_BITS;
     const int n = min(VGL_BLK, g_count - base);
-    for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) s_x[i] = op.load(base + i);
+    vgl_blk_load_window(op, s_x, base, n);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane >> 3, off = (lane & 7) * 8;                // this lane: entries off..off+7 of chunk m0 + sub
@@ -223,7 +251,13 @@ __global__ __launch_bounds__(VGL_BTHREADS) void vgl_k_blk_accumulate(const vgl_b
         return;
     }
     if (u.slab < 0) {
-        for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) op.finish(base + i, s_acc[i]);
+        if constexpr (OP::CHECKED) {
+            unsigned flags = 0;
+            for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) op.finish(base + i, s_acc[i], flags);
+            op.raise(flags);
+        } else {
+            for (int i = threadIdx.x; i < n; i += VGL_BTHREADS) op.finish(base + i, s_acc[i]);
+        }
     } else {
         acc_t *slab = slabs + (size_t)u.slab * AN;
         for (int i = threadIdx.x; i < n; i += VGL_BTHREADS)
@@ -238,6 +272,7 @@ template <class OP, bool WEIGHTED>
 __global__ __launch_bounds__(VGL_BTHREADS) void vgl_k_blk_fused(const vgl_blk_funit *units, const vgl_blk_fseg *segs, const uint16_t *g_lo, const uint16_t *a_lo,
                                                                 const float *w, int32_t g_count, int32_t a_count, OP op)
 {
+    static_assert(!OP::CHECKED, "fused tiles load their window without the operator's check: CHECKED operators are two-pass only");
     __shared__ uint32_t s_x[VGL_FBLK];
     __shared__ uint32_t s_acc[VGL_FBLK + VGL_CHUNK];
     const vgl_blk_funit u = units[blockIdx.x];
@@ -299,11 +334,14 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_blk_finish_slabs(const vgl_bl
     const vgl_blk_multi mb = multi[blockIdx.x];
     const int32_t base = mb.block << ABITS;
     const int n = min(AN, a_count - base);
+    unsigned flags = 0;
     for (int i = blockIdx.y * VGL_BLOCK + threadIdx.x; i < n; i += gridDim.y * VGL_BLOCK) {
         acc_t acc = op.identity();
         for (int s = 0; s < mb.nslabs; s++) acc = op.combine(acc, slabs[(size_t)(mb.first_slab + s) * AN + i]);
-        op.finish(base + i, acc);
+        if constexpr (OP::CHECKED) op.finish(base + i, acc, flags);
+        else op.finish(base + i, acc);
     }
+    if constexpr (OP::CHECKED) op.raise(flags);
 }
 
 // one blocked pass: per piece the gather kernel, the accumulate kernel, the fused tiles and (sum-type operators) the slab epilogue, enqueued on

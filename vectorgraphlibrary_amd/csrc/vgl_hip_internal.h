@@ -36,6 +36,7 @@ enum {
     C_EDGES = 6, C_TMP0 = 7, C_TMP1 = 8, C_JUMP = 9,
     C_NEXT_F = 10, C_NEXT_M = 11,    // device only: size / out-degree sum of the frontier an emitting top-down level (or the list kernel) just produced
     C_SKIPPED = 12, C_HINT = 13,     // host mirror only: the bitmap count skipped its degree pass (the level turns bottom-up) / the list kernel left C_NEXT_*
+    C_SUM_CHECK = 14,                // device only: VGL_HIP_SUM_* bits of the sum over edges, kept until vgl_hip_sum_over_edges_check takes them
     C_NSLOTS = 32
 };
 // sharded accumulators: kernels launched with very many workgroups add into shard (blockIdx & (VGL_NSHARD-1)) so that no

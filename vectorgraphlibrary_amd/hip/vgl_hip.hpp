@@ -1011,7 +1011,11 @@ inline vgl_declared_relax VGL_RELAX_OVER_EDGES(VerticesArray<float> &distances, 
 // VGL_SUM_OVER_EDGES(sums, values[, bound]): "sums[src] = sum of values[dst] over every edge src -> dst with dst != src" (the pull of PageRank,
 // pr.hpp:109-123, whose edge operator is `page_ranks[src] += old_rank[dst] * reversed_degree[dst]` outside self loops).  Runs as the blocked pass:
 // values from LDS windows, exact fixed-point accumulation (the same bits for any schedule; <= 1e-6 of the f32 chain while rows are short).
-// values must be non-negative, every per-vertex sum at most `bound`.  Pre / post vertex operators are honoured around it.
+// values must be non-negative and finite (-0.0 is a zero), every per-vertex sum at most `bound`; the sum is the exact one, rounded to f32 once.
+// The contract is enforced (vgl_hip_sum_over_edges_f32 in vgl_hip.h): a negative or non-finite value, a value or a sum at or above the capacity
+// (the power of two that is at least twice the bound) contributes nothing / is unspecified and makes scatter() throw -- where scatter() waits
+// for the device anyway (sync_after_primitive()); a caller that runs asynchronously asks vgl_hip_sum_over_edges_check when it next waits.  A sum
+// that wrapped past 2^64 units (four times the capacity) cannot be detected.  Pre / post vertex operators are honoured around it.
 struct vgl_declared_sum { float *sums; const float *values; float bound; };
 inline vgl_declared_sum VGL_SUM_OVER_EDGES(VerticesArray<float> &sums, VerticesArray<float> &values, float bound = 1.0f)
 { return vgl_declared_sum{sums.get_ptr(), values.get_ptr(), bound}; }
@@ -1183,7 +1187,15 @@ public:
         if (!is_empty_vertex_op<PreOp>()) vertex_pass(g, f, SCATTER, pre_op);
         VGL_HIP_CALL(vgl_hip_sum_over_edges_f32(VGL_RUNTIME::ctx(), g.get_handle(), op.values, op.bound, op.sums));
         if (!is_empty_vertex_op<PostOp>()) vertex_pass(g, f, SCATTER, post_op);
-        if (sync_after_primitive()) VGL_RUNTIME::sync();
+        if (sync_after_primitive()) {
+            VGL_RUNTIME::sync();
+            unsigned broken = 0;                // only where the call waits anyway: an asynchronous scatter stays asynchronous
+            VGL_HIP_CALL(vgl_hip_sum_over_edges_check(VGL_RUNTIME::ctx(), &broken));
+            if (broken & VGL_HIP_SUM_NEGATIVE) throw "VGL ERROR: VGL_SUM_OVER_EDGES: negative value";
+            if (broken & VGL_HIP_SUM_NOT_FINITE) throw "VGL ERROR: VGL_SUM_OVER_EDGES: value not finite";
+            if (broken & VGL_HIP_SUM_VALUE_TOO_LARGE) throw "VGL ERROR: VGL_SUM_OVER_EDGES: value at or above the capacity (raise the bound)";
+            if (broken & VGL_HIP_SUM_TOTAL_TOO_LARGE) throw "VGL ERROR: VGL_SUM_OVER_EDGES: sum at or above the capacity (raise the bound)";
+        }
         advance_stats(watch, g.get_direction_view(SCATTER).edges, false);
     }
     void scatter(VGL_Graph &g, VGL_Frontier &f, vgl_declared_sum op) { scatter(g, f, op, EMPTY_VERTEX_OP, EMPTY_VERTEX_OP); }
