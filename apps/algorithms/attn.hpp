@@ -5,6 +5,8 @@
 //   softmax    w = softmax over each row of s;             backward: ge = w (t - sum w t), t a given entry gradient
 //   attention  e = q . k, w = softmax(e), out = sum w v;   backward of out's gradient g: gw = g . v, gv, ge, gq, gk
 // q holds the scale F^-1/2 already (the C interface has no scaling call; in Python it is a torch product).
+// With -heads H every stage runs its heads form (the vgl_hip_agg_*_heads calls): head h owns the columns [h D, (h + 1) D), D = F / H, the entry
+// scalars are E x H, q holds D^-1/2, and the restatement runs per head with D in place of F in the bound of the dot.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -14,7 +16,11 @@
 
 struct GraphAttention {
     enum { DOT = 0, SOFTMAX = 1, ATTENTION = 2 };
-    struct Options { int features = 64, stage = ATTENTION; bool outgoing = false, backward = false; };
+    struct Options {
+        int features = 64, stage = ATTENTION, heads = 1;
+        bool outgoing = false, backward = false, use_heads = false;    // use_heads: -heads was given, the heads calls run (also with H = 1)
+        size_t H() const { return use_heads ? (size_t)heads : 1; }
+    };
     // the largest error of the device expf in ulps, measured (tests/studies/expf_ulps.hip), plus one
     static constexpr double EXP_ULPS = 1.857;
 
@@ -23,7 +29,7 @@ struct GraphAttention {
     struct Inputs {
         void *q = nullptr, *k = nullptr, *v = nullptr, *g = nullptr, *s = nullptr, *t = nullptr;
         std::vector<float> hq, hk, hv, hg, hs, ht;
-        size_t V = 0, E = 0, F = 0;
+        size_t V = 0, E = 0, F = 0, H = 1;
         void make(void **d, std::vector<float> &h, size_t n, unsigned long long seed, float scale)
         {
             vgl_hip_ctx *c = VGL_RUNTIME::ctx();
@@ -35,14 +41,14 @@ struct GraphAttention {
             for (float &x : h) x = (x / 100.0f - 0.5f) * scale;
             VGL_HIP_CALL(vgl_hip_memcpy_h2d(c, *d, h.data(), sizeof(float) * n));
         }
-        Inputs(VGL_Graph &graph, const vgl_csr_view &view, const Options &o, unsigned long long seed) : V((size_t)graph.get_vertices_count()), E((size_t)view.edges), F((size_t)o.features)
+        Inputs(VGL_Graph &graph, const vgl_csr_view &view, const Options &o, unsigned long long seed) : V((size_t)graph.get_vertices_count()), E((size_t)view.edges), F((size_t)o.features), H(o.H())
         {
-            make(&q, hq, V * F, seed, 1.0f / std::sqrt((float)F));
+            make(&q, hq, V * F, seed, 1.0f / std::sqrt((float)(F / H)));
             make(&k, hk, V * F, seed + 1, 1.0f);
             make(&v, hv, V * F, seed + 2, 1.0f);
             make(&g, hg, V * F, seed + 3, 1.0f);
-            make(&s, hs, E, seed + 4, 16.0f);
-            make(&t, ht, E, seed + 5, 16.0f);
+            make(&s, hs, E * H, seed + 4, 16.0f);
+            make(&t, ht, E * H, seed + 5, 16.0f);
             VGL_HIP_CALL(vgl_hip_ctx_sync(VGL_RUNTIME::ctx()));
         }
         ~Inputs()
@@ -71,7 +77,7 @@ struct GraphAttention {
     {
         std::cout << "ATTN " << what << ": rows " << s.rows << ", entries " << s.entries << ", rows short / wave / wg " << s.rows_short << " / " << s.rows_wave << " / " << s.rows_wg
                   << ", chunks " << s.chunks << ", hub rows " << s.hub_rows << ", column tiles " << s.column_tiles[0] << " / " << s.column_tiles[1] << " / " << s.column_tiles[2]
-                  << ", vec " << s.vec << ", transposed " << s.transposed << ", " << s.algorithmic_bytes << " bytes of the model, " << seconds * 1000.0 << " ms, "
+                  << ", vec " << s.vec << ", transposed " << s.transposed << (s.heads > 0 ? ", heads " + std::to_string(s.heads) : std::string()) << ", " << s.algorithmic_bytes << " bytes of the model, " << seconds * 1000.0 << " ms, "
                   << s.algorithmic_bytes / (seconds * 1e9) << " GB/s" << std::endl;
     }
 
@@ -80,10 +86,11 @@ struct GraphAttention {
     static double hip_fused(const vgl_csr_view &view, const Inputs &in, const Options &o, Result &r, bool launches = false)
     {
         vgl_hip_ctx *c = VGL_RUNTIME::ctx();
-        const size_t V = in.V, E = in.E, F = in.F;
+        const size_t V = in.V, E = in.E, F = in.F, H = in.H;
         const int64_t ld = (int64_t)F;
-        const int32_t f = (int32_t)F;
-        DeviceArray e(E), w(E), out(V * F), gw(E), ge(E), gq(V * F), gk(V * F), gv(V * F);
+        const int32_t f = (int32_t)F, hd = (int32_t)H;
+        const bool heads = o.use_heads;
+        DeviceArray e(E * H), w(E * H), out(V * F), gw(E * H), ge(E * H), gq(V * F), gk(V * F), gv(V * F);
         vgl_hip_agg_plan *plan = nullptr;
         Timer prep;
         prep.start();
@@ -107,11 +114,23 @@ struct GraphAttention {
             calls++;
             if (!launches) print_stats(what, st, tm.get_time());
         };
-        auto dot = [&](const float *a, const float *b, float *to) { return vgl_hip_agg_sddmm(c, plan, a, ld, b, ld, f, 0, to, &st); };
-        auto softmax = [&](const float *from, float *to) { return vgl_hip_agg_edge_softmax(c, plan, from, to, &st); };
-        auto softmax_back = [&](const float *y, const float *gy, float *to) { return vgl_hip_agg_edge_softmax_backward(c, plan, y, gy, to, &st); };
-        auto sum = [&](const float *weight, const float *x, float *to) { return vgl_hip_agg_run(c, plan, VGL_HIP_AGG_SUM, weight, x, ld, f, to, ld, nullptr, &st); };
-        auto sum_t = [&](const float *weight, const float *grad, float *to) { return vgl_hip_agg_run_transposed(c, plan, VGL_HIP_AGG_SUM, weight, nullptr, grad, ld, f, to, ld, &st); };
+        auto dot = [&](const float *a, const float *b, float *to) {
+            return heads ? vgl_hip_agg_sddmm_heads(c, plan, a, ld, b, ld, f, hd, 0, to, &st) : vgl_hip_agg_sddmm(c, plan, a, ld, b, ld, f, 0, to, &st);
+        };
+        auto softmax = [&](const float *from, float *to) {
+            return heads ? vgl_hip_agg_edge_softmax_heads(c, plan, from, hd, to, &st) : vgl_hip_agg_edge_softmax(c, plan, from, to, &st);
+        };
+        auto softmax_back = [&](const float *y, const float *gy, float *to) {
+            return heads ? vgl_hip_agg_edge_softmax_backward_heads(c, plan, y, gy, hd, to, &st) : vgl_hip_agg_edge_softmax_backward(c, plan, y, gy, to, &st);
+        };
+        auto sum = [&](const float *weight, const float *x, float *to) {
+            return heads ? vgl_hip_agg_run_heads(c, plan, VGL_HIP_AGG_SUM, weight, hd, x, ld, f, to, ld, &st)
+                         : vgl_hip_agg_run(c, plan, VGL_HIP_AGG_SUM, weight, x, ld, f, to, ld, nullptr, &st);
+        };
+        auto sum_t = [&](const float *weight, const float *grad, float *to) {
+            return heads ? vgl_hip_agg_run_transposed_heads(c, plan, VGL_HIP_AGG_SUM, weight, hd, grad, ld, f, to, ld, &st)
+                         : vgl_hip_agg_run_transposed(c, plan, VGL_HIP_AGG_SUM, weight, nullptr, grad, ld, f, to, ld, &st);
+        };
         const float *q = (const float *)in.q, *k = (const float *)in.k, *v = (const float *)in.v, *g = (const float *)in.g, *s = (const float *)in.s, *t = (const float *)in.t;
         if (o.stage == DOT) {
             run("dot", false, [&] { return dot(q, k, e.f()); });
@@ -182,49 +201,59 @@ struct GraphAttention {
             if (!(err <= bound) && errors++ < 10) std::cout << "error in " << what << " at " << at << ": " << got << " vs " << want << " (bound " << bound << ")" << std::endl;
         }
     };
-    static void check_dot(Judge &judge, const char *what, const HostCSR &h, size_t F, const std::vector<float> &a, const std::vector<float> &b, const std::vector<float> &e)
+    // H heads: e is E x H, head hd owns the D = F / H columns from hd D on (H = 1: the single-head stage)
+    static void check_dot(Judge &judge, const char *what, const HostCSR &h, size_t F, size_t H, const std::vector<float> &a, const std::vector<float> &b, const std::vector<float> &e)
     {
+        const size_t D = F / H;
         for (size_t i = 0; i < (size_t)h.V; i++)
-            for (long long p = h.rowptr[i]; p < h.rowptr[i + 1]; p++) {
-                double acc = 0.0, mag = 0.0;
-                const float *x = a.data() + i * F, *y = b.data() + (size_t)h.adj[(size_t)p] * F;
-                for (size_t f = 0; f < F; f++) { acc += (double)x[f] * y[f]; mag += std::fabs((double)x[f] * y[f]); }
-                judge(what, (size_t)p, e[(size_t)p], acc, tolerance((double)F + 2) * mag);       // F products, F - 1 additions (and the division of mean)
-            }
+            for (long long p = h.rowptr[i]; p < h.rowptr[i + 1]; p++)
+                for (size_t hd = 0; hd < H; hd++) {
+                    double acc = 0.0, mag = 0.0;
+                    const float *x = a.data() + i * F + hd * D, *y = b.data() + (size_t)h.adj[(size_t)p] * F + hd * D;
+                    for (size_t f = 0; f < D; f++) { acc += (double)x[f] * y[f]; mag += std::fabs((double)x[f] * y[f]); }
+                    judge(what, (size_t)p * H + hd, e[(size_t)p * H + hd], acc, tolerance((double)D + 2) * mag);   // D products, D - 1 additions (and the division of mean)
+                }
     }
-    static void check_softmax(Judge &judge, const HostCSR &h, const std::vector<float> &e, const std::vector<float> &w)
+    static void check_softmax(Judge &judge, const HostCSR &h, size_t H, const std::vector<float> &e, const std::vector<float> &w)
     {
         const double u = std::ldexp(1.0, -24), eps = EXP_ULPS * std::ldexp(1.0, -23), tiny = std::ldexp(1.0, -126);
-        for (size_t i = 0; i < (size_t)h.V; i++) {
-            const long long lo = h.rowptr[i], hi = h.rowptr[i + 1];
-            double m = -INFINITY, s = 0.0, R = 0.0;
-            for (long long p = lo; p < hi; p++) m = std::max(m, (double)e[(size_t)p]);
-            for (long long p = lo; p < hi; p++)
-                if (e[(size_t)p] > -INFINITY) { s += std::exp((double)e[(size_t)p] - m); R = std::max(R, m - (double)e[(size_t)p]); }
-            // 3 (R u + eps_exp) + gamma_(d + 3), relative to the exact value, plus 2^-126
-            const double rel = 3.0 * (R * u + eps) + tolerance((double)(hi - lo) + 3) + 3.0 * (R + 2.0) * std::ldexp(1.0, -53);
-            for (long long p = lo; p < hi; p++) {
-                const double want = e[(size_t)p] > -INFINITY ? std::exp((double)e[(size_t)p] - m) / s : 0.0;
-                judge("softmax", (size_t)p, w[(size_t)p], want, rel * want + tiny);
+        for (size_t i = 0; i < (size_t)h.V; i++)
+            for (size_t hd = 0; hd < H; hd++) {
+                const long long lo = h.rowptr[i], hi = h.rowptr[i + 1];
+                double m = -INFINITY, s = 0.0, R = 0.0;
+                for (long long p = lo; p < hi; p++) m = std::max(m, (double)e[(size_t)p * H + hd]);
+                for (long long p = lo; p < hi; p++)
+                    if (e[(size_t)p * H + hd] > -INFINITY) { s += std::exp((double)e[(size_t)p * H + hd] - m); R = std::max(R, m - (double)e[(size_t)p * H + hd]); }
+                // 3 (R u + eps_exp) + gamma_(d + 3), relative to the exact value, plus 2^-126
+                const double rel = 3.0 * (R * u + eps) + tolerance((double)(hi - lo) + 3) + 3.0 * (R + 2.0) * std::ldexp(1.0, -53);
+                for (long long p = lo; p < hi; p++) {
+                    const double want = e[(size_t)p * H + hd] > -INFINITY ? std::exp((double)e[(size_t)p * H + hd] - m) / s : 0.0;
+                    judge("softmax", (size_t)p * H + hd, w[(size_t)p * H + hd], want, rel * want + tiny);
+                }
             }
-        }
     }
-    static void check_softmax_backward(Judge &judge, const HostCSR &h, const std::vector<float> &y, const std::vector<float> &gy, const std::vector<float> &ge)
+    static void check_softmax_backward(Judge &judge, const HostCSR &h, size_t H, const std::vector<float> &y, const std::vector<float> &gy, const std::vector<float> &ge)
     {
-        for (size_t i = 0; i < (size_t)h.V; i++) {
-            const long long lo = h.rowptr[i], hi = h.rowptr[i + 1];
-            double d = 0.0, mag = 0.0;
-            for (long long p = lo; p < hi; p++) { d += (double)y[(size_t)p] * gy[(size_t)p]; mag += std::fabs((double)y[(size_t)p] * gy[(size_t)p]); }
-            for (long long p = lo; p < hi; p++)
-                judge("softmax backward", (size_t)p, ge[(size_t)p], (double)y[(size_t)p] * ((double)gy[(size_t)p] - d),
-                      tolerance((double)(hi - lo) + 3) * std::fabs((double)y[(size_t)p]) * (std::fabs((double)gy[(size_t)p]) + mag));
-        }
+        for (size_t i = 0; i < (size_t)h.V; i++)
+            for (size_t hd = 0; hd < H; hd++) {
+                const long long lo = h.rowptr[i], hi = h.rowptr[i + 1];
+                double d = 0.0, mag = 0.0;
+                for (long long p = lo; p < hi; p++) {
+                    const size_t at = (size_t)p * H + hd;
+                    d += (double)y[at] * gy[at]; mag += std::fabs((double)y[at] * gy[at]);
+                }
+                for (long long p = lo; p < hi; p++) {
+                    const size_t at = (size_t)p * H + hd;
+                    judge("softmax backward", at, ge[at], (double)y[at] * ((double)gy[at] - d), tolerance((double)(hi - lo) + 3) * std::fabs((double)y[at]) * (std::fabs((double)gy[at]) + mag));
+                }
+            }
     }
     // out[i] = sum_p weight_p x[adj p] (forward) or out[adj p] += weight_p x[i] (transposed), within gamma_(d + 2) of the sum of magnitudes
-    static void check_sum(Judge &judge, const char *what, const HostCSR &h, size_t F, bool transposed, const std::vector<float> &weight, const std::vector<float> &x,
+    // (weight is E x H: column f / D weighs column f)
+    static void check_sum(Judge &judge, const char *what, const HostCSR &h, size_t F, size_t H, bool transposed, const std::vector<float> &weight, const std::vector<float> &x,
                           const std::vector<float> &out)
     {
-        const size_t V = (size_t)h.V;
+        const size_t V = (size_t)h.V, D = F / H;
         std::vector<double> acc(V * F, 0.0), mag(V * F, 0.0);
         std::vector<long long> terms(V, 0);
         for (size_t i = 0; i < V; i++)
@@ -232,7 +261,7 @@ struct GraphAttention {
                 const size_t u = (size_t)h.adj[(size_t)p], to = transposed ? u : i, from = transposed ? i : u;
                 terms[to]++;
                 for (size_t f = 0; f < F; f++) {
-                    const double t = (double)weight[(size_t)p] * x[from * F + f];
+                    const double t = (double)weight[(size_t)p * H + f / D] * x[from * F + f];
                     acc[to * F + f] += t; mag[to * F + f] += std::fabs(t);
                 }
             }
@@ -245,26 +274,26 @@ struct GraphAttention {
         Judge judge;
         Timer host;
         host.start();
-        const size_t F = in.F;
+        const size_t F = in.F, H = in.H;
         if (o.stage == DOT) {
-            check_dot(judge, "dot", h, F, in.hq, in.hk, r.e);
+            check_dot(judge, "dot", h, F, H, in.hq, in.hk, r.e);
             if (o.backward) {
-                check_sum(judge, "grad q", h, F, false, in.hs, in.hk, r.gq);
-                check_sum(judge, "grad k", h, F, true, in.hs, in.hq, r.gk);
+                check_sum(judge, "grad q", h, F, H, false, in.hs, in.hk, r.gq);
+                check_sum(judge, "grad k", h, F, H, true, in.hs, in.hq, r.gk);
             }
         } else if (o.stage == SOFTMAX) {
-            check_softmax(judge, h, in.hs, r.w);
-            if (o.backward) check_softmax_backward(judge, h, r.w, in.ht, r.ge);
+            check_softmax(judge, h, H, in.hs, r.w);
+            if (o.backward) check_softmax_backward(judge, h, H, r.w, in.ht, r.ge);
         } else {
-            check_dot(judge, "dot", h, F, in.hq, in.hk, r.e);
-            check_softmax(judge, h, r.e, r.w);
-            check_sum(judge, "out", h, F, false, r.w, in.hv, r.out);
+            check_dot(judge, "dot", h, F, H, in.hq, in.hk, r.e);
+            check_softmax(judge, h, H, r.e, r.w);
+            check_sum(judge, "out", h, F, H, false, r.w, in.hv, r.out);
             if (o.backward) {
-                check_dot(judge, "grad weights", h, F, in.hg, in.hv, r.gw);
-                check_sum(judge, "grad v", h, F, true, r.w, in.hg, r.gv);
-                check_softmax_backward(judge, h, r.w, r.gw, r.ge);
-                check_sum(judge, "grad q", h, F, false, r.ge, in.hk, r.gq);
-                check_sum(judge, "grad k", h, F, true, r.ge, in.hq, r.gk);
+                check_dot(judge, "grad weights", h, F, H, in.hg, in.hv, r.gw);
+                check_sum(judge, "grad v", h, F, H, true, r.w, in.hg, r.gv);
+                check_softmax_backward(judge, h, H, r.w, r.gw, r.ge);
+                check_sum(judge, "grad q", h, F, H, false, r.ge, in.hk, r.gq);
+                check_sum(judge, "grad k", h, F, H, true, r.ge, in.hq, r.gk);
             }
         }
         host.end();

@@ -1,6 +1,8 @@
 // attn app: edge scores, edge softmax and dot-product graph attention of V x F float32 features over a stored direction of the graph; plan, every
 // call of the stage once to heat and once timed.
 //   -features F      columns (default 64)
+//   -heads H         H heads in one walk: the heads form of every call, head h on the columns [h F / H, (h + 1) F / H); H must divide F (default: the
+//                    single-head calls)
 //   -stage NAME      dot | softmax | attention (default attention: dot, softmax, weighted sum)
 //   -out             over the outgoing entries (default: the incoming direction)
 //   -backward        also the gradients of the stage; the transpose build is timed apart
@@ -19,10 +21,11 @@ int main(int argc, char **argv)
         std::vector<char *> rest{argv[0]};
         for (int i = 1; i < argc; i++) {
             const std::string a = argv[i];
-            if (a == "-features" || a == "-stage") {
+            if (a == "-features" || a == "-stage" || a == "-heads") {
                 if (i + 1 >= argc) throw "missing value for command line option";
                 const std::string v = argv[++i];
                 if (a == "-features") opt.features = atoi(v.c_str());
+                else if (a == "-heads") { opt.heads = atoi(v.c_str()); opt.use_heads = true; }
                 else if (v == "dot") opt.stage = ATTN::DOT;
                 else if (v == "softmax") opt.stage = ATTN::SOFTMAX;
                 else if (v == "attention") opt.stage = ATTN::ATTENTION;
@@ -32,6 +35,8 @@ int main(int argc, char **argv)
             else rest.push_back(argv[i]);
         }
         if (opt.features < 1) throw "attn: -features must be at least 1";
+        if (opt.heads < 1) throw "attn: -heads must be at least 1";
+        if (opt.features % opt.heads != 0) throw "attn: -heads must divide -features";
         Parser parser;
         parser.parse_args((int)rest.size(), rest.data());
         if (!parser.fused) throw "attn: only the fused path exists (pass -fused)";

@@ -1303,7 +1303,7 @@ typedef struct {
     int32_t column_tiles[3];    /* walks per row of the short, wave and workgroup class */
     int32_t vec;                /* 4: 16-byte loads and stores; 1: scalar */
     int32_t transposed;         /* the run walked the transpose (plan_info: it exists) */
-    int32_t reserved;
+    int32_t heads;              /* H of the _heads calls (below); 0 from every other call */
 } vgl_hip_agg_stats;
 int vgl_hip_agg_plan_create(vgl_hip_ctx *ctx, const int64_t *d_rowptr, const int32_t *d_adj, int32_t n_rows, int32_t n_cols, vgl_hip_agg_plan **out);
 int vgl_hip_agg_plan_info(vgl_hip_agg_plan *plan, vgl_hip_agg_stats *stats);
@@ -1354,14 +1354,59 @@ int vgl_hip_agg_run_transposed(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op,
  *   backward entries x (8 x 2 walks of y and gy + 4 written) + rows x 8 + the list entries; the same remarks.
  * Fails, before anything is written: a NULL argument (stats may be NULL), a plan of another context, F < 1, a leading dimension below F, mean outside
  * {0, 1}.  Threads: as above.
- * Not here: heads (call per column slice: one adjacency walk per head); the u_add_v score of the original GAT (s[row] + t[adj], two gathers in any
- * tensor library); a fused attention that never materialises the E scalars (they are 12 bytes per entry against 8 F); a softmax grouped by column;
- * float16 / bfloat16. */
+ * Not here: the u_add_v score of the original GAT (s[row] + t[adj], two gathers in any tensor library); a fused attention that never materialises
+ * the E scalars (they are 12 bytes per entry against 8 F); a softmax grouped by column; float16 / bfloat16.  Heads are the _heads calls below. */
 int vgl_hip_agg_sddmm(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int mean,
                       float *d_e, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_edge_softmax(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_e, float *d_y, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_edge_softmax_backward(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_y, const float *d_gy, float *d_ge,
                                       vgl_hip_agg_stats *stats);
+
+/* Heads (`heads`): the five calls above with H heads in one walk.  F is the total width, F % H == 0, D = F / H; head h owns the
+ * columns [h D, (h + 1) D) of every feature matrix.  The edge scalars are ONE float32 per (entry, head), E x H row-major and contiguous:
+ * e[p * H + h], p the entry's position in CSR order; they have no leading dimension.  For every head h, entry p and column f with f / D == h:
+ *   sddmm     vgl_hip_agg_sddmm_heads: e[p, h] = the sum over the columns f of head h of a[row(p), f] * b[adj[p], f]; with mean = 1 divided once by
+ *             (float) len(row(p)).
+ *   softmax   vgl_hip_agg_edge_softmax_heads / _backward_heads: the formulas, the -inf rules, the empty rows, the one division per entry and the
+ *             overlap conditions of the calls above, per (row, head) on column h of e.
+ *   forward   vgl_hip_agg_run_heads: out[i, f] = the sum over the entries p of row i of w[p, h] * x[adj[p], f]; MEAN divides once by the row's length.
+ *   backward  vgl_hip_agg_run_transposed_heads: gx[u, f] = the sum over the transposed row of u, in its order, of coef * g[row(p), f], coef = w[p, h]
+ *             for SUM and w[p, h] / (float) len(row(p)) for MEAN (one division, then one product); the weight is read through the origin.
+ *   floating point: everything above stands.  VEC = 4 when D, every leading dimension and every base address are multiples of 4 elements / 16 bytes
+ *             (a 16-byte access then stays inside one head), else 1.  The dot product of (entry, head) has the shape vgl_hip_agg_sddmm gives at width
+ *             D on the column slice of the head: lanes per tile and tiles from (D, VEC), the butterfly over the lanes of that head only, so e[:, h]
+ *             equals vgl_hip_agg_sddmm on a[:, h D : (h + 1) D], b[:, h D : (h + 1) D] BIT FOR BIT.  Every row sum of the softmax and of its backward
+ *             has the shape above per head, one thread per (hub row, head) merges the chunks in chunk order: y[:, h] equals the call above on a
+ *             contiguous copy of e[:, h] BIT FOR BIT.  The two runs keep the sum of the width-F call (slots and tiles from (F, VEC)); only the
+ *             coefficient depends on the lane's head: with H equal weight columns and the same VEC they return the bits of vgl_hip_agg_run /
+ *             _run_transposed with that column as the weight.  With H = 1 every call returns the bits of its counterpart above.
+ *   tolerance the ones above with D in place of F for the dot: gamma_(D + 2) * the sum of |a b|; the softmax bounds unchanged; the runs
+ *             gamma_(d + 2) * the sum of |w v|.
+ * Method: vgl_k_edge_dot_heads<CLS, VEC>: the lanes of an entry slot are (head of the pass x column group of the head); NQ_D lanes per head from
+ * (D, VEC), as many heads beside each other as the class's lane budget holds (8 short, 64 otherwise; a power of two, no more than H needs), the
+ * remaining heads in further passes; adj[p] is read once per entry for all passes; the butterfly stops at NQ_D / 2 and the lane of column group 0
+ * stores e[p * H + h].  vgl_k_edge_rows_heads<CLS, BWD, HB>: every lane an entry slot that carries a block of HB heads (the largest of 8, 4, 2, 1
+ * that divides H) in registers and loads them as one 8- or 16-byte access when the arrays are 16-byte aligned, a loop over the blocks; the hub
+ * partial is a pair per (item, head), one thread per (hub row, head) merges.  vgl_k_agg_rows<..., HEADS>: the walk of vgl_hip_agg_run, the
+ * coefficient weight[o * H + c0 / D] with the head taken once per column tile.
+ * stats: as above, heads = H.  column_tiles: sddmm: passes x the tiles of a head per class; softmax: 1; the runs: those of (F, VEC).  vec: the VEC
+ * above; softmax: 4 where a lane's head block is read in 16-byte pieces, else 1.  algorithmic_bytes:
+ *   sddmm    per class entries x column_tiles x 4 (adjacency; REQUESTED as above: the kernel keeps adj[p] in a register, an upper bound)
+ *            + entries x 4 F (b gathered) + entries x 4 H (e written) + rows x (8 bounds + 4 F of a) + the list entries (4 per short or wave
+ *            row, 8 per chunk).
+ *   softmax  entries x H x (4 x 3 + 4) + rows x 8 + the list entries.   backward  entries x H x (8 x 2 + 4) + rows x 8 + the list entries.
+ *   runs     the formula of vgl_hip_agg_run / _run_transposed with 4 H of weights per entry and per walk in place of 4.
+ * Fails, before anything is written: what the calls above refuse; H < 1; F % H != 0; a NULL d_weight; an op other than SUM or MEAN in the runs.
+ * Not here: a leading dimension for the E x H arrays; the fused attention; the u_add_v score; float16 / bfloat16. */
+int vgl_hip_agg_sddmm_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int32_t H,
+                            int mean, float *d_e, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_edge_softmax_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_e, int32_t H, float *d_y, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_edge_softmax_backward_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_y, const float *d_gy, int32_t H, float *d_ge,
+                                            vgl_hip_agg_stats *stats);
+int vgl_hip_agg_run_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, int32_t H, const float *d_x, int64_t ldx, int32_t F,
+                          float *d_out, int64_t ldo, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_run_transposed_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, int32_t H, const float *d_g, int64_t ldg,
+                                     int32_t F, float *d_gx, int64_t ldgx, vgl_hip_agg_stats *stats);
 
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */

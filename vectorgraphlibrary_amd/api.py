@@ -1483,7 +1483,7 @@ AGG_OPS = {"sum": 0, "mean": 1, "max": 2, "min": 3}
 
 
 def _agg_stats(st):
-    d = {k: getattr(st, k) for k, _ in st._fields_ if k not in ("column_tiles", "reserved")}
+    d = {k: getattr(st, k) for k, _ in st._fields_ if k != "column_tiles"}
     d["column_tiles"] = list(st.column_tiles)
     return d
 
@@ -1613,6 +1613,67 @@ class AggregationPlan:
             return ge
         st = _l.AggStats()
         _l.check(self.ctx.L.vgl_hip_agg_edge_softmax_backward(self.ctx.h, self.h, _ptr(y), _ptr(gy), _ptr(ge), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return ge
+
+    # H heads in one walk (the vgl_hip_agg_*_heads calls): the edge scalars are E x H contiguous, head h owns F / H columns
+    def _forward_heads(self, x, op, weight, H):
+        ctx, F = self.ctx, int(x.shape[1])
+        out = torch.empty((self.n_rows, F), dtype=torch.float32, device=ctx.device)
+        if self.n_rows == 0 or F == 0:
+            return out
+        if self.n_cols == 0 or self.E == 0:
+            return out.zero_()
+        x, ldx = self._rows(x, "spmm: x")
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_run_heads(ctx.h, self.h, op, _ptr(weight), H, _ptr(x), ldx, F, _ptr(out), F, C.byref(st)))
+        self.last_stats = _agg_stats(st)
+        return out
+
+    def _backward_heads(self, g, op, weight, H):
+        ctx, F = self.ctx, int(g.shape[1])
+        gx = torch.empty((self.n_cols, F), dtype=torch.float32, device=ctx.device)
+        if self.n_cols == 0 or F == 0:
+            return gx
+        if self.n_rows == 0 or self.E == 0:
+            return gx.zero_()
+        g, ldg = self._rows(g, "spmm: grad")
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_run_transposed_heads(ctx.h, self.h, op, _ptr(weight), H, _ptr(g), ldg, F, _ptr(gx), F, C.byref(st)))
+        self.last_backward_stats = _agg_stats(st)
+        return gx
+
+    def _sddmm_heads(self, a, b, H, mean=0):
+        ctx, F = self.ctx, int(a.shape[1])
+        e = torch.empty((self.E, H), dtype=torch.float32, device=ctx.device)
+        if self.E == 0:
+            return e
+        if F == 0:
+            return e.zero_()
+        a, lda = self._rows(a, "sddmm: a")
+        b, ldb = self._rows(b, "sddmm: b")
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_sddmm_heads(ctx.h, self.h, _ptr(a), lda, _ptr(b), ldb, F, H, int(mean), _ptr(e), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return e
+
+    def _edge_softmax_heads(self, e):
+        H = int(e.shape[1])
+        y = torch.empty((self.E, H), dtype=torch.float32, device=self.ctx.device)
+        if self.E == 0 or H == 0:
+            return y
+        st = _l.AggStats()
+        _l.check(self.ctx.L.vgl_hip_agg_edge_softmax_heads(self.ctx.h, self.h, _ptr(e), H, _ptr(y), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return y
+
+    def _edge_softmax_backward_heads(self, y, gy):
+        H = int(y.shape[1])
+        ge = torch.empty((self.E, H), dtype=torch.float32, device=self.ctx.device)
+        if self.E == 0 or H == 0:
+            return ge
+        st = _l.AggStats()
+        _l.check(self.ctx.L.vgl_hip_agg_edge_softmax_backward_heads(self.ctx.h, self.h, _ptr(y), _ptr(gy), H, _ptr(ge), C.byref(st)))
         self.last_edge_stats = _agg_stats(st)
         return ge
 
@@ -1750,47 +1811,148 @@ class _Spmm(torch.autograd.Function):
         return gw, gx, None, None
 
 
-def sddmm(plan, a, b):
+# ---- heads: E x H scalars, head h owns F / H columns (the vgl_hip_agg_*_heads calls in include/vgl_hip.h) ----
+def _edge_heads(who, heads):
+    if isinstance(heads, bool) or not isinstance(heads, int) or heads < 1:
+        raise _l.VglHipError("%s: heads must be an int of at least 1, got %r" % (who, heads))
+    return heads
+
+
+def _edge_scalars_heads(who, name, plan, t):
+    """(E,) or (E, H) float32 on the plan's device -> H, or None for (E,)"""
+    if torch.is_tensor(t) and t.dim() == 2:
+        if t.dtype != torch.float32:
+            raise _l.VglHipError("%s: %s must be a float32 tensor, got %s" % (who, name, t.dtype))
+        if int(t.shape[0]) != plan.E or int(t.shape[1]) < 1 or t.device != plan.ctx.device:
+            raise _l.VglHipError("%s: %s must hold one value per entry (%d), or per entry and head (%d x H, H >= 1), on the plan's device" % (who, name, plan.E, plan.E))
+        return int(t.shape[1])
+    _edge_scalars(who, name, plan, t)
+    return None
+
+
+class _SddmmHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, a, b, plan, H):
+        fctx.plan, fctx.H = plan, H
+        fctx.save_for_backward(a, b)
+        return plan._sddmm_heads(a.detach(), b.detach(), H, 0)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, ge):
+        a, b = fctx.saved_tensors
+        ge = ge.contiguous()
+        # the two heads runs with the E x H entry gradient as the weight
+        ga = fctx.plan._forward_heads(b, AGG_OPS["sum"], ge, fctx.H) if fctx.needs_input_grad[0] else None
+        gb = fctx.plan._backward_heads(a, AGG_OPS["sum"], ge, fctx.H) if fctx.needs_input_grad[1] else None
+        return ga, gb, None, None
+
+
+class _EdgeSoftmaxHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, e, plan):
+        y = plan._edge_softmax_heads(e.detach().contiguous())
+        fctx.plan = plan
+        fctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gy):
+        (y,) = fctx.saved_tensors
+        return fctx.plan._edge_softmax_backward_heads(y, gy.contiguous()), None
+
+
+class _SpmmHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, weight, x, plan, op):
+        fctx.plan, fctx.op, fctx.H = plan, op, int(weight.shape[1])
+        fctx.save_for_backward(weight, x)
+        return plan._forward_heads(x.detach(), op, weight.detach(), fctx.H)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g):
+        weight, x = fctx.saved_tensors
+        g = g.contiguous()
+        gw = fctx.plan._sddmm_heads(g, x, fctx.H, 1 if fctx.op == AGG_OPS["mean"] else 0) if fctx.needs_input_grad[0] else None
+        gx = fctx.plan._backward_heads(g, fctx.op, weight, fctx.H) if fctx.needs_input_grad[1] else None
+        return gw, gx, None, None
+
+
+def sddmm(plan, a, b, heads=None):
     """e[p] = the dot product of a[row(p), :] and b[adj[p], :] for every stored entry p of the plan, in CSR order (a: n_rows x F, b: n_cols x F, float32
-    on the plan's device) -> E float32.  Differentiable in a and b, first order: the backward is aggregate's forward kernel (grad a) and its transposed
-    kernel (grad b) with the entry gradient as the weight, without atomics, the same bits on every run.  Column slices and offset views go with their
+    on the plan's device) -> E float32.  With heads=H (an int that divides F) head h owns the columns [h F / H, (h + 1) F / H) and the result is
+    E x H: e[p, h] = the dot product over the columns of head h, every head in one walk of the plan, each column with the bits of the call on the
+    head's column slice.  Differentiable in a and b, first order: the backward is aggregate's forward kernel (grad a) and its transposed kernel
+    (grad b) with the entry gradient as the weight, without atomics, the same bits on every run.  Column slices and offset views go with their
     leading dimension.  One call at a time per context."""
     _edge_plan("sddmm", plan)
     _edge_features("sddmm", "a", plan, a, plan.n_rows, "n_rows")
     _edge_features("sddmm", "b", plan, b, plan.n_cols, "n_cols")
     if int(a.shape[1]) != int(b.shape[1]):
         raise _l.VglHipError("sddmm: a and b must have the same width F, got %d and %d" % (int(a.shape[1]), int(b.shape[1])))
-    return _Sddmm.apply(a, b, plan)
+    if heads is None:
+        return _Sddmm.apply(a, b, plan)
+    H = _edge_heads("sddmm", heads)
+    if int(a.shape[1]) % H != 0:
+        raise _l.VglHipError("sddmm: the width F = %d must be divisible by heads = %d" % (int(a.shape[1]), H))
+    return _SddmmHeads.apply(a, b, plan, H)
 
 
 def edge_softmax(plan, e):
     """y[p] = exp(e[p] - m) / s over the entries of each row of the plan (m the row's largest score, s the sum; one division per entry) -> E float32.
+    e may also be E x H (one column per head, H >= 2; E x 1 is refused as it always was: one head is (E,)): the softmax of every (row, head), each
+    column with the bits of the call on that column -> E x H.
     An entry at -inf gets 0, a row of -inf alone 0 everywhere; with NaN or +inf the result is unspecified.  Differentiable, first order:
     ge[p] = y[p] * (gy[p] - sum_q y[q] gy[q])."""
     _edge_plan("edge_softmax", plan)
-    _edge_scalars("edge_softmax", "e", plan, e)
-    return _EdgeSoftmax.apply(e, plan)
+    if torch.is_tensor(e) and e.dim() == 2 and int(e.shape[1]) == 1:
+        # E x 1 stays refused, as it was before heads existed: one head is (E,); graph_attention(heads=1) keeps its E x 1 scores to itself
+        _edge_scalars("edge_softmax", "e", plan, e)
+    return _edge_softmax_any(plan, e)
+
+
+def _edge_softmax_any(plan, e):
+    if _edge_scalars_heads("edge_softmax", "e", plan, e) is None:
+        return _EdgeSoftmax.apply(e, plan)
+    return _EdgeSoftmaxHeads.apply(e, plan)
 
 
 def spmm(plan, weight, x, op="sum"):
     """aggregate(plan, x, op, weight) for op "sum" or "mean", differentiable in BOTH weight (one float32 per entry) and x (n_cols x F): grad x is the
-    transposed run, grad weight[p] = the dot product of grad_out[row(p), :] and x[adj[p], :] (divided by the row's length for "mean"), first order."""
+    transposed run, grad weight[p] = the dot product of grad_out[row(p), :] and x[adj[p], :] (divided by the row's length for "mean"), first order.
+    weight may also be E x H with F divisible by H: column h weighs the columns [h F / H, (h + 1) F / H) of x, and grad weight is E x H."""
     _edge_plan("spmm", plan)
     if op not in ("sum", "mean"):
         raise _l.VglHipError("spmm: op must be 'sum' or 'mean', got %r" % (op,))
-    _edge_scalars("spmm", "weight", plan, weight)
+    H = _edge_scalars_heads("spmm", "weight", plan, weight)
     _edge_features("spmm", "x", plan, x, plan.n_cols, "n_cols")
-    return _Spmm.apply(weight.contiguous(), x, plan, AGG_OPS[op])
+    if H is None:
+        return _Spmm.apply(weight.contiguous(), x, plan, AGG_OPS[op])
+    if int(x.shape[1]) % H != 0:
+        raise _l.VglHipError("spmm: the width F = %d of x must be divisible by the heads of weight (%d)" % (int(x.shape[1]), H))
+    return _SpmmHeads.apply(weight.contiguous(), x, plan, AGG_OPS[op])
 
 
-def graph_attention(plan, q, k, v, scale=None, return_weights=False):
+def graph_attention(plan, q, k, v, scale=None, return_weights=False, heads=None):
     """out[i, :] = sum over the entries p of row i of softmax_row(scale * q[i] . k[adj[p]])[p] * v[adj[p], :]: dot-product attention of every row over
     its stored entries (q: n_rows x F, k: n_cols x F, v: n_cols x Fv; scale F ** -0.5 unless given).  It IS spmm(plan, edge_softmax(plan, sddmm(plan,
-    q, k) * scale), v) and nothing else, so it is differentiable in q, k and v.  One head: call per column slice for more.  With return_weights=True
-    also the E attention weights."""
-    e = sddmm(plan, q, k)
-    if scale is None:
-        scale = float(q.shape[1]) ** -0.5 if int(q.shape[1]) > 0 else 1.0
-    w = edge_softmax(plan, e * scale)
+    q, k) * scale), v) and nothing else, so it is differentiable in q, k and v.  With heads=H (H divides F and Fv) every head attends on its own
+    columns in the same three calls: spmm(plan, edge_softmax(plan, sddmm(plan, q, k, heads=H) * scale), v) with scale (F / H) ** -0.5 unless given,
+    head h of out in the columns [h Fv / H, (h + 1) Fv / H).  With return_weights=True also the attention weights: E, with heads E x H."""
+    if heads is None:
+        e = sddmm(plan, q, k)
+        if scale is None:
+            scale = float(q.shape[1]) ** -0.5 if int(q.shape[1]) > 0 else 1.0
+    else:
+        H = _edge_heads("graph_attention", heads)
+        _edge_features("graph_attention", "v", plan, v, plan.n_cols, "n_cols")
+        if int(v.shape[1]) % H != 0:
+            raise _l.VglHipError("graph_attention: the width %d of v must be divisible by heads = %d" % (int(v.shape[1]), H))
+        e = sddmm(plan, q, k, heads=H)
+        if scale is None:
+            scale = float(int(q.shape[1]) // H) ** -0.5 if int(q.shape[1]) > 0 else 1.0
+    w = edge_softmax(plan, e * scale) if heads is None else _edge_softmax_any(plan, e * scale)
     out = spmm(plan, w, v)
     return (out, w) if return_weights else out

@@ -12,6 +12,8 @@
 //              in flight, then the slots of a column group are folded by an xor butterfly and, in a workgroup, the four waves from LDS in wave order.
 //              A wider F walks the row once per column tile.  Max / min carry (value, position) and prefer the smaller position on equal values.
 //   hubs       a row of more than one chunk leaves one partial per chunk; one writer per (row, column) finishes them in chunk order.
+//   heads      vgl_hip_agg_run_heads / _run_transposed_heads: E x H weights, head h weighs the columns [h D, (h + 1) D); the team kernel's HEADS
+//              instantiations differ in the coefficient alone, the hub kernel serves as it is.
 // Every value has one writer and every sum a shape fixed by (row length, F, VEC, the three switches): no floating-point atomic, no scratch memory, no
 // cooperative launch, no wait on a flag, no retry loop.
 #include "vgl_agg.h"
@@ -44,20 +46,23 @@ struct agg_args {
     int32_t F, chunk;
     int32_t lognq[VGL_RC_N];     // log2 of the lanes that cover a column tile, per class
     int32_t mean, neg;           // forward MEAN: divide by the row's length at the end; MIN: the extreme of -x
+    int32_t H, D;                // the heads form: weight is E x H, head h owns the columns [h D, (h + 1) D); else 0
 };
 
-// the source row, the coefficient and the origin of the term at position p of the walked CSR
-template <bool TR>
-__device__ __forceinline__ void agg_term(const agg_args &a, int64_t p, int32_t &u, float &cf, int32_t &o)
+// the source row, the coefficient and the origin of the term at position p of the walked CSR; the heads form reads the weight of head hd of the origin
+template <bool TR, bool HEADS>
+__device__ __forceinline__ void agg_term(const agg_args &a, int64_t p, int hd, int32_t &u, float &cf, int32_t &o)
 {
     u = a.adj[p];
     if constexpr (TR) {
         o = a.origin[p];
-        cf = a.weight ? a.weight[o] : 1.0f;
+        if constexpr (HEADS) cf = a.weight[(int64_t)o * a.H + hd];
+        else cf = a.weight ? a.weight[o] : 1.0f;
         if (a.len_rowptr) cf = cf / (float)(a.len_rowptr[u + 1] - a.len_rowptr[u]);
     } else {
         o = (int32_t)p;
-        cf = a.weight ? a.weight[p] : 1.0f;
+        if constexpr (HEADS) cf = a.weight[p * a.H + hd];
+        else cf = a.weight ? a.weight[p] : 1.0f;
     }
 }
 // the VEC values of the term at column c0; transposed MAX / MIN: 0 where the origin did not attain the extreme
@@ -77,11 +82,13 @@ __device__ __forceinline__ void agg_values(const agg_args &a, int32_t u, int32_t
 __device__ __forceinline__ bool agg_better(float v, int32_t p, float v2, int32_t p2) { return p2 >= 0 && (p < 0 || v2 > v || (v2 == v && p2 < p)); }
 
 // ---- rows: a team per row (short, wave) or per chunk (workgroup) ----
-template <int CLS, int OP, int VEC, bool TR>
+// HEADS: the same walk, slots and fold; the coefficient of a term is the weight of the lane's head, taken per column tile (the tile changes the head)
+template <int CLS, int OP, int VEC, bool TR, bool HEADS = false>
 __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_agg_rows(agg_list l, int32_t n, agg_args a)
 {
     using T = vgl_rc_team<CLS>;
     static_assert(!(TR && OP == AGG_K_EXT), "every backward is a sum");
+    static_assert(!(HEADS && OP == AGG_K_EXT), "heads weigh a sum");
     constexpr int FOLD = T::LANES < 64 ? T::LANES : 64;
     const int lognq = a.lognq[CLS], nq = 1 << lognq, slots = T::LANES >> lognq;
     const int q = T::lane() & (nq - 1), slot = T::lane() >> lognq;
@@ -106,6 +113,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_agg_rows(agg_list l, int32_t 
             const int c0 = base + q * VEC;
             const bool act = c0 < a.F;
             const int64_t end = act ? hi : lo;                          // a lane past the last column walks nothing
+            const int hd = HEADS && act ? c0 / a.D : 0;                 // one division per tile, none per term
             int64_t p = lo + slot;
             if constexpr (OP == AGG_K_SUM) {
                 float acc[VEC];
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_agg_rows(agg_list l, int32_t 
                     int32_t u[4], o[4];
                     float cf[4], t[4][VEC];
 #pragma unroll
-                    for (int j = 0; j < 4; j++) agg_term<TR>(a, p + j * (int64_t)slots, u[j], cf[j], o[j]);
+                    for (int j = 0; j < 4; j++) agg_term<TR, HEADS>(a, p + j * (int64_t)slots, hd, u[j], cf[j], o[j]);
 #pragma unroll
                     for (int j = 0; j < 4; j++) agg_values<VEC, TR>(a, u[j], o[j], c0, t[j]);
 #pragma unroll
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_agg_rows(agg_list l, int32_t 
                 for (; p < end; p += slots) {
                     int32_t u, o;
                     float cf, t[VEC];
-                    agg_term<TR>(a, p, u, cf, o);
+                    agg_term<TR, HEADS>(a, p, hd, u, cf, o);
                     agg_values<VEC, TR>(a, u, o, c0, t);
 #pragma unroll
                     for (int k = 0; k < VEC; k++) acc[k] = acc[k] + cf * t[k];
@@ -429,13 +437,13 @@ int agg_build_transpose(vgl_hip_ctx *c, vgl_hip_agg_plan *p)
     return 0;
 }
 
-template <int OP, int VEC, bool TR>
+template <int OP, int VEC, bool TR, bool HEADS = false>
 int agg_pass(vgl_hip_ctx *c, const vgl_agg_lists &L, const agg_args &a)
 {
     const char *const slot[VGL_RC_N] = {"agg_short", "agg_wave", "agg_wg"};
     const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
-    VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_agg_rows<VGL_RC_SHORT, OP, VEC, TR>, vgl_k_agg_rows<VGL_RC_WAVE, OP, VEC, TR>,
-                               vgl_k_agg_rows<VGL_RC_WG, OP, VEC, TR>, list, a));
+    VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_agg_rows<VGL_RC_SHORT, OP, VEC, TR, HEADS>, vgl_k_agg_rows<VGL_RC_WAVE, OP, VEC, TR, HEADS>,
+                               vgl_k_agg_rows<VGL_RC_WG, OP, VEC, TR, HEADS>, list, a));
     if (L.nhubs > 0) {
         const agg_hubs hubs{L.hub_row.p, L.hub_first.p, L.hub_nch.p, (int32_t)L.nhubs};
         vgl_timed_launch tl(c, "agg_hubs");
@@ -460,7 +468,15 @@ int agg_run(vgl_hip_ctx *c, const vgl_agg_lists &L, bool transposed, int op, agg
         if (ext) VGL_TRY(cpart_arg.alloc(st, (size_t)L.n[VGL_RC_WG] * (size_t)a.F));
     }
     a.cpart = cpart.p; a.cpart_arg = cpart_arg.p;
-    if (ext) {
+    if (a.H > 0) {                                                    // the heads form: SUM or MEAN with E x H weights
+        if (transposed) {
+            if (vec == 4) VGL_TRY((agg_pass<AGG_K_SUM, 4, true, true>(c, L, a)));
+            else VGL_TRY((agg_pass<AGG_K_SUM, 1, true, true>(c, L, a)));
+        } else {
+            if (vec == 4) VGL_TRY((agg_pass<AGG_K_SUM, 4, false, true>(c, L, a)));
+            else VGL_TRY((agg_pass<AGG_K_SUM, 1, false, true>(c, L, a)));
+        }
+    } else if (ext) {
         if (vec == 4) VGL_TRY((agg_pass<AGG_K_EXT, 4, false>(c, L, a)));
         else VGL_TRY((agg_pass<AGG_K_EXT, 1, false>(c, L, a)));
     } else if (transposed) {
@@ -477,10 +493,10 @@ int agg_run(vgl_hip_ctx *c, const vgl_agg_lists &L, bool transposed, int op, agg
         s.rows = rows; s.entries = L.entries;
         s.rows_short = L.rows_of[0]; s.rows_wave = L.rows_of[1]; s.rows_wg = L.rows_of[2];
         s.chunks = L.n[VGL_RC_WG]; s.hub_rows = L.nhubs;
-        s.transposed = transposed ? 1 : 0; s.vec = vec;
+        s.transposed = transposed ? 1 : 0; s.vec = vec; s.heads = a.H;
         const int64_t F = a.F;
         // the model (include/vgl_hip.h has the terms)
-        int64_t per_entry = 4 + (a.weight ? 4 : 0);
+        int64_t per_entry = 4 + (a.H > 0 ? 4 * (int64_t)a.H : a.weight ? 4 : 0);
         if (transposed) per_entry += 4 + (a.len_rowptr ? 16 : 0);
         int64_t bytes = 0;
         for (int q = 0; q < VGL_RC_N; q++) { s.column_tiles[q] = tiles[q]; bytes += L.entries_of[q] * tiles[q] * per_entry; }
@@ -502,6 +518,18 @@ int agg_check_call(const char *who, vgl_hip_ctx *c, vgl_hip_agg_plan *p, int op,
     if (op < VGL_HIP_AGG_SUM || op > VGL_HIP_AGG_MIN) return fail("op must be VGL_HIP_AGG_SUM, _MEAN, _MAX or _MIN");
     if (d_weight && (op == VGL_HIP_AGG_MAX || op == VGL_HIP_AGG_MIN)) return fail("MAX and MIN take no entry weights");
     if (F < 1) return fail("F must be at least 1");
+    return 0;
+}
+
+// what the two heads runs refuse beside agg_check_call
+int agg_check_heads(const char *who, int op, const float *d_weight, int32_t F, int32_t H)
+{
+    static thread_local std::string msg;
+    auto fail = [&](const char *what) { msg = std::string(who) + ": " + what; return vgl_set_error(__FILE__, __LINE__, msg.c_str()); };
+    if (op != VGL_HIP_AGG_SUM && op != VGL_HIP_AGG_MEAN) return fail("op must be VGL_HIP_AGG_SUM or _MEAN");
+    if (!d_weight) return fail("d_weight must not be NULL");
+    if (H < 1) return fail("H must be at least 1");
+    if (F % H != 0) return fail("F must be a multiple of H");
     return 0;
 }
 
@@ -608,6 +636,46 @@ int vgl_hip_agg_run_transposed(vgl_hip_ctx *c, vgl_hip_agg_plan *p, int op, cons
     a.x = d_g; a.ldx = ldg; a.out = d_gx; a.ldo = ldgx;
     a.F = F;
     const int vec = F % 4 == 0 && ldg % 4 == 0 && ldgx % 4 == 0 && agg_aligned16(d_g) && agg_aligned16(d_gx) && (!a.arg || agg_aligned16(a.arg)) ? 4 : 1;
+    return agg_run(c, p->tr, true, op, a, vec, p->n_cols, stats);
+}
+
+int vgl_hip_agg_run_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, int op, const float *d_weight, int32_t H, const float *d_x, int64_t ldx, int32_t F, float *d_out, int64_t ldo,
+                          vgl_hip_agg_stats *stats)
+{
+    // every refusal comes before the first write to an output
+    VGL_TRY(agg_check_call("agg_run_heads", c, p, op, nullptr, F));
+    VGL_TRY(agg_check_heads("agg_run_heads", op, d_weight, F, H));
+    if (!d_x || !d_out) VGL_FAIL("agg_run_heads: d_x and d_out must not be NULL");
+    if (ldx < F || ldo < F) VGL_FAIL("agg_run_heads: a leading dimension must not be below F");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    agg_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.adj = p->adj;
+    a.weight = d_weight; a.H = H; a.D = F / H;
+    a.x = d_x; a.ldx = ldx; a.out = d_out; a.ldo = ldo;
+    a.F = F;
+    a.mean = op == VGL_HIP_AGG_MEAN ? 1 : 0;
+    const int vec = a.D % 4 == 0 && ldx % 4 == 0 && ldo % 4 == 0 && agg_aligned16(d_x) && agg_aligned16(d_out) ? 4 : 1;
+    return agg_run(c, p->fwd, false, op, a, vec, p->n_rows, stats);
+}
+
+int vgl_hip_agg_run_transposed_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, int op, const float *d_weight, int32_t H, const float *d_g, int64_t ldg, int32_t F, float *d_gx,
+                                     int64_t ldgx, vgl_hip_agg_stats *stats)
+{
+    VGL_TRY(agg_check_call("agg_run_transposed_heads", c, p, op, nullptr, F));
+    VGL_TRY(agg_check_heads("agg_run_transposed_heads", op, d_weight, F, H));
+    if (!d_g || !d_gx) VGL_FAIL("agg_run_transposed_heads: d_g and d_gx must not be NULL");
+    if (ldg < F || ldgx < F) VGL_FAIL("agg_run_transposed_heads: a leading dimension must not be below F");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    if (!p->has_tr) VGL_TRY(agg_build_transpose(c, p));
+    agg_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->t_rowptr.p; a.adj = p->t_adj.p; a.origin = p->t_origin.p;
+    a.len_rowptr = op == VGL_HIP_AGG_MEAN ? p->rowptr : nullptr;
+    a.weight = d_weight; a.H = H; a.D = F / H;
+    a.x = d_g; a.ldx = ldg; a.out = d_gx; a.ldo = ldgx;
+    a.F = F;
+    const int vec = a.D % 4 == 0 && ldg % 4 == 0 && ldgx % 4 == 0 && agg_aligned16(d_g) && agg_aligned16(d_gx) ? 4 : 1;
     return agg_run(c, p->tr, true, op, a, vec, p->n_cols, stats);
 }
 

@@ -11,6 +11,9 @@
 //   rows     softmax and its backward: every lane an entry slot.  A row of one chunk is finished by its team (walks: max, sum, write; backward: sum,
 //            write).  A chunk of a longer row leaves (m_c, s_c) (backward: d_c); vgl_k_edge_hubs, a thread per such row, merges them in chunk order
 //            and leaves the row's (M, S) in every one of its chunks' slots; vgl_k_edge_hub_write writes the entries, a workgroup per chunk.
+//   heads    the same three calls on H scalars per entry, e[p * H + h], head h on the columns [h D, (h + 1) D): separate kernels
+//            (vgl_k_edge_dot_heads, vgl_k_edge_rows_heads, ...) further down, so that the single-head instantiations stay as they were; each head
+//            has the bits of the single-head call on its column slice.
 // Every value has one writer and every sum a shape fixed by (row length, F, VEC, the three switches): no floating-point atomic, no scratch memory, no
 // cooperative launch, no wait on a flag, no retry loop.
 #include "vgl_agg.h"
@@ -218,8 +221,319 @@ __global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_hub_write(agg_list l, in
     }
 }
 
+// ---- heads: H scalars per entry, e[p * H + h]; head h owns the columns [h D, (h + 1) D) ----
+// The dot product: the lanes of an entry slot are (head of the pass x column group of the head).  NQ lanes per head and the tiles of a head come from
+// agg_shape(D, VEC), HP heads sit beside each other (a power of two: what the class's lane budget holds, no more than H needs), the remaining heads
+// follow in further passes over the same adj[p].  The butterfly stops at NQ / 2, so it folds the lanes of one head only and e[:, h] has the bits of
+// vgl_k_edge_dot at width D on the head's column slice.
+struct edge_dot_heads_args {
+    const int64_t *rowptr;
+    const int32_t *adj;
+    const float *a, *b;          // n_rows x F (lda), n_cols x F (ldb), F = H * D
+    float *e;                    // E x H
+    int64_t lda, ldb;
+    int32_t H, D, chunk;
+    int32_t lognq[VGL_RC_N], tiles[VGL_RC_N];    // of one head: agg_shape(D, VEC)
+    int32_t loghp[VGL_RC_N], passes[VGL_RC_N];   // heads beside each other in a slot, passes over the heads
+    int32_t mean;
+};
+
+template <int CLS, int VEC>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_dot_heads(agg_list l, int32_t n, edge_dot_heads_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    const int lognq = a.lognq[CLS], nq = 1 << lognq, hp = 1 << a.loghp[CLS], logw = lognq + a.loghp[CLS], slots = T::LANES >> logw;
+    const int q = T::lane() & (nq - 1), hl = (T::lane() >> lognq) & (hp - 1), slot = T::lane() >> logw;
+    const int tiles = a.tiles[CLS], passes = a.passes[CLS], cq = q * VEC;
+    const bool one = tiles == 1 && passes == 1;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        int32_t v = 0;
+        int64_t lo = 0, hi = 0, len = 0;
+        if (has) {
+            v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            len = hi - lo;
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const float *arow = a.a + (int64_t)v * a.lda;
+        float av[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; k++) av[k] = 0.0f;
+        if (one && hl < a.H && cq < a.D && lo < hi) agg_load<VEC>(arow + hl * a.D + cq, av);      // one pass of one tile: the row's values stay in registers
+        int64_t p = lo + slot;
+        // the lanes of a slot share p: they stay together through the loops and the butterflies; a lane past the last head or column loads nothing
+        for (; p + 3 * (int64_t)slots < hi; p += 4 * (int64_t)slots) {                 // four gathers in flight, adj read once for every pass
+            int32_t u[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) u[j] = a.adj[p + j * (int64_t)slots];
+            for (int ps = 0; ps < passes; ps++) {
+                const int h = ps * hp + hl;
+                const bool hact = h < a.H;
+                float acc[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = 0.0f;
+                for (int t = 0, c = cq; t < tiles; t++, c += nq * VEC) {
+                    if (hact && c < a.D) {
+                        const int c0 = h * a.D + c;
+                        float x[4][VEC];
+#pragma unroll
+                        for (int j = 0; j < 4; j++) agg_load<VEC>(a.b + (int64_t)u[j] * a.ldb + c0, x[j]);
+                        if (!one) agg_load<VEC>(arow + c0, av);
+#pragma unroll
+                        for (int j = 0; j < 4; j++)
+#pragma unroll
+                            for (int k = 0; k < VEC; k++) acc[j] = acc[j] + av[k] * x[j][k];
+                    }
+                }
+                for (int o = 1; o < nq; o <<= 1)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) acc[j] = acc[j] + __shfl_xor(acc[j], o);
+                if (q == 0 && hact)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) a.e[(p + j * (int64_t)slots) * a.H + h] = a.mean ? acc[j] / (float)len : acc[j];
+            }
+        }
+        for (; p < hi; p += slots) {
+            const int32_t u = a.adj[p];
+            for (int ps = 0; ps < passes; ps++) {
+                const int h = ps * hp + hl;
+                const bool hact = h < a.H;
+                float acc = 0.0f;
+                for (int t = 0, c = cq; t < tiles; t++, c += nq * VEC) {
+                    if (hact && c < a.D) {
+                        const int c0 = h * a.D + c;
+                        float x[VEC];
+                        agg_load<VEC>(a.b + (int64_t)u * a.ldb + c0, x);
+                        if (!one) agg_load<VEC>(arow + c0, av);
+#pragma unroll
+                        for (int k = 0; k < VEC; k++) acc = acc + av[k] * x[k];
+                    }
+                }
+                for (int o = 1; o < nq; o <<= 1) acc = acc + __shfl_xor(acc, o);
+                if (q == 0 && hact) a.e[p * a.H + h] = a.mean ? acc / (float)len : acc;
+            }
+        }
+    }
+}
+
+// The softmax and its backward: every lane an entry slot that carries a block of HB heads in registers; HB divides H, the blocks follow each other.
+struct edge_rows_heads_args {
+    const int64_t *rowptr;
+    const float *x, *g;          // E x H.  forward: x = e; backward: x = y, g = gy
+    float *out;                  // E x H: y; backward: ge
+    float2 *part;                // per (workgroup item, head), as in edge_rows_args
+    int32_t chunk, H;
+    int32_t wide;                // x, g and out are 16-byte aligned: a lane's block of heads goes as 8- or 16-byte accesses
+};
+
+template <int HB> __device__ __forceinline__ void edge_load_heads(const float *p, bool wide, float *v)
+{
+    if constexpr (HB >= 4) {
+        if (wide) {
+#pragma unroll
+            for (int k = 0; k < HB; k += 4) agg_load<4>(p + k, v + k);
+            return;
+        }
+    } else if constexpr (HB == 2) {
+        if (wide) { const float2 t = *reinterpret_cast<const float2 *>(p); v[0] = t.x; v[1] = t.y; return; }
+    }
+#pragma unroll
+    for (int k = 0; k < HB; k++) v[k] = p[k];
+}
+template <int HB> __device__ __forceinline__ void edge_store_heads(float *p, bool wide, const float *v)
+{
+    if constexpr (HB >= 4) {
+        if (wide) {
+#pragma unroll
+            for (int k = 0; k < HB; k += 4) agg_store<4>(p + k, v + k);
+            return;
+        }
+    } else if constexpr (HB == 2) {
+        if (wide) { *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]); return; }
+    }
+#pragma unroll
+    for (int k = 0; k < HB; k++) p[k] = v[k];
+}
+
+// edge_team_sum for HB values at once: the same butterfly and the same wave order per value, one pair of barriers for the block
+template <int CLS, int HB>
+__device__ __forceinline__ void edge_team_sum_heads(float *v)
+{
+    constexpr int FOLD = vgl_rc_team<CLS>::LANES < 64 ? vgl_rc_team<CLS>::LANES : 64;
+#pragma unroll
+    for (int k = 0; k < HB; k++)
+#pragma unroll
+        for (int o = 1; o < FOLD; o <<= 1) v[k] = v[k] + __shfl_xor(v[k], o);
+    if constexpr (CLS == VGL_RC_WG) {
+        __shared__ float s_sum[VGL_WAVES][HB];
+        __syncthreads();                                              // the sums of the block before have been read
+        if (vgl_lane() == 0)
+#pragma unroll
+            for (int k = 0; k < HB; k++) s_sum[vgl_wave()][k] = v[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < HB; k++) {
+            v[k] = s_sum[0][k];
+#pragma unroll
+            for (int w = 1; w < VGL_WAVES; w++) v[k] = v[k] + s_sum[w][k];
+        }
+    }
+}
+// the largest of each of HB values over the team, in every lane (a maximum has no rounding: its shape is free)
+template <int CLS, int HB>
+__device__ __forceinline__ void edge_team_max_heads(float *v)
+{
+    constexpr int FOLD = vgl_rc_team<CLS>::LANES < 64 ? vgl_rc_team<CLS>::LANES : 64;
+#pragma unroll
+    for (int k = 0; k < HB; k++)
+#pragma unroll
+        for (int o = 1; o < FOLD; o <<= 1) { const float t = __shfl_xor(v[k], o); v[k] = t > v[k] ? t : v[k]; }
+    if constexpr (CLS == VGL_RC_WG) {
+        __shared__ float s_max[VGL_WAVES][HB];
+        __syncthreads();                                              // the maxima of the block before have been read
+        if (vgl_lane() == 0)
+#pragma unroll
+            for (int k = 0; k < HB; k++) s_max[vgl_wave()][k] = v[k];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < HB; k++)
+#pragma unroll
+            for (int w = 0; w < VGL_WAVES; w++) v[k] = s_max[w][k] > v[k] ? s_max[w][k] : v[k];
+    }
+}
+
+// the heads h0 .. h0 + HB - 1 of the entries first, first + step, ... below hi, given (m, s) per head (backward: d in s)
+template <bool BWD, int HB>
+__device__ __forceinline__ void edge_write_heads(const edge_rows_heads_args &a, int64_t first, int64_t hi, int step, int h0, const float *m, const float *s)
+{
+    const bool wide = a.wide != 0;
+    for (int64_t p = first; p < hi; p += step) {
+        const int64_t at = p * a.H + h0;
+        float x[HB], r[HB];
+        edge_load_heads<HB>(a.x + at, wide, x);
+        if constexpr (BWD) {
+            float g[HB];
+            edge_load_heads<HB>(a.g + at, wide, g);
+#pragma unroll
+            for (int k = 0; k < HB; k++) r[k] = x[k] * (g[k] - s[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < HB; k++) r[k] = m[k] == -INFINITY ? 0.0f : expf(x[k] - m[k]) / s[k];      // (a head whose row is at -inf alone: 0)
+        }
+        edge_store_heads<HB>(a.out + at, wide, r);
+    }
+}
+
+template <int CLS, bool BWD, int HB>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_rows_heads(agg_list l, int32_t n, edge_rows_heads_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    const bool wide = a.wide != 0;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        int64_t lo = 0, hi = 0;
+        bool whole = true;
+        if (has) {
+            const int32_t v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                whole = hi - lo <= a.chunk;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const int64_t first = lo + T::lane();
+        for (int h0 = 0; h0 < a.H; h0 += HB) {                         // the blocks of heads: the same trips in every lane
+            float m[HB], acc[HB];
+#pragma unroll
+            for (int k = 0; k < HB; k++) { m[k] = 0.0f; acc[k] = 0.0f; }
+            if constexpr (BWD) {
+                for (int64_t p = first; p < hi; p += T::LANES) {
+                    float x[HB], g[HB];
+                    edge_load_heads<HB>(a.x + p * a.H + h0, wide, x);
+                    edge_load_heads<HB>(a.g + p * a.H + h0, wide, g);
+#pragma unroll
+                    for (int k = 0; k < HB; k++) acc[k] = acc[k] + x[k] * g[k];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < HB; k++) m[k] = -INFINITY;
+                for (int64_t p = first; p < hi; p += T::LANES) {
+                    float x[HB];
+                    edge_load_heads<HB>(a.x + p * a.H + h0, wide, x);
+#pragma unroll
+                    for (int k = 0; k < HB; k++) m[k] = x[k] > m[k] ? x[k] : m[k];
+                }
+                edge_team_max_heads<CLS, HB>(m);
+                for (int64_t p = first; p < hi; p += T::LANES) {
+                    float x[HB];
+                    edge_load_heads<HB>(a.x + p * a.H + h0, wide, x);
+#pragma unroll
+                    for (int k = 0; k < HB; k++)
+                        if (m[k] != -INFINITY) acc[k] = acc[k] + expf(x[k] - m[k]);      // (else every term is 0, and -inf - -inf is not formed)
+                }
+            }
+            edge_team_sum_heads<CLS, HB>(acc);
+            if (CLS == VGL_RC_WG && !whole) {
+                if (T::lead() && has)
+#pragma unroll
+                    for (int k = 0; k < HB; k++) a.part[i * a.H + h0 + k] = make_float2(BWD ? acc[k] : m[k], BWD ? 0.0f : acc[k]);
+            } else edge_write_heads<BWD, HB>(a, first, hi, T::LANES, h0, m, acc);
+        }
+    }
+}
+
+// the rows of more than one chunk: a thread per (row, head) merges the head's partials in chunk order, as vgl_k_edge_hubs does for one head
+template <bool BWD>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_hubs_heads(edge_hubs h, int32_t H, float2 *part)
+{
+    const int64_t total = (int64_t)h.n * H;
+    for (int64_t t = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; t < total; t += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t k = (int32_t)(t / H);
+        float2 *mine = part + (int64_t)h.first[k] * H + (t - (int64_t)k * H);
+        const int32_t nch = h.nch[k];
+        float m = 0.0f, s = 0.0f;
+        if constexpr (BWD) {
+            s = mine[0].x;
+            for (int32_t j = 1; j < nch; j++) s = s + mine[(int64_t)j * H].x;
+        } else {
+            m = mine[0].x;
+            for (int32_t j = 1; j < nch; j++) m = mine[(int64_t)j * H].x > m ? mine[(int64_t)j * H].x : m;
+            for (int32_t j = 0; j < nch; j++) {
+                const float2 c = mine[(int64_t)j * H];
+                if (c.x != -INFINITY) s = s + c.y * expf(c.x - m);    // a chunk of -inf alone contributes nothing
+            }
+        }
+        for (int32_t j = 0; j < nch; j++) mine[(int64_t)j * H] = make_float2(BWD ? s : m, BWD ? 0.0f : s);
+    }
+}
+template <bool BWD, int HB>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_hub_write_heads(agg_list l, int32_t n, edge_rows_heads_args a)
+{
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int32_t v = l.rows[i];
+        const int64_t row_lo = a.rowptr[v], end = a.rowptr[v + 1];
+        if (end - row_lo <= a.chunk) continue;                        // (uniform over the workgroup)
+        const int64_t lo = row_lo + (int64_t)l.chunk[i] * a.chunk, hi = min(end, lo + a.chunk);
+        for (int h0 = 0; h0 < a.H; h0 += HB) {
+            float m[HB], s[HB];
+#pragma unroll
+            for (int k = 0; k < HB; k++) { const float2 ms = a.part[i * a.H + h0 + k]; m[k] = ms.x; s[k] = BWD ? ms.x : ms.y; }
+            edge_write_heads<BWD, HB>(a, lo + threadIdx.x, hi, VGL_BLOCK, h0, m, s);
+        }
+    }
+}
+
 // the stats of a run over the plan's CSR; `per_entry` bytes per entry beside the adjacency walks, `per_row` per row beside the list entries
-void edge_stats(const vgl_hip_agg_plan *p, const int32_t *tiles, int vec, int64_t adj_bytes, int64_t per_entry, int64_t per_row, vgl_hip_agg_stats *stats)
+void edge_stats(const vgl_hip_agg_plan *p, const int32_t *tiles, int vec, int64_t adj_bytes, int64_t per_entry, int64_t per_row, vgl_hip_agg_stats *stats, int32_t heads = 0)
 {
     const vgl_agg_lists &L = p->fwd;
     vgl_hip_agg_stats s;
@@ -227,7 +541,7 @@ void edge_stats(const vgl_hip_agg_plan *p, const int32_t *tiles, int vec, int64_
     s.rows = p->n_rows; s.entries = L.entries;
     s.rows_short = L.rows_of[0]; s.rows_wave = L.rows_of[1]; s.rows_wg = L.rows_of[2];
     s.chunks = L.n[VGL_RC_WG]; s.hub_rows = L.nhubs;
-    s.transposed = 0; s.vec = vec;
+    s.transposed = 0; s.vec = vec; s.heads = heads;
     int64_t bytes = 0;
     for (int q = 0; q < VGL_RC_N; q++) { s.column_tiles[q] = tiles[q]; bytes += L.entries_of[q] * tiles[q] * adj_bytes; }
     bytes += L.entries * per_entry + (int64_t)p->n_rows * per_row;
@@ -280,9 +594,116 @@ int edge_rows_run(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_x, const f
     return 0;
 }
 
+// the largest of 8, 4, 2, 1 that divides H: the heads a lane carries at a time
+int edge_head_block(int32_t H) { return H % 8 == 0 ? 8 : H % 4 == 0 ? 4 : H % 2 == 0 ? 2 : 1; }
+
+template <bool BWD, int HB>
+int edge_rows_heads_launch(vgl_hip_ctx *c, const vgl_agg_lists &L, const edge_rows_heads_args &a)
+{
+    hipStream_t st = c->stream;
+    const char *const slot[VGL_RC_N] = {"edge_short", "edge_wave", "edge_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_rows_heads<VGL_RC_SHORT, BWD, HB>, vgl_k_edge_rows_heads<VGL_RC_WAVE, BWD, HB>,
+                               vgl_k_edge_rows_heads<VGL_RC_WG, BWD, HB>, list, a));
+    if (L.nhubs > 0) {
+        const edge_hubs hubs{L.hub_first.p, L.hub_nch.p, (int32_t)L.nhubs};
+        {
+            vgl_timed_launch tl(c, "edge_hubs");
+            hipLaunchKernelGGL(vgl_k_edge_hubs_heads<BWD>, dim3(vgl_grid(L.nhubs * a.H, VGL_BLOCK, AGG_MAX_GRID)), dim3(VGL_BLOCK), 0, st, hubs, a.H, a.part);
+        }
+        vgl_timed_launch tl(c, "edge_hub_write");
+        hipLaunchKernelGGL((vgl_k_edge_hub_write_heads<BWD, HB>), dim3(vgl_grid(L.n[VGL_RC_WG], 1, agg_grid_cap[VGL_RC_WG])), dim3(VGL_BLOCK), 0, st, list[VGL_RC_WG],
+                           (int32_t)L.n[VGL_RC_WG], a);
+    }
+    return 0;
+}
+
+template <bool BWD>
+int edge_rows_heads_run(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_x, const float *d_g, int32_t H, float *d_out, vgl_hip_agg_stats *stats)
+{
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const vgl_agg_lists &L = p->fwd;
+    edge_rows_heads_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.x = d_x; a.g = d_g; a.out = d_out;
+    a.chunk = L.ch.chunk; a.H = H;
+    a.wide = agg_aligned16(d_x) && agg_aligned16(d_out) && (!BWD || agg_aligned16(d_g)) ? 1 : 0;
+    vgl_dev<float> part;
+    if (L.nhubs > 0) VGL_TRY(part.alloc(st, 2 * (size_t)L.n[VGL_RC_WG] * (size_t)H));
+    a.part = reinterpret_cast<float2 *>(part.p);
+    const int hb = edge_head_block(H);
+    if (hb == 8) VGL_TRY((edge_rows_heads_launch<BWD, 8>(c, L, a)));
+    else if (hb == 4) VGL_TRY((edge_rows_heads_launch<BWD, 4>(c, L, a)));
+    else if (hb == 2) VGL_TRY((edge_rows_heads_launch<BWD, 2>(c, L, a)));
+    else VGL_TRY((edge_rows_heads_launch<BWD, 1>(c, L, a)));
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_HIP_TRY(hipStreamSynchronize(st));                            // (the partials are free again; the result is there when the call returns)
+    if (stats) {
+        const int32_t tiles[VGL_RC_N] = {1, 1, 1};
+        // per (entry, head): forward three walks of e and y written; backward two walks of y and gy and ge written; 8 bytes of bounds per row
+        edge_stats(p, tiles, a.wide && hb >= 4 ? 4 : 1, 0, (int64_t)H * (BWD ? 8 * 2 + 4 : 4 * 3 + 4), 8, stats, H);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vgl_hip_agg_sddmm_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int32_t H, int mean, float *d_e,
+                            vgl_hip_agg_stats *stats)
+{
+    // every refusal comes before the first write to an output
+    VGL_TRY(edge_check_call("agg_sddmm_heads", c, p, d_a, d_b, d_e));
+    if (F < 1) VGL_FAIL("agg_sddmm_heads: F must be at least 1");
+    if (H < 1) VGL_FAIL("agg_sddmm_heads: H must be at least 1");
+    if (F % H != 0) VGL_FAIL("agg_sddmm_heads: F must be a multiple of H");
+    if (lda < F || ldb < F) VGL_FAIL("agg_sddmm_heads: a leading dimension must not be below F");
+    if (mean != 0 && mean != 1) VGL_FAIL("agg_sddmm_heads: mean must be 0 or 1");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    const vgl_agg_lists &L = p->fwd;
+    edge_dot_heads_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.adj = p->adj;
+    a.a = d_a; a.lda = lda; a.b = d_b; a.ldb = ldb; a.e = d_e;
+    a.H = H; a.D = F / H; a.chunk = L.ch.chunk; a.mean = mean;
+    const int vec = a.D % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && agg_aligned16(d_a) && agg_aligned16(d_b) ? 4 : 1;
+    agg_shape(a.D, vec, a.lognq, a.tiles);
+    int32_t walks[VGL_RC_N];
+    for (int q = 0; q < VGL_RC_N; q++) {
+        const int room = (q == VGL_RC_SHORT ? 3 : 6) - a.lognq[q];    // the lanes of a slot: 8 in the short class, 64 in the others
+        int lg = 0;
+        while (lg < room && ((int64_t)1 << lg) < H) lg++;
+        a.loghp[q] = lg;
+        a.passes[q] = (int32_t)vgl_ceil_div(H, (int64_t)1 << lg);
+        walks[q] = a.passes[q] * a.tiles[q];
+    }
+    const char *const slot[VGL_RC_N] = {"edge_dot_short", "edge_dot_wave", "edge_dot_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    if (vec == 4)
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_dot_heads<VGL_RC_SHORT, 4>, vgl_k_edge_dot_heads<VGL_RC_WAVE, 4>, vgl_k_edge_dot_heads<VGL_RC_WG, 4>, list, a));
+    else
+        VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_dot_heads<VGL_RC_SHORT, 1>, vgl_k_edge_dot_heads<VGL_RC_WAVE, 1>, vgl_k_edge_dot_heads<VGL_RC_WG, 1>, list, a));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));                     // (the result is there when the call returns)
+    // per entry: 4 F of b gathered and 4 H of e written; per row: the bounds and 4 F of a; the adjacency once per pass and tile (requested)
+    if (stats) edge_stats(p, walks, vec, 4, 4 * (int64_t)F + 4 * (int64_t)H, 8 + 4 * (int64_t)F, stats, H);
+    return 0;
+}
+
+int vgl_hip_agg_edge_softmax_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_e, int32_t H, float *d_y, vgl_hip_agg_stats *stats)
+{
+    VGL_TRY(edge_check_call("agg_edge_softmax_heads", c, p, d_e, d_y, d_y));
+    if (H < 1) VGL_FAIL("agg_edge_softmax_heads: H must be at least 1");
+    return edge_rows_heads_run<false>(c, p, d_e, nullptr, H, d_y, stats);
+}
+
+int vgl_hip_agg_edge_softmax_backward_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_y, const float *d_gy, int32_t H, float *d_ge, vgl_hip_agg_stats *stats)
+{
+    VGL_TRY(edge_check_call("agg_edge_softmax_backward_heads", c, p, d_y, d_gy, d_ge));
+    if (H < 1) VGL_FAIL("agg_edge_softmax_backward_heads: H must be at least 1");
+    return edge_rows_heads_run<true>(c, p, d_y, d_gy, H, d_ge, stats);
+}
 
 int vgl_hip_agg_sddmm(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int mean, float *d_e, vgl_hip_agg_stats *stats)
 {

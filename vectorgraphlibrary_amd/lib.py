@@ -136,7 +136,7 @@ class PprStats(C.Structure):
 class AggStats(C.Structure):
     _fields_ = [("rows", C.c_int64), ("entries", C.c_int64), ("rows_short", C.c_int64), ("rows_wave", C.c_int64), ("rows_wg", C.c_int64),
                 ("chunks", C.c_int64), ("hub_rows", C.c_int64), ("algorithmic_bytes", C.c_int64), ("column_tiles", C.c_int32 * 3), ("vec", C.c_int32),
-                ("transposed", C.c_int32), ("reserved", C.c_int32)]
+                ("transposed", C.c_int32), ("heads", C.c_int32)]
 
 
 class KhopStats(C.Structure):
@@ -272,6 +272,11 @@ _SIGNATURES = {
     "vgl_hip_agg_sddmm": [_p, _p, _p, _i64, _p, _i64, _i32, _int, _p, C.POINTER(AggStats)],
     "vgl_hip_agg_edge_softmax": [_p, _p, _p, _p, C.POINTER(AggStats)],
     "vgl_hip_agg_edge_softmax_backward": [_p, _p, _p, _p, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_sddmm_heads": [_p, _p, _p, _i64, _p, _i64, _i32, _i32, _int, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_edge_softmax_heads": [_p, _p, _p, _i32, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_edge_softmax_backward_heads": [_p, _p, _p, _p, _i32, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_run_heads": [_p, _p, _int, _p, _i32, _p, _i64, _i32, _p, _i64, C.POINTER(AggStats)],
+    "vgl_hip_agg_run_transposed_heads": [_p, _p, _int, _p, _i32, _p, _i64, _i32, _p, _i64, C.POINTER(AggStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
