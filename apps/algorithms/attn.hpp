@@ -7,9 +7,14 @@
 // q holds the scale F^-1/2 already (the C interface has no scaling call; in Python it is a torch product).
 // With -heads H every stage runs its heads form (the vgl_hip_agg_*_heads calls): head h owns the columns [h D, (h + 1) D), D = F / H, the entry
 // scalars are E x H, q holds D^-1/2, and the restatement runs per head with D in place of F in the bound of the dot.
+// With -score add the score is the additive one of GAT (vgl_hip_agg_edge_add_heads): e = leaky_relu(a[row] + b[adj], slope) from two V x H terms
+// a, b; its gradients are the two entry sums (vgl_hip_agg_edge_sum_heads, the score as the gate).  The restatement holds the score to equality of
+// bits and the sums to gamma_d of the sum of |c|.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <functional>
 #include <string>
 #include <vector>
@@ -19,6 +24,8 @@ struct GraphAttention {
     struct Options {
         int features = 64, stage = ATTENTION, heads = 1;
         bool outgoing = false, backward = false, use_heads = false;    // use_heads: -heads was given, the heads calls run (also with H = 1)
+        bool score_add = false;                                        // -score add: the additive score in place of the dot product
+        float slope = 0.2f;
         size_t H() const { return use_heads ? (size_t)heads : 1; }
     };
     // the largest error of the device expf in ulps, measured (tests/studies/expf_ulps.hip), plus one
@@ -27,8 +34,8 @@ struct GraphAttention {
     // q, k, v, g (V x F) in [-0.5, 0.5) (q times F^-1/2) and s, t (one per entry) in [-8, 8): the counter hash of the position that agg_hip uses,
     // brought from its range [0, 100) on the host; the host keeps its copies for -check
     struct Inputs {
-        void *q = nullptr, *k = nullptr, *v = nullptr, *g = nullptr, *s = nullptr, *t = nullptr;
-        std::vector<float> hq, hk, hv, hg, hs, ht;
+        void *q = nullptr, *k = nullptr, *v = nullptr, *g = nullptr, *s = nullptr, *t = nullptr, *a = nullptr, *b = nullptr;
+        std::vector<float> hq, hk, hv, hg, hs, ht, ha, hb;            // a, b: the V x H terms of the additive score, in [-2, 2)
         size_t V = 0, E = 0, F = 0, H = 1;
         void make(void **d, std::vector<float> &h, size_t n, unsigned long long seed, float scale)
         {
@@ -49,16 +56,22 @@ struct GraphAttention {
             make(&g, hg, V * F, seed + 3, 1.0f);
             make(&s, hs, E * H, seed + 4, 16.0f);
             make(&t, ht, E * H, seed + 5, 16.0f);
+            if (o.score_add) {
+                make(&a, ha, V * H, seed + 6, 4.0f);
+                make(&b, hb, V * H, seed + 7, 4.0f);
+            }
             VGL_HIP_CALL(vgl_hip_ctx_sync(VGL_RUNTIME::ctx()));
         }
         ~Inputs()
         {
             vgl_hip_ctx *c = VGL_RUNTIME::ctx();
             for (void *p : {q, k, v, g, s, t}) vgl_hip_free(c, p);
+            if (a) vgl_hip_free(c, a);
+            if (b) vgl_hip_free(c, b);
         }
     };
     // what a run leaves on the host
-    struct Result { std::vector<float> e, w, out, gw, ge, gq, gk, gv; long long entries = 0; };
+    struct Result { std::vector<float> e, w, out, gw, ge, gq, gk, gv, gs, gt; long long entries = 0; };
 
     struct DeviceArray {
         void *p = nullptr; size_t n = 0;
@@ -91,6 +104,7 @@ struct GraphAttention {
         const int32_t f = (int32_t)F, hd = (int32_t)H;
         const bool heads = o.use_heads;
         DeviceArray e(E * H), w(E * H), out(V * F), gw(E * H), ge(E * H), gq(V * F), gk(V * F), gv(V * F);
+        DeviceArray gs(o.score_add ? V * H : 0), gt(o.score_add ? V * H : 0);
         vgl_hip_agg_plan *plan = nullptr;
         Timer prep;
         prep.start();
@@ -131,8 +145,31 @@ struct GraphAttention {
             return heads ? vgl_hip_agg_run_transposed_heads(c, plan, VGL_HIP_AGG_SUM, weight, hd, grad, ld, f, to, ld, &st)
                          : vgl_hip_agg_run_transposed(c, plan, VGL_HIP_AGG_SUM, weight, nullptr, grad, ld, f, to, ld, &st);
         };
+        // the additive score from the two V x H terms, and the sum of the gated entry gradient over the rows / over the columns
+        auto add = [&](float *to) { return vgl_hip_agg_edge_add_heads(c, plan, (const float *)in.a, (int64_t)H, (const float *)in.b, (int64_t)H, hd, o.slope, to, &st); };
+        auto entry_sum = [&](const float *grad, const float *gate, int transposed, float *to) {
+            return vgl_hip_agg_edge_sum_heads(c, plan, grad, gate, o.slope, hd, transposed, to, (int64_t)H, &st);
+        };
         const float *q = (const float *)in.q, *k = (const float *)in.k, *v = (const float *)in.v, *g = (const float *)in.g, *s = (const float *)in.s, *t = (const float *)in.t;
-        if (o.stage == DOT) {
+        if (o.score_add && o.stage != SOFTMAX) {
+            run("score (add)", false, [&] { return add(e.f()); });
+            if (o.stage == DOT) {
+                if (o.backward) {
+                    run("score backward, grad s (entry sum)", false, [&] { return entry_sum(s, e.f(), 0, gs.f()); });
+                    run("score backward, grad t (transposed entry sum)", true, [&] { return entry_sum(s, e.f(), 1, gt.f()); });
+                }
+            } else {
+                run("softmax", false, [&] { return softmax(e.f(), w.f()); });
+                run("weighted sum", false, [&] { return sum(w.f(), v, out.f()); });
+                if (o.backward) {
+                    run("backward, grad weights (dot of g and v)", false, [&] { return dot(g, v, gw.f()); });
+                    run("backward, grad v (transposed run)", true, [&] { return sum_t(w.f(), g, gv.f()); });
+                    run("backward, softmax backward", false, [&] { return softmax_back(w.f(), gw.f(), ge.f()); });
+                    run("backward, grad s (entry sum)", false, [&] { return entry_sum(ge.f(), e.f(), 0, gs.f()); });
+                    run("backward, grad t (transposed entry sum)", true, [&] { return entry_sum(ge.f(), e.f(), 1, gt.f()); });
+                }
+            }
+        } else if (o.stage == DOT) {
             run("dot", false, [&] { return dot(q, k, e.f()); });
             if (o.backward) {
                 run("dot backward, grad q (forward run)", false, [&] { return sum(s, k, gq.f()); });
@@ -156,6 +193,7 @@ struct GraphAttention {
         if (!launches) {
             if (transpose >= 0.0) std::cout << "ATTN transpose: " << transpose * 1000.0 << " ms (the first transposed run less a later one)" << std::endl;
             r.e = e.host(); r.w = w.host(); r.out = out.host(); r.gw = gw.host(); r.ge = ge.host(); r.gq = gq.host(); r.gk = gk.host(); r.gv = gv.host();
+            r.gs = gs.host(); r.gt = gt.host();
             r.entries = (long long)E;
         }
         VGL_HIP_CALL(vgl_hip_agg_plan_destroy(c, plan));
@@ -174,8 +212,11 @@ struct GraphAttention {
         hip_fused(view, in, o, r, true);
         int64_t total = 0;
         std::cout << "ATTN launches:";
-        for (const char *name : {"agg_prepare", "agg_transpose", "edge_dot_short", "edge_dot_wave", "edge_dot_wg", "edge_short", "edge_wave", "edge_wg", "edge_hubs", "edge_hub_write",
-                                 "agg_short", "agg_wave", "agg_wg", "agg_hubs"}) {
+        std::vector<const char *> names{"agg_prepare", "agg_transpose", "edge_dot_short", "edge_dot_wave", "edge_dot_wg", "edge_short", "edge_wave", "edge_wg", "edge_hubs", "edge_hub_write",
+                                        "agg_short", "agg_wave", "agg_wg", "agg_hubs"};
+        if (o.score_add)
+            for (const char *name : {"edge_add_short", "edge_add_wave", "edge_add_wg", "edge_sum_short", "edge_sum_wave", "edge_sum_wg", "edge_sum_hubs"}) names.push_back(name);
+        for (const char *name : names) {
             int64_t n = 0;
             double ms = 0.0;
             VGL_HIP_CALL(vgl_hip_timing_get(c, name, &n, &ms));
@@ -269,13 +310,67 @@ struct GraphAttention {
             for (size_t f = 0; f < F; f++) judge(what, i * F + f, out[i * F + f], acc[i * F + f], tolerance((double)terms[i] + 2) * mag[i * F + f]);
     }
 
+    // the additive score restated in float32: one addition, one product; equality of bits
+    static void check_score(Judge &judge, const HostCSR &h, size_t H, float slope, const std::vector<float> &a, const std::vector<float> &b, const std::vector<float> &e)
+    {
+        for (size_t i = 0; i < (size_t)h.V; i++)
+            for (long long p = h.rowptr[i]; p < h.rowptr[i + 1]; p++)
+                for (size_t hd = 0; hd < H; hd++) {
+                    const volatile float z = a[i * H + hd] + b[(size_t)h.adj[(size_t)p] * H + hd];
+                    const volatile float want = z > 0.0f ? z : slope * z;
+                    const float got = e[(size_t)p * H + hd], w = want;
+                    uint32_t gb, wb;
+                    memcpy(&gb, &got, 4); memcpy(&wb, &w, 4);
+                    judge("score (add)", (size_t)p * H + hd, gb == wb ? 0.0 : 1.0, 0.0, 0.0);
+                }
+    }
+    // out[i] = the sum over row i of c_p (forward) or out[adj p] += c_p (transposed), c = w or slope * w where the gate is not above 0, within
+    // gamma_d of the sum of |c|, d the terms of the value
+    static void check_entry_sum(Judge &judge, const char *what, const HostCSR &h, size_t H, bool transposed, float slope, const std::vector<float> &w, const std::vector<float> &gate,
+                                const std::vector<float> &out)
+    {
+        const size_t V = (size_t)h.V;
+        std::vector<double> acc(V * H, 0.0), mag(V * H, 0.0);
+        std::vector<long long> terms(V, 0);
+        for (size_t i = 0; i < V; i++)
+            for (long long p = h.rowptr[i]; p < h.rowptr[i + 1]; p++) {
+                const size_t to = transposed ? (size_t)h.adj[(size_t)p] : i;
+                terms[to]++;
+                for (size_t hd = 0; hd < H; hd++) {
+                    const size_t at = (size_t)p * H + hd;
+                    const double c = gate[at] > 0.0f ? (double)w[at] : (double)slope * w[at];
+                    acc[to * H + hd] += c; mag[to * H + hd] += std::fabs(c);
+                }
+            }
+        for (size_t i = 0; i < V; i++)
+            for (size_t hd = 0; hd < H; hd++) judge(what, i * H + hd, out[i * H + hd], acc[i * H + hd], tolerance((double)terms[i]) * mag[i * H + hd]);
+    }
+
     static int verify(const HostCSR &h, const Inputs &in, const Options &o, const Result &r)
     {
         Judge judge;
         Timer host;
         host.start();
         const size_t F = in.F, H = in.H;
-        if (o.stage == DOT) {
+        if (o.score_add && o.stage != SOFTMAX) {
+            check_score(judge, h, H, o.slope, in.ha, in.hb, r.e);
+            if (o.stage == DOT) {
+                if (o.backward) {
+                    check_entry_sum(judge, "grad s", h, H, false, o.slope, in.hs, r.e, r.gs);
+                    check_entry_sum(judge, "grad t", h, H, true, o.slope, in.hs, r.e, r.gt);
+                }
+            } else {
+                check_softmax(judge, h, H, r.e, r.w);
+                check_sum(judge, "out", h, F, H, false, r.w, in.hv, r.out);
+                if (o.backward) {
+                    check_dot(judge, "grad weights", h, F, H, in.hg, in.hv, r.gw);
+                    check_sum(judge, "grad v", h, F, H, true, r.w, in.hg, r.gv);
+                    check_softmax_backward(judge, h, H, r.w, r.gw, r.ge);
+                    check_entry_sum(judge, "grad s", h, H, false, o.slope, r.ge, r.e, r.gs);
+                    check_entry_sum(judge, "grad t", h, H, true, o.slope, r.ge, r.e, r.gt);
+                }
+            }
+        } else if (o.stage == DOT) {
             check_dot(judge, "dot", h, F, H, in.hq, in.hk, r.e);
             if (o.backward) {
                 check_sum(judge, "grad q", h, F, H, false, in.hs, in.hk, r.gq);

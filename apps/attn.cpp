@@ -6,6 +6,9 @@
 //   -stage NAME      dot | softmax | attention (default attention: dot, softmax, weighted sum)
 //   -out             over the outgoing entries (default: the incoming direction)
 //   -backward        also the gradients of the stage; the transpose build is timed apart
+//   -score NAME      dot | add (default dot).  add: the additive score of GAT, leaky_relu(a[row] + b[adj]) from two V x H terms, in place of the dot
+//                    product in the stages dot and attention; its gradients are the two entry sums
+//   -slope X         the negative slope of -score add (default 0.2; not negative)
 //   -check           compare every stage with the sequential host restatement in float64 within the derived bounds; exit status 1 on a difference
 //   -dump FILE       float32: the forward result of the stage (e, the weights, or n_rows x F) in the graph's own order
 #define INT_ELEMENTS_PER_EDGE 2.0      // one adjacency entry and (per column) one 4-byte value of its far end per entry walked
@@ -21,11 +24,16 @@ int main(int argc, char **argv)
         std::vector<char *> rest{argv[0]};
         for (int i = 1; i < argc; i++) {
             const std::string a = argv[i];
-            if (a == "-features" || a == "-stage" || a == "-heads") {
+            if (a == "-features" || a == "-stage" || a == "-heads" || a == "-score" || a == "-slope") {
                 if (i + 1 >= argc) throw "missing value for command line option";
                 const std::string v = argv[++i];
                 if (a == "-features") opt.features = atoi(v.c_str());
                 else if (a == "-heads") { opt.heads = atoi(v.c_str()); opt.use_heads = true; }
+                else if (a == "-slope") opt.slope = (float)atof(v.c_str());
+                else if (a == "-score") {
+                    if (v != "dot" && v != "add") throw "attn: unknown value for -score (dot or add)";
+                    opt.score_add = v == "add";
+                }
                 else if (v == "dot") opt.stage = ATTN::DOT;
                 else if (v == "softmax") opt.stage = ATTN::SOFTMAX;
                 else if (v == "attention") opt.stage = ATTN::ATTENTION;
@@ -37,6 +45,7 @@ int main(int argc, char **argv)
         if (opt.features < 1) throw "attn: -features must be at least 1";
         if (opt.heads < 1) throw "attn: -heads must be at least 1";
         if (opt.features % opt.heads != 0) throw "attn: -heads must divide -features";
+        if (!(opt.slope >= 0.0f) || std::isinf(opt.slope)) throw "attn: -slope must be a finite number that is not negative";
         Parser parser;
         parser.parse_args((int)rest.size(), rest.data());
         if (!parser.fused) throw "attn: only the fused path exists (pass -fused)";

@@ -1354,8 +1354,8 @@ int vgl_hip_agg_run_transposed(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op,
  *   backward entries x (8 x 2 walks of y and gy + 4 written) + rows x 8 + the list entries; the same remarks.
  * Fails, before anything is written: a NULL argument (stats may be NULL), a plan of another context, F < 1, a leading dimension below F, mean outside
  * {0, 1}.  Threads: as above.
- * Not here: the u_add_v score of the original GAT (s[row] + t[adj], two gathers in any tensor library); a fused attention that never materialises
- * the E scalars (they are 12 bytes per entry against 8 F); a softmax grouped by column; float16 / bfloat16.  Heads are the _heads calls below. */
+ * Not here: a fused attention that never materialises the E scalars (they are 12 bytes per entry against 8 F); a softmax grouped by column;
+ * float16 / bfloat16.  Heads are the _heads calls below; the u_add_v score of the original GAT is vgl_hip_agg_edge_add_heads further down. */
 int vgl_hip_agg_sddmm(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int mean,
                       float *d_e, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_edge_softmax(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_e, float *d_y, vgl_hip_agg_stats *stats);
@@ -1397,7 +1397,7 @@ int vgl_hip_agg_edge_softmax_backward(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, 
  *   softmax  entries x H x (4 x 3 + 4) + rows x 8 + the list entries.   backward  entries x H x (8 x 2 + 4) + rows x 8 + the list entries.
  *   runs     the formula of vgl_hip_agg_run / _run_transposed with 4 H of weights per entry and per walk in place of 4.
  * Fails, before anything is written: what the calls above refuse; H < 1; F % H != 0; a NULL d_weight; an op other than SUM or MEAN in the runs.
- * Not here: a leading dimension for the E x H arrays; the fused attention; the u_add_v score; float16 / bfloat16. */
+ * Not here: a leading dimension for the E x H arrays; the fused attention; float16 / bfloat16. */
 int vgl_hip_agg_sddmm_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_a, int64_t lda, const float *d_b, int64_t ldb, int32_t F, int32_t H,
                             int mean, float *d_e, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_edge_softmax_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_e, int32_t H, float *d_y, vgl_hip_agg_stats *stats);
@@ -1407,6 +1407,55 @@ int vgl_hip_agg_run_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, cons
                           float *d_out, int64_t ldo, vgl_hip_agg_stats *stats);
 int vgl_hip_agg_run_transposed_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, int op, const float *d_weight, int32_t H, const float *d_g, int64_t ldg,
                                      int32_t F, float *d_gx, int64_t ldgx, vgl_hip_agg_stats *stats);
+
+/* The additive score of GAT and the entry sums (`gat`): the u_add_v score act(s[row(p)] + t[adj[p]]) of the original graph
+ * attention layer on the E x H layout above, and the two reductions that are its gradients.  A single head is H = 1.  With the softmax and the run of
+ * the heads section they make the GAT layer three calls.  The reference has no counterpart, so this comment is the contract:
+ *   score     vgl_hip_agg_edge_add_heads: s is n_rows x H float32 (leading dimension lds >= H, in elements), t n_cols x H (ldt >= H), e E x H
+ *             contiguous in CSR order.  z = s[row(p), h] + t[adj[p], h]: ONE float32 addition;  e[p, h] = z > 0 ? z : slope * z: ONE float32 product
+ *             (LeakyReLU; slope is a float, slope = 1 is the identity on bits, slope = 0 is ReLU).  Exactly one of d_s, d_t may be NULL: the term is
+ *             then ABSENT and nothing is added, z = t[adj[p], h] or z = s[row(p), h] with its bits (a -0 stays -0): the two broadcasts "copy a row
+ *             value / a column value onto its entries".  With a NaN or an infinity in s or t the result is UNSPECIFIED.
+ *   sums      vgl_hip_agg_edge_sum_heads: w is E x H, gate E x H or NULL.  c(p, h) = w[p, h] when gate is NULL or gate[p, h] > 0, otherwise
+ *             slope * w[p, h]: ONE product.  This is the derivative of the activation above as torch defines it (slope at 0), applied on the fly;
+ *             because slope >= 0 the score itself serves as the gate.  transposed = 0: out[i, h] = the sum of c(p, h) over the entries p of row i,
+ *             out n_rows x H with ldo >= H.  transposed = 1: out[u, h] = the sum over the transposed row of u, in its order, of c(origin, h): w and
+ *             gate are read through the origin as vgl_hip_agg_run_transposed reads its weight, out is n_cols x H; the transpose is built on first
+ *             use and kept.  An empty row gives 0.  With ge the gradient of e: gs = the sum (gate = e) and gt = the transposed sum (gate = e); the
+ *             gradient of a sum is the score with one term absent and slope 1, so the pair closes under differentiation.
+ *   floating point: as above (float32, -ffp-contract=off, NO floating-point atomic, one writer per value).  The score has at most two roundings per
+ *             value and no sum: it has no shape, and equals the float32 restatement BIT FOR BIT on every class, switch setting and alignment.  A sum
+ *             has the shape of the softmax's row sums: lane s of the team (8 / 64 / 256 lanes) adds entries s, s + LANES, ... of the row or chunk in
+ *             order; an xor butterfly at offsets 1, 2, ... folds the lanes of a wave; a workgroup adds its four waves in wave order; a row of more
+ *             than one chunk leaves one float per (item, head) and ONE thread per (hub row, head) adds them in chunk order and writes the result.
+ *             The shape is a function of (row length, the three switches) only: the same call returns the same bits on every run, and on data whose
+ *             partial sums are all exact every setting returns the same bits.
+ *   tolerance per value of a sum with d terms:  |computed - exact| <= gamma_k * the sum of |c(p, h)|, k = d, gamma_k = k u / (1 - k u), u = 2^-24: one
+ *             rounding for the product of a gated term, at most d - 1 additions on a chain whatever the shape (an addition of a lane without
+ *             entries adds an exact 0); c in the bound is the exact product.
+ * Method: vgl_k_edge_add_heads<CLS, HB> over the plan's forward class lists: every lane an entry slot that carries a block of HB heads (the largest of
+ * 8, 4, 2, 1 that divides H), four entries in flight; adj[p] is read once per entry and kept across the blocks; the row's s block stays in registers
+ * where one block covers H and is re-read per block from cache otherwise; a block of s, t, e moves as one 8- or 16-byte access where the base
+ * address is 16-byte aligned and the leading dimension a multiple of 4 elements (2 for a block of two), else scalar.  No fold, no LDS, no hub stage.
+ * vgl_k_edge_sum_heads<CLS, GATE, TR, HB>: the walk and fold of the softmax backward's row sum, with TR over the transpose through t_origin; the
+ * lead lane writes a row of one chunk; vgl_k_edge_sum_hubs finishes the rows of more chunks.
+ * stats: heads = H; column_tiles = 1 / 1 / 1; vec = 4 where a lane's head block moves in 16-byte pieces in every array of the call (HB >= 4), else
+ * 1; transposed as passed; rows, entries, rows_short / _wave / _wg, chunks, hub_rows = of the CSR walked (the transpose: n_cols rows).
+ * algorithmic_bytes:
+ *   score    entries x (4 adjacency + 4 H of t gathered when d_t is given + 4 H of e written) + rows x (8 bounds + 4 H of s when d_s is given) + the
+ *            list entries (4 per short or wave row, 8 per chunk).  The gather is requested bytes, as for vgl_hip_agg_run; without d_t the kernel
+ *            does not read the adjacency and that term is an upper bound.
+ *   sums     entries x (4 H of w + 4 H of the gate when given + 4 of the origin when transposed) + rows x (8 bounds + 4 H written) + the list
+ *            entries.  The chunk partials are left out.
+ * Fails, before anything is written: a NULL ctx, plan, d_e / d_out or d_w; d_s and d_t both NULL; a plan of another context; H < 1; a leading
+ * dimension below H; a slope that is negative, NaN or infinite; transposed outside {0, 1}; an output that overlaps an input.  stats may be NULL.
+ * Threads: as above.
+ * Not here: a fused score + softmax + sum that never materialises E x H; GATv2 (the activation before a second dot product); a softmax grouped by
+ * column; float16 / bfloat16; a leading dimension for the E x H arrays. */
+int vgl_hip_agg_edge_add_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_s, int64_t lds, const float *d_t, int64_t ldt, int32_t H,
+                               float slope, float *d_e, vgl_hip_agg_stats *stats);
+int vgl_hip_agg_edge_sum_heads(vgl_hip_ctx *ctx, vgl_hip_agg_plan *plan, const float *d_w, const float *d_gate, float slope, int32_t H,
+                               int transposed, float *d_out, int64_t ldo, vgl_hip_agg_stats *stats);
 
 /* ---- super-step pieces for the edge-cut multi-GPU path (one process per GPU; the exchange between steps is an
  *      RCCL collective issued by the host side, replacing common/mpi_exchange.hpp:110-150,222-271) ---- */

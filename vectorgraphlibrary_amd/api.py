@@ -1677,6 +1677,31 @@ class AggregationPlan:
         self.last_edge_stats = _agg_stats(st)
         return ge
 
+    # the additive score and the entry sums (vgl_hip_agg_edge_add_heads / _edge_sum_heads); s or t None: the term is absent
+    def _edge_add(self, s, t, H, slope):
+        ctx = self.ctx
+        e = torch.empty((self.E, H), dtype=torch.float32, device=ctx.device)
+        if self.E == 0 or H == 0:
+            return e
+        s, lds = self._rows(s, "u_add_v: s") if s is not None else (None, 0)
+        t, ldt = self._rows(t, "u_add_v: t") if t is not None else (None, 0)
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_edge_add_heads(ctx.h, self.h, _ptr(s), lds, _ptr(t), ldt, H, float(slope), _ptr(e), C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return e
+
+    def _edge_sum(self, w, gate, slope, transposed):
+        ctx, H = self.ctx, int(w.shape[1])
+        out = torch.empty((self.n_cols if transposed else self.n_rows, H), dtype=torch.float32, device=ctx.device)
+        if out.numel() == 0:
+            return out
+        if self.E == 0:
+            return out.zero_()
+        st = _l.AggStats()
+        _l.check(ctx.L.vgl_hip_agg_edge_sum_heads(ctx.h, self.h, _ptr(w), _ptr(gate), float(slope), H, 1 if transposed else 0, _ptr(out), H, C.byref(st)))
+        self.last_edge_stats = _agg_stats(st)
+        return out
+
 
 class _Aggregate(torch.autograd.Function):
     @staticmethod
@@ -1954,5 +1979,105 @@ def graph_attention(plan, q, k, v, scale=None, return_weights=False, heads=None)
         if scale is None:
             scale = float(int(q.shape[1]) // H) ** -0.5 if int(q.shape[1]) > 0 else 1.0
     w = edge_softmax(plan, e * scale) if heads is None else _edge_softmax_any(plan, e * scale)
+    out = spmm(plan, w, v)
+    return (out, w) if return_weights else out
+
+
+# ---- the additive score of GAT, the entry sums and GAT attention (vgl_hip_agg_edge_add_heads / _edge_sum_heads in include/vgl_hip.h) ----
+def _gat_slope(who, negative_slope):
+    """(slope, gated): None is the identity"""
+    if negative_slope is None:
+        return 1.0, False
+    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)) or not 0.0 <= float(negative_slope) < float("inf"):
+        raise _l.VglHipError("%s: negative_slope must be None or a finite number that is not negative, got %r" % (who, negative_slope))
+    return float(negative_slope), True
+
+
+def _gat_term(who, name, plan, t, rows, what):
+    """(n,) or (n, H) float32 on the plan's device -> the n x H view, and whether it was one-dimensional"""
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise _l.VglHipError("%s: %s must be a float32 tensor, got %s" % (who, name, t.dtype if torch.is_tensor(t) else type(t).__name__))
+    if t.dim() not in (1, 2) or int(t.shape[0]) != rows:
+        raise _l.VglHipError("%s: %s must be (%s,) or %s x H = %d [x H], got %s" % (who, name, what, what, rows, tuple(t.shape)))
+    if t.device != plan.ctx.device:
+        raise _l.VglHipError("%s: %s must live on the plan's device" % (who, name))
+    return (t.unsqueeze(1), True) if t.dim() == 1 else (t, False)
+
+
+class _UAddV(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, s, t, plan, slope, gated):
+        e = plan._edge_add(s.detach(), t.detach(), int(s.shape[1]), slope)
+        fctx.plan, fctx.slope, fctx.gated = plan, slope, gated
+        if gated:
+            fctx.save_for_backward(e)
+        return e
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, ge):
+        gate = fctx.saved_tensors[0] if fctx.gated else None              # slope >= 0: the score has the sign of the sum, it is its own gate
+        ge = ge.contiguous()
+        gs = fctx.plan._edge_sum(ge, gate, fctx.slope, False) if fctx.needs_input_grad[0] else None
+        gt = fctx.plan._edge_sum(ge, gate, fctx.slope, True) if fctx.needs_input_grad[1] else None
+        return gs, gt, None, None, None
+
+
+class _EdgeSum(torch.autograd.Function):
+    @staticmethod
+    def forward(fctx, w, plan, transposed):
+        fctx.plan, fctx.transposed = plan, transposed
+        return plan._edge_sum(w.detach().contiguous(), None, 1.0, transposed)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, g):
+        # the broadcast of g onto the entries: the score with one term absent and slope 1
+        H = int(g.shape[1])
+        return (fctx.plan._edge_add(None, g, H, 1.0) if fctx.transposed else fctx.plan._edge_add(g, None, H, 1.0)), None, None
+
+
+def u_add_v(plan, s, t, negative_slope=None):
+    """e[p] = act(s[row(p)] + t[adj[p]]) for every stored entry p of the plan, in CSR order: the additive score of the original GAT.  s is (n_rows,)
+    and t (n_cols,), float32 on the plan's device -> (E,); or s is n_rows x H and t n_cols x H -> E x H, every head in one walk.  act is LeakyReLU
+    with negative_slope (z > 0 ? z : negative_slope * z, one float32 product after one float32 addition; 0 is ReLU); None is the identity.  The
+    result equals the float32 formula bit for bit.  Differentiable in s and t, first order: grad s[i] = the sum over the entries of row i of the
+    gated entry gradient, grad t[u] the same sum over the entries with adj[p] = u in ascending p (the saved score is the gate), both without atomics:
+    the same bits on every run.  Column slices and offset views go with their leading dimension.  One call at a time per context."""
+    _edge_plan("u_add_v", plan)
+    slope, gated = _gat_slope("u_add_v", negative_slope)
+    s2, s_flat = _gat_term("u_add_v", "s", plan, s, plan.n_rows, "n_rows")
+    t2, t_flat = _gat_term("u_add_v", "t", plan, t, plan.n_cols, "n_cols")
+    if s_flat != t_flat or int(s2.shape[1]) != int(t2.shape[1]):
+        raise _l.VglHipError("u_add_v: s and t must both be one-dimensional or have the same number of heads, got %s and %s" % (tuple(s.shape), tuple(t.shape)))
+    e = _UAddV.apply(s2, t2, plan, slope, gated)
+    return e.squeeze(1) if s_flat else e
+
+
+def edge_sum(plan, w, transposed=False):
+    """out[i] = the sum of w[p] over the entries p of row i of the plan (w: (E,) or E x H float32 -> (n_rows,) or n_rows x H); with transposed=True
+    out[u] = the sum over the entries with adj[p] = u, in ascending p -> (n_cols,) or n_cols x H.  An empty row or column gives 0.  No atomics: the
+    same bits on every run.  Differentiable, first order: the gradient of w[p] is grad_out[row(p)], or grad_out[adj[p]] when transposed."""
+    _edge_plan("edge_sum", plan)
+    if not isinstance(transposed, (bool, int)) or transposed not in (0, 1):
+        raise _l.VglHipError("edge_sum: transposed must be True or False, got %r" % (transposed,))
+    if _edge_scalars_heads("edge_sum", "w", plan, w) is None:
+        return _EdgeSum.apply(w.unsqueeze(1), plan, bool(transposed)).squeeze(1)
+    return _EdgeSum.apply(w, plan, bool(transposed))
+
+
+def gat_attention(plan, s, t, v, negative_slope=0.2, return_weights=False):
+    """out[i, :] = the sum over the entries p of row i of softmax_row(leaky_relu(s[i] + t[adj[p]]))[p] * v[adj[p], :]: the attention of the original
+    GAT layer, given the two projections of the features on the attention vector (s: n_rows x H, t: n_cols x H, v: n_cols x Fv with Fv divisible by
+    H; head h of out in the columns [h Fv / H, (h + 1) Fv / H)).  It IS spmm(plan, edge_softmax(plan, u_add_v(plan, s, t, negative_slope)), v) and
+    nothing else, so it is differentiable in s, t and v.  The heads are s.shape[1]; one-dimensional s and t are one head with (E,) weights, n x 1 one
+    head with E x 1 weights as graph_attention(heads=1) has them.  With return_weights=True also the attention weights."""
+    _edge_plan("gat_attention", plan)
+    _edge_features("gat_attention", "v", plan, v, plan.n_cols, "n_cols")
+    e = u_add_v(plan, s, t, negative_slope)
+    H = int(e.shape[1]) if e.dim() == 2 else 1
+    if H < 1 or int(v.shape[1]) % H != 0:
+        raise _l.VglHipError("gat_attention: the width %d of v must be divisible by the heads of s and t (%d)" % (int(v.shape[1]), H))
+    w = _edge_softmax_any(plan, e)
     out = spmm(plan, w, v)
     return (out, w) if return_weights else out

@@ -402,6 +402,9 @@ int agg_build_lists(vgl_hip_ctx *c, const char *slot, const int64_t *rowptr, int
     return 0;
 }
 
+}  // namespace
+
+// (declared in vgl_agg.h: edge.hip's transposed entry sum builds the transpose on first use as the transposed runs below do)
 int agg_build_transpose(vgl_hip_ctx *c, vgl_hip_agg_plan *p)
 {
     hipStream_t st = c->stream;
@@ -436,6 +439,8 @@ int agg_build_transpose(vgl_hip_ctx *c, vgl_hip_agg_plan *p)
     p->has_tr = true;
     return 0;
 }
+
+namespace {
 
 template <int OP, int VEC, bool TR, bool HEADS = false>
 int agg_pass(vgl_hip_ctx *c, const vgl_agg_lists &L, const agg_args &a)

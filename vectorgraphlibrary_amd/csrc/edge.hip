@@ -14,6 +14,9 @@
 //   heads    the same three calls on H scalars per entry, e[p * H + h], head h on the columns [h D, (h + 1) D): separate kernels
 //            (vgl_k_edge_dot_heads, vgl_k_edge_rows_heads, ...) further down, so that the single-head instantiations stay as they were; each head
 //            has the bits of the single-head call on its column slice.
+//   gat      the additive score e[p, h] = leaky_relu(s[row(p), h] + t[adj[p], h]) on the same E x H layout, and the sums of (gated) entry scalars
+//            over the rows or, through the transpose, over the columns, which are its gradients: vgl_k_edge_add_heads,
+//            vgl_k_edge_sum_heads, vgl_k_edge_sum_hubs at the end of the kernels.
 // Every value has one writer and every sum a shape fixed by (row length, F, VEC, the three switches): no floating-point atomic, no scratch memory, no
 // cooperative launch, no wait on a flag, no retry loop.
 #include "vgl_agg.h"
@@ -647,6 +650,248 @@ int edge_rows_heads_run(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_x, c
     return 0;
 }
 
+// ---- the additive score of GAT and the entry sums that are its gradients ----
+// e[p, h] = act(s[row(p), h] + t[adj[p], h]), act(z) = z > 0 ? z : slope * z.  Every lane is an entry slot that carries a block of HB heads, four
+// entries in flight; adj[p] is read once per entry and kept across the blocks, the row's s block stays in registers where one block covers H and is
+// re-read per (four entries, block) from cache otherwise (the address is the team's).  A NULL s or t is ABSENT: no addition is made, so the other
+// term passes with its bits (a -0 stays -0).  No fold, no LDS, no hub stage: a chunk is an item like any other.
+struct edge_add_args {
+    const int64_t *rowptr;
+    const int32_t *adj;
+    const float *s, *t;          // n_rows x H (lds), n_cols x H (ldt); one of them may be NULL
+    float *e;                    // E x H
+    int64_t lds, ldt;
+    int32_t H, chunk;
+    float slope;
+    int32_t wide_s, wide_t, wide_e;      // a lane's block of heads goes as 8- or 16-byte accesses
+};
+
+template <int HB>
+__device__ __forceinline__ void edge_add_act(const edge_add_args &a, const float *sv, const float *x, float *r)
+{
+#pragma unroll
+    for (int k = 0; k < HB; k++) {
+        const float z = a.s ? (a.t ? sv[k] + x[k] : sv[k]) : x[k];
+        r[k] = z > 0.0f ? z : a.slope * z;
+    }
+}
+
+template <int CLS, int HB>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_add_heads(agg_list l, int32_t n, edge_add_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    const bool ws = a.wide_s != 0, wt = a.wide_t != 0, we = a.wide_e != 0, single = a.H == HB;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        int32_t v = 0;
+        int64_t lo = 0, hi = 0;
+        if (i < n) {
+            v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const float *srow = a.s ? a.s + (int64_t)v * a.lds : nullptr;
+        float sv[HB];
+#pragma unroll
+        for (int k = 0; k < HB; k++) sv[k] = 0.0f;
+        if (single && srow && lo < hi) edge_load_heads<HB>(srow, ws, sv);
+        int64_t p = lo + T::lane();
+        for (; p + 3 * (int64_t)T::LANES < hi; p += 4 * (int64_t)T::LANES) {          // four entries in flight
+            int32_t u[4] = {0, 0, 0, 0};
+            if (a.t)
+#pragma unroll
+                for (int j = 0; j < 4; j++) u[j] = a.adj[p + j * (int64_t)T::LANES];
+            for (int h0 = 0; h0 < a.H; h0 += HB) {
+                if (!single && srow) edge_load_heads<HB>(srow + h0, ws, sv);
+                float x[4][HB];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+#pragma unroll
+                    for (int k = 0; k < HB; k++) x[j][k] = 0.0f;
+                    if (a.t) edge_load_heads<HB>(a.t + (int64_t)u[j] * a.ldt + h0, wt, x[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    float r[HB];
+                    edge_add_act<HB>(a, sv, x[j], r);
+                    edge_store_heads<HB>(a.e + (p + j * (int64_t)T::LANES) * a.H + h0, we, r);
+                }
+            }
+        }
+        for (; p < hi; p += T::LANES) {
+            const int32_t u = a.t ? a.adj[p] : 0;
+            for (int h0 = 0; h0 < a.H; h0 += HB) {
+                if (!single && srow) edge_load_heads<HB>(srow + h0, ws, sv);
+                float x[HB], r[HB];
+#pragma unroll
+                for (int k = 0; k < HB; k++) x[k] = 0.0f;
+                if (a.t) edge_load_heads<HB>(a.t + (int64_t)u * a.ldt + h0, wt, x);
+                edge_add_act<HB>(a, sv, x, r);
+                edge_store_heads<HB>(a.e + p * a.H + h0, we, r);
+            }
+        }
+    }
+}
+
+// out[i, h] = the sum over the entries p of row i of c(p, h), c = w[p, h], or slope * w[p, h] where GATE and gate[p, h] <= 0 (the derivative of the
+// activation above, torch's: 1 for gate > 0, slope otherwise).  The walk and the fold of vgl_k_edge_rows_heads's backward sum; with TR over the
+// transpose, w and gate read through the origin.  A row of one chunk is written by its team's lead lane, a chunk of a longer row leaves one float
+// per (item, head) and vgl_k_edge_sum_hubs, a thread per (hub row, head), adds them in chunk order and writes the value.
+struct edge_sum_args {
+    const int64_t *rowptr;       // of the CSR walked
+    const int32_t *origin;       // TR: the position p of each entry of the transpose
+    const float *w, *gate;       // E x H
+    float *out;                  // rows x H (ldo)
+    float *part;                 // per (workgroup item, head)
+    int64_t ldo;
+    int32_t chunk, H;
+    float slope;
+    int32_t wide;                // w and gate are 16-byte aligned
+};
+
+template <bool GATE, int HB>
+__device__ __forceinline__ void edge_sum_term(const edge_sum_args &a, int64_t o, int h0, bool wide, float *c)
+{
+    edge_load_heads<HB>(a.w + o * a.H + h0, wide, c);
+    if constexpr (GATE) {
+        float g[HB];
+        edge_load_heads<HB>(a.gate + o * a.H + h0, wide, g);
+#pragma unroll
+        for (int k = 0; k < HB; k++) c[k] = g[k] > 0.0f ? c[k] : a.slope * c[k];
+    }
+}
+
+template <int CLS, bool GATE, bool TR, int HB>
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_sum_heads(agg_list l, int32_t n, edge_sum_args a)
+{
+    using T = vgl_rc_team<CLS>;
+    const bool wide = a.wide != 0;
+    for (int64_t at = T::begin(); at < n; at += T::stride()) {
+        const int64_t i = T::item(at);
+        const bool has = i < n;
+        int32_t v = 0;
+        int64_t lo = 0, hi = 0;
+        bool whole = true;
+        if (has) {
+            v = l.rows[i];
+            lo = a.rowptr[v]; hi = a.rowptr[v + 1];
+            if constexpr (CLS == VGL_RC_WG) {
+                const int64_t end = hi;
+                whole = hi - lo <= a.chunk;
+                lo += (int64_t)l.chunk[i] * a.chunk;
+                hi = min(end, lo + a.chunk);
+            }
+        }
+        const int64_t first = lo + T::lane();
+        for (int h0 = 0; h0 < a.H; h0 += HB) {                         // the blocks of heads: the same trips in every lane
+            float acc[HB];
+#pragma unroll
+            for (int k = 0; k < HB; k++) acc[k] = 0.0f;
+            int64_t p = first;
+            for (; p + 3 * (int64_t)T::LANES < hi; p += 4 * (int64_t)T::LANES) {      // four entries in flight, added in entry order
+                int64_t o[4];
+                float c[4][HB];
+#pragma unroll
+                for (int j = 0; j < 4; j++) o[j] = TR ? (int64_t)a.origin[p + j * (int64_t)T::LANES] : p + j * (int64_t)T::LANES;
+#pragma unroll
+                for (int j = 0; j < 4; j++) edge_sum_term<GATE, HB>(a, o[j], h0, wide, c[j]);
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+#pragma unroll
+                    for (int k = 0; k < HB; k++) acc[k] = acc[k] + c[j][k];
+            }
+            for (; p < hi; p += T::LANES) {
+                float c[HB];
+                edge_sum_term<GATE, HB>(a, TR ? (int64_t)a.origin[p] : p, h0, wide, c);
+#pragma unroll
+                for (int k = 0; k < HB; k++) acc[k] = acc[k] + c[k];
+            }
+            edge_team_sum_heads<CLS, HB>(acc);
+            if (T::lead() && has) {
+                float *to = CLS == VGL_RC_WG && !whole ? a.part + i * a.H + h0 : a.out + (int64_t)v * a.ldo + h0;
+#pragma unroll
+                for (int k = 0; k < HB; k++) to[k] = acc[k];
+            }
+        }
+    }
+}
+
+struct edge_sum_hubs { const int32_t *row, *first, *nch; int32_t n; };
+__global__ __launch_bounds__(VGL_BLOCK) void vgl_k_edge_sum_hubs(edge_sum_hubs h, int32_t H, const float *part, float *out, int64_t ldo)
+{
+    const int64_t total = (int64_t)h.n * H;
+    for (int64_t t = (int64_t)blockIdx.x * VGL_BLOCK + threadIdx.x; t < total; t += (int64_t)gridDim.x * VGL_BLOCK) {
+        const int32_t k = (int32_t)(t / H);
+        const int64_t hd = t - (int64_t)k * H;
+        const float *mine = part + (int64_t)h.first[k] * H + hd;
+        const int32_t nch = h.nch[k];
+        float s = mine[0];
+        for (int32_t j = 1; j < nch; j++) s = s + mine[(int64_t)j * H];
+        out[(int64_t)h.row[k] * ldo + hd] = s;
+    }
+}
+
+template <int HB>
+int edge_add_launch(vgl_hip_ctx *c, const vgl_agg_lists &L, const edge_add_args &a)
+{
+    const char *const slot[VGL_RC_N] = {"edge_add_short", "edge_add_wave", "edge_add_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    return vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_add_heads<VGL_RC_SHORT, HB>, vgl_k_edge_add_heads<VGL_RC_WAVE, HB>, vgl_k_edge_add_heads<VGL_RC_WG, HB>, list, a);
+}
+
+template <bool GATE, bool TR, int HB>
+int edge_sum_launch(vgl_hip_ctx *c, const vgl_agg_lists &L, const edge_sum_args &a)
+{
+    const char *const slot[VGL_RC_N] = {"edge_sum_short", "edge_sum_wave", "edge_sum_wg"};
+    const agg_list list[VGL_RC_N] = {{L.rows.p, nullptr}, {L.rows.p + L.n[0], nullptr}, {L.item_row.p, L.item_chunk.p}};
+    VGL_TRY(vgl_rc_launch_trio(c, slot, L.n, agg_grid_cap, vgl_k_edge_sum_heads<VGL_RC_SHORT, GATE, TR, HB>, vgl_k_edge_sum_heads<VGL_RC_WAVE, GATE, TR, HB>,
+                               vgl_k_edge_sum_heads<VGL_RC_WG, GATE, TR, HB>, list, a));
+    if (L.nhubs > 0) {
+        const edge_sum_hubs hubs{L.hub_row.p, L.hub_first.p, L.hub_nch.p, (int32_t)L.nhubs};
+        vgl_timed_launch tl(c, "edge_sum_hubs");
+        hipLaunchKernelGGL(vgl_k_edge_sum_hubs, dim3(vgl_grid(L.nhubs * a.H, VGL_BLOCK, AGG_MAX_GRID)), dim3(VGL_BLOCK), 0, c->stream, hubs, a.H, (const float *)a.part, a.out, a.ldo);
+    }
+    return 0;
+}
+
+template <bool GATE, bool TR>
+int edge_sum_pick(vgl_hip_ctx *c, const vgl_agg_lists &L, const edge_sum_args &a)
+{
+    const int hb = edge_head_block(a.H);
+    if (hb == 8) return edge_sum_launch<GATE, TR, 8>(c, L, a);
+    if (hb == 4) return edge_sum_launch<GATE, TR, 4>(c, L, a);
+    if (hb == 2) return edge_sum_launch<GATE, TR, 2>(c, L, a);
+    return edge_sum_launch<GATE, TR, 1>(c, L, a);
+}
+
+// the stats of a walk over L (the plan's lists or the transpose's, `rows` rows): `per_entry` bytes per entry, `per_row` per row beside the list entries
+void edge_walk_stats(const vgl_agg_lists &L, int64_t rows, int transposed, int vec, int64_t per_entry, int64_t per_row, int32_t heads, vgl_hip_agg_stats *stats)
+{
+    vgl_hip_agg_stats s;
+    memset(&s, 0, sizeof(s));
+    s.rows = rows; s.entries = L.entries;
+    s.rows_short = L.rows_of[0]; s.rows_wave = L.rows_of[1]; s.rows_wg = L.rows_of[2];
+    s.chunks = L.n[VGL_RC_WG]; s.hub_rows = L.nhubs;
+    s.transposed = transposed; s.vec = vec; s.heads = heads;
+    for (int q = 0; q < VGL_RC_N; q++) s.column_tiles[q] = 1;
+    s.algorithmic_bytes = L.entries * per_entry + rows * per_row + 4 * (L.rows_of[0] + L.rows_of[1]) + 8 * L.n[VGL_RC_WG];
+    *stats = s;
+}
+
+// [a, a + na) and [b, b + nb) in bytes share a byte
+bool edge_overlap(const void *a, int64_t na, const void *b, int64_t nb)
+{
+    if (!a || !b || na <= 0 || nb <= 0) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+// the bytes from the first to the last element of a rows x H matrix of leading dimension ld
+int64_t edge_span(int64_t rows, int64_t ld, int32_t H) { return rows > 0 ? 4 * ((rows - 1) * ld + H) : 0; }
+
 }  // namespace
 
 extern "C" {
@@ -743,6 +988,84 @@ int vgl_hip_agg_edge_softmax_backward(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const
 {
     VGL_TRY(edge_check_call("agg_edge_softmax_backward", c, p, d_y, d_gy, d_ge));
     return edge_rows_run<true>(c, p, d_y, d_gy, d_ge, stats);
+}
+
+int vgl_hip_agg_edge_add_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_s, int64_t lds, const float *d_t, int64_t ldt, int32_t H, float slope, float *d_e,
+                               vgl_hip_agg_stats *stats)
+{
+    // every refusal comes before the first write to an output
+    if (!c || !p || !d_e) VGL_FAIL("agg_edge_add_heads: null argument");
+    if (!d_s && !d_t) VGL_FAIL("agg_edge_add_heads: d_s and d_t must not both be NULL");
+    if (p->c != c) VGL_FAIL("agg_edge_add_heads: the plan belongs to another context");
+    if (H < 1) VGL_FAIL("agg_edge_add_heads: H must be at least 1");
+    if ((d_s && lds < H) || (d_t && ldt < H)) VGL_FAIL("agg_edge_add_heads: a leading dimension must not be below H");
+    if (!(slope >= 0.0f) || std::isinf(slope)) VGL_FAIL("agg_edge_add_heads: slope must be finite and not negative");
+    const vgl_agg_lists &L = p->fwd;
+    const int64_t e_bytes = 4 * L.entries * (int64_t)H;
+    if (edge_overlap(d_e, e_bytes, d_s, edge_span(p->n_rows, lds, H)) || edge_overlap(d_e, e_bytes, d_t, edge_span(p->n_cols, ldt, H)))
+        VGL_FAIL("agg_edge_add_heads: d_e must not overlap d_s or d_t");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    edge_add_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = p->rowptr; a.adj = p->adj;
+    a.s = d_s; a.lds = lds; a.t = d_t; a.ldt = ldt; a.e = d_e;
+    a.H = H; a.chunk = L.ch.chunk; a.slope = slope;
+    const int hb = edge_head_block(H), piece = hb >= 4 ? 4 : 2;      // a block goes in pieces of 16 bytes, a block of two heads in one of 8
+    a.wide_s = d_s && agg_aligned16(d_s) && lds % piece == 0 ? 1 : 0;
+    a.wide_t = d_t && agg_aligned16(d_t) && ldt % piece == 0 ? 1 : 0;
+    a.wide_e = agg_aligned16(d_e) ? 1 : 0;
+    if (hb == 8) VGL_TRY(edge_add_launch<8>(c, L, a));
+    else if (hb == 4) VGL_TRY(edge_add_launch<4>(c, L, a));
+    else if (hb == 2) VGL_TRY(edge_add_launch<2>(c, L, a));
+    else VGL_TRY(edge_add_launch<1>(c, L, a));
+    VGL_HIP_TRY(hipStreamSynchronize(c->stream));                     // (the result is there when the call returns)
+    if (stats) {
+        const bool wide = a.wide_e && (!d_s || a.wide_s) && (!d_t || a.wide_t);
+        // per entry: the adjacency, 4 H of t gathered, 4 H of e written; per row: the bounds and 4 H of s
+        edge_walk_stats(L, p->n_rows, 0, wide && hb >= 4 ? 4 : 1, 4 + (d_t ? 4 * (int64_t)H : 0) + 4 * (int64_t)H, 8 + (d_s ? 4 * (int64_t)H : 0), H, stats);
+    }
+    return 0;
+}
+
+int vgl_hip_agg_edge_sum_heads(vgl_hip_ctx *c, vgl_hip_agg_plan *p, const float *d_w, const float *d_gate, float slope, int32_t H, int transposed, float *d_out, int64_t ldo,
+                               vgl_hip_agg_stats *stats)
+{
+    // every refusal comes before the first write to an output
+    if (!c || !p || !d_w || !d_out) VGL_FAIL("agg_edge_sum_heads: null argument");
+    if (p->c != c) VGL_FAIL("agg_edge_sum_heads: the plan belongs to another context");
+    if (H < 1) VGL_FAIL("agg_edge_sum_heads: H must be at least 1");
+    if (ldo < H) VGL_FAIL("agg_edge_sum_heads: a leading dimension must not be below H");
+    if (!(slope >= 0.0f) || std::isinf(slope)) VGL_FAIL("agg_edge_sum_heads: slope must be finite and not negative");
+    if (transposed != 0 && transposed != 1) VGL_FAIL("agg_edge_sum_heads: transposed must be 0 or 1");
+    const int64_t rows = transposed ? p->n_cols : p->n_rows, e_bytes = 4 * p->E * (int64_t)H, out_bytes = edge_span(rows, ldo, H);
+    if (edge_overlap(d_out, out_bytes, d_w, e_bytes) || edge_overlap(d_out, out_bytes, d_gate, e_bytes)) VGL_FAIL("agg_edge_sum_heads: d_out must not overlap d_w or d_gate");
+    VGL_HIP_TRY(hipSetDevice(c->device));
+    if (transposed && !p->has_tr) VGL_TRY(agg_build_transpose(c, p));
+    hipStream_t st = c->stream;
+    const vgl_agg_lists &L = transposed ? p->tr : p->fwd;
+    edge_sum_args a;
+    memset(&a, 0, sizeof(a));
+    a.rowptr = transposed ? p->t_rowptr.p : p->rowptr;
+    a.origin = transposed ? p->t_origin.p : nullptr;
+    a.w = d_w; a.gate = d_gate; a.out = d_out; a.ldo = ldo;
+    a.chunk = L.ch.chunk; a.H = H; a.slope = slope;
+    a.wide = agg_aligned16(d_w) && (!d_gate || agg_aligned16(d_gate)) ? 1 : 0;
+    vgl_dev<float> part;
+    if (L.nhubs > 0) VGL_TRY(part.alloc(st, (size_t)L.n[VGL_RC_WG] * (size_t)H));
+    a.part = part.p;
+    if (d_gate) {
+        if (transposed) VGL_TRY((edge_sum_pick<true, true>(c, L, a)));
+        else VGL_TRY((edge_sum_pick<true, false>(c, L, a)));
+    } else {
+        if (transposed) VGL_TRY((edge_sum_pick<false, true>(c, L, a)));
+        else VGL_TRY((edge_sum_pick<false, false>(c, L, a)));
+    }
+    VGL_HIP_TRY(hipGetLastError());
+    VGL_HIP_TRY(hipStreamSynchronize(st));                            // (the partials are free again; the result is there when the call returns)
+    // per entry: 4 H of w, 4 H of the gate, the origin of a transposed entry; per row: the bounds and 4 H written
+    if (stats)
+        edge_walk_stats(L, rows, transposed, a.wide && edge_head_block(H) >= 4 ? 4 : 1, 4 * (int64_t)H * (d_gate ? 2 : 1) + (transposed ? 4 : 0), 8 + 4 * (int64_t)H, H, stats);
+    return 0;
 }
 
 }  // extern "C"

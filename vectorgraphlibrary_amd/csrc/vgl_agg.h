@@ -72,3 +72,6 @@ struct vgl_hip_agg_plan {
     vgl_dev<int64_t> t_rowptr;                       // the transpose: n_cols rows
     vgl_dev<int32_t> t_adj, t_origin;                // row(p) and p of its entries
 };
+
+// agg.hip: builds p->tr, t_rowptr, t_adj and t_origin (the caller has made the context's device current and checks p->has_tr first)
+int agg_build_transpose(vgl_hip_ctx *c, vgl_hip_agg_plan *p);

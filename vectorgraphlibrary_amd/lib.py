@@ -277,6 +277,8 @@ _SIGNATURES = {
     "vgl_hip_agg_edge_softmax_backward_heads": [_p, _p, _p, _p, _i32, _p, C.POINTER(AggStats)],
     "vgl_hip_agg_run_heads": [_p, _p, _int, _p, _i32, _p, _i64, _i32, _p, _i64, C.POINTER(AggStats)],
     "vgl_hip_agg_run_transposed_heads": [_p, _p, _int, _p, _i32, _p, _i64, _i32, _p, _i64, C.POINTER(AggStats)],
+    "vgl_hip_agg_edge_add_heads": [_p, _p, _p, _i64, _p, _i64, _i32, C.c_float, _p, C.POINTER(AggStats)],
+    "vgl_hip_agg_edge_sum_heads": [_p, _p, _p, _p, C.c_float, _i32, _int, _p, _i64, C.POINTER(AggStats)],
     "vgl_hip_bfs_init": [_p, _i32, _i32, _p],
     "vgl_hip_bfs_step_top_down": [_p, _p, _p, _i32, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "vgl_hip_bfs_step_top_down_bits": [_p, _p, _p, _i32, _p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
